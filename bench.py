@@ -18,8 +18,10 @@ per-rank step times, the RCCL world size seen by a device all-reduce, the time o
 T) and a `single_process` block: the same shards behind ONE handle of the C-ABI (mckpp_hip_multi_*), all N GPUs
 driven from rank 0's process while the other ranks wait.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with `roofline` and `cpu_baseline`,
-plus (N=1 only, never part of `value`):
+Prints ONE JSON line on rank 0 with `roofline` (from the timed steps' own kernel times).  A plain run does only what
+that line needs: set-up, spin-up, warmup and settle steps, the K timed steps, `--dump-outputs DIR` if given, the line.
+Everything else is measured with `--full` only: `cpu_baseline`, at N > 1 the diagnostics gather, `config3_strong` and
+`single_process`, and (N=1 only, never part of `value`):
   burst                the K steps as a cold device runs them (before the settle leg; `value` is measured after
                        SETTLE steps of the same work, i.e. at the clock a model run sees)
   sustained            400 more steps of the headline workload in one call
@@ -202,6 +204,32 @@ def time_steps(ctx, nt_first, nsteps, barrier):
     dt = time.perf_counter() - t0
     kms, nlaunch = ctx.last_kernel_ms()   # (nlaunch: the steps the call covered; step(nt, n) is one launch for all n)
     return dt, (kms / max(nlaunch, 1)) * 1e-3
+
+
+DUMP_BYTES = 64 * 10**6
+# what mckpp_hip_download (every field group) returns of the state a step leaves, without the inputs it passes through
+DUMP_FIELDS = ("U", "X", "Us", "Xs", "hmixd", "Ssurf", "Tref", "uref", "vref", "reset_flag", "dampu_flag", "dampv_flag",
+               "freeze_flag", "old", "new_", "rho", "cp", "buoy", "difm", "difs", "dift", "wU", "wX", "wXNT", "ghat", "Rig",
+               "Shsq", "dbloc", "swfrac", "swdk_opt")
+
+
+def dump_outputs(d, mk, ctx, k3, npass):
+    """The state after the last timed step as mckpp_physics_driver hands it back, in float64 under `d`: hmix, kmix and the
+    pass counts of every column, and every DUMP_FIELDS array on a fixed seeded sample of the columns (sample_columns.npy:
+    their indices), as many as fit in DUMP_BYTES in all."""
+    ctx.download(k3, mk.api.F_ALL)
+    ctx.synchronize()
+    n = k3.npts
+    whole = {"hmix": k3.hmix, "kmix": k3.kmix, "npasses": npass}
+    per_column = sum(getattr(k3, f)[0].size for f in DUMP_FIELDS) * 8 + 8
+    nsample = min(n, 2048, (DUMP_BYTES - 8 * n * len(whole)) // per_column)
+    if nsample < 1:
+        raise SystemExit(f"bench.py: {n} columns are too many for --dump-outputs ({DUMP_BYTES} bytes at most)")
+    cols = np.sort(np.random.default_rng(20261016).choice(n, size=nsample, replace=False))
+    arrays = dict(whole, sample_columns=cols, **{"sample_" + f: getattr(k3, f)[cols] for f in DUMP_FIELDS})
+    os.makedirs(d, exist_ok=True)
+    for name, v in arrays.items():
+        np.save(os.path.join(d, name + ".npy"), np.ascontiguousarray(v, dtype=np.float64))
 
 
 def side_shape(mk, cm, ncol, nz, grid, dto, land_frac, steps, warmup, diag, dev_index):
@@ -647,6 +675,12 @@ def main():
     ap.add_argument("--ncol", type=int, default=100000, help="columns per GPU")
     ap.add_argument("--nz", type=int, default=60)
     ap.add_argument("--diag", type=int, default=1, help="write the per-step diagnostic fields (reference behaviour)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: burst, the extra legs, cpu_baseline, and at N > 1 the "
+                         "diagnostics gather, config3_strong and single_process (--no-cpu-baseline, --no-extras, --legs, "
+                         "--sustained-steps and --cpu-* select among these)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="write the state after the last timed step to DIR/<name>.npy (float64, rank 0's columns)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-extras", action="store_true", help="headline only: skip diurnal / other_shapes / strong_scaling_proxy")
     ap.add_argument("--cpu-stride", type=int, default=1)
@@ -741,12 +775,15 @@ def main():
         ctx.step(1 + SPINUP, a.warmup)
     nt_next = 1 + SPINUP + a.warmup
     burst = None
-    if a.settle > 0:   # the K steps as a cold device runs them (reported, not `value`), then the settle leg
-        dtb, kern_b = time_steps(ctx, nt_next, a.steps, barrier)
+    if a.settle > 0:   # the K steps as a cold device runs them (reported with --full, not `value`), then the settle leg
+        if a.full:
+            dtb, kern_b = time_steps(ctx, nt_next, a.steps, barrier)
+            burst = {"value_this_rank": nocean * a.steps / dtb, "unit": "column-steps/s", "ms_per_step": dtb / a.steps * 1e3,
+                     "kernel_avg_ms": kern_b * 1e3,
+                     "what": f"the same {a.steps} steps right after the {a.warmup} warmup steps, device cold (this rank's columns)"}
+        else:   # the same steps untimed: both kinds of run time the same model steps from the same state
+            ctx.step(nt_next, a.steps)
         nt_next += a.steps
-        burst = {"value_this_rank": nocean * a.steps / dtb, "unit": "column-steps/s", "ms_per_step": dtb / a.steps * 1e3,
-                 "kernel_avg_ms": kern_b * 1e3,
-                 "what": f"the same {a.steps} steps right after the {a.warmup} warmup steps, device cold (this rank's columns)"}
         ctx.step(nt_next, a.settle)
         ctx.synchronize()
         nt_next += a.settle
@@ -754,6 +791,8 @@ def main():
     nt_next += a.steps
 
     st, nflag, npass = ctx.status()
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, mk, ctx, k3, npass)
     ocean = k3.run_physics != 0
     ncols_all = nocean
     multi = None
@@ -776,6 +815,8 @@ def main():
             "backend": dist.get_backend(), "rccl_ranks": int(round(float(ones.item()))) if backend == "nccl" else None,
             "collective_ranks": int(round(float(ones.item()))), "world_size": dist.get_world_size(),
         }
+
+    if dist is not None and a.full:
         # diagnostics gather (not timed into `value`): hmix and T of every rank's columns to rank 0.  The line does not
         # depend on it - but every rank must take the same way through it: a rank whose download fails must not leave
         # the others inside a gather (sharding.guarded_block: the ranks agree on failures before and after the
@@ -884,14 +925,14 @@ def main():
             # the diagnostics alone do not)
             out["ok"] = not (isinstance(multi.get("gather"), dict) and multi["gather"].get("complete_and_finite") is False)
 
-    if dist is not None:   # the same shards behind one handle, from rank 0's process; the other ranks wait
+    if dist is not None and a.full:   # the same shards behind one handle, from rank 0's process; the other ranks wait
         barrier()
         if rank == 0:
             devs = [0] * world if os.environ.get("MCKPP_BENCH_SHARE_GPU") else list(range(world))
             out["multi_gpu"]["single_process"] = run_single_process_leg(a, devs)
         barrier()
 
-    extras = world == 1 and not a.no_extras
+    extras = a.full and world == 1 and not a.no_extras
     if extras and a.legs != "all":   # experiments: only the named legs of the second block below
         ctx.close()
         del ctx, k3, kc
@@ -1004,13 +1045,13 @@ def main():
         del ctx, k3, kc
         gc.collect()
     if rank == 0:
-        if world > 1 and not a.no_cpu_baseline:
+        if a.full and world > 1 and not a.no_cpu_baseline:
             # rank 0's host cores, every 4th of rank 0's columns (bounded: the line must come within the driver's limit
             # at every N), no diurnal leg
             cb = cpu_baseline(ncol, nz, a.warmup, a.cpu_steps, max(a.cpu_stride, 4), 4, 0, a.dto, with_diurnal=False)
             cb["note"] = "timed on rank 0's host while the other ranks wait; a sample of rank 0's shard of the workload"
             out["cpu_baseline"] = cb
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             cb = cpu_baseline(ncol, nz, a.warmup, a.cpu_steps, a.cpu_stride, 4, SPINUP + a.warmup + a.steps, a.dto)
             if extras:
                 cb["diurnal"]["note"] = ("the CPU leg runs the diurnal steps right after the headline's; the GPU leg after its "

@@ -2,10 +2,13 @@
 """Golden vector of the round-5 part of the compiler-convention probe: what amdflang (-fdefault-real-8 -O2, the
 flags of oracle/Makefile) returns for EXP, SQRT, ABS, x**2, the Jerlov transmission forms of swfrac / swdk,
 SIGN, MAX / MIN / AMAX1 / AMIN1 with two to four arguments (equal and signed-zero operands included) and
-ifix / int / float (oracle/conv_probe.F90 - our own source, no reference code).  Run in the build container:
+ifix / int / float (oracle/conv_probe.F90 - our own source, no reference code).  Run where amdflang is installed:
     python tests/golden/make_conv_golden2.py
+The file holds the inputs and a SHA-256 digest of each of amdflang's output arrays (the outputs themselves would take
+2.5 MB): a bit-for-bit comparison with them is a comparison of digests.
 """
 import ctypes as C
+import hashlib
 import os
 import sys
 
@@ -55,6 +58,12 @@ def inputs(seed=20261005, n=12000):
                                    48.0, 48.999999999, 49.0])])
     return {"x": np.ascontiguousarray(x), "a": np.ascontiguousarray(a), "b": np.ascontiguousarray(b),
             "c": np.ascontiguousarray(c), "d": np.ascontiguousarray(d), "xc": np.ascontiguousarray(xc), "z": zs}
+
+
+def digest(a):
+    """SHA-256 of an array's dtype, shape and bytes: equal digests <=> bit-identical arrays."""
+    a = np.ascontiguousarray(a)
+    return hashlib.sha256(f"{a.dtype.str}{a.shape}".encode() + a.tobytes()).hexdigest()
 
 
 def run_probe(P, inp):
@@ -122,7 +131,7 @@ def main():
     inp = inputs()
     got = run_probe(P, inp)
     np.savez_compressed(os.path.join(HERE, "conv_probe_intrinsics.npz"), **{"in_" + k: v for k, v in inp.items()},
-                        **{"out_" + k: v for k, v in got.items()})
+                        **{"sha256_" + k: np.array(digest(v)) for k, v in got.items()})
     print("wrote conv_probe_intrinsics.npz:", {k: len(v) for k, v in inp.items()})
 
 

@@ -79,7 +79,8 @@ def test_bench_starts_its_own_ranks_without_touching_the_gpu():
     """`python bench.py --gpus N` with no launcher around it becomes the launcher: N ranks under
     torch.distributed.run on 127.0.0.1, started before this process imports torch or loads the library (a process
     that has initialised the GPU must not start the ranks).  Without a GPU the ranks refuse to run and the exit
-    code comes back."""
+    code comes back; the devices are hidden from the launch (HIP_VISIBLE_DEVICES=-1), so that this holds on a machine
+    with GPUs as well."""
     import json
     import subprocess
 
@@ -93,9 +94,9 @@ def test_bench_starts_its_own_ranks_without_touching_the_gpu():
     cmd = plan["cmd"]
     assert cmd[1:3] == ["-m", "torch.distributed.run"] and "--nproc-per-node=2" in cmd and "--nnodes=1" in cmd
     assert "--standalone" in cmd and cmd[cmd.index("--local-addr") + 1] == "127.0.0.1" and cmd[-4:] == ["--gpus", "2", "--steps", "3"]
-    # a real launch here (no GPU): both ranks say so, the parent hands the failure on
+    # a real launch with no GPU visible: both ranks say so, the parent hands the failure on
     r = subprocess.run([sys.executable, bench, "--gpus", "2", "--steps", "2", "--no-cpu-baseline"], capture_output=True,
-                       text=True, env=env, timeout=300)
+                       text=True, env=dict(env, HIP_VISIBLE_DEVICES="-1"), timeout=300)
     assert r.returncode != 0
     assert "MI355X" in r.stderr and '"metric"' not in r.stdout
 
@@ -184,7 +185,7 @@ def test_a_failure_on_one_rank_cannot_leave_the_others_inside_a_collective():
 
 
 def test_bench_has_the_config3_block_and_guards_it():
-    """The N>1 line carries BASELINE configs[3] itself (config3_strong: 1e5 x 100 dealt over the ranks, 200 steps in one
+    """The N>1 line of a --full run carries BASELINE configs[3] itself (config3_strong: 1e5 x 100 dealt over the ranks, 200 steps in one
     call past step 60) and the diagnostics gather, both through sharding.guarded_block, and a state gathered on rank 0
     that is incomplete or not finite fails the run ("ok": false, non-zero exit)."""
     src = open(os.path.join(cm.ROOT, "bench.py")).read()

@@ -2,6 +2,7 @@
 golden vectors produced by the compiled reference, and (when oracle/_ref is
 present) to the compiled reference itself on a million points."""
 import ctypes as C
+import json
 import os
 import sys
 
@@ -54,46 +55,49 @@ def test_z121_golden_bitexact():
         assert np.array_equal(w, wout[: km + 2])
 
 
-def _need_ref():
-    """oracle/_ref is built by __graft_entry__.build() where /root/reference is mounted; only a box
-    without the reference (the GPU box) may skip."""
-    if not os.path.exists(orc.REFLIB):
-        if os.path.isdir("/root/reference/src"):
-            import __graft_entry__ as g
-            g.build()
-        else:
-            pytest.skip("compiled reference (oracle/_ref) not available: /root/reference is not mounted here")
-    assert os.path.exists(orc.REFLIB)
+def _golden_module():
+    sys.path.insert(0, GOLD)
+    import make_golden as mg
+    return mg
+
+
+def _ref_checks():
+    """What the compiled reference returned for the two tests below (tests/golden/eos_ref_checks.json, written by
+    tests/golden/make_golden.py), and the compiled reference itself where __graft_entry__.build() made oracle/_ref."""
+    with open(os.path.join(GOLD, "eos_ref_checks.json")) as f:
+        checks = json.load(f)
+    return checks, (orc.ref() if os.path.exists(orc.REFLIB) else None)
 
 
 def test_eos_vs_compiled_reference_1e6(built):
-    _need_ref()
-    L, R = orc.lib(), orc.ref()
-    rng = np.random.default_rng(7)
-    n = 1_000_000
-    s, t, p = rng.uniform(0, 42, n), rng.uniform(-4, 35, n), rng.uniform(0.05, 6000, n)
-    o = [np.zeros(n) for _ in range(10)]
-    L.orc_abk80_batch(n, dp(s), dp(t), dp(p), *[dp(x) for x in o[:4]])
-    R.ref_abk80_batch(n, dp(s), dp(t), dp(p), *[dp(x) for x in o[4:8]])
-    L.orc_cpsw_batch(n, dp(s), dp(t), dp(p), dp(o[8]))
-    R.ref_cpsw_batch(n, dp(s), dp(t), dp(p), dp(o[9]))
-    for i in range(4):
-        assert np.array_equal(o[i].view(np.int64), o[4 + i].view(np.int64))
-    assert np.array_equal(o[8].view(np.int64), o[9].view(np.int64))
+    mg = _golden_module()
+    checks, R = _ref_checks()
+    L = orc.lib()
+    pts = mg.eos_points_1e6()
+    assert mg.digest(np.stack(pts)) == checks["eos_1e6"]["inputs_sha256"], "the seeded 1e6 points are not the recorded ones"
+    o = mg.eos_batch(L, "orc", *pts)
+    for name in mg.EOS_NAMES:
+        assert mg.digest(o[name]) == checks["eos_1e6"]["sha256"][name], name
+    if R is not None:
+        r = mg.eos_batch(R, "ref", *pts)
+        for name in mg.EOS_NAMES:
+            assert np.array_equal(o[name].view(np.int64), r[name].view(np.int64)), name
 
 
 def test_abk80_flag_paths_vs_compiled_reference(built):
     """P = 0 short-cuts and the kappa-only / alpha-only entry paths of mckpp_abk80."""
-    _need_ref()
-    L, R = orc.lib(), orc.ref()
-    for S, T, P in ((35.0, 10.0, 0.0), (0.0, 4.0, 0.0), (35.0, 10.0, 500.0), (20.0, -5.0, 50.0)):
-        for a0, b0, k0 in ((1, 1, 1), (1, 0, 0), (0, 1, 0), (0, 0, 1), (1, 0, 1), (0, 0, 0)):
-            res = []
-            for fn in (L.orc_abk80, R.ref_abk80):
-                a, b, k, s0, s = (C.c_double(v) for v in (a0, b0, k0, 9.0, 9.0))
-                fn(S, T, P, C.byref(a), C.byref(b), C.byref(k), C.byref(s0), C.byref(s))
-                res.append((a.value, b.value, k.value, s0.value, s.value))
-            assert res[0] == res[1], (S, T, P, a0, b0, k0, res)
+    mg = _golden_module()
+    checks, R = _ref_checks()
+    L = orc.lib()
+    mine = mg.abk80_paths(L.orc_abk80)
+    refs = [[[float.fromhex(v) for v in r] for r in checks["abk80_paths"]]]
+    if R is not None:
+        refs.append(mg.abk80_paths(R.ref_abk80))
+    entries = [(S, T, P, a0, b0, k0) for S, T, P in mg.ABK80_POINTS for a0, b0, k0 in mg.ABK80_FLAGS]
+    for ref in refs:
+        assert len(ref) == len(entries)
+        for e, got, want in zip(entries, mine, ref):
+            assert tuple(got) == tuple(want), (e, got, want)
 
 
 def test_portable_exp_accuracy():
@@ -389,19 +393,23 @@ def test_compiler_conventions_intrinsics_golden():
     SIGN(a, b) incl. SIGN(0.5, +-0.0) and SIGN(0.5, x + epsln) near zero (bldepth_mod.F90:123,196,201), MAX / MIN /
     AMAX1 / AMIN1 with 2-4 arguments incl. equal and signed-zero operands, ifix / int / float (blmix_mod.F90:68,
     wscale_mod.F90:65-77): what amdflang returned for them under the reference's flags
-    (tests/golden/conv_probe_intrinsics.npz, made by tests/golden/make_conv_golden2.py from oracle/conv_probe.F90)
-    against the oracle's lowering - exp(), sqrt(), fabs(), copysign, a > b ? a : b left to right, (int) - bit for bit.
-    exp_mode = 0 of the oracle is therefore amdflang's EXP, not an assumption about it."""
+    (tests/golden/conv_probe_intrinsics.npz, made by tests/golden/make_conv_golden2.py from oracle/conv_probe.F90: the
+    inputs and a SHA-256 digest of each output array) against the oracle's lowering - exp(), sqrt(), fabs(), copysign,
+    a > b ? a : b left to right, (int) - bit for bit.  exp_mode = 0 of the oracle is therefore amdflang's EXP, not an
+    assumption about it."""
     g2 = _conv2_module()
     z = np.load(os.path.join(GOLD, "conv_probe_intrinsics.npz"))
     inp = {k[3:]: np.ascontiguousarray(z[k]) for k in z.files if k.startswith("in_")}
-    want = {k[4:]: z[k] for k in z.files if k.startswith("out_")}
+    want = {k[7:]: str(z[k]) for k in z.files if k.startswith("sha256_")}
     assert (inp["x"] <= 0).sum() >= 10000 and len(inp["z"]) > 3000
-    _conv2_compare(want, g2.run_oracle(inp))
-    # what the probe says about the lowering itself
-    assert np.array_equal(want["sign_half"][np.signbit(inp["b"])], np.zeros(int(np.signbit(inp["b"]).sum())))   # SIGN(0.5, -0.0) = -0.5
-    assert np.array_equal(want["amax1"].view(np.int64), want["max"].view(np.int64))
-    assert np.array_equal(want["amin1"].view(np.int64), want["min"].view(np.int64))
+    got = g2.run_oracle(inp)
+    assert set(want) == set(got)
+    bad = sorted(name for name in want if g2.digest(got[name]) != want[name])
+    assert not bad, f"the oracle's C lowering differs from amdflang's bit for bit in {bad}"
+    # what the probe says about the lowering itself (`got` is amdflang's result, bit for bit)
+    assert np.array_equal(got["sign_half"][np.signbit(inp["b"])], np.zeros(int(np.signbit(inp["b"]).sum())))   # SIGN(0.5, -0.0) = -0.5
+    assert np.array_equal(got["amax1"].view(np.int64), got["max"].view(np.int64))
+    assert np.array_equal(got["amin1"].view(np.int64), got["min"].view(np.int64))
 
 
 def test_compiler_conventions_intrinsics_live():

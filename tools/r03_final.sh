@@ -6,8 +6,7 @@ mkdir -p $O
 if [ "${PART:-a}" = "a" ]; then
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -2 | tee $O/smoke.txt
   timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/tests.log 2>&1; echo "pytest rc=$?"; tail -4 $O/tests.log
-  bash tools/r03_bench.sh 2>&1 | tail -40
-  cp gpurun_out/r03bench/*.json $O/ 2>/dev/null
+  OUT_DIR=$O bash tools/r03_bench.sh 2>&1 | tail -40
 else
   bash tools/r03_profile.sh 2>&1 | grep -E "done|du|prof_r03" | tail -6
   LIBS=S CFGS="40 60 69 100" bash tools/r03_stamp.sh 2>&1 | cut -c1-420 > $O/stamps.txt

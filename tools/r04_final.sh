@@ -8,7 +8,7 @@ if [ "${PART:-a}" = "a" ]; then
   python -c "import __graft_entry__ as g; g.smoke()" 2>&1 | grep -v amdgpu.ids | tail -2 | tee $O/smoke.txt
   timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/tests.log 2>&1; echo "pytest rc=$?"; tail -3 $O/tests.log
   MCKPP_SOLVER_MODE=1 timeout -k 10 900 python -m pytest tests -x -q -m gpu > $O/tests_solver_mode_1.log 2>&1; echo "pytest (MCKPP_SOLVER_MODE=1) rc=$?"; tail -3 $O/tests_solver_mode_1.log
-  timeout -k 10 600 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+  timeout -k 10 600 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
   python tools/r04_digest.py $O/bench_n1.json | tee $O/bench_n1_digest.txt
   cp gpurun_out/parity_tolerance_gpu_*.json $O/ 2>/dev/null
 else

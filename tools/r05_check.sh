@@ -10,6 +10,6 @@ fi
 if [ "${RATES:-1}" = 1 ]; then
   timeout -k 10 400 python tools/r05_lone_probe.py 60 100 > $O/lone.txt 2>&1; grep "launcher\|15x8x2\|19x16x1" $O/lone.txt
   for nz in 60 100; do for solo in 0 1; do
-    MCKPP_SOLO=$solo timeout -k 10 300 python bench.py --no-cpu-baseline --no-extras --steps 20 --warmup 3 --settle ${SETTLE:-200} --nz $nz 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('nz=$nz solo=$solo value %.4g ms %.3f burst %.3f maxpass %d' % (d['value'], d['ms_per_step'], d['burst']['ms_per_step'], d['config']['max_passes_last_step']))"
+    MCKPP_SOLO=$solo timeout -k 10 300 python bench.py --full --no-cpu-baseline --no-extras --steps 20 --warmup 3 --settle ${SETTLE:-200} --nz $nz 2>/dev/null | python3 -c "import json,sys; d=json.loads(sys.stdin.read()); print('nz=$nz solo=$solo value %.4g ms %.3f burst %.3f maxpass %d' % (d['value'], d['ms_per_step'], d['burst']['ms_per_step'], d['config']['max_passes_last_step']))"
   done; done
 fi

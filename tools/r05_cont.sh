@@ -9,7 +9,7 @@ if [ "${TESTS:-1}" = 1 ]; then
   [ $rc = 0 ] || exit 1
 fi
 for lim in ${LIMS:-8 32 128 100000}; do
-  MCKPP_SOLO_LIMIT=$lim timeout -k 10 300 python bench.py --no-cpu-baseline --steps 5 --warmup 2 --settle 0 --legs config3_long_12500${LEGS} 2>/dev/null | python3 -c "
+  MCKPP_SOLO_LIMIT=$lim timeout -k 10 300 python bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --settle 0 --legs config3_long_12500${LEGS} 2>/dev/null | python3 -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 for k in ('config3_long_12500','config3_long'):

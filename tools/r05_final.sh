@@ -15,7 +15,7 @@ if [ "${PART:-a}" = "a" ]; then
   MCKPP_MULTISTEP=0 timeout -k 10 900 python -m pytest tests -x -q -m gpu -k "$S" > $O/tests_multistep0.log 2>&1; echo "pytest (MCKPP_MULTISTEP=0) rc=$?"; tail -2 $O/tests_multistep0.log
   MCKPP_PS_FIXED_L=0 timeout -k 10 900 python -m pytest tests -x -q -m gpu -k "$S" > $O/tests_general_kernels.log 2>&1; echo "pytest (MCKPP_PS_FIXED_L=0) rc=$?"; tail -2 $O/tests_general_kernels.log
   MCKPP_L3_CAP=3 timeout -k 10 900 python -m pytest tests -x -q -m gpu -k "$S" > $O/tests_l3cap3.log 2>&1; echo "pytest (MCKPP_L3_CAP=3) rc=$?"; tail -2 $O/tests_l3cap3.log
-  timeout -k 10 800 python bench.py > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
+  timeout -k 10 800 python bench.py --full > $O/bench_n1.json 2> $O/bench_n1.err; echo "bench rc=$?"
   python tools/r05_digest.py $O/bench_n1.json | tee $O/bench_n1_digest.txt
   python3 - $O/bench_n1.json <<'PY'
 import json, sys

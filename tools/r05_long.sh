@@ -2,7 +2,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${OUT:-r05d}; mkdir -p $O
 for solo in ${SOLOS:-0 1}; do
-  MCKPP_SOLO=$solo timeout -k 10 500 python bench.py --no-cpu-baseline --steps 5 --warmup 2 --settle 0 --legs ${LEGS:-config3_long,config3_long_12500} > $O/long_solo$solo.json 2>$O/long_solo$solo.err
+  MCKPP_SOLO=$solo timeout -k 10 500 python bench.py --full --no-cpu-baseline --steps 5 --warmup 2 --settle 0 --legs ${LEGS:-config3_long,config3_long_12500} > $O/long_solo$solo.json 2>$O/long_solo$solo.err
   python3 - $O/long_solo$solo.json $solo <<'PY'
 import json, sys
 d = json.load(open(sys.argv[1]))

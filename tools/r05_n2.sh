@@ -3,7 +3,7 @@
 cd $GRAFT_REPO_ROOT
 O=gpurun_out/${OUT:-r05g}; mkdir -p $O
 export MCKPP_BENCH_SHARE_GPU=1 MCKPP_BENCH_BACKEND=gloo
-A="--gpus 2 --steps 10 --warmup 2 --settle 40 --ncol 50000"
+A="--full --gpus 2 --steps 10 --warmup 2 --settle 40 --ncol 50000"
 timeout -k 10 500 python3 bench.py $A > $O/bench_n2_shared.json 2> $O/bench_n2_shared.err; echo "rc=$?"
 MCKPP_BENCH_FAIL_RANK=1 MCKPP_BENCH_FAIL_RANK3=1 timeout -k 10 500 python3 bench.py $A --no-cpu-baseline > $O/bench_n2_fail.json 2> $O/bench_n2_fail.err; echo "rc(fail on rank 1)=$?"
 python3 - $O <<'PY'
