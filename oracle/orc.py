@@ -1,5 +1,6 @@
 """ctypes front-end for the CPU oracle (oracle/liboracle.so) and, when built,
-the compiled reference pieces (oracle/_ref/libmckpp_ref.so).
+the compiled reference pieces (oracle/_ref/libmckpp_ref.so: EOS, cpsw, z121;
+oracle/_ref/libmckpp_ref_step{,_pexp}.so: the reference's whole physics step).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, bench.py's cpu_baseline leg and
 __graft_entry__.smoke().  The product package never imports this module.
@@ -13,6 +14,8 @@ import numpy as np
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB = os.path.join(HERE, "liboracle.so")
 REFLIB = os.path.join(HERE, "_ref", "libmckpp_ref.so")
+REFSTEPLIB = {0: os.path.join(HERE, "_ref", "libmckpp_ref_step.so"),        # EXP = libm exp (the reference's build)
+              1: os.path.join(HERE, "_ref", "libmckpp_ref_step_pexp.so")}  # EXP = the portable exp (exp_mode=1)
 
 NI, NJ = 890, 48
 TABLE_SHAPE = (NJ + 2, NI + 2)  # C-order view of Fortran wmt(0:891,0:49)
@@ -26,7 +29,7 @@ def build(force=False):
         os.path.getmtime(LIB) < os.path.getmtime(os.path.join(HERE, "mckpp_oracle.c"))
     ):
         subprocess.check_call(["make", "-C", HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference/src") and not os.path.exists(REFLIB):
+    if os.path.isdir("/root/reference/src") and not all(map(os.path.exists, [REFLIB] + list(REFSTEPLIB.values()))):
         subprocess.check_call(["make", "-C", HERE, "ref"], stdout=subprocess.DEVNULL)
 
 
@@ -147,6 +150,136 @@ def ref():
         R.ref_z121.argtypes = [C.c_int, C.c_double, C.c_double, C.POINTER(C.c_double), C.POINTER(C.c_double)]
         _ref = R
     return _ref
+
+
+def have_ref_step():
+    """True where oracle/_ref holds both builds of the reference's physics step."""
+    build()
+    return all(os.path.exists(p) for p in REFSTEPLIB.values())
+
+
+_ref_step = {}
+
+
+def _ref_step_lib(exp_mode):
+    if exp_mode not in _ref_step:
+        R = C.CDLL(REFSTEPLIB[exp_mode])
+        R.ref_step_setup.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 6
+        R.ref_step_xfer.restype = C.c_int
+        R.ref_step_xfer.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int]
+        R.ref_step_run.argtypes = [C.c_int, C.c_int]
+        _ref_step[exp_mode] = R
+    return _ref_step[exp_mode]
+
+
+# switches of kpp_const_fields in the order of ref_step_setup's sw(1:16) (oracle/ref_step_shim.F90)
+_REF_SWITCHES = ["LKPP", "LRI", "LDD", "L_SSref", "L_RELAX_SST", "L_RELAX_CALCONLY", "L_FCORR", "L_FCORR_WITHZ",
+                 "L_SFCORR", "L_SFCORR_WITHZ", "L_RELAX_SAL", "L_RELAX_OCNT", "L_NO_FREEZE", "L_NO_ISOTHERM",
+                 "L_DAMP_CURR"]
+
+
+def _ref_layout(nz):
+    """batch field -> (reference field, component index tuple after the level axis, first Fortran index, count);
+    the reference allocates with nztmax = nz + 1 (as the library's KppConstFields)."""
+    nzp1, nzt = nz + 1, nz + 1
+    m = {}
+    for nm, ref, l in (("U", "U", 0), ("V", "U", 1), ("T", "X", 0), ("S", "X", 1), ("U_init", "U_init", 0),
+                       ("V_init", "U_init", 1)):
+        m[nm] = (ref, (l,), 1, nzp1)
+    for t in (0, 1):
+        for nm, ref, l in (("Us", "Us", 0), ("Vs", "Us", 1), ("Ts", "Xs", 0), ("Ss", "Xs", 1)):
+            m[f"{nm}{t}"] = (ref, (l, t), 1, nzp1)
+    for nm in ("Rig", "Shsq", "swfrac", "tinc_fcorr", "sinc_fcorr", "fcorr_withz", "sfcorr_withz", "scorr",
+               "ocnTcorr", "sal_clim", "ocnT_clim"):
+        m[nm] = (nm, (), 1, nzp1)
+    m["dbloc"] = ("dbloc", (), 1, nz)
+    m["swdk_opt"] = ("swdk_opt", (), 0, nz + 1)
+    m["rho"] = ("rho", (), 0, nzt + 2)
+    m["cp"] = ("cp", (), 0, nzt + 2)
+    m["buoy"] = ("buoy", (), 1, nzt + 1)
+    for nm in ("difm", "difs", "dift"):
+        m[nm] = (nm, (), 0, nzt + 1)
+    m["ghat"] = ("ghat", (), 1, nzt)
+    m["wU1"], m["wU2"] = ("wU", (0,), 0, nzt + 1), ("wU", (1,), 0, nzt + 1)
+    m["wX1"], m["wX2"], m["wX3"] = ("wX", (0,), 0, nzt + 1), ("wX", (1,), 0, nzt + 1), ("wX", (2,), 0, nzt + 1)
+    m["wXNT1"] = ("wXNT", (0,), 0, nzt + 1)
+    return m
+
+
+_REF_SHAPES = {"U": (2,), "X": (2,), "U_init": (2,), "Us": (2, 2), "Xs": (2, 2), "wU": (3,), "wX": (3,), "wXNT": (2,)}
+_REF_SCALARS = ["f", "Ssurf", "Sref", "SSref", "ocdepth", "hmix", "kmix", "uref", "vref", "Tref", "reset_flag",
+                "dampu_flag", "dampv_flag", "freeze_flag", "fcorr", "relax_sst", "SST0", "fcorr_twod", "relax_sal",
+                "relax_ocnT"]
+_REF_INTS = {"old": "old", "newi": "new", "jerlov": "jerlov", "l_initflag": "l_initflag", "l_ocean": "l_ocean"}
+
+
+def ref_step(const, batch, forcing, exp_mode=1, ntime0=1, run_physics=None, bottom_temp=None, vary_bottom_temp=False):
+    """Run the compiled reference's own mckpp_physics_driver() on the columns of `batch` (left unchanged), one step
+    per entry of `forcing` (a list of sflux(1:6) arrays [ncol, 6], set before each step), with the grid, constants
+    and switches of `const` and EXP from libm (exp_mode=0) or the portable exp (exp_mode=1).  Returns one Batch per
+    step holding what the reference's kpp_3d_fields carries after it (fields the reference has no counterpart for -
+    talpha, sbeta, status, npasses - stay zero)."""
+    R = _ref_step_lib(exp_mode)
+    c, nz, ncol = const.c, const.nz, batch.ncol
+    nzp1, nzt = nz + 1, nz + 1
+    sw = (C.c_int * 16)(*([int(getattr(c, k)) for k in _REF_SWITCHES] + [int(bool(vary_bottom_temp))]))
+    iv = (C.c_int * 4)(c.itermax, c.iso_bot, c.dt_uvdamp, c.clim_present)
+    rv = np.array([c.hmixtolfrac, c.dto, c.grav, c.vonk, c.sice, c.iso_thresh])
+    zm, hm = np.ascontiguousarray(const.zm[1:nzp1 + 1]), np.ascontiguousarray(const.hm[1:nzp1 + 1])
+    dm, t0, t1 = (np.ascontiguousarray(a[0:nz + 1]) for a in (const.dm, const.tri0, const.tri1))
+    R.ref_step_setup(nz, ncol, sw, iv, _dp(rv), _dp(zm), _dp(hm), _dp(dm), _dp(t0), _dp(t1))
+
+    def xfer(name, arr, put):
+        a = np.asfortranarray(arr, dtype=np.float64)
+        flat = a.reshape(-1, order="F")
+        rc = R.ref_step_xfer(name.encode(), len(name), _dp(flat), flat.size, 1 if put else 0)
+        if rc != 0:
+            raise RuntimeError(f"ref_step_xfer({name}): {rc}")
+        return flat.reshape(a.shape, order="F")
+
+    lay = _ref_layout(nz)
+    full = {"U": (nzp1,), "X": (nzp1,), "U_init": (nzp1,), "Us": (nzp1,), "Xs": (nzp1,), "Rig": (nzp1,),
+            "Shsq": (nzp1,), "dbloc": (nz,), "rho": (nzt + 2,), "cp": (nzt + 2,), "buoy": (nzt + 1,),
+            "swfrac": (nzp1,), "swdk_opt": (nz + 1,), "difm": (nzt + 1,), "difs": (nzt + 1,), "dift": (nzt + 1,),
+            "wU": (nzt + 1,), "wX": (nzt + 1,), "wXNT": (nzt + 1,), "ghat": (nzt,)}
+    for nm in ("tinc_fcorr", "sinc_fcorr", "fcorr_withz", "sfcorr_withz", "scorr", "ocnTcorr", "sal_clim", "ocnT_clim"):
+        full[nm] = (nzp1,)
+    arrays = {r: np.zeros((ncol,) + lv + _REF_SHAPES.get(r, ())) for r, lv in full.items()}
+    for b, (r, comp, lo, n) in lay.items():
+        arrays[r][(slice(None), slice(None)) + comp] = batch.a[b][:, lo:lo + n]
+    for r, a in arrays.items():
+        xfer(r, a, True)
+    for nm in _REF_SCALARS:
+        xfer(nm, batch[nm], True)
+    for b, r in _REF_INTS.items():
+        xfer(r, batch[b], True)
+    xfer("hmixd", batch["hmixd"], True)
+    xfer("nmodeadv", batch["nmodeadv"], True)
+    xfer("modeadv", batch["modeadv"].transpose(0, 2, 1), True)
+    xfer("advection", batch["advection"].transpose(0, 2, 1), True)
+    xfer("run_physics", np.ones(ncol) if run_physics is None else run_physics, True)
+    if bottom_temp is not None:
+        xfer("bottom_temp", bottom_temp, True)
+    sflux = np.zeros((ncol, 9, 5, 2))
+    out = []
+    for i, sf in enumerate(forcing):
+        sflux[:, 0:6, 4, 0] = sf
+        xfer("sflux", sflux, True)
+        R.ref_step_run(int(ntime0 + i), 1)
+        ob = batch.copy()
+        ob["sflux"] = sf
+        for nm in ("talpha", "sbeta", "status", "npasses"):
+            ob[nm] = 0
+        got = {r: xfer(r, a, False) for r, a in arrays.items()}
+        for b, (r, comp, lo, n) in lay.items():
+            ob.a[b][:, lo:lo + n] = got[r][(slice(None), slice(None)) + comp]
+        for nm in _REF_SCALARS:
+            ob[nm] = xfer(nm, np.zeros(ncol), False)
+        for b, r in _REF_INTS.items():
+            ob[b] = xfer(r, np.zeros(ncol), False)
+        ob["hmixd"] = xfer("hmixd", np.zeros((ncol, 2)), False)
+        out.append(ob)
+    return out
 
 
 # ---------------------------------------------------------------------------

@@ -7,9 +7,9 @@
 !   /root/reference/src/mckpp_physics_verticalmixing_z121_mod.F90 (z121)
 ! Built only by oracle/Makefile target `ref` into oracle/_ref/ and used by
 ! tests/ to pin oracle/mckpp_oracle.c bit-for-bit on those functions.
-! Everything else on the hot path USEs mckpp_data_fields -> mckpp_netcdf_read
-! -> netcdf (not in this image) and is therefore treated as unbuildable here
-! (see DESIGN.md, "Oracle pinning").
+! The rest of the hot path USEs mckpp_data_fields -> mckpp_netcdf_read -> netcdf;
+! it is built with the stand-in oracle/netcdf_standin.F90 and driven through
+! oracle/ref_step_shim.F90 (DESIGN.md section 4, "What pins it").
 !
 ! Compiled with -fdefault-real-8, so REAL == c_double.
 

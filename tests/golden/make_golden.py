@@ -12,8 +12,8 @@ Produces (inputs + expected outputs only, no reference source):
   eos_ref_checks.json - what tests/test_oracle_cpu.py compares with the compiled reference where it is built:
                   SHA-256 digests of mckpp_abk80 / mckpp_cpsw on its 1e6 seeded points, and mckpp_abk80 on
                   every entry path (`python tests/golden/make_golden.py checks` writes this file alone)
-The rest of the path cannot be built here without a stand-in netcdf module
-(DESIGN.md "Oracle pinning"), so there are no reference vectors for it.
+The reference's whole physics step is recorded by the sibling script make_ref_step_golden.py
+(tests/golden/ref_step.npz; DESIGN.md section 4, "What pins it").
 """
 import ctypes as C
 import hashlib

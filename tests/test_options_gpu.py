@@ -413,3 +413,20 @@ def test_restart_and_ancillary_update_on_optional_physics_context(mk, tmp_path):
     ctx2.download(k3c)
     assert np.array_equal(k3c.X[ocean], k3b.X[ocean]) and np.array_equal(k3c.hmix[ocean], k3b.hmix[ocean])
     ctx2.close()
+
+
+# the switch families pinned to the reference's own physics step (tests/ref_step_cases.py, recorded outputs of the
+# portable-exp build in tests/golden/ref_step.npz): bit for bit on every field after every step
+_REF_STEP_SWITCH_CASES = [t for t, c in __import__("ref_step_cases").CASES.items()
+                          if (c.switches or c.bottom_temp) and not t.startswith("nz40_")]
+
+
+@pytest.mark.parametrize("tag", _REF_STEP_SWITCH_CASES)
+def test_switches_match_the_reference_step(mk, tag):
+    import ref_step_cases as rc
+
+    golden = rc.Golden()
+    case = rc.CASES[tag]
+    for nt, got in rc.run_hip(mk, tag, golden):
+        bad = rc.mismatches(case, golden.digests(tag, "pexp"), golden.values(tag), nt, got.__getitem__)
+        assert not bad, f"{tag} step {nt}: HIP differs from the reference's own step: {bad}"

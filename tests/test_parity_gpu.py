@@ -1552,3 +1552,35 @@ def test_multi_device_handle_equals_single_context(mk, nz, shards):
     m.gather(4, 0, h)
     assert np.array_equal(h, k3.hmix)
     m.close()
+
+
+# ---------------------------------------------------------------------------
+# pinned to the reference's own physics step: the recorded outputs of the portable-exp build
+# (tests/golden/ref_step.npz, tests/ref_step_cases.py), bit for bit on every field after every step
+# ---------------------------------------------------------------------------
+_REF_STEP_CASES = [t for t, c in __import__("ref_step_cases").CASES.items()
+                   if not (c.switches or c.bottom_temp) or t.startswith("nz40_")]
+
+
+@pytest.mark.parametrize("tag", _REF_STEP_CASES)
+def test_kernel_matches_the_reference_step(mk, tag):
+    import ref_step_cases as rc
+
+    golden = rc.Golden()
+    case = rc.CASES[tag]
+    for nt, got in rc.run_hip(mk, tag, golden):
+        bad = rc.mismatches(case, golden.digests(tag, "pexp"), golden.values(tag), nt, got.__getitem__)
+        assert not bad, f"{tag} step {nt}: HIP differs from the reference's own step: {bad}"
+
+
+def test_two_ended_solver_within_rounding_of_the_reference_step(mk):
+    """Solver mode 1 (two-ended elimination) against the recorded reference: the same mixed-layer depth index and
+    T, hmix within rounding after the last step."""
+    import ref_step_cases as rc
+
+    golden = rc.Golden()
+    ref = golden.values("nz40")
+    got = rc.run_hip(mk, "nz40", golden, solver_mode=1)[-1][1]
+    assert np.array_equal(got["kmix"], ref["kmix"])
+    assert np.allclose(got["hmix"], ref["hmix"], rtol=1e-10, atol=0)
+    assert np.abs(got["T"] - ref["T"]).max() <= 1e-10 * np.abs(ref["T"]).max()
