@@ -292,6 +292,38 @@ int mckpp_hip_window_reset(mckpp_hip_handle h);
 int mckpp_hip_window_accumulate(mckpp_hip_handle h);
 int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out);
 
+/* Output windows accumulated inside the step launches, so that a run with output can still take many steps in one
+ * launch (mckpp_hip_run_forced, mckpp_hip_step with nsteps > 1).  A schedule is one XIOS <file> of iodef.xml: a
+ * period in steps, MCKPP_OUT_* fields, and per field a mask of operations - MCKPP_WIN_MEAN, _MIN, _MAX, and _LAST,
+ * the value after the window's last step (XIOS "instant" at the output step).  A context holds up to
+ * MCKPP_WIN_SCHEDULES of them.  Window w >= 0 covers steps nt_origin + w*period .. nt_origin + (w+1)*period - 1.
+ *   window_schedule: sets schedule `sched` (nfields 0: cancels it) with a ring of nrec records; window w lives in
+ *     ring slot w % nrec.  Fails for an unknown field, an empty mask, a diagnostic field with the diagnostics off,
+ *     a correction field without the correction rows, or device memory that cannot be allocated (the schedule is
+ *     then not set).  upload and load_restart cancel every schedule.
+ *   Every MCKPP_MODE_STEP launch - step, run_forced and their multi_ forms, one launch or a launch per step -
+ *     accumulates every schedule in the column kernel, after each column's step (init_ocean, vmix_pass and
+ *     vmix_only never do).  The steps under a schedule must follow on from one another, and a launch may not reach
+ *     a window at or beyond first_kept + nrec: such a launch fails before anything is launched.
+ *   window_record_fetch: record `rec`, op 0 mean, 1 min, 2 max, 3 last (the bit 1 << op of the field's mask), into
+ *     out(npts[,nzp1]) as window_fetch lays it out; land points keep what `out` held.  Bit for bit what
+ *     window_select, window_reset at the window's first step, window_accumulate after each of its steps and
+ *     window_fetch (op 3: at its last step) give.  Fails, naming the record's steps, for a record that is not
+ *     complete - one whose first steps ran before the schedule was set included - or has been released.
+ *   window_record_release: releases records up to and including upto_rec (complete ones only), freeing their slots.
+ *   window_records: first_kept, the first record not released, and last_complete, the last record whose steps have
+ *     all run (-1: none); records first_kept .. last_complete can be fetched. */
+#define MCKPP_WIN_MEAN 1u
+#define MCKPP_WIN_MIN  2u
+#define MCKPP_WIN_MAX  4u
+#define MCKPP_WIN_LAST 8u
+#define MCKPP_WIN_SCHEDULES 4
+int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int period, int nrec,
+                              const int32_t *fields, const uint32_t *ops, int32_t nfields);
+int mckpp_hip_window_record_fetch(mckpp_hip_handle h, int sched, int64_t rec, int field, int op, double *out);
+int mckpp_hip_window_record_release(mckpp_hip_handle h, int sched, int64_t upto_rec);
+int mckpp_hip_window_records(mckpp_hip_handle h, int sched, int64_t *first_kept, int64_t *last_complete);
+
 /* Per-column status words (npts entries in 3D ordering; land = 0), number of
  * columns with a non-zero word, and (optional) vmix+ocnint passes per column
  * of the last step. Any output pointer may be NULL. */
@@ -390,6 +422,13 @@ int mckpp_hip_multi_window_select(mckpp_hip_multi_handle m, const int32_t *field
 int mckpp_hip_multi_window_reset(mckpp_hip_multi_handle m);
 int mckpp_hip_multi_window_accumulate(mckpp_hip_multi_handle m);
 int mckpp_hip_multi_window_fetch(mckpp_hip_multi_handle m, int field, int op, double *out);
+/* Output windows inside the step launches (mckpp_hip_window_schedule) over all shards: every shard keeps the records
+ * of its own columns; record_fetch gathers a record into 3-D order like window_fetch. */
+int mckpp_hip_multi_window_schedule(mckpp_hip_multi_handle m, int sched, int nt_origin, int period, int nrec,
+                                    const int32_t *fields, const uint32_t *ops, int32_t nfields);
+int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, double *out);
+int mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle m, int sched, int64_t upto_rec);
+int mckpp_hip_multi_window_records(mckpp_hip_multi_handle m, int sched, int64_t *first_kept, int64_t *last_complete);
 /* Restart set (src/mckpp_xios_io.F90:368-465) of all shards: one file per shard, <path>.<shard>of<ndev>.
  * load needs the state uploaded first (it gives the shards their column maps) and refuses files written for
  * another number of shards or another land mask, before anything resident is replaced. */

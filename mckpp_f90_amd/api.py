@@ -80,6 +80,50 @@ OUT_FIELDS = ("u", "v", "T", "S_anom", "hmix", "S", "B", "wu", "wv", "wT", "wS",
               "tauy_in", "solar_in", "nsolar_in", "PminusE_in", "freeze_flag", "comp_flag", "dampu_flag", "dampv_flag")
 OUT = {n: i for i, n in enumerate(OUT_FIELDS)}
 OP_MEAN, OP_MIN, OP_MAX, OP_INSTANT = 0, 1, 2, 3
+# operations of an output schedule (mckpp_hip_window_schedule), one bit per op of window_record_fetch: 1 << op
+WIN_MEAN, WIN_MIN, WIN_MAX, WIN_LAST = 1, 2, 4, 8
+OP_LAST = 3
+WIN_SCHEDULES = 4
+
+
+def _win_field(f):
+    """An OUT_* index or field name -> the index, or ValueError."""
+    if isinstance(f, str):
+        if f not in OUT:
+            raise ValueError(f"unknown output field {f!r}")
+        return OUT[f]
+    i = int(f)
+    if not 0 <= i < len(OUT_FIELDS):
+        raise ValueError(f"unknown output field {f}")
+    return i
+
+
+def _win_args(fields, ops):
+    """(fields, ops) of window_schedule as the int32 / uint32 arrays the library takes; ops is one mask for every field
+    or one per field.  Unknown fields, empty or foreign masks and a field named twice are refused here."""
+    f = [_win_field(x) for x in fields]
+    o = [int(ops)] * len(f) if np.ndim(ops) == 0 else [int(x) for x in ops]
+    if len(o) != len(f):
+        raise ValueError(f"{len(f)} fields but {len(o)} operation masks")
+    for fi, oi in zip(f, o):
+        if oi == 0 or oi & ~0xF:
+            raise ValueError(f"field {OUT_FIELDS[fi]}: operations {oi:#x} (a non-empty mask of WIN_MEAN, WIN_MIN, WIN_MAX, WIN_LAST)")
+    if len(set(f)) != len(f):
+        raise ValueError("a field named twice in one schedule")
+    return np.ascontiguousarray(f, dtype=np.int32), np.ascontiguousarray(o, dtype=np.uint32)
+
+
+def _win_check_fetch(scheds, sched, field, op):
+    """the field and op of a record fetch against what schedule `sched` keeps (as this object set it)"""
+    f = _win_field(field)
+    if not 0 <= int(op) <= 3:
+        raise ValueError(f"op {op} (OP_MEAN 0, OP_MIN 1, OP_MAX 2, OP_LAST 3)")
+    kept = scheds.get(int(sched), {})
+    if f not in kept:
+        raise ValueError(f"field {OUT_FIELDS[f]} is not in output schedule {sched}")
+    if not (kept[f] >> int(op)) & 1:
+        raise ValueError(f"output schedule {sched} keeps no op {op} of field {OUT_FIELDS[f]} (operations {kept[f]:#x})")
+    return f
 
 
 class MckppHipError(RuntimeError):
@@ -159,6 +203,12 @@ def _bind(lib):
     lib.mckpp_hip_multi_window_reset.argtypes = [C.c_void_p]
     lib.mckpp_hip_multi_window_accumulate.argtypes = [C.c_void_p]
     lib.mckpp_hip_multi_window_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+    _up = C.POINTER(C.c_uint32)
+    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
+        getattr(lib, pre + "window_schedule").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _up, C.c_int32]
+        getattr(lib, pre + "window_record_fetch").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, _dp]
+        getattr(lib, pre + "window_record_release").argtypes = [C.c_void_p, C.c_int, C.c_int64]
+        getattr(lib, pre + "window_records").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
     lib.mckpp_hip_multi_save_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_load_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
@@ -310,7 +360,53 @@ class Kpp3dFields:
         return s
 
 
-class MckppHip:
+class _WindowSchedules:
+    """Output windows accumulated inside the step launches (mckpp_hip_window_schedule and its kin), for one context or
+    for all shards of a multi handle (_pre).  The schedules this object set are kept here so that a fetch of a field or
+    an op a schedule does not keep is refused before the library is called."""
+    _pre = "mckpp_hip_"
+
+    def _scheds(self):
+        return self.__dict__.setdefault("_wsched", {})
+
+    def window_schedule(self, sched, nt_origin, period, nrec, fields, ops):
+        """Schedule `sched` (0..WIN_SCHEDULES-1): window w covers steps nt_origin + w*period .. + period-1, nrec records
+        in a ring; fields are OUT_* indices or names, ops one WIN_* mask for all or one per field.  No fields: cancel."""
+        f, o = _win_args(fields, ops)
+        lib = _lib()
+        if getattr(lib, self._pre + "window_schedule")(self._h, int(sched), int(nt_origin), int(period), int(nrec),
+                                                       f.ctypes.data_as(_ip), o.ctypes.data_as(C.POINTER(C.c_uint32)), len(f)) != 0:
+            err = lib.mckpp_hip_last_error().decode()
+            a = C.c_int64()
+            if getattr(lib, self._pre + "window_records")(self._h, int(sched), C.byref(a), C.byref(a)) != 0:
+                self._scheds().pop(int(sched), None)   # (a refused schedule leaves the one in place; memory that could
+            raise MckppHipError(err)                    # not be had leaves none)
+        if len(f):
+            self._scheds()[int(sched)] = {int(a): int(b) for a, b in zip(f, o)}
+        else:
+            self._scheds().pop(int(sched), None)
+
+    def window_record_fetch(self, sched, rec, field, op, out):
+        """Record `rec` of schedule `sched`: op OP_MEAN / OP_MIN / OP_MAX / OP_LAST of `field` into out(npts[, nzp1])
+        (Fortran order; land points keep what out held)."""
+        f = _win_check_fetch(self._scheds(), sched, field, op)
+        assert out.flags["F_CONTIGUOUS"] and out.dtype == np.float64
+        self._hold(out)
+        _chk(getattr(_lib(), self._pre + "window_record_fetch")(self._h, int(sched), int(rec), f, int(op), out.ctypes.data_as(_dp)))
+        return out
+
+    def window_record_release(self, sched, upto_rec):
+        """Release the records of `sched` up to and including upto_rec (their ring slots are free again)."""
+        _chk(getattr(_lib(), self._pre + "window_record_release")(self._h, int(sched), int(upto_rec)))
+
+    def window_records(self, sched):
+        """(first_kept, last_complete): records first_kept .. last_complete of `sched` can be fetched."""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(getattr(_lib(), self._pre + "window_records")(self._h, int(sched), C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+
+class MckppHip(_WindowSchedules):
     """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
 
     def __init__(self, kpp_const_fields, device=0):
@@ -357,6 +453,7 @@ class MckppHip:
         s = kpp_3d_fields.as_c()
         _chk(_lib().mckpp_hip_upload(self._h, C.byref(s)))
         self._npts_cache = kpp_3d_fields.npts
+        self._scheds().clear()   # (upload cancels every output schedule)
 
     def set_forcing(self, sflux):
         assert sflux.flags["F_CONTIGUOUS"]
@@ -390,6 +487,7 @@ class MckppHip:
     def load_restart(self, path, npts):
         _chk(_lib().mckpp_hip_load_restart(self._h, str(path).encode()))
         self._npts_cache = npts
+        self._scheds().clear()
 
     def update_ancillaries(self, kpp_3d_fields):
         """Re-upload what mckpp_boundary_update rewrites between steps (optional-physics inputs only)."""
@@ -508,8 +606,9 @@ class MckppHip:
         return y
 
 
-class MckppHipMulti:
+class MckppHipMulti(_WindowSchedules):
     """Several GPUs behind one handle (mckpp_hip_multi_*): columns dealt round-robin to the devices."""
+    _pre = "mckpp_hip_multi_"
 
     def __init__(self, kpp_const_fields, devices):
         self._h = C.c_void_p()
@@ -546,6 +645,7 @@ class MckppHipMulti:
         sc = k3.as_c()
         _chk(_lib().mckpp_hip_multi_upload(self._h, C.byref(sc)))
         self._npts = k3.npts
+        self._scheds().clear()   # (upload cancels every output schedule)
 
     def set_forcing(self, sflux):
         self._hold(sflux)
@@ -620,6 +720,7 @@ class MckppHipMulti:
 
     def load_restart(self, path):
         _chk(_lib().mckpp_hip_multi_load_restart(self._h, str(path).encode()))
+        self._scheds().clear()
 
     def release_host_arrays(self):
         _chk(_lib().mckpp_hip_multi_release_host_arrays(self._h))

@@ -37,6 +37,22 @@ enum { MCKPP_MODE_STEP = 0, MCKPP_MODE_INIT = 1, MCKPP_MODE_PASS = 2, MCKPP_MODE
 template <class T> using mckpp_ptr_plain = T *;
 template <class T> using mckpp_ptr_global = __attribute__((address_space(1))) T *;
 
+// Output windows accumulated by the column kernel itself (mckpp_hip_window_schedule): one entry per (schedule, field).
+// The field is read as k_out_sample reads it - element off + l of row c (row length ld), plus the column's Sref if
+// add_sref - and folded into the record of the window the step belongs to: window w = (nt - origin) / period, ring slot
+// w % nrec; operation j of the entry (the j-th set bit of ops: sum for the mean, min, max, last) at
+// acc + (slot * nops + j) * plane + c * ld_out + l.
+#define MCKPP_WIN_ENTRIES 64
+template <template <class> class P>
+struct mckpp_win_t {
+  P<const double> src;
+  P<double> acc;
+  long long plane;        // doubles of one operation's record: ncol * ld_out
+  int ld, off, nlev, add_sref, ld_out;
+  int ops, nops;          // MCKPP_WIN_* mask and its number of bits
+  int origin, period, nrec;
+};
+
 template <template <class> class P>
 struct mckpp_kparams_t {
   int nz, nzp1, ncol, ld;
@@ -98,10 +114,16 @@ struct mckpp_kparams_t {
   int view_kmax;      // most slots of a view (0: as many as the workgroup's waves other than the manager's hold items for; MCKPP_VIEW_KMAX)
   int solo_limit;     // workgroups leave their other slots empty for a straggler while the device holds at most this many
                       // (0: never - MCKPP_SOLO=0; default: workgroups / 32, at least 2; MCKPP_SOLO_LIMIT)
+  // output windows of MCKPP_MODE_STEP launches (k_column_ps, finish round): nwin entries of the context's device table
+  // (0: no schedule, nothing sampled)
+  P<const mckpp_win_t<P>> win;
+  int nwin;
 };
 using mckpp_kparams = mckpp_kparams_t<mckpp_ptr_plain>;
 using mckpp_kparams_dev = mckpp_kparams_t<mckpp_ptr_global>;
+using mckpp_win = mckpp_win_t<mckpp_ptr_plain>;
 static_assert(sizeof(mckpp_kparams) == sizeof(mckpp_kparams_dev), "same layout");
+static_assert(sizeof(mckpp_win) == sizeof(mckpp_win_t<mckpp_ptr_global>), "same layout");
 
 // what the last cooperative-kernel launch looked like (for the residency check of the tests)
 struct mckpp_launch_info { int nblocks, threads, max_blocks_per_cu; size_t lds_bytes; };

@@ -2871,6 +2871,35 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         }
       }
     END_ITEMS
+    // ---- output windows (mckpp_hip_window_schedule): every scheduled field of a column that has finished its step,
+    // sampled from the rows and records just stored - what window_accumulate after the step reads - and folded into
+    // the record of the step's window with k_out_sample's operations in its order (a column's steps come here in
+    // order, so its sums are the per-step API's bit for bit).  Before M0 publishes the step: once p.done[c] moves, the
+    // column's next step may start elsewhere and rewrite the rows.  The records are plain loads and stores: a column
+    // stays on one XCD for the launch, and its next step's acquire (M0) covers them like the rows.
+    if (p.nwin > 0 && p.mode == MCKPP_MODE_STEP) {   // (uniform)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's stores of the rows have left it ...
+      __syncthreads();                                    // ... before any wave reads them
+      FOR_ITEMS
+        if (!act) continue;   // the two equation-of-state items exist for L1 only
+        if (si[I_FIN] != F_FINAL) continue;
+        const int nt = ntime + si[I_STEP], l = k - 1;
+        for (int e = 0; e < p.nwin; ++e) {
+          const auto &d = p.win[e];
+          if (l >= d.nlev || nt < d.origin) continue;
+          const int q = nt - d.origin, w = q / d.period;
+          const bool first = q == w * d.period;   // the window's first step initialises its record
+          double v = d.src[(size_t)col * d.ld + d.off + l];
+          if (d.add_sref) v = v + p.cs[(size_t)col * MCKPP_CS + CS_SREF];
+          auto r = d.acc + ((size_t)(w % d.nrec) * (size_t)d.nops * (size_t)d.plane + (size_t)col * d.ld_out + l);
+          const int ops = d.ops;
+          if (ops & 1) { const double s_ = first ? 0.0 : r[0]; r[0] = s_ + v; r += d.plane; }
+          if (ops & 2) { const double a = first ? v : r[0]; r[0] = v < a ? v : a; r += d.plane; }
+          if (ops & 4) { const double b = first ? v : r[0]; r[0] = v > b ? v : b; r += d.plane; }
+          if (ops & 8) r[0] = v;
+        }
+      END_ITEMS
+    }
     }   // finish round
     }   // pass of the active slots
     if (!finishing && !(any_waiting && (solo_perm || !sparse))) continue;   // (a workgroup in a view of a few slots asks for its waiting tickets when their columns are done)

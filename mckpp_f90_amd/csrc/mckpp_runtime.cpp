@@ -111,6 +111,20 @@ struct mckpp_hip_ctx {
   std::vector<int> wsel{0, 1, 2, 3, 4};
   std::vector<double *> d_wacc;   // [wsel.size()], each 3 * (ncol*ld | ncol) doubles
   int window_count = 0;
+  // output windows the step launches accumulate themselves (mckpp_hip_window_schedule): per schedule its fields, their
+  // operation masks and rings of records; the steps run under it; the device table of all schedules' fields
+  struct win_sched {
+    std::vector<int> fields;        // empty: no schedule
+    std::vector<unsigned> ops;
+    std::vector<int> ld_out;
+    std::vector<double *> acc;      // [field]: nrec records of popcount(ops) planes of ncol * ld_out doubles
+    int64_t origin = 1, period = 1;
+    int nrec = 1;
+    int64_t first_nt = -1, next_nt = -1;   // the first step run under the schedule, the step the next launch must start at (-1: none yet)
+    int64_t first_kept = 0;                // the records before it are released, or began before first_nt
+  } wsched[MCKPP_WIN_SCHEDULES];
+  mckpp_win *d_win = nullptr;   // [MCKPP_WIN_ENTRIES]
+  int nwin = 0;                 // entries of d_win in use (mckpp_kparams_t::nwin of the step launches)
   double *d_cs = nullptr;
   int *d_ci = nullptr;
   int *d_qhead = nullptr;  // QBLOCK_INTS ints, zeroed before every launch: [0..15] queue heads, [16..31] queue owners, [32] stragglers on the device
@@ -395,8 +409,13 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   return 0;
 }
 
+static void win_cancel(mckpp_hip_ctx *h, int s);
+static int win_cancel_all(mckpp_hip_ctx *h);
+
 static void free_state(mckpp_hip_ctx *h)
 {
+  for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) win_cancel(h, s);   // the records are sized to the resident columns
+  h->nwin = 0;
   for (auto &p : h->d_prof) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_diag) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_ext_in) { if (p) hipFree(p); p = nullptr; }
@@ -447,6 +466,7 @@ int mckpp_hip_finalize(mckpp_hip_handle h)
   free_state(h);
   hipFree(h->d_zm); hipFree(h->d_hm); hipFree(h->d_tri0); hipFree(h->d_tri1);
   hipFree(h->d_swfrac_tab); hipFree(h->d_swdk_tab); hipFree(h->d_wtab); hipFree(h->d_qhead); hipFree(h->d_params); hipFree(h->d_scratch); hipFree(h->d_dm); hipFree(h->d_hsum);
+  if (h->d_win) hipFree(h->d_win);
   if (h->d_dbg) hipFree(h->d_dbg);
   if (h->ev0) hipEventDestroy(h->ev0);
   if (h->ev1) hipEventDestroy(h->ev1);
@@ -654,6 +674,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   if (s->npts <= 0) return fail("mckpp_hip_upload: npts=%lld", (long long)s->npts);
   if (!s->U || !s->X) return fail("mckpp_hip_upload: U and X are required");
   HIPCHK(hipSetDevice(h->device));
+  if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
   const int64_t npts = s->npts;
   const int nzp1 = h->nzp1;
   std::vector<int> ipt;
@@ -875,13 +896,30 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
   p.wX1 = h->d_diag[D_WX1]; p.wX2 = h->d_diag[D_WX2]; p.wX3 = h->d_diag[D_WX3]; p.wXNT1 = h->d_diag[D_WXNT1];
   p.Rig = h->d_diag[D_RIG]; p.dbloc = h->d_diag[D_DBLOC]; p.Shsq = h->d_diag[D_SHSQ];
   p.scratch = h->d_scratch; p.scratch_doubles = h->scratch_doubles;
+  if (mode == MCKPP_MODE_STEP && h->nwin > 0) { p.win = h->d_win; p.nwin = h->nwin; }   // (init / vmix never accumulate)
 }
 
 struct forced_run { int ndtocn, l_rest; double flsn, el; };
 
-static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced = nullptr)
+static int win_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
+static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
+static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced);
+
+// A step launch under output schedules: checked against them before anything is launched, then the schedules know
+// which steps have run (and so which of their records are complete)
+static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced = nullptr,
+               const char *who = "mckpp_hip_step")
 {
   if (!h) return fail("null handle");
+  const bool sched = mode == MCKPP_MODE_STEP && nsteps > 0;
+  if (sched && win_check_launch(h, ntime, nsteps, who)) return -1;
+  if (run_launch(h, ntime, nsteps, mode, forced)) return -1;
+  if (sched) win_advance(h, ntime, nsteps);
+  return 0;
+}
+
+static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced)
+{
   if (h->ncol == 0) { h->nlaunch = 0; h->timed = false; return 0; }
   if (h->ext && !h->ext_inputs_resident)
     return fail("optional-physics context: the relaxation / correction / advection inputs are not resident "
@@ -989,7 +1027,7 @@ int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtoc
     return fail("mckpp_hip_run_forced: steps %d..%d need flux records %d..%d, resident are %d..%d", nt_first,
                 nt_first + nsteps - 1, first_upd, last_upd, h->series_rec0, h->series_rec0 + h->series_nrec - 1);
   const forced_run fr{ndtocn, l_rest, flsn, el};
-  return run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr);
+  return run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr, "mckpp_hip_run_forced");
 }
 
 int mckpp_hip_synchronize(mckpp_hip_handle h)
@@ -1329,6 +1367,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
     const int jw = ci[c * MCKPP_CI + CI_JERLOV];
     if (jw < 1 || jw > 5) return fail("mckpp_hip_load_restart: %s: jerlov=%d in column %zu", path, jw, c);
   }
+  if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
   const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
   if (!same_shape) {
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
@@ -1513,6 +1552,238 @@ int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
   if (h->ncol == 0) return 0;
   if (down_rows(h, src, ld_out, 0, nlev, out)) return -1;
   return xfer_finish(h);
+}
+
+// ---------------------------------------------------------------------------
+// Output windows accumulated inside the step launches (mckpp_hip_window_schedule): k_column_ps samples every field
+// of every schedule after each column's step, into the record of the step's window (see mckpp_win_t).  The host
+// keeps the bookkeeping: which steps have run under a schedule, so which records are complete, and which are
+// released; a launch that would break it fails before anything is launched.
+// ---------------------------------------------------------------------------
+static bool win_is_diag(int f) { return f >= MCKPP_OUT_B && f <= MCKPP_OUT_SINC_FCORR; }
+
+static void win_cancel(mckpp_hip_ctx *h, int s)
+{
+  for (auto *p : h->wsched[s].acc) if (p) hipFree(p);
+  h->wsched[s] = mckpp_hip_ctx::win_sched{};
+}
+
+static int win_cancel_all(mckpp_hip_ctx *h)
+{
+  bool any = false;
+  for (auto &w : h->wsched) any = any || !w.fields.empty();
+  if (!any) return 0;
+  HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still write the records
+  for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) win_cancel(h, s);
+  h->nwin = 0;
+  return 0;
+}
+
+// the device table the step launches read: every field of every schedule
+static int win_table(mckpp_hip_ctx *h)
+{
+  std::vector<mckpp_win> t;
+  for (auto &w : h->wsched)
+    for (size_t i = 0; i < w.fields.size(); ++i) {
+      out_desc d;
+      if (out_field(h, w.fields[i], d)) return -1;
+      mckpp_win e{};
+      e.src = d.src; e.acc = w.acc[i]; e.plane = (long long)h->ncol * w.ld_out[i];
+      e.ld = d.ld; e.off = d.off; e.nlev = d.nlev; e.add_sref = d.add_sref; e.ld_out = w.ld_out[i];
+      e.ops = (int)w.ops[i]; e.nops = __builtin_popcount(w.ops[i]);
+      e.origin = (int)w.origin; e.period = (int)w.period; e.nrec = w.nrec;
+      t.push_back(e);
+    }
+  h->nwin = 0;
+  if (t.empty() || h->ncol == 0) return 0;
+  if (!h->d_win) HIPCHK(hipMalloc(&h->d_win, MCKPP_WIN_ENTRIES * sizeof(mckpp_win)));
+  HIPCHK(hipMemcpy(h->d_win, t.data(), t.size() * sizeof(mckpp_win), hipMemcpyHostToDevice));
+  h->nwin = (int)t.size();
+  return 0;
+}
+
+// the first record a schedule can complete when its first step is nt0
+static int64_t win_first_kept(const mckpp_hip_ctx::win_sched &w, int64_t nt0)
+{
+  return nt0 <= w.origin ? 0 : (nt0 - w.origin + w.period - 1) / w.period;
+}
+
+// the last record all of whose steps have run under the schedule (-1: none)
+static int64_t win_last_complete(const mckpp_hip_ctx::win_sched &w)
+{
+  if (w.next_nt < 0 || w.next_nt < w.origin) return -1;
+  return (w.next_nt - w.origin) / w.period - 1;
+}
+
+static int win_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who)
+{
+  const int64_t last = (int64_t)nt0 + nsteps - 1;
+  for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) {
+    const auto &w = h->wsched[s];
+    if (w.fields.empty()) continue;
+    if (w.next_nt >= 0 && nt0 != w.next_nt)
+      return fail("%s: steps %d..%lld, but output schedule %d has run up to step %lld: the steps under a schedule follow "
+                  "on from one another (the next launch starts at step %lld)", who, nt0, (long long)last, s,
+                  (long long)w.next_nt - 1, (long long)w.next_nt);
+    for (int f : w.fields)
+      if (win_is_diag(f) && !h->diag)
+        return fail("%s: output schedule %d has field %d, a diagnostic, and diagnostics are switched off", who, s, f);
+    if (last < w.origin) continue;
+    const int64_t kept = w.first_nt < 0 ? win_first_kept(w, nt0) : w.first_kept;
+    const int64_t wl = (last - w.origin) / w.period;
+    if (wl >= kept + w.nrec)
+      return fail("%s: steps %d..%lld reach record %lld of output schedule %d (steps %lld..%lld), but its ring of %d "
+                  "records holds records %lld..%lld: fetch and release records first", who, nt0, (long long)last,
+                  (long long)wl, s, (long long)(w.origin + wl * w.period), (long long)(w.origin + (wl + 1) * w.period - 1),
+                  w.nrec, (long long)kept, (long long)(kept + w.nrec - 1));
+  }
+  return 0;
+}
+
+static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps)
+{
+  for (auto &w : h->wsched) {
+    if (w.fields.empty()) continue;
+    if (w.first_nt < 0) { w.first_nt = nt0; w.first_kept = win_first_kept(w, nt0); }
+    w.next_nt = (int64_t)nt0 + nsteps;
+  }
+}
+
+int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int period, int nrec, const int32_t *fields,
+                              const uint32_t *ops, int32_t nfields)
+{
+  const char *who = "mckpp_hip_window_schedule";
+  if (!h) return fail("%s: null handle", who);
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  if (nfields < 0 || (nfields > 0 && (!fields || !ops))) return fail("%s: bad argument (nfields=%d)", who, nfields);
+  if (nfields > 0) {   // everything is checked before the schedule in place is touched
+    if (nt_origin < 1 || period < 1 || nrec < 1)
+      return fail("%s: nt_origin=%d period=%d nrec=%d (each at least 1)", who, nt_origin, period, nrec);
+    if (h->npts <= 0) return fail("%s: upload the state first (the records are sized to the resident columns)", who);
+    int others = 0;
+    for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) if (s != sched) others += (int)h->wsched[s].fields.size();
+    if (others + nfields > MCKPP_WIN_ENTRIES)
+      return fail("%s: %d fields, and the other schedules hold %d: at most %d in all", who, nfields, others, MCKPP_WIN_ENTRIES);
+    for (int i = 0; i < nfields; ++i) {
+      const int f = fields[i];
+      if (f < 0 || f >= MCKPP_OUT_COUNT) return fail("%s: unknown output field %d", who, f);
+      if (ops[i] == 0 || (ops[i] & ~0xFu))
+        return fail("%s: field %d: operations 0x%x (a non-empty mask of MCKPP_WIN_MEAN 1, _MIN 2, _MAX 4, _LAST 8)", who, f, ops[i]);
+      for (int j = 0; j < i; ++j)
+        if (fields[j] == f) return fail("%s: field %d twice in one schedule", who, f);
+      out_desc d;
+      if (out_field(h, f, d)) return -1;   // (the message of window_accumulate: a correction field without the rows)
+      if (win_is_diag(f) && !h->diag) return fail("%s: field %d is a diagnostic, and diagnostics are switched off", who, f);
+    }
+  }
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the table or write the records
+  win_cancel(h, sched);
+  auto &w = h->wsched[sched];
+  if (nfields > 0) {
+    w.origin = nt_origin; w.period = period; w.nrec = nrec;
+    for (int i = 0; i < nfields; ++i) {
+      out_desc d;
+      out_field(h, fields[i], d);
+      const int ld_out = d.nlev == 1 ? 1 : h->ld;
+      const size_t bytes = (size_t)nrec * (size_t)__builtin_popcount(ops[i]) * (size_t)h->ncol * (size_t)ld_out * sizeof(double);
+      double *p = nullptr;
+      if (bytes > 0) {
+        const hipError_t e = hipMalloc(&p, bytes);
+        if (e != hipSuccess) {
+          (void)hipGetLastError();
+          win_cancel(h, sched);
+          win_table(h);
+          return fail("%s: cannot allocate %zu bytes of device memory for the %d records of field %d (%s); the schedule is "
+                      "not set", who, bytes, nrec, fields[i], hipGetErrorString(e));
+        }
+      }
+      w.fields.push_back(fields[i]); w.ops.push_back(ops[i]); w.ld_out.push_back(ld_out); w.acc.push_back(p);
+    }
+  }
+  return win_table(h);
+}
+
+// the record's plane of one field and operation on the device (the mean formed into the staging buffer), or an error
+// that names the record's steps
+static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, int field, int op,
+                      const double **src_out, int *ld_out, int *nlev)
+{
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  const auto &w = h->wsched[sched];
+  if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
+  if (op < 0 || op > 3) return fail("%s: op %d (0 mean, 1 min, 2 max, 3 last)", who, op);
+  size_t i = 0;
+  while (i < w.fields.size() && w.fields[i] != field) ++i;
+  if (i == w.fields.size()) return fail("%s: field %d is not in schedule %d", who, field, sched);
+  if (!((w.ops[i] >> op) & 1u)) return fail("%s: schedule %d keeps no op %d of field %d (operations 0x%x)", who, sched, op, field, w.ops[i]);
+  if (rec < 0) return fail("%s: record %lld", who, (long long)rec);
+  const long long a = w.origin + rec * w.period, b = a + w.period - 1;
+  if (w.first_nt >= 0 && a < w.first_nt)
+    return fail("%s: record %lld of schedule %d (steps %lld..%lld) is incomplete: its first steps ran before the schedule "
+                "was set (its first step was %lld)", who, (long long)rec, sched, a, b, (long long)w.first_nt);
+  if (rec < w.first_kept) return fail("%s: record %lld of schedule %d (steps %lld..%lld) has been released", who, (long long)rec, sched, a, b);
+  if (w.next_nt < 0 || b >= w.next_nt)
+    return fail("%s: record %lld of schedule %d (steps %lld..%lld) is incomplete: steps have run up to %lld", who,
+                (long long)rec, sched, a, b, (long long)(w.next_nt < 0 ? w.origin - 1 : w.next_nt - 1));
+  out_desc d;
+  if (out_field(h, field, d)) return -1;
+  *ld_out = w.ld_out[i];
+  *nlev = d.nlev;
+  *src_out = nullptr;
+  if (h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  const size_t n = (size_t)h->ncol * w.ld_out[i];
+  const int j = __builtin_popcount(w.ops[i] & ((1u << op) - 1u));
+  const double *src = w.acc[i] + ((size_t)(rec % w.nrec) * (size_t)__builtin_popcount(w.ops[i]) + (size_t)j) * n;
+  if (op == 0) {   // the mean: window_fetch's sum / count, the count a whole window's
+    if (ensure_stage(h, n)) return -1;
+    HIPCHK(mckpp_launch_window_mean(src, h->d_stage, n, (double)w.period, h->stream));
+    src = h->d_stage;
+  }
+  *src_out = src;
+  return 0;
+}
+
+int mckpp_hip_window_record_fetch(mckpp_hip_handle h, int sched, int64_t rec, int field, int op, double *out)
+{
+  const char *who = "mckpp_hip_window_record_fetch";
+  if (!h) return fail("%s: null handle", who);
+  if (!out) return fail("%s: null argument", who);
+  const double *src = nullptr;
+  int ld_out = 0, nlev = 0;
+  if (win_record(h, who, sched, rec, field, op, &src, &ld_out, &nlev)) return -1;
+  if (h->ncol == 0) return 0;
+  if (down_rows(h, src, ld_out, 0, nlev, out)) return -1;
+  return xfer_finish(h);
+}
+
+int mckpp_hip_window_record_release(mckpp_hip_handle h, int sched, int64_t upto_rec)
+{
+  const char *who = "mckpp_hip_window_record_release";
+  if (!h) return fail("%s: null handle", who);
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  auto &w = h->wsched[sched];
+  if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
+  const int64_t lc = win_last_complete(w);
+  if (upto_rec > lc)
+    return fail("%s: record %lld of schedule %d (steps %lld..%lld) is not complete (complete are up to record %lld)", who,
+                (long long)upto_rec, sched, (long long)(w.origin + upto_rec * w.period),
+                (long long)(w.origin + (upto_rec + 1) * w.period - 1), (long long)lc);
+  if (upto_rec + 1 > w.first_kept) w.first_kept = upto_rec + 1;
+  return 0;
+}
+
+int mckpp_hip_window_records(mckpp_hip_handle h, int sched, int64_t *first_kept, int64_t *last_complete)
+{
+  const char *who = "mckpp_hip_window_records";
+  if (!h) return fail("%s: null handle", who);
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  const auto &w = h->wsched[sched];
+  if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
+  if (first_kept) *first_kept = w.first_kept;
+  if (last_complete) *last_complete = win_last_complete(w);
+  return 0;
 }
 
 int mckpp_hip_status(mckpp_hip_handle h, int32_t *per_col, int64_t *n_flagged, int32_t *npasses)
@@ -1945,6 +2216,39 @@ int mckpp_hip_multi_window_fetch(mckpp_hip_multi_handle m, int field, int op, do
     if (window_prepare(m->ctx[d], field, op, &src[d], &ld_out, &nlev)) return -1;
   if (multi_gather_rows(m, 0, src, ld_out, 0, nlev, out)) return -1;
   return multi_gather_finish(m);
+}
+
+// output windows inside the step launches: every shard keeps its columns' records (and the same bookkeeping: the
+// shards run the same steps); a record is gathered into 3-D order like window_fetch's fields
+int mckpp_hip_multi_window_schedule(mckpp_hip_multi_handle m, int sched, int nt_origin, int period, int nrec,
+                                    const int32_t *fields, const uint32_t *ops, int32_t nfields)
+{
+  if (!m) return fail("mckpp_hip_multi_window_schedule: null handle");
+  MULTI_EACH(mckpp_hip_window_schedule(x, sched, nt_origin, period, nrec, fields, ops, nfields));
+}
+int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, double *out)
+{
+  const char *who = "mckpp_hip_multi_window_record_fetch";
+  if (!m) return fail("%s: null handle", who);
+  if (!out) return fail("%s: null argument", who);
+  if (m->npts <= 0) return fail("%s: nothing uploaded", who);
+  const int ndev = (int)m->ctx.size();
+  std::vector<const double *> src(ndev, nullptr);
+  int ld_out = 0, nlev = 0;
+  for (int d = 0; d < ndev; ++d)
+    if (win_record(m->ctx[d], who, sched, rec, field, op, &src[d], &ld_out, &nlev)) return -1;
+  if (multi_gather_rows(m, 0, src, ld_out, 0, nlev, out)) return -1;
+  return multi_gather_finish(m);
+}
+int mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle m, int sched, int64_t upto_rec)
+{
+  if (!m) return fail("mckpp_hip_multi_window_record_release: null handle");
+  MULTI_EACH(mckpp_hip_window_record_release(x, sched, upto_rec));
+}
+int mckpp_hip_multi_window_records(mckpp_hip_multi_handle m, int sched, int64_t *first_kept, int64_t *last_complete)
+{
+  if (!m) return fail("mckpp_hip_multi_window_records: null handle");
+  return mckpp_hip_window_records(m->ctx[0], sched, first_kept, last_complete);
 }
 
 // one file per shard: <path>.<d>of<ndev>

@@ -20,7 +20,9 @@ program kpp_driver
   use mckpp_hip_session, only: mckpp_hip_ndevices, mckpp_hip_device_list, mckpp_hip_gather_field, mckpp_hip_sync_host, &
                                mckpp_hip_output_mask, mckpp_hip_host_behind, &
                                mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select, &
-                               mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch
+                               mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch, &
+                               mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, &
+                               mckpp_hip_all_window_record_release
   implicit none
   character(len=512) :: fin, fout
   integer :: u, nt, nsteps, ncol, nlev, use_1d, ipt, flags
@@ -46,6 +48,8 @@ program kpp_driver
   !           without it every call of mckpp_physics_driver leaves all of kpp_3d_fields current, as the reference does
   !        128 itermax = 4 (columns run beyond itermax+1 passes: the reference's located warnings on stderr) with
   !           dlon = 0.5 ipt, dlat = -60 + 0.25 ipt
+  !        256 flag 32's output (mean hmix, maximum T) from ONE forced run under an output schedule of period 2: every
+  !           record of the run (appended, record after record)
   flags = hdr(6)
   if (iand(flags, 64) /= 0) mckpp_hip_output_mask = MCKPP_F_SCALARS
   ! hdr(7) > 0: that many device shards; hdr(8) = 1 puts them all on HIP device 0 (one-GPU rehearsal of the
@@ -91,7 +95,7 @@ program kpp_driver
 
   kpp_3d_fields%sflux(:, 1:6, 5, 0) = sf6
   call cpu_time(t0)
-  if (iand(flags, 48) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
+  if (iand(flags, 48 + 256) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
     allocate (series(ncol, 8, 1))
     series(:, 1, 1) = 0.01_c_double; series(:, 2, 1) = 0; series(:, 3, 1) = 200; series(:, 4, 1) = 0
     series(:, 5, 1) = -150; series(:, 6, 1) = 0; series(:, 7, 1) = 6e-5_c_double; series(:, 8, 1) = 0
@@ -103,6 +107,10 @@ program kpp_driver
         call mckpp_hip_all_run_forced(nt, 1, nsteps + 1)
         call mckpp_hip_all_window_accumulate()
       end do
+    else if (iand(flags, 256) /= 0) then   ! the same output, accumulated inside the one forced run
+      call mckpp_hip_all_window_schedule(0, 1, 2, nsteps / 2, [4_c_int32_t, 2_c_int32_t], &   ! MCKPP_OUT_HMIX, MCKPP_OUT_T
+                                         [1_c_int32_t, 4_c_int32_t])                          ! MCKPP_WIN_MEAN, MCKPP_WIN_MAX
+      call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)
     else
       call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)   ! one flux update (step 1), as ndtocn > nsteps
     end if
@@ -129,7 +137,7 @@ program kpp_driver
   write (*, '(a,3es14.6)') 'kpp_driver: hmix min/mean/max ', minval(kpp_3d_fields%hmix, kpp_3d_fields%run_physics), &
         sum(kpp_3d_fields%hmix)/max(1, count(kpp_3d_fields%run_physics)), maxval(kpp_3d_fields%hmix)
 
-  if (iand(flags, 64 + 48) == 0 .and. mckpp_hip_host_behind() /= 0) then   ! the default mask: nothing may be stale
+  if (iand(flags, 64 + 48 + 256) == 0 .and. mckpp_hip_host_behind() /= 0) then   ! the default mask: nothing may be stale
     write (0, '(a,i0)') 'kpp_driver: kpp_3d_fields is behind the device after mckpp_physics_driver: ', mckpp_hip_host_behind()
     error stop 2
   end if
@@ -153,6 +161,17 @@ program kpp_driver
     call mckpp_hip_all_window_fetch(4, 0, vm_h)
     call mckpp_hip_all_window_fetch(2, 2, vm_difm)
     write (u) vm_h, vm_difm
+    deallocate (vm_h, vm_difm)
+  end if
+  if (iand(flags, 256) /= 0) then
+    allocate (vm_h(ncol), vm_difm(ncol, nzp1))
+    do nt = 0, hdr(3) / 2 - 1
+      vm_h = -1; vm_difm = -1
+      call mckpp_hip_all_window_record_fetch(0, nt, 4, 0, vm_h)
+      call mckpp_hip_all_window_record_fetch(0, nt, 2, 2, vm_difm)
+      write (u) vm_h, vm_difm
+    end do
+    call mckpp_hip_all_window_record_release(0, hdr(3) / 2 - 1)
     deallocate (vm_h, vm_difm)
   end if
   if (iand(flags, 4) /= 0) then

@@ -20,6 +20,9 @@ module mckpp_hip_binding
     MCKPP_OUT_NSOLAR_IN = 29, MCKPP_OUT_PMINUSE_IN = 30, MCKPP_OUT_FREEZE_FLAG = 31, MCKPP_OUT_COMP_FLAG = 32, &
     MCKPP_OUT_DAMPU_FLAG = 33, MCKPP_OUT_DAMPV_FLAG = 34
   integer(c_int), parameter :: MCKPP_OP_MEAN = 0, MCKPP_OP_MIN = 1, MCKPP_OP_MAX = 2, MCKPP_OP_INSTANT = 3
+  ! operations of an output schedule (mckpp_hip_window_schedule): bit 2**op of a record fetch's op
+  integer(c_int32_t), parameter :: MCKPP_WIN_MEAN = 1, MCKPP_WIN_MIN = 2, MCKPP_WIN_MAX = 4, MCKPP_WIN_LAST = 8
+  integer(c_int), parameter :: MCKPP_OP_LAST = 3
 
   type, bind(C) :: mckpp_const_c
     integer(c_int32_t) :: nz, nztmax, nsflxs, njdt, itermax
@@ -295,6 +298,34 @@ module mckpp_hip_binding
       type(c_ptr), value :: handle
       integer(c_int), value :: field, op
       real(c_double), intent(inout) :: out(*)
+      integer(c_int) :: rc
+    end function
+    ! output windows accumulated inside the step launches (mckpp_hip_window_schedule of include/mckpp_hip.h)
+    function mckpp_hip_multi_window_schedule(handle, sched, nt_origin, period, nrec, fields, ops, nfields) &
+        bind(C, name="mckpp_hip_multi_window_schedule") result(rc)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched, nt_origin, period, nrec
+      integer(c_int32_t), intent(in) :: fields(*), ops(*)
+      integer(c_int32_t), value :: nfields
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_window_record_fetch(handle, sched, rec, field, op, out) &
+        bind(C, name="mckpp_hip_multi_window_record_fetch") result(rc)
+      import :: c_int, c_int64_t, c_ptr, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched
+      integer(c_int64_t), value :: rec
+      integer(c_int), value :: field, op
+      real(c_double), intent(inout) :: out(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_window_record_release(handle, sched, upto_rec) &
+        bind(C, name="mckpp_hip_multi_window_record_release") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched
+      integer(c_int64_t), value :: upto_rec
       integer(c_int) :: rc
     end function
     function mckpp_hip_multi_save_restart(handle, path) bind(C, name="mckpp_hip_multi_save_restart") result(rc)

@@ -17,6 +17,7 @@ module mckpp_hip_session
   public :: mckpp_hip_const_view, mckpp_hip_state_view, l2i
   public :: mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select
   public :: mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch
+  public :: mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, mckpp_hip_all_window_record_release
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
   public :: mckpp_hip_host_behind
   public :: mckpp_hip_warnings, mckpp_hip_abort_on_zero_pivot, mckpp_hip_report_warnings, mckpp_hip_column_messages
@@ -347,6 +348,37 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_window_fetch(mckpp_hip_multi_handle, int(field, c_int), int(op, c_int), out), &
                          'mckpp_hip_multi_window_fetch')
   end subroutine mckpp_hip_all_window_fetch
+
+  !> Output windows accumulated inside the step launches (one XIOS <file> of iodef.xml per schedule), so that
+  !! mckpp_hip_all_run_forced can take many steps in one call: schedule `sched` (0..3) keeps nrec records of the
+  !! windows of `period` steps from step nt_origin on, for fields(i) with the operations ops(i) (MCKPP_WIN_MEAN,
+  !! _MIN, _MAX, _LAST); no fields cancels it.  The state goes to the devices first (an upload cancels schedules).
+  subroutine mckpp_hip_all_window_schedule(sched, nt_origin, period, nrec, fields, ops)
+    integer, intent(in) :: sched, nt_origin, period, nrec
+    integer(c_int32_t), intent(in) :: fields(:), ops(:)
+    if (size(ops) /= size(fields)) then
+      write (0, '(a)') 'MCKPP-HIP ERROR in mckpp_hip_all_window_schedule: one operations mask per field'
+      error stop 1
+    end if
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_window_schedule(mckpp_hip_multi_handle, int(sched, c_int), int(nt_origin, c_int), &
+                         int(period, c_int), int(nrec, c_int), fields, ops, int(size(fields), c_int32_t)), &
+                         'mckpp_hip_multi_window_schedule')
+  end subroutine mckpp_hip_all_window_schedule
+  !> record `rec` (0: the window from nt_origin) of schedule `sched`, op 0 mean / 1 min / 2 max / 3 last, into
+  !! out(npts[,nzp1]); land points keep what out held
+  subroutine mckpp_hip_all_window_record_fetch(sched, rec, field, op, out)
+    integer, intent(in) :: sched, rec, field, op
+    real(c_double), intent(inout) :: out(*)
+    call mckpp_hip_check(mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle, int(sched, c_int), int(rec, c_int64_t), &
+                         int(field, c_int), int(op, c_int), out), 'mckpp_hip_multi_window_record_fetch')
+  end subroutine mckpp_hip_all_window_record_fetch
+  !> the records of `sched` up to and including upto_rec are written out: their ring slots are free again
+  subroutine mckpp_hip_all_window_record_release(sched, upto_rec)
+    integer, intent(in) :: sched, upto_rec
+    call mckpp_hip_check(mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle, int(sched, c_int), &
+                         int(upto_rec, c_int64_t)), 'mckpp_hip_multi_window_record_release')
+  end subroutine mckpp_hip_all_window_record_release
 
   !> Restart set of all devices (src/mckpp_xios_io.F90:368-465): one file per shard, <path>.<shard>of<ndevices>
   subroutine mckpp_hip_all_save_restart(path)
