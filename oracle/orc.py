@@ -1,6 +1,7 @@
 """ctypes front-end for the CPU oracle (oracle/liboracle.so) and, when built,
 the compiled reference pieces (oracle/_ref/libmckpp_ref.so: EOS, cpsw, z121;
-oracle/_ref/libmckpp_ref_step{,_pexp}.so: the reference's whole physics step).
+oracle/_ref/libmckpp_ref_step{,_pexp}.so: the reference's whole physics step, and its
+own init, flux assembly and time loop served from an in-memory flux file).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, bench.py's cpu_baseline leg and
 __graft_entry__.smoke().  The product package never imports this module.
@@ -29,7 +30,11 @@ def build(force=False):
         os.path.getmtime(LIB) < os.path.getmtime(os.path.join(HERE, "mckpp_oracle.c"))
     ):
         subprocess.check_call(["make", "-C", HERE, "liboracle.so"], stdout=subprocess.DEVNULL)
-    if os.path.isdir("/root/reference/src") and not all(map(os.path.exists, [REFLIB] + list(REFSTEPLIB.values()))):
+    own = [os.path.join(HERE, f) for f in ("ref_step_shim.F90", "netcdf_standin.F90", "Makefile")]
+    libs = [REFLIB] + list(REFSTEPLIB.values())
+    if os.path.isdir("/root/reference/src") and not (
+            all(map(os.path.exists, libs))
+            and min(map(os.path.getmtime, REFSTEPLIB.values())) >= max(map(os.path.getmtime, own))):
         subprocess.check_call(["make", "-C", HERE, "ref"], stdout=subprocess.DEVNULL)
 
 
@@ -161,9 +166,20 @@ def have_ref_step():
 _ref_step = {}
 
 
-def _ref_step_lib(exp_mode):
+def _ref_step_lib(exp_mode, fresh=False):
+    """The reference library for exp_mode.  fresh: loaded anew, its module variables as at program start (the
+    reference's flux reader allocates its table of file times once per run, src/mckpp_read_fluxes_mod.F90:47)."""
+    if fresh and exp_mode in _ref_step:
+        import _ctypes
+
+        _ctypes.dlclose(_ref_step.pop(exp_mode)._handle)
     if exp_mode not in _ref_step:
         R = C.CDLL(REFSTEPLIB[exp_mode])
+        R.ref_loop_config.argtypes = [C.POINTER(C.c_int), C.c_int, C.POINTER(C.c_double)]
+        R.ref_loop_flux_file.argtypes = [C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]
+        R.ref_loop_init.argtypes = []
+        R.ref_loop_tri.argtypes = [C.POINTER(C.c_double)] * 2
+        R.ref_loop_run.argtypes = [C.c_int, C.c_int]
         R.ref_step_setup.argtypes = [C.c_int, C.c_int, C.POINTER(C.c_int), C.POINTER(C.c_int)] + [C.POINTER(C.c_double)] * 6
         R.ref_step_xfer.restype = C.c_int
         R.ref_step_xfer.argtypes = [C.c_char_p, C.c_int, C.POINTER(C.c_double), C.c_int, C.c_int]
@@ -213,6 +229,90 @@ _REF_SCALARS = ["f", "Ssurf", "Sref", "SSref", "ocdepth", "hmix", "kmix", "uref"
 _REF_INTS = {"old": "old", "newi": "new", "jerlov": "jerlov", "l_initflag": "l_initflag", "l_ocean": "l_ocean"}
 
 
+class _RefFields:
+    """The columns of a Batch in the compiled reference's kpp_3d_fields (after ref_step_setup) and back."""
+
+    def __init__(self, R, const, batch):
+        self.R, self.nz, self.ncol, self.batch = R, const.nz, batch.ncol, batch
+        nz, ncol = self.nz, self.ncol
+        nzp1, nzt = nz + 1, nz + 1
+        self.lay = _ref_layout(nz)
+        full = {"U": (nzp1,), "X": (nzp1,), "U_init": (nzp1,), "Us": (nzp1,), "Xs": (nzp1,), "Rig": (nzp1,),
+                "Shsq": (nzp1,), "dbloc": (nz,), "rho": (nzt + 2,), "cp": (nzt + 2,), "buoy": (nzt + 1,),
+                "swfrac": (nzp1,), "swdk_opt": (nz + 1,), "difm": (nzt + 1,), "difs": (nzt + 1,), "dift": (nzt + 1,),
+                "wU": (nzt + 1,), "wX": (nzt + 1,), "wXNT": (nzt + 1,), "ghat": (nzt,)}
+        for nm in ("tinc_fcorr", "sinc_fcorr", "fcorr_withz", "sfcorr_withz", "scorr", "ocnTcorr", "sal_clim",
+                   "ocnT_clim"):
+            full[nm] = (nzp1,)
+        self.arrays = {r: np.zeros((ncol,) + lv + _REF_SHAPES.get(r, ())) for r, lv in full.items()}
+
+    def xfer(self, name, arr, put):
+        a = np.asfortranarray(arr, dtype=np.float64)
+        flat = a.reshape(-1, order="F")
+        rc = self.R.ref_step_xfer(name.encode(), len(name), _dp(flat), flat.size, 1 if put else 0)
+        if rc != 0:
+            raise RuntimeError(f"ref_step_xfer({name}): {rc}")
+        return flat.reshape(a.shape, order="F")
+
+    def put(self, run_physics=None, bottom_temp=None):
+        batch, ncol = self.batch, self.ncol
+        for b, (r, comp, lo, n) in self.lay.items():
+            self.arrays[r][(slice(None), slice(None)) + comp] = batch.a[b][:, lo:lo + n]
+        for r, a in self.arrays.items():
+            self.xfer(r, a, True)
+        for nm in _REF_SCALARS:
+            self.xfer(nm, batch[nm], True)
+        for b, r in _REF_INTS.items():
+            self.xfer(r, batch[b], True)
+        self.xfer("hmixd", batch["hmixd"], True)
+        self.xfer("nmodeadv", batch["nmodeadv"], True)
+        self.xfer("modeadv", batch["modeadv"].transpose(0, 2, 1), True)
+        self.xfer("advection", batch["advection"].transpose(0, 2, 1), True)
+        self.xfer("run_physics", np.ones(ncol) if run_physics is None else run_physics, True)
+        if bottom_temp is not None:
+            self.xfer("bottom_temp", bottom_temp, True)
+
+    def put_sflux(self, sf):
+        sflux = np.zeros((self.ncol, 9, 5, 2))
+        sflux[:, 0:6, 4, 0] = sf
+        self.xfer("sflux", sflux, True)
+
+    def get_sflux(self):
+        return np.ascontiguousarray(self.xfer("sflux", np.zeros((self.ncol, 9, 5, 2)), False)[:, 0:6, 4, 0])
+
+    def get(self, sflux):
+        """A Batch of what kpp_3d_fields holds now (fields the reference has no counterpart for - talpha, sbeta,
+        status, npasses - stay zero), with `sflux` as its forcing rows."""
+        ob = self.batch.copy()
+        ob["sflux"] = sflux
+        for nm in ("talpha", "sbeta", "status", "npasses"):
+            ob[nm] = 0
+        got = {r: self.xfer(r, a, False) for r, a in self.arrays.items()}
+        for b, (r, comp, lo, n) in self.lay.items():
+            ob.a[b][:, lo:lo + n] = got[r][(slice(None), slice(None)) + comp]
+        for nm in _REF_SCALARS:
+            ob[nm] = self.xfer(nm, np.zeros(self.ncol), False)
+        for b, r in _REF_INTS.items():
+            ob[b] = self.xfer(r, np.zeros(self.ncol), False)
+        ob["hmixd"] = self.xfer("hmixd", np.zeros((self.ncol, 2)), False)
+        return ob
+
+
+def _ref_setup(R, const, ncol, vary_bottom_temp=False, tri=True):
+    """ref_step_setup with the grid, constants and switches of `const`; tri=False hands the reference zeros for
+    tri(:,0:1,1), so that whatever the step then uses is what the reference's own init computed."""
+    c, nz = const.c, const.nz
+    nzp1 = nz + 1
+    sw = (C.c_int * 16)(*([int(getattr(c, k)) for k in _REF_SWITCHES] + [int(bool(vary_bottom_temp))]))
+    iv = (C.c_int * 4)(c.itermax, c.iso_bot, c.dt_uvdamp, c.clim_present)
+    rv = np.array([c.hmixtolfrac, c.dto, c.grav, c.vonk, c.sice, c.iso_thresh])
+    zm, hm = np.ascontiguousarray(const.zm[1:nzp1 + 1]), np.ascontiguousarray(const.hm[1:nzp1 + 1])
+    dm, t0, t1 = (np.ascontiguousarray(a[0:nz + 1]) for a in (const.dm, const.tri0, const.tri1))
+    if not tri:
+        t0, t1 = np.zeros(nz + 1), np.zeros(nz + 1)
+    R.ref_step_setup(nz, ncol, sw, iv, _dp(rv), _dp(zm), _dp(hm), _dp(dm), _dp(t0), _dp(t1))
+
+
 def ref_step(const, batch, forcing, exp_mode=1, ntime0=1, run_physics=None, bottom_temp=None, vary_bottom_temp=False):
     """Run the compiled reference's own mckpp_physics_driver() on the columns of `batch` (left unchanged), one step
     per entry of `forcing` (a list of sflux(1:6) arrays [ncol, 6], set before each step), with the grid, constants
@@ -220,65 +320,76 @@ def ref_step(const, batch, forcing, exp_mode=1, ntime0=1, run_physics=None, bott
     step holding what the reference's kpp_3d_fields carries after it (fields the reference has no counterpart for -
     talpha, sbeta, status, npasses - stay zero)."""
     R = _ref_step_lib(exp_mode)
-    c, nz, ncol = const.c, const.nz, batch.ncol
-    nzp1, nzt = nz + 1, nz + 1
-    sw = (C.c_int * 16)(*([int(getattr(c, k)) for k in _REF_SWITCHES] + [int(bool(vary_bottom_temp))]))
-    iv = (C.c_int * 4)(c.itermax, c.iso_bot, c.dt_uvdamp, c.clim_present)
-    rv = np.array([c.hmixtolfrac, c.dto, c.grav, c.vonk, c.sice, c.iso_thresh])
-    zm, hm = np.ascontiguousarray(const.zm[1:nzp1 + 1]), np.ascontiguousarray(const.hm[1:nzp1 + 1])
-    dm, t0, t1 = (np.ascontiguousarray(a[0:nz + 1]) for a in (const.dm, const.tri0, const.tri1))
-    R.ref_step_setup(nz, ncol, sw, iv, _dp(rv), _dp(zm), _dp(hm), _dp(dm), _dp(t0), _dp(t1))
-
-    def xfer(name, arr, put):
-        a = np.asfortranarray(arr, dtype=np.float64)
-        flat = a.reshape(-1, order="F")
-        rc = R.ref_step_xfer(name.encode(), len(name), _dp(flat), flat.size, 1 if put else 0)
-        if rc != 0:
-            raise RuntimeError(f"ref_step_xfer({name}): {rc}")
-        return flat.reshape(a.shape, order="F")
-
-    lay = _ref_layout(nz)
-    full = {"U": (nzp1,), "X": (nzp1,), "U_init": (nzp1,), "Us": (nzp1,), "Xs": (nzp1,), "Rig": (nzp1,),
-            "Shsq": (nzp1,), "dbloc": (nz,), "rho": (nzt + 2,), "cp": (nzt + 2,), "buoy": (nzt + 1,),
-            "swfrac": (nzp1,), "swdk_opt": (nz + 1,), "difm": (nzt + 1,), "difs": (nzt + 1,), "dift": (nzt + 1,),
-            "wU": (nzt + 1,), "wX": (nzt + 1,), "wXNT": (nzt + 1,), "ghat": (nzt,)}
-    for nm in ("tinc_fcorr", "sinc_fcorr", "fcorr_withz", "sfcorr_withz", "scorr", "ocnTcorr", "sal_clim", "ocnT_clim"):
-        full[nm] = (nzp1,)
-    arrays = {r: np.zeros((ncol,) + lv + _REF_SHAPES.get(r, ())) for r, lv in full.items()}
-    for b, (r, comp, lo, n) in lay.items():
-        arrays[r][(slice(None), slice(None)) + comp] = batch.a[b][:, lo:lo + n]
-    for r, a in arrays.items():
-        xfer(r, a, True)
-    for nm in _REF_SCALARS:
-        xfer(nm, batch[nm], True)
-    for b, r in _REF_INTS.items():
-        xfer(r, batch[b], True)
-    xfer("hmixd", batch["hmixd"], True)
-    xfer("nmodeadv", batch["nmodeadv"], True)
-    xfer("modeadv", batch["modeadv"].transpose(0, 2, 1), True)
-    xfer("advection", batch["advection"].transpose(0, 2, 1), True)
-    xfer("run_physics", np.ones(ncol) if run_physics is None else run_physics, True)
-    if bottom_temp is not None:
-        xfer("bottom_temp", bottom_temp, True)
-    sflux = np.zeros((ncol, 9, 5, 2))
+    _ref_setup(R, const, batch.ncol, vary_bottom_temp)
+    rf = _RefFields(R, const, batch)
+    rf.put(run_physics, bottom_temp)
     out = []
     for i, sf in enumerate(forcing):
-        sflux[:, 0:6, 4, 0] = sf
-        xfer("sflux", sflux, True)
+        rf.put_sflux(sf)
         R.ref_step_run(int(ntime0 + i), 1)
-        ob = batch.copy()
-        ob["sflux"] = sf
-        for nm in ("talpha", "sbeta", "status", "npasses"):
-            ob[nm] = 0
-        got = {r: xfer(r, a, False) for r, a in arrays.items()}
-        for b, (r, comp, lo, n) in lay.items():
-            ob.a[b][:, lo:lo + n] = got[r][(slice(None), slice(None)) + comp]
-        for nm in _REF_SCALARS:
-            ob[nm] = xfer(nm, np.zeros(ncol), False)
-        for b, r in _REF_INTS.items():
-            ob[b] = xfer(r, np.zeros(ncol), False)
-        ob["hmixd"] = xfer("hmixd", np.zeros((ncol, 2)), False)
-        out.append(ob)
+        out.append(rf.get(sf))
+    return out
+
+
+# the flux fields of a record in the order of the in-memory file (oracle/netcdf_standin.F90); a record as
+# mckpp_hip_set_flux_series takes it has `snow` as an eighth row, which the reference's reader never reads
+REF_FLUX_FILE_FIELDS = ("taux", "tauy", "swf", "lwf", "lhf", "shf", "precip")
+_ref_loop_state = {}
+
+
+def ref_flux_file_times(nrec, ndtocn, dto, startt=0.0, spd=86400.0):
+    """Time coordinate of a flux file whose record r (0-based) belongs to steps r*ndtocn + 1 .. (r+1)*ndtocn.
+    The reference's reader wants record `pos` within 0.01*dtsec/spd of time + 0.5*ndtocn*dto/spd (its method 1,
+    src/mckpp_time_control.F90:121-133), and takes pos = NINT((time - times[0]) * spd / (dto*ndtocn)) + 1 (:153-161).
+    With the times exactly at the middle of their intervals that argument is r - 0.5, a tie for NINT which rounding
+    noise decides (and which for r = 0 goes to -1, one entry before the array); the times here lie a quarter of
+    that tolerance before the middle, which makes the argument r - 0.5 + 0.0025/ndtocn and NINT of it r.  The reader
+    also refuses a time to read beyond the file's last one (:95-109), which the middle of the last interval then is:
+    ref_init ends the file with one more record, of NaN, that no step of the run reads."""
+    mid = startt + (np.arange(nrec) + 0.5) * ndtocn * dto / spd
+    return mid - 0.0025 * dto / spd
+
+
+def ref_init(const, batch, exp_mode=1, run_physics=None, flux_records=None, ndtocn=1, startt=0.0, l_rest=0,
+             flsn=334000.0, el=2.5e6, spd=86400.0):
+    """The compiled reference's own start of a run on the columns of `batch` (raw profiles, left unchanged):
+    mckpp_initialize_time(), mckpp_initialize_fluxes() and mckpp_initialize_ocean_model(), the reference computing
+    tri(:,0:1,1) itself.  `flux_records` [nrec, 8 or 7, ncol] (the rows of mckpp_hip_set_flux_series; record r is for
+    steps r*ndtocn+1 ..) become the in-memory flux file the reference's reader is served from; None is a run without a
+    flux file (l_fluxdata = .FALSE.).  l_ocean is the batch's, run_physics as given.  Returns (Batch after init,
+    tri0, tri1); ref_loop(...) then steps this run, on the same exp_mode."""
+    R = _ref_step_lib(exp_mode, fresh=True)
+    ncol = batch.ncol
+    _ref_setup(R, const, ncol, tri=False)
+    rf = _RefFields(R, const, batch)
+    rf.put(run_physics)
+    lv = (C.c_int * 2)(int(flux_records is not None), int(bool(l_rest)))
+    rv = np.array([flsn, el, startt, spd, const.c.dto, 100.0, -10.0])
+    R.ref_loop_config(lv, int(ndtocn), _dp(rv))
+    if flux_records is not None:
+        rec = np.asarray(flux_records, dtype=np.float64)
+        assert rec.ndim == 3 and rec.shape[1] in (7, 8) and rec.shape[2] == ncol
+        rec = np.concatenate([rec[:, 0:7, :], np.full((1, 7, ncol), np.nan)])     # (see ref_flux_file_times)
+        times = ref_flux_file_times(rec.shape[0], ndtocn, const.c.dto, startt, spd)
+        # flux(nx, ny = 1, ntimes, 7) in Fortran order: column fastest, then record, then field
+        flat = np.ascontiguousarray(rec.transpose(1, 0, 2)).reshape(-1)
+        R.ref_loop_flux_file(rec.shape[0], _dp(times), _dp(flat))
+    R.ref_loop_init()
+    t0, t1 = np.zeros(const.nz + 1), np.zeros(const.nz + 1)
+    R.ref_loop_tri(_dp(t0), _dp(t1))
+    _ref_loop_state[exp_mode] = rf
+    return rf.get(rf.get_sflux()), t0, t1
+
+
+def ref_loop(nt_first, n, exp_mode=1):
+    """Steps nt_first .. nt_first+n-1 of the run ref_init started, by the body of the reference's time loop
+    (mckpp_update_time, mckpp_fluxes at the update steps - the record its own mckpp_get_update_time picks -,
+    mckpp_physics_driver).  Returns one Batch per step, its sflux rows what the reference holds after the step."""
+    R, rf = _ref_step_lib(exp_mode), _ref_loop_state[exp_mode]
+    out = []
+    for nt in range(nt_first, nt_first + n):
+        R.ref_loop_run(int(nt), 1)
+        out.append(rf.get(rf.get_sflux()))
     return out
 
 

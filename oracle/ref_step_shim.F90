@@ -15,6 +15,18 @@
 !                    mckpp_physics_lookup for the wmt / wst tables;
 !   ref_step_xfer    copies one 3D field in or out by name (Fortran layout, npts fastest);
 !   ref_step_run     runs mckpp_physics_driver() for nsteps steps (ntime = ntime0 ...).
+! and, for the reference's own init, flux assembly and time loop (oracle/orc.py: ref_init, ref_loop), after a
+! ref_step_setup that was handed tri0 = tri1 = 0:
+!   ref_loop_config    sets what those routines read beyond the step's (l_fluxdata, l_rest, flsn, el, ndtocn,
+!                      startt, spd, dtsec, forcing_file, dlon, dlat, L_RESTART = .false.);
+!   ref_loop_flux_file registers the flux records as the in-memory file behind oracle/netcdf_standin.F90, under
+!                      the name forcing_file holds, on the longitudes and the latitude ref_loop_config set;
+!   ref_loop_init      runs mckpp_initialize_time(), mckpp_initialize_fluxes(), mckpp_initialize_ocean_model()
+!                      (src/mckpp_ocean_model_3D.F90:29, src/mckpp_initialize_fields_mod.F90:129-133);
+!   ref_loop_tri       reads back tri(:,0,1), tri(:,1,1) as the reference's init computed them;
+!   ref_loop_run       the body of the reference's time loop (src/mckpp_ocean_model_3D.F90:38-58 without the
+!                      boundary update and the output) for steps nt_first .. nt_first + n - 1, written here in
+!                      that order and calling the reference's routines only.
 !
 ! Compiled with -fdefault-real-8, so REAL == c_double.
 
@@ -258,5 +270,73 @@ contains
       call mckpp_physics_driver()
     end do
   end subroutine ref_step_run
+
+  ! lv(1:2) = l_fluxdata l_rest;  rv(1:7) = flsn el startt spd dtsec lon0 lat0
+  ! (column i lies at longitude lon0 + i - 1 on the one latitude lat0)
+  subroutine ref_loop_config(lv, ndtocn_in, rv) bind(C, name="ref_loop_config")
+    integer(c_int), intent(in) :: lv(2)
+    integer(c_int), value :: ndtocn_in
+    real(c_double), intent(in) :: rv(7)
+    integer :: i
+    kpp_const_fields%l_fluxdata = lv(1) /= 0
+    kpp_const_fields%l_rest = lv(2) /= 0
+    kpp_const_fields%L_RESTART = .false.
+    kpp_const_fields%ndtocn = ndtocn_in
+    kpp_const_fields%flsn = rv(1)
+    kpp_const_fields%el = rv(2)
+    kpp_const_fields%startt = rv(3)
+    kpp_const_fields%spd = rv(4)
+    kpp_const_fields%dtsec = rv(5)
+    kpp_const_fields%forcing_file = 'ref_loop_fluxes.nc'
+    do i = 1, npts
+      kpp_3d_fields%dlon(i) = rv(6) + (i - 1)
+    end do
+    kpp_3d_fields%dlat = rv(7)
+  end subroutine ref_loop_config
+
+  ! times(1:ntimes) and flux(npts, 1, ntimes, 7) = taux tauy swf lwf lhf shf precip (copied by the stand-in)
+  subroutine ref_loop_flux_file(ntimes, times, flux) bind(C, name="ref_loop_flux_file")
+    use netcdf, only: standin_register, standin_clear
+    integer(c_int), value :: ntimes
+    real(c_double), intent(in) :: times(ntimes), flux(nx, ny, ntimes, 7)
+    if (ntimes <= 0) then
+      call standin_clear()
+    else
+      call standin_register(trim(kpp_const_fields%forcing_file), nx, ny, ntimes, kpp_3d_fields%dlon(1:nx), &
+                            kpp_3d_fields%dlat(1:1), times, flux)
+    end if
+  end subroutine ref_loop_flux_file
+
+  subroutine ref_loop_init() bind(C, name="ref_loop_init")
+    use mckpp_time_control, only: mckpp_initialize_time
+    use mckpp_fluxes_mod, only: mckpp_initialize_fluxes
+    use mckpp_initialize_ocean, only: mckpp_initialize_ocean_model
+    use mckpp_timer, only: mckpp_initialize_timers
+    call mckpp_initialize_timers()
+    call mckpp_initialize_time()
+    call mckpp_initialize_fluxes()
+    call mckpp_initialize_ocean_model()
+  end subroutine ref_loop_init
+
+  subroutine ref_loop_tri(tri0, tri1) bind(C, name="ref_loop_tri")
+    real(c_double), intent(out) :: tri0(0:nz), tri1(0:nz)
+    tri0 = kpp_const_fields%tri(0:nz, 0, 1)
+    tri1 = kpp_const_fields%tri(0:nz, 1, 1)
+  end subroutine ref_loop_tri
+
+  subroutine ref_loop_run(nt_first, n) bind(C, name="ref_loop_run")
+    use mckpp_time_control, only: mckpp_update_time
+    use mckpp_fluxes_mod, only: mckpp_fluxes
+    use mckpp_physics_driver_mod, only: mckpp_physics_driver
+    use mckpp_timer, only: mckpp_initialize_timers
+    integer(c_int), value :: nt_first, n
+    integer :: nt
+    call mckpp_initialize_timers()
+    do nt = nt_first, nt_first + n - 1
+      call mckpp_update_time(nt)
+      if (mod(nt - 1, kpp_const_fields%ndtocn) == 0) call mckpp_fluxes()
+      call mckpp_physics_driver()
+    end do
+  end subroutine ref_loop_run
 
 end module ref_step_shim
