@@ -606,6 +606,7 @@ typedef struct {
   int modeadv[ORC_MAXMODEADV + 1][3];
   double advection[ORC_MAXMODEADV + 1][3];
   int status, npasses;
+  int paths;                           /* ORC_PATH_* bits of this step (test bookkeeping, read by nothing) */
   /* scratch */
   double *dVsq, *Ritop, *alphaDT, *betaDS;
   double *blmc[4];
@@ -717,6 +718,7 @@ static void ddmix(const orc_const *c, orc_col *q, int km)
       diffdd = dsfmax * diffdd * diffdd * diffdd;
       q->dift[ki] = q->dift[ki] + diffdd * 0.8 / Rrho;
       q->difs[ki] = q->difs[ki] + diffdd;
+      q->paths |= ORC_PATH_DD_FINGER;
     } else if ((aDT < 0.0) && (bDS < 0.0) && (aDT < bDS)) { /* :39-48 */
       double Rrho = aDT / bDS;
       double diffdd = 1.5e-6 * 9.0 * 0.101 * orc_exp(c, 4.6 * orc_exp(c, -0.54 * (1 / Rrho - 1)));
@@ -724,8 +726,23 @@ static void ddmix(const orc_const *c, orc_col *q, int km)
       if (Rrho > 0.5) prandtl = (1.85 - 0.85 / Rrho) * Rrho;
       q->dift[ki] = q->dift[ki] + diffdd;
       q->difs[ki] = q->difs[ki] + prandtl * diffdd;
+      q->paths |= ORC_PATH_DD_DIFFCONV;
     }
   }
+}
+
+/* ORC_PATH_HBL_* of the hmin that becomes hbl (bldepth :161, or :175 when `second`, which leaves hekman out): the
+ * sea floor where -ocdepth lies strictly below the others, else whichever of them is the minimum */
+static int hbl_winner(double hri, double hmonob, double hekman, double floor, int second)
+{
+  int p = second ? ORC_PATH_HBL_SECOND_MIN : 0;
+  double others = fmin2(hri, hmonob);
+  if (!second) others = fmin2(others, hekman);
+  if (floor < others) return p | ORC_PATH_HBL_SEAFLOOR;
+  if (hri == others) p |= ORC_PATH_HBL_RI;
+  if (hmonob == others) p |= ORC_PATH_HBL_MONOB;
+  if (!second && hekman == others) p |= ORC_PATH_HBL_EKMAN;
+  return p;
 }
 
 /* ------------------------------------------------------------------------
@@ -742,7 +759,7 @@ static void bldepth(const orc_const *c, orc_col *q, int ntime, int km, int kmp1,
   double Rib[3], dmo[3];
   double bfsfc = 0, stable = 0, sigma = 0, caseA = 0, wm, ws;
   double Vtc = cv * sqrt(0.2 / cs / epsilon) / (c->vonk * c->vonk) / Ricr;  /* :91 */
-  int ka = 1, ku = 2;
+  int ka = 1, ku = 2, hit = ORC_PATH_HBL_NO_HIT;
   Rib[ka] = 0.0;                                          /* :99 */
   dmo[ka] = -zm[kmp1];
   int kbl = km;
@@ -778,14 +795,16 @@ static void bldepth(const orc_const *c, orc_col *q, int ntime, int km, int kmp1,
       double hekman = fekman * hek - (1. - fekman) * zm[kmp1];              /* :158 */
       double hmin = fmin2(fmin2(fmin2(hri, hmonob), hekman), -q->ocdepth);  /* :161 */
       if (hmin < -zm[kl]) {                                                 /* :162 */
+        int second = 0;
         if (!q->l_initflag) {                                               /* :173-180 */
           if (hmin < -zm[kl - 1]) {
             double hmin2 = fmin2(fmin2(hri, hmonob), -q->ocdepth);
-            if (hmin2 < -zm[kl]) hmin = hmin2;
+            if (hmin2 < -zm[kl]) { hmin = hmin2; second = 1; }
           }
         }
         hbl = hmin;                                                         /* :182-183 */
         kbl = kl;
+        hit = hbl_winner(hri, hmonob, hekman, -q->ocdepth, second);
       }
     }
     int ksave = ka;                                       /* :188-190 */
@@ -797,6 +816,7 @@ static void bldepth(const orc_const *c, orc_col *q, int ntime, int km, int kmp1,
   stable = 0.5 + fsign(0.5, bfsfc);                       /* :196 */
   bfsfc = bfsfc + stable * epsln;                         /* :197 */
   caseA = 0.5 + fsign(0.5, -zm[kbl] - 0.5 * c->hm[kbl] - hbl); /* :201 */
+  q->paths |= hit;
   *hbl_o = hbl; *bfsfc_o = bfsfc; *stable_o = stable; *caseA_o = caseA; *kbl_o = kbl;
 }
 
@@ -1224,6 +1244,7 @@ static void ocnstep(const orc_const *c, orc_col *q, int ntime)
             continue;
           } else {
             if (hmixn > hmixe) {
+              q->paths |= ORC_PATH_ITER_DEEPER_AT_ITERMAX;
               hmixe = hmixn;
               kmixe = kmixn;
               continue;
@@ -1238,6 +1259,7 @@ static void ocnstep(const orc_const *c, orc_col *q, int ntime)
     for (int k = 1; k <= NZ; k++) {                       /* :201-207 */
       if (fabs(q->U[1][k]) >= 10 || fabs(q->U[2][k]) >= 10 ||
           fabs(q->X[1][k] - q->X[1][k + 1]) >= 10) {
+        q->paths |= (fabs(q->U[1][k]) >= 10 || fabs(q->U[2][k]) >= 10) ? ORC_PATH_TRAP_U : ORC_PATH_TRAP_TJUMP;
         q->comp_flag = 1;
         q->f = q->f * 1.01;
       }
@@ -1253,6 +1275,7 @@ static void ocnstep(const orc_const *c, orc_col *q, int ntime)
       for (int k = 1; k <= 4; k++) {
         rmsd[k] = sqrt(rmsd[k]);
         if (rmsd[k] >= rmsd_threshold[k]) {
+          q->paths |= ORC_PATH_TRAP_RMS_U << (k - 1);
           q->comp_flag = 1;
           q->f = q->f * 1.01;
         }
@@ -1414,7 +1437,7 @@ int orc_batch_set(orc_batch *b, const char *name, void *ptr)
   F(U) F(V) F(T) F(S) F(Us0) F(Us1) F(Vs0) F(Vs1) F(Ts0) F(Ts1) F(Ss0) F(Ss1)
   F(U_init) F(V_init) F(f) F(Ssurf) F(Sref) F(SSref) F(ocdepth) F(sflux) F(hmixd)
   F(hmix) F(kmix) F(uref) F(vref) F(Tref) F(reset_flag) F(dampu_flag) F(dampv_flag)
-  F(freeze_flag) F(fcorr) F(old) F(newi) F(jerlov) F(l_initflag) F(l_ocean) F(status) F(npasses)
+  F(freeze_flag) F(fcorr) F(old) F(newi) F(jerlov) F(l_initflag) F(l_ocean) F(status) F(npasses) F(paths)
   F(swfrac) F(swdk_opt) F(rho) F(cp) F(buoy) F(talpha) F(sbeta) F(difm) F(difs) F(dift)
   F(ghat) F(wU1) F(wU2) F(wX1) F(wX2) F(wX3) F(wXNT1) F(Rig) F(dbloc) F(Shsq)
   F(tinc_fcorr) F(sinc_fcorr) F(ocnTcorr) F(scorr) F(relax_sst) F(SST0) F(fcorr_twod)
@@ -1486,6 +1509,7 @@ static void gather(const orc_const *c, const orc_batch *b, long col, orc_col *q)
   q->l_ocean = b->l_ocean ? b->l_ocean[col] : 1;
   q->status = 0;
   q->npasses = 0;
+  q->paths = 0;
   q->rhoh2o = 0.0;
   for (int i = 1; i <= 2; i++) {
     q->nmodeadv[i] = b->nmodeadv ? b->nmodeadv[col * 2 + (i - 1)] : 0;
@@ -1527,7 +1551,7 @@ static void scatter(const orc_const *c, orc_batch *b, long col, const orc_col *q
   STS(dampu_flag, q->dampu_flag); STS(dampv_flag, q->dampv_flag); STS(freeze_flag, q->freeze_flag);
   STS(fcorr, q->fcorr);
   STS(old, q->old); STS(newi, q->newi); STS(l_initflag, q->l_initflag);
-  STS(status, q->status); STS(npasses, q->npasses);
+  STS(status, q->status); STS(npasses, q->npasses); STS(paths, q->paths);
 }
 
 static int pick_threads(int nthreads)

@@ -43,6 +43,24 @@ extern "C" {
 #define ORC_ST_FAILED       8   /* ocnstep_mod.F90:229-236: 10 retries spent */
 #define ORC_ST_DODGY_OLDNEW 16  /* ocnstep_mod.F90:93-102                    */
 
+/* paths word: which branch of the physics a column took during its step, OR-ed over all its passes and retries
+ * (cleared when the column is loaded).  Test bookkeeping only: nothing reads it, no result depends on it. */
+#define ORC_PATH_HBL_SEAFLOOR    0x0001  /* bldepth :161/:175: -ocdepth strictly below the others in the hmin that became hbl */
+#define ORC_PATH_HBL_SECOND_MIN  0x0002  /* bldepth :175-176: hmin = hmin2 taken */
+#define ORC_PATH_HBL_NO_HIT      0x0004  /* bldepth left with kbl = km: no level hit */
+#define ORC_PATH_HBL_MONOB       0x0008  /* the winning hmin was the Monin-Obukhov depth ... */
+#define ORC_PATH_HBL_EKMAN       0x0010  /* ... the Ekman depth ... */
+#define ORC_PATH_HBL_RI          0x0020  /* ... the bulk Richardson depth */
+#define ORC_PATH_TRAP_U          0x0040  /* ocnstep :202: |U| or |V| >= 10 at a level */
+#define ORC_PATH_TRAP_TJUMP      0x0080  /* ocnstep :203: |T(k) - T(k+1)| >= 10 alone */
+#define ORC_PATH_TRAP_RMS_U      0x0100  /* ocnstep :208-227: the rms change of U reached its threshold */
+#define ORC_PATH_TRAP_RMS_V      0x0200
+#define ORC_PATH_TRAP_RMS_T      0x0400
+#define ORC_PATH_TRAP_RMS_S      0x0800
+#define ORC_PATH_ITER_DEEPER_AT_ITERMAX 0x1000  /* ocnstep :176-181: iterating on past itermax because hmixn > hmixe */
+#define ORC_PATH_DD_FINGER       0x2000  /* ddmix :31-36 at some level */
+#define ORC_PATH_DD_DIFFCONV     0x4000  /* ddmix :39-48 at some level */
+
 typedef struct {
   int nz;               /* layers; nzp1 = nz + 1 grid points */
   int itermax;          /* initialize_namelist_mod.F90:31 (200) */
@@ -103,6 +121,7 @@ typedef struct {
   int *nmodeadv;        /* [ncol][2] */
   int *modeadv;         /* [ncol][2][ORC_MAXMODEADV] */
   double *advection;    /* [ncol][2][ORC_MAXMODEADV] */
+  int *paths;           /* ORC_PATH_* bits of the column's last step (output only) */
 } orc_batch;
 
 /* ---- scalar / small functions (per-function fixtures) ---- */

@@ -13,7 +13,8 @@ import subprocess
 import numpy as np
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-LIB = os.path.join(HERE, "liboracle.so")
+# MCKPP_ORACLE_LIBRARY names another build of the oracle (the instrumented one of tools/oracle_coverage.py)
+LIB = os.environ.get("MCKPP_ORACLE_LIBRARY") or os.path.join(HERE, "liboracle.so")
 REFLIB = os.path.join(HERE, "_ref", "libmckpp_ref.so")
 REFSTEPLIB = {0: os.path.join(HERE, "_ref", "libmckpp_ref_step.so"),        # EXP = libm exp (the reference's build)
               1: os.path.join(HERE, "_ref", "libmckpp_ref_step_pexp.so")}  # EXP = the portable exp (exp_mode=1)
@@ -22,6 +23,11 @@ NI, NJ = 890, 48
 TABLE_SHAPE = (NJ + 2, NI + 2)  # C-order view of Fortran wmt(0:891,0:49)
 
 ST_ZERO_PIVOT, ST_LONG_ITER, ST_RETRIED, ST_FAILED, ST_DODGY = 1, 2, 4, 8, 16
+# bits of a batch's `paths` word (ORC_PATH_* of mckpp_oracle.h): which branches a column took during its last step,
+# OR-ed over all its passes and retries
+PATHS = {name: 1 << i for i, name in enumerate((
+    "HBL_SEAFLOOR", "HBL_SECOND_MIN", "HBL_NO_HIT", "HBL_MONOB", "HBL_EKMAN", "HBL_RI", "TRAP_U", "TRAP_TJUMP",
+    "TRAP_RMS_U", "TRAP_RMS_V", "TRAP_RMS_T", "TRAP_RMS_S", "ITER_DEEPER_AT_ITERMAX", "DD_FINGER", "DD_DIFFCONV"))}
 
 
 def build(force=False):
@@ -285,7 +291,7 @@ class _RefFields:
         status, npasses - stay zero), with `sflux` as its forcing rows."""
         ob = self.batch.copy()
         ob["sflux"] = sflux
-        for nm in ("talpha", "sbeta", "status", "npasses"):
+        for nm in ("talpha", "sbeta", "status", "npasses", "paths"):
             ob[nm] = 0
         got = {r: self.xfer(r, a, False) for r, a in self.arrays.items()}
         for b, (r, comp, lo, n) in self.lay.items():
@@ -456,7 +462,7 @@ SCALAR_FIELDS = [
     "reset_flag", "dampu_flag", "dampv_flag", "freeze_flag", "fcorr",
     "relax_sst", "SST0", "fcorr_twod", "relax_sal", "relax_ocnT",
 ]
-INT_FIELDS = ["old", "newi", "jerlov", "l_initflag", "l_ocean", "status", "npasses"]
+INT_FIELDS = ["old", "newi", "jerlov", "l_initflag", "l_ocean", "status", "npasses", "paths"]
 
 
 class Batch:

@@ -18,6 +18,8 @@ def grid_for(nz, kind="uniform"):
         return synth.uniform_grid(nz, 200.0)
     if kind == "stretched":
         return synth.stretched_grid(nz, 1000.0, 4.0)
+    if kind == "thin":          # a 10 m column: a wind stress of a few N/m2 moves all of it by 1 m/s in a step
+        return synth.uniform_grid(nz, 10.0)
     raise ValueError(kind)
 
 

@@ -34,6 +34,7 @@ class Case:
     switches: dict = field(default_factory=dict)
     pre: Optional[Callable] = None          # (ncol, nzp1, ob) -> {field: array}, before init_ocean
     post: Optional[Callable] = None         # (ncol, nzp1, ob) -> {field: array}, after init_ocean
+    stress: Optional[Callable] = None       # (ncol) -> (taux, tauy) in place of the bench mix's wind stress
     land_every: int = 0                     # run_physics = l_ocean = 0 on every land_every-th column
     jerlov_mix: bool = False
     diurnal: bool = False                   # short-wave follows the sun, step by step
@@ -90,6 +91,163 @@ def _trap_clim(ncol, nzp1, ob):
     return d
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the physics regimes the generators of tests/common.py never reach by themselves ("Regimes"): each hook
+# below is a closed form of the column index; test_the_cases_reach_what_they_are_for asserts through the oracle's
+# `paths` word that the branch a case is named after is really taken
+# ---------------------------------------------------------------------------------------------------------------
+def bathymetry(ncol, shallow, deep, every=1):
+    """ocdepth = -linspace(shallow, deep) on every `every`-th column (from column every-1), -10000 elsewhere"""
+    d = np.full(ncol, -10000.0)
+    sel = np.arange(every - 1, ncol, every)
+    d[sel] = -np.linspace(shallow, deep, len(sel))
+    return d
+
+
+def _bathymetry(shallow, deep):
+    return lambda ncol, nzp1, ob: {"ocdepth": bathymetry(ncol, shallow, deep)}
+
+
+# -ocdepth on level centres of the 40-level grid (2.5, 7.5: `hmin < -zm(k)` is strict), on an interface (10), just
+# past a centre (2.6) and above the first centre (0.01 ... 2: hbl shallower than level 1, kbl = 2, blmix with kn = 1)
+SEAFLOOR_EDGES = (2.5, 7.5, 10.0, 2.6, 0.01, 0.5, 1.0, 2.0)
+
+
+def _seafloor_edges(ncol, nzp1, ob):
+    return {"ocdepth": -np.resize(np.array(SEAFLOOR_EDGES), ncol)}
+
+
+def isothermal(T, S):
+    """T(k) = T(1) - 1e-4 k, S = 0: nothing but the surface forcing decides how deep a column mixes"""
+    return T[:, 0:1] - 1e-4 * np.arange(T.shape[1])[None, :], np.zeros_like(S)
+
+
+def tjump(T):
+    """a 12 K step down between levels 9 and 10: |T(k) - T(k+1)| >= 10 on every retry"""
+    T = T.copy()
+    T[:, 9:] -= 12.0
+    return T
+
+
+def _profiles(ob, nzp1):
+    return (ob[k][:, 1:nzp1 + 1].copy() for k in "TSUV")
+
+
+def _isothermal(ncol, nzp1, ob):
+    T, S, _, _ = _profiles(ob, nzp1)
+    T, S = isothermal(T, S)
+    return {"T": T, "S": S}
+
+
+def _isothermal_bathymetry(ncol, nzp1, ob):
+    d = _isothermal(ncol, nzp1, ob)
+    d["ocdepth"] = bathymetry(ncol, 3.0, 260.0, every=2)       # the deepest lie below the 200 m grid
+    return d
+
+
+def _tjump(ncol, nzp1, ob):
+    T, _, _, _ = _profiles(ob, nzp1)
+    T[::3] = tjump(T[::3])
+    return {"T": T}
+
+
+def _tjump_clim(ncol, nzp1, ob):
+    d = _tjump(ncol, nzp1, ob)
+    d["ocnT_clim"] = ob["T"][:, 1:nzp1 + 1] - 0.25
+    d["sal_clim"] = ob["S"][:, 1:nzp1 + 1] + 0.01
+    return d
+
+
+def _stress_ramp(ncol):
+    """a wind stress from 0.5 to 6 N/m2 across the columns, eastward on the even and northward on the odd ones: on the
+    10 m grid the rms change of U (of V) over a step crosses its threshold of 1 m/s inside the ramp, while no level
+    reaches 10 m/s"""
+    ramp = np.linspace(0.5, 6.0, ncol)
+    even = np.arange(ncol) % 2 == 0
+    return np.where(even, ramp, 1e-3), np.where(even, 0.0, ramp)
+
+
+def _moving(ncol, nzp1, ob):
+    """2 m/s in U and V at every level: the Coriolis term is a good part of a step's change, so that the retries'
+    f * 1.01 moves the rms change - columns just past the threshold are retried and then accepted"""
+    return {"U": np.full((ncol, nzp1), 2.0), "V": np.full((ncol, nzp1), 2.0)}
+
+
+def diffconv(T, S):
+    """cold fresh water over warm salty water, the warmth outweighing the salt (alphaDT < betaDS < 0: what the
+    reference's ddmix takes for diffusive convection, ddmix_mod.F90:39)"""
+    k = np.linspace(0.0, 1.0, T.shape[1])[None, :]
+    return 4.0 + 8.0 * k + 0 * T, -0.25 + 0.5 * k + 0 * S
+
+
+def _diffconv(ncol, nzp1, ob):
+    T, S, _, _ = _profiles(ob, nzp1)
+    T[::2], S[::2] = diffconv(T[::2], S[::2])
+    S[1::2] = 0.4 - 0.8 * np.linspace(0, 1, nzp1)[None, :]       # salt fingers on the others
+    return {"T": T, "S": S}
+
+
+SWEEP_SEED, LID = 20261016, 4
+SWEEP_REGIMES = ("plain", "seafloor", "isothermal", "isothermal_seafloor", "tjump", "diffconv", "fingers", "spun_up",
+                 "cold_lid", "salty_lid", "trap_u")
+
+
+def sweep_regimes(ncol):
+    """regime name -> the columns of the seeded sweep that have it (a shuffled, even deal of SWEEP_REGIMES)"""
+    reg = np.random.default_rng(SWEEP_SEED).permutation(np.arange(ncol) % len(SWEEP_REGIMES))
+    return {name: np.nonzero(reg == i)[0] for i, name in enumerate(SWEEP_REGIMES)}
+
+
+def _sweep(ncol, nzp1, ob):
+    """every regime above side by side in one batch, dealt over the columns by a seeded shuffle; and three that only
+    the sweep has: a column moving at 7 m/s at every level (Coriolis turns it by more than 1 m/s rms in a step:
+    the rms check on U and V), and a lid of four levels 9.5 K colder / 8 psu saltier than the water below it (convection
+    changes T / S by more than 1 rms over the column in a step: the rms check on T and S)"""
+    reg = sweep_regimes(ncol)
+    T, S, U, V = _profiles(ob, nzp1)
+    d = np.full(ncol, -10000.0)
+    d[reg["seafloor"]] = -np.linspace(0.5, 40.0, len(reg["seafloor"]))
+    iso = np.concatenate([reg["isothermal"], reg["isothermal_seafloor"]])
+    T[iso], S[iso] = isothermal(T[iso], S[iso])
+    d[reg["isothermal_seafloor"]] = -np.linspace(3.0, 260.0, len(reg["isothermal_seafloor"]))
+    T[reg["tjump"]] = tjump(T[reg["tjump"]])
+    T[reg["diffconv"]], S[reg["diffconv"]] = diffconv(T[reg["diffconv"]], S[reg["diffconv"]])
+    S[reg["fingers"]] = 0.4 - 0.8 * np.linspace(0, 1, nzp1)[None, :]
+    U[reg["spun_up"]], V[reg["spun_up"]] = 7.0, 7.0
+    T[reg["cold_lid"], :LID] -= 9.5
+    S[reg["salty_lid"], :LID] += 8.0
+    return {"T": T, "S": S, "U": U, "V": V, "ocdepth": d}
+
+
+def regime_mix(ncol, nzp1, ob):
+    """The sea-floor, full-depth and T-jump regimes side by side, by column index modulo 8 (so that the workgroups of
+    a large batch hold columns of different regimes next to each other, at every latitude): 0, 4 the plain
+    stratified start; 1, 5 shallow bathymetry (0.5 ... 40 m); 2 near-isothermal; 6 near-isothermal over bathymetry
+    from 3 m to below the grid; 3 the 12 K temperature step (trapped: 11 tries of 6 passes, every step); 7 the
+    stratified start over bathymetry between 20 and 150 m."""
+    T, S, _, _ = _profiles(ob, nzp1)
+    i = np.arange(ncol)
+    d = np.full(ncol, -10000.0)
+    for r, (lo, hi) in {1: (0.5, 40.0), 5: (40.0, 0.5), 6: (3.0, 260.0), 7: (20.0, 150.0)}.items():
+        d[i % 8 == r] = -np.linspace(lo, hi, int((i % 8 == r).sum()))
+    iso = (i % 8 == 2) | (i % 8 == 6)
+    T[iso], S[iso] = isothermal(T[iso], S[iso])
+    T[i % 8 == 3] = tjump(T[i % 8 == 3])
+    return {"T": T, "S": S, "ocdepth": d}
+
+
+def apply_both(ob, k3, nzp1, d):
+    """{batch field: array} on an oracle batch and on the HIP Kpp3dFields"""
+    _apply_batch(ob, nzp1, d)
+    apply_hip(k3, d)
+
+
+def _sweep_trap(ncol, nzp1, ob):
+    U = ob["U"][:, 1:nzp1 + 1].copy()
+    U[sweep_regimes(ncol)["trap_u"], 0:4] = 50.0
+    return {"U": U}
+
+
 CASES = {
     "nz40": Case(32, 40, 3),
     "nz60_land_jerlov": Case(30, 60, 2, land_every=4, jerlov_mix=True),
@@ -112,7 +270,28 @@ CASES = {
     "bottom_temp": Case(24, 40, 2, bottom_temp=True),
     # the seeded sweep: a model day of a sunlit, mixed-Jerlov 2000-column batch
     "sweep_2000x24": Case(2000, 60, 24, jerlov_mix=True, diurnal=True, full=False),
+    # the regimes: the sea floor clamps the boundary layer ...
+    "seafloor_nz40": Case(60, 40, 3, pre=_bathymetry(3.0, 40.0)),
+    "seafloor_nz69_stretched": Case(60, 69, 3, grid="stretched", dto=1200.0, pre=_bathymetry(3.0, 40.0), land_every=5,
+                                    jerlov_mix=True, diurnal=True),
+    "seafloor_edges_nz40": Case(24, 40, 3, pre=_seafloor_edges),
+    # ... columns mix down to the last level of the grid ...
+    "seafloor_fulldepth_nz60": Case(96, 60, 3, pre=_isothermal_bathymetry),
+    "fulldepth_nz100": Case(48, 100, 3, pre=_isothermal),
+    # ... the instability trap fires on a temperature jump, and on the rms change of a step ...
+    "tjump_trap_nz40": Case(60, 40, 2, pre=_tjump),
+    "tjump_trap_clim_nz40": Case(30, 40, 2, switches=dict(clim_present=1), pre=_tjump_clim),
+    "rms_retry_thin_grid": Case(96, 12, 2, grid="thin", pre=_moving, stress=_stress_ramp),
+    # ... the surface salinity follows the column, double diffusion takes its diffusive-convection arm ...
+    "ssref0_nz40": Case(24, 40, 3, switches=dict(L_SSref=0)),
+    "ldd_diffconv_nz40": Case(24, 40, 3, switches=dict(LDD=1), pre=_diffconv),
+    # ... and all of them side by side, seeded, under the bench forcing
+    "regime_sweep_nz60": Case(400, 60, 4, switches=dict(LDD=1), pre=_sweep, post=_sweep_trap, jerlov_mix=True, full=False),
 }
+
+
+REGIME_CASES = [t for t in CASES if t.startswith(("seafloor_", "fulldepth_", "tjump_", "rms_retry_", "ssref0_",
+                                                  "ldd_diffconv_", "regime_sweep_"))]
 
 
 def _apply_batch(ob, nzp1, d):
@@ -139,7 +318,10 @@ def apply_hip(k3, d):
 def forcing(case, step):
     """sflux(1:6) of model step `step` (1-based)"""
     t = step * case.dto if case.diurnal else None
-    return cm.synth.forcing(case.ncol, "bench", t_seconds=t)
+    sf = cm.synth.forcing(case.ncol, "bench", t_seconds=t)
+    if case.stress:
+        sf[:, 0], sf[:, 1] = case.stress(case.ncol)
+    return sf
 
 
 def jerlov(case):
@@ -279,7 +461,7 @@ def hip_get(k3, nz):
 
 def run_hip(mk, tag, golden, solver_mode=0):
     """The HIP kernel through the case from the same start, through the C-ABI as the parity tests drive it; returns
-    [(step, Kpp3dFields copy of the fields)] after asserting that its starting state is the oracle's and that the
+    [(step, Kpp3dFields copy of the fields, plus the status words and pass counts)] after asserting that its starting state is the oracle's and that the
     oracle's is the recorded one."""
     case = CASES[tag]
     oc, ob, pre, post = oracle_start(case, exp_mode=1, solver_mode=solver_mode)
@@ -302,8 +484,10 @@ def run_hip(mk, tag, golden, solver_mode=0):
     out = []
     for nt in range(1, case.nsteps + 1):
         cm.set_forcing_3d(k3, forcing(case, nt))
-        mk.mckpp_physics_driver(k3, kc, nt)
-        out.append((nt, {n: np.array(hip_get(k3, case.nz)(n)) for n in STEP_FIELDS}))
+        ctx = mk.mckpp_physics_driver(k3, kc, nt)
+        got = {n: np.array(hip_get(k3, case.nz)(n)) for n in STEP_FIELDS}
+        got["status"], _, got["npasses"] = (np.array(a) for a in ctx.status())
+        out.append((nt, got))
     return out
 
 
