@@ -255,6 +255,34 @@ int mckpp_hip_release_host_arrays(mckpp_hip_handle h);
 int mckpp_hip_save_restart(mckpp_hip_handle h, const char *path);
 int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path);
 
+/* Restart snapshots taken inside the step launches, so that a run with restart output can still take many steps in
+ * one launch.  The reference writes a restart whenever MOD(ntime, ndt_per_restart) == 0
+ * (src/mckpp_xios_control.F90:61-83): restart_schedule(h, 1, ndt_per_restart, nslots).  Its other restart, "always
+ * at the end of the run", is the ordinary mckpp_hip_save_restart after the last step.
+ *   Snapshot s >= 0 is the state after step nt_origin + (s+1)*period - 1; it lives in ring slot s % nslots of device
+ *   memory (a slot is as large as a restart file).  The column kernel copies each column's restart set there right
+ *   after that column's step.
+ *   restart_schedule: sets the schedule (period 0: cancels it).  The schedule in place is dropped first; if the slots
+ *     cannot be allocated the call fails and no schedule is set.  upload and load_restart cancel the schedule.
+ *   Every MCKPP_MODE_STEP launch - step, run_forced and their multi_ forms, one launch or a launch per step - takes
+ *     the snapshots whose steps it runs (init_ocean, vmix_pass and vmix_only never do).  The steps under the schedule
+ *     must follow on from one another, and a launch may not reach a snapshot whose slot holds one that is not yet
+ *     released: such a launch fails before anything is launched.  A snapshot whose step ran before the schedule was
+ *     set does not exist.
+ *   restart_snapshots: first_kept, the first snapshot not released, and last_complete, the last one whose step has
+ *     been launched (-1: none).
+ *   restart_snapshot_save: writes snapshot `snap` to `path`, byte for byte the file mckpp_hip_save_restart would have
+ *     written had the run stopped after the snapshot's step; mckpp_hip_load_restart reads it.  Waits for the launches
+ *     of the call that completed the snapshot only, not for launches queued behind it: they keep running while the
+ *     file is written.  Fails, naming the snapshot's step, for a snapshot that is incomplete, released or never existed.
+ *   restart_snapshot_release: releases snapshots up to and including upto_snap (complete ones only).
+ * What the host applies to the state after a step - the L_VARY_BOTTOM_TEMP override, mckpp_hip_bottomtemp - is not
+ * part of a snapshot: a snapshot is the state as the step's kernel left it. */
+int mckpp_hip_restart_schedule(mckpp_hip_handle h, int nt_origin, int period, int nslots);
+int mckpp_hip_restart_snapshots(mckpp_hip_handle h, int64_t *first_kept, int64_t *last_complete);
+int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char *path);
+int mckpp_hip_restart_snapshot_release(mckpp_hip_handle h, int64_t upto_snap);
+
 /* What the reference's time loop rewrites on the host between steps when the
  * optional physics is on (mckpp_boundary_update, src/mckpp_ocean_model_3D.F90:51-55;
  * the ndtupd* cadences of src/mckpp_boundary_update.F90): relax_sst, SST0,
@@ -434,6 +462,13 @@ int mckpp_hip_multi_window_records(mckpp_hip_multi_handle m, int sched, int64_t 
  * another number of shards or another land mask, before anything resident is replaced. */
 int mckpp_hip_multi_save_restart(mckpp_hip_multi_handle m, const char *path);
 int mckpp_hip_multi_load_restart(mckpp_hip_multi_handle m, const char *path);
+/* Restart snapshots inside the step launches (mckpp_hip_restart_schedule) over all shards: every shard keeps the
+ * snapshots of its own columns; snapshot_save writes one file per shard, <path>.<shard>of<ndev>, which
+ * mckpp_hip_multi_load_restart reads. */
+int mckpp_hip_multi_restart_schedule(mckpp_hip_multi_handle m, int nt_origin, int period, int nslots);
+int mckpp_hip_multi_restart_snapshots(mckpp_hip_multi_handle m, int64_t *first_kept, int64_t *last_complete);
+int mckpp_hip_multi_restart_snapshot_save(mckpp_hip_multi_handle m, int64_t snap, const char *path);
+int mckpp_hip_multi_restart_snapshot_release(mckpp_hip_multi_handle m, int64_t upto_snap);
 
 #ifdef __cplusplus
 }

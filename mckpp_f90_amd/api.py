@@ -209,6 +209,10 @@ def _bind(lib):
         getattr(lib, pre + "window_record_fetch").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, _dp]
         getattr(lib, pre + "window_record_release").argtypes = [C.c_void_p, C.c_int, C.c_int64]
         getattr(lib, pre + "window_records").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        getattr(lib, pre + "restart_schedule").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
+        getattr(lib, pre + "restart_snapshots").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        getattr(lib, pre + "restart_snapshot_save").argtypes = [C.c_void_p, C.c_int64, C.c_char_p]
+        getattr(lib, pre + "restart_snapshot_release").argtypes = [C.c_void_p, C.c_int64]
     lib.mckpp_hip_multi_save_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_load_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
@@ -406,7 +410,43 @@ class _WindowSchedules:
         return int(a.value), int(b.value)
 
 
-class MckppHip(_WindowSchedules):
+class _RestartSchedule:
+    """Restart snapshots taken inside the step launches (mckpp_hip_restart_schedule and its kin), for one context or
+    for all shards of a multi handle (_pre).  restart_scheduled is (nt_origin, period, nslots) of the schedule this
+    object set, or None."""
+    _pre = "mckpp_hip_"
+    restart_scheduled = None
+
+    def restart_schedule(self, nt_origin, period, nslots):
+        """Snapshot s is the state after step nt_origin + (s+1)*period - 1, kept in ring slot s % nslots.  Period 0:
+        cancel.  (1, ndt_per_restart, n) is the reference's MOD(ntime, ndt_per_restart) == 0."""
+        nt_origin, period, nslots = int(nt_origin), int(period), int(nslots)
+        if period < 0:
+            raise ValueError(f"restart_schedule: period={period} (0 cancels the schedule)")
+        if period > 0 and (nt_origin < 1 or nslots < 1):
+            raise ValueError(f"restart_schedule: nt_origin={nt_origin} nslots={nslots} (each at least 1)")
+        self.restart_scheduled = None   # (the library drops the schedule in place before it sets the new one)
+        _chk(getattr(_lib(), self._pre + "restart_schedule")(self._h, nt_origin, period, nslots))
+        if period > 0:
+            self.restart_scheduled = (nt_origin, period, nslots)
+
+    def restart_snapshots(self):
+        """(first_kept, last_complete): snapshots first_kept .. last_complete can be saved."""
+        a, b = C.c_int64(), C.c_int64()
+        _chk(getattr(_lib(), self._pre + "restart_snapshots")(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+    def restart_snapshot_save(self, snap, path):
+        """Snapshot `snap` as the file save_restart would have written after the snapshot's step (a multi handle: one
+        file per shard, <path>.<shard>of<ndev>).  Launches queued behind the snapshot's keep running meanwhile."""
+        _chk(getattr(_lib(), self._pre + "restart_snapshot_save")(self._h, int(snap), str(path).encode()))
+
+    def restart_snapshot_release(self, upto_snap):
+        """Release the snapshots up to and including upto_snap (their ring slots are free again)."""
+        _chk(getattr(_lib(), self._pre + "restart_snapshot_release")(self._h, int(upto_snap)))
+
+
+class MckppHip(_WindowSchedules, _RestartSchedule):
     """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
 
     def __init__(self, kpp_const_fields, device=0):
@@ -453,7 +493,8 @@ class MckppHip(_WindowSchedules):
         s = kpp_3d_fields.as_c()
         _chk(_lib().mckpp_hip_upload(self._h, C.byref(s)))
         self._npts_cache = kpp_3d_fields.npts
-        self._scheds().clear()   # (upload cancels every output schedule)
+        self._scheds().clear()   # (upload cancels every output schedule, and the restart schedule)
+        self.restart_scheduled = None
 
     def set_forcing(self, sflux):
         assert sflux.flags["F_CONTIGUOUS"]
@@ -488,6 +529,7 @@ class MckppHip(_WindowSchedules):
         _chk(_lib().mckpp_hip_load_restart(self._h, str(path).encode()))
         self._npts_cache = npts
         self._scheds().clear()
+        self.restart_scheduled = None
 
     def update_ancillaries(self, kpp_3d_fields):
         """Re-upload what mckpp_boundary_update rewrites between steps (optional-physics inputs only)."""
@@ -606,7 +648,7 @@ class MckppHip(_WindowSchedules):
         return y
 
 
-class MckppHipMulti(_WindowSchedules):
+class MckppHipMulti(_WindowSchedules, _RestartSchedule):
     """Several GPUs behind one handle (mckpp_hip_multi_*): columns dealt round-robin to the devices."""
     _pre = "mckpp_hip_multi_"
 
@@ -645,7 +687,8 @@ class MckppHipMulti(_WindowSchedules):
         sc = k3.as_c()
         _chk(_lib().mckpp_hip_multi_upload(self._h, C.byref(sc)))
         self._npts = k3.npts
-        self._scheds().clear()   # (upload cancels every output schedule)
+        self._scheds().clear()   # (upload cancels every output schedule, and the restart schedule)
+        self.restart_scheduled = None
 
     def set_forcing(self, sflux):
         self._hold(sflux)
@@ -721,6 +764,7 @@ class MckppHipMulti(_WindowSchedules):
     def load_restart(self, path):
         _chk(_lib().mckpp_hip_multi_load_restart(self._h, str(path).encode()))
         self._scheds().clear()
+        self.restart_scheduled = None
 
     def release_host_arrays(self):
         _chk(_lib().mckpp_hip_multi_release_host_arrays(self._h))

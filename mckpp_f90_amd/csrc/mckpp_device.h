@@ -118,7 +118,17 @@ struct mckpp_kparams_t {
   // (0: no schedule, nothing sampled)
   P<const mckpp_win_t<P>> win;
   int nwin;
+  // restart snapshots of MCKPP_MODE_STEP launches (mckpp_hip_restart_schedule; k_column_ps, finish round).  A column
+  // that has finished step snap_origin + (s+1)*snap_period - 1 copies its restart set into ring slot s % snap_nslots:
+  // whole rows (ld doubles) of U, V, T, S, Us/Vs/Ts/Ss(0:1), cp, rho - MCKPP_SNAP_ROWS planes of snap_plane doubles in
+  // the order of the restart file - at snap_rows + slot * snap_slot, and its records at snap_cs / snap_ci + slot * ncol
+  // records.  snap_period 0: no schedule, nothing copied.
+  P<double> snap_rows, snap_cs;
+  P<int> snap_ci;
+  long long snap_slot, snap_plane;
+  int snap_origin, snap_period, snap_nslots;
 };
+#define MCKPP_SNAP_ROWS 14
 using mckpp_kparams = mckpp_kparams_t<mckpp_ptr_plain>;
 using mckpp_kparams_dev = mckpp_kparams_t<mckpp_ptr_global>;
 using mckpp_win = mckpp_win_t<mckpp_ptr_plain>;

@@ -2877,9 +2877,11 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     // order, so its sums are the per-step API's bit for bit).  Before M0 publishes the step: once p.done[c] moves, the
     // column's next step may start elsewhere and rewrite the rows.  The records are plain loads and stores: a column
     // stays on one XCD for the launch, and its next step's acquire (M0) covers them like the rows.
-    if (p.nwin > 0 && p.mode == MCKPP_MODE_STEP) {   // (uniform)
+    // ---- restart snapshots (mckpp_hip_restart_schedule) share the place and the barrier: see below.
+    if ((p.nwin > 0 || p.snap_period > 0) && p.mode == MCKPP_MODE_STEP) {   // (uniform)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // every wave's stores of the rows have left it ...
       __syncthreads();                                    // ... before any wave reads them
+      if (p.nwin > 0) {
       FOR_ITEMS
         if (!act) continue;   // the two equation-of-state items exist for L1 only
         if (si[I_FIN] != F_FINAL) continue;
@@ -2899,6 +2901,48 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
           if (ops & 8) r[0] = v;
         }
       END_ITEMS
+      }
+      // The restart set of a column that has finished a snapshot step, copied from the rows and records just stored -
+      // what save_restart after that step reads - into the snapshot's ring slot.  Whole rows: item k takes elements
+      // k-1, k-1+L, ... of each (two at most from 31 levels on), so a slot's items cover all ld elements of a row, consecutive
+      // lanes consecutive elements; the equation-of-state items take part (rho and cp have nzp1+1 levels).  Plain loads
+      // and stores, like the window records: the launch boundary makes the slot visible to the host's copy, and no
+      // later step of the launch touches the slot (the host's ring guard).
+      if (p.snap_period > 0) {
+      FOR_ITEMS
+        if (si[I_FIN] != F_FINAL) continue;
+        const int q = ntime + si[I_STEP] - p.snap_origin + 1;   // steps from the origin, this one included
+        if (q <= 0) continue;
+        const int s = q / p.snap_period;
+        if (q != s * p.snap_period) continue;
+        const size_t slot_ = (size_t)((s - 1) % p.snap_nslots);
+        const auto dst = p.snap_rows + slot_ * (size_t)p.snap_slot + ro;
+        const size_t pl = (size_t)p.snap_plane;
+        for (int j = k - 1; j < p.ld; j += L) {
+          const size_t o = ro + j;
+          // four rows at a time: four loads in flight, not fourteen (the finish round is not where the kernel's
+          // registers should peak)
+          auto four = [&](int i, const auto r0, const auto r1, const auto r2, const auto r3) {
+            const double a0 = r0[o], a1 = r1[o], a2 = r2[o], a3 = r3[o];
+            const auto d = dst + (size_t)i * pl + j;
+            d[0] = a0; d[pl] = a1; d[2 * pl] = a2; d[3 * pl] = a3;
+          };
+          four(0, p.U, p.V, p.T, p.S);
+          four(4, p.Us[0], p.Us[1], p.Vs[0], p.Vs[1]);
+          four(8, p.Ts[0], p.Ts[1], p.Ss[0], p.Ss[1]);
+          const double a12 = p.cp[o], a13 = p.rho[o];
+          dst[12 * pl + j] = a12; dst[13 * pl + j] = a13;
+        }
+        if (is1) {
+          const auto cs = p.cs + (size_t)col * MCKPP_CS;
+          const auto ci = p.ci + (size_t)col * MCKPP_CI;
+          const auto dcs = p.snap_cs + (slot_ * (size_t)p.ncol + (size_t)col) * MCKPP_CS;
+          const auto dci = p.snap_ci + (slot_ * (size_t)p.ncol + (size_t)col) * MCKPP_CI;
+          for (int i = 0; i < MCKPP_CS; ++i) dcs[i] = cs[i];
+          for (int i = 0; i < MCKPP_CI; ++i) dci[i] = ci[i];
+        }
+      END_ITEMS
+      }
     }
     }   // finish round
     }   // pass of the active slots

@@ -14,6 +14,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <functional>
 #include <string>
 #include <thread>
 #include <vector>
@@ -125,6 +126,22 @@ struct mckpp_hip_ctx {
   } wsched[MCKPP_WIN_SCHEDULES];
   mckpp_win *d_win = nullptr;   // [MCKPP_WIN_ENTRIES]
   int nwin = 0;                 // entries of d_win in use (mckpp_kparams_t::nwin of the step launches)
+  // restart snapshots the step launches take themselves (mckpp_hip_restart_schedule): a ring of slots, each a restart
+  // set (mckpp_kparams_t::snap_*); the steps run under the schedule; per slot the event behind the launches of the
+  // call that completed its snapshot; a transfer stream and two pinned staging blocks for snapshot_save
+  struct snap_sched {
+    int64_t origin = 1, period = 0;        // period 0: no schedule
+    int nslots = 0;
+    int64_t first_nt = -1, next_nt = -1;   // as win_sched's
+    int64_t first_exists = 0;              // the snapshots before it were due before first_nt
+    int64_t first_kept = 0;                // the snapshots before it are released, or do not exist
+    double *rows = nullptr, *cs = nullptr;
+    int *ci = nullptr;
+    std::vector<hipEvent_t> ev;            // [nslots]
+  } rs;
+  hipStream_t snap_stream = nullptr;
+  char *h_snap[2] = {nullptr, nullptr};
+  hipEvent_t ev_snap[2] = {nullptr, nullptr};
   double *d_cs = nullptr;
   int *d_ci = nullptr;
   int *d_qhead = nullptr;  // QBLOCK_INTS ints, zeroed before every launch: [0..15] queue heads, [16..31] queue owners, [32] stragglers on the device
@@ -411,11 +428,13 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
 
 static void win_cancel(mckpp_hip_ctx *h, int s);
 static int win_cancel_all(mckpp_hip_ctx *h);
+static int snap_cancel(mckpp_hip_ctx *h);
 
 static void free_state(mckpp_hip_ctx *h)
 {
   for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) win_cancel(h, s);   // the records are sized to the resident columns
   h->nwin = 0;
+  snap_cancel(h);   // ... and so are the snapshot slots
   for (auto &p : h->d_prof) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_diag) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_ext_in) { if (p) hipFree(p); p = nullptr; }
@@ -464,6 +483,11 @@ int mckpp_hip_finalize(mckpp_hip_handle h)
   if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
   unpin_all(h);
   free_state(h);
+  for (int b = 0; b < 2; ++b) {
+    if (h->h_snap[b]) hipHostFree(h->h_snap[b]);
+    if (h->ev_snap[b]) hipEventDestroy(h->ev_snap[b]);
+  }
+  if (h->snap_stream) hipStreamDestroy(h->snap_stream);
   hipFree(h->d_zm); hipFree(h->d_hm); hipFree(h->d_tri0); hipFree(h->d_tri1);
   hipFree(h->d_swfrac_tab); hipFree(h->d_swdk_tab); hipFree(h->d_wtab); hipFree(h->d_qhead); hipFree(h->d_params); hipFree(h->d_scratch); hipFree(h->d_dm); hipFree(h->d_hsum);
   if (h->d_win) hipFree(h->d_win);
@@ -675,6 +699,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   if (!s->U || !s->X) return fail("mckpp_hip_upload: U and X are required");
   HIPCHK(hipSetDevice(h->device));
   if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
+  if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
   const int64_t npts = s->npts;
   const int nzp1 = h->nzp1;
   std::vector<int> ipt;
@@ -897,24 +922,32 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
   p.Rig = h->d_diag[D_RIG]; p.dbloc = h->d_diag[D_DBLOC]; p.Shsq = h->d_diag[D_SHSQ];
   p.scratch = h->d_scratch; p.scratch_doubles = h->scratch_doubles;
   if (mode == MCKPP_MODE_STEP && h->nwin > 0) { p.win = h->d_win; p.nwin = h->nwin; }   // (init / vmix never accumulate)
+  if (mode == MCKPP_MODE_STEP && h->rs.period > 0 && h->rs.rows) {   // (... and never take a snapshot)
+    p.snap_rows = h->rs.rows; p.snap_cs = h->rs.cs; p.snap_ci = h->rs.ci;
+    p.snap_plane = (long long)h->ncol * h->ld; p.snap_slot = MCKPP_SNAP_ROWS * p.snap_plane;
+    p.snap_origin = (int)h->rs.origin; p.snap_period = (int)h->rs.period; p.snap_nslots = h->rs.nslots;
+  }
 }
 
 struct forced_run { int ndtocn, l_rest; double flsn, el; };
 
 static int win_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
+static int snap_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
+static int snap_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
 static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced);
 
-// A step launch under output schedules: checked against them before anything is launched, then the schedules know
-// which steps have run (and so which of their records are complete)
+// A step launch under output schedules and the restart schedule: checked against them before anything is launched,
+// then the schedules know which steps have run (and so which of their records and snapshots are complete)
 static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced = nullptr,
                const char *who = "mckpp_hip_step")
 {
   if (!h) return fail("null handle");
   const bool sched = mode == MCKPP_MODE_STEP && nsteps > 0;
-  if (sched && win_check_launch(h, ntime, nsteps, who)) return -1;
+  if (sched && (win_check_launch(h, ntime, nsteps, who) || snap_check_launch(h, ntime, nsteps, who))) return -1;
   if (run_launch(h, ntime, nsteps, mode, forced)) return -1;
   if (sched) win_advance(h, ntime, nsteps);
+  if (sched && snap_advance(h, ntime, nsteps)) return -1;
   return 0;
 }
 
@@ -1302,6 +1335,25 @@ struct restart_header {
   int64_t npts, ncol;
 };
 const char kRestartMagic[8] = {'M', 'C', 'K', 'P', 'P', 'R', 'S', '1'};
+
+// The file of a restart set - the one writer of mckpp_hip_save_restart and mckpp_hip_restart_snapshot_save: the
+// header, the column map, then what `payload` writes: P_COUNT + 2 whole rows (ncol * ld doubles each: the profile rows
+// in the order of the P_ enumeration, cp, rho), the cs records, the ci records.
+int restart_write(mckpp_hip_ctx *h, const char *who, const char *path, const std::function<bool(FILE *)> &payload)
+{
+  FILE *f = fopen(path, "wb");
+  if (!f) return fail("%s: cannot open %s", who, path);
+  restart_header hd{};
+  memcpy(hd.magic, kRestartMagic, 8);
+  hd.version = 1; hd.nz = h->nz; hd.ld = h->ld; hd.cs = MCKPP_CS; hd.ci = MCKPP_CI; hd.nprof = P_COUNT + 2;
+  hd.npts = h->npts; hd.ncol = h->ncol;
+  bool ok = fwrite(&hd, sizeof hd, 1, f) == 1;
+  ok = ok && fwrite(h->ipt.data(), sizeof(int), (size_t)h->ncol, f) == (size_t)h->ncol;
+  ok = ok && payload(f);
+  ok = (fclose(f) == 0) && ok;
+  if (!ok) return fail("%s: write to %s failed", who, path);
+  return 0;
+}
 }  // namespace
 
 int mckpp_hip_save_restart(mckpp_hip_handle h, const char *path)
@@ -1310,30 +1362,222 @@ int mckpp_hip_save_restart(mckpp_hip_handle h, const char *path)
   if (h->ncol <= 0) return fail("mckpp_hip_save_restart: no resident columns");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  FILE *f = fopen(path, "wb");
-  if (!f) return fail("mckpp_hip_save_restart: cannot open %s", path);
-  restart_header hd{};
-  memcpy(hd.magic, kRestartMagic, 8);
-  hd.version = 1; hd.nz = h->nz; hd.ld = h->ld; hd.cs = MCKPP_CS; hd.ci = MCKPP_CI; hd.nprof = P_COUNT + 2;
-  hd.npts = h->npts; hd.ncol = h->ncol;
-  bool ok = fwrite(&hd, sizeof hd, 1, f) == 1;
-  ok = ok && fwrite(h->ipt.data(), sizeof(int), (size_t)h->ncol, f) == (size_t)h->ncol;
-  const size_t rowelems = (size_t)h->ncol * h->ld;
-  std::vector<double> buf(rowelems);
-  auto dump = [&](const double *d, size_t n) -> int {
-    if (n > buf.size()) buf.resize(n);
-    if (hipMemcpy(buf.data(), d, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-    return fwrite(buf.data(), sizeof(double), n, f) == n ? 0 : -1;
-  };
-  for (int i = 0; i < P_COUNT && ok; ++i) ok = dump(h->d_prof[i], rowelems) == 0;
-  ok = ok && dump(h->d_diag[D_CP], rowelems) == 0 && dump(h->d_diag[D_RHO], rowelems) == 0;
-  ok = ok && dump(h->d_cs, (size_t)h->ncol * MCKPP_CS) == 0;
-  std::vector<int> ci((size_t)h->ncol * MCKPP_CI);
-  ok = ok && hipMemcpy(ci.data(), h->d_ci, ci.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-  ok = ok && fwrite(ci.data(), sizeof(int), ci.size(), f) == ci.size();
-  ok = (fclose(f) == 0) && ok;
-  if (!ok) return fail("mckpp_hip_save_restart: write to %s failed", path);
+  return restart_write(h, "mckpp_hip_save_restart", path, [&](FILE *f) {
+    const size_t rowelems = (size_t)h->ncol * h->ld;
+    std::vector<double> buf(rowelems);
+    auto dump = [&](const double *d, size_t n) -> int {
+      if (n > buf.size()) buf.resize(n);
+      if (hipMemcpy(buf.data(), d, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
+      return fwrite(buf.data(), sizeof(double), n, f) == n ? 0 : -1;
+    };
+    bool ok = true;
+    for (int i = 0; i < P_COUNT && ok; ++i) ok = dump(h->d_prof[i], rowelems) == 0;
+    ok = ok && dump(h->d_diag[D_CP], rowelems) == 0 && dump(h->d_diag[D_RHO], rowelems) == 0;
+    ok = ok && dump(h->d_cs, (size_t)h->ncol * MCKPP_CS) == 0;
+    std::vector<int> ci((size_t)h->ncol * MCKPP_CI);
+    ok = ok && hipMemcpy(ci.data(), h->d_ci, ci.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
+    ok = ok && fwrite(ci.data(), sizeof(int), ci.size(), f) == ci.size();
+    return ok;
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Restart snapshots taken inside the step launches (mckpp_hip_restart_schedule): k_column_ps copies the restart set
+// of every column that has finished a scheduled step into a ring slot (see mckpp_kparams_t::snap_*).  The host keeps
+// the bookkeeping, as for the output schedules: which steps have run under the schedule, so which snapshots are
+// complete, and which are released; a launch that would overwrite a kept snapshot fails before anything is launched.
+// Snapshot s is the state after step origin + (s+1)*period - 1.
+// ---------------------------------------------------------------------------
+static long long snap_step(const mckpp_hip_ctx::snap_sched &r, int64_t s) { return r.origin + (s + 1) * r.period - 1; }
+
+// the first snapshot whose step is nt0 or later
+static int64_t snap_first_from(const mckpp_hip_ctx::snap_sched &r, int64_t nt0)
+{
+  return nt0 <= r.origin ? 0 : (nt0 - r.origin) / r.period;
+}
+
+// the last snapshot whose step has run (-1: none)
+static int64_t snap_last_complete(const mckpp_hip_ctx::snap_sched &r)
+{
+  if (r.next_nt < 0 || r.next_nt < r.origin) return -1;
+  return (r.next_nt - r.origin) / r.period - 1;
+}
+
+static int snap_cancel(mckpp_hip_ctx *h)
+{
+  auto &r = h->rs;
+  if (r.period == 0) return 0;
+  if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still write the slots
+  if (h->snap_stream) HIPCHK(hipStreamSynchronize(h->snap_stream));
+  if (r.rows) hipFree(r.rows);
+  if (r.cs) hipFree(r.cs);
+  if (r.ci) hipFree(r.ci);
+  for (auto e : r.ev) if (e) hipEventDestroy(e);
+  r = mckpp_hip_ctx::snap_sched{};
   return 0;
+}
+
+static int snap_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who)
+{
+  const auto &r = h->rs;
+  if (r.period == 0) return 0;
+  const int64_t last = (int64_t)nt0 + nsteps - 1;
+  if (r.next_nt >= 0 && nt0 != r.next_nt)
+    return fail("%s: steps %d..%lld, but the restart schedule has run up to step %lld: the steps under a schedule follow "
+                "on from one another (the next launch starts at step %lld)", who, nt0, (long long)last,
+                (long long)r.next_nt - 1, (long long)r.next_nt);
+  if (last - r.origin + 1 < r.period) return 0;   // no snapshot step yet
+  const int64_t kept = r.first_nt < 0 ? snap_first_from(r, nt0) : r.first_kept;
+  const int64_t sl = (last - r.origin + 1) / r.period - 1;
+  if (sl >= kept + r.nslots)
+    return fail("%s: steps %d..%lld reach restart snapshot %lld (after step %lld), whose slot in the ring of %d still holds "
+                "snapshot %lld (after step %lld), not released: save and release snapshots first", who, nt0, (long long)last,
+                (long long)sl, snap_step(r, sl), r.nslots, (long long)(sl - r.nslots), snap_step(r, sl - r.nslots));
+  return 0;
+}
+
+// after the call's launches: the schedule knows the steps, and every snapshot they completed gets the event its
+// save waits for
+static int snap_advance(mckpp_hip_ctx *h, int nt0, int nsteps)
+{
+  auto &r = h->rs;
+  if (r.period == 0) return 0;
+  if (r.first_nt < 0) { r.first_nt = nt0; r.first_exists = r.first_kept = snap_first_from(r, nt0); }
+  r.next_nt = (int64_t)nt0 + nsteps;
+  if (h->ncol == 0) return 0;
+  const int64_t lc = snap_last_complete(r);
+  for (int64_t s = std::max(r.first_exists, snap_first_from(r, nt0)); s <= lc; ++s)
+    HIPCHK(hipEventRecord(r.ev[(size_t)(s % r.nslots)], h->stream));
+  return 0;
+}
+
+int mckpp_hip_restart_schedule(mckpp_hip_handle h, int nt_origin, int period, int nslots)
+{
+  const char *who = "mckpp_hip_restart_schedule";
+  if (!h) return fail("%s: null handle", who);
+  if (period < 0) return fail("%s: period=%d (0 cancels the schedule)", who, period);
+  if (period > 0) {   // everything is checked before the schedule in place is touched
+    if (nt_origin < 1 || nslots < 1) return fail("%s: nt_origin=%d nslots=%d (each at least 1)", who, nt_origin, nslots);
+    if (h->npts <= 0) return fail("%s: upload the state first (the slots are sized to the resident columns)", who);
+  }
+  HIPCHK(hipSetDevice(h->device));
+  if (snap_cancel(h)) return -1;
+  if (period == 0) return 0;
+  auto &r = h->rs;
+  if (h->ncol > 0) {
+    if (!h->snap_stream) HIPCHK(hipStreamCreateWithFlags(&h->snap_stream, hipStreamNonBlocking));
+    const size_t plane = (size_t)h->ncol * h->ld * sizeof(double);
+    const size_t nb[3] = {(size_t)nslots * MCKPP_SNAP_ROWS * plane, (size_t)nslots * h->ncol * MCKPP_CS * sizeof(double),
+                          (size_t)nslots * h->ncol * MCKPP_CI * sizeof(int)};
+    void *blk[3] = {nullptr, nullptr, nullptr};
+    r.ev.assign((size_t)nslots, nullptr);
+    hipError_t e = hipSuccess;
+    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipMalloc(&blk[i], nb[i]);
+    for (int i = 0; i < nslots && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&r.ev[(size_t)i], hipEventDisableTiming);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      for (void *b : blk) if (b) hipFree(b);
+      for (auto ev : r.ev) if (ev) hipEventDestroy(ev);
+      r = mckpp_hip_ctx::snap_sched{};
+      return fail("%s: cannot allocate %zu bytes of device memory for the %d snapshot slots (%s); the schedule is not set",
+                  who, nb[0] + nb[1] + nb[2], nslots, hipGetErrorString(e));
+    }
+    r.rows = static_cast<double *>(blk[0]); r.cs = static_cast<double *>(blk[1]); r.ci = static_cast<int *>(blk[2]);
+  }
+  r.origin = nt_origin; r.period = period; r.nslots = nslots;
+  return 0;
+}
+
+int mckpp_hip_restart_snapshots(mckpp_hip_handle h, int64_t *first_kept, int64_t *last_complete)
+{
+  const char *who = "mckpp_hip_restart_snapshots";
+  if (!h) return fail("%s: null handle", who);
+  if (h->rs.period == 0) return fail("%s: no restart schedule is set", who);
+  if (first_kept) *first_kept = h->rs.first_kept;
+  if (last_complete) *last_complete = snap_last_complete(h->rs);
+  return 0;
+}
+
+int mckpp_hip_restart_snapshot_release(mckpp_hip_handle h, int64_t upto_snap)
+{
+  const char *who = "mckpp_hip_restart_snapshot_release";
+  if (!h) return fail("%s: null handle", who);
+  auto &r = h->rs;
+  if (r.period == 0) return fail("%s: no restart schedule is set", who);
+  const int64_t lc = snap_last_complete(r);
+  if (upto_snap > lc)
+    return fail("%s: snapshot %lld (after step %lld) is not complete (complete are up to snapshot %lld)", who,
+                (long long)upto_snap, snap_step(r, upto_snap), (long long)lc);
+  if (upto_snap + 1 > r.first_kept) r.first_kept = upto_snap + 1;
+  return 0;
+}
+
+// Snapshot `snap` as the file mckpp_hip_save_restart would have written after the snapshot's step.  Waits for the
+// event behind the launches of the call that completed the snapshot - not for the context's stream: launches queued
+// later keep running, and the ring guard keeps them off the slot.  The copies run on the snapshot transfer stream
+// through two pinned staging blocks: the next chunk crosses the bus while the previous one is written to the file.
+int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char *path)
+{
+  const char *who = "mckpp_hip_restart_snapshot_save";
+  if (!h) return fail("%s: null handle", who);
+  if (!path) return fail("%s: null argument", who);
+  const auto &r = h->rs;
+  if (r.period == 0) return fail("%s: no restart schedule is set", who);
+  if (snap < 0) return fail("%s: snapshot %lld", who, (long long)snap);
+  const long long st = snap_step(r, snap);
+  if (r.first_nt >= 0 && snap < r.first_exists)
+    return fail("%s: snapshot %lld (after step %lld) does not exist: that step ran before the schedule was set (its first "
+                "step was %lld)", who, (long long)snap, st, (long long)r.first_nt);
+  if (snap < r.first_kept) return fail("%s: snapshot %lld (after step %lld) has been released", who, (long long)snap, st);
+  if (snap > snap_last_complete(r))
+    return fail("%s: snapshot %lld (after step %lld) is incomplete: steps have run up to %lld", who, (long long)snap, st,
+                (long long)(r.next_nt < 0 ? r.origin - 1 : r.next_nt - 1));
+  if (h->ncol <= 0) return fail("%s: no resident columns", who);
+  HIPCHK(hipSetDevice(h->device));
+  const size_t chunk = (size_t)32 << 20;
+  for (int b = 0; b < 2; ++b) {
+    if (!h->h_snap[b]) HIPCHK(hipHostMalloc(&h->h_snap[b], chunk, hipHostMallocDefault));
+    if (!h->ev_snap[b]) HIPCHK(hipEventCreateWithFlags(&h->ev_snap[b], hipEventDisableTiming));
+  }
+  // the file's payload as device segments: the snapshot's planes, with U_init / V_init - never written by a step -
+  // from the live rows
+  const size_t slot = (size_t)(snap % r.nslots), rowbytes = (size_t)h->ncol * h->ld * sizeof(double);
+  struct seg { const char *dev; size_t bytes; };
+  std::vector<seg> segs;
+  const double *planes = r.rows + slot * MCKPP_SNAP_ROWS * (size_t)h->ncol * h->ld;
+  auto plane = [&](int i) { return reinterpret_cast<const char *>(planes + (size_t)i * h->ncol * h->ld); };
+  for (int i = 0; i < P_UINIT; ++i) segs.push_back({plane(i), rowbytes});
+  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_UINIT]), rowbytes});
+  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_VINIT]), rowbytes});
+  segs.push_back({plane(P_UINIT), rowbytes});       // cp
+  segs.push_back({plane(P_UINIT + 1), rowbytes});   // rho
+  segs.push_back({reinterpret_cast<const char *>(r.cs + slot * (size_t)h->ncol * MCKPP_CS), (size_t)h->ncol * MCKPP_CS * sizeof(double)});
+  segs.push_back({reinterpret_cast<const char *>(r.ci + slot * (size_t)h->ncol * MCKPP_CI), (size_t)h->ncol * MCKPP_CI * sizeof(int)});
+  std::vector<seg> chunks;
+  for (const seg &g : segs)
+    for (size_t o = 0; o < g.bytes; o += chunk) chunks.push_back({g.dev + o, std::min(chunk, g.bytes - o)});
+  HIPCHK(hipStreamWaitEvent(h->snap_stream, r.ev[slot], 0));
+  hipError_t herr = hipSuccess;
+  const int rc = restart_write(h, who, path, [&](FILE *f) {
+    auto issue = [&](size_t i) {
+      herr = hipMemcpyAsync(h->h_snap[i & 1], chunks[i].dev, chunks[i].bytes, hipMemcpyDeviceToHost, h->snap_stream);
+      if (herr == hipSuccess) herr = hipEventRecord(h->ev_snap[i & 1], h->snap_stream);
+      return herr == hipSuccess;
+    };
+    if (!issue(0)) return false;
+    for (size_t i = 0; i < chunks.size(); ++i) {
+      if (i + 1 < chunks.size() && !issue(i + 1)) return false;   // (its block was written out in the previous round)
+      herr = hipEventSynchronize(h->ev_snap[i & 1]);
+      if (herr != hipSuccess) return false;
+      if (fwrite(h->h_snap[i & 1], 1, chunks[i].bytes, f) != chunks[i].bytes) return false;
+    }
+    return true;
+  });
+  if (herr != hipSuccess) {
+    (void)hipStreamSynchronize(h->snap_stream);
+    return fail("%s: copy of snapshot %lld (after step %lld) failed: %s", who, (long long)snap, st, hipGetErrorString(herr));
+  }
+  return rc;
 }
 
 int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
@@ -1368,6 +1612,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
     if (jw < 1 || jw > 5) return fail("mckpp_hip_load_restart: %s: jerlov=%d in column %zu", path, jw, c);
   }
   if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
+  if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
   const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
   if (!same_shape) {
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
@@ -2287,6 +2532,40 @@ int mckpp_hip_multi_load_restart(mckpp_hip_multi_handle m, const char *path)
   for (int d = 0; d < ndev; ++d)
     if (m->ctx[d]->ncol > 0 && mckpp_hip_load_restart(m->ctx[d], shard_path(path, d, ndev).c_str()) != 0) return -1;
   return 0;
+}
+
+// restart snapshots inside the step launches (mckpp_hip_restart_schedule) over all shards: every shard keeps the
+// snapshots of its own columns (and the same bookkeeping: the shards run the same steps); a snapshot is one file per
+// shard, named as multi_save_restart names them, and multi_load_restart reads them
+int mckpp_hip_multi_restart_schedule(mckpp_hip_multi_handle m, int nt_origin, int period, int nslots)
+{
+  if (!m) return fail("mckpp_hip_multi_restart_schedule: null handle");
+  for (auto *x : m->ctx)
+    if (mckpp_hip_restart_schedule(x, nt_origin, period, nslots) != 0) {   // all shards or none
+      const std::string why = g_err;
+      for (auto *y : m->ctx) mckpp_hip_restart_schedule(y, 1, 0, 0);
+      return fail("%s", why.c_str());
+    }
+  return 0;
+}
+int mckpp_hip_multi_restart_snapshots(mckpp_hip_multi_handle m, int64_t *first_kept, int64_t *last_complete)
+{
+  if (!m) return fail("mckpp_hip_multi_restart_snapshots: null handle");
+  return mckpp_hip_restart_snapshots(m->ctx[0], first_kept, last_complete);
+}
+int mckpp_hip_multi_restart_snapshot_save(mckpp_hip_multi_handle m, int64_t snap, const char *path)
+{
+  if (!m) return fail("mckpp_hip_multi_restart_snapshot_save: null handle");
+  if (!path) return fail("mckpp_hip_multi_restart_snapshot_save: null argument");
+  const int ndev = (int)m->ctx.size();
+  for (int d = 0; d < ndev; ++d)
+    if (m->ctx[d]->ncol > 0 && mckpp_hip_restart_snapshot_save(m->ctx[d], snap, shard_path(path, d, ndev).c_str()) != 0) return -1;
+  return 0;
+}
+int mckpp_hip_multi_restart_snapshot_release(mckpp_hip_multi_handle m, int64_t upto_snap)
+{
+  if (!m) return fail("mckpp_hip_multi_restart_snapshot_release: null handle");
+  MULTI_EACH(mckpp_hip_restart_snapshot_release(x, upto_snap));
 }
 
 // the caller's arrays pinned on behalf of this handle go back to pageable memory (before the caller frees them)

@@ -22,7 +22,9 @@ program kpp_driver
                                mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select, &
                                mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch, &
                                mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, &
-                               mckpp_hip_all_window_record_release
+                               mckpp_hip_all_window_record_release, mckpp_hip_all_restart_schedule, &
+                               mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
+                               mckpp_hip_all_restart_snapshot_release
   implicit none
   character(len=512) :: fin, fout
   integer :: u, nt, nsteps, ncol, nlev, use_1d, ipt, flags
@@ -32,7 +34,8 @@ program kpp_driver
   real(c_double) :: t0, t1
   real(c_double), allocatable :: vm_h(:), vm_k(:), vm_difm(:,:), vm_difs(:,:), vm_dift(:,:), vm_ghat(:,:)
   real(c_double) :: hmixn
-  integer :: kmixn
+  integer :: kmixn, snap_first, snap_last
+  character(len=16) :: snap_name
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -50,6 +53,8 @@ program kpp_driver
   !           dlon = 0.5 ipt, dlat = -60 + 0.25 ipt
   !        256 flag 32's output (mean hmix, maximum T) from ONE forced run under an output schedule of period 2: every
   !           record of the run (appended, record after record)
+  !        512 the time loop as ONE forced run under a restart schedule of period 2 (MOD(ntime, 2) == 0 of
+  !           mckpp_restart_control); after it every snapshot s goes to <out.bin>.rst<s> (one file per shard)
   flags = hdr(6)
   if (iand(flags, 64) /= 0) mckpp_hip_output_mask = MCKPP_F_SCALARS
   ! hdr(7) > 0: that many device shards; hdr(8) = 1 puts them all on HIP device 0 (one-GPU rehearsal of the
@@ -95,7 +100,7 @@ program kpp_driver
 
   kpp_3d_fields%sflux(:, 1:6, 5, 0) = sf6
   call cpu_time(t0)
-  if (iand(flags, 48 + 256) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
+  if (iand(flags, 48 + 256 + 512) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
     allocate (series(ncol, 8, 1))
     series(:, 1, 1) = 0.01_c_double; series(:, 2, 1) = 0; series(:, 3, 1) = 200; series(:, 4, 1) = 0
     series(:, 5, 1) = -150; series(:, 6, 1) = 0; series(:, 7, 1) = 6e-5_c_double; series(:, 8, 1) = 0
@@ -111,6 +116,15 @@ program kpp_driver
       call mckpp_hip_all_window_schedule(0, 1, 2, nsteps / 2, [4_c_int32_t, 2_c_int32_t], &   ! MCKPP_OUT_HMIX, MCKPP_OUT_T
                                          [1_c_int32_t, 4_c_int32_t])                          ! MCKPP_WIN_MEAN, MCKPP_WIN_MAX
       call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)
+    else if (iand(flags, 512) /= 0) then   ! restart output inside the one forced run
+      call mckpp_hip_all_restart_schedule(1, 2, max(1, nsteps / 2))
+      call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)
+      call mckpp_hip_all_restart_snapshots(snap_first, snap_last)
+      do nt = snap_first, snap_last
+        write (snap_name, '(i0)') nt
+        call mckpp_hip_all_restart_snapshot_save(nt, trim(fout)//'.rst'//trim(snap_name))
+      end do
+      call mckpp_hip_all_restart_snapshot_release(snap_last)
     else
       call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)   ! one flux update (step 1), as ndtocn > nsteps
     end if
@@ -137,7 +151,7 @@ program kpp_driver
   write (*, '(a,3es14.6)') 'kpp_driver: hmix min/mean/max ', minval(kpp_3d_fields%hmix, kpp_3d_fields%run_physics), &
         sum(kpp_3d_fields%hmix)/max(1, count(kpp_3d_fields%run_physics)), maxval(kpp_3d_fields%hmix)
 
-  if (iand(flags, 64 + 48 + 256) == 0 .and. mckpp_hip_host_behind() /= 0) then   ! the default mask: nothing may be stale
+  if (iand(flags, 64 + 48 + 256 + 512) == 0 .and. mckpp_hip_host_behind() /= 0) then   ! the default mask: nothing may be stale
     write (0, '(a,i0)') 'kpp_driver: kpp_3d_fields is behind the device after mckpp_physics_driver: ', mckpp_hip_host_behind()
     error stop 2
   end if

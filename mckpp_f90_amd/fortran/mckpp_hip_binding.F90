@@ -340,6 +340,61 @@ module mckpp_hip_binding
       character(kind=c_char), intent(in) :: path(*)
       integer(c_int) :: rc
     end function
+    ! restart snapshots taken inside the step launches (mckpp_hip_restart_schedule of include/mckpp_hip.h)
+    function mckpp_hip_multi_restart_schedule(handle, nt_origin, period, nslots) &
+        bind(C, name="mckpp_hip_multi_restart_schedule") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: nt_origin, period, nslots
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_restart_snapshots(handle, first_kept, last_complete) &
+        bind(C, name="mckpp_hip_multi_restart_snapshots") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: first_kept, last_complete
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_restart_snapshot_save(handle, snap, path) &
+        bind(C, name="mckpp_hip_multi_restart_snapshot_save") result(rc)
+      import :: c_int, c_int64_t, c_ptr, c_char
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: snap
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_restart_snapshot_release(handle, upto_snap) &
+        bind(C, name="mckpp_hip_multi_restart_snapshot_release") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: upto_snap
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_restart_schedule(handle, nt_origin, period, nslots) bind(C, name="mckpp_hip_restart_schedule") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: nt_origin, period, nslots
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_restart_snapshots(handle, first_kept, last_complete) bind(C, name="mckpp_hip_restart_snapshots") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: first_kept, last_complete
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_restart_snapshot_save(handle, snap, path) bind(C, name="mckpp_hip_restart_snapshot_save") result(rc)
+      import :: c_int, c_int64_t, c_ptr, c_char
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: snap
+      character(kind=c_char), intent(in) :: path(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_restart_snapshot_release(handle, upto_snap) bind(C, name="mckpp_hip_restart_snapshot_release") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: upto_snap
+      integer(c_int) :: rc
+    end function
     function mckpp_hip_multi_release_host_arrays(handle) bind(C, name="mckpp_hip_multi_release_host_arrays") result(rc)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle

@@ -18,6 +18,8 @@ module mckpp_hip_session
   public :: mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select
   public :: mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch
   public :: mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, mckpp_hip_all_window_record_release
+  public :: mckpp_hip_all_restart_schedule, mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
+            mckpp_hip_all_restart_snapshot_release
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
   public :: mckpp_hip_host_behind
   public :: mckpp_hip_warnings, mckpp_hip_abort_on_zero_pivot, mckpp_hip_report_warnings, mckpp_hip_column_messages
@@ -379,6 +381,39 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle, int(sched, c_int), &
                          int(upto_rec, c_int64_t)), 'mckpp_hip_multi_window_record_release')
   end subroutine mckpp_hip_all_window_record_release
+
+  !> Restart snapshots taken inside the step launches (mckpp_restart_control, src/mckpp_xios_control.F90:61-83), so that
+  !! mckpp_hip_all_run_forced can take many steps in one call: snapshot s (from 0) is the state after step
+  !! nt_origin + (s+1)*period - 1, kept in ring slot mod(s, nslots) on the devices; (1, ndt_per_restart, n) is the
+  !! reference's MOD(ntime, ndt_per_restart) == 0.  Period 0 cancels.  The state goes to the devices first (an upload
+  !! cancels the schedule).
+  subroutine mckpp_hip_all_restart_schedule(nt_origin, period, nslots)
+    integer, intent(in) :: nt_origin, period, nslots
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_restart_schedule(mckpp_hip_multi_handle, int(nt_origin, c_int), int(period, c_int), &
+                         int(nslots, c_int)), 'mckpp_hip_multi_restart_schedule')
+  end subroutine mckpp_hip_all_restart_schedule
+  !> snapshots first_kept .. last_complete can be saved (last_complete -1: none yet)
+  subroutine mckpp_hip_all_restart_snapshots(first_kept, last_complete)
+    integer, intent(out) :: first_kept, last_complete
+    integer(c_int64_t) :: a, b
+    call mckpp_hip_check(mckpp_hip_multi_restart_snapshots(mckpp_hip_multi_handle, a, b), 'mckpp_hip_multi_restart_snapshots')
+    first_kept = int(a); last_complete = int(b)
+  end subroutine mckpp_hip_all_restart_snapshots
+  !> snapshot `snap` as the files mckpp_hip_all_save_restart would have written after its step (one per shard); the
+  !! launches queued behind the snapshot's keep running meanwhile
+  subroutine mckpp_hip_all_restart_snapshot_save(snap, path)
+    integer, intent(in) :: snap
+    character(len=*), intent(in) :: path
+    call mckpp_hip_check(mckpp_hip_multi_restart_snapshot_save(mckpp_hip_multi_handle, int(snap, c_int64_t), &
+                         trim(path)//c_null_char), 'mckpp_hip_multi_restart_snapshot_save')
+  end subroutine mckpp_hip_all_restart_snapshot_save
+  !> the snapshots up to and including upto_snap are written out: their ring slots are free again
+  subroutine mckpp_hip_all_restart_snapshot_release(upto_snap)
+    integer, intent(in) :: upto_snap
+    call mckpp_hip_check(mckpp_hip_multi_restart_snapshot_release(mckpp_hip_multi_handle, int(upto_snap, c_int64_t)), &
+                         'mckpp_hip_multi_restart_snapshot_release')
+  end subroutine mckpp_hip_all_restart_snapshot_release
 
   !> Restart set of all devices (src/mckpp_xios_io.F90:368-465): one file per shard, <path>.<shard>of<ndevices>
   subroutine mckpp_hip_all_save_restart(path)
