@@ -72,6 +72,12 @@ struct mckpp_kparams_t {
   int solver_mode;   // 0: tridiagonal sweeps in the reference's order (solvers.F90:112-161); 1: two-ended elimination (opt-in)
   int l3cap;      // > 0: L3 forms the bulk Richardson numbers at most down to this level before the scan asks for the
                   // rest (MCKPP_L3_CAP, tests: the second round of the scan on every pass)
+  // How far down L3 forms them (k_column_ps: M0, scan_result; read on the manager wave only)
+  int first_margin;   // >= 0: a column's first pass of a step goes down to the kmix its previous step left plus this many
+                      // levels (MCKPP_FIRST_MARGIN); < 0: to every level (MCKPP_FIRST_GUESS=0)
+  int scan_rule;      // bits 0-15: later passes go down to the level the scan of the pass before ended at plus this many
+                      // (MCKPP_GUESS_MARGIN); bit 16: a scan that runs out of levels with every column across counts as
+                      // stopped (not under MCKPP_FIRST_GUESS=0)
   P<const double> wtab;        // [(NJ+2)][(NI+2)] pairs {wmt, wst}
   // state
   P<double> U, V, T, S;
@@ -90,7 +96,7 @@ struct mckpp_kparams_t {
   P<int> qowner;  // [16] per queue: 0 free, else hardware XCC id + 1 of the XCD whose workgroups serve it (zeroed per launch)
   P<int> done;    // [ncol] steps of this launch a column has completed, then [ncol] steps of it that have been started
                   // (zeroed per launch; nsteps_launch > 1 only)
-  P<unsigned long long> dbg;   // optional [32] phase-cycle accumulators (diagnostic builds of a run only)
+  P<unsigned long long> dbg;   // optional [40] phase-cycle accumulators, counts of L3's guesses (diagnostic builds of a run only)
   // optional physics: ext != 0 selects the kernel build that carries it
   int ext, L_RELAX_SST, L_RELAX_CALCONLY, L_FCORR, L_FCORR_WITHZ, L_SFCORR, L_SFCORR_WITHZ;
   int L_RELAX_SAL, L_RELAX_OCNT, L_NO_FREEZE, L_NO_ISOTHERM, L_DAMP_CURR, iso_bot, dt_uvdamp, maxmodeadv;

@@ -215,7 +215,7 @@ __device__ __forceinline__ double ps_max(double a, double b)
 // to go on from); L3 has formed the bulk Richardson numbers down to level nz only.  out[0]: the deepest level whose
 // running maximum is in place; out[1]: 1 if the scan stopped because every column had crossed.
 __device__ __forceinline__ void ps_scan_rib(int W, int row, double *slots, int SS, int KS, int k0, int nz, const int *sact,
-                                            int sact_stride, int lane, double Ricr, int *out)
+                                            int sact_stride, int lane, double Ricr, int *out, bool tail_ok)
 {
   const double epsln16 = 1.e-16;
   asm volatile("" : "+v"(lane));
@@ -225,6 +225,7 @@ __device__ __forceinline__ void ps_scan_rib(int W, int row, double *slots, int S
     asm volatile("" : "+v"(rb));   // its wait here, not at its first use inside the loop
     int k = k0;
     bool stop = false;   // every column of the wave had crossed before the last eight levels scanned
+    int ktail = 0;   // > 0: ... or before the last four to eleven (which end at level nz) - the level they count as scanned to
     if (k + 3 <= nz) {   // a trip: levels k .. k+3; KS = 9, 11 or 15 doubles per level
       const unsigned step = 4u * (unsigned)KS * 8u;
       unsigned ad = ps_lds_addr(r + k * KS);
@@ -255,6 +256,10 @@ __device__ __forceinline__ void ps_scan_rib(int W, int row, double *slots, int S
       // (past the loop nothing stays in flight across a branch: see ps_backsub)
       ps_lds_wait<0>(a01, a23);   // on a stop: fetched, not needed
       if (!stop) {
+        // the levels left are too few for another trip of the loop, but there are four at least: if every column has
+        // crossed by now, the first four are all the scan needs (the crossing's level and the next) - it counts as
+        // stopped there, whatever it goes on to scan
+        if (tail_ok && __builtin_amdgcn_ballot_w64(!(rb > Ricr)) == 0ull) ktail = k + 3;
         body(k, a01, a23);
         k += 4;
         if (k + 3 <= nz) {
@@ -273,7 +278,7 @@ __device__ __forceinline__ void ps_scan_rib(int W, int row, double *slots, int S
         r[k * KS] = rb;
       }
     }
-    out[0] = stop ? k - 1 : nz; out[1] = stop ? 1 : 0;   // the same for every column of the wave
+    out[0] = stop ? k - 1 : (ktail > 0 ? ktail : nz); out[1] = (stop || ktail > 0) ? 1 : 0;   // the same for every column of the wave
   }
 }
 
@@ -1297,13 +1302,17 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
   // the hardware (HW_REG_XCC_ID, mapped to 0..nq-1 by a probe at mckpp_hip_init) - so a column's rows live in one L2,
   // the coherence point of all CUs that ever touch them, and plain stores are enough.
   // A slot whose ticket is not ready keeps it (PS_WAIT) and asks again at every later M0.
+#ifdef MCKPP_PS_STAMPS
+  int stamp_new = 0;   // M0 has just started a column here: the pass to come is a first pass
+  unsigned long long gacc[6] = {0, 0, 0, 0, 0, 0};   // first passes, later passes, their sums of kguess, second rounds, sum of the scans' ends
+#endif
   auto M0 = [&]() {
     int lane = lane_k; asm volatile("" : "+v"(lane));
     bool a = false, wt = false, sticky = false;
     const bool multi = p.nsteps_launch > 1;
     int *msi = sirec + (lane < W ? lane : 0) * I_COUNT;
     double *msc = screc + (lane < W ? lane : 0) * C_COUNT;
-    int st = PS_DONE, c = 0, step = 0;
+    int st = PS_DONE, c = 0, step = 0, kfirst = 0;
     bool want = false, ready = false, idle = false, dropped = false;
     // Who starts a column's next step.  A step is started by whoever first moves the column's count of started steps
     // (p.done[ncol + c]) from s to s+1, and there are two who try:
@@ -1455,6 +1464,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
           const auto ci = p.ci + (size_t)c * MCKPP_CI;
           const auto cs = p.cs + (size_t)c * MCKPP_CS;
           int old = ci[CI_OLD], newi = ci[CI_NEW], status = 0;
+          const double kprev = cs[CS_KMIX];   // (with the loads above: the record's first)
           if (old < 0 || old > 1) { old = newi; status |= 16; }
           if (newi < 0 || newi > 1) { newi = old; status |= 16; }
           msi[I_ACT] = 1; msi[I_COL] = c; msi[I_STEP] = step; msi[I_OLD] = old; msi[I_NEW] = newi; msi[I_JER] = ci[CI_JERLOV];
@@ -1468,7 +1478,14 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
           // (at itermax in its previous step - ci holds that step's pass count: a straggler from its first pass on)
           sticky = p.solo_limit > 0 && p.mode == MCKPP_MODE_STEP && (ci[CI_NPASS] > 50 || cont);
           msi[I_STRAG] = sticky ? 1 : 0;
-          s_flags[3] = nz;   // no guess for a new column: L3 forms the bulk Richardson numbers of every level
+          // Where L3 forms the bulk Richardson numbers down to in the column's first pass: the level its boundary layer
+          // ended at in its previous step (the finish round's kmix, in the column's record) plus a margin.  Whatever
+          // else the record holds there - uploaded, initialised elsewhere, garbage - means every level: a guess that
+          // is too shallow costs a second round of the scan, never a result.
+          kfirst = nz;
+          if (!DD && p.mode == MCKPP_MODE_STEP && p.first_margin >= 0) {
+            if (kprev >= 1.0 && kprev <= (double)nz) kfirst = (int)kprev + p.first_margin < nz ? (int)kprev + p.first_margin : nz;   // (a NaN fails both)
+          }
           msc[C_F] = cs[CS_F]; msc[C_WXNT0] = 0.0; msc[C_HMIXE] = 0.0; msc[C_HMIXN] = 0.0;
           msc[C_SREF] = cs[CS_SREF]; msc[C_SSURF] = cs[CS_SSURF]; msc[C_OCDEPTH] = cs[CS_OCDEPTH];
           double s1 = cs[CS_SFLUX1], s2 = cs[CS_SFLUX2], s3 = cs[CS_SFLUX3], s4 = cs[CS_SFLUX4], s5 = cs[CS_SFLUX5], s6 = cs[CS_SFLUX6];
@@ -1505,6 +1522,18 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       wt = st == PS_WAIT || (idle && more) || dropped;
     }
     const unsigned long long m = __ballot(a), mw = __ballot(wt);
+    if (__ballot(kfirst > 0) != 0ull) {
+      // The workgroup's guess for the pass to come: the deepest first guess of the columns started here and, if some
+      // slot goes on iterating, the guess it holds for those (a retry included).  With no slot going on the old
+      // value must not come back in: it may be a straggler's, deep.
+      // (a maximum in LDS: the wave's LDS instructions take effect in order)
+      const bool goes_on = __ballot(a && kfirst == 0) != 0ull;   // (every lane votes)
+      if (lane == 0 && !goes_on) s_flags[3] = 0;
+      if (kfirst > 0) atomicMax(&s_flags[3], kfirst);
+#ifdef MCKPP_PS_STAMPS
+      stamp_new = 1;
+#endif
+    }
     {
       const int nsticky = __popcll(__ballot(sticky));
       if (nsticky > 0 && lane == 0) atomicAdd((int *)p.sync, nsticky);
@@ -2119,10 +2148,12 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     }
     // ---- M1 | L2: surface fluxes (wave 0) | reference-level loop, Ri pieces (verticalmixing_mod.F90:111-137)
     // The bulk Richardson numbers of bldepth, and with them the reference-level averages here, are formed down to
-    // the level the scan of the pass before ended at plus eight (s_flags[3]; every level for a new column, with
-    // double diffusion - whose rows the second round below would need - and in the modes that return uref/vref of
-    // the deepest level).  MCKPP_L3_CAP caps the guess (tests).
+    // the level the scan of the pass before ended at plus a margin (s_flags[3]; for a new column the level its
+    // boundary layer ended at in its previous step plus another margin: M0; every level with double diffusion -
+    // whose rows the second round below would need - and in the modes that return uref/vref of the deepest level).
+    // MCKPP_L3_CAP caps the guess (tests).
     const int kguess = (DD || p.mode != MCKPP_MODE_STEP) ? nz : (p.l3cap > 0 && p.l3cap < s_flags[3] ? p.l3cap : s_flags[3]);
+    const int scan_rule = wv == mgr ? p.scan_rule : 0;   // (M2's: the margin of the next guess, whether a scan may stop in its tail; loaded here, ahead of its use)
     if (wv == mgr) M1();
     if (kguess < nz && sparse) {   // a view of a few slots: one level-major item per thread, none on the manager wave
       FOR_ITEMS_RISING
@@ -2246,8 +2277,8 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     // the boundary layer has deepened since the pass the guess comes from - the other levels follow)
     auto scan_result = [&](int kmax) {   // what the scan's outcome means for L4, for a second round and for the next pass
       if (lane < W && sirec[lane * I_COUNT + I_ACT]) {
-        const int kdone = s_flags[2], stopped = s_flags[5];
-        if (stopped) { s_flags[4] = 0; s_flags[3] = kdone + 8 < nz ? kdone + 8 : nz; }
+        const int kdone = s_flags[2], stopped = s_flags[5], gmargin = scan_rule & 0xffff;
+        if (stopped) { s_flags[4] = 0; s_flags[3] = kdone + gmargin < nz ? kdone + gmargin : nz; }
         else if (kmax >= nz) { s_flags[4] = 0; s_flags[3] = nz; }
         else s_flags[4] = 1;
       }
@@ -2257,10 +2288,15 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       // levels above the scan's start are taken as they are; the scan's fifth slot of s_flags: its `stopped`
       {
         int out[2] = {nz, 0};
-        ps_scan_rib(W, Q_YV, slots, SS, ROWS, 2, kguess, sirec + I_ACT, I_COUNT, lane, Ricr, out);
+        ps_scan_rib(W, Q_YV, slots, SS, ROWS, 2, kguess, sirec + I_ACT, I_COUNT, lane, Ricr, out, (scan_rule >> 16) != 0);
         if (lane < W && sirec[lane * I_COUNT + I_ACT]) { s_flags[2] = out[0]; s_flags[5] = out[1]; }
       }
       scan_result(kguess);
+#ifdef MCKPP_PS_STAMPS
+      gacc[stamp_new ? 0 : 1] += 1; gacc[stamp_new ? 2 : 3] += (unsigned long long)kguess;
+      gacc[4] += (unsigned long long)s_flags[4]; gacc[5] += (unsigned long long)s_flags[2];
+      stamp_new = 0;
+#endif
     }
     STAMP(6);
     __syncthreads();
@@ -2286,7 +2322,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       __syncthreads();
       if (wv == mgr) {
         int out[2] = {nz, 0};
-        ps_scan_rib(W, Q_YV, slots, SS, ROWS, kguess + 1, nz, sirec + I_ACT, I_COUNT, lane, Ricr, out);
+        ps_scan_rib(W, Q_YV, slots, SS, ROWS, kguess + 1, nz, sirec + I_ACT, I_COUNT, lane, Ricr, out, false);
         if (lane < W && sirec[lane * I_COUNT + I_ACT]) { s_flags[2] = out[0]; s_flags[5] = out[1]; }
         scan_result(nz);
       }
@@ -2968,6 +3004,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     atomicAdd((unsigned long long *)p.dbg + 25, tacc[25]);   // of M5: its forward part
     for (int i = 26; i < 31; ++i) atomicAdd((unsigned long long *)p.dbg + i, tacc[i]);   // parts of the finish round
     atomicAdd((unsigned long long *)p.dbg + 31, tacc[23]);
+    for (int i = 0; i < 6; ++i) atomicAdd((unsigned long long *)p.dbg + 32 + i, gacc[i]);   // the guesses of L3 and the scan
   }
 #endif
 #undef STAMP

@@ -80,6 +80,9 @@ const double jer_a2[6] = {0, 23.0, 20.0, 17.0, 14.0, 7.9};
 }  // namespace
 
 enum { QBLOCK_INTS = 64 };
+// margins of the guesses the column kernel forms its bulk Richardson numbers down to (mckpp_kparams_t::first_margin,
+// guess_margin): chosen on the headline workload, profiles/r06/README.md
+enum { FIRST_MARGIN_DEFAULT = 12, GUESS_MARGIN_DEFAULT = 0 };
 
 struct mckpp_hip_ctx {
   int device = 0;
@@ -152,6 +155,7 @@ struct mckpp_hip_ctx {
   int nqueues = 0;         // XCDs of the device, found by a probe at init: the queues of such a launch
   int xcc_queue[16];       // hardware XCC id -> queue (-1: no workgroup of the probe ran there)
   int l3cap = 0;   // MCKPP_L3_CAP (tests): see mckpp_kparams_t::l3cap
+  int first_guess = 1, first_margin = FIRST_MARGIN_DEFAULT, guess_margin = GUESS_MARGIN_DEFAULT;   // mckpp_kparams_t::first_margin, scan_rule
   int solver_mode = 0;   // mckpp_hip_set_solver_mode / MCKPP_SOLVER_MODE
   unsigned long long *d_dbg = nullptr;
   mckpp_kparams *d_params = nullptr;   // device copy of the kernel parameter block
@@ -341,8 +345,8 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   HIPCHK(hipMalloc(&h->d_scratch, h->scratch_doubles * sizeof(double)));
   HIPCHK(hipMemset(h->d_scratch, 0, h->scratch_doubles * sizeof(double)));
   if (getenv("MCKPP_STAMP")) {
-    HIPCHK(hipMalloc(&h->d_dbg, 32 * sizeof(unsigned long long)));
-    HIPCHK(hipMemset(h->d_dbg, 0, 32 * sizeof(unsigned long long)));
+    HIPCHK(hipMalloc(&h->d_dbg, 40 * sizeof(unsigned long long)));
+    HIPCHK(hipMemset(h->d_dbg, 0, 40 * sizeof(unsigned long long)));
   }
   HIPCHK(hipEventCreate(&h->ev0));
   HIPCHK(hipEventCreate(&h->ev1));
@@ -368,6 +372,13 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
     h->l2pre = (nref >= 16 && !c->LDD) ? 1 : 0;
     if (const char *e = getenv("MCKPP_L2PRE")) h->l2pre = (atoi(e) != 0 && !c->LDD) ? 1 : 0;
     if (const char *e = getenv("MCKPP_L3_CAP")) h->l3cap = atoi(e) > 0 ? atoi(e) : 0;
+    // the guesses L3 works from (profiles/r06: the margins' sweep).  MCKPP_FIRST_GUESS=0 is the rule before them: every
+    // level in a column's first pass, the scan's end plus eight after it (A/B runs, tests)
+    if (const char *e = getenv("MCKPP_FIRST_MARGIN")) h->first_margin = std::min(std::max(0, atoi(e)), 0xffff);
+    if (const char *e = getenv("MCKPP_GUESS_MARGIN")) h->guess_margin = std::min(std::max(0, atoi(e)), 0xffff);
+    if (const char *e = getenv("MCKPP_FIRST_GUESS")) {
+      if (atoi(e) == 0) { h->first_guess = 0; h->guess_margin = 8; }
+    }
     h->solver_mode = solver_mode_env;
     if (const char *e = getenv("MCKPP_MULTISTEP")) h->multistep = atoi(e) != 0 && h->nqueues > 0;
   }
@@ -890,7 +901,9 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
   p.nz = h->nz; p.nzp1 = h->nzp1; p.ncol = (int)h->ncol; p.ld = h->ld;
   p.ntime = ntime; p.itermax = h->c.itermax; p.mode = mode; p.diag = h->diag;
   p.L_SSref = h->c.L_SSref; p.LDD = h->c.LDD; p.clim_present = h->c.clim_present;
-  p.l2pre = h->l2pre; p.LRI = h->c.LRI ? 1 : 0; p.l3cap = h->l3cap; p.solver_mode = h->solver_mode;
+  p.l2pre = h->l2pre; p.LRI = h->c.LRI ? 1 : 0; p.l3cap = h->l3cap;
+  p.first_margin = h->first_guess ? h->first_margin : -1; p.scan_rule = h->guess_margin | (h->first_guess ? 1 << 16 : 0);
+  p.solver_mode = h->solver_mode;
   p.hmixtolfrac = h->c.hmixtolfrac; p.dto = h->c.dto; p.grav = h->c.grav; p.vonk = h->c.vonk; p.sice = h->c.sice;
   p.Vtc = h->Vtc; p.cg = h->cg; p.dm_nz = h->dm_nz;
   p.zm = h->d_zm; p.hm = h->d_hm; p.tri0 = h->d_tri0; p.tri1 = h->d_tri1;
@@ -1077,7 +1090,7 @@ int mckpp_hip_synchronize(mckpp_hip_handle h)
     fprintf(stderr, "\n");
   }
   if (h->d_dbg) {   // MCKPP_STAMP=1: print and reset the per-segment cycle sums of the stamping wave of every workgroup
-    unsigned long long t[32];
+    unsigned long long t[40];
     HIPCHK(hipMemcpy(t, h->d_dbg, sizeof t, hipMemcpyDeviceToHost));
     HIPCHK(hipMemset(h->d_dbg, 0, sizeof t));
     if (t[31]) {
@@ -1101,6 +1114,11 @@ int mckpp_hip_synchronize(mckpp_hip_handle h)
         fprintf(stderr, " all=%.0f]", fin / (double)t[31]);
       }
       fprintf(stderr, " total=%.0f\n", tot / (double)t[31]);
+      if (t[32] + t[33])   // how far down L3 formed the bulk Richardson numbers, per workgroup pass (first: a column was started before it)
+        fprintf(stderr, "[mckpp guesses ps] first passes %llu, mean kguess %.1f; later passes %llu, mean kguess %.1f; second rounds %llu "
+                        "(%.4f of the passes); mean end of the first scan %.1f\n",
+                t[32], t[32] ? (double)t[34] / (double)t[32] : 0.0, t[33], t[33] ? (double)t[35] / (double)t[33] : 0.0, t[36],
+                (double)t[36] / (double)(t[32] + t[33]), (double)t[37] / (double)(t[32] + t[33]));
     }
   }
   return 0;
