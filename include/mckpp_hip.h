@@ -283,6 +283,33 @@ int mckpp_hip_restart_snapshots(mckpp_hip_handle h, int64_t *first_kept, int64_t
 int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char *path);
 int mckpp_hip_restart_snapshot_release(mckpp_hip_handle h, int64_t upto_snap);
 
+/* The step log: what the status words and pass counts of the steps inside a launch were.  mckpp_hip_status reads the
+ * words of the last step only - a column's word is zeroed when its next step starts - so after mckpp_hip_step(nt, n > 1)
+ * or mckpp_hip_run_forced it says nothing of steps nt .. nt+n-2.  With a log set, every MCKPP_MODE_STEP launch - step,
+ * run_forced and their multi_ forms, one launch or a launch per step - appends one record for each column-step that
+ * ends with a non-zero status word or with at least min_passes passes (init_ocean, vmix_pass and vmix_only never
+ * log).  The reference's STOP on a zero pivot (src/mckpp_physics_solvers.F90:140-148) and its located warnings
+ * (src/mckpp_physics_ocnstep_mod.F90:184-191, 229-236) can so be reported for every step of a run of one launch.
+ *   A column-step retried by the instability trap is one record, with the status accumulated over its tries and the
+ *   passes of all of them, as mckpp_hip_status would have reported it after that step.
+ *   step_log: sets the log: `capacity` records of 16 bytes in device memory; min_passes 0: flagged column-steps only.
+ *     Capacity 0 cancels it; negative arguments are errors.  The log in place is dropped first; if the records cannot
+ *     be allocated the call fails and no log is set.  upload and load_restart cancel the log (its records name
+ *     resident columns).
+ *   step_log_count: waits for the context's stream.  n_events: every event since the log was set or cleared;
+ *     n_stored = min(n_events, capacity); status_or: the OR of the status words of all events, those that found no room
+ *     included - a zero pivot is never lost to overflow.  Overflow never refuses or stops a launch; which `capacity`
+ *     events are the stored ones is then unspecified.  (The device counts events in 32 bits.)
+ *   step_log_fetch: the first n <= n_stored stored records, sorted by (nt, point): the step, the 0-based point in the
+ *     caller's 3-D ordering - as mckpp_hip_status numbers its words - the status word and the passes.  Null arrays are
+ *     skipped.  Does not clear the log.
+ *   step_log_clear: keeps the log set; the event count and the OR are zero again (behind the launches already queued).
+ * A launch without a log runs what it ran before the log existed, apart from one uniform branch. */
+int mckpp_hip_step_log(mckpp_hip_handle h, int64_t capacity, int min_passes);
+int mckpp_hip_step_log_count(mckpp_hip_handle h, int64_t *n_events, int64_t *n_stored, int32_t *status_or);
+int mckpp_hip_step_log_fetch(mckpp_hip_handle h, int64_t n, int32_t *nt, int32_t *point, int32_t *status, int32_t *npasses);
+int mckpp_hip_step_log_clear(mckpp_hip_handle h);
+
 /* What the reference's time loop rewrites on the host between steps when the
  * optional physics is on (mckpp_boundary_update, src/mckpp_ocean_model_3D.F90:51-55;
  * the ndtupd* cadences of src/mckpp_boundary_update.F90): relax_sst, SST0,
@@ -469,6 +496,14 @@ int mckpp_hip_multi_restart_schedule(mckpp_hip_multi_handle m, int nt_origin, in
 int mckpp_hip_multi_restart_snapshots(mckpp_hip_multi_handle m, int64_t *first_kept, int64_t *last_complete);
 int mckpp_hip_multi_restart_snapshot_save(mckpp_hip_multi_handle m, int64_t snap, const char *path);
 int mckpp_hip_multi_restart_snapshot_release(mckpp_hip_multi_handle m, int64_t upto_snap);
+/* The step log (mckpp_hip_step_log) over all shards: one log of `capacity` records per shard; count adds the shards'
+ * counts and ORs their status words; fetch merges the shards' stored records and sorts them by (nt, point) - the points
+ * are the caller's, the round-robin deal undone. */
+int mckpp_hip_multi_step_log(mckpp_hip_multi_handle m, int64_t capacity, int min_passes);
+int mckpp_hip_multi_step_log_count(mckpp_hip_multi_handle m, int64_t *n_events, int64_t *n_stored, int32_t *status_or);
+int mckpp_hip_multi_step_log_fetch(mckpp_hip_multi_handle m, int64_t n, int32_t *nt, int32_t *point, int32_t *status,
+                                   int32_t *npasses);
+int mckpp_hip_multi_step_log_clear(mckpp_hip_multi_handle m);
 
 #ifdef __cplusplus
 }

@@ -213,6 +213,11 @@ def _bind(lib):
         getattr(lib, pre + "restart_snapshots").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         getattr(lib, pre + "restart_snapshot_save").argtypes = [C.c_void_p, C.c_int64, C.c_char_p]
         getattr(lib, pre + "restart_snapshot_release").argtypes = [C.c_void_p, C.c_int64]
+        getattr(lib, pre + "step_log").argtypes = [C.c_void_p, C.c_int64, C.c_int]
+        getattr(lib, pre + "step_log_count").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
+                                                         C.POINTER(C.c_int32)]
+        getattr(lib, pre + "step_log_fetch").argtypes = [C.c_void_p, C.c_int64] + [C.POINTER(C.c_int32)] * 4
+        getattr(lib, pre + "step_log_clear").argtypes = [C.c_void_p]
     lib.mckpp_hip_multi_save_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_load_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
@@ -446,7 +451,45 @@ class _RestartSchedule:
         _chk(getattr(_lib(), self._pre + "restart_snapshot_release")(self._h, int(upto_snap)))
 
 
-class MckppHip(_WindowSchedules, _RestartSchedule):
+class _StepLog:
+    """The step log of the step launches (mckpp_hip_step_log and its kin), for one context or for all shards of a multi
+    handle (_pre).  step_logged is (capacity, min_passes) of the log this object set, or None."""
+    _pre = "mckpp_hip_"
+    step_logged = None
+
+    def step_log(self, capacity, min_passes=0):
+        """Every column-step of a step launch that ends with a non-zero status word, or with at least min_passes passes
+        (0: status only), leaves a record, up to `capacity` of them (a multi handle: per shard).  Capacity 0: cancel."""
+        capacity, min_passes = int(capacity), int(min_passes)
+        if capacity < 0 or min_passes < 0:
+            raise ValueError(f"step_log: capacity={capacity} min_passes={min_passes} (0 cancels the log / logs flagged "
+                             "steps only)")
+        self.step_logged = None   # (the library drops the log in place before it sets the new one)
+        _chk(getattr(_lib(), self._pre + "step_log")(self._h, capacity, min_passes))
+        if capacity > 0:
+            self.step_logged = (capacity, min_passes)
+
+    def step_log_count(self):
+        """(n_events, n_stored, status_or) since the log was set or cleared; status_or covers the events that found no
+        room too."""
+        a, b, c = C.c_int64(), C.c_int64(), C.c_int32()
+        _chk(getattr(_lib(), self._pre + "step_log_count")(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        return int(a.value), int(b.value), int(c.value)
+
+    def step_log_fetch(self):
+        """The stored records as int32 arrays (nt, point, status, npasses), sorted by (nt, point); point is the 0-based
+        index in the caller's 3-D ordering, as status() numbers its words."""
+        n = self.step_log_count()[1]
+        out = [np.zeros(n, np.int32) for _ in range(4)]
+        _chk(getattr(_lib(), self._pre + "step_log_fetch")(self._h, n, *[a.ctypes.data_as(C.POINTER(C.c_int32)) for a in out]))
+        return tuple(out)
+
+    def step_log_clear(self):
+        """Keep the log; the event count and the OR of the status words are zero again."""
+        _chk(getattr(_lib(), self._pre + "step_log_clear")(self._h))
+
+
+class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog):
     """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
 
     def __init__(self, kpp_const_fields, device=0):
@@ -493,8 +536,9 @@ class MckppHip(_WindowSchedules, _RestartSchedule):
         s = kpp_3d_fields.as_c()
         _chk(_lib().mckpp_hip_upload(self._h, C.byref(s)))
         self._npts_cache = kpp_3d_fields.npts
-        self._scheds().clear()   # (upload cancels every output schedule, and the restart schedule)
+        self._scheds().clear()   # (upload cancels every output schedule, the restart schedule and the step log)
         self.restart_scheduled = None
+        self.step_logged = None
 
     def set_forcing(self, sflux):
         assert sflux.flags["F_CONTIGUOUS"]
@@ -530,6 +574,7 @@ class MckppHip(_WindowSchedules, _RestartSchedule):
         self._npts_cache = npts
         self._scheds().clear()
         self.restart_scheduled = None
+        self.step_logged = None
 
     def update_ancillaries(self, kpp_3d_fields):
         """Re-upload what mckpp_boundary_update rewrites between steps (optional-physics inputs only)."""
@@ -648,7 +693,7 @@ class MckppHip(_WindowSchedules, _RestartSchedule):
         return y
 
 
-class MckppHipMulti(_WindowSchedules, _RestartSchedule):
+class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog):
     """Several GPUs behind one handle (mckpp_hip_multi_*): columns dealt round-robin to the devices."""
     _pre = "mckpp_hip_multi_"
 
@@ -687,8 +732,9 @@ class MckppHipMulti(_WindowSchedules, _RestartSchedule):
         sc = k3.as_c()
         _chk(_lib().mckpp_hip_multi_upload(self._h, C.byref(sc)))
         self._npts = k3.npts
-        self._scheds().clear()   # (upload cancels every output schedule, and the restart schedule)
+        self._scheds().clear()   # (upload cancels every output schedule, the restart schedule and the step log)
         self.restart_scheduled = None
+        self.step_logged = None
 
     def set_forcing(self, sflux):
         self._hold(sflux)
@@ -765,6 +811,7 @@ class MckppHipMulti(_WindowSchedules, _RestartSchedule):
         _chk(_lib().mckpp_hip_multi_load_restart(self._h, str(path).encode()))
         self._scheds().clear()
         self.restart_scheduled = None
+        self.step_logged = None
 
     def release_host_arrays(self):
         _chk(_lib().mckpp_hip_multi_release_host_arrays(self._h))

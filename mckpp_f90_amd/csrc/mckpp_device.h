@@ -53,6 +53,9 @@ struct mckpp_win_t {
   int origin, period, nrec;
 };
 
+// A record of the step log: {nt, resident column, status word, passes} of one column-step, one 16-byte store
+typedef int mckpp_log_rec __attribute__((ext_vector_type(4)));
+
 template <template <class> class P>
 struct mckpp_kparams_t {
   int nz, nzp1, ncol, ld;
@@ -133,6 +136,12 @@ struct mckpp_kparams_t {
   P<int> snap_ci;
   long long snap_slot, snap_plane;
   int snap_origin, snap_period, snap_nslots;
+  // step log of MCKPP_MODE_STEP launches (mckpp_hip_step_log; k_column_ps, finish round).  A column-step that ends with
+  // a non-zero status word, or with at least log_min_passes passes (0: status only), is an event: it ORs its status into
+  // log_ctl[1], takes the next index from log_ctl[0] and, below log_cap, writes its record there.  log_cap 0: no log.
+  P<mckpp_log_rec> log_rec;
+  P<int> log_ctl;
+  int log_cap, log_min_passes;
 };
 #define MCKPP_SNAP_ROWS 14
 using mckpp_kparams = mckpp_kparams_t<mckpp_ptr_plain>;

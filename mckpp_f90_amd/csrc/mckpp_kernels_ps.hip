@@ -2878,6 +2878,17 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
           cs[CS_DAMPU] = dampu; cs[CS_DAMPV] = dampv;
           ci[CI_OLD] = old; ci[CI_NEW] = newi;
           ci[CI_STATUS] = si[I_STATUS]; ci[CI_NPASS] = si[I_NPASS];
+          // ---- step log (mckpp_hip_step_log): a column-step that ends flagged, or after log_min_passes passes, leaves
+          // a record.  Here a retried step is at its final try, its status accumulated over the tries.  The slot's own
+          // record is all it reads, so it waits for nothing; the launch boundary shows the records to the host.
+          if (p.log_cap > 0) {   // (uniform)
+            const int status = si[I_STATUS], np = si[I_NPASS];
+            if (status != 0 || (p.log_min_passes > 0 && np >= p.log_min_passes)) {
+              if (status != 0) atomicOr((int *)p.log_ctl + 1, status);
+              const int i = atomicAdd((int *)p.log_ctl, 1);
+              if ((unsigned)i < (unsigned)p.log_cap) p.log_rec[i] = mckpp_log_rec{ntime + si[I_STEP], col, status, np};
+            }
+          }
         }
       } else if (p.mode == MCKPP_MODE_INIT) {
         if (act) {

@@ -9,11 +9,13 @@
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 
+#include <algorithm>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <exception>
 #include <functional>
 #include <string>
 #include <thread>
@@ -142,6 +144,12 @@ struct mckpp_hip_ctx {
     int *ci = nullptr;
     std::vector<hipEvent_t> ev;            // [nslots]
   } rs;
+  // the step log of the step launches (mckpp_hip_step_log): log_cap records and the two control ints - events so far,
+  // OR of their status words (mckpp_kparams_t::log_*); log_cap 0: no log
+  mckpp_log_rec *d_log_rec = nullptr;
+  int *d_log_ctl = nullptr;
+  int64_t log_cap = 0;
+  int log_min_passes = 0;
   hipStream_t snap_stream = nullptr;
   char *h_snap[2] = {nullptr, nullptr};
   hipEvent_t ev_snap[2] = {nullptr, nullptr};
@@ -440,12 +448,14 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
 static void win_cancel(mckpp_hip_ctx *h, int s);
 static int win_cancel_all(mckpp_hip_ctx *h);
 static int snap_cancel(mckpp_hip_ctx *h);
+static int log_cancel(mckpp_hip_ctx *h);
 
 static void free_state(mckpp_hip_ctx *h)
 {
   for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) win_cancel(h, s);   // the records are sized to the resident columns
   h->nwin = 0;
   snap_cancel(h);   // ... and so are the snapshot slots
+  log_cancel(h);    // the step log's records name resident columns
   for (auto &p : h->d_prof) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_diag) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_ext_in) { if (p) hipFree(p); p = nullptr; }
@@ -711,6 +721,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   HIPCHK(hipSetDevice(h->device));
   if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
   if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
+  if (log_cancel(h)) return -1;       // ... and the step log's records (they name resident columns)
   const int64_t npts = s->npts;
   const int nzp1 = h->nzp1;
   std::vector<int> ipt;
@@ -939,6 +950,10 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
     p.snap_rows = h->rs.rows; p.snap_cs = h->rs.cs; p.snap_ci = h->rs.ci;
     p.snap_plane = (long long)h->ncol * h->ld; p.snap_slot = MCKPP_SNAP_ROWS * p.snap_plane;
     p.snap_origin = (int)h->rs.origin; p.snap_period = (int)h->rs.period; p.snap_nslots = h->rs.nslots;
+  }
+  if (mode == MCKPP_MODE_STEP && h->log_cap > 0) {   // (... and never log)
+    p.log_rec = h->d_log_rec; p.log_ctl = h->d_log_ctl;
+    p.log_cap = (int)h->log_cap; p.log_min_passes = h->log_min_passes;
   }
 }
 
@@ -1598,6 +1613,131 @@ int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char
   return rc;
 }
 
+// ---------------------------------------------------------------------------
+// The step log (mckpp_hip_step_log): k_column_ps appends a record {nt, resident column, status, passes} for every
+// column-step of a MCKPP_MODE_STEP launch that ends flagged or after min_passes passes (mckpp_kparams_t::log_*).  The
+// host only sets, reads and zeroes it: no launch is checked against it, and an overflow costs records, never the
+// count or the OR of the status words.
+// ---------------------------------------------------------------------------
+static int log_cancel(mckpp_hip_ctx *h)
+{
+  if (h->log_cap == 0) return 0;
+  if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still write the records
+  if (h->d_log_rec) hipFree(h->d_log_rec);
+  if (h->d_log_ctl) hipFree(h->d_log_ctl);
+  h->d_log_rec = nullptr; h->d_log_ctl = nullptr;
+  h->log_cap = 0; h->log_min_passes = 0;
+  return 0;
+}
+
+int mckpp_hip_step_log(mckpp_hip_handle h, int64_t capacity, int min_passes)
+{
+  const char *who = "mckpp_hip_step_log";
+  if (!h) return fail("%s: null handle", who);
+  if (capacity < 0 || min_passes < 0)
+    return fail("%s: capacity=%lld min_passes=%d (capacity 0 cancels the log, min_passes 0 logs flagged steps only)", who,
+                (long long)capacity, min_passes);
+  if (capacity > INT32_MAX) return fail("%s: capacity=%lld (at most %d records)", who, (long long)capacity, INT32_MAX);
+  if (capacity > 0 && h->npts <= 0) return fail("%s: upload the state first (the records name the resident columns)", who);
+  HIPCHK(hipSetDevice(h->device));
+  if (log_cancel(h)) return -1;
+  if (capacity == 0) return 0;
+  void *rec = nullptr, *ctl = nullptr;
+  hipError_t e = hipMalloc(&rec, (size_t)capacity * sizeof(mckpp_log_rec));
+  if (e == hipSuccess) e = hipMalloc(&ctl, 2 * sizeof(int));
+  if (e == hipSuccess) e = hipMemsetAsync(ctl, 0, 2 * sizeof(int), h->stream);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (rec) hipFree(rec);
+    if (ctl) hipFree(ctl);
+    return fail("%s: cannot allocate %zu bytes of device memory for %lld records (%s); no log is set", who,
+                (size_t)capacity * sizeof(mckpp_log_rec), (long long)capacity, hipGetErrorString(e));
+  }
+  h->d_log_rec = static_cast<mckpp_log_rec *>(rec); h->d_log_ctl = static_cast<int *>(ctl);
+  h->log_cap = capacity; h->log_min_passes = min_passes;
+  return 0;
+}
+
+// events so far (the device counts them in 32 bits), how many of them are stored, the OR of all their status words
+static int log_read_ctl(mckpp_hip_ctx *h, int64_t *n_events, int64_t *n_stored, int32_t *status_or)
+{
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  int ctl[2] = {0, 0};
+  HIPCHK(hipMemcpy(ctl, h->d_log_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+  const int64_t n = (int64_t)(uint32_t)ctl[0];
+  if (n_events) *n_events = n;
+  if (n_stored) *n_stored = std::min(n, h->log_cap);
+  if (status_or) *status_or = ctl[1];
+  return 0;
+}
+
+int mckpp_hip_step_log_count(mckpp_hip_handle h, int64_t *n_events, int64_t *n_stored, int32_t *status_or)
+{
+  const char *who = "mckpp_hip_step_log_count";
+  if (!h) return fail("%s: null handle", who);
+  if (h->log_cap == 0) return fail("%s: no step log is set", who);
+  return log_read_ctl(h, n_events, n_stored, status_or);
+}
+
+namespace {
+struct log_event { int32_t nt, point, status, npasses; };
+bool log_before(const log_event &a, const log_event &b) { return a.nt != b.nt ? a.nt < b.nt : a.point < b.point; }
+
+// the first n stored records of a context, points in the caller's numbering, unsorted
+int log_fetch_raw(mckpp_hip_ctx *h, const char *who, int64_t n, std::vector<log_event> &out)
+{
+  int64_t stored = 0;
+  if (log_read_ctl(h, nullptr, &stored, nullptr)) return -1;
+  if (n < 0 || n > stored) return fail("%s: n=%lld (%lld records are stored)", who, (long long)n, (long long)stored);
+  out.resize((size_t)n);
+  if (n == 0) return 0;
+  static_assert(sizeof(log_event) == sizeof(mckpp_log_rec), "a record is four ints");
+  HIPCHK(hipMemcpy(out.data(), h->d_log_rec, (size_t)n * sizeof(log_event), hipMemcpyDeviceToHost));
+  for (auto &e : out) {
+    if (e.point < 0 || e.point >= h->ncol) return fail("%s: a record names column %d of %lld", who, e.point, (long long)h->ncol);
+    e.point = h->ipt[(size_t)e.point];
+  }
+  return 0;
+}
+
+int log_deliver(std::vector<log_event> &ev, int32_t *nt, int32_t *point, int32_t *status, int32_t *npasses)
+{
+  std::sort(ev.begin(), ev.end(), log_before);
+  for (size_t i = 0; i < ev.size(); ++i) {
+    if (nt) nt[i] = ev[i].nt;
+    if (point) point[i] = ev[i].point;
+    if (status) status[i] = ev[i].status;
+    if (npasses) npasses[i] = ev[i].npasses;
+  }
+  return 0;
+}
+}  // namespace
+
+int mckpp_hip_step_log_fetch(mckpp_hip_handle h, int64_t n, int32_t *nt, int32_t *point, int32_t *status, int32_t *npasses)
+{
+  const char *who = "mckpp_hip_step_log_fetch";
+  if (!h) return fail("%s: null handle", who);
+  if (h->log_cap == 0) return fail("%s: no step log is set", who);
+  try {
+    std::vector<log_event> ev;
+    if (log_fetch_raw(h, who, n, ev)) return -1;
+    return log_deliver(ev, nt, point, status, npasses);
+  } catch (const std::exception &e) {
+    return fail("%s: %s", who, e.what());
+  }
+}
+
+int mckpp_hip_step_log_clear(mckpp_hip_handle h)
+{
+  const char *who = "mckpp_hip_step_log_clear";
+  if (!h) return fail("%s: null handle", who);
+  if (h->log_cap == 0) return fail("%s: no step log is set", who);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipMemsetAsync(h->d_log_ctl, 0, 2 * sizeof(int), h->stream));   // (behind the launches already queued)
+  return 0;
+}
+
 int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
 {
   if (!h || !path) return fail("mckpp_hip_load_restart: null argument");
@@ -1631,6 +1771,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
   }
   if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
   if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
+  if (log_cancel(h)) return -1;       // ... and the step log's records
   const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
   if (!same_shape) {
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
@@ -2584,6 +2725,63 @@ int mckpp_hip_multi_restart_snapshot_release(mckpp_hip_multi_handle m, int64_t u
 {
   if (!m) return fail("mckpp_hip_multi_restart_snapshot_release: null handle");
   MULTI_EACH(mckpp_hip_restart_snapshot_release(x, upto_snap));
+}
+
+// the step log (mckpp_hip_step_log) over all shards: one log of `capacity` records per shard; the counts add up, the
+// ORs are ORed, and fetch merges the shards' records (their points are the caller's already) and sorts them
+int mckpp_hip_multi_step_log(mckpp_hip_multi_handle m, int64_t capacity, int min_passes)
+{
+  if (!m) return fail("mckpp_hip_multi_step_log: null handle");
+  for (auto *x : m->ctx)
+    if (mckpp_hip_step_log(x, capacity, min_passes) != 0) {   // all shards or none
+      const std::string why = g_err;
+      for (auto *y : m->ctx) mckpp_hip_step_log(y, 0, 0);
+      return fail("%s", why.c_str());
+    }
+  return 0;
+}
+int mckpp_hip_multi_step_log_count(mckpp_hip_multi_handle m, int64_t *n_events, int64_t *n_stored, int32_t *status_or)
+{
+  if (!m) return fail("mckpp_hip_multi_step_log_count: null handle");
+  int64_t ne = 0, ns = 0;
+  int32_t so = 0;
+  for (auto *x : m->ctx) {
+    int64_t a = 0, b = 0;
+    int32_t c = 0;
+    if (mckpp_hip_step_log_count(x, &a, &b, &c) != 0) return -1;
+    ne += a; ns += b; so |= c;
+  }
+  if (n_events) *n_events = ne;
+  if (n_stored) *n_stored = ns;
+  if (status_or) *status_or = so;
+  return 0;
+}
+int mckpp_hip_multi_step_log_fetch(mckpp_hip_multi_handle m, int64_t n, int32_t *nt, int32_t *point, int32_t *status,
+                                   int32_t *npasses)
+{
+  const char *who = "mckpp_hip_multi_step_log_fetch";
+  if (!m) return fail("%s: null handle", who);
+  try {
+    std::vector<log_event> all, ev;
+    for (auto *x : m->ctx) {
+      if (x->log_cap == 0) return fail("%s: no step log is set", who);
+      int64_t stored = 0;
+      if (log_read_ctl(x, nullptr, &stored, nullptr) || log_fetch_raw(x, who, stored, ev)) return -1;
+      all.insert(all.end(), ev.begin(), ev.end());
+    }
+    if (n < 0 || n > (int64_t)all.size())
+      return fail("%s: n=%lld (%lld records are stored)", who, (long long)n, (long long)all.size());
+    std::sort(all.begin(), all.end(), log_before);
+    all.resize((size_t)n);
+    return log_deliver(all, nt, point, status, npasses);
+  } catch (const std::exception &e) {
+    return fail("%s: %s", who, e.what());
+  }
+}
+int mckpp_hip_multi_step_log_clear(mckpp_hip_multi_handle m)
+{
+  if (!m) return fail("mckpp_hip_multi_step_log_clear: null handle");
+  MULTI_EACH(mckpp_hip_step_log_clear(x));
 }
 
 // the caller's arrays pinned on behalf of this handle go back to pageable memory (before the caller frees them)

@@ -24,7 +24,7 @@ program kpp_driver
                                mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, &
                                mckpp_hip_all_window_record_release, mckpp_hip_all_restart_schedule, &
                                mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
-                               mckpp_hip_all_restart_snapshot_release
+                               mckpp_hip_all_restart_snapshot_release, mckpp_hip_all_step_log
   implicit none
   character(len=512) :: fin, fout
   integer :: u, nt, nsteps, ncol, nlev, use_1d, ipt, flags
@@ -55,6 +55,8 @@ program kpp_driver
   !           record of the run (appended, record after record)
   !        512 the time loop as ONE forced run under a restart schedule of period 2 (MOD(ntime, 2) == 0 of
   !           mckpp_restart_control); after it every snapshot s goes to <out.bin>.rst<s> (one file per shard)
+  !        1024 the time loop as ONE forced run under a step log of ncol * nsteps records: with flag 128 the located
+  !           warnings of every step of the run, not only of its last
   flags = hdr(6)
   if (iand(flags, 64) /= 0) mckpp_hip_output_mask = MCKPP_F_SCALARS
   ! hdr(7) > 0: that many device shards; hdr(8) = 1 puts them all on HIP device 0 (one-GPU rehearsal of the
@@ -100,11 +102,12 @@ program kpp_driver
 
   kpp_3d_fields%sflux(:, 1:6, 5, 0) = sf6
   call cpu_time(t0)
-  if (iand(flags, 48 + 256 + 512) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
+  if (iand(flags, 48 + 256 + 512 + 1024) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
     allocate (series(ncol, 8, 1))
     series(:, 1, 1) = 0.01_c_double; series(:, 2, 1) = 0; series(:, 3, 1) = 200; series(:, 4, 1) = 0
     series(:, 5, 1) = -150; series(:, 6, 1) = 0; series(:, 7, 1) = 6e-5_c_double; series(:, 8, 1) = 0
     call mckpp_hip_all_set_flux_series(0, 1, series)
+    if (iand(flags, 1024) /= 0) call mckpp_hip_all_step_log(ncol * nsteps, 0)
     if (iand(flags, 32) /= 0) then
       call mckpp_hip_all_window_select([4_c_int32_t, 2_c_int32_t])   ! MCKPP_OUT_HMIX, MCKPP_OUT_T
       call mckpp_hip_all_window_reset()
@@ -151,7 +154,7 @@ program kpp_driver
   write (*, '(a,3es14.6)') 'kpp_driver: hmix min/mean/max ', minval(kpp_3d_fields%hmix, kpp_3d_fields%run_physics), &
         sum(kpp_3d_fields%hmix)/max(1, count(kpp_3d_fields%run_physics)), maxval(kpp_3d_fields%hmix)
 
-  if (iand(flags, 64 + 48 + 256 + 512) == 0 .and. mckpp_hip_host_behind() /= 0) then   ! the default mask: nothing may be stale
+  if (iand(flags, 64 + 48 + 256 + 512 + 1024) == 0 .and. mckpp_hip_host_behind() /= 0) then   ! the default mask: nothing may be stale
     write (0, '(a,i0)') 'kpp_driver: kpp_3d_fields is behind the device after mckpp_physics_driver: ', mckpp_hip_host_behind()
     error stop 2
   end if

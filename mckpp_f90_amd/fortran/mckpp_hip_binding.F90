@@ -395,6 +395,61 @@ module mckpp_hip_binding
       integer(c_int64_t), value :: upto_snap
       integer(c_int) :: rc
     end function
+    ! the step log of the step launches (mckpp_hip_step_log of include/mckpp_hip.h)
+    function mckpp_hip_multi_step_log(handle, capacity, min_passes) bind(C, name="mckpp_hip_multi_step_log") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: capacity
+      integer(c_int), value :: min_passes
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_step_log_count(handle, n_events, n_stored, status_or) &
+        bind(C, name="mckpp_hip_multi_step_log_count") result(rc)
+      import :: c_int, c_int32_t, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: n_events, n_stored
+      integer(c_int32_t), intent(out) :: status_or
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_step_log_fetch(handle, n, nt, point, status, npasses) &
+        bind(C, name="mckpp_hip_multi_step_log_fetch") result(rc)
+      import :: c_int, c_int32_t, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: n
+      integer(c_int32_t), intent(out) :: nt(*), point(*), status(*), npasses(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_step_log_clear(handle) bind(C, name="mckpp_hip_multi_step_log_clear") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_step_log(handle, capacity, min_passes) bind(C, name="mckpp_hip_step_log") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: capacity
+      integer(c_int), value :: min_passes
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_step_log_count(handle, n_events, n_stored, status_or) bind(C, name="mckpp_hip_step_log_count") result(rc)
+      import :: c_int, c_int32_t, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), intent(out) :: n_events, n_stored
+      integer(c_int32_t), intent(out) :: status_or
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_step_log_fetch(handle, n, nt, point, status, npasses) bind(C, name="mckpp_hip_step_log_fetch") result(rc)
+      import :: c_int, c_int32_t, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int64_t), value :: n
+      integer(c_int32_t), intent(out) :: nt(*), point(*), status(*), npasses(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_step_log_clear(handle) bind(C, name="mckpp_hip_step_log_clear") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int) :: rc
+    end function
     function mckpp_hip_multi_release_host_arrays(handle) bind(C, name="mckpp_hip_multi_release_host_arrays") result(rc)
       import :: c_int, c_ptr
       type(c_ptr), value :: handle

@@ -20,6 +20,7 @@ module mckpp_hip_session
   public :: mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, mckpp_hip_all_window_record_release
   public :: mckpp_hip_all_restart_schedule, mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
             mckpp_hip_all_restart_snapshot_release
+  public :: mckpp_hip_all_step_log
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
   public :: mckpp_hip_host_behind
   public :: mckpp_hip_warnings, mckpp_hip_abort_on_zero_pivot, mckpp_hip_report_warnings, mckpp_hip_column_messages
@@ -66,6 +67,8 @@ module mckpp_hip_session
   !> .true. (the reference: CALL MCKPP_ABORT in tridmat): a zero pivot anywhere stops the run after the messages.
   !! .false.: the step's result stands - the pivot replaced by 1.E-12, the statement behind the reference's abort.
   logical, save :: mckpp_hip_abort_on_zero_pivot = .true.
+  !> a step log is set on the devices (mckpp_hip_all_step_log; an upload or a restart load cancels it)
+  logical, save :: step_log_set = .false.
 
 contains
 
@@ -196,6 +199,7 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_upload(mckpp_hip_multi_handle, s), 'mckpp_hip_upload')
     resident = .true.
     host_behind = 0
+    step_log_set = .false.   ! (an upload cancels the step log)
   end subroutine mckpp_hip_push_state
 
   !> HBM -> kpp_3d_fields for the selected field groups.
@@ -327,7 +331,49 @@ contains
                          int(ndtocn, c_int), l2i(kpp_const_fields%L_REST), kpp_const_fields%FLSN, kpp_const_fields%EL), &
                          'mckpp_hip_multi_run_forced')
     call mckpp_hip_device_advanced()
+    if (step_log_set .and. mckpp_hip_warnings) call mckpp_hip_report_step_log()
   end subroutine mckpp_hip_all_run_forced
+
+  !> The step log (mckpp_hip_step_log of include/mckpp_hip.h) on all devices: every column-step of the step launches
+  !! that ends with a non-zero status word, or with at least min_passes passes (0: status only), leaves a record, up to
+  !! `capacity` of them per device; capacity 0 cancels.  With a log set and mckpp_hip_warnings, mckpp_hip_all_run_forced
+  !! writes the reference's located messages for every flagged column-step of the run - not only of its last step -
+  !! and stops on a zero pivot anywhere in it (mckpp_hip_abort_on_zero_pivot), then clears the log.  The state goes to
+  !! the devices first (an upload cancels the log).
+  subroutine mckpp_hip_all_step_log(capacity, min_passes)
+    integer, intent(in) :: capacity, min_passes
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_step_log(mckpp_hip_multi_handle, int(capacity, c_int64_t), int(min_passes, c_int)), &
+                         'mckpp_hip_multi_step_log')
+    step_log_set = capacity > 0
+  end subroutine mckpp_hip_all_step_log
+
+  !> The reference's warnings for every flagged column-step the log holds, in (time step, point) order, each with its
+  !! own time step and the point's dlon / dlat; the scalars of a step that is not the last are gone, so the messages
+  !! take the form without hmix / kmix.  One more line if flagged column-steps found no room in the log.  Clears the log.
+  subroutine mckpp_hip_report_step_log()
+    integer(c_int32_t), allocatable :: nt(:), pt(:), st(:), np(:)
+    integer(c_int64_t) :: n_events, n_stored
+    integer(c_int32_t) :: status_or
+    integer :: i, ipt
+    logical :: zero_pivot
+    call mckpp_hip_check(mckpp_hip_multi_step_log_count(mckpp_hip_multi_handle, n_events, n_stored, status_or), &
+                         'mckpp_hip_multi_step_log_count')
+    allocate (nt(n_stored), pt(n_stored), st(n_stored), np(n_stored))
+    if (n_stored > 0) call mckpp_hip_check(mckpp_hip_multi_step_log_fetch(mckpp_hip_multi_handle, n_stored, nt, pt, st, np), &
+                                           'mckpp_hip_multi_step_log_fetch')
+    zero_pivot = .false.
+    do i = 1, int(n_stored)
+      if (st(i) == 0) cycle   ! (a pass-count event)
+      ipt = pt(i) + 1
+      call mckpp_hip_column_messages(st(i), np(i), int(nt(i)), kpp_3d_fields%dlat(ipt), kpp_3d_fields%dlon(ipt), ipt, &
+                                     .false., 0.0_c_double, 0.0_c_double, zero_pivot)
+    end do
+    if (n_events > n_stored) write (0, '(a,i0,a)') ' MCKPP-HIP: ', n_events - n_stored, &
+      ' flagged column-steps were not recorded: the step log is full'
+    call mckpp_hip_check(mckpp_hip_multi_step_log_clear(mckpp_hip_multi_handle), 'mckpp_hip_multi_step_log_clear')
+    if (iand(status_or, MCKPP_ST_ZERO_PIVOT) /= 0 .and. mckpp_hip_abort_on_zero_pivot) error stop 1   ! MCKPP_ABORT
+  end subroutine mckpp_hip_report_step_log
 
   !> Output windows on the devices (what XIOS does with the fields mckpp_xios_output_control sends,
   !! src/mckpp_xios_io.F90:74-210, run/iodef.xml:88-157): select the MCKPP_OUT_* fields, accumulate once after
@@ -424,6 +470,7 @@ contains
     character(len=*), intent(in) :: path
     call mckpp_hip_push_state()   ! the shards' column maps come from the upload
     call mckpp_hip_check(mckpp_hip_multi_load_restart(mckpp_hip_multi_handle, trim(path)//c_null_char), 'mckpp_hip_multi_load_restart')
+    step_log_set = .false.   ! (a restart load cancels the step log)
     call mckpp_hip_device_advanced()
   end subroutine mckpp_hip_all_load_restart
 
