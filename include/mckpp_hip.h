@@ -195,6 +195,26 @@ int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtoc
  * their X(:,NZP1,1), which nothing reads). */
 int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp);
 
+/* The same override from a resident field, inside the launches.  In the reference it is the driver's last act of a
+ * step (src/mckpp_physics_driver_mod.F90:67-71, src/mckpp_physics_overrides.F90:12-24): step n+1 starts from the
+ * overridden X(:,NZP1,1), and output and restart files, written after the driver, carry it.
+ *   set_bottomtemp: `bottom_temp` (npts, 3D ordering) is compacted to the resident columns into a device array of its
+ *     own and stays resident until replaced; NULL cancels it.  Allocates and zeroes the correction rows of a
+ *     default-physics context, as mckpp_hip_bottomtemp does.  Output, restart and step-log schedules are left alone.
+ *     upload and load_restart cancel the field (the column map may change).
+ *   While a field is resident every MCKPP_MODE_STEP launch - step, run_forced and their multi_ forms, one launch or a
+ *     launch per step - ends each column-step with the three assignments above on its own column, after check_profile
+ *     (climatology reset, no-freeze clamp, isotherm reset) and before the launch's windows, snapshots and the
+ *     column's next step.  rho and cp are those of the step's last vmix; Xs(:,:,:,new) keeps the step's own value.
+ *     init_ocean, vmix_pass and vmix_only never apply it.  Such a launch needs the diagnostics on (rho and cp are
+ *     diagnostics): with them off it fails before anything is launched.
+ *   mckpp_hip_bottomtemp is refused while a field is resident: the override applied twice zeroes tinc_fcorr(:,NZP1)
+ *     and ocnTcorr(:,NZP1).  Drop that call, or cancel the field.
+ *   Cadence: the field is constant within a launch.  A run that updates bottom_temp every ndtupdbottom steps
+ *     (L_UPD_BOTTOM_TEMP of mckpp_boundary_update) cuts its launches there and calls set_bottomtemp with the new
+ *     field between them. */
+int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp);
+
 /* Enable/disable writing of the MCKPP_F_DIAG fields by step/init (default on). */
 int mckpp_hip_set_diagnostics(mckpp_hip_handle h, int on);
 
@@ -276,8 +296,10 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path);
  *     of the call that completed the snapshot only, not for launches queued behind it: they keep running while the
  *     file is written.  Fails, naming the snapshot's step, for a snapshot that is incomplete, released or never existed.
  *   restart_snapshot_release: releases snapshots up to and including upto_snap (complete ones only).
- * What the host applies to the state after a step - the L_VARY_BOTTOM_TEMP override, mckpp_hip_bottomtemp - is not
- * part of a snapshot: a snapshot is the state as the step's kernel left it. */
+ * A snapshot is the state as the step's kernel left it.  The L_VARY_BOTTOM_TEMP override from a resident field
+ * (mckpp_hip_set_bottomtemp) is part of the step's kernel, so it is in the snapshot, as it is in the reference's restart
+ * file; the override the host applies after a launch (mckpp_hip_bottomtemp) is not.  Scheduled output windows
+ * likewise. */
 int mckpp_hip_restart_schedule(mckpp_hip_handle h, int nt_origin, int period, int nslots);
 int mckpp_hip_restart_snapshots(mckpp_hip_handle h, int64_t *first_kept, int64_t *last_complete);
 int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char *path);
@@ -449,6 +471,7 @@ int mckpp_hip_multi_set_diagnostics(mckpp_hip_multi_handle m, int on);
 int mckpp_hip_multi_set_solver_mode(mckpp_hip_multi_handle m, int mode);
 int mckpp_hip_multi_update_ancillaries(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s);
 int mckpp_hip_multi_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp);
+int mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp);
 int mckpp_hip_multi_fluxes(mckpp_hip_multi_handle m, int ntime, const double *taux, const double *tauy,
                            const double *swf, const double *lwf, const double *lhf, const double *shf,
                            const double *rain, const double *snow, int l_rest, double flsn, double el);

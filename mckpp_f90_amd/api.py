@@ -158,6 +158,7 @@ def _bind(lib):
     lib.mckpp_hip_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
     lib.mckpp_hip_fluxes.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8 + [C.c_int, C.c_double, C.c_double]
     lib.mckpp_hip_bottomtemp.argtypes = [C.c_void_p, _dp]
+    lib.mckpp_hip_set_bottomtemp.argtypes = [C.c_void_p, _dp]
     lib.mckpp_hip_set_flux_series.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
     lib.mckpp_hip_run_forced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
     lib.mckpp_hip_init_ocean.argtypes = [C.c_void_p, C.c_int]
@@ -222,6 +223,7 @@ def _bind(lib):
     lib.mckpp_hip_multi_load_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
     lib.mckpp_hip_multi_bottomtemp.argtypes = [C.c_void_p, _dp]
+    lib.mckpp_hip_multi_set_bottomtemp.argtypes = [C.c_void_p, _dp]
     lib.mckpp_hip_multi_fluxes.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8 + [C.c_int, C.c_double, C.c_double]
     lib._mckpp_bound = True
     return lib
@@ -566,6 +568,17 @@ class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog):
         assert bt.shape == (self._npts_cache,)
         _chk(_lib().mckpp_hip_bottomtemp(self._h, bt.ctypes.data_as(_dp)))
 
+    def set_bottomtemp(self, bottom_temp):
+        """bottom_temp(npts) becomes resident: from now on every step launch ends each column-step with the
+        L_VARY_BOTTOM_TEMP override (src/mckpp_physics_overrides.F90:12-24); None cancels it.  Do not also call
+        bottomtemp(): it is refused while a field is resident."""
+        if bottom_temp is None:
+            _chk(_lib().mckpp_hip_set_bottomtemp(self._h, None))
+            return
+        bt = np.ascontiguousarray(bottom_temp, dtype=np.float64)
+        assert bt.shape == (self._npts_cache,)
+        _chk(_lib().mckpp_hip_set_bottomtemp(self._h, bt.ctypes.data_as(_dp)))
+
     def save_restart(self, path):
         _chk(_lib().mckpp_hip_save_restart(self._h, str(path).encode()))
 
@@ -803,6 +816,15 @@ class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog):
         self._hold(out)
         _chk(_lib().mckpp_hip_multi_window_fetch(self._h, int(field), int(op), out.ctypes.data_as(_dp)))
         return out
+
+    def set_bottomtemp(self, bottom_temp):
+        """As MckppHip.set_bottomtemp, on every shard."""
+        if bottom_temp is None:
+            _chk(_lib().mckpp_hip_multi_set_bottomtemp(self._h, None))
+            return
+        bt = np.ascontiguousarray(bottom_temp, dtype=np.float64)
+        assert bt.shape == (self._npts,)
+        _chk(_lib().mckpp_hip_multi_set_bottomtemp(self._h, bt.ctypes.data_as(_dp)))
 
     def save_restart(self, path):
         _chk(_lib().mckpp_hip_multi_save_restart(self._h, str(path).encode()))

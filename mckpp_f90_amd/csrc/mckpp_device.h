@@ -142,6 +142,10 @@ struct mckpp_kparams_t {
   P<mckpp_log_rec> log_rec;
   P<int> log_ctl;
   int log_cap, log_min_passes;
+  // resident bottom temperature of MCKPP_MODE_STEP launches (mckpp_hip_set_bottomtemp; k_column_ps, finish round): one
+  // value per resident column.  Every column-step ends with mckpp_physics_overrides_bottomtemp (overrides.F90:12-24) on
+  // its own column, from bot_temp[c].  Null: nothing is set, no override.
+  P<const double> bot_temp;
 };
 #define MCKPP_SNAP_ROWS 14
 using mckpp_kparams = mckpp_kparams_t<mckpp_ptr_plain>;

@@ -2918,6 +2918,30 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         }
       }
     END_ITEMS
+    // ---- bottom-temperature override (mckpp_physics_overrides_bottomtemp, overrides.F90:12-24; mckpp_hip_set_bottomtemp):
+    // the driver's last act of a step, so the last act of a column-step here - after check_profile's stores above, before
+    // the window and snapshot stage and before M0 publishes the step, so records, snapshots and the column's next step
+    // (refilled from the rows, or going on in this slot: either way it reads T from the rows) all see T(nzp1) = b.
+    // k_bottomtemp's operations in its order, by the item of level nzp1.  Its operands come from memory: T and
+    // tinc_fcorr(nzp1) were stored by this very thread (the loops above; L6 for tinc_fcorr - a view changes hands between
+    // L1 and L2a, never later in a pass), but rho and cp of the last vmix were stored by L1 of this pass, which a slot
+    // that finishes in the pass in which its workgroup went into a view ran on another wave.  So, as the window stage
+    // does: every wave's stores drained, a barrier, then the loads.  Ts(new) keeps the step's own value, as in the
+    // reference.
+    if (p.bot_temp && p.mode == MCKPP_MODE_STEP) {   // (uniform)
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+      __syncthreads();
+      FOR_ITEMS
+        if (!isnzp1 || si[I_FIN] != F_FINAL) continue;
+        const size_t o = ro + (k - 1), od = ro + k;
+        const double b = p.bot_temp[col];
+        const double rho = p.rho[od], cp = p.cp[od];
+        const double tinc = b - p.T[o];                  // :16
+        p.tinc_fcorr[od] = tinc;
+        p.ocnTcorr[od] = tinc * rho * cp / p.dto;        // :17-19
+        p.T[o] = b;                                      // :20
+      END_ITEMS
+    }
     // ---- output windows (mckpp_hip_window_schedule): every scheduled field of a column that has finished its step,
     // sampled from the rows and records just stored - what window_accumulate after the step reads - and folded into
     // the record of the step's window with k_out_sample's operations in its order (a column's steps come here in

@@ -150,6 +150,9 @@ struct mckpp_hip_ctx {
   int *d_log_ctl = nullptr;
   int64_t log_cap = 0;
   int log_min_passes = 0;
+  // the resident bottom temperature (mckpp_hip_set_bottomtemp): ncol values in column order, an array of its own (the
+  // staging buffer is rewritten by every transfer); null: none is set (mckpp_kparams_t::bot_temp)
+  double *d_bot_temp = nullptr;
   hipStream_t snap_stream = nullptr;
   char *h_snap[2] = {nullptr, nullptr};
   hipEvent_t ev_snap[2] = {nullptr, nullptr};
@@ -449,6 +452,7 @@ static void win_cancel(mckpp_hip_ctx *h, int s);
 static int win_cancel_all(mckpp_hip_ctx *h);
 static int snap_cancel(mckpp_hip_ctx *h);
 static int log_cancel(mckpp_hip_ctx *h);
+static int bt_cancel(mckpp_hip_ctx *h);
 
 static void free_state(mckpp_hip_ctx *h)
 {
@@ -456,6 +460,7 @@ static void free_state(mckpp_hip_ctx *h)
   h->nwin = 0;
   snap_cancel(h);   // ... and so are the snapshot slots
   log_cancel(h);    // the step log's records name resident columns
+  bt_cancel(h);     // the resident bottom temperature is compacted to them
   for (auto &p : h->d_prof) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_diag) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_ext_in) { if (p) hipFree(p); p = nullptr; }
@@ -722,6 +727,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
   if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
   if (log_cancel(h)) return -1;       // ... and the step log's records (they name resident columns)
+  if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
   const int64_t npts = s->npts;
   const int nzp1 = h->nzp1;
   std::vector<int> ipt;
@@ -858,16 +864,26 @@ int mckpp_hip_fluxes(mckpp_hip_handle h, int ntime, const double *taux, const do
   return 0;
 }
 
+// default-physics contexts carry no correction rows until someone needs them
+static int ensure_correction_rows(mckpp_hip_ctx *h)
+{
+  if (h->d_ext_out[O_TINC]) return 0;
+  const size_t rowbytes = (size_t)h->ncol * h->ld * sizeof(double);
+  for (auto &p : h->d_ext_out) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
+  return 0;
+}
+
 int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
 {
   if (!h || !bottom_temp) return fail("mckpp_hip_bottomtemp: null argument");
+  if (h->d_bot_temp)
+    return fail("mckpp_hip_bottomtemp: a bottom temperature is resident (mckpp_hip_set_bottomtemp) and every step launch "
+                "already applies the override; a second one would zero tinc_fcorr and ocnTcorr of the bottom level - drop "
+                "this call, or cancel the resident field with mckpp_hip_set_bottomtemp(NULL)");
   if (h->ncol == 0) return 0;
   if (!h->diag) return fail("mckpp_hip_bottomtemp: needs the diagnostics on (rho, cp of the last vmix)");
   HIPCHK(hipSetDevice(h->device));
-  if (!h->d_ext_out[O_TINC]) {   // default-physics contexts carry no correction rows until someone needs them
-    const size_t rowbytes = (size_t)h->ncol * h->ld * sizeof(double);
-    for (auto &p : h->d_ext_out) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
-  }
+  if (ensure_correction_rows(h)) return -1;
   std::vector<double> bt((size_t)h->ncol);
   for (int64_t c = 0; c < h->ncol; ++c) bt[(size_t)c] = bottom_temp[h->ipt[c]];
   if (ensure_stage(h, bt.size())) return -1;
@@ -875,6 +891,36 @@ int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
   mckpp_kparams p;
   fill_params(h, p, 0, MCKPP_MODE_STEP);
   HIPCHK(mckpp_launch_bottomtemp(p, h->d_stage, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+static int bt_cancel(mckpp_hip_ctx *h)
+{
+  if (!h->d_bot_temp) return 0;
+  if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the field
+  hipFree(h->d_bot_temp);
+  h->d_bot_temp = nullptr;
+  return 0;
+}
+
+// The resident form of the override: from here on every MCKPP_MODE_STEP launch ends each column-step with it
+// (k_column_ps, finish round).  Output, restart and step-log schedules are left alone.
+int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
+{
+  const char *who = "mckpp_hip_set_bottomtemp";
+  if (!h) return fail("%s: null handle", who);
+  HIPCHK(hipSetDevice(h->device));
+  if (!bottom_temp) return bt_cancel(h);
+  if (h->npts <= 0) return fail("%s: upload the state first (the field is compacted to the resident columns)", who);
+  if (h->ncol == 0) return 0;
+  if (ensure_correction_rows(h)) return -1;
+  std::vector<double> bt((size_t)h->ncol);
+  for (int64_t c = 0; c < h->ncol; ++c) bt[(size_t)c] = bottom_temp[h->ipt[c]];
+  if (!h->d_bot_temp) HIPCHK(hipMalloc(&h->d_bot_temp, bt.size() * sizeof(double)));
+  // on the launches' stream, behind those already queued (they keep the field they were launched with); the host
+  // image is this call's own, so wait for the copy
+  HIPCHK(hipMemcpyAsync(h->d_bot_temp, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
@@ -955,6 +1001,7 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
     p.log_rec = h->d_log_rec; p.log_ctl = h->d_log_ctl;
     p.log_cap = (int)h->log_cap; p.log_min_passes = h->log_min_passes;
   }
+  if (mode == MCKPP_MODE_STEP) p.bot_temp = h->d_bot_temp;   // (init / vmix / pass never apply the override)
 }
 
 struct forced_run { int ndtocn, l_rest; double flsn, el; };
@@ -972,6 +1019,9 @@ static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_r
 {
   if (!h) return fail("null handle");
   const bool sched = mode == MCKPP_MODE_STEP && nsteps > 0;
+  if (sched && h->d_bot_temp && !h->diag)
+    return fail("%s: a bottom temperature is resident (mckpp_hip_set_bottomtemp) and the diagnostics are switched off "
+                "(mckpp_hip_set_diagnostics): the override needs rho and cp of the last vmix, which are diagnostics", who);
   if (sched && (win_check_launch(h, ntime, nsteps, who) || snap_check_launch(h, ntime, nsteps, who))) return -1;
   if (run_launch(h, ntime, nsteps, mode, forced)) return -1;
   if (sched) win_advance(h, ntime, nsteps);
@@ -1772,6 +1822,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
   if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
   if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
   if (log_cancel(h)) return -1;       // ... and the step log's records
+  if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
   const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
   if (!same_shape) {
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
@@ -2408,6 +2459,7 @@ int mckpp_hip_multi_step(mckpp_hip_multi_handle m, int ntime, int nsteps) { MULT
 int mckpp_hip_multi_synchronize(mckpp_hip_multi_handle m) { MULTI_EACH(mckpp_hip_synchronize(x)); }
 int mckpp_hip_multi_update_ancillaries(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s) { MULTI_EACH(mckpp_hip_update_ancillaries(x, s)); }
 int mckpp_hip_multi_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { MULTI_EACH(mckpp_hip_bottomtemp(x, bottom_temp)); }
+int mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { MULTI_EACH(mckpp_hip_set_bottomtemp(x, bottom_temp)); }
 int mckpp_hip_multi_fluxes(mckpp_hip_multi_handle m, int ntime, const double *taux, const double *tauy, const double *swf,
                            const double *lwf, const double *lhf, const double *shf, const double *rain, const double *snow,
                            int l_rest, double flsn, double el)

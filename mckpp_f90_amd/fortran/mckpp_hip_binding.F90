@@ -134,6 +134,12 @@ module mckpp_hip_binding
       real(c_double), intent(in) :: bottom_temp(*)
       integer(c_int) :: rc
     end function
+    function mckpp_hip_set_bottomtemp(handle, bottom_temp) bind(C, name="mckpp_hip_set_bottomtemp") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      real(c_double), intent(in), optional :: bottom_temp(*)   ! absent: NULL, cancels the resident field
+      integer(c_int) :: rc
+    end function
     function mckpp_hip_save_restart(handle, path) bind(C, name="mckpp_hip_save_restart") result(rc)
       import :: c_int, c_ptr, c_char
       type(c_ptr), value :: handle
@@ -227,6 +233,12 @@ module mckpp_hip_binding
       import :: c_int, c_ptr, c_double
       type(c_ptr), value :: handle
       real(c_double), intent(in) :: bottom_temp(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_set_bottomtemp(handle, bottom_temp) bind(C, name="mckpp_hip_multi_set_bottomtemp") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      real(c_double), intent(in), optional :: bottom_temp(*)   ! absent: NULL, cancels the resident field
       integer(c_int) :: rc
     end function
     function mckpp_hip_multi_init_ocean(handle, ntime) bind(C, name="mckpp_hip_multi_init_ocean") result(rc)

@@ -21,6 +21,7 @@ module mckpp_hip_session
   public :: mckpp_hip_all_restart_schedule, mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
             mckpp_hip_all_restart_snapshot_release
   public :: mckpp_hip_all_step_log
+  public :: mckpp_hip_all_set_bottomtemp, mckpp_hip_bottomtemp_resident
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
   public :: mckpp_hip_host_behind
   public :: mckpp_hip_warnings, mckpp_hip_abort_on_zero_pivot, mckpp_hip_report_warnings, mckpp_hip_column_messages
@@ -69,6 +70,9 @@ module mckpp_hip_session
   logical, save :: mckpp_hip_abort_on_zero_pivot = .true.
   !> a step log is set on the devices (mckpp_hip_all_step_log; an upload or a restart load cancels it)
   logical, save :: step_log_set = .false.
+  !> a bottom temperature is resident on the devices (mckpp_hip_all_set_bottomtemp; an upload or a restart load cancels
+  !! it): the step launches apply the L_VARY_BOTTOM_TEMP override themselves
+  logical, save :: bottomtemp_set = .false.
 
 contains
 
@@ -200,6 +204,7 @@ contains
     resident = .true.
     host_behind = 0
     step_log_set = .false.   ! (an upload cancels the step log)
+    bottomtemp_set = .false.   ! (... and the resident bottom temperature)
   end subroutine mckpp_hip_push_state
 
   !> HBM -> kpp_3d_fields for the selected field groups.
@@ -324,15 +329,41 @@ contains
                          'mckpp_hip_multi_set_flux_series')
   end subroutine mckpp_hip_all_set_flux_series
 
+  !> With kpp_const_fields%L_VARY_BOTTOM_TEMP the run ends every step with mckpp_physics_overrides_bottomtemp, as the
+  !! reference's driver does (src/mckpp_physics_driver_mod.F90:67-71): kpp_3d_fields%bottom_temp as it stands now becomes
+  !! resident first (a run whose bottom_temp changes every ndtupdbottom steps is cut into calls there).
   subroutine mckpp_hip_all_run_forced(nt_first, nsteps, ndtocn)
     integer, intent(in) :: nt_first, nsteps, ndtocn
     call mckpp_hip_push_state()
+    if (kpp_const_fields%L_VARY_BOTTOM_TEMP) then
+      if (.not. allocated(kpp_3d_fields%bottom_temp)) then
+        write (0, '(a)') 'MCKPP-HIP ERROR: L_VARY_BOTTOM_TEMP needs kpp_3d_fields%bottom_temp (mckpp_allocate_3d_optional)'
+        error stop 1
+      end if
+      call mckpp_hip_all_set_bottomtemp(kpp_3d_fields%bottom_temp)
+    end if
     call mckpp_hip_check(mckpp_hip_multi_run_forced(mckpp_hip_multi_handle, int(nt_first, c_int), int(nsteps, c_int), &
                          int(ndtocn, c_int), l2i(kpp_const_fields%L_REST), kpp_const_fields%FLSN, kpp_const_fields%EL), &
                          'mckpp_hip_multi_run_forced')
     call mckpp_hip_device_advanced()
     if (step_log_set .and. mckpp_hip_warnings) call mckpp_hip_report_step_log()
   end subroutine mckpp_hip_all_run_forced
+
+  !> The L_VARY_BOTTOM_TEMP override inside the step launches (mckpp_hip_set_bottomtemp of include/mckpp_hip.h) on all
+  !! devices: bottom_temp(npts) stays resident until replaced, and every step of mckpp_hip_all_run_forced and of
+  !! mckpp_physics_driver ends with mckpp_physics_overrides_bottomtemp (src/mckpp_physics_overrides.F90:12-24) from it;
+  !! mckpp_physics_driver then leaves out its own call after the launch.  Without the argument the field is cancelled.
+  !! The state goes to the devices first (an upload cancels the field).
+  subroutine mckpp_hip_all_set_bottomtemp(bottom_temp)
+    real(c_double), intent(in), optional :: bottom_temp(*)
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle, bottom_temp), 'mckpp_hip_multi_set_bottomtemp')
+    bottomtemp_set = present(bottom_temp)
+  end subroutine mckpp_hip_all_set_bottomtemp
+
+  logical function mckpp_hip_bottomtemp_resident()
+    mckpp_hip_bottomtemp_resident = bottomtemp_set
+  end function mckpp_hip_bottomtemp_resident
 
   !> The step log (mckpp_hip_step_log of include/mckpp_hip.h) on all devices: every column-step of the step launches
   !! that ends with a non-zero status word, or with at least min_passes passes (0: status only), leaves a record, up to
@@ -471,6 +502,7 @@ contains
     call mckpp_hip_push_state()   ! the shards' column maps come from the upload
     call mckpp_hip_check(mckpp_hip_multi_load_restart(mckpp_hip_multi_handle, trim(path)//c_null_char), 'mckpp_hip_multi_load_restart')
     step_log_set = .false.   ! (a restart load cancels the step log)
+    bottomtemp_set = .false.   ! (... and the resident bottom temperature)
     call mckpp_hip_device_advanced()
   end subroutine mckpp_hip_all_load_restart
 

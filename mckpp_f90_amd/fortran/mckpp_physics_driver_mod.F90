@@ -22,8 +22,10 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_set_forcing(mckpp_hip_multi_handle, kpp_3d_fields%sflux), 'mckpp_hip_set_forcing')
     ! every device's shard is launched before anything waits (the download below is the first wait)
     call mckpp_hip_check(mckpp_hip_multi_step(mckpp_hip_multi_handle, int(ntime, c_int), 1_c_int), 'mckpp_hip_step')
-    ! mckpp_physics_overrides_bottomtemp after the column loop (src/mckpp_physics_driver_mod.F90:67-71)
-    if (kpp_const_fields%L_VARY_BOTTOM_TEMP) then
+    ! mckpp_physics_overrides_bottomtemp after the column loop (src/mckpp_physics_driver_mod.F90:67-71); with a resident
+    ! field (mckpp_hip_all_set_bottomtemp) the launch above has applied it already, and a second one would zero the
+    ! bottom level's tinc_fcorr and ocnTcorr
+    if (kpp_const_fields%L_VARY_BOTTOM_TEMP .and. .not. mckpp_hip_bottomtemp_resident()) then
       if (.not. allocated(kpp_3d_fields%bottom_temp)) then
         write (0, '(a)') 'MCKPP-HIP ERROR: L_VARY_BOTTOM_TEMP needs kpp_3d_fields%bottom_temp (mckpp_allocate_3d_optional)'
         error stop 1
