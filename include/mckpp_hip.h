@@ -210,10 +210,55 @@ int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp);
  *     diagnostics): with them off it fails before anything is launched.
  *   mckpp_hip_bottomtemp is refused while a field is resident: the override applied twice zeroes tinc_fcorr(:,NZP1)
  *     and ocnTcorr(:,NZP1).  Drop that call, or cancel the field.
- *   Cadence: the field is constant within a launch.  A run that updates bottom_temp every ndtupdbottom steps
- *     (L_UPD_BOTTOM_TEMP of mckpp_boundary_update) cuts its launches there and calls set_bottomtemp with the new
- *     field between them. */
+ *   Cadence: the field set here is constant within a launch.  A run that updates bottom_temp every ndtupdbottom steps
+ *     (L_UPD_BOTTOM_TEMP of mckpp_boundary_update) either cuts its launches there and calls set_bottomtemp with the new
+ *     field between them, or keeps the records resident and schedules them (mckpp_hip_ancillary_schedule with
+ *     MCKPP_ANC_BOTTOM_TEMP, below).  The two are mutually exclusive: the second one asked for is refused. */
 int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp);
+
+/* Ancillary record series: what mckpp_boundary_update (src/mckpp_boundary_update_mod.F90:24-124, called for every
+ * nt /= 1 at src/mckpp_ocean_model_3D.F90:51-55) rewrites at the ndtupd* cadences, and with L_INTERP_OCNT /
+ * L_INTERP_SAL every ndt_interp_* steps as a weighted sum of two records (src/mckpp_boundary_interpolate.F90:14-121),
+ * inside the launches.  Columns of one launch are at different steps, so nothing is rewritten in place: the records
+ * are resident and immutable, and every column-step selects its own record, or pair and weights, from the step it is in.
+ *   set_ancillary_series keeps `nrec` records of one kind on the device: records[rec][npts] for the 2-D kinds (SST0,
+ *     FCORR_TWOD, BOTTOM_TEMP), records[rec][nzp1][npts] for the others - each record the Fortran array (npts) or
+ *     (npts, nzp1) the reference's reader leaves in kpp_3d_fields.  Record 0 of the array is record number `rec0` of
+ *     the run.  Compacted to the resident columns; the 3-D kinds re-laid into rows as upload does.  Ordered on the
+ *     context's stream behind the launches already queued; `records` may change when the call returns.  A call replaces
+ *     the kind's resident records; nrec = 0 frees them (records may then be NULL).
+ *   ancillary_schedule: step nt belongs to epoch (nt - nt_origin) / cadence, and epochs[i] describes epoch epoch0 + i:
+ *     rec_next < 0: the field of the epoch is record rec_prev as it is, no arithmetic; otherwise it is
+ *     record[rec_next]*w_next + record[rec_prev]*w_prev, two products and a sum in that order
+ *     (boundary_interpolate.F90:60, :115), each separately rounded.  Interpolated epochs are accepted for OCNT_CLIM and
+ *     SAL_CLIM only, as in the reference.  nepochs = 0 cancels the schedule.  Records are named by their number in
+ *     the run; which file position the reference's reader would pick (mckpp_get_update_time) stays with the caller,
+ *     as for the flux series.  mckpp_host_interp_weights gives the weights.
+ *   While a kind has a schedule every MCKPP_MODE_STEP launch - step, run_forced, their multi_ forms, one launch or a
+ *     launch per step - reads that kind, for each column-step, from the series through its epoch; the plain resident
+ *     copy that update_ancillaries / set_bottomtemp write is left alone and not read by those launches.  The climatology
+ *     that a step's check_profile resets to is that step's.  init_ocean, vmix_pass and vmix_only are unaffected.  A launch
+ *     with a step before nt_origin, an epoch outside the table or a record that is not resident fails before anything is
+ *     launched, naming kind, step, epoch and record.
+ *   BOTTOM_TEMP with a schedule is the in-launch override of set_bottomtemp with the record chosen per column-step:
+ *     the same rules (diagnostics on, mckpp_hip_bottomtemp refused), and refused while a set_bottomtemp field is resident.
+ *   The other kinds are refused on a context without optional physics (none of L_RELAX_SST, L_FCORR, L_FCORR_WITHZ,
+ *     L_SFCORR_WITHZ, L_RELAX_OCNT, L_RELAX_SAL, L_NO_ISOTHERM, clim_present, ...): nothing there reads them.
+ *   upload and load_restart cancel all series and schedules (the column map may change).  Output windows, restart
+ *     snapshots and the step log are left alone. */
+enum { MCKPP_ANC_SST0 = 0, MCKPP_ANC_FCORR_TWOD, MCKPP_ANC_FCORR_WITHZ, MCKPP_ANC_SFCORR_WITHZ,
+       MCKPP_ANC_OCNT_CLIM, MCKPP_ANC_SAL_CLIM, MCKPP_ANC_BOTTOM_TEMP, MCKPP_ANC_COUNT };
+typedef struct { int32_t rec_prev, rec_next; double w_prev, w_next; } mckpp_anc_epoch_c;
+int mckpp_hip_set_ancillary_series(mckpp_hip_handle h, int kind, int rec0, int nrec, const double *records);
+int mckpp_hip_ancillary_schedule(mckpp_hip_handle h, int kind, int nt_origin, int cadence, int epoch0, int nepochs,
+                                 const mckpp_anc_epoch_c *epochs);
+
+/* The weights of mckpp_boundary_interpolate_temp / _sal (src/mckpp_boundary_interpolate.F90:25-35, :49-50; :80-90,
+ * :104-105) at model time `time` (days) for records ndtupd steps of dto seconds apart (spd seconds per day), with the
+ * reference's INTEGER true_time, prev_time and next_time (a REAL assigned to an INTEGER truncates toward zero) and its
+ * prev_time < 0 branch, which adds `period`.  A restatement: no compiled reference pins it. */
+void mckpp_host_interp_weights(double time, int32_t ndtupd, double dto, double spd, int32_t period, int32_t *prev_time,
+                               int32_t *next_time, double *w_prev, double *w_next);
 
 /* Enable/disable writing of the MCKPP_F_DIAG fields by step/init (default on). */
 int mckpp_hip_set_diagnostics(mckpp_hip_handle h, int on);
@@ -472,6 +517,9 @@ int mckpp_hip_multi_set_solver_mode(mckpp_hip_multi_handle m, int mode);
 int mckpp_hip_multi_update_ancillaries(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s);
 int mckpp_hip_multi_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp);
 int mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp);
+int mckpp_hip_multi_set_ancillary_series(mckpp_hip_multi_handle m, int kind, int rec0, int nrec, const double *records);
+int mckpp_hip_multi_ancillary_schedule(mckpp_hip_multi_handle m, int kind, int nt_origin, int cadence, int epoch0,
+                                       int nepochs, const mckpp_anc_epoch_c *epochs);
 int mckpp_hip_multi_fluxes(mckpp_hip_multi_handle m, int ntime, const double *taux, const double *tauy,
                            const double *swf, const double *lwf, const double *lhf, const double *shf,
                            const double *rain, const double *snow, int l_rest, double flsn, double el);

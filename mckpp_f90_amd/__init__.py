@@ -39,6 +39,7 @@ from .api import (  # noqa: E402,F401
     MckppHipMulti,
     MckppHipError,
     host_shard_mask,
+    interp_weights,
     mckpp_initialize_ocean_model,
     mckpp_physics_driver,
     mckpp_physics_lookup,

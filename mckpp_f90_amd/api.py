@@ -126,6 +126,27 @@ def _win_check_fetch(scheds, sched, field, op):
     return f
 
 
+# kinds of the ancillary record series (MCKPP_ANC_* of mckpp_hip.h)
+(ANC_SST0, ANC_FCORR_TWOD, ANC_FCORR_WITHZ, ANC_SFCORR_WITHZ, ANC_OCNT_CLIM, ANC_SAL_CLIM, ANC_BOTTOM_TEMP,
+ ANC_COUNT) = range(8)
+ANC_3D = (ANC_FCORR_WITHZ, ANC_SFCORR_WITHZ, ANC_OCNT_CLIM, ANC_SAL_CLIM)
+
+
+class _AncEpochC(C.Structure):
+    """mckpp_anc_epoch_c"""
+    _fields_ = [("rec_prev", C.c_int32), ("rec_next", C.c_int32), ("w_prev", C.c_double), ("w_next", C.c_double)]
+
+
+def interp_weights(time, ndtupd, dto, spd=86400.0, period=0):
+    """(prev_time, next_time, w_prev, w_next) of mckpp_boundary_interpolate_temp / _sal at model time `time` (days):
+    mckpp_host_interp_weights, the reference's INTEGER times and its prev_time < 0 branch included."""
+    lib = _lib()
+    pt, nx, wp, wn = C.c_int32(), C.c_int32(), C.c_double(), C.c_double()
+    lib.mckpp_host_interp_weights(float(time), int(ndtupd), float(dto), float(spd), int(period), C.byref(pt), C.byref(nx),
+                                  C.byref(wp), C.byref(wn))
+    return int(pt.value), int(nx.value), float(wp.value), float(wn.value)
+
+
 class MckppHipError(RuntimeError):
     pass
 
@@ -159,6 +180,12 @@ def _bind(lib):
     lib.mckpp_hip_fluxes.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8 + [C.c_int, C.c_double, C.c_double]
     lib.mckpp_hip_bottomtemp.argtypes = [C.c_void_p, _dp]
     lib.mckpp_hip_set_bottomtemp.argtypes = [C.c_void_p, _dp]
+    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
+        getattr(lib, pre + "set_ancillary_series").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
+        getattr(lib, pre + "ancillary_schedule").argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(_AncEpochC)]
+    lib.mckpp_host_interp_weights.argtypes = [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
+                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp]
+    lib.mckpp_host_interp_weights.restype = None
     lib.mckpp_hip_set_flux_series.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
     lib.mckpp_hip_run_forced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
     lib.mckpp_hip_init_ocean.argtypes = [C.c_void_p, C.c_int]
@@ -491,7 +518,43 @@ class _StepLog:
         _chk(getattr(_lib(), self._pre + "step_log_clear")(self._h))
 
 
-class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog):
+class _AncillarySeries:
+    """Ancillary record series and their schedules (mckpp_hip_set_ancillary_series, mckpp_hip_ancillary_schedule), for
+    one context or for all shards of a multi handle (_pre)."""
+    _pre = "mckpp_hip_"
+    interp_weights = staticmethod(interp_weights)
+
+    def set_ancillary_series(self, kind, rec0, records):
+        """records[nrec, npts] (ANC_SST0, ANC_FCORR_TWOD, ANC_BOTTOM_TEMP) or records[nrec, nzp1, npts] (the others) become
+        the kind's resident records, number rec0 of the run first; None or an empty array frees them."""
+        kind = int(kind)
+        if records is None or len(records) == 0:
+            _chk(getattr(_lib(), self._pre + "set_ancillary_series")(self._h, kind, int(rec0), 0, None))
+            return
+        r = np.ascontiguousarray(records, dtype=np.float64)
+        n = self._npts() if callable(self._npts) else self._npts
+        if r.ndim != (3 if kind in ANC_3D else 2) or r.shape[-1] != n:
+            raise ValueError(f"set_ancillary_series: kind {kind} takes records[nrec{', nzp1' if kind in ANC_3D else ''}, "
+                             f"npts={n}], got {r.shape}")
+        self._hold(r)
+        _chk(getattr(_lib(), self._pre + "set_ancillary_series")(self._h, kind, int(rec0), int(r.shape[0]), r.ctypes.data_as(_dp)))
+
+    def ancillary_schedule(self, kind, nt_origin, cadence, epochs, epoch0=0):
+        """Step nt is in epoch (nt - nt_origin) // cadence; epochs[i] describes epoch epoch0 + i: a record number (the
+        record as it is), or (rec_prev, rec_next, w_prev, w_next) for record[rec_next]*w_next + record[rec_prev]*w_prev
+        (ANC_OCNT_CLIM and ANC_SAL_CLIM only).  None or no epochs: cancel the kind's schedule."""
+        ep = list(epochs) if epochs is not None else []
+        arr = (_AncEpochC * max(1, len(ep)))()
+        for i, e in enumerate(ep):
+            if np.ndim(e) == 0:
+                arr[i] = _AncEpochC(int(e), -1, 0.0, 0.0)
+            else:
+                arr[i] = _AncEpochC(int(e[0]), int(e[1]), float(e[2]), float(e[3]))
+        _chk(getattr(_lib(), self._pre + "ancillary_schedule")(self._h, int(kind), int(nt_origin), int(cadence), int(epoch0),
+                                                              len(ep), arr))
+
+
+class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries):
     """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
 
     def __init__(self, kpp_const_fields, device=0):
@@ -706,7 +769,7 @@ class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog):
         return y
 
 
-class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog):
+class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries):
     """Several GPUs behind one handle (mckpp_hip_multi_*): columns dealt round-robin to the devices."""
     _pre = "mckpp_hip_multi_"
 

@@ -53,6 +53,11 @@ struct mckpp_win_t {
   int origin, period, nrec;
 };
 
+// One column-step's selection of one ancillary kind (mckpp_kparams_t::anc_sel): offsets in doubles from the kind's records
+#define MCKPP_ANC_KINDS 7
+enum { ANC_SST0 = 0, ANC_FCORR_TWOD, ANC_FCORR_WITHZ, ANC_SFCORR_WITHZ, ANC_OCNT_CLIM, ANC_SAL_CLIM, ANC_BOTTOM_TEMP };
+struct mckpp_anc_sel { long long off_prev, off_next; double w_prev, w_next; };
+
 // A record of the step log: {nt, resident column, status word, passes} of one column-step, one 16-byte store
 typedef int mckpp_log_rec __attribute__((ext_vector_type(4)));
 
@@ -146,6 +151,15 @@ struct mckpp_kparams_t {
   // value per resident column.  Every column-step ends with mckpp_physics_overrides_bottomtemp (overrides.F90:12-24) on
   // its own column, from bot_temp[c].  Null: nothing is set, no override.
   P<const double> bot_temp;
+  // ancillary record series of MCKPP_MODE_STEP launches (mckpp_hip_ancillary_schedule).  Bit `kind` of anc_mask: the kind
+  // has a schedule, and a column-step reads it not from xs / the rows above / bot_temp but from anc_rec[kind] - records
+  // [ncol] (2-D kinds) or [ncol][ld] - through the selection of its own step: entry (nt - anc_nt0) * MCKPP_ANC_KINDS +
+  // kind of anc_sel, which the host writes per launch call.  off_next < 0: the record at off_prev as it is; otherwise
+  // rec[off_next + i] * w_next + rec[off_prev + i] * w_prev (boundary_interpolate.F90:60, :115).  Nothing is ever
+  // rewritten in place: columns of one launch are at different steps.  anc_mask 0: no schedule, the plain pointers.
+  P<const mckpp_anc_sel> anc_sel;
+  P<const double> anc_rec[MCKPP_ANC_KINDS];
+  int anc_mask, anc_nt0;
 };
 #define MCKPP_SNAP_ROWS 14
 using mckpp_kparams = mckpp_kparams_t<mckpp_ptr_plain>;

@@ -1783,6 +1783,21 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     }
   };
 
+  // ---- an ancillary field as the column-step of slot record `si` sees it (mckpp_hip_ancillary_schedule).  No schedule
+  // for the kind (a uniform branch): element ip of the plain resident copy.  Otherwise element ir of the record the step
+  // it is in selects from the kind's immutable resident records, or of its pair: next*w_next + prev*w_prev, two products
+  // and a sum in that order (boundary_interpolate.F90:60, :115).  Columns of one launch are at different steps, so the
+  // selection is the item's own: one small load from the launch's table (mckpp_kparams_t::anc_sel).
+  auto anc_read = [&](const int kind, const int *si, const auto plain, const size_t ip, const size_t ir) -> double {
+    if (!((p.anc_mask >> kind) & 1)) return plain[ip];
+    const auto e = p.anc_sel + ((size_t)(ntime + si[I_STEP] - p.anc_nt0) * MCKPP_ANC_KINDS + kind);
+    const auto r = p.anc_rec[kind];
+    const long long on = e->off_next;
+    const double prv = r[e->off_prev + (long long)ir];
+    if (on < 0) return prv;
+    return r[on + (long long)ir] * e->w_next + prv * e->w_prev;
+  };
+
   // ---- optional terms of the T and S right-hand sides (ocnint_mod.F90:97-215), level k of item (my, si, col):
   // relaxation / flux corrections / prescribed advection (rhsmod, solvers.F90:176-335, salinity only)
   auto ext_rhs = [&](double *my, const int *si, int col, int k, int kmixe, double To_k, double So_k, double &rhsT,
@@ -1793,7 +1808,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     const size_t oin = (size_t)col * p.ld + (k - 1);
     if (k == 1) {
       if (p.L_RELAX_SST && !p.L_FCORR_WITHZ && !p.L_FCORR) {   // :97-114
-        const double relax_sst = xs[XS_RELAX_SST], SST0 = xs[XS_SST0];
+        const double relax_sst = xs[XS_RELAX_SST], SST0 = anc_read(ANC_SST0, si, xs, XS_SST0, col);
         double fc = 0.0;
         if (relax_sst > 1.e-10) {
           if (!p.L_RELAX_CALCONLY) rhsT = rhsT + dto * relax_sst * (SST0 - To_k) * p.dm[kmixe] / c_hm[1];
@@ -1802,11 +1817,11 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         p.cs[(size_t)col * MCKPP_CS + CS_FCORR] = fc;
       }
       if (p.L_FCORR && !p.L_RELAX_SST && !p.L_FCORR_WITHZ)     // :121-125
-        rhsT = rhsT + dto * xs[XS_FCORR_TWOD] / (rhok * cpk * c_hm[1]);
+        rhsT = rhsT + dto * anc_read(ANC_FCORR_TWOD, si, xs, XS_FCORR_TWOD, col) / (rhok * cpk * c_hm[1]);
     }
     double tinc = 0.;                                           // :133-160
-    if (p.L_FCORR_WITHZ && !p.L_FCORR) tinc = dto * p.fcorr_withz[oin] / (rhok * cpk);
-    if (p.L_RELAX_OCNT) tinc = tinc + dto * xs[XS_RELAX_OCNT] * (p.ocnT_clim[oin] - To_k);
+    if (p.L_FCORR_WITHZ && !p.L_FCORR) tinc = dto * anc_read(ANC_FCORR_WITHZ, si, p.fcorr_withz, oin, oin) / (rhok * cpk);
+    if (p.L_RELAX_OCNT) tinc = tinc + dto * xs[XS_RELAX_OCNT] * (anc_read(ANC_OCNT_CLIM, si, p.ocnT_clim, oin, oin) - To_k);
     rhsT = rhsT + tinc;
     const double ocnTcorr = tinc * rhok * cpk / dto;
     // prescribed advection of salinity, rhsmod with jsclr = 2 (:179-184)
@@ -1850,8 +1865,8 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       }
     }
     double sinc = 0.;                                           // :187-213
-    if (p.L_SFCORR_WITHZ && !p.L_SFCORR) sinc = dto * p.sfcorr_withz[oin];
-    if (p.L_RELAX_SAL) sinc = sinc + dto * xs[XS_RELAX_SAL] * (p.sal_clim[oin] - So_k);
+    if (p.L_SFCORR_WITHZ && !p.L_SFCORR) sinc = dto * anc_read(ANC_SFCORR_WITHZ, si, p.sfcorr_withz, oin, oin);
+    if (p.L_RELAX_SAL) sinc = sinc + dto * xs[XS_RELAX_SAL] * (anc_read(ANC_SAL_CLIM, si, p.sal_clim, oin, oin) - So_k);
     rhsS = rhsS + sinc;
     // tinc_fcorr of the latest pass is what check_profile adds to (overrides.F90:87-88): always stored
     const size_t o = (size_t)col * p.ld + k;
@@ -2792,7 +2807,10 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       if (act) { U = row(Q_YU)[k]; V = row(Q_YV)[k]; T = row(Q_YT)[k]; S = row(Q_YS)[k]; }
       if (act) { p.Us[newi][o] = U; p.Vs[newi][o] = V; p.Ts[newi][o] = T; p.Ss[newi][o] = S; }
       if (si[I_COMP] && act) {   // overrides.F90:57-78
-        if (p.clim_present) { T = p.ocnT_clim[o]; S = p.sal_clim[o]; row(Q_YT)[k] = T; row(Q_YS)[k] = S; }
+        if (p.clim_present) {   // (the step's own climatology)
+          T = anc_read(ANC_OCNT_CLIM, si, p.ocnT_clim, o, o); S = anc_read(ANC_SAL_CLIM, si, p.sal_clim, o, o);
+          row(Q_YT)[k] = T; row(Q_YS)[k] = S;
+        }
         U = p.U_init[o]; V = p.V_init[o];
         row(Q_YU)[k] = U; row(Q_YV)[k] = V;
       }
@@ -2849,7 +2867,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         }
         if (act) {
           double U = row(Q_YU)[k], V = row(Q_YV)[k], T = row(Q_YT)[k], S = row(Q_YS)[k];
-          if (EXT && iso_reset) { T = p.ocnT_clim[o]; S = p.sal_clim[o]; }
+          if (EXT && iso_reset) { T = anc_read(ANC_OCNT_CLIM, si, p.ocnT_clim, o, o); S = anc_read(ANC_SAL_CLIM, si, p.sal_clim, o, o); }
           p.U[o] = U; p.V[o] = V; p.T[o] = T; p.S[o] = S;
         }
         if (is1) {
@@ -2928,13 +2946,13 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     // that finishes in the pass in which its workgroup went into a view ran on another wave.  So, as the window stage
     // does: every wave's stores drained, a barrier, then the loads.  Ts(new) keeps the step's own value, as in the
     // reference.
-    if (p.bot_temp && p.mode == MCKPP_MODE_STEP) {   // (uniform)
+    if ((p.bot_temp || (p.anc_mask >> ANC_BOTTOM_TEMP & 1)) && p.mode == MCKPP_MODE_STEP) {   // (uniform)
       asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
       __syncthreads();
       FOR_ITEMS
         if (!isnzp1 || si[I_FIN] != F_FINAL) continue;
         const size_t o = ro + (k - 1), od = ro + k;
-        const double b = p.bot_temp[col];
+        const double b = anc_read(ANC_BOTTOM_TEMP, si, p.bot_temp, col, col);   // the resident field, or the step's record
         const double rho = p.rho[od], cp = p.cp[od];
         const double tinc = b - p.T[o];                  // :16
         p.tinc_fcorr[od] = tinc;

@@ -153,6 +153,18 @@ struct mckpp_hip_ctx {
   // the resident bottom temperature (mckpp_hip_set_bottomtemp): ncol values in column order, an array of its own (the
   // staging buffer is rewritten by every transfer); null: none is set (mckpp_kparams_t::bot_temp)
   double *d_bot_temp = nullptr;
+  // ancillary record series and their schedules (mckpp_hip_set_ancillary_series, mckpp_hip_ancillary_schedule), per kind:
+  // `nrec` immutable records from number rec0 on, compacted to the resident columns ([ncol], or rows [ncol][ld]); step nt
+  // belongs to epoch (nt - origin) / cadence, which ep[epoch - epoch0] describes (ep empty: no schedule).  d_anc_sel is the
+  // selection table of the latest launch call ([nsteps][kinds], mckpp_kparams_t::anc_sel), written on the stream ahead of
+  // its kernels from one of two pinned host images.
+  struct anc_kind { double *d = nullptr; int rec0 = 0, nrec = 0, origin = 0, cadence = 0, epoch0 = 0; std::vector<mckpp_anc_epoch_c> ep; };
+  anc_kind anc[MCKPP_ANC_COUNT];
+  mckpp_anc_sel *d_anc_sel = nullptr, *h_anc_sel[2] = {nullptr, nullptr};
+  size_t anc_sel_cap = 0, h_anc_sel_cap[2] = {0, 0};
+  hipEvent_t ev_anc[2] = {nullptr, nullptr};
+  unsigned anc_seq = 0;
+  int anc_mask = 0, anc_nt0 = 0;   // of the launch call being issued (anc_prepare)
   hipStream_t snap_stream = nullptr;
   char *h_snap[2] = {nullptr, nullptr};
   hipEvent_t ev_snap[2] = {nullptr, nullptr};
@@ -453,6 +465,7 @@ static int win_cancel_all(mckpp_hip_ctx *h);
 static int snap_cancel(mckpp_hip_ctx *h);
 static int log_cancel(mckpp_hip_ctx *h);
 static int bt_cancel(mckpp_hip_ctx *h);
+static int anc_cancel_all(mckpp_hip_ctx *h);
 
 static void free_state(mckpp_hip_ctx *h)
 {
@@ -461,6 +474,7 @@ static void free_state(mckpp_hip_ctx *h)
   snap_cancel(h);   // ... and so are the snapshot slots
   log_cancel(h);    // the step log's records name resident columns
   bt_cancel(h);     // the resident bottom temperature is compacted to them
+  anc_cancel_all(h);   // ... and so are the ancillary records
   for (auto &p : h->d_prof) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_diag) { if (p) hipFree(p); p = nullptr; }
   for (auto &p : h->d_ext_in) { if (p) hipFree(p); p = nullptr; }
@@ -524,7 +538,10 @@ int mckpp_hip_finalize(mckpp_hip_handle h)
     if (h->ev_lay[b]) hipEventDestroy(h->ev_lay[b]);
     if (h->ev_copy[b]) hipEventDestroy(h->ev_copy[b]);
     if (h->ev_params[b]) hipEventDestroy(h->ev_params[b]);
+    if (h->ev_anc[b]) hipEventDestroy(h->ev_anc[b]);
+    if (h->h_anc_sel[b]) hipHostFree(h->h_anc_sel[b]);
   }
+  if (h->d_anc_sel) hipFree(h->d_anc_sel);
   if (h->ev_f) hipEventDestroy(h->ev_f);
   if (h->h_params) hipHostFree(h->h_params);
   if (h->copy_stream) hipStreamDestroy(h->copy_stream);
@@ -728,6 +745,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
   if (log_cancel(h)) return -1;       // ... and the step log's records (they name resident columns)
   if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
+  if (anc_cancel_all(h)) return -1;   // ... and the ancillary record series and their schedules (likewise)
   const int64_t npts = s->npts;
   const int nzp1 = h->nzp1;
   std::vector<int> ipt;
@@ -880,6 +898,10 @@ int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
     return fail("mckpp_hip_bottomtemp: a bottom temperature is resident (mckpp_hip_set_bottomtemp) and every step launch "
                 "already applies the override; a second one would zero tinc_fcorr and ocnTcorr of the bottom level - drop "
                 "this call, or cancel the resident field with mckpp_hip_set_bottomtemp(NULL)");
+  if (!h->anc[MCKPP_ANC_BOTTOM_TEMP].ep.empty())
+    return fail("mckpp_hip_bottomtemp: the bottom temperature has a schedule (mckpp_hip_ancillary_schedule) and every step "
+                "launch already applies the override; a second one would zero tinc_fcorr and ocnTcorr of the bottom level - "
+                "drop this call, or cancel the schedule");
   if (h->ncol == 0) return 0;
   if (!h->diag) return fail("mckpp_hip_bottomtemp: needs the diagnostics on (rho, cp of the last vmix)");
   HIPCHK(hipSetDevice(h->device));
@@ -912,6 +934,9 @@ int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
   if (!h) return fail("%s: null handle", who);
   HIPCHK(hipSetDevice(h->device));
   if (!bottom_temp) return bt_cancel(h);
+  if (!h->anc[MCKPP_ANC_BOTTOM_TEMP].ep.empty())
+    return fail("%s: the bottom temperature has a schedule (mckpp_hip_ancillary_schedule, MCKPP_ANC_BOTTOM_TEMP); the two "
+                "are mutually exclusive - cancel the schedule first", who);
   if (h->npts <= 0) return fail("%s: upload the state first (the field is compacted to the resident columns)", who);
   if (h->ncol == 0) return 0;
   if (ensure_correction_rows(h)) return -1;
@@ -923,6 +948,197 @@ int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
   HIPCHK(hipMemcpyAsync(h->d_bot_temp, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// Ancillary record series: boundary updates inside the launches
+// ---------------------------------------------------------------------------
+static const char *const anc_names[MCKPP_ANC_COUNT] = {"SST0", "fcorr_twod", "fcorr_withz", "sfcorr_withz", "ocnT_clim",
+                                                       "sal_clim", "bottom_temp"};
+static_assert(MCKPP_ANC_COUNT == MCKPP_ANC_KINDS && (int)MCKPP_ANC_BOTTOM_TEMP == (int)ANC_BOTTOM_TEMP &&
+              (int)MCKPP_ANC_OCNT_CLIM == (int)ANC_OCNT_CLIM, "the kinds of the header are those of the kernel");
+static bool anc_is_3d(int kind) { return kind >= MCKPP_ANC_FCORR_WITHZ && kind <= MCKPP_ANC_SAL_CLIM; }
+static size_t anc_stride(const mckpp_hip_ctx *h, int kind) { return anc_is_3d(kind) ? (size_t)h->ncol * h->ld : (size_t)h->ncol; }
+
+static int anc_free_records(mckpp_hip_ctx *h, int kind)
+{
+  auto &a = h->anc[kind];
+  if (a.d) {
+    if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the records
+    hipFree(a.d);
+    a.d = nullptr;
+  }
+  a.nrec = 0; a.rec0 = 0;
+  return 0;
+}
+
+static int anc_cancel_all(mckpp_hip_ctx *h)
+{
+  for (int k = 0; k < MCKPP_ANC_COUNT; ++k) {
+    if (anc_free_records(h, k)) return -1;
+    h->anc[k].ep.clear();
+  }
+  return 0;
+}
+
+static int anc_check_kind(mckpp_hip_ctx *h, int kind, const char *who)
+{
+  if (!h) return fail("%s: null handle", who);
+  if (kind < 0 || kind >= MCKPP_ANC_COUNT) return fail("%s: kind=%d (0..%d)", who, kind, MCKPP_ANC_COUNT - 1);
+  if (kind != MCKPP_ANC_BOTTOM_TEMP && !h->ext)
+    return fail("%s: %s on a context of the default physics: nothing there reads it (the switch that does is off: "
+                "L_RELAX_SST / L_FCORR / L_FCORR_WITHZ / L_SFCORR_WITHZ / L_RELAX_OCNT / L_RELAX_SAL / L_NO_ISOTHERM / "
+                "clim_present in mckpp_const_c)", who, anc_names[kind]);
+  return 0;
+}
+
+int mckpp_hip_set_ancillary_series(mckpp_hip_handle h, int kind, int rec0, int nrec, const double *records)
+{
+  const char *who = "mckpp_hip_set_ancillary_series";
+  if (anc_check_kind(h, kind, who)) return -1;
+  if (nrec < 0 || rec0 < 0 || (nrec > 0 && !records))
+    return fail("%s: %s rec0=%d nrec=%d records=%s", who, anc_names[kind], rec0, nrec, records ? "set" : "NULL");
+  if (nrec > 0 && h->npts <= 0) return fail("%s: upload the state first (the records are compacted to the resident columns)", who);
+  HIPCHK(hipSetDevice(h->device));
+  if (anc_free_records(h, kind)) return -1;
+  if (nrec == 0) return 0;
+  auto &a = h->anc[kind];
+  if (h->ncol > 0) {
+    const size_t stride = anc_stride(h, kind), n = stride * (size_t)nrec;
+    HIPCHK(hipMalloc(&a.d, n * sizeof(double)));
+    if (anc_is_3d(kind)) {   // rows, by the path of upload / update_ancillaries
+      const size_t slab = (size_t)h->npts * h->nzp1;
+      HIPCHK(hipMemsetAsync(a.d, 0, n * sizeof(double), h->stream));
+      for (int r = 0; r < nrec; ++r)
+        if (up_rows(h, records + (size_t)r * slab, h->nzp1, a.d + (size_t)r * stride, 0, records, slab * (size_t)nrec)) return -1;
+      if (xfer_finish(h)) return -1;   // the caller's array is its own again
+    } else {
+      std::vector<double> f(n);
+      for (int r = 0; r < nrec; ++r)
+        for (int64_t c = 0; c < h->ncol; ++c) f[(size_t)r * stride + (size_t)c] = records[(size_t)r * (size_t)h->npts + h->ipt[c]];
+      // on the launches' stream, behind those already queued; the host image is this call's own, so wait for the copy
+      HIPCHK(hipMemcpyAsync(a.d, f.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipStreamSynchronize(h->stream));
+    }
+  }
+  a.rec0 = rec0;
+  a.nrec = nrec;
+  return 0;
+}
+
+int mckpp_hip_ancillary_schedule(mckpp_hip_handle h, int kind, int nt_origin, int cadence, int epoch0, int nepochs,
+                                 const mckpp_anc_epoch_c *epochs)
+{
+  const char *who = "mckpp_hip_ancillary_schedule";
+  if (anc_check_kind(h, kind, who)) return -1;
+  if (nepochs < 0) return fail("%s: %s nepochs=%d", who, anc_names[kind], nepochs);
+  if (nepochs == 0) { h->anc[kind].ep.clear(); return 0; }
+  if (!epochs || cadence < 1 || epoch0 < 0 || nt_origin < 0)
+    return fail("%s: %s nt_origin=%d cadence=%d epoch0=%d epochs=%s", who, anc_names[kind], nt_origin, cadence, epoch0,
+                epochs ? "set" : "NULL");
+  const bool interp_ok = kind == MCKPP_ANC_OCNT_CLIM || kind == MCKPP_ANC_SAL_CLIM;
+  for (int i = 0; i < nepochs; ++i) {
+    if (epochs[i].rec_prev < 0) return fail("%s: %s epoch %d: rec_prev=%d", who, anc_names[kind], epoch0 + i, epochs[i].rec_prev);
+    if (epochs[i].rec_next >= 0 && !interp_ok)
+      return fail("%s: %s epoch %d is interpolated (rec_next=%d): the reference interpolates ocnT_clim and sal_clim only "
+                  "(L_INTERP_OCNT, L_INTERP_SAL)", who, anc_names[kind], epoch0 + i, epochs[i].rec_next);
+  }
+  if (kind == MCKPP_ANC_BOTTOM_TEMP) {
+    if (h->d_bot_temp)
+      return fail("%s: a bottom temperature is resident (mckpp_hip_set_bottomtemp); the two are mutually exclusive - cancel "
+                  "it with mckpp_hip_set_bottomtemp(NULL) first", who);
+    if (h->npts <= 0) return fail("%s: upload the state first", who);
+    HIPCHK(hipSetDevice(h->device));
+    if (h->ncol > 0 && ensure_correction_rows(h)) return -1;
+  }
+  auto &a = h->anc[kind];
+  a.origin = nt_origin; a.cadence = cadence; a.epoch0 = epoch0;
+  a.ep.assign(epochs, epochs + nepochs);
+  return 0;
+}
+
+// A step launch call under ancillary schedules: every step's selection of every scheduled kind, checked - nothing is
+// launched for a step before the origin, an epoch outside the table or a record that is not resident - and then written
+// behind the launches already queued, ahead of this call's own.
+static int anc_prepare(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who)
+{
+  h->anc_mask = 0;
+  h->anc_nt0 = nt0;
+  int mask = 0;
+  for (int k = 0; k < MCKPP_ANC_COUNT; ++k) if (!h->anc[k].ep.empty()) mask |= 1 << k;
+  if (!mask) return 0;
+  if ((mask >> MCKPP_ANC_BOTTOM_TEMP & 1) && !h->diag)
+    return fail("%s: the bottom temperature has a schedule (mckpp_hip_ancillary_schedule) and the diagnostics are switched "
+                "off (mckpp_hip_set_diagnostics): the override needs rho and cp of the last vmix, which are diagnostics", who);
+  const size_t n = (size_t)nsteps * MCKPP_ANC_KINDS;
+  std::vector<mckpp_anc_sel> sel(n, mckpp_anc_sel{0, -1, 0.0, 0.0});
+  for (int k = 0; k < MCKPP_ANC_COUNT; ++k) {
+    if (!(mask >> k & 1)) continue;
+    const auto &a = h->anc[k];
+    const long long stride = (long long)anc_stride(h, k);
+    auto resident = [&](int rec) { return rec >= a.rec0 && rec < a.rec0 + a.nrec; };
+    for (int i = 0; i < nsteps; ++i) {
+      const int nt = nt0 + i;
+      if (nt < a.origin) return fail("%s: %s: step %d lies before the schedule's origin %d", who, anc_names[k], nt, a.origin);
+      const int e = (nt - a.origin) / a.cadence;
+      if (e < a.epoch0 || e >= a.epoch0 + (int)a.ep.size())
+        return fail("%s: %s: step %d is in epoch %d, the table holds epochs %d..%d", who, anc_names[k], nt, e, a.epoch0,
+                    a.epoch0 + (int)a.ep.size() - 1);
+      const mckpp_anc_epoch_c &ep = a.ep[(size_t)(e - a.epoch0)];
+      for (const int rec : {ep.rec_prev, ep.rec_next}) {
+        if (rec < 0 || resident(rec)) continue;
+        if (a.nrec == 0) return fail("%s: %s: step %d (epoch %d) needs record %d, none is resident", who, anc_names[k], nt, e, rec);
+        return fail("%s: %s: step %d (epoch %d) needs record %d, resident are %d..%d", who, anc_names[k], nt, e, rec, a.rec0,
+                    a.rec0 + a.nrec - 1);
+      }
+      mckpp_anc_sel &q = sel[(size_t)i * MCKPP_ANC_KINDS + k];
+      q.off_prev = (ep.rec_prev - a.rec0) * stride;
+      q.off_next = ep.rec_next < 0 ? -1 : (ep.rec_next - a.rec0) * stride;
+      q.w_prev = ep.w_prev; q.w_next = ep.w_next;
+    }
+  }
+  if (h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (n > h->anc_sel_cap) {
+    if (h->d_anc_sel) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->d_anc_sel); h->d_anc_sel = nullptr; h->anc_sel_cap = 0; }
+    HIPCHK(hipMalloc(&h->d_anc_sel, n * sizeof(mckpp_anc_sel)));
+    h->anc_sel_cap = n;
+  }
+  const unsigned slot = h->anc_seq++ & 1u;
+  if (!h->ev_anc[slot]) HIPCHK(hipEventCreateWithFlags(&h->ev_anc[slot], hipEventDisableTiming));
+  HIPCHK(hipEventSynchronize(h->ev_anc[slot]));   // the copy that last read this host image
+  if (n > h->h_anc_sel_cap[slot]) {
+    if (h->h_anc_sel[slot]) hipHostFree(h->h_anc_sel[slot]);
+    h->h_anc_sel[slot] = nullptr; h->h_anc_sel_cap[slot] = 0;
+    HIPCHK(hipHostMalloc(&h->h_anc_sel[slot], n * sizeof(mckpp_anc_sel), hipHostMallocDefault));
+    h->h_anc_sel_cap[slot] = n;
+  }
+  memcpy(h->h_anc_sel[slot], sel.data(), n * sizeof(mckpp_anc_sel));
+  HIPCHK(hipMemcpyAsync(h->d_anc_sel, h->h_anc_sel[slot], n * sizeof(mckpp_anc_sel), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipEventRecord(h->ev_anc[slot], h->stream));
+  h->anc_mask = mask;
+  return 0;
+}
+
+// mckpp_boundary_interpolate_temp / _sal, boundary_interpolate.F90:25-35 and :49-50 (:80-90, :104-105): true_time,
+// prev_time and next_time are INTEGER there, so each REAL assigned to them is truncated toward zero.
+void mckpp_host_interp_weights(double time, int32_t ndtupd, double dto, double spd, int32_t period, int32_t *prev_time,
+                               int32_t *next_time, double *w_prev, double *w_next)
+{
+  const int32_t true_time = (int32_t)time;                                                          // :25
+  const double ndays = ndtupd * dto / spd;                                                          // :26
+  int32_t prev = (int32_t)(std::floor((true_time + ndays / 2) / ndays) * ndays - ndays * 0.5);      // :29
+  double wp;
+  if (prev < 0) {
+    wp = (ndays - std::abs(true_time - prev)) / ndays;                                              // :31
+    prev = prev + period;                                                                           // :32
+  } else {
+    wp = (ndays - (true_time - prev)) / ndays;                                                      // :34
+  }
+  if (prev_time) *prev_time = prev;
+  if (next_time) *next_time = (int32_t)(prev + ndays);                                              // :49
+  if (w_prev) *w_prev = wp;
+  if (w_next) *w_next = 1 - wp;                                                                     // :50
 }
 
 // the caller's arrays pinned on behalf of this context go back to pageable memory (before the caller frees them)
@@ -1002,6 +1218,10 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
     p.log_cap = (int)h->log_cap; p.log_min_passes = h->log_min_passes;
   }
   if (mode == MCKPP_MODE_STEP) p.bot_temp = h->d_bot_temp;   // (init / vmix / pass never apply the override)
+  if (mode == MCKPP_MODE_STEP && h->anc_mask) {   // (... and never read a series; anc_prepare of this launch call)
+    p.anc_sel = h->d_anc_sel; p.anc_mask = h->anc_mask; p.anc_nt0 = h->anc_nt0;
+    for (int k = 0; k < MCKPP_ANC_KINDS; ++k) p.anc_rec[k] = h->anc[k].d;
+  }
 }
 
 struct forced_run { int ndtocn, l_rest; double flsn, el; };
@@ -1011,6 +1231,7 @@ static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
 static int snap_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 static int snap_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
 static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced);
+static int anc_prepare(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 
 // A step launch under output schedules and the restart schedule: checked against them before anything is launched,
 // then the schedules know which steps have run (and so which of their records and snapshots are complete)
@@ -1023,6 +1244,7 @@ static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_r
     return fail("%s: a bottom temperature is resident (mckpp_hip_set_bottomtemp) and the diagnostics are switched off "
                 "(mckpp_hip_set_diagnostics): the override needs rho and cp of the last vmix, which are diagnostics", who);
   if (sched && (win_check_launch(h, ntime, nsteps, who) || snap_check_launch(h, ntime, nsteps, who))) return -1;
+  if (sched && anc_prepare(h, ntime, nsteps, who)) return -1;
   if (run_launch(h, ntime, nsteps, mode, forced)) return -1;
   if (sched) win_advance(h, ntime, nsteps);
   if (sched && snap_advance(h, ntime, nsteps)) return -1;
@@ -1823,6 +2045,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
   if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
   if (log_cancel(h)) return -1;       // ... and the step log's records
   if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
+  if (anc_cancel_all(h)) return -1;   // ... and the ancillary record series and their schedules (likewise)
   const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
   if (!same_shape) {
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
@@ -2460,6 +2683,15 @@ int mckpp_hip_multi_synchronize(mckpp_hip_multi_handle m) { MULTI_EACH(mckpp_hip
 int mckpp_hip_multi_update_ancillaries(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s) { MULTI_EACH(mckpp_hip_update_ancillaries(x, s)); }
 int mckpp_hip_multi_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { MULTI_EACH(mckpp_hip_bottomtemp(x, bottom_temp)); }
 int mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { MULTI_EACH(mckpp_hip_set_bottomtemp(x, bottom_temp)); }
+int mckpp_hip_multi_set_ancillary_series(mckpp_hip_multi_handle m, int kind, int rec0, int nrec, const double *records)
+{
+  MULTI_EACH(mckpp_hip_set_ancillary_series(x, kind, rec0, nrec, records));
+}
+int mckpp_hip_multi_ancillary_schedule(mckpp_hip_multi_handle m, int kind, int nt_origin, int cadence, int epoch0, int nepochs,
+                                       const mckpp_anc_epoch_c *epochs)
+{
+  MULTI_EACH(mckpp_hip_ancillary_schedule(x, kind, nt_origin, cadence, epoch0, nepochs, epochs));
+}
 int mckpp_hip_multi_fluxes(mckpp_hip_multi_handle m, int ntime, const double *taux, const double *tauy, const double *swf,
                            const double *lwf, const double *lhf, const double *shf, const double *rain, const double *snow,
                            int l_rest, double flsn, double el)

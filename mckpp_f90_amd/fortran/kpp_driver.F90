@@ -10,7 +10,7 @@ program kpp_driver
   use mckpp_parameters
   use mckpp_data_fields
   use mckpp_time_control
-  use mckpp_hip_binding, only: MCKPP_F_SCALARS
+  use mckpp_hip_binding, only: MCKPP_F_SCALARS, mckpp_anc_epoch_c, MCKPP_ANC_SST0, MCKPP_ANC_OCNT_CLIM
   use mckpp_physics_lookup_mod, only: mckpp_physics_lookup
   use mckpp_initialize_ocean, only: mckpp_initialize_ocean_model
   use mckpp_physics_driver_mod, only: mckpp_physics_driver, mckpp_physics_finalize
@@ -24,7 +24,9 @@ program kpp_driver
                                mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, &
                                mckpp_hip_all_window_record_release, mckpp_hip_all_restart_schedule, &
                                mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
-                               mckpp_hip_all_restart_snapshot_release, mckpp_hip_all_step_log
+                               mckpp_hip_all_restart_snapshot_release, mckpp_hip_all_step_log, &
+                               mckpp_hip_all_set_ancillary_series, mckpp_hip_all_ancillary_schedule, &
+                               mckpp_hip_push_ancillaries, mckpp_hip_ancillaries_every_step
   implicit none
   character(len=512) :: fin, fout
   integer :: u, nt, nsteps, ncol, nlev, use_1d, ipt, flags
@@ -36,6 +38,10 @@ program kpp_driver
   real(c_double) :: hmixn
   integer :: kmixn, snap_first, snap_last
   character(len=16) :: snap_name
+  ! flag 2048: records of SST0 (npts, nrec) and ocnT_clim (npts, nzp1, nrec) and the epochs of ocnT_clim
+  integer, parameter :: anc_cad_sst = 3, anc_cad_ocnt = 2
+  real(c_double), allocatable :: anc_sst(:,:), anc_ocnt(:,:,:)
+  type(mckpp_anc_epoch_c), allocatable :: anc_ep_sst(:), anc_ep_ocnt(:)
 
   call get_command_argument(1, fin)
   call get_command_argument(2, fout)
@@ -57,6 +63,10 @@ program kpp_driver
   !           mckpp_restart_control); after it every snapshot s goes to <out.bin>.rst<s> (one file per shard)
   !        1024 the time loop as ONE forced run under a step log of ncol * nsteps records: with flag 128 the located
   !           warnings of every step of the run, not only of its last
+  !        2048 L_RELAX_SST and L_RELAX_OCNT with SST0 changing every 3 steps (record after record) and ocnT_clim every 2
+  !           (interpolated between two records, mckpp_boundary_interpolate_temp's sum), the records made from the
+  !           case's own profiles.  With 16 the one forced run reads them from resident series under schedules; with 1
+  !           the per-step driver gets the same fields through mckpp_hip_push_ancillaries at those cadences
   flags = hdr(6)
   if (iand(flags, 64) /= 0) mckpp_hip_output_mask = MCKPP_F_SCALARS
   ! hdr(7) > 0: that many device shards; hdr(8) = 1 puts them all on HIP device 0 (one-GPU rehearsal of the
@@ -93,6 +103,16 @@ program kpp_driver
     kpp_const_fields%L_VARY_BOTTOM_TEMP = .true.
     kpp_3d_fields%bottom_temp = kpp_3d_fields%X(:, nzp1, 1) + 0.125_c_double
   end if
+  if (iand(flags, 2048) /= 0) then
+    if (iand(flags, 2) == 0) call mckpp_allocate_3d_optional()
+    kpp_const_fields%L_RELAX_SST = .true.
+    kpp_const_fields%L_RELAX_OCNT = .true.
+    kpp_3d_fields%relax_sst = 1 / (5 * 86400._c_double)
+    kpp_3d_fields%relax_ocnT = 1 / (30 * 86400._c_double)
+    call make_ancillary_records()
+    call ancillaries_of_step(1)   ! epoch 0: the fields the run is initialised with
+    mckpp_hip_ancillaries_every_step = .false.
+  end if
   kpp_3d_fields%sflux = 0
   kpp_3d_fields%sflux(:, :, 5, 0) = 1e-20_c_double      ! mckpp_initialize_fluxes, src/mckpp_fluxes_mod.F90:19-32
 
@@ -108,6 +128,12 @@ program kpp_driver
     series(:, 5, 1) = -150; series(:, 6, 1) = 0; series(:, 7, 1) = 6e-5_c_double; series(:, 8, 1) = 0
     call mckpp_hip_all_set_flux_series(0, 1, series)
     if (iand(flags, 1024) /= 0) call mckpp_hip_all_step_log(ncol * nsteps, 0)
+    if (iand(flags, 2048) /= 0) then   ! the records resident, every column-step reads its own epoch's
+      call mckpp_hip_all_set_ancillary_series(MCKPP_ANC_SST0, 0, size(anc_sst, 2), anc_sst)
+      call mckpp_hip_all_ancillary_schedule(MCKPP_ANC_SST0, 1, anc_cad_sst, 0, size(anc_ep_sst), anc_ep_sst)
+      call mckpp_hip_all_set_ancillary_series(MCKPP_ANC_OCNT_CLIM, 0, size(anc_ocnt, 3), anc_ocnt)
+      call mckpp_hip_all_ancillary_schedule(MCKPP_ANC_OCNT_CLIM, 1, anc_cad_ocnt, 0, size(anc_ep_ocnt), anc_ep_ocnt)
+    end if
     if (iand(flags, 32) /= 0) then
       call mckpp_hip_all_window_select([4_c_int32_t, 2_c_int32_t])   ! MCKPP_OUT_HMIX, MCKPP_OUT_T
       call mckpp_hip_all_window_reset()
@@ -136,6 +162,12 @@ program kpp_driver
   do nt = 1, nsteps
     call mckpp_update_time(nt)
     if (iand(flags, 1) /= 0) call mckpp_fluxes()      ! ndtocn = 1 (src/mckpp_ocean_model_3D.F90:44-48)
+    if (iand(flags, 2048) /= 0 .and. nt > 1) then     ! mckpp_boundary_update's place (src/mckpp_ocean_model_3D.F90:51-55)
+      if (mod(nt - 1, anc_cad_sst) == 0 .or. mod(nt - 1, anc_cad_ocnt) == 0) then
+        call ancillaries_of_step(nt)
+        call mckpp_hip_push_ancillaries()
+      end if
+    end if
     if (use_1d == 0) then
       call mckpp_physics_driver()
     else
@@ -207,6 +239,39 @@ program kpp_driver
   call mckpp_physics_finalize()
 
 contains
+
+  !> flag 2048: record r of SST0 is T(:,1) + 1.5 + r/4, of ocnT_clim T - 0.3 + r/8 (the case's starting T); SST0's epoch e
+  !! is record e, ocnT_clim's is record(e/3 + 1) * w + record(e/3) * (1 - w) with w = mod(e, 3) / 3
+  subroutine make_ancillary_records()
+    integer :: r, e, nes, neo, nro
+    nes = (hdr(3) + anc_cad_sst - 1) / anc_cad_sst
+    neo = (hdr(3) + anc_cad_ocnt - 1) / anc_cad_ocnt
+    nro = (neo - 1) / 3 + 2
+    allocate (anc_sst(npts, nes), anc_ocnt(npts, nzp1, nro), anc_ep_sst(nes), anc_ep_ocnt(neo))
+    do r = 1, nes
+      anc_sst(:, r) = kpp_3d_fields%X(:, 1, 1) + 1.5_c_double + 0.25_c_double * (r - 1)
+      anc_ep_sst(r) = mckpp_anc_epoch_c(r - 1, -1, 0._c_double, 0._c_double)
+    end do
+    do r = 1, nro
+      anc_ocnt(:, :, r) = kpp_3d_fields%X(:, :, 1) - 0.3_c_double + 0.125_c_double * (r - 1)
+    end do
+    do e = 0, neo - 1
+      anc_ep_ocnt(e + 1)%rec_prev = e / 3
+      anc_ep_ocnt(e + 1)%rec_next = e / 3 + 1
+      anc_ep_ocnt(e + 1)%w_next = mod(e, 3) / 3._c_double
+      anc_ep_ocnt(e + 1)%w_prev = 1 - anc_ep_ocnt(e + 1)%w_next
+    end do
+  end subroutine make_ancillary_records
+
+  !> ... and the fields of step n's epochs in kpp_3d_fields, as mckpp_boundary_update would leave them
+  !! (src/mckpp_boundary_interpolate.F90:60)
+  subroutine ancillaries_of_step(n)
+    integer, intent(in) :: n
+    type(mckpp_anc_epoch_c) :: ep
+    kpp_3d_fields%SST0 = anc_sst(:, anc_ep_sst((n - 1) / anc_cad_sst + 1)%rec_prev + 1)
+    ep = anc_ep_ocnt((n - 1) / anc_cad_ocnt + 1)
+    kpp_3d_fields%ocnT_clim = anc_ocnt(:, :, ep%rec_next + 1) * ep%w_next + anc_ocnt(:, :, ep%rec_prev + 1) * ep%w_prev
+  end subroutine ancillaries_of_step
 
   subroutine gather_1d(i, c)
     integer, intent(in) :: i

@@ -23,6 +23,16 @@ module mckpp_hip_binding
   ! operations of an output schedule (mckpp_hip_window_schedule): bit 2**op of a record fetch's op
   integer(c_int32_t), parameter :: MCKPP_WIN_MEAN = 1, MCKPP_WIN_MIN = 2, MCKPP_WIN_MAX = 4, MCKPP_WIN_LAST = 8
   integer(c_int), parameter :: MCKPP_OP_LAST = 3
+  ! kinds of the ancillary record series (MCKPP_ANC_*)
+  integer(c_int), parameter :: MCKPP_ANC_SST0 = 0, MCKPP_ANC_FCORR_TWOD = 1, MCKPP_ANC_FCORR_WITHZ = 2, &
+    MCKPP_ANC_SFCORR_WITHZ = 3, MCKPP_ANC_OCNT_CLIM = 4, MCKPP_ANC_SAL_CLIM = 5, MCKPP_ANC_BOTTOM_TEMP = 6, MCKPP_ANC_COUNT = 7
+
+  !> one epoch of mckpp_hip_ancillary_schedule: record rec_prev as it is (rec_next < 0), or
+  !! record(rec_next)*w_next + record(rec_prev)*w_prev
+  type, bind(C) :: mckpp_anc_epoch_c
+    integer(c_int32_t) :: rec_prev, rec_next
+    real(c_double) :: w_prev, w_next
+  end type mckpp_anc_epoch_c
 
   type, bind(C) :: mckpp_const_c
     integer(c_int32_t) :: nz, nztmax, nsflxs, njdt, itermax
@@ -140,6 +150,29 @@ module mckpp_hip_binding
       real(c_double), intent(in), optional :: bottom_temp(*)   ! absent: NULL, cancels the resident field
       integer(c_int) :: rc
     end function
+    function mckpp_hip_set_ancillary_series(handle, kind, rec0, nrec, records) bind(C, name="mckpp_hip_set_ancillary_series") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: kind, rec0, nrec
+      real(c_double), intent(in), optional :: records(*)   ! absent: NULL (nrec = 0 frees the kind's records)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_ancillary_schedule(handle, kind, nt_origin, cadence, epoch0, nepochs, epochs) &
+        bind(C, name="mckpp_hip_ancillary_schedule") result(rc)
+      import :: c_int, c_ptr, mckpp_anc_epoch_c
+      type(c_ptr), value :: handle
+      integer(c_int), value :: kind, nt_origin, cadence, epoch0, nepochs
+      type(mckpp_anc_epoch_c), intent(in), optional :: epochs(*)   ! absent: NULL (nepochs = 0 cancels the schedule)
+      integer(c_int) :: rc
+    end function
+    subroutine mckpp_host_interp_weights(time, ndtupd, dto, spd, period, prev_time, next_time, w_prev, w_next) &
+        bind(C, name="mckpp_host_interp_weights")
+      import :: c_double, c_int32_t
+      real(c_double), value :: time, dto, spd
+      integer(c_int32_t), value :: ndtupd, period
+      integer(c_int32_t), intent(out) :: prev_time, next_time
+      real(c_double), intent(out) :: w_prev, w_next
+    end subroutine
     function mckpp_hip_save_restart(handle, path) bind(C, name="mckpp_hip_save_restart") result(rc)
       import :: c_int, c_ptr, c_char
       type(c_ptr), value :: handle
@@ -239,6 +272,21 @@ module mckpp_hip_binding
       import :: c_int, c_ptr, c_double
       type(c_ptr), value :: handle
       real(c_double), intent(in), optional :: bottom_temp(*)   ! absent: NULL, cancels the resident field
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_set_ancillary_series(handle, kind, rec0, nrec, records) bind(C, name="mckpp_hip_multi_set_ancillary_series") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: kind, rec0, nrec
+      real(c_double), intent(in), optional :: records(*)   ! absent: NULL (nrec = 0 frees the kind's records)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_ancillary_schedule(handle, kind, nt_origin, cadence, epoch0, nepochs, epochs) &
+        bind(C, name="mckpp_hip_multi_ancillary_schedule") result(rc)
+      import :: c_int, c_ptr, mckpp_anc_epoch_c
+      type(c_ptr), value :: handle
+      integer(c_int), value :: kind, nt_origin, cadence, epoch0, nepochs
+      type(mckpp_anc_epoch_c), intent(in), optional :: epochs(*)   ! absent: NULL (nepochs = 0 cancels the schedule)
       integer(c_int) :: rc
     end function
     function mckpp_hip_multi_init_ocean(handle, ntime) bind(C, name="mckpp_hip_multi_init_ocean") result(rc)

@@ -22,6 +22,7 @@ module mckpp_hip_session
             mckpp_hip_all_restart_snapshot_release
   public :: mckpp_hip_all_step_log
   public :: mckpp_hip_all_set_bottomtemp, mckpp_hip_bottomtemp_resident
+  public :: mckpp_hip_all_set_ancillary_series, mckpp_hip_all_ancillary_schedule
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
   public :: mckpp_hip_host_behind
   public :: mckpp_hip_warnings, mckpp_hip_abort_on_zero_pivot, mckpp_hip_report_warnings, mckpp_hip_column_messages
@@ -73,6 +74,8 @@ module mckpp_hip_session
   !> a bottom temperature is resident on the devices (mckpp_hip_all_set_bottomtemp; an upload or a restart load cancels
   !! it): the step launches apply the L_VARY_BOTTOM_TEMP override themselves
   logical, save :: bottomtemp_set = .false.
+  !> ... or the bottom temperature has a schedule there (mckpp_hip_all_ancillary_schedule, MCKPP_ANC_BOTTOM_TEMP): likewise
+  logical, save :: bottomtemp_scheduled = .false.
 
 contains
 
@@ -205,6 +208,7 @@ contains
     host_behind = 0
     step_log_set = .false.   ! (an upload cancels the step log)
     bottomtemp_set = .false.   ! (... and the resident bottom temperature)
+    bottomtemp_scheduled = .false.   ! (... and every ancillary series and schedule)
   end subroutine mckpp_hip_push_state
 
   !> HBM -> kpp_3d_fields for the selected field groups.
@@ -331,11 +335,12 @@ contains
 
   !> With kpp_const_fields%L_VARY_BOTTOM_TEMP the run ends every step with mckpp_physics_overrides_bottomtemp, as the
   !! reference's driver does (src/mckpp_physics_driver_mod.F90:67-71): kpp_3d_fields%bottom_temp as it stands now becomes
-  !! resident first (a run whose bottom_temp changes every ndtupdbottom steps is cut into calls there).
+  !! resident first (a run whose bottom_temp changes every ndtupdbottom steps is cut into calls there, or schedules its
+  !! records: mckpp_hip_all_ancillary_schedule).
   subroutine mckpp_hip_all_run_forced(nt_first, nsteps, ndtocn)
     integer, intent(in) :: nt_first, nsteps, ndtocn
     call mckpp_hip_push_state()
-    if (kpp_const_fields%L_VARY_BOTTOM_TEMP) then
+    if (kpp_const_fields%L_VARY_BOTTOM_TEMP .and. .not. bottomtemp_scheduled) then   ! (a schedule: the records are resident)
       if (.not. allocated(kpp_3d_fields%bottom_temp)) then
         write (0, '(a)') 'MCKPP-HIP ERROR: L_VARY_BOTTOM_TEMP needs kpp_3d_fields%bottom_temp (mckpp_allocate_3d_optional)'
         error stop 1
@@ -361,8 +366,36 @@ contains
     bottomtemp_set = present(bottom_temp)
   end subroutine mckpp_hip_all_set_bottomtemp
 
+  !> Ancillary record series on all devices (mckpp_hip_set_ancillary_series of include/mckpp_hip.h): `nrec` records of
+  !! one kind (MCKPP_ANC_*), records(npts, nrec) for SST0, fcorr_twod and bottom_temp, records(npts, nzp1, nrec) for the
+  !! others - each record the array the reference's reader leaves in kpp_3d_fields; record 1 of the array is record
+  !! number rec0 of the run.  nrec = 0 (records may be left out) frees the kind's records.  The state goes to the devices
+  !! first (an upload cancels every series and schedule).
+  subroutine mckpp_hip_all_set_ancillary_series(kind, rec0, nrec, records)
+    integer, intent(in) :: kind, rec0, nrec
+    real(c_double), intent(in), optional :: records(*)
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_set_ancillary_series(mckpp_hip_multi_handle, int(kind, c_int), int(rec0, c_int), &
+                         int(nrec, c_int), records), 'mckpp_hip_multi_set_ancillary_series')
+  end subroutine mckpp_hip_all_set_ancillary_series
+
+  !> The kind's schedule on all devices (mckpp_hip_ancillary_schedule): step nt is in epoch (nt - nt_origin) / cadence,
+  !! epochs(i) describes epoch epoch0 + i - 1.  From then on every step of mckpp_hip_all_run_forced and of
+  !! mckpp_physics_driver reads the kind from the series; what mckpp_hip_push_ancillaries sends is left alone and not
+  !! read.  nepochs = 0 (epochs may be left out) cancels the schedule.  With MCKPP_ANC_BOTTOM_TEMP the launches apply the
+  !! L_VARY_BOTTOM_TEMP override themselves, as with mckpp_hip_all_set_bottomtemp (the two exclude each other).
+  subroutine mckpp_hip_all_ancillary_schedule(kind, nt_origin, cadence, epoch0, nepochs, epochs)
+    integer, intent(in) :: kind, nt_origin, cadence, epoch0, nepochs
+    type(mckpp_anc_epoch_c), intent(in), optional :: epochs(*)
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_ancillary_schedule(mckpp_hip_multi_handle, int(kind, c_int), int(nt_origin, c_int), &
+                         int(cadence, c_int), int(epoch0, c_int), int(nepochs, c_int), epochs), &
+                         'mckpp_hip_multi_ancillary_schedule')
+    if (kind == MCKPP_ANC_BOTTOM_TEMP) bottomtemp_scheduled = nepochs > 0
+  end subroutine mckpp_hip_all_ancillary_schedule
+
   logical function mckpp_hip_bottomtemp_resident()
-    mckpp_hip_bottomtemp_resident = bottomtemp_set
+    mckpp_hip_bottomtemp_resident = bottomtemp_set .or. bottomtemp_scheduled
   end function mckpp_hip_bottomtemp_resident
 
   !> The step log (mckpp_hip_step_log of include/mckpp_hip.h) on all devices: every column-step of the step launches
@@ -503,6 +536,7 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_load_restart(mckpp_hip_multi_handle, trim(path)//c_null_char), 'mckpp_hip_multi_load_restart')
     step_log_set = .false.   ! (a restart load cancels the step log)
     bottomtemp_set = .false.   ! (... and the resident bottom temperature)
+    bottomtemp_scheduled = .false.   ! (... and every ancillary series and schedule)
     call mckpp_hip_device_advanced()
   end subroutine mckpp_hip_all_load_restart
 
