@@ -260,7 +260,8 @@ int mckpp_hip_ancillary_schedule(mckpp_hip_handle h, int kind, int nt_origin, in
 void mckpp_host_interp_weights(double time, int32_t ndtupd, double dto, double spd, int32_t period, int32_t *prev_time,
                                int32_t *next_time, double *w_prev, double *w_next);
 
-/* Enable/disable writing of the MCKPP_F_DIAG fields by step/init (default on). */
+/* Enable/disable writing of the MCKPP_F_DIAG fields by step/init (default on; which steps of a
+ * call of several steps write them: mckpp_hip_step). */
 int mckpp_hip_set_diagnostics(mckpp_hip_handle h, int on);
 
 /* Tridiagonal solver mode of the implicit step (an extension: the reference has one solver,
@@ -280,7 +281,13 @@ int mckpp_hip_get_solver_mode(mckpp_hip_handle h);
 int mckpp_hip_init_ocean(mckpp_hip_handle h, int ntime);
 
 /* mckpp_physics_driver (src/mckpp_physics_driver_mod.F90:15-73): nsteps calls,
- * step i run with ntime+i.  Asynchronous on the context's stream. */
+ * step i run with ntime+i.  Asynchronous on the context's stream.
+ * After the call the MCKPP_F_DIAG fields are those of step ntime+nsteps-1.  Inside a
+ * call of several steps (one launch; mckpp_hip_run_forced too) a step stores them only
+ * where something can read them before the column's next step overwrites them: the
+ * launch's last step, the restart schedule's snapshot steps, and every step while an
+ * output schedule holds a diagnostic field or a bottom temperature is resident or
+ * scheduled.  MCKPP_LEAN_DIAG=0 (read at every launch) makes every step store them. */
 int mckpp_hip_step(mckpp_hip_handle h, int ntime, int nsteps);
 
 /* One vmix + ocnint pass per column with Uo=U, Xo=X ("kppmix + tridiag

@@ -160,6 +160,12 @@ struct mckpp_kparams_t {
   P<const mckpp_anc_sel> anc_sel;
   P<const double> anc_rec[MCKPP_ANC_KINDS];
   int anc_mask, anc_nt0;
+  // 1 (only with diag != 0; always in the modes other than STEP): every step of the launch is a diagnostic step -
+  // something inside the launch reads what the last vmix leaves behind (an output schedule with a diagnostic field, the
+  // bottom-temperature override), or MCKPP_LEAN_DIAG=0.  0: with diag != 0 only the launch's last step and the restart
+  // schedule's snapshot steps are (k_column_ps, M0); the others store no diagnostics - their column's next step would
+  // overwrite them before the host could see them.
+  int diag_every;
 };
 #define MCKPP_SNAP_ROWS 14
 using mckpp_kparams = mckpp_kparams_t<mckpp_ptr_plain>;

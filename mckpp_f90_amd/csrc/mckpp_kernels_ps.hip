@@ -46,9 +46,11 @@ enum {
 // per-slot int record
 enum {
   I_STATE = 0, I_ACT, I_COL, I_OLD, I_NEW, I_JER, I_INITFLAG, I_STATUS, I_NPASS, I_NPASS_TRY, I_ICONV, I_COMP, I_KMIXN,
-  I_KBL, I_NRESET, I_FIN, I_MAYBE, I_LOAD /* 1: new column, 2: restart the iteration (trap retry) */, I_JU,
+  I_KBL, I_NRESET, I_FIN,
+  I_MAYBE /* bit 0: this pass may be the step's last; bit 1: a diagnostic step, set for the whole step (M0) */,
+  I_LOAD /* 1: new column, 2: restart the iteration (trap retry) */, I_JU,
   I_KBLC, I_NVIOL, I_NOVER, I_NU, I_NV, I_NF, I_BAD, I_L1A /* L1 but for V done ahead, during the V sweep */,
-  I_MAYBE_NEXT, I_LOCEAN, I_PAR /* which C_T1X holds the iterate's level-1 temperature */,
+  I_MAYBE_NEXT /* of the pass to come, same bits */, I_LOCEAN, I_PAR /* which C_T1X holds the iterate's level-1 temperature */,
   I_TINY /* some whole-layer term of the reference-level sums is a tiny non-zero number (L2) */,
   I_STEP /* which step of the launch this column is in (0 .. nsteps_launch-1) */,
   I_STRAG /* counted as a straggler: past its solo_after-th pass of a try, or at itermax in its previous step (M0) */, I_COUNT_USED,
@@ -1472,7 +1474,18 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
           msi[I_LOCEAN] = ci[CI_LOCEAN];
           msi[I_STATUS] = status; msi[I_NPASS] = 0; msi[I_NPASS_TRY] = 0; msi[I_ICONV] = 0; msi[I_COMP] = 1;
           msi[I_NRESET] = 0; msi[I_KMIXN] = 0; msi[I_KBL] = 0; msi[I_LOAD] = 1; msi[I_BAD] = 0;
-          msi[I_MAYBE] = (p.mode != MCKPP_MODE_STEP) ? 1 : 0;
+          // A diagnostic step stores what the last vmix leaves behind; a lean one does not, for nothing could read it
+          // before the column's next step of this launch overwrites it (the host sees memory at the launch boundary):
+          // the launch's last step, a snapshot step of the restart schedule (its set carries rho and cp), or every step
+          // (p.diag_every: a reader inside the launch, or the switch - the host's fill_params).
+          // (p.diag_every is set whenever the mode is not STEP, and never with the diagnostics off)
+          const int snap_q = p.ntime + step - p.snap_origin + 1;   // the snapshot stage's arithmetic (finish round)
+          const int snap_p = p.snap_period > 0 ? p.snap_period : 0x7fffffff;
+          const int dstep = (p.diag_every != 0) | ((p.diag != 0) & ((step == p.nsteps_launch - 1) | ((snap_q > 0) & (snap_q % snap_p == 0))));
+          msi[I_MAYBE] = ((p.mode != MCKPP_MODE_STEP) ? 1 : 0) | (dstep << 1);
+#ifdef MCKPP_PS_STAMPS
+          if (p.dbg) atomicAdd((unsigned long long *)p.dbg + (dstep ? 38 : 39), 1ull);   // census: diagnostic | lean column-steps
+#endif
           msi[I_KBLC] = 0x7fffffff; msi[I_NVIOL] = 0; msi[I_NU] = 0; msi[I_NV] = 0; msi[I_NF] = 0; msi[I_PAR] = 0;
           msi[I_L1A] = 0; msi[I_MAYBE_NEXT] = msi[I_MAYBE]; msi[I_TINY] = 0;
           // (at itermax in its previous step - ci holds that step's pass count: a straggler from its first pass on)
@@ -1731,7 +1744,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
               msi[I_NVIOL] = 0;
             }
           }
-          msi[I_MAYBE_NEXT] = (npass_try >= 3 && (iconv >= 2 || npass_try + 1 >= p.itermax)) ? 1 : 0;
+          msi[I_MAYBE_NEXT] = ((npass_try >= 3 && (iconv >= 2 || npass_try + 1 >= p.itermax)) ? 1 : 0) | (msi[I_MAYBE] & 2);
         }
         msi[I_STATUS] = status; msi[I_NPASS_TRY] = npass_try; msi[I_ICONV] = iconv;
         msi[I_FIN] = fin;
@@ -1871,7 +1884,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     // tinc_fcorr of the latest pass is what check_profile adds to (overrides.F90:87-88): always stored
     const size_t o = (size_t)col * p.ld + k;
     p.tinc_fcorr[o] = tinc;
-    if (si[I_MAYBE]) { p.ocnTcorr[o] = ocnTcorr; p.sinc_fcorr[o] = sinc; p.scorr[o] = sinc / dto; }
+    if (si[I_MAYBE] & 1) { p.ocnTcorr[o] = ocnTcorr; p.sinc_fcorr[o] = sinc; p.scorr[o] = sinc / dto; }
   };
 
   // ---- L1 of one item: under-relaxation of the iterate against the last solution (ocnstep_mod.F90:123-132 /
@@ -1893,7 +1906,8 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       return;
     }
     const bool with_v = part == L1_FULL;
-    const int maybe = part == L1_ALL_BUT_V ? si[I_MAYBE_NEXT] : si[I_MAYBE];
+    const int maybe_ = part == L1_ALL_BUT_V ? si[I_MAYBE_NEXT] : si[I_MAYBE];   // 3: may be the last pass of a diagnostic step
+    const int maybe = maybe_ & 1, dstep = maybe_ >> 1;
     const int ldf = with_v ? si[I_LOAD] : 0, par = si[I_PAR];
     const size_t o = ro + (kr - 1);
     double U = 0, V = 0, T = 0, S = 0;
@@ -1939,11 +1953,11 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     if (virt1) { Sin = 0.0; Pin = -zm1; }
     if (virt2) { Sin = p.sice; Pin = -zm1; }
     // Only sigma-0 (density, buoyancy) feeds the pass; alpha, beta and cp of the levels are diagnostics of the
-    // last vmix (and inputs of the optional physics), level 1's are formed in M1: passes that cannot be the
+    // last vmix of a diagnostic step (and inputs of the optional physics), level 1's are formed in M1: passes that cannot be the
     // last evaluate a tenth of the equation of state.
     // (Optional physics: rho cp enters the right-hand sides under three switches, double diffusion needs alpha
     // and beta, and the correction diagnostics of a pass that may be the last need rho cp too.)
-    const bool full_eos = (maybe && (p.diag || EXT)) ||
+    const bool full_eos = (maybe && (dstep || EXT)) ||
                           (EXT && (p.LDD || p.L_RELAX_SST || p.L_FCORR || p.L_FCORR_WITHZ));
     double s0, talpha = 0.0, sbeta = 0.0, cp = 0.0;
     if (full_eos) {
@@ -1958,7 +1972,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     if (virt1) sc[X_RHOH2O] = rho;
     if (virt2) sc[X_RHOB] = rho;
     if (act) { row(Q_YU)[k] = U; row(Q_YS)[k] = buoy; if (with_v) row(Q_YV)[k] = V; }
-    if (p.diag && maybe) {   // what the last vmix leaves behind (types_transfer.F90:199-327)
+    if (maybe_ == 3) {   // what the last vmix leaves behind (types_transfer.F90:199-327)
       const size_t od = ro + k;
       if (act) { p.rho[od] = rho; p.cp[od] = cp; p.buoy[od] = buoy; p.talpha[od] = talpha; p.sbeta[od] = sbeta; }
       if (is1) { p.rho[od - 1] = rho; p.cp[od - 1] = cp; p.talpha[od - 1] = talpha; p.sbeta[od - 1] = sbeta; }
@@ -2082,7 +2096,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
     if (actz) { row(Q_GM)[k] = Rig; row(Q_YT)[k] = dbloc; }
     if (is1) row(Q_GM)[0] = 0.0;
     if (isnzp1) row(Q_GM)[k] = 0.0;
-    if (p.diag && si[I_MAYBE]) {
+    if (si[I_MAYBE] == 3) {   // a diagnostic step's pass that may be the last
       const size_t od = ro + k;
       if (actz) { if (p.LRI) p.Rig[od] = Rig; p.dbloc[od] = dbloc; p.Shsq[od] = shsq; }   // (Rig is rimix's, rimix_mod.F90:47-56)
     }
@@ -2481,7 +2495,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         }
       }
       row(ps_sysrows<XV>::dl6_t)[k] = dift; if (DD) row(ps_sysrows<XV>::dl6_s)[k] = difs; row(Q_YV)[k] = ghat;
-      if (p.diag && si[I_MAYBE]) {   // the sweeps reuse these rows: what the last vmix leaves behind goes out now
+      if (si[I_MAYBE] == 3) {   // the sweeps reuse these rows: what the last vmix leaves behind goes out now
         const size_t od = ro + k;
         p.difm[od] = difm; p.difs[od] = difs; p.dift[od] = dift;
         if (actz) p.ghat[od] = ghat;
@@ -2720,7 +2734,7 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
           if (nreset > 10) status |= 8;
           msi[I_COMP] = comp_flag; msi[I_STATUS] = status; msi[I_NRESET] = nreset;
           if (comp_flag && nreset <= 10) {   // retry, ocnstep_mod.F90:89
-            msi[I_FIN] = F_NONE; msi[I_LOAD] = 2; msi[I_NPASS_TRY] = 0; msi[I_ICONV] = 0; msi[I_MAYBE] = 0;
+            msi[I_FIN] = F_NONE; msi[I_LOAD] = 2; msi[I_NPASS_TRY] = 0; msi[I_ICONV] = 0; msi[I_MAYBE] = msi[I_MAYBE] & 2;   // (the step keeps its kind)
           } else {
             msi[I_FIN] = F_FINAL;
             msi[I_NU] = 0; msi[I_NV] = 0; msi[I_NF] = 0;
@@ -2743,11 +2757,12 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         if (sol) { U = row(Q_YU)[k]; V = row(Q_YV)[k]; T = row(Q_YT)[k]; S = row(Q_YS)[k]; }
         else { U = p.U[o]; V = p.V[o]; T = p.T[o]; S = p.S[o]; }
       }
-      if (actz && p.diag && flux_diag) {
+      const int dstep = si[I_MAYBE] & 2;   // a diagnostic step (p.diag is on): a lean one leaves the diagnostic rows alone
+      if (actz && dstep && flux_diag) {
         if (sol) { uk1 = row(Q_YU)[k + 1]; vk1 = row(Q_YV)[k + 1]; tk1 = row(Q_YT)[k + 1]; sk1 = row(Q_YS)[k + 1]; }
         else { uk1 = p.U[o + 1]; vk1 = p.V[o + 1]; tk1 = p.T[o + 1]; sk1 = p.S[o + 1]; }
       }
-      if (p.diag) {
+      if (dstep) {
         const double wX0_1 = sc[C_WX01], wX0_2 = sc[C_WX02];
         const double rho0cp0 = sc[C_RHO0CP0], sflux3 = sc[C_SFLUX3];
         const size_t od = ro + k;

@@ -1168,6 +1168,9 @@ int mckpp_hip_set_solver_mode(mckpp_hip_handle h, int mode)
 
 int mckpp_hip_get_solver_mode(mckpp_hip_handle h) { return h ? h->solver_mode : fail("null handle"); }
 
+// output fields that are diagnostics of the last vmix (or correction rows): need mckpp_hip_set_diagnostics on
+static bool win_is_diag(int f) { return f >= MCKPP_OUT_B && f <= MCKPP_OUT_SINC_FCORR; }
+
 static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
 {
   memset(&p, 0, sizeof p);
@@ -1222,6 +1225,20 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
     p.anc_sel = h->d_anc_sel; p.anc_mask = h->anc_mask; p.anc_nt0 = h->anc_nt0;
     for (int k = 0; k < MCKPP_ANC_KINDS; ++k) p.anc_rec[k] = h->anc[k].d;
   }
+  // Which steps of a launch store their diagnostics: every one if something inside the launch reads them - a window
+  // folds every step of its period, the bottom-temperature override takes rho and cp of each step's last vmix - or if
+  // MCKPP_LEAN_DIAG=0 says so (read at every launch: A/B runs, tests); otherwise the kernel keeps them for the
+  // launch's last step and the snapshot steps, the only ones anything can see (k_column_ps, M0).
+  p.diag_every = h->diag ? 1 : 0;
+  if (mode == MCKPP_MODE_STEP && h->diag) {
+    const char *e = getenv("MCKPP_LEAN_DIAG");
+    bool every = e && atoi(e) == 0;
+    every = every || h->d_bot_temp || (h->anc_mask >> MCKPP_ANC_BOTTOM_TEMP & 1);
+    if (h->nwin > 0)
+      for (const auto &w : h->wsched)
+        for (int f : w.fields) every = every || win_is_diag(f);
+    p.diag_every = every ? 1 : 0;
+  }
 }
 
 struct forced_run { int ndtocn, l_rest; double flsn, el; };
@@ -1269,7 +1286,8 @@ static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const f
   // Several steps of constant forcing (mckpp_hip_step with nsteps > 1): ONE launch takes every column through all of
   // them - ncol x nsteps tickets, a column's step waiting only for that column's previous step (k_column_ps, M0) -
   // instead of a launch per step, each of which would wait for its slowest column.  Same results bit for bit (the
-  // columns are independent; every step still stores its outputs and diagnostics).  The forced run too: a step
+  // columns are independent; every step stores its outputs, and its diagnostics if anything can read them before the
+  // column's next step overwrites them - fill_params, diag_every).  The forced run too: a step
   // that is a flux update assembles its column's forcing from the resident record itself.  Not for a step at ntime = 0.
   if (mode == MCKPP_MODE_STEP && nsteps > 1 && ntime >= 1 && h->multistep) {
     if (!h->d_done) HIPCHK(hipMalloc(&h->d_done, 2 * (size_t)h->ncol * sizeof(int)));   // done[ncol], then the steps started (k_column_ps, M0)
@@ -1401,6 +1419,7 @@ int mckpp_hip_synchronize(mckpp_hip_handle h)
         fprintf(stderr, " all=%.0f]", fin / (double)t[31]);
       }
       fprintf(stderr, " total=%.0f\n", tot / (double)t[31]);
+      if (t[38] + t[39]) fprintf(stderr, "[mckpp steps ps] diagnostic column-steps %llu, lean %llu\n", t[38], t[39]);
       if (t[32] + t[33])   // how far down L3 formed the bulk Richardson numbers, per workgroup pass (first: a column was started before it)
         fprintf(stderr, "[mckpp guesses ps] first passes %llu, mean kguess %.1f; later passes %llu, mean kguess %.1f; second rounds %llu "
                         "(%.4f of the passes); mean end of the first scan %.1f\n",
@@ -2238,7 +2257,6 @@ int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
 // keeps the bookkeeping: which steps have run under a schedule, so which records are complete, and which are
 // released; a launch that would break it fails before anything is launched.
 // ---------------------------------------------------------------------------
-static bool win_is_diag(int f) { return f >= MCKPP_OUT_B && f <= MCKPP_OUT_SINC_FCORR; }
 
 static void win_cancel(mckpp_hip_ctx *h, int s)
 {
