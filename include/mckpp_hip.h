@@ -453,6 +453,41 @@ int mckpp_hip_window_record_fetch(mckpp_hip_handle h, int sched, int64_t rec, in
 int mckpp_hip_window_record_release(mckpp_hip_handle h, int sched, int64_t upto_rec);
 int mckpp_hip_window_records(mckpp_hip_handle h, int sched, int64_t *first_kept, int64_t *last_complete);
 
+/* Packed export of a schedule's records, fetched while later launches run.  window_record_fetch re-lays a plane on
+ * the context's stream, behind every launch already queued, and waits for that stream.  With an export set, every
+ * step-launch call queues, behind its own column-kernel launches, one more launch per record the call completed:
+ * it packs all planes of the record into an export slot in device memory, in the layout the host wants, and an
+ * event marks the slot.  A fetch waits for that event alone and is one copy on a transfer stream of its own, into
+ * the caller's array: launches queued later keep running (only DMA runs beside the column kernel, which fills
+ * every CU).  The export ring has the schedule's nrec slots, record w in slot w % nrec, and no bookkeeping of its
+ * own: window_records and window_record_release govern both rings.  It costs one more copy of every kept record in
+ * device memory: npts * nlev * 8 (or 4) bytes per plane, 49 MB for a three-dimensional plane of 1e5 points x 61
+ * levels as double.
+ *   window_export: dtype MCKPP_EXP_F64, or MCKPP_EXP_F32 - every value narrowed to float after the mean's division,
+ *     one conversion rounded to nearest even - or MCKPP_EXP_OFF, which drops the export.  Waits for the context's
+ *     stream like window_schedule, allocates the slots, fills their land points with land_value once (no step ever
+ *     writes them) and packs at once every record that is complete and not released.  Fails for an unset schedule,
+ *     an unknown dtype, or memory that cannot be allocated (the schedule then stays set, without an export).
+ *     window_schedule on the schedule, upload and load_restart cancel the export with the schedule.
+ *   window_export_layout: the planes of a record - the schedule's fields in its order, within a field the kept
+ *     operations in bit order (mean, min, max, last): per plane its field, op (0..3), levels and offset in bytes, a
+ *     multiple of 256; record_bytes is the size of a record.  Plane (field, op) is [nlev][npts] values, points
+ *     fastest: out(npts[,nzp1]) of window_record_fetch.  The arrays may be NULL (nplanes alone is the count).
+ *   window_export_fetch: one plane of record `rec` into out (npts * nlev doubles or floats); bit for bit
+ *     window_record_fetch into an array pre-filled with land_value (narrowed: that, converted).
+ *   window_export_fetch_record: the whole record into out (out_bytes >= record_bytes); the bytes between planes are
+ *     not specified.
+ *   The fetches fail as window_record_fetch does, with the same messages, for a record that is incomplete or
+ *     released; also for a schedule without an export, a plane it does not keep, or an out_bytes too small. */
+#define MCKPP_EXP_OFF 0
+#define MCKPP_EXP_F64 1
+#define MCKPP_EXP_F32 2
+int mckpp_hip_window_export(mckpp_hip_handle h, int sched, int dtype, double land_value);
+int mckpp_hip_window_export_layout(mckpp_hip_handle h, int sched, int32_t *nplanes, int32_t *field, int32_t *op,
+                                   int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes);
+int mckpp_hip_window_export_fetch(mckpp_hip_handle h, int sched, int64_t rec, int field, int op, void *out);
+int mckpp_hip_window_export_fetch_record(mckpp_hip_handle h, int sched, int64_t rec, void *out, int64_t out_bytes);
+
 /* Per-column status words (npts entries in 3D ordering; land = 0), number of
  * columns with a non-zero word, and (optional) vmix+ocnint passes per column
  * of the last step. Any output pointer may be NULL. */
@@ -562,6 +597,22 @@ int mckpp_hip_multi_window_schedule(mckpp_hip_multi_handle m, int sched, int nt_
 int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, double *out);
 int mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle m, int sched, int64_t upto_rec);
 int mckpp_hip_multi_window_records(mckpp_hip_multi_handle m, int sched, int64_t *first_kept, int64_t *last_complete);
+/* The export (mckpp_hip_window_export) over all shards: every shard packs its records compactly over its own resident
+ * columns, points fastest in resident order; a fetch starts every shard's copy into pinned staging at once and the
+ * host then merges them through the shards' point lists into `out`, setting land points to land_value
+ * (mckpp_host_export_merge).  The layout is that of one context over all npts points.  A handle with one shard
+ * copies straight into `out`. */
+int mckpp_hip_multi_window_export(mckpp_hip_multi_handle m, int sched, int dtype, double land_value);
+int mckpp_hip_multi_window_export_layout(mckpp_hip_multi_handle m, int sched, int32_t *nplanes, int32_t *field, int32_t *op,
+                                         int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes);
+int mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, void *out);
+int mckpp_hip_multi_window_export_fetch_record(mckpp_hip_multi_handle m, int sched, int64_t rec, void *out, int64_t out_bytes);
+/* The merge of the shards' planes (host only, no device work): out(npts, nlev), points fastest, of doubles
+ * (MCKPP_EXP_F64) or floats (MCKPP_EXP_F32).  Shard d holds ncol[d] columns, column c at point points[d][c]; its plane
+ * planes[d] is [nlev][ncol[d]] values of the same type.  A point of no shard gets land_value (converted to the
+ * type) at every level.  Returns <0 on a bad argument (a point outside 0..npts-1 included; `out` is then untouched). */
+int mckpp_host_export_merge(int64_t npts, int32_t nlev, int32_t dtype, double land_value, int32_t nshards,
+                            const int64_t *ncol, const int32_t *const *points, const void *const *planes, void *out);
 /* Restart set (src/mckpp_xios_io.F90:368-465) of all shards: one file per shard, <path>.<shard>of<ndev>.
  * load needs the state uploaded first (it gives the shards their column maps) and refuses files written for
  * another number of shards or another land mask, before anything resident is replaced. */

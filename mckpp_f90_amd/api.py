@@ -126,6 +126,55 @@ def _win_check_fetch(scheds, sched, field, op):
     return f
 
 
+# element types of an export (mckpp_hip_window_export): MCKPP_EXP_* of mckpp_hip.h
+EXP_OFF, EXP_F64, EXP_F32 = 0, 1, 2
+_EXP_DTYPES = {"f8": EXP_F64, "f4": EXP_F32, None: EXP_OFF}
+_EXP_NUMPY = {EXP_F64: np.dtype(np.float64), EXP_F32: np.dtype(np.float32)}
+
+
+def _exp_dtype(dtype):
+    """"f8", "f4" or None -> MCKPP_EXP_*, or ValueError."""
+    if dtype is not None and not isinstance(dtype, str):
+        raise ValueError(f"export dtype {dtype!r} (\"f8\", \"f4\" or None)")
+    if dtype not in _EXP_DTYPES:
+        raise ValueError(f"export dtype {dtype!r} (\"f8\", \"f4\" or None)")
+    return _EXP_DTYPES[dtype]
+
+
+def _exp_check_out(exports, sched, out):
+    """the array of an export fetch against the export of schedule `sched` (as this object set it): its numpy dtype"""
+    code = exports.get(int(sched))
+    if code is None:
+        raise ValueError(f"output schedule {sched} has no export")
+    want = _EXP_NUMPY[code]
+    if not isinstance(out, np.ndarray) or out.dtype != want:
+        raise ValueError(f"the export of output schedule {sched} holds {want.name}, not {getattr(out, 'dtype', type(out).__name__)}")
+    if not out.flags["F_CONTIGUOUS"] or not out.flags["WRITEABLE"]:
+        raise ValueError("the array of an export fetch must be writeable and contiguous in Fortran order")
+    return want
+
+
+def host_export_merge(npts, nlev, dtype, land_value, points, planes):
+    """mckpp_host_export_merge: the shards' planes - planes[d] is (ncol_d, nlev) in Fortran order, column c of shard d
+    at point points[d][c] - merged into out(npts, nlev) of `dtype` ("f8" or "f4"); points of no shard get land_value."""
+    code = _exp_dtype(dtype)
+    if code == EXP_OFF:
+        raise ValueError("export dtype None: nothing to merge")
+    want = _EXP_NUMPY[code]
+    points, planes = list(points), list(planes)
+    if len(planes) != len(points):
+        raise ValueError(f"{len(points)} point lists but {len(planes)} planes")
+    pts = [np.ascontiguousarray(p, dtype=np.int32) for p in points]
+    pls = [np.asfortranarray(p, dtype=want).reshape((len(q), int(nlev)), order="F") for p, q in zip(planes, pts)]
+    n = len(pts)
+    ncol = (C.c_int64 * max(n, 1))(*[len(p) for p in pts])
+    pp = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in pts])
+    pl = (C.c_void_p * max(n, 1))(*[p.ctypes.data for p in pls])
+    out = np.zeros((int(npts), int(nlev)), dtype=want, order="F")
+    _chk(_lib().mckpp_host_export_merge(int(npts), int(nlev), code, float(land_value), n, ncol, pp, pl, out.ctypes.data))
+    return out
+
+
 # kinds of the ancillary record series (MCKPP_ANC_* of mckpp_hip.h)
 (ANC_SST0, ANC_FCORR_TWOD, ANC_FCORR_WITHZ, ANC_SFCORR_WITHZ, ANC_OCNT_CLIM, ANC_SAL_CLIM, ANC_BOTTOM_TEMP,
  ANC_COUNT) = range(8)
@@ -237,6 +286,13 @@ def _bind(lib):
         getattr(lib, pre + "window_record_fetch").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, _dp]
         getattr(lib, pre + "window_record_release").argtypes = [C.c_void_p, C.c_int, C.c_int64]
         getattr(lib, pre + "window_records").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
+        if hasattr(lib, pre + "window_export"):   # (MCKPP_HIP_LIBRARY may name an older build, tools/export_rate.py --lib:
+            # everything else works with it, and a call of the export fails there by name)
+            getattr(lib, pre + "window_export").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
+            getattr(lib, pre + "window_export_layout").argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip, C.POINTER(C.c_int64),
+                                                                   C.POINTER(C.c_int64)]
+            getattr(lib, pre + "window_export_fetch").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
+            getattr(lib, pre + "window_export_fetch_record").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
         getattr(lib, pre + "restart_schedule").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
         getattr(lib, pre + "restart_snapshots").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
         getattr(lib, pre + "restart_snapshot_save").argtypes = [C.c_void_p, C.c_int64, C.c_char_p]
@@ -246,6 +302,9 @@ def _bind(lib):
                                                          C.POINTER(C.c_int32)]
         getattr(lib, pre + "step_log_fetch").argtypes = [C.c_void_p, C.c_int64] + [C.POINTER(C.c_int32)] * 4
         getattr(lib, pre + "step_log_clear").argtypes = [C.c_void_p]
+    if hasattr(lib, "mckpp_host_export_merge"):
+        lib.mckpp_host_export_merge.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int64),
+                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
     lib.mckpp_hip_multi_save_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_load_restart.argtypes = [C.c_void_p, C.c_char_p]
     lib.mckpp_hip_multi_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
@@ -419,6 +478,7 @@ class _WindowSchedules:
             if getattr(lib, self._pre + "window_records")(self._h, int(sched), C.byref(a), C.byref(a)) != 0:
                 self._scheds().pop(int(sched), None)   # (a refused schedule leaves the one in place; memory that could
             raise MckppHipError(err)                    # not be had leaves none)
+        self.__dict__.get("_wexport", {}).pop(int(sched), None)   # (a schedule set anew has no export)
         if len(f):
             self._scheds()[int(sched)] = {int(a): int(b) for a, b in zip(f, o)}
         else:
@@ -442,6 +502,58 @@ class _WindowSchedules:
         a, b = C.c_int64(), C.c_int64()
         _chk(getattr(_lib(), self._pre + "window_records")(self._h, int(sched), C.byref(a), C.byref(b)))
         return int(a.value), int(b.value)
+
+    # The export of a schedule's records (mckpp_hip_window_export): every step-launch call packs the records it completed
+    # into export slots in the host's layout, and a fetch is one copy behind the slot's event, on a stream of its own -
+    # it runs while later launches do.  The exports this object set are kept here (like the schedules) so that an array
+    # of the wrong type is refused before the library is called.
+    def _exports(self):
+        live = self.__dict__.setdefault("_wexport", {})
+        for s in [s for s in live if s not in self._scheds()]:   # (cancelled with its schedule)
+            del live[s]
+        return live
+
+    def window_export(self, sched, dtype, land_value=1e20):
+        """Export schedule `sched` as "f8" (double) or "f4" (narrowed to float after the mean's division); None drops the
+        export.  Land points of every plane hold land_value.  Records already complete are packed at once."""
+        code = _exp_dtype(dtype)
+        self._exports().pop(int(sched), None)
+        _chk(getattr(_lib(), self._pre + "window_export")(self._h, int(sched), code, float(land_value)))
+        if code != EXP_OFF:
+            self._exports()[int(sched)] = code
+
+    def window_export_layout(self, sched):
+        """(planes, record_bytes): planes is a list of (field, op, nlev, offset_bytes) in the order of a record - the
+        schedule's fields in its order, the kept ops of each in the order mean, min, max, last."""
+        lib = _lib()
+        f = getattr(lib, self._pre + "window_export_layout")
+        n, rb = C.c_int32(), C.c_int64()
+        _chk(f(self._h, int(sched), C.byref(n), None, None, None, None, C.byref(rb)))
+        fld, op, nlev = (np.zeros(n.value, dtype=np.int32) for _ in range(3))
+        off = np.zeros(n.value, dtype=np.int64)
+        _chk(f(self._h, int(sched), C.byref(n), fld.ctypes.data_as(_ip), op.ctypes.data_as(_ip), nlev.ctypes.data_as(_ip),
+               off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(rb)))
+        return [(int(a), int(b), int(c), int(d)) for a, b, c, d in zip(fld, op, nlev, off)], int(rb.value)
+
+    def window_export_fetch(self, sched, rec, field, op, out):
+        """Plane (field, op) of record `rec` through the export into out(npts[, nzp1]) (Fortran order, float64 or float32
+        as the export was set): what window_record_fetch gives into an array pre-filled with land_value."""
+        f = _win_check_fetch(self._scheds(), sched, field, op)
+        _exp_check_out(self._exports(), sched, out)
+        self._hold(out)
+        _chk(getattr(_lib(), self._pre + "window_export_fetch")(self._h, int(sched), int(rec), f, int(op), out.ctypes.data))
+        return out
+
+    def window_export_fetch_record(self, sched, rec, out):
+        """All of record `rec` through the export into the one-dimensional array `out` (at least record_bytes of
+        window_export_layout, whose offsets locate the planes)."""
+        _exp_check_out(self._exports(), sched, out)
+        if out.ndim != 1:
+            raise ValueError("the array of a whole-record fetch is one-dimensional")
+        self._hold(out)
+        _chk(getattr(_lib(), self._pre + "window_export_fetch_record")(self._h, int(sched), int(rec), out.ctypes.data,
+                                                                       int(out.nbytes)))
+        return out
 
 
 class _RestartSchedule:

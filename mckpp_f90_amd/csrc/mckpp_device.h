@@ -202,6 +202,20 @@ hipError_t mckpp_launch_out_sample(const double *src, int src_ld, int src_off, c
                                    int64_t ncol, int nlev, int ld_out, double *sum, double *mn, double *mx, int first,
                                    double *inst, hipStream_t stream);
 hipError_t mckpp_launch_window_mean(const double *sum, double *out, size_t n, double count, hipStream_t stream);
+// One plane of an export record (mckpp_hip_window_export; k_record_pack): operation `op` (0 mean: sum / period,
+// 1 min, 2 max, 3 last) of one field of a schedule.  Ring slot s of the plane is rows [ncol][ld] at src + s *
+// slot_stride, elements off .. off + nlev - 1 of a row; it goes to dst_off bytes (a multiple of 256) into the export
+// slot, as [nlev][npts] values.
+struct mckpp_pack_plane {
+  const double *src;
+  long long slot_stride, dst_off;
+  int ld, off, nlev, op;
+};
+// all `nplanes` planes of the record in ring slot `ring_slot` into the export slot at dst_slot; maxlev: the most
+// levels of a plane; ipt null: point = column; f32: the slot holds floats
+hipError_t mckpp_launch_record_pack(const mckpp_pack_plane *tab, int nplanes, int maxlev, int ring_slot, double period,
+                                    const int *ipt, int64_t ncol, int64_t npts, void *dst_slot, int f32, hipStream_t stream);
+hipError_t mckpp_launch_export_fill(void *p, size_t nelem, double v, int f32, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

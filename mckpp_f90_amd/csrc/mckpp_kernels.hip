@@ -186,7 +186,88 @@ __global__ void k_window_mean(const double *__restrict__ sum, double *__restrict
   if (i < n) out[i] = sum[i] / count;
 }
 
+// ---------------------------------------------------------------------------
+// Export of an output schedule's records (mckpp_hip_window_export): one launch packs every plane of one record into
+// an export slot, in the layout the host wants - plane(point, level) with points fastest, no ld padding, through the
+// column map (null: the columns themselves, a shard's compact form), as double or narrowed to float - so that the
+// fetch is a plain copy.  The planes go on blockIdx.z and are described by the table the export built.  The mean is
+// k_window_mean's one division; the narrowing, after it, is one round-to-nearest-even conversion.  The 64x64 tile
+// through LDS is k_scatter_rows': both sides move whole segments.  Only resident columns are written: the slot's
+// land points were filled when the export was set.
+// ---------------------------------------------------------------------------
+template <class T>
+__global__ __launch_bounds__(256) void k_record_pack(const mckpp_pack_plane *__restrict__ tab, int ring_slot, double period,
+                                                     const int *__restrict__ ipt, int64_t ncol, int64_t npts,
+                                                     char *__restrict__ dst_slot)
+{
+  __shared__ double tile[64][65];
+  const mckpp_pack_plane e = tab[blockIdx.z];
+  const int l0 = blockIdx.y * 64;
+  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  const bool mean = e.op == 0;
+  const double *__restrict__ src = e.src + (long long)ring_slot * e.slot_stride;
+  T *__restrict__ dst = reinterpret_cast<T *>(dst_slot + e.dst_off);
+  const int64_t c0 = (int64_t)blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  if (e.nlev == 1) {   // a two-dimensional field: nothing to transpose, a column per thread; the grid's x extent is
+    // that of 64-column tiles, so every fourth workgroup takes 256 columns and the others leave
+    if (blockIdx.x & 3) return;
+    const int64_t c = c0 + threadIdx.x;
+    if (c < ncol) {
+      double v = src[c * e.ld + e.off];
+      if (mean) v = v / period;
+      dst[ipt ? (int64_t)ipt[c] : c] = (T)v;
+    }
+    return;
+  }
+  for (int cc = ty; cc < 64; cc += 4) {       // read: levels fastest
+    const int64_t c = c0 + cc;
+    const int lev = l0 + tx;
+    double v = 0.0;
+    if (c < ncol && lev < e.nlev) v = src[c * e.ld + e.off + lev];
+    if (mean) v = v / period;
+    tile[tx][cc] = v;
+  }
+  __syncthreads();
+  const int64_t c = c0 + tx;
+  const int64_t pt = c < ncol ? (ipt ? (int64_t)ipt[c] : c) : 0;
+  for (int l = ty; l < 64; l += 4) {          // write: points fastest
+    const int lev = l0 + l;
+    if (c < ncol && lev < e.nlev) dst[(int64_t)lev * npts + pt] = (T)tile[l][tx];
+  }
+}
+
+template <class T>
+__global__ void k_export_fill(T *__restrict__ p, size_t n, T v)
+{
+  for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
+}
+
 }  // namespace
+
+hipError_t mckpp_launch_record_pack(const mckpp_pack_plane *tab, int nplanes, int maxlev, int ring_slot, double period,
+                                    const int *ipt, int64_t ncol, int64_t npts, void *dst_slot, int f32, hipStream_t stream)
+{
+  if (ncol <= 0 || nplanes <= 0 || maxlev <= 0) return hipSuccess;
+  dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  if (f32)
+    hipLaunchKernelGGL(k_record_pack<float>, grid, dim3(256), 0, stream, tab, ring_slot, period, ipt, ncol, npts,
+                       static_cast<char *>(dst_slot));
+  else
+    hipLaunchKernelGGL(k_record_pack<double>, grid, dim3(256), 0, stream, tab, ring_slot, period, ipt, ncol, npts,
+                       static_cast<char *>(dst_slot));
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_export_fill(void *p, size_t nelem, double v, int f32, hipStream_t stream)
+{
+  if (nelem == 0) return hipSuccess;
+  const size_t want = (nelem + 255) / 256;
+  const unsigned nb = (unsigned)(want < 8192 ? want : 8192);
+  if (f32) hipLaunchKernelGGL(k_export_fill<float>, dim3(nb), dim3(256), 0, stream, static_cast<float *>(p), nelem, (float)v);
+  else hipLaunchKernelGGL(k_export_fill<double>, dim3(nb), dim3(256), 0, stream, static_cast<double *>(p), nelem, v);
+  return hipGetLastError();
+}
 
 
 // Which XCDs does this device have?  Every workgroup of a large grid ORs the bit of the XCC it runs on (read from

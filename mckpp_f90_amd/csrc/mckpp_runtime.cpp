@@ -128,6 +128,23 @@ struct mckpp_hip_ctx {
     int nrec = 1;
     int64_t first_nt = -1, next_nt = -1;   // the first step run under the schedule, the step the next launch must start at (-1: none yet)
     int64_t first_kept = 0;                // the records before it are released, or began before first_nt
+    // its export (mckpp_hip_window_export; dtype MCKPP_EXP_OFF: none): nrec slots of record_bytes each, record w in slot
+    // w % nrec like the ring's, every plane as [nlev][npts] values of the dtype (npts: the grid's points, or with
+    // `compact` - a shard of a multi handle - the resident columns themselves); per slot the event behind the launch
+    // that packed it; the device table of the planes (k_record_pack)
+    struct exp_plane { int field, op, nlev; int64_t offset; };
+    struct win_export {
+      int dtype = 0;
+      bool compact = false;
+      double land = 0;
+      int64_t npts = 0;
+      size_t record_bytes = 0;
+      int maxlev = 0;
+      std::vector<exp_plane> planes;
+      char *slots = nullptr;
+      mckpp_pack_plane *d_tab = nullptr;
+      std::vector<hipEvent_t> ev;
+    } ex;
   } wsched[MCKPP_WIN_SCHEDULES];
   mckpp_win *d_win = nullptr;   // [MCKPP_WIN_ENTRIES]
   int nwin = 0;                 // entries of d_win in use (mckpp_kparams_t::nwin of the step launches)
@@ -1245,6 +1262,7 @@ struct forced_run { int ndtocn, l_rest; double flsn, el; };
 
 static int win_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
+static int exp_advance(mckpp_hip_ctx *h, int nt0);
 static int snap_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 static int snap_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
 static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced);
@@ -1264,6 +1282,7 @@ static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_r
   if (sched && anc_prepare(h, ntime, nsteps, who)) return -1;
   if (run_launch(h, ntime, nsteps, mode, forced)) return -1;
   if (sched) win_advance(h, ntime, nsteps);
+  if (sched && exp_advance(h, ntime)) return -1;
   if (sched && snap_advance(h, ntime, nsteps)) return -1;
   return 0;
 }
@@ -2258,8 +2277,20 @@ int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
 // released; a launch that would break it fails before anything is launched.
 // ---------------------------------------------------------------------------
 
+// the schedule's export goes (nothing of it is in flight: its fetches end with a wait for the transfer stream, and the
+// callers have waited for the context's)
+static void exp_drop(mckpp_hip_ctx::win_sched &w)
+{
+  auto &x = w.ex;
+  if (x.slots) hipFree(x.slots);
+  if (x.d_tab) hipFree(x.d_tab);
+  for (auto e : x.ev) if (e) hipEventDestroy(e);
+  x = mckpp_hip_ctx::win_sched::win_export{};
+}
+
 static void win_cancel(mckpp_hip_ctx *h, int s)
 {
+  exp_drop(h->wsched[s]);
   for (auto *p : h->wsched[s].acc) if (p) hipFree(p);
   h->wsched[s] = mckpp_hip_ctx::win_sched{};
 }
@@ -2400,19 +2431,21 @@ int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int 
   return win_table(h);
 }
 
-// the record's plane of one field and operation on the device (the mean formed into the staging buffer), or an error
-// that names the record's steps
-static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, int field, int op,
-                      const double **src_out, int *ld_out, int *nlev)
+// may record `rec` of the schedule be fetched - all of it (plane false), or its plane of `field` and `op`, whose index
+// among the schedule's fields comes back in *fi?  Otherwise an error that names the record's steps.
+static int win_record_check(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, bool plane, int field, int op, size_t *fi)
 {
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
   const auto &w = h->wsched[sched];
   if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
-  if (op < 0 || op > 3) return fail("%s: op %d (0 mean, 1 min, 2 max, 3 last)", who, op);
   size_t i = 0;
-  while (i < w.fields.size() && w.fields[i] != field) ++i;
-  if (i == w.fields.size()) return fail("%s: field %d is not in schedule %d", who, field, sched);
-  if (!((w.ops[i] >> op) & 1u)) return fail("%s: schedule %d keeps no op %d of field %d (operations 0x%x)", who, sched, op, field, w.ops[i]);
+  if (plane) {
+    if (op < 0 || op > 3) return fail("%s: op %d (0 mean, 1 min, 2 max, 3 last)", who, op);
+    while (i < w.fields.size() && w.fields[i] != field) ++i;
+    if (i == w.fields.size()) return fail("%s: field %d is not in schedule %d", who, field, sched);
+    if (!((w.ops[i] >> op) & 1u)) return fail("%s: schedule %d keeps no op %d of field %d (operations 0x%x)", who, sched, op, field, w.ops[i]);
+  }
+  if (fi) *fi = i;
   if (rec < 0) return fail("%s: record %lld", who, (long long)rec);
   const long long a = w.origin + rec * w.period, b = a + w.period - 1;
   if (w.first_nt >= 0 && a < w.first_nt)
@@ -2422,6 +2455,17 @@ static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec,
   if (w.next_nt < 0 || b >= w.next_nt)
     return fail("%s: record %lld of schedule %d (steps %lld..%lld) is incomplete: steps have run up to %lld", who,
                 (long long)rec, sched, a, b, (long long)(w.next_nt < 0 ? w.origin - 1 : w.next_nt - 1));
+  return 0;
+}
+
+// the record's plane of one field and operation on the device (the mean formed into the staging buffer), or an error
+// that names the record's steps
+static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, int field, int op,
+                      const double **src_out, int *ld_out, int *nlev)
+{
+  size_t i = 0;
+  if (win_record_check(h, who, sched, rec, true, field, op, &i)) return -1;
+  const auto &w = h->wsched[sched];
   out_desc d;
   if (out_field(h, field, d)) return -1;
   *ld_out = w.ld_out[i];
@@ -2480,6 +2524,238 @@ int mckpp_hip_window_records(mckpp_hip_handle h, int sched, int64_t *first_kept,
   if (first_kept) *first_kept = w.first_kept;
   if (last_complete) *last_complete = win_last_complete(w);
   return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The export of a schedule's records (mckpp_hip_window_export).  window_record_fetch re-lays a plane on the context's
+// stream and waits for it, so it cannot run under a later launch - and nothing but DMA can: k_column_ps fills every
+// CU.  So all re-laying happens between the launches, on the context's stream: behind the launches of a call, one
+// k_record_pack per record the call completed packs the record into its export slot, in the layout the host wants,
+// and an event marks the slot.  A fetch is then one copy on the transfer stream behind that event; it never touches
+// the context's stream.  The ring guard keeps later launches off the slots of unreleased records, as for snapshots.
+// ---------------------------------------------------------------------------
+using win_sched_t = mckpp_hip_ctx::win_sched;
+
+static size_t exp_elem(int dtype) { return dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double); }
+
+// the planes of a record of `w` over npts points: the fields in the schedule's order, the kept operations of each in
+// bit order, every offset a multiple of 256 bytes
+static int exp_layout(mckpp_hip_ctx *h, const win_sched_t &w, int64_t npts, int dtype, std::vector<win_sched_t::exp_plane> &planes,
+                      size_t &record_bytes, int &maxlev)
+{
+  planes.clear();
+  size_t off = 0;
+  maxlev = 0;
+  for (size_t i = 0; i < w.fields.size(); ++i) {
+    out_desc d;
+    if (out_field(h, w.fields[i], d)) return -1;
+    for (int op = 0; op < 4; ++op) {
+      if (!((w.ops[i] >> op) & 1u)) continue;
+      planes.push_back({w.fields[i], op, d.nlev, (int64_t)off});
+      off += (size_t)npts * (size_t)d.nlev * exp_elem(dtype);
+      off = (off + 255) & ~(size_t)255;
+      maxlev = std::max(maxlev, d.nlev);
+    }
+  }
+  record_bytes = off;
+  return 0;
+}
+
+// record `rec` into its export slot, and the slot's event, behind whatever the context's stream holds
+static int exp_pack(mckpp_hip_ctx *h, win_sched_t &w, int64_t rec)
+{
+  auto &x = w.ex;
+  const size_t slot = (size_t)(rec % w.nrec);
+  if (x.slots && h->ncol > 0)
+    HIPCHK(mckpp_launch_record_pack(x.d_tab, (int)x.planes.size(), x.maxlev, (int)slot, (double)w.period,
+                                    x.compact ? nullptr : h->d_ipt, h->ncol, x.npts, x.slots + slot * x.record_bytes,
+                                    x.dtype == MCKPP_EXP_F32, h->stream));
+  HIPCHK(hipEventRecord(x.ev[slot], h->stream));
+  return 0;
+}
+
+// after the launches of a call that began at step nt0 (win_advance has run): every record the call completed - one
+// begun in an earlier call included - is packed
+static int exp_advance(mckpp_hip_ctx *h, int nt0)
+{
+  if (h->ncol == 0) return 0;
+  for (auto &w : h->wsched) {
+    if (w.fields.empty() || w.ex.dtype == MCKPP_EXP_OFF) continue;
+    const int64_t before = nt0 >= w.origin ? (nt0 - w.origin) / w.period - 1 : -1;   // complete before the call
+    const int64_t lc = win_last_complete(w);
+    for (int64_t rec = std::max(before + 1, w.first_kept); rec <= lc; ++rec)
+      if (exp_pack(h, w, rec)) return -1;
+  }
+  return 0;
+}
+
+// a new export's first work on the stream: the land points, once - no step ever writes them (a shard's compact slots
+// have none) -, every slot's event, and at once the records that are complete and not released
+static int exp_start(mckpp_hip_ctx *h, win_sched_t &w, size_t total)
+{
+  const auto &x = w.ex;
+  if (!x.compact && total > 0)
+    HIPCHK(mckpp_launch_export_fill(x.slots, total / exp_elem(x.dtype), x.land, x.dtype == MCKPP_EXP_F32, h->stream));
+  for (auto ev : x.ev) HIPCHK(hipEventRecord(ev, h->stream));
+  if (w.first_nt >= 0)
+    for (int64_t rec = w.first_kept; rec <= win_last_complete(w); ++rec)
+      if (exp_pack(h, w, rec)) return -1;
+  return 0;
+}
+
+static int exp_set(mckpp_hip_ctx *h, const char *who, int sched, int dtype, double land_value, bool compact)
+{
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  auto &w = h->wsched[sched];
+  if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
+  if (dtype != MCKPP_EXP_OFF && dtype != MCKPP_EXP_F64 && dtype != MCKPP_EXP_F32)
+    return fail("%s: dtype %d (MCKPP_EXP_OFF 0, MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, dtype);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));   // no pack in flight may still write the slots
+  exp_drop(w);
+  if (dtype == MCKPP_EXP_OFF) return 0;
+  win_sched_t::win_export x;
+  x.dtype = dtype; x.compact = compact; x.land = land_value;
+  x.npts = compact ? h->ncol : h->npts;
+  if (exp_layout(h, w, x.npts, dtype, x.planes, x.record_bytes, x.maxlev)) return -1;
+  std::vector<mckpp_pack_plane> tab;
+  for (const auto &p : x.planes) {
+    size_t i = 0;
+    while (w.fields[i] != p.field) ++i;
+    const long long n = (long long)h->ncol * w.ld_out[i];
+    mckpp_pack_plane e{};
+    e.src = w.acc[i] + (long long)__builtin_popcount(w.ops[i] & ((1u << p.op) - 1u)) * n;
+    e.slot_stride = (long long)__builtin_popcount(w.ops[i]) * n;
+    e.dst_off = p.offset;
+    e.ld = w.ld_out[i]; e.off = 0; e.nlev = p.nlev; e.op = p.op;
+    tab.push_back(e);
+  }
+  const size_t total = (size_t)w.nrec * x.record_bytes;
+  x.ev.assign((size_t)w.nrec, nullptr);
+  hipError_t e = hipSuccess;
+  if (!h->snap_stream) e = hipStreamCreateWithFlags(&h->snap_stream, hipStreamNonBlocking);
+  if (e == hipSuccess && total > 0) e = hipMalloc(&x.slots, total);
+  if (e == hipSuccess) e = hipMalloc(&x.d_tab, tab.size() * sizeof(mckpp_pack_plane));
+  for (int i = 0; i < w.nrec && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&x.ev[(size_t)i], hipEventDisableTiming);
+  if (e == hipSuccess) e = hipMemcpy(x.d_tab, tab.data(), tab.size() * sizeof(mckpp_pack_plane), hipMemcpyHostToDevice);
+  if (e != hipSuccess) {
+    (void)hipGetLastError();
+    if (x.slots) hipFree(x.slots);
+    if (x.d_tab) hipFree(x.d_tab);
+    for (auto ev : x.ev) if (ev) hipEventDestroy(ev);
+    return fail("%s: cannot allocate %zu bytes of device memory for the %d export slots of schedule %d (%s); the schedule "
+                "stays set, without an export", who, total, w.nrec, sched, hipGetErrorString(e));
+  }
+  w.ex = x;
+  if (exp_start(h, w, total)) {   // a failed call leaves the schedule without an export
+    (void)hipStreamSynchronize(h->stream);
+    exp_drop(w);
+    return -1;
+  }
+  return 0;
+}
+
+int mckpp_hip_window_export(mckpp_hip_handle h, int sched, int dtype, double land_value)
+{
+  const char *who = "mckpp_hip_window_export";
+  if (!h) return fail("%s: null handle", who);
+  return exp_set(h, who, sched, dtype, land_value, false);
+}
+
+// the layout of a record of the schedule's export over npts points
+static int exp_layout_out(mckpp_hip_ctx *h, const char *who, int sched, int64_t npts, int32_t *nplanes, int32_t *field, int32_t *op,
+                          int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes)
+{
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  const auto &w = h->wsched[sched];
+  if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
+  if (w.ex.dtype == MCKPP_EXP_OFF) return fail("%s: schedule %d has no export (mckpp_hip_window_export)", who, sched);
+  std::vector<win_sched_t::exp_plane> planes;
+  size_t rb = 0;
+  int maxlev = 0;
+  if (exp_layout(h, w, npts, w.ex.dtype, planes, rb, maxlev)) return -1;
+  if (nplanes) *nplanes = (int32_t)planes.size();
+  for (size_t k = 0; k < planes.size(); ++k) {
+    if (field) field[k] = planes[k].field;
+    if (op) op[k] = planes[k].op;
+    if (nlev) nlev[k] = planes[k].nlev;
+    if (offset_bytes) offset_bytes[k] = planes[k].offset;
+  }
+  if (record_bytes) *record_bytes = (int64_t)rb;
+  return 0;
+}
+
+int mckpp_hip_window_export_layout(mckpp_hip_handle h, int sched, int32_t *nplanes, int32_t *field, int32_t *op, int32_t *nlev,
+                                   int64_t *offset_bytes, int64_t *record_bytes)
+{
+  const char *who = "mckpp_hip_window_export_layout";
+  if (!h) return fail("%s: null handle", who);
+  return exp_layout_out(h, who, sched, h->npts, nplanes, field, op, nlev, offset_bytes, record_bytes);
+}
+
+// may record `rec` (plane: its plane of field and op, whose index among the export's planes comes back) be fetched
+// through the export?  win_record's checks and messages, then the export's own
+static int exp_check(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, bool plane, int field, int op, size_t *k)
+{
+  if (win_record_check(h, who, sched, rec, plane, field, op, nullptr)) return -1;
+  const auto &x = h->wsched[sched].ex;
+  if (x.dtype == MCKPP_EXP_OFF) return fail("%s: schedule %d has no export (mckpp_hip_window_export)", who, sched);
+  size_t i = 0;
+  if (plane) while (x.planes[i].field != field || x.planes[i].op != op) ++i;   // (kept: win_record_check)
+  if (k) *k = i;
+  return 0;
+}
+
+// `bytes` from `off` of the record's slot on their way into `out`, on the transfer stream behind the slot's event
+static int exp_copy_start(mckpp_hip_ctx *h, const win_sched_t &w, int64_t rec, size_t off, size_t bytes, void *out)
+{
+  if (bytes == 0 || !w.ex.slots) return 0;
+  const size_t slot = (size_t)(rec % w.nrec);
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamWaitEvent(h->snap_stream, w.ex.ev[slot], 0));
+  HIPCHK(hipMemcpyAsync(out, w.ex.slots + slot * w.ex.record_bytes + off, bytes, hipMemcpyDeviceToHost, h->snap_stream));
+  return 0;
+}
+
+static int exp_copy_finish(mckpp_hip_ctx *h)
+{
+  if (!h->snap_stream) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->snap_stream));
+  return 0;
+}
+
+static int exp_fetch(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, bool plane, int field, int op, void *out,
+                     int64_t out_bytes)
+{
+  size_t k = 0;
+  if (exp_check(h, who, sched, rec, plane, field, op, &k)) return -1;
+  const auto &w = h->wsched[sched];
+  const auto &x = w.ex;
+  size_t off = 0, bytes = x.record_bytes;
+  if (plane) { off = (size_t)x.planes[k].offset; bytes = (size_t)x.npts * (size_t)x.planes[k].nlev * exp_elem(x.dtype); }
+  else if (out_bytes < (int64_t)x.record_bytes)
+    return fail("%s: out_bytes %lld, but a record of schedule %d takes %zu bytes", who, (long long)out_bytes, sched, x.record_bytes);
+  pin_host(h, out, bytes);
+  const int rc = exp_copy_start(h, w, rec, off, bytes, out);
+  if (exp_copy_finish(h)) return -1;   // (also behind a copy that could not be started: nothing stays in flight)
+  return rc;
+}
+
+int mckpp_hip_window_export_fetch(mckpp_hip_handle h, int sched, int64_t rec, int field, int op, void *out)
+{
+  const char *who = "mckpp_hip_window_export_fetch";
+  if (!h) return fail("%s: null handle", who);
+  if (!out) return fail("%s: null argument", who);
+  return exp_fetch(h, who, sched, rec, true, field, op, out, 0);
+}
+
+int mckpp_hip_window_export_fetch_record(mckpp_hip_handle h, int sched, int64_t rec, void *out, int64_t out_bytes)
+{
+  const char *who = "mckpp_hip_window_export_fetch_record";
+  if (!h) return fail("%s: null handle", who);
+  if (!out) return fail("%s: null argument", who);
+  return exp_fetch(h, who, sched, rec, false, 0, 0, out, out_bytes);
 }
 
 int mckpp_hip_status(mckpp_hip_handle h, int32_t *per_col, int64_t *n_flagged, int32_t *npasses)
@@ -2587,6 +2863,9 @@ struct mckpp_hip_multi {
   std::vector<hipEvent_t> ev_owner;         // [ndev], each on its shard's device
   std::vector<hipEvent_t> ev_done;          // [ndev], on the root device
   hipEvent_t ev_init = nullptr, ev_gcopy = nullptr;   // on the root device: 3-D image ready for the shards / delivered to the host
+  // pinned staging the shards' export planes arrive in before the host merges them (mckpp_hip_multi_window_export_fetch)
+  char *h_exp = nullptr;
+  size_t h_exp_bytes = 0;
 };
 
 // run_physics mask of shard `dev` of `ndev`: the j-th ocean point (in ipt order) goes to shard j mod ndev
@@ -2653,6 +2932,7 @@ int mckpp_hip_multi_finalize(mckpp_hip_multi_handle m)
 {
   if (!m) return 0;
   multi_release_root(m);
+  if (m->h_exp) hipHostFree(m->h_exp);
   for (size_t d = 0; d < m->ev_owner.size(); ++d)
     if (m->ev_owner[d]) { hipSetDevice(m->ctx[d]->device); hipEventDestroy(m->ev_owner[d]); }
   for (auto *x : m->ctx) mckpp_hip_finalize(x);
@@ -2955,6 +3235,162 @@ int mckpp_hip_multi_window_records(mckpp_hip_multi_handle m, int sched, int64_t 
 {
   if (!m) return fail("mckpp_hip_multi_window_records: null handle");
   return mckpp_hip_window_records(m->ctx[0], sched, first_kept, last_complete);
+}
+
+// ---- the export (mckpp_hip_window_export) over all shards
+extern "C++" {
+namespace {
+template <class T>
+void export_merge_t(int64_t npts, int nlev, T land, int nsh, const int64_t *ncol, const int32_t *const *points,
+                    const void *const *planes, T *out, const unsigned char *covered)
+{
+  for_columns(npts, [&](int64_t i0, int64_t i1) {
+    for (int l = 0; l < nlev; ++l)
+      for (int64_t i = i0; i < i1; ++i)
+        if (!covered[i]) out[(int64_t)l * npts + i] = land;
+  });
+  for (int d = 0; d < nsh; ++d) {
+    const int64_t n = ncol[d];
+    const T *p = static_cast<const T *>(planes[d]);
+    const int32_t *pt = points[d];
+    for_columns(n, [&](int64_t c0, int64_t c1) {
+      for (int l = 0; l < nlev; ++l)
+        for (int64_t c = c0; c < c1; ++c) out[(int64_t)l * npts + pt[c]] = p[(int64_t)l * n + c];
+    });
+  }
+}
+
+void export_merge(int64_t npts, int nlev, int dtype, double land, int nsh, const int64_t *ncol, const int32_t *const *points,
+                  const void *const *planes, void *out, const unsigned char *covered)
+{
+  if (dtype == MCKPP_EXP_F32) export_merge_t<float>(npts, nlev, (float)land, nsh, ncol, points, planes, static_cast<float *>(out), covered);
+  else export_merge_t<double>(npts, nlev, land, nsh, ncol, points, planes, static_cast<double *>(out), covered);
+}
+
+// which points belong to a shard; -1 for a point outside the grid
+int export_covered(int64_t npts, int nsh, const int64_t *ncol, const int32_t *const *points, std::vector<unsigned char> &covered)
+{
+  covered.assign((size_t)npts, 0);
+  for (int d = 0; d < nsh; ++d)
+    for (int64_t c = 0; c < ncol[d]; ++c) {
+      const int64_t i = points[d][c];
+      if (i < 0 || i >= npts) return -1;
+      covered[(size_t)i] = 1;
+    }
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_host_export_merge(int64_t npts, int32_t nlev, int32_t dtype, double land_value, int32_t nshards, const int64_t *ncol,
+                            const int32_t *const *points, const void *const *planes, void *out)
+{
+  const char *who = "mckpp_host_export_merge";
+  if (npts < 0 || nlev < 1 || nshards < 0 || (nshards > 0 && (!ncol || !points || !planes)) || (npts > 0 && !out))
+    return fail("%s: bad argument (npts=%lld nlev=%d nshards=%d)", who, (long long)npts, nlev, nshards);
+  if (dtype != MCKPP_EXP_F64 && dtype != MCKPP_EXP_F32) return fail("%s: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, dtype);
+  for (int d = 0; d < nshards; ++d)
+    if (ncol[d] < 0 || (ncol[d] > 0 && (!points[d] || !planes[d]))) return fail("%s: shard %d: bad argument (ncol=%lld)", who, d, (long long)ncol[d]);
+  try {
+    std::vector<unsigned char> covered;
+    if (export_covered(npts, nshards, ncol, points, covered)) return fail("%s: a point outside 0..%lld", who, (long long)npts - 1);
+    export_merge(npts, nlev, dtype, land_value, nshards, ncol, points, planes, out, covered.data());
+  } catch (const std::exception &e) {
+    return fail("%s: %s", who, e.what());
+  }
+  return 0;
+}
+
+int mckpp_hip_multi_window_export(mckpp_hip_multi_handle m, int sched, int dtype, double land_value)
+{
+  const char *who = "mckpp_hip_multi_window_export";
+  if (!m) return fail("%s: null handle", who);
+  const bool compact = m->ctx.size() > 1;
+  for (auto *x : m->ctx)
+    if (exp_set(x, who, sched, dtype, land_value, compact) != 0) {   // all shards or none
+      const std::string why = g_err;
+      for (auto *y : m->ctx)
+        if (sched >= 0 && sched < MCKPP_WIN_SCHEDULES && !y->wsched[sched].fields.empty()) exp_set(y, who, sched, MCKPP_EXP_OFF, 0.0, compact);
+      return fail("%s", why.c_str());
+    }
+  return 0;
+}
+
+int mckpp_hip_multi_window_export_layout(mckpp_hip_multi_handle m, int sched, int32_t *nplanes, int32_t *field, int32_t *op,
+                                         int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes)
+{
+  const char *who = "mckpp_hip_multi_window_export_layout";
+  if (!m) return fail("%s: null handle", who);
+  return exp_layout_out(m->ctx[0], who, sched, m->npts, nplanes, field, op, nlev, offset_bytes, record_bytes);
+}
+
+// every shard's copy into the pinned staging is started before any is waited for; the host then merges
+static int multi_exp_fetch(mckpp_hip_multi *m, const char *who, int sched, int64_t rec, bool plane, int field, int op, void *out,
+                           int64_t out_bytes)
+{
+  if (!m) return fail("%s: null handle", who);
+  if (!out) return fail("%s: null argument", who);
+  const int ndev = (int)m->ctx.size();
+  if (ndev == 1) return exp_fetch(m->ctx[0], who, sched, rec, plane, field, op, out, out_bytes);
+  if (m->npts <= 0) return fail("%s: nothing uploaded", who);
+  size_t k = 0;
+  for (auto *x : m->ctx)
+    if (exp_check(x, who, sched, rec, plane, field, op, &k)) return -1;
+  const auto &w0 = m->ctx[0]->wsched[sched];
+  const int dtype = w0.ex.dtype;
+  std::vector<win_sched_t::exp_plane> gp;   // the layout over all points
+  size_t grb = 0;
+  int maxlev = 0;
+  if (exp_layout(m->ctx[0], w0, m->npts, dtype, gp, grb, maxlev)) return -1;
+  if (!plane && out_bytes < (int64_t)grb)
+    return fail("%s: out_bytes %lld, but a record of schedule %d takes %zu bytes", who, (long long)out_bytes, sched, grb);
+  try {
+    std::vector<size_t> at((size_t)ndev, 0), nb((size_t)ndev, 0);
+    size_t total = 0;
+    for (int d = 0; d < ndev; ++d) {
+      const auto &x = m->ctx[d]->wsched[sched].ex;
+      nb[(size_t)d] = plane ? (size_t)x.npts * (size_t)x.planes[k].nlev * exp_elem(dtype) : x.record_bytes;
+      at[(size_t)d] = total;
+      total += (nb[(size_t)d] + 255) & ~(size_t)255;
+    }
+    if (total > m->h_exp_bytes) {
+      if (m->h_exp) hipHostFree(m->h_exp);
+      m->h_exp = nullptr; m->h_exp_bytes = 0;
+      HIPCHK(hipHostMalloc(&m->h_exp, total, hipHostMallocPortable));
+      m->h_exp_bytes = total;
+    }
+    int rc = 0;
+    for (int d = 0; d < ndev && rc == 0; ++d) {
+      const auto &w = m->ctx[d]->wsched[sched];
+      rc = exp_copy_start(m->ctx[d], w, rec, plane ? (size_t)w.ex.planes[k].offset : 0, nb[(size_t)d], m->h_exp + at[(size_t)d]);
+    }
+    for (auto *x : m->ctx) if (exp_copy_finish(x)) return -1;
+    if (rc) return -1;
+    std::vector<int64_t> ncol((size_t)ndev);
+    std::vector<const int32_t *> points((size_t)ndev);
+    std::vector<const void *> planes((size_t)ndev);
+    for (int d = 0; d < ndev; ++d) { ncol[(size_t)d] = m->ctx[d]->ncol; points[(size_t)d] = m->ctx[d]->ipt.data(); }
+    std::vector<unsigned char> covered;
+    if (export_covered(m->npts, ndev, ncol.data(), points.data(), covered)) return fail("%s: a shard's point outside the grid", who);
+    for (size_t q = plane ? k : 0; q < (plane ? k + 1 : gp.size()); ++q) {
+      for (int d = 0; d < ndev; ++d)
+        planes[(size_t)d] = m->h_exp + at[(size_t)d] + (plane ? 0 : (size_t)m->ctx[d]->wsched[sched].ex.planes[q].offset);
+      export_merge(m->npts, gp[q].nlev, dtype, w0.ex.land, ndev, ncol.data(), points.data(), planes.data(),
+                   static_cast<char *>(out) + (plane ? 0 : (size_t)gp[q].offset), covered.data());
+    }
+  } catch (const std::exception &e) {
+    return fail("%s: %s", who, e.what());
+  }
+  return 0;
+}
+
+int mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, void *out)
+{
+  return multi_exp_fetch(m, "mckpp_hip_multi_window_export_fetch", sched, rec, true, field, op, out, 0);
+}
+int mckpp_hip_multi_window_export_fetch_record(mckpp_hip_multi_handle m, int sched, int64_t rec, void *out, int64_t out_bytes)
+{
+  return multi_exp_fetch(m, "mckpp_hip_multi_window_export_fetch_record", sched, rec, false, 0, 0, out, out_bytes);
 }
 
 // one file per shard: <path>.<d>of<ndev>

@@ -10,7 +10,7 @@ program kpp_driver
   use mckpp_parameters
   use mckpp_data_fields
   use mckpp_time_control
-  use mckpp_hip_binding, only: MCKPP_F_SCALARS, mckpp_anc_epoch_c, MCKPP_ANC_SST0, MCKPP_ANC_OCNT_CLIM
+  use mckpp_hip_binding, only: MCKPP_F_SCALARS, mckpp_anc_epoch_c, MCKPP_ANC_SST0, MCKPP_ANC_OCNT_CLIM, MCKPP_EXP_F64
   use mckpp_physics_lookup_mod, only: mckpp_physics_lookup
   use mckpp_initialize_ocean, only: mckpp_initialize_ocean_model
   use mckpp_physics_driver_mod, only: mckpp_physics_driver, mckpp_physics_finalize
@@ -22,7 +22,8 @@ program kpp_driver
                                mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select, &
                                mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch, &
                                mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, &
-                               mckpp_hip_all_window_record_release, mckpp_hip_all_restart_schedule, &
+                               mckpp_hip_all_window_record_release, mckpp_hip_all_window_export, &
+                               mckpp_hip_all_window_export_fetch, mckpp_hip_all_restart_schedule, &
                                mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
                                mckpp_hip_all_restart_snapshot_release, mckpp_hip_all_step_log, &
                                mckpp_hip_all_set_ancillary_series, mckpp_hip_all_ancillary_schedule, &
@@ -36,7 +37,8 @@ program kpp_driver
   real(c_double) :: t0, t1
   real(c_double), allocatable :: vm_h(:), vm_k(:), vm_difm(:,:), vm_difs(:,:), vm_dift(:,:), vm_ghat(:,:)
   real(c_double) :: hmixn
-  integer :: kmixn, snap_first, snap_last
+  integer :: kmixn, snap_first, snap_last, ncut
+  real(c_double), allocatable :: exp_h(:,:), exp_t(:,:,:)   ! flag 4096: the records fetched through the export
   character(len=16) :: snap_name
   ! flag 2048: records of SST0 (npts, nrec) and ocnT_clim (npts, nzp1, nrec) and the epochs of ocnT_clim
   integer, parameter :: anc_cad_sst = 3, anc_cad_ocnt = 2
@@ -63,6 +65,9 @@ program kpp_driver
   !           mckpp_restart_control); after it every snapshot s goes to <out.bin>.rst<s> (one file per shard)
   !        1024 the time loop as ONE forced run under a step log of ncol * nsteps records: with flag 128 the located
   !           warnings of every step of the run, not only of its last
+  !        4096 with 256: the schedule's records through its export (land value -1): the steps as TWO forced runs, the
+  !           second begun inside a window, and the first run's records fetched while the second is queued; the same
+  !           appended records as flag 256 alone
   !        2048 L_RELAX_SST and L_RELAX_OCNT with SST0 changing every 3 steps (record after record) and ocnT_clim every 2
   !           (interpolated between two records, mckpp_boundary_interpolate_temp's sum), the records made from the
   !           case's own profiles.  With 16 the one forced run reads them from resident series under schedules; with 1
@@ -144,7 +149,24 @@ program kpp_driver
     else if (iand(flags, 256) /= 0) then   ! the same output, accumulated inside the one forced run
       call mckpp_hip_all_window_schedule(0, 1, 2, nsteps / 2, [4_c_int32_t, 2_c_int32_t], &   ! MCKPP_OUT_HMIX, MCKPP_OUT_T
                                          [1_c_int32_t, 4_c_int32_t])                          ! MCKPP_WIN_MEAN, MCKPP_WIN_MAX
-      call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)
+      if (iand(flags, 4096) /= 0 .and. nsteps >= 4) then
+        allocate (exp_h(ncol, nsteps / 2), exp_t(ncol, nzp1, nsteps / 2))
+        call mckpp_hip_all_window_export(0, MCKPP_EXP_F64, -1._c_double)
+        ncut = ior(nsteps / 2, 1)   ! odd: the window of steps ncut, ncut + 1 is cut by the two runs
+        call mckpp_hip_all_run_forced(1, ncut, nsteps + 1)
+        call mckpp_hip_all_run_forced(ncut + 1, nsteps - ncut, nsteps + 1)
+        do nt = 0, ncut / 2 - 1   ! the first run's records, while the second run is queued
+          call mckpp_hip_all_window_export_fetch(0, nt, 4, 0, exp_h(:, nt + 1))
+          call mckpp_hip_all_window_export_fetch(0, nt, 2, 2, exp_t(:, :, nt + 1))
+        end do
+        if (ncut / 2 > 0) call mckpp_hip_all_window_record_release(0, ncut / 2 - 1)
+        do nt = ncut / 2, nsteps / 2 - 1
+          call mckpp_hip_all_window_export_fetch(0, nt, 4, 0, exp_h(:, nt + 1))
+          call mckpp_hip_all_window_export_fetch(0, nt, 2, 2, exp_t(:, :, nt + 1))
+        end do
+      else
+        call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)
+      end if
     else if (iand(flags, 512) /= 0) then   ! restart output inside the one forced run
       call mckpp_hip_all_restart_schedule(1, 2, max(1, nsteps / 2))
       call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)
@@ -215,6 +237,10 @@ program kpp_driver
   if (iand(flags, 256) /= 0) then
     allocate (vm_h(ncol), vm_difm(ncol, nzp1))
     do nt = 0, hdr(3) / 2 - 1
+      if (allocated(exp_h)) then
+        write (u) exp_h(:, nt + 1), exp_t(:, :, nt + 1)
+        cycle
+      end if
       vm_h = -1; vm_difm = -1
       call mckpp_hip_all_window_record_fetch(0, nt, 4, 0, vm_h)
       call mckpp_hip_all_window_record_fetch(0, nt, 2, 2, vm_difm)

@@ -23,6 +23,8 @@ module mckpp_hip_binding
   ! operations of an output schedule (mckpp_hip_window_schedule): bit 2**op of a record fetch's op
   integer(c_int32_t), parameter :: MCKPP_WIN_MEAN = 1, MCKPP_WIN_MIN = 2, MCKPP_WIN_MAX = 4, MCKPP_WIN_LAST = 8
   integer(c_int), parameter :: MCKPP_OP_LAST = 3
+  ! element types of an export of a schedule's records (mckpp_hip_window_export)
+  integer(c_int), parameter :: MCKPP_EXP_OFF = 0, MCKPP_EXP_F64 = 1, MCKPP_EXP_F32 = 2
   ! kinds of the ancillary record series (MCKPP_ANC_*)
   integer(c_int), parameter :: MCKPP_ANC_SST0 = 0, MCKPP_ANC_FCORR_TWOD = 1, MCKPP_ANC_FCORR_WITHZ = 2, &
     MCKPP_ANC_SFCORR_WITHZ = 3, MCKPP_ANC_OCNT_CLIM = 4, MCKPP_ANC_SAL_CLIM = 5, MCKPP_ANC_BOTTOM_TEMP = 6, MCKPP_ANC_COUNT = 7
@@ -386,6 +388,44 @@ module mckpp_hip_binding
       type(c_ptr), value :: handle
       integer(c_int), value :: sched
       integer(c_int64_t), value :: upto_rec
+      integer(c_int) :: rc
+    end function
+    ! the packed export of a schedule's records, fetched while later launches run (mckpp_hip_window_export of
+    ! include/mckpp_hip.h); `out` is the address of the caller's array of doubles or floats
+    function mckpp_hip_multi_window_export(handle, sched, dtype, land_value) &
+        bind(C, name="mckpp_hip_multi_window_export") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched, dtype
+      real(c_double), value :: land_value
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_window_export_layout(handle, sched, nplanes, field, op, nlev, offset_bytes, record_bytes) &
+        bind(C, name="mckpp_hip_multi_window_export_layout") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched
+      type(c_ptr), value :: nplanes, field, op, nlev, offset_bytes, record_bytes   ! each may be c_null_ptr
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_window_export_fetch(handle, sched, rec, field, op, out) &
+        bind(C, name="mckpp_hip_multi_window_export_fetch") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched
+      integer(c_int64_t), value :: rec
+      integer(c_int), value :: field, op
+      type(c_ptr), value :: out
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_window_export_fetch_record(handle, sched, rec, out, out_bytes) &
+        bind(C, name="mckpp_hip_multi_window_export_fetch_record") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched
+      integer(c_int64_t), value :: rec
+      type(c_ptr), value :: out
+      integer(c_int64_t), value :: out_bytes
       integer(c_int) :: rc
     end function
     function mckpp_hip_multi_save_restart(handle, path) bind(C, name="mckpp_hip_multi_save_restart") result(rc)

@@ -18,6 +18,7 @@ module mckpp_hip_session
   public :: mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select
   public :: mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch
   public :: mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, mckpp_hip_all_window_record_release
+  public :: mckpp_hip_all_window_export, mckpp_hip_all_window_export_fetch, mckpp_hip_all_window_export_fetch_record
   public :: mckpp_hip_all_restart_schedule, mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
             mckpp_hip_all_restart_snapshot_release
   public :: mckpp_hip_all_step_log
@@ -26,6 +27,12 @@ module mckpp_hip_session
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
   public :: mckpp_hip_host_behind
   public :: mckpp_hip_warnings, mckpp_hip_abort_on_zero_pivot, mckpp_hip_report_warnings, mckpp_hip_column_messages
+
+  !> a plane of an exported record into an array of doubles or of floats, as the export was set
+  interface mckpp_hip_all_window_export_fetch
+    module procedure mckpp_hip_all_window_export_fetch_f64, mckpp_hip_all_window_export_fetch_f64_2d, &
+                     mckpp_hip_all_window_export_fetch_f32, mckpp_hip_all_window_export_fetch_f32_2d
+  end interface mckpp_hip_all_window_export_fetch
 
   !> All devices of the run behind one handle (include/mckpp_hip.h, mckpp_hip_multi_*): the columns of
   !! kpp_3d_fields are dealt round-robin over mckpp_hip_ndevices GPUs, HIP devices mckpp_hip_device,
@@ -491,6 +498,53 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle, int(sched, c_int), &
                          int(upto_rec, c_int64_t)), 'mckpp_hip_multi_window_record_release')
   end subroutine mckpp_hip_all_window_record_release
+
+  !> The packed export of schedule `sched` (mckpp_hip_window_export): from now on every mckpp_hip_all_run_forced packs
+  !! the records it completed into export slots in the host's layout, and a fetch of such a record is one copy that
+  !! runs while forced runs queued later do.  dtype MCKPP_EXP_F64, MCKPP_EXP_F32 (narrowed to real(c_float)) or
+  !! MCKPP_EXP_OFF (drops the export); land points of every plane hold land_value.  The time loop: queue run k+1, fetch
+  !! the records of run k, release them.
+  subroutine mckpp_hip_all_window_export(sched, dtype, land_value)
+    integer, intent(in) :: sched, dtype
+    real(c_double), intent(in) :: land_value
+    call mckpp_hip_check(mckpp_hip_multi_window_export(mckpp_hip_multi_handle, int(sched, c_int), int(dtype, c_int), &
+                         land_value), 'mckpp_hip_multi_window_export')
+  end subroutine mckpp_hip_all_window_export
+  !> record `rec` of schedule `sched` through its export: op 0 mean / 1 min / 2 max / 3 last of `field` into
+  !! out(npts) or out(npts,nzp1) of real(c_double) or real(c_float), land points included
+  subroutine mckpp_hip_all_window_export_fetch_f64(sched, rec, field, op, out)
+    integer, intent(in) :: sched, rec, field, op
+    real(c_double), intent(inout), target, contiguous :: out(:)
+    call mckpp_hip_check(mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle, int(sched, c_int), int(rec, c_int64_t), &
+                         int(field, c_int), int(op, c_int), c_loc(out)), 'mckpp_hip_multi_window_export_fetch')
+  end subroutine mckpp_hip_all_window_export_fetch_f64
+  subroutine mckpp_hip_all_window_export_fetch_f64_2d(sched, rec, field, op, out)
+    integer, intent(in) :: sched, rec, field, op
+    real(c_double), intent(inout), target, contiguous :: out(:,:)
+    call mckpp_hip_check(mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle, int(sched, c_int), int(rec, c_int64_t), &
+                         int(field, c_int), int(op, c_int), c_loc(out)), 'mckpp_hip_multi_window_export_fetch')
+  end subroutine mckpp_hip_all_window_export_fetch_f64_2d
+  subroutine mckpp_hip_all_window_export_fetch_f32(sched, rec, field, op, out)
+    integer, intent(in) :: sched, rec, field, op
+    real(c_float), intent(inout), target, contiguous :: out(:)
+    call mckpp_hip_check(mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle, int(sched, c_int), int(rec, c_int64_t), &
+                         int(field, c_int), int(op, c_int), c_loc(out)), 'mckpp_hip_multi_window_export_fetch')
+  end subroutine mckpp_hip_all_window_export_fetch_f32
+  subroutine mckpp_hip_all_window_export_fetch_f32_2d(sched, rec, field, op, out)
+    integer, intent(in) :: sched, rec, field, op
+    real(c_float), intent(inout), target, contiguous :: out(:,:)
+    call mckpp_hip_check(mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle, int(sched, c_int), int(rec, c_int64_t), &
+                         int(field, c_int), int(op, c_int), c_loc(out)), 'mckpp_hip_multi_window_export_fetch')
+  end subroutine mckpp_hip_all_window_export_fetch_f32_2d
+  !> all planes of record `rec` into `out` (out_bytes of it: at least the record_bytes of
+  !! mckpp_hip_multi_window_export_layout, whose offsets locate the planes)
+  subroutine mckpp_hip_all_window_export_fetch_record(sched, rec, out, out_bytes)
+    integer, intent(in) :: sched, rec
+    type(c_ptr), intent(in) :: out
+    integer(c_int64_t), intent(in) :: out_bytes
+    call mckpp_hip_check(mckpp_hip_multi_window_export_fetch_record(mckpp_hip_multi_handle, int(sched, c_int), &
+                         int(rec, c_int64_t), out, out_bytes), 'mckpp_hip_multi_window_export_fetch_record')
+  end subroutine mckpp_hip_all_window_export_fetch_record
 
   !> Restart snapshots taken inside the step launches (mckpp_restart_control, src/mckpp_xios_control.F90:61-83), so that
   !! mckpp_hip_all_run_forced can take many steps in one call: snapshot s (from 0) is the state after step
