@@ -8,6 +8,7 @@
 #include "../../include/mckpp_hip.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
+#include "mckpp_own.h"
 
 #include <algorithm>
 #include <cmath>
@@ -86,36 +87,29 @@ enum { QBLOCK_INTS = 64 };
 // guess_margin): chosen on the headline workload, profiles/r06/README.md
 enum { FIRST_MARGIN_DEFAULT = 12, GUESS_MARGIN_DEFAULT = 0 };
 
-struct mckpp_hip_ctx {
-  int device = 0;
-  hipStream_t stream = nullptr;
-  hipEvent_t ev0 = nullptr, ev1 = nullptr;
-  bool timed = false;
-  int nlaunch = 0;
-  int nkernels = 0;   // kernel launches of the last call (a call of several steps may be one launch)
-  mckpp_const_c c{};
-  int nz = 0, nzp1 = 0, lpl = 1, ld = 64, ldc = 72;
-  double Vtc = 0, cg = 0, dm_nz = 0;
-  std::vector<double> h_swfrac_tab, h_swdk_tab;
-  double *d_zm = nullptr, *d_hm = nullptr, *d_tri0 = nullptr, *d_tri1 = nullptr;
-  double *d_swfrac_tab = nullptr, *d_swdk_tab = nullptr;
-  double2 *d_wtab = nullptr;
-  // state
+// The streams: the first base of the context, so declared before - and destroyed after - everything queued on them.
+struct mckpp_ctx_streams {
+  hip_stream stream;
+  // Row transfers (upload / download): two device staging buffers used in turn and a copy stream, so the PCIe
+  // transfer of one field runs while the layout kernel of the next does; the caller's arrays are pinned
+  // (hipHostRegister, once per array) so those transfers are asynchronous and run at the bus rate.
+  hip_stream copy_stream;
+  hip_stream snap_stream;   // transfers of snapshot_save and of the export's fetches
+};
+
+// Everything sized to the resident columns: free_state drops it as a whole, by one assignment.  A new feature whose
+// buffers live as long as the resident state adds its members here, and nothing to free_state or finalize.
+struct mckpp_ctx_resident {
   int64_t npts = 0, ncol = 0;
-  std::vector<int> ipt;
-  int *d_ipt = nullptr;
-  double *d_prof[P_COUNT] = {};
-  double *d_diag[D_COUNT] = {};
-  bool ext = false;          // any optional-physics switch on: the context carries their input / output fields
-  bool ext_kernel = false;   // ... and needs the kernel build with the N3 code (a T/S climatology for the reset of
-                             // failed columns alone - the shipped namelist - does not: the default build reads it)
-  double *d_ext_in[E_COUNT] = {};
-  double *d_ext_out[O_COUNT] = {};
-  double *d_xs = nullptr, *d_adv_d = nullptr, *d_dm = nullptr, *d_hsum = nullptr;
-  int *d_adv_i = nullptr;
-  // output-window reductions: selected MCKPP_OUT_* fields, three accumulators (sum, min, max) each
-  std::vector<int> wsel{0, 1, 2, 3, 4};
-  std::vector<double *> d_wacc;   // [wsel.size()], each 3 * (ncol*ld | ncol) doubles
+  dev_buf<int> d_ipt;
+  dev_buf<double> d_prof[P_COUNT];
+  dev_buf<double> d_diag[D_COUNT];
+  dev_buf<double> d_ext_in[E_COUNT];
+  dev_buf<double> d_ext_out[O_COUNT];
+  dev_buf<double> d_xs, d_adv_d;
+  dev_buf<int> d_adv_i;
+  // output-window reductions: per selected field (mckpp_hip_ctx::wsel) three accumulators (sum, min, max)
+  std::vector<dev_buf<double>> d_wacc;   // [wsel.size()], each 3 * (ncol*ld | ncol) doubles
   int window_count = 0;
   // output windows the step launches accumulate themselves (mckpp_hip_window_schedule): per schedule its fields, their
   // operation masks and rings of records; the steps run under it; the device table of all schedules' fields
@@ -123,7 +117,7 @@ struct mckpp_hip_ctx {
     std::vector<int> fields;        // empty: no schedule
     std::vector<unsigned> ops;
     std::vector<int> ld_out;
-    std::vector<double *> acc;      // [field]: nrec records of popcount(ops) planes of ncol * ld_out doubles
+    std::vector<dev_buf<double>> acc;   // [field]: nrec records of popcount(ops) planes of ncol * ld_out doubles
     int64_t origin = 1, period = 1;
     int nrec = 1;
     int64_t first_nt = -1, next_nt = -1;   // the first step run under the schedule, the step the next launch must start at (-1: none yet)
@@ -141,95 +135,104 @@ struct mckpp_hip_ctx {
       size_t record_bytes = 0;
       int maxlev = 0;
       std::vector<exp_plane> planes;
-      char *slots = nullptr;
-      mckpp_pack_plane *d_tab = nullptr;
-      std::vector<hipEvent_t> ev;
+      dev_buf<char> slots;
+      dev_buf<mckpp_pack_plane> d_tab;
+      std::vector<hip_event> ev;
     } ex;
   } wsched[MCKPP_WIN_SCHEDULES];
-  mckpp_win *d_win = nullptr;   // [MCKPP_WIN_ENTRIES]
   int nwin = 0;                 // entries of d_win in use (mckpp_kparams_t::nwin of the step launches)
   // restart snapshots the step launches take themselves (mckpp_hip_restart_schedule): a ring of slots, each a restart
   // set (mckpp_kparams_t::snap_*); the steps run under the schedule; per slot the event behind the launches of the
-  // call that completed its snapshot; a transfer stream and two pinned staging blocks for snapshot_save
+  // call that completed its snapshot
   struct snap_sched {
     int64_t origin = 1, period = 0;        // period 0: no schedule
     int nslots = 0;
     int64_t first_nt = -1, next_nt = -1;   // as win_sched's
     int64_t first_exists = 0;              // the snapshots before it were due before first_nt
     int64_t first_kept = 0;                // the snapshots before it are released, or do not exist
-    double *rows = nullptr, *cs = nullptr;
-    int *ci = nullptr;
-    std::vector<hipEvent_t> ev;            // [nslots]
+    dev_buf<double> rows, cs;
+    dev_buf<int> ci;
+    std::vector<hip_event> ev;             // [nslots]
   } rs;
-  // the step log of the step launches (mckpp_hip_step_log): log_cap records and the two control ints - events so far,
-  // OR of their status words (mckpp_kparams_t::log_*); log_cap 0: no log
-  mckpp_log_rec *d_log_rec = nullptr;
-  int *d_log_ctl = nullptr;
-  int64_t log_cap = 0;
-  int log_min_passes = 0;
+  // the step log of the step launches (mckpp_hip_step_log): cap records and the two control ints - events so far,
+  // OR of their status words (mckpp_kparams_t::log_*); cap 0: no log
+  struct log_sched {
+    dev_buf<mckpp_log_rec> rec;
+    dev_buf<int> ctl;
+    int64_t cap = 0;
+    int min_passes = 0;
+  } slog;
   // the resident bottom temperature (mckpp_hip_set_bottomtemp): ncol values in column order, an array of its own (the
-  // staging buffer is rewritten by every transfer); null: none is set (mckpp_kparams_t::bot_temp)
-  double *d_bot_temp = nullptr;
+  // staging buffer is rewritten by every transfer); empty: none is set (mckpp_kparams_t::bot_temp)
+  dev_buf<double> d_bot_temp;
   // ancillary record series and their schedules (mckpp_hip_set_ancillary_series, mckpp_hip_ancillary_schedule), per kind:
   // `nrec` immutable records from number rec0 on, compacted to the resident columns ([ncol], or rows [ncol][ld]); step nt
-  // belongs to epoch (nt - origin) / cadence, which ep[epoch - epoch0] describes (ep empty: no schedule).  d_anc_sel is the
-  // selection table of the latest launch call ([nsteps][kinds], mckpp_kparams_t::anc_sel), written on the stream ahead of
-  // its kernels from one of two pinned host images.
-  struct anc_kind { double *d = nullptr; int rec0 = 0, nrec = 0, origin = 0, cadence = 0, epoch0 = 0; std::vector<mckpp_anc_epoch_c> ep; };
+  // belongs to epoch (nt - origin) / cadence, which ep[epoch - epoch0] describes (ep empty: no schedule).
+  struct anc_kind { dev_buf<double> d; int rec0 = 0, nrec = 0, origin = 0, cadence = 0, epoch0 = 0; std::vector<mckpp_anc_epoch_c> ep; };
   anc_kind anc[MCKPP_ANC_COUNT];
-  mckpp_anc_sel *d_anc_sel = nullptr, *h_anc_sel[2] = {nullptr, nullptr};
-  size_t anc_sel_cap = 0, h_anc_sel_cap[2] = {0, 0};
-  hipEvent_t ev_anc[2] = {nullptr, nullptr};
-  unsigned anc_seq = 0;
+  dev_buf<double> d_cs;
+  dev_buf<int> d_ci;
+  dev_buf<int> d_done;   // [2][ncol] steps of a multi-step launch each column has completed, and has started (mckpp_kparams_t::done)
+  dev_buf<double> d_series;   // [nrec][8][ncol] forcing records (mckpp_hip_set_flux_series)
+  int series_rec0 = 0, series_nrec = 0;
+  dev_buf<double> d_stage;    // grow-only (ensure_stage)
+  dev_buf<double> d_xfer[2];  // the staging buffers of the row transfers, grow-only (ensure_xfer)
+  // pinned host images of the column records and of the forcing staging (grow-only: ensure_host_f)
+  pinned_buf<double> h_cs, h_f;
+  pinned_buf<int> h_ci;
+  // record slots as (npts) slabs in 3-D order, packed on the device (a context that holds every grid point)
+  dev_buf<double> d_pack;       // packed record slabs of a download: device block,
+  pinned_buf<double> h_pack;    // ... pinned host block
+};
+
+struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
+  int device = 0;
+  hip_event ev0, ev1;
+  bool timed = false;
+  int nlaunch = 0;
+  int nkernels = 0;   // kernel launches of the last call (a call of several steps may be one launch)
+  mckpp_const_c c{};
+  int nz = 0, nzp1 = 0, lpl = 1, ld = 64, ldc = 72;
+  double Vtc = 0, cg = 0, dm_nz = 0;
+  std::vector<double> h_swfrac_tab, h_swdk_tab;
+  dev_buf<double> d_zm, d_hm, d_tri0, d_tri1, d_swfrac_tab, d_swdk_tab, d_dm, d_hsum;
+  dev_buf<double2> d_wtab;
+  std::vector<int> ipt;      // the resident columns' grid points (d_ipt)
+  bool ext = false;          // any optional-physics switch on: the context carries their input / output fields
+  bool ext_kernel = false;   // ... and needs the kernel build with the N3 code (a T/S climatology for the reset of
+                             // failed columns alone - the shipped namelist - does not: the default build reads it)
+  std::vector<int> wsel{0, 1, 2, 3, 4};   // selected MCKPP_OUT_* fields of the output-window reductions (d_wacc)
+  dev_buf<mckpp_win> d_win;   // [MCKPP_WIN_ENTRIES]: the device table of all output schedules' fields
+  // the selection table of the latest launch call under ancillary schedules ([nsteps][kinds], mckpp_kparams_t::anc_sel),
+  // grow-only, written on the stream ahead of its kernels from a pinned host image
+  dev_buf<mckpp_anc_sel> d_anc_sel;
+  pinned_turns<mckpp_anc_sel> h_anc_sel;
   int anc_mask = 0, anc_nt0 = 0;   // of the launch call being issued (anc_prepare)
-  hipStream_t snap_stream = nullptr;
-  char *h_snap[2] = {nullptr, nullptr};
-  hipEvent_t ev_snap[2] = {nullptr, nullptr};
-  double *d_cs = nullptr;
-  int *d_ci = nullptr;
-  int *d_qhead = nullptr;  // QBLOCK_INTS ints, zeroed before every launch: [0..15] queue heads, [16..31] queue owners, [32] stragglers on the device
+  pinned_buf<char> h_snap[2];      // two pinned staging blocks for snapshot_save
+  hip_event ev_snap[2];
+  dev_buf<int> d_qhead;  // QBLOCK_INTS ints, zeroed before every launch: [0..15] queue heads, [16..31] queue owners, [32] stragglers on the device
   int view_kmax = 0;   // mckpp_kparams_t::view_kmax (MCKPP_VIEW_KMAX)
   int solo_after = 12, solo_limit = 8;   // mckpp_kparams_t::solo_after / solo_limit (MCKPP_SOLO=0, MCKPP_SOLO_AFTER, MCKPP_SOLO_LIMIT)
-  int *d_done = nullptr;   // [2][ncol] steps of a multi-step launch each column has completed, and has started (mckpp_kparams_t::done)
   bool multistep = true;   // mckpp_hip_step(nt, n > 1) as one launch (MCKPP_MULTISTEP=0: a launch per step)
   int nqueues = 0;         // XCDs of the device, found by a probe at init: the queues of such a launch
   int xcc_queue[16];       // hardware XCC id -> queue (-1: no workgroup of the probe ran there)
   int l3cap = 0;   // MCKPP_L3_CAP (tests): see mckpp_kparams_t::l3cap
   int first_guess = 1, first_margin = FIRST_MARGIN_DEFAULT, guess_margin = GUESS_MARGIN_DEFAULT;   // mckpp_kparams_t::first_margin, scan_rule
   int solver_mode = 0;   // mckpp_hip_set_solver_mode / MCKPP_SOLVER_MODE
-  unsigned long long *d_dbg = nullptr;
-  mckpp_kparams *d_params = nullptr;   // device copy of the kernel parameter block
-  // its source: two pinned host slots used in turn, so a call never waits for its own upload (a slot is reused
-  // only when the copy that read it - two calls back - has completed)
-  mckpp_kparams *h_params = nullptr;
-  hipEvent_t ev_params[2] = {nullptr, nullptr};
-  unsigned params_seq = 0;
-  double *d_scratch = nullptr;         // k_column_ps: scratch rows of the iterate, per (workgroup, slot)
+  dev_buf<unsigned long long> d_dbg;
+  dev_buf<mckpp_kparams> d_params;   // device copy of the kernel parameter block
+  // its source: a pinned host image used in turn, so a call never waits for its own upload
+  pinned_turns<mckpp_kparams> h_params;
+  dev_buf<double> d_scratch;         // k_column_ps: scratch rows of the iterate, per (workgroup, slot)
   size_t scratch_doubles = 0;
   int num_cu = 256;
   int l2pre = 0;   // the reference-level sums of the deepest level span many layers: form the layer terms once per column
-  double *d_series = nullptr;   // [nrec][8][ncol] forcing records (mckpp_hip_set_flux_series)
-  int series_rec0 = 0, series_nrec = 0;
   mckpp_launch_info last_launch{};   // geometry of this context's most recent cooperative launch
-  double *d_stage = nullptr;
-  size_t stage_elems = 0;
-  // Row transfers (upload / download): two device staging buffers used in turn and a copy stream, so the PCIe
-  // transfer of one field runs while the layout kernel of the next does; the caller's arrays are pinned
-  // (hipHostRegister, once per array) so those transfers are asynchronous and run at the bus rate.
-  hipStream_t copy_stream = nullptr;
-  double *d_xfer[2] = {nullptr, nullptr};
-  size_t xfer_elems[2] = {0, 0};
-  hipEvent_t ev_lay[2] = {nullptr, nullptr}, ev_copy[2] = {nullptr, nullptr};   // layout kernel done / transfer done, per buffer
+  hip_event ev_lay[2], ev_copy[2];   // of the row transfers: layout kernel done / transfer done, per staging buffer
   unsigned xfer_seq = 0;
   std::vector<std::pair<const void *, size_t>> pinned;   // caller arrays this context registered
   std::vector<std::pair<const void *, size_t>> unpinnable;   // ... and those it could not (not tried again)
-  // pinned host images of the column records and of the forcing staging
-  double *h_cs = nullptr, *h_f = nullptr;
-  int *h_ci = nullptr;
-  size_t h_f_elems = 0;
-  hipEvent_t ev_f = nullptr;
-  // record slots as (npts) slabs in 3-D order, packed on the device (a context that holds every grid point)
-  double *d_pack = nullptr, *h_pack = nullptr;   // packed record slabs of a download: device block, pinned host block
+  hip_event ev_f;   // the forcing staging has been read
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
   // update_ancillaries); load_restart does not carry them, so stepping is refused until they are there
@@ -352,8 +355,8 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
            c->clim_present || c->L_ADVECT;
   h->ext_kernel = c->LDD || c->L_RELAX_SST || c->L_FCORR || c->L_FCORR_WITHZ || c->L_SFCORR || c->L_SFCORR_WITHZ ||
                   c->L_RELAX_SAL || c->L_RELAX_OCNT || c->L_NO_FREEZE || c->L_NO_ISOTHERM || c->L_DAMP_CURR || c->L_ADVECT;
-  HIPCHK(hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking));
-  HIPCHK(hipMalloc(&h->d_qhead, QBLOCK_INTS * sizeof(int)));   // queue heads [16], queue owners [16], straggler count and spare [32]
+  HIPCHK(h->stream.create());
+  HIPCHK(h->d_qhead.alloc(QBLOCK_INTS));   // queue heads [16], queue owners [16], straggler count and spare [32]
   h->solo_after = 12;
   h->solo_limit = std::max(2, h->num_cu / 32);
   if (const char *e = getenv("MCKPP_SOLO")) { if (atoi(e) == 0) h->solo_limit = 0; }
@@ -362,7 +365,7 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   if (const char *e = getenv("MCKPP_VIEW_KMAX")) h->view_kmax = std::max(0, atoi(e));
   {   // the device's XCDs (a column of a multi-step launch stays on one: mckpp_kernels_ps.hip, M0)
     HIPCHK(hipMemsetAsync(h->d_qhead, 0, sizeof(int), h->stream));
-    HIPCHK(mckpp_launch_xcc_probe(reinterpret_cast<unsigned *>(h->d_qhead), h->stream));
+    HIPCHK(mckpp_launch_xcc_probe(reinterpret_cast<unsigned *>(h->d_qhead.get()), h->stream));
     unsigned mask = 0;
     HIPCHK(hipMemcpyAsync(&mask, h->d_qhead, sizeof mask, hipMemcpyDeviceToHost, h->stream));
     HIPCHK(hipStreamSynchronize(h->stream));
@@ -380,24 +383,23 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
     if (getenv("MCKPP_PS_VERBOSE"))
       fprintf(stderr, "[mckpp] XCC ids seen by the probe: mask 0x%x, %d queues\n", mask, h->nqueues);
   }
-  HIPCHK(hipMalloc(&h->d_params, sizeof(mckpp_kparams)));
+  HIPCHK(h->d_params.alloc(1));
   h->scratch_doubles = mckpp_ps_scratch_doubles(nzp1, h->ext_kernel ? (c->LDD ? 2 : 1) : 0, h->num_cu);
-  HIPCHK(hipMalloc(&h->d_scratch, h->scratch_doubles * sizeof(double)));
+  HIPCHK(h->d_scratch.alloc(h->scratch_doubles));
   HIPCHK(hipMemset(h->d_scratch, 0, h->scratch_doubles * sizeof(double)));
   if (getenv("MCKPP_STAMP")) {
-    HIPCHK(hipMalloc(&h->d_dbg, 40 * sizeof(unsigned long long)));
+    HIPCHK(h->d_dbg.alloc(40));
     HIPCHK(hipMemset(h->d_dbg, 0, 40 * sizeof(unsigned long long)));
   }
-  HIPCHK(hipEventCreate(&h->ev0));
-  HIPCHK(hipEventCreate(&h->ev1));
-  HIPCHK(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
+  HIPCHK(h->ev0.create(hipEventDefault));   // the two that are timed (mckpp_hip_last_kernel_ms)
+  HIPCHK(h->ev1.create(hipEventDefault));
+  HIPCHK(h->copy_stream.create());
   for (int b = 0; b < 2; ++b) {
-    HIPCHK(hipEventCreateWithFlags(&h->ev_lay[b], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_copy[b], hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&h->ev_params[b], hipEventDisableTiming));
+    HIPCHK(h->ev_lay[b].create());
+    HIPCHK(h->ev_copy[b].create());
   }
-  HIPCHK(hipEventCreateWithFlags(&h->ev_f, hipEventDisableTiming));
-  HIPCHK(hipHostMalloc(&h->h_params, 2 * sizeof(mckpp_kparams), hipHostMallocDefault));
+  HIPCHK(h->ev_f.create());
+  HIPCHK(h->h_params.prepare(1));
 
   const int ldc = h->ldc, nz = h->nz, n1 = c->nztmax + 1;
   std::vector<double> zm(ldc, 0.0), hm(ldc, 0.0), t0(ldc, 0.0), t1(ldc, 0.0);
@@ -422,15 +424,18 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
     h->solver_mode = solver_mode_env;
     if (const char *e = getenv("MCKPP_MULTISTEP")) h->multistep = atoi(e) != 0 && h->nqueues > 0;
   }
+  auto up = [&](dev_buf<double> &dst, const double *src, size_t n) -> hipError_t {
+    hipError_t e = dst.alloc(n);
+    if (e != hipSuccess) return e;
+    return hipMemcpy(dst, src, n * sizeof(double), hipMemcpyHostToDevice);
+  };
   {
     std::vector<double> dm(ldc, 0.0), hs(ldc, 0.0);
     for (int k = 0; k <= nz; ++k) dm[k] = c->dm[k];
     double acc = 0.0;
     for (int n = 1; n <= nzp1; ++n) { acc = acc + hm[n]; hs[n] = acc; }
-    HIPCHK(hipMalloc(&h->d_dm, ldc * sizeof(double)));
-    HIPCHK(hipMemcpy(h->d_dm, dm.data(), ldc * sizeof(double), hipMemcpyHostToDevice));
-    HIPCHK(hipMalloc(&h->d_hsum, ldc * sizeof(double)));
-    HIPCHK(hipMemcpy(h->d_hsum, hs.data(), ldc * sizeof(double), hipMemcpyHostToDevice));
+    HIPCHK(up(h->d_dm, dm.data(), ldc));
+    HIPCHK(up(h->d_hsum, hs.data(), ldc));
   }
   // Jerlov tables: swfrac_opt (swfrac_mod.F90:36-41, fact = hbf = 1) and swdk_opt (fluxes_mod.F90:104-107)
   h->h_swfrac_tab.assign((size_t)6 * ldc, 0.0);
@@ -457,18 +462,13 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   std::vector<double2> wtab(nt);
   for (size_t i = 0; i < nt; ++i) wtab[i] = make_double2(c->wmt[i], c->wst[i]);
 
-  auto up = [&](double **dst, const double *src, size_t n) -> hipError_t {
-    hipError_t e = hipMalloc(dst, n * sizeof(double));
-    if (e != hipSuccess) return e;
-    return hipMemcpy(*dst, src, n * sizeof(double), hipMemcpyHostToDevice);
-  };
-  HIPCHK(up(&h->d_zm, zm.data(), ldc));
-  HIPCHK(up(&h->d_hm, hm.data(), ldc));
-  HIPCHK(up(&h->d_tri0, t0.data(), ldc));
-  HIPCHK(up(&h->d_tri1, t1.data(), ldc));
-  HIPCHK(up(&h->d_swfrac_tab, h->h_swfrac_tab.data(), (size_t)6 * ldc));
-  HIPCHK(up(&h->d_swdk_tab, h->h_swdk_tab.data(), (size_t)6 * ldc));
-  HIPCHK(hipMalloc(&h->d_wtab, nt * sizeof(double2)));
+  HIPCHK(up(h->d_zm, zm.data(), ldc));
+  HIPCHK(up(h->d_hm, hm.data(), ldc));
+  HIPCHK(up(h->d_tri0, t0.data(), ldc));
+  HIPCHK(up(h->d_tri1, t1.data(), ldc));
+  HIPCHK(up(h->d_swfrac_tab, h->h_swfrac_tab.data(), (size_t)6 * ldc));
+  HIPCHK(up(h->d_swdk_tab, h->h_swdk_tab.data(), (size_t)6 * ldc));
+  HIPCHK(h->d_wtab.alloc(nt));
   HIPCHK(hipMemcpy(h->d_wtab, wtab.data(), nt * sizeof(double2), hipMemcpyHostToDevice));
   // the host pointers are not kept
   h->c.zm = h->c.hm = h->c.dm = h->c.tri = h->c.wmt = h->c.wst = nullptr;
@@ -477,51 +477,15 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   return 0;
 }
 
-static void win_cancel(mckpp_hip_ctx *h, int s);
 static int win_cancel_all(mckpp_hip_ctx *h);
 static int snap_cancel(mckpp_hip_ctx *h);
 static int log_cancel(mckpp_hip_ctx *h);
 static int bt_cancel(mckpp_hip_ctx *h);
 static int anc_cancel_all(mckpp_hip_ctx *h);
 
-static void free_state(mckpp_hip_ctx *h)
-{
-  for (int s = 0; s < MCKPP_WIN_SCHEDULES; ++s) win_cancel(h, s);   // the records are sized to the resident columns
-  h->nwin = 0;
-  snap_cancel(h);   // ... and so are the snapshot slots
-  log_cancel(h);    // the step log's records name resident columns
-  bt_cancel(h);     // the resident bottom temperature is compacted to them
-  anc_cancel_all(h);   // ... and so are the ancillary records
-  for (auto &p : h->d_prof) { if (p) hipFree(p); p = nullptr; }
-  for (auto &p : h->d_diag) { if (p) hipFree(p); p = nullptr; }
-  for (auto &p : h->d_ext_in) { if (p) hipFree(p); p = nullptr; }
-  for (auto &p : h->d_ext_out) { if (p) hipFree(p); p = nullptr; }
-  if (h->d_xs) hipFree(h->d_xs);
-  if (h->d_adv_d) hipFree(h->d_adv_d);
-  if (h->d_adv_i) hipFree(h->d_adv_i);
-  h->d_xs = nullptr; h->d_adv_d = nullptr; h->d_adv_i = nullptr;
-  if (h->d_series) hipFree(h->d_series);
-  h->d_series = nullptr; h->series_nrec = 0;
-  for (auto *p : h->d_wacc) if (p) hipFree(p);
-  h->d_wacc.clear(); h->window_count = 0;
-  if (h->d_cs) hipFree(h->d_cs);
-  if (h->d_ci) hipFree(h->d_ci);
-  if (h->d_ipt) hipFree(h->d_ipt);
-  if (h->d_stage) hipFree(h->d_stage);
-  h->d_cs = nullptr; h->d_ci = nullptr; h->d_ipt = nullptr; h->d_stage = nullptr;
-  h->stage_elems = 0;
-  for (int b = 0; b < 2; ++b) { if (h->d_xfer[b]) hipFree(h->d_xfer[b]); h->d_xfer[b] = nullptr; h->xfer_elems[b] = 0; }
-  if (h->d_done) hipFree(h->d_done);
-  h->d_done = nullptr;
-  if (h->d_pack) hipFree(h->d_pack);
-  if (h->h_pack) hipHostFree(h->h_pack);
-  h->d_pack = nullptr; h->h_pack = nullptr;
-  if (h->h_cs) hipHostFree(h->h_cs);
-  if (h->h_ci) hipHostFree(h->h_ci);
-  if (h->h_f) hipHostFree(h->h_f);
-  h->h_cs = nullptr; h->h_ci = nullptr; h->h_f = nullptr; h->h_f_elems = 0;
-  h->ncol = 0; h->npts = 0;
-}
+// Everything sized to the resident columns goes.  No wait here: the callers have cancelled the schedules, which waits
+// for the launches that may still use their records.
+static void free_state(mckpp_hip_ctx *h) { static_cast<mckpp_ctx_resident &>(*h) = mckpp_ctx_resident{}; }
 
 // The caller's arrays stay pinned until the context goes (or mckpp_hip_release_host_arrays is called)
 static void unpin_all(mckpp_hip_ctx *h)
@@ -536,33 +500,10 @@ int mckpp_hip_finalize(mckpp_hip_handle h)
 {
   if (!h) return 0;
   hipSetDevice(h->device);
-  if (h->stream) hipStreamSynchronize(h->stream);
+  if (h->stream) hipStreamSynchronize(h->stream);   // nothing in flight may still use what the owners release
   if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
+  if (h->snap_stream) hipStreamSynchronize(h->snap_stream);
   unpin_all(h);
-  free_state(h);
-  for (int b = 0; b < 2; ++b) {
-    if (h->h_snap[b]) hipHostFree(h->h_snap[b]);
-    if (h->ev_snap[b]) hipEventDestroy(h->ev_snap[b]);
-  }
-  if (h->snap_stream) hipStreamDestroy(h->snap_stream);
-  hipFree(h->d_zm); hipFree(h->d_hm); hipFree(h->d_tri0); hipFree(h->d_tri1);
-  hipFree(h->d_swfrac_tab); hipFree(h->d_swdk_tab); hipFree(h->d_wtab); hipFree(h->d_qhead); hipFree(h->d_params); hipFree(h->d_scratch); hipFree(h->d_dm); hipFree(h->d_hsum);
-  if (h->d_win) hipFree(h->d_win);
-  if (h->d_dbg) hipFree(h->d_dbg);
-  if (h->ev0) hipEventDestroy(h->ev0);
-  if (h->ev1) hipEventDestroy(h->ev1);
-  for (int b = 0; b < 2; ++b) {
-    if (h->ev_lay[b]) hipEventDestroy(h->ev_lay[b]);
-    if (h->ev_copy[b]) hipEventDestroy(h->ev_copy[b]);
-    if (h->ev_params[b]) hipEventDestroy(h->ev_params[b]);
-    if (h->ev_anc[b]) hipEventDestroy(h->ev_anc[b]);
-    if (h->h_anc_sel[b]) hipHostFree(h->h_anc_sel[b]);
-  }
-  if (h->d_anc_sel) hipFree(h->d_anc_sel);
-  if (h->ev_f) hipEventDestroy(h->ev_f);
-  if (h->h_params) hipHostFree(h->h_params);
-  if (h->copy_stream) hipStreamDestroy(h->copy_stream);
-  if (h->stream) hipStreamDestroy(h->stream);
   delete h;
   return 0;
 }
@@ -571,15 +512,11 @@ int64_t mckpp_hip_ncolumns(mckpp_hip_handle h) { return h ? h->ncol : -1; }
 
 static int ensure_stage(mckpp_hip_ctx *h, size_t elems)
 {
-  if (elems <= h->stage_elems) return 0;
+  if (elems <= h->d_stage.size()) return 0;
   // a fluxes / unpack / window kernel queued by an earlier call may still be reading the block (those calls do not
   // end with a synchronisation): wait for this context's stream, not - through hipFree - for the whole device
   if (h->d_stage) HIPCHK(hipStreamSynchronize(h->stream));
-  if (h->d_stage) hipFree(h->d_stage);
-  h->d_stage = nullptr;
-  h->stage_elems = 0;
-  HIPCHK(hipMalloc(&h->d_stage, elems * sizeof(double)));
-  h->stage_elems = elems;
+  HIPCHK(h->d_stage.reserve(elems));
   return 0;
 }
 
@@ -610,14 +547,10 @@ static void pin_host(mckpp_hip_ctx *h, const void *ptr, size_t bytes)
 
 static int ensure_xfer(mckpp_hip_ctx *h, unsigned b, size_t elems)
 {
-  if (elems <= h->xfer_elems[b]) return 0;
+  if (elems <= h->d_xfer[b].size()) return 0;
   HIPCHK(hipStreamSynchronize(h->stream));        // nothing in flight may still use the buffer
   HIPCHK(hipStreamSynchronize(h->copy_stream));
-  if (h->d_xfer[b]) hipFree(h->d_xfer[b]);
-  h->d_xfer[b] = nullptr;
-  h->xfer_elems[b] = 0;
-  HIPCHK(hipMalloc(&h->d_xfer[b], elems * sizeof(double)));
-  h->xfer_elems[b] = elems;
+  HIPCHK(h->d_xfer[b].reserve(elems));
   return 0;
 }
 
@@ -677,30 +610,34 @@ static int xfer_finish(mckpp_hip_ctx *h)
 static int alloc_state(mckpp_hip_ctx *h, int64_t npts, int64_t ncol)
 {
   free_state(h);
-  h->npts = npts;
-  h->ncol = ncol;
   h->ext_inputs_resident = false;
-  if (ncol <= 0) return 0;
-  const size_t rowbytes = (size_t)ncol * h->ld * sizeof(double);
-  for (auto &p : h->d_prof) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
-  for (auto &p : h->d_diag) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
-  HIPCHK(hipMalloc(&h->d_cs, (size_t)ncol * MCKPP_CS * sizeof(double)));
-  HIPCHK(hipMalloc(&h->d_ci, (size_t)ncol * MCKPP_CI * sizeof(int)));
-  HIPCHK(hipMalloc(&h->d_ipt, (size_t)ncol * sizeof(int)));
-  HIPCHK(hipHostMalloc(&h->h_cs, (size_t)ncol * MCKPP_CS * sizeof(double), hipHostMallocDefault));
-  HIPCHK(hipHostMalloc(&h->h_ci, (size_t)ncol * MCKPP_CI * sizeof(int), hipHostMallocDefault));
-  if (h->ext) {
-    for (auto &p : h->d_ext_in) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
-    for (auto &p : h->d_ext_out) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
-    const size_t nadv = (size_t)ncol * (h->c.maxmodeadv + 1);
-    HIPCHK(hipMalloc(&h->d_xs, (size_t)ncol * MCKPP_XS * sizeof(double)));
-    HIPCHK(hipMemsetAsync(h->d_xs, 0, (size_t)ncol * MCKPP_XS * sizeof(double), h->stream));
-    HIPCHK(hipMalloc(&h->d_adv_d, nadv * sizeof(double)));
-    HIPCHK(hipMemsetAsync(h->d_adv_d, 0, nadv * sizeof(double), h->stream));
-    HIPCHK(hipMalloc(&h->d_adv_i, nadv * sizeof(int)));
-    HIPCHK(hipMemsetAsync(h->d_adv_i, 0, nadv * sizeof(int), h->stream));
+  mckpp_ctx_resident n;   // built here and moved in whole: a failure leaves the context without a state, not with half of one
+  n.npts = npts;
+  n.ncol = ncol;
+  if (ncol > 0) {
+    auto zeroed = [&](auto &p, size_t elems) -> hipError_t {
+      const hipError_t e = p.alloc(elems);
+      return e != hipSuccess ? e : hipMemsetAsync(p, 0, elems * sizeof(*p.get()), h->stream);
+    };
+    const size_t rowelems = (size_t)ncol * h->ld;
+    for (auto &p : n.d_prof) HIPCHK(zeroed(p, rowelems));
+    for (auto &p : n.d_diag) HIPCHK(zeroed(p, rowelems));
+    HIPCHK(n.d_cs.alloc((size_t)ncol * MCKPP_CS));
+    HIPCHK(n.d_ci.alloc((size_t)ncol * MCKPP_CI));
+    HIPCHK(n.d_ipt.alloc((size_t)ncol));
+    HIPCHK(n.h_cs.alloc((size_t)ncol * MCKPP_CS));
+    HIPCHK(n.h_ci.alloc((size_t)ncol * MCKPP_CI));
+    if (h->ext) {
+      for (auto &p : n.d_ext_in) HIPCHK(zeroed(p, rowelems));
+      for (auto &p : n.d_ext_out) HIPCHK(zeroed(p, rowelems));
+      const size_t nadv = (size_t)ncol * (h->c.maxmodeadv + 1);
+      HIPCHK(zeroed(n.d_xs, (size_t)ncol * MCKPP_XS));
+      HIPCHK(zeroed(n.d_adv_d, nadv));
+      HIPCHK(zeroed(n.d_adv_i, nadv));
+    }
+    HIPCHK(hipStreamSynchronize(h->stream));
   }
-  HIPCHK(hipStreamSynchronize(h->stream));
+  static_cast<mckpp_ctx_resident &>(*h) = std::move(n);
   return 0;
 }
 
@@ -774,8 +711,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
     if (alloc_state(h, npts, ncol)) return -1;
   }
   if (ipt != h->ipt && h->d_series) {   // resident flux records were compacted with the previous land mask
-    hipFree(h->d_series);
-    h->d_series = nullptr;
+    h->d_series.reset();
     h->series_nrec = 0;
   }
   h->ipt = ipt;
@@ -846,13 +782,9 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
 
 static int ensure_host_f(mckpp_hip_ctx *h, size_t elems)
 {
-  if (elems <= h->h_f_elems) return 0;
-  HIPCHK(hipEventSynchronize(h->ev_f));
-  if (h->h_f) hipHostFree(h->h_f);
-  h->h_f = nullptr;
-  h->h_f_elems = 0;
-  HIPCHK(hipHostMalloc(&h->h_f, elems * sizeof(double), hipHostMallocDefault));
-  h->h_f_elems = elems;
+  if (elems <= h->h_f.size()) return 0;
+  HIPCHK(hipEventSynchronize(h->ev_f));   // the copy that last read the block
+  HIPCHK(h->h_f.reserve(elems));
   return 0;
 }
 
@@ -903,8 +835,10 @@ int mckpp_hip_fluxes(mckpp_hip_handle h, int ntime, const double *taux, const do
 static int ensure_correction_rows(mckpp_hip_ctx *h)
 {
   if (h->d_ext_out[O_TINC]) return 0;
-  const size_t rowbytes = (size_t)h->ncol * h->ld * sizeof(double);
-  for (auto &p : h->d_ext_out) { HIPCHK(hipMalloc(&p, rowbytes)); HIPCHK(hipMemsetAsync(p, 0, rowbytes, h->stream)); }
+  const size_t rowelems = (size_t)h->ncol * h->ld;
+  dev_buf<double> rows[O_COUNT];   // all four or none
+  for (auto &p : rows) { HIPCHK(p.alloc(rowelems)); HIPCHK(hipMemsetAsync(p, 0, rowelems * sizeof(double), h->stream)); }
+  for (int o = 0; o < O_COUNT; ++o) h->d_ext_out[o] = std::move(rows[o]);
   return 0;
 }
 
@@ -938,8 +872,7 @@ static int bt_cancel(mckpp_hip_ctx *h)
 {
   if (!h->d_bot_temp) return 0;
   if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the field
-  hipFree(h->d_bot_temp);
-  h->d_bot_temp = nullptr;
+  h->d_bot_temp.reset();
   return 0;
 }
 
@@ -959,11 +892,13 @@ int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
   if (ensure_correction_rows(h)) return -1;
   std::vector<double> bt((size_t)h->ncol);
   for (int64_t c = 0; c < h->ncol; ++c) bt[(size_t)c] = bottom_temp[h->ipt[c]];
-  if (!h->d_bot_temp) HIPCHK(hipMalloc(&h->d_bot_temp, bt.size() * sizeof(double)));
+  dev_buf<double> first;   // a first field is built here and moved in once it is filled
+  if (!h->d_bot_temp) HIPCHK(first.alloc(bt.size()));
   // on the launches' stream, behind those already queued (they keep the field they were launched with); the host
   // image is this call's own, so wait for the copy
-  HIPCHK(hipMemcpyAsync(h->d_bot_temp, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(hipMemcpyAsync(first ? first : h->d_bot_temp, bt.data(), bt.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
+  if (first) h->d_bot_temp = std::move(first);
   return 0;
 }
 
@@ -982,8 +917,7 @@ static int anc_free_records(mckpp_hip_ctx *h, int kind)
   auto &a = h->anc[kind];
   if (a.d) {
     if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the records
-    hipFree(a.d);
-    a.d = nullptr;
+    a.d.reset();
   }
   a.nrec = 0; a.rec0 = 0;
   return 0;
@@ -1020,24 +954,26 @@ int mckpp_hip_set_ancillary_series(mckpp_hip_handle h, int kind, int rec0, int n
   if (anc_free_records(h, kind)) return -1;
   if (nrec == 0) return 0;
   auto &a = h->anc[kind];
+  dev_buf<double> d;   // built here, moved in once every record is there
   if (h->ncol > 0) {
     const size_t stride = anc_stride(h, kind), n = stride * (size_t)nrec;
-    HIPCHK(hipMalloc(&a.d, n * sizeof(double)));
+    HIPCHK(d.alloc(n));
     if (anc_is_3d(kind)) {   // rows, by the path of upload / update_ancillaries
       const size_t slab = (size_t)h->npts * h->nzp1;
-      HIPCHK(hipMemsetAsync(a.d, 0, n * sizeof(double), h->stream));
+      HIPCHK(hipMemsetAsync(d, 0, n * sizeof(double), h->stream));
       for (int r = 0; r < nrec; ++r)
-        if (up_rows(h, records + (size_t)r * slab, h->nzp1, a.d + (size_t)r * stride, 0, records, slab * (size_t)nrec)) return -1;
+        if (up_rows(h, records + (size_t)r * slab, h->nzp1, d + (size_t)r * stride, 0, records, slab * (size_t)nrec)) return -1;
       if (xfer_finish(h)) return -1;   // the caller's array is its own again
     } else {
       std::vector<double> f(n);
       for (int r = 0; r < nrec; ++r)
         for (int64_t c = 0; c < h->ncol; ++c) f[(size_t)r * stride + (size_t)c] = records[(size_t)r * (size_t)h->npts + h->ipt[c]];
       // on the launches' stream, behind those already queued; the host image is this call's own, so wait for the copy
-      HIPCHK(hipMemcpyAsync(a.d, f.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(hipMemcpyAsync(d, f.data(), n * sizeof(double), hipMemcpyHostToDevice, h->stream));
       HIPCHK(hipStreamSynchronize(h->stream));
     }
   }
+  a.d = std::move(d);
   a.rec0 = rec0;
   a.nrec = nrec;
   return 0;
@@ -1116,23 +1052,15 @@ static int anc_prepare(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who)
   }
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  if (n > h->anc_sel_cap) {
-    if (h->d_anc_sel) { HIPCHK(hipStreamSynchronize(h->stream)); hipFree(h->d_anc_sel); h->d_anc_sel = nullptr; h->anc_sel_cap = 0; }
-    HIPCHK(hipMalloc(&h->d_anc_sel, n * sizeof(mckpp_anc_sel)));
-    h->anc_sel_cap = n;
+  if (n > h->d_anc_sel.size()) {
+    if (h->d_anc_sel) HIPCHK(hipStreamSynchronize(h->stream));   // a launch in flight may still read the table
+    HIPCHK(h->d_anc_sel.reserve(n));
   }
-  const unsigned slot = h->anc_seq++ & 1u;
-  if (!h->ev_anc[slot]) HIPCHK(hipEventCreateWithFlags(&h->ev_anc[slot], hipEventDisableTiming));
-  HIPCHK(hipEventSynchronize(h->ev_anc[slot]));   // the copy that last read this host image
-  if (n > h->h_anc_sel_cap[slot]) {
-    if (h->h_anc_sel[slot]) hipHostFree(h->h_anc_sel[slot]);
-    h->h_anc_sel[slot] = nullptr; h->h_anc_sel_cap[slot] = 0;
-    HIPCHK(hipHostMalloc(&h->h_anc_sel[slot], n * sizeof(mckpp_anc_sel), hipHostMallocDefault));
-    h->h_anc_sel_cap[slot] = n;
-  }
-  memcpy(h->h_anc_sel[slot], sel.data(), n * sizeof(mckpp_anc_sel));
-  HIPCHK(hipMemcpyAsync(h->d_anc_sel, h->h_anc_sel[slot], n * sizeof(mckpp_anc_sel), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(hipEventRecord(h->ev_anc[slot], h->stream));
+  mckpp_anc_sel *img = nullptr;
+  HIPCHK(h->h_anc_sel.take(n, &img));   // (waits for the copy that last read this host image)
+  memcpy(img, sel.data(), n * sizeof(mckpp_anc_sel));
+  HIPCHK(hipMemcpyAsync(h->d_anc_sel, img, n * sizeof(mckpp_anc_sel), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h->h_anc_sel.queued(h->stream));
   h->anc_mask = mask;
   return 0;
 }
@@ -1200,7 +1128,7 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
   p.hmixtolfrac = h->c.hmixtolfrac; p.dto = h->c.dto; p.grav = h->c.grav; p.vonk = h->c.vonk; p.sice = h->c.sice;
   p.Vtc = h->Vtc; p.cg = h->cg; p.dm_nz = h->dm_nz;
   p.zm = h->d_zm; p.hm = h->d_hm; p.tri0 = h->d_tri0; p.tri1 = h->d_tri1;
-  p.swfrac_tab = h->d_swfrac_tab; p.swdk_tab = h->d_swdk_tab; p.ldc = h->ldc; p.wtab = reinterpret_cast<const double *>(h->d_wtab);
+  p.swfrac_tab = h->d_swfrac_tab; p.swdk_tab = h->d_swdk_tab; p.ldc = h->ldc; p.wtab = reinterpret_cast<const double *>(h->d_wtab.get());
   p.U = h->d_prof[P_U]; p.V = h->d_prof[P_V]; p.T = h->d_prof[P_T]; p.S = h->d_prof[P_S];
   p.Us[0] = h->d_prof[P_US0]; p.Us[1] = h->d_prof[P_US1]; p.Vs[0] = h->d_prof[P_VS0]; p.Vs[1] = h->d_prof[P_VS1];
   p.Ts[0] = h->d_prof[P_TS0]; p.Ts[1] = h->d_prof[P_TS1]; p.Ss[0] = h->d_prof[P_SS0]; p.Ss[1] = h->d_prof[P_SS1];
@@ -1233,9 +1161,9 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
     p.snap_plane = (long long)h->ncol * h->ld; p.snap_slot = MCKPP_SNAP_ROWS * p.snap_plane;
     p.snap_origin = (int)h->rs.origin; p.snap_period = (int)h->rs.period; p.snap_nslots = h->rs.nslots;
   }
-  if (mode == MCKPP_MODE_STEP && h->log_cap > 0) {   // (... and never log)
-    p.log_rec = h->d_log_rec; p.log_ctl = h->d_log_ctl;
-    p.log_cap = (int)h->log_cap; p.log_min_passes = h->log_min_passes;
+  if (mode == MCKPP_MODE_STEP && h->slog.cap > 0) {   // (... and never log)
+    p.log_rec = h->slog.rec; p.log_ctl = h->slog.ctl;
+    p.log_cap = (int)h->slog.cap; p.log_min_passes = h->slog.min_passes;
   }
   if (mode == MCKPP_MODE_STEP) p.bot_temp = h->d_bot_temp;   // (init / vmix / pass never apply the override)
   if (mode == MCKPP_MODE_STEP && h->anc_mask) {   // (... and never read a series; anc_prepare of this launch call)
@@ -1295,11 +1223,11 @@ static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const f
                 "(after mckpp_hip_load_restart call mckpp_hip_update_ancillaries before stepping)");
   HIPCHK(hipSetDevice(h->device));
   {   // parameter block (identical for every launch of this call but ntime), from a pinned slot: no host wait
-    const unsigned slot = h->params_seq++ & 1u;
-    HIPCHK(hipEventSynchronize(h->ev_params[slot]));
-    fill_params(h, h->h_params[slot], ntime, mode);
-    HIPCHK(hipMemcpyAsync(h->d_params, &h->h_params[slot], sizeof(mckpp_kparams), hipMemcpyHostToDevice, h->stream));
-    HIPCHK(hipEventRecord(h->ev_params[slot], h->stream));
+    mckpp_kparams *q = nullptr;
+    HIPCHK(h->h_params.take(1, &q));
+    fill_params(h, *q, ntime, mode);
+    HIPCHK(hipMemcpyAsync(h->d_params, q, sizeof(mckpp_kparams), hipMemcpyHostToDevice, h->stream));
+    HIPCHK(h->h_params.queued(h->stream));
   }
   HIPCHK(hipEventRecord(h->ev0, h->stream));
   // Several steps of constant forcing (mckpp_hip_step with nsteps > 1): ONE launch takes every column through all of
@@ -1309,24 +1237,24 @@ static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const f
   // column's next step overwrites them - fill_params, diag_every).  The forced run too: a step
   // that is a flux update assembles its column's forcing from the resident record itself.  Not for a step at ntime = 0.
   if (mode == MCKPP_MODE_STEP && nsteps > 1 && ntime >= 1 && h->multistep) {
-    if (!h->d_done) HIPCHK(hipMalloc(&h->d_done, 2 * (size_t)h->ncol * sizeof(int)));   // done[ncol], then the steps started (k_column_ps, M0)
+    if (!h->d_done) HIPCHK(h->d_done.alloc(2 * (size_t)h->ncol));   // done[ncol], then the steps started (k_column_ps, M0)
     const int per_launch = (int)std::max<int64_t>(1, ((int64_t)1 << 30) / h->ncol);   // tickets are 32-bit (per queue: fewer still)
     for (int i = 0; i < nsteps; i += per_launch) {
       const int n = nsteps - i < per_launch ? nsteps - i : per_launch;
-      const unsigned slot = h->params_seq++ & 1u;   // this launch's parameter block (its step count differs from the call's first)
-      HIPCHK(hipEventSynchronize(h->ev_params[slot]));
-      fill_params(h, h->h_params[slot], ntime + i, mode);
-      h->h_params[slot].nsteps_launch = n;
+      mckpp_kparams *qp = nullptr;   // this launch's parameter block (its step count differs from the call's first)
+      HIPCHK(h->h_params.take(1, &qp));
+      mckpp_kparams &q = *qp;
+      fill_params(h, q, ntime + i, mode);
+      q.nsteps_launch = n;
       if (forced) {   // the forced run: every step finds its flux record itself (k_column_ps, M0)
-        mckpp_kparams &q = h->h_params[slot];
         q.series = h->d_series; q.series_rec0 = h->series_rec0; q.ndtocn = forced->ndtocn; q.l_rest = forced->l_rest;
         q.flsn = forced->flsn; q.el = forced->el;
       }
-      HIPCHK(hipMemcpyAsync(h->d_params, &h->h_params[slot], sizeof(mckpp_kparams), hipMemcpyHostToDevice, h->stream));
-      HIPCHK(hipEventRecord(h->ev_params[slot], h->stream));
+      HIPCHK(hipMemcpyAsync(h->d_params, qp, sizeof(mckpp_kparams), hipMemcpyHostToDevice, h->stream));
+      HIPCHK(h->h_params.queued(h->stream));
       HIPCHK(hipMemsetAsync(h->d_qhead, 0, QBLOCK_INTS * sizeof(int), h->stream));
       HIPCHK(hipMemsetAsync(h->d_done, 0, 2 * (size_t)h->ncol * sizeof(int), h->stream));
-      HIPCHK(mckpp_launch_column_kernel_ps(h->h_params[slot], h->d_params, h->num_cu, h->stream, &h->last_launch));
+      HIPCHK(mckpp_launch_column_kernel_ps(q, h->d_params, h->num_cu, h->stream, &h->last_launch));
     }
     HIPCHK(hipEventRecord(h->ev1, h->stream));
     h->nlaunch = nsteps;   // (mckpp_hip_last_kernel_ms: time per STEP, whatever the number of launches)
@@ -1367,7 +1295,7 @@ int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const doub
   if (nrec < 1 || rec0 < 0) return fail("mckpp_hip_set_flux_series: rec0=%d nrec=%d", rec0, nrec);
   if (h->npts <= 0) return fail("mckpp_hip_set_flux_series: upload the state first (the records are compacted to the resident columns)");
   HIPCHK(hipSetDevice(h->device));
-  if (h->d_series) { HIPCHK(hipFree(h->d_series)); h->d_series = nullptr; h->series_nrec = 0; }
+  h->d_series.reset();
   h->series_rec0 = rec0;
   h->series_nrec = nrec;
   if (h->ncol == 0) return 0;
@@ -1379,7 +1307,7 @@ int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const doub
       double *dst = f.data() + ((size_t)r * 8 + m) * (size_t)h->ncol;
       for (int64_t c = 0; c < h->ncol; ++c) dst[c] = src[h->ipt[c]];
     }
-  HIPCHK(hipMalloc(&h->d_series, n * sizeof(double)));
+  HIPCHK(h->d_series.alloc(n));
   HIPCHK(hipMemcpy(h->d_series, f.data(), n * sizeof(double), hipMemcpyHostToDevice));
   return 0;
 }
@@ -1581,8 +1509,8 @@ static int download_records(mckpp_hip_ctx *h, mckpp_state_ptrs_c *s, uint32_t ma
     // threads.  (A transfer per array costs a round trip each: 1.8 ms of a 4.7 ms drop-in step on a link that has
     // been idle, r03.)
     const size_t pack_bytes = (size_t)npts * (MCKPP_CS * sizeof(double) + MCKPP_CI * sizeof(int));
-    if (!h->d_pack) HIPCHK(hipMalloc(&h->d_pack, pack_bytes));
-    if (!h->h_pack) HIPCHK(hipHostMalloc(&h->h_pack, pack_bytes, hipHostMallocDefault));
+    if (!h->d_pack) HIPCHK(h->d_pack.alloc((pack_bytes + 7) / sizeof(double)));
+    if (!h->h_pack) HIPCHK(h->h_pack.alloc((pack_bytes + 7) / sizeof(double)));
     int *d_ipack = reinterpret_cast<int *>(h->d_pack + (size_t)npts * l.nd);
     HIPCHK(mckpp_launch_pack_records(h->d_cs, h->d_ci, h->d_ipt, ncol, npts, l, h->d_pack, d_ipack, h->stream));
     const size_t used = (size_t)npts * (l.nd * sizeof(double) + l.ni * sizeof(int));
@@ -1752,10 +1680,6 @@ static int snap_cancel(mckpp_hip_ctx *h)
   if (r.period == 0) return 0;
   if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still write the slots
   if (h->snap_stream) HIPCHK(hipStreamSynchronize(h->snap_stream));
-  if (r.rows) hipFree(r.rows);
-  if (r.cs) hipFree(r.cs);
-  if (r.ci) hipFree(r.ci);
-  for (auto e : r.ev) if (e) hipEventDestroy(e);
   r = mckpp_hip_ctx::snap_sched{};
   return 0;
 }
@@ -1806,28 +1730,24 @@ int mckpp_hip_restart_schedule(mckpp_hip_handle h, int nt_origin, int period, in
   HIPCHK(hipSetDevice(h->device));
   if (snap_cancel(h)) return -1;
   if (period == 0) return 0;
-  auto &r = h->rs;
+  mckpp_hip_ctx::snap_sched r;   // built here, moved in when all of it is there
   if (h->ncol > 0) {
-    if (!h->snap_stream) HIPCHK(hipStreamCreateWithFlags(&h->snap_stream, hipStreamNonBlocking));
-    const size_t plane = (size_t)h->ncol * h->ld * sizeof(double);
-    const size_t nb[3] = {(size_t)nslots * MCKPP_SNAP_ROWS * plane, (size_t)nslots * h->ncol * MCKPP_CS * sizeof(double),
-                          (size_t)nslots * h->ncol * MCKPP_CI * sizeof(int)};
-    void *blk[3] = {nullptr, nullptr, nullptr};
-    r.ev.assign((size_t)nslots, nullptr);
-    hipError_t e = hipSuccess;
-    for (int i = 0; i < 3 && e == hipSuccess; ++i) e = hipMalloc(&blk[i], nb[i]);
-    for (int i = 0; i < nslots && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&r.ev[(size_t)i], hipEventDisableTiming);
+    if (!h->snap_stream) HIPCHK(h->snap_stream.create());
+    const size_t plane = (size_t)h->ncol * h->ld;
+    const size_t ne[3] = {(size_t)nslots * MCKPP_SNAP_ROWS * plane, (size_t)nslots * h->ncol * MCKPP_CS, (size_t)nslots * h->ncol * MCKPP_CI};
+    r.ev.resize((size_t)nslots);
+    hipError_t e = r.rows.alloc(ne[0]);
+    if (e == hipSuccess) e = r.cs.alloc(ne[1]);
+    if (e == hipSuccess) e = r.ci.alloc(ne[2]);
+    for (int i = 0; i < nslots && e == hipSuccess; ++i) e = r.ev[(size_t)i].create();
     if (e != hipSuccess) {
       (void)hipGetLastError();
-      for (void *b : blk) if (b) hipFree(b);
-      for (auto ev : r.ev) if (ev) hipEventDestroy(ev);
-      r = mckpp_hip_ctx::snap_sched{};
       return fail("%s: cannot allocate %zu bytes of device memory for the %d snapshot slots (%s); the schedule is not set",
-                  who, nb[0] + nb[1] + nb[2], nslots, hipGetErrorString(e));
+                  who, (ne[0] + ne[1]) * sizeof(double) + ne[2] * sizeof(int), nslots, hipGetErrorString(e));
     }
-    r.rows = static_cast<double *>(blk[0]); r.cs = static_cast<double *>(blk[1]); r.ci = static_cast<int *>(blk[2]);
   }
   r.origin = nt_origin; r.period = period; r.nslots = nslots;
+  h->rs = std::move(r);
   return 0;
 }
 
@@ -1879,8 +1799,8 @@ int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char
   HIPCHK(hipSetDevice(h->device));
   const size_t chunk = (size_t)32 << 20;
   for (int b = 0; b < 2; ++b) {
-    if (!h->h_snap[b]) HIPCHK(hipHostMalloc(&h->h_snap[b], chunk, hipHostMallocDefault));
-    if (!h->ev_snap[b]) HIPCHK(hipEventCreateWithFlags(&h->ev_snap[b], hipEventDisableTiming));
+    if (!h->h_snap[b]) HIPCHK(h->h_snap[b].alloc(chunk));
+    if (!h->ev_snap[b]) HIPCHK(h->ev_snap[b].create());
   }
   // the file's payload as device segments: the snapshot's planes, with U_init / V_init - never written by a step -
   // from the live rows
@@ -1890,8 +1810,8 @@ int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char
   const double *planes = r.rows + slot * MCKPP_SNAP_ROWS * (size_t)h->ncol * h->ld;
   auto plane = [&](int i) { return reinterpret_cast<const char *>(planes + (size_t)i * h->ncol * h->ld); };
   for (int i = 0; i < P_UINIT; ++i) segs.push_back({plane(i), rowbytes});
-  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_UINIT]), rowbytes});
-  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_VINIT]), rowbytes});
+  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_UINIT].get()), rowbytes});
+  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_VINIT].get()), rowbytes});
   segs.push_back({plane(P_UINIT), rowbytes});       // cp
   segs.push_back({plane(P_UINIT + 1), rowbytes});   // rho
   segs.push_back({reinterpret_cast<const char *>(r.cs + slot * (size_t)h->ncol * MCKPP_CS), (size_t)h->ncol * MCKPP_CS * sizeof(double)});
@@ -1931,12 +1851,9 @@ int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char
 // ---------------------------------------------------------------------------
 static int log_cancel(mckpp_hip_ctx *h)
 {
-  if (h->log_cap == 0) return 0;
+  if (h->slog.cap == 0) return 0;
   if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still write the records
-  if (h->d_log_rec) hipFree(h->d_log_rec);
-  if (h->d_log_ctl) hipFree(h->d_log_ctl);
-  h->d_log_rec = nullptr; h->d_log_ctl = nullptr;
-  h->log_cap = 0; h->log_min_passes = 0;
+  h->slog = mckpp_hip_ctx::log_sched{};
   return 0;
 }
 
@@ -1952,19 +1869,17 @@ int mckpp_hip_step_log(mckpp_hip_handle h, int64_t capacity, int min_passes)
   HIPCHK(hipSetDevice(h->device));
   if (log_cancel(h)) return -1;
   if (capacity == 0) return 0;
-  void *rec = nullptr, *ctl = nullptr;
-  hipError_t e = hipMalloc(&rec, (size_t)capacity * sizeof(mckpp_log_rec));
-  if (e == hipSuccess) e = hipMalloc(&ctl, 2 * sizeof(int));
-  if (e == hipSuccess) e = hipMemsetAsync(ctl, 0, 2 * sizeof(int), h->stream);
+  mckpp_hip_ctx::log_sched l;   // built here, moved in when all of it is there
+  hipError_t e = l.rec.alloc((size_t)capacity);
+  if (e == hipSuccess) e = l.ctl.alloc(2);
+  if (e == hipSuccess) e = hipMemsetAsync(l.ctl, 0, 2 * sizeof(int), h->stream);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    if (rec) hipFree(rec);
-    if (ctl) hipFree(ctl);
     return fail("%s: cannot allocate %zu bytes of device memory for %lld records (%s); no log is set", who,
                 (size_t)capacity * sizeof(mckpp_log_rec), (long long)capacity, hipGetErrorString(e));
   }
-  h->d_log_rec = static_cast<mckpp_log_rec *>(rec); h->d_log_ctl = static_cast<int *>(ctl);
-  h->log_cap = capacity; h->log_min_passes = min_passes;
+  l.cap = capacity; l.min_passes = min_passes;
+  h->slog = std::move(l);
   return 0;
 }
 
@@ -1974,10 +1889,10 @@ static int log_read_ctl(mckpp_hip_ctx *h, int64_t *n_events, int64_t *n_stored, 
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   int ctl[2] = {0, 0};
-  HIPCHK(hipMemcpy(ctl, h->d_log_ctl, sizeof ctl, hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(ctl, h->slog.ctl, sizeof ctl, hipMemcpyDeviceToHost));
   const int64_t n = (int64_t)(uint32_t)ctl[0];
   if (n_events) *n_events = n;
-  if (n_stored) *n_stored = std::min(n, h->log_cap);
+  if (n_stored) *n_stored = std::min(n, h->slog.cap);
   if (status_or) *status_or = ctl[1];
   return 0;
 }
@@ -1986,7 +1901,7 @@ int mckpp_hip_step_log_count(mckpp_hip_handle h, int64_t *n_events, int64_t *n_s
 {
   const char *who = "mckpp_hip_step_log_count";
   if (!h) return fail("%s: null handle", who);
-  if (h->log_cap == 0) return fail("%s: no step log is set", who);
+  if (h->slog.cap == 0) return fail("%s: no step log is set", who);
   return log_read_ctl(h, n_events, n_stored, status_or);
 }
 
@@ -2003,7 +1918,7 @@ int log_fetch_raw(mckpp_hip_ctx *h, const char *who, int64_t n, std::vector<log_
   out.resize((size_t)n);
   if (n == 0) return 0;
   static_assert(sizeof(log_event) == sizeof(mckpp_log_rec), "a record is four ints");
-  HIPCHK(hipMemcpy(out.data(), h->d_log_rec, (size_t)n * sizeof(log_event), hipMemcpyDeviceToHost));
+  HIPCHK(hipMemcpy(out.data(), h->slog.rec, (size_t)n * sizeof(log_event), hipMemcpyDeviceToHost));
   for (auto &e : out) {
     if (e.point < 0 || e.point >= h->ncol) return fail("%s: a record names column %d of %lld", who, e.point, (long long)h->ncol);
     e.point = h->ipt[(size_t)e.point];
@@ -2028,7 +1943,7 @@ int mckpp_hip_step_log_fetch(mckpp_hip_handle h, int64_t n, int32_t *nt, int32_t
 {
   const char *who = "mckpp_hip_step_log_fetch";
   if (!h) return fail("%s: null handle", who);
-  if (h->log_cap == 0) return fail("%s: no step log is set", who);
+  if (h->slog.cap == 0) return fail("%s: no step log is set", who);
   try {
     std::vector<log_event> ev;
     if (log_fetch_raw(h, who, n, ev)) return -1;
@@ -2042,9 +1957,9 @@ int mckpp_hip_step_log_clear(mckpp_hip_handle h)
 {
   const char *who = "mckpp_hip_step_log_clear";
   if (!h) return fail("%s: null handle", who);
-  if (h->log_cap == 0) return fail("%s: no step log is set", who);
+  if (h->slog.cap == 0) return fail("%s: no step log is set", who);
   HIPCHK(hipSetDevice(h->device));
-  HIPCHK(hipMemsetAsync(h->d_log_ctl, 0, 2 * sizeof(int), h->stream));   // (behind the launches already queued)
+  HIPCHK(hipMemsetAsync(h->slog.ctl, 0, 2 * sizeof(int), h->stream));   // (behind the launches already queued)
   return 0;
 }
 
@@ -2089,8 +2004,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
   } else if (ipt != h->ipt) {
     if (h->d_series) {   // resident flux records were compacted with the previous land mask
-      hipFree(h->d_series);
-      h->d_series = nullptr;
+      h->d_series.reset();
       h->series_nrec = 0;
     }
     h->ext_inputs_resident = false;   // and so were the optional-physics inputs
@@ -2188,7 +2102,6 @@ int mckpp_hip_window_select(mckpp_hip_handle h, const int32_t *fields, int32_t n
     if (fields[i] < 0 || fields[i] >= MCKPP_OUT_COUNT) return fail("mckpp_hip_window_select: unknown output field %d", fields[i]);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  for (auto *p : h->d_wacc) if (p) hipFree(p);
   h->d_wacc.clear();
   h->wsel.assign(fields, fields + nfields);
   h->window_count = 0;
@@ -2207,7 +2120,7 @@ int mckpp_hip_window_accumulate(mckpp_hip_handle h)
   if (!h) return fail("null handle");
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  if (h->d_wacc.size() != h->wsel.size()) h->d_wacc.assign(h->wsel.size(), nullptr);
+  if (h->d_wacc.size() != h->wsel.size()) h->d_wacc = std::vector<dev_buf<double>>(h->wsel.size());
   for (size_t i = 0; i < h->wsel.size(); ++i) {
     out_desc d;
     if (out_field(h, h->wsel[i], d)) return -1;
@@ -2215,7 +2128,7 @@ int mckpp_hip_window_accumulate(mckpp_hip_handle h)
       return fail("mckpp_hip_window_accumulate: field %d is a diagnostic, and diagnostics are switched off", h->wsel[i]);
     const int ld_out = d.nlev == 1 ? 1 : h->ld;
     const size_t n = (size_t)h->ncol * ld_out;
-    if (!h->d_wacc[i]) HIPCHK(hipMalloc(&h->d_wacc[i], 3 * n * sizeof(double)));
+    if (!h->d_wacc[i]) HIPCHK(h->d_wacc[i].alloc(3 * n));
     HIPCHK(mckpp_launch_out_sample(d.src, d.ld, d.off, h->d_cs, d.add_sref, h->ncol, d.nlev, ld_out, h->d_wacc[i],
                                    h->d_wacc[i] + n, h->d_wacc[i] + 2 * n, h->window_count == 0, nullptr, h->stream));
   }
@@ -2279,21 +2192,10 @@ int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
 
 // the schedule's export goes (nothing of it is in flight: its fetches end with a wait for the transfer stream, and the
 // callers have waited for the context's)
-static void exp_drop(mckpp_hip_ctx::win_sched &w)
-{
-  auto &x = w.ex;
-  if (x.slots) hipFree(x.slots);
-  if (x.d_tab) hipFree(x.d_tab);
-  for (auto e : x.ev) if (e) hipEventDestroy(e);
-  x = mckpp_hip_ctx::win_sched::win_export{};
-}
+static void exp_drop(mckpp_hip_ctx::win_sched &w) { w.ex = mckpp_hip_ctx::win_sched::win_export{}; }
 
-static void win_cancel(mckpp_hip_ctx *h, int s)
-{
-  exp_drop(h->wsched[s]);
-  for (auto *p : h->wsched[s].acc) if (p) hipFree(p);
-  h->wsched[s] = mckpp_hip_ctx::win_sched{};
-}
+// ... and so does the schedule, its export with it (the callers have waited for the context's stream)
+static void win_cancel(mckpp_hip_ctx *h, int s) { h->wsched[s] = mckpp_hip_ctx::win_sched{}; }
 
 static int win_cancel_all(mckpp_hip_ctx *h)
 {
@@ -2323,7 +2225,7 @@ static int win_table(mckpp_hip_ctx *h)
     }
   h->nwin = 0;
   if (t.empty() || h->ncol == 0) return 0;
-  if (!h->d_win) HIPCHK(hipMalloc(&h->d_win, MCKPP_WIN_ENTRIES * sizeof(mckpp_win)));
+  if (!h->d_win) HIPCHK(h->d_win.alloc(MCKPP_WIN_ENTRIES));
   HIPCHK(hipMemcpy(h->d_win, t.data(), t.size() * sizeof(mckpp_win), hipMemcpyHostToDevice));
   h->nwin = (int)t.size();
   return 0;
@@ -2406,27 +2308,27 @@ int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int 
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the table or write the records
   win_cancel(h, sched);
-  auto &w = h->wsched[sched];
   if (nfields > 0) {
+    mckpp_hip_ctx::win_sched w;   // built here, moved in when every ring is there
     w.origin = nt_origin; w.period = period; w.nrec = nrec;
     for (int i = 0; i < nfields; ++i) {
       out_desc d;
       out_field(h, fields[i], d);
       const int ld_out = d.nlev == 1 ? 1 : h->ld;
-      const size_t bytes = (size_t)nrec * (size_t)__builtin_popcount(ops[i]) * (size_t)h->ncol * (size_t)ld_out * sizeof(double);
-      double *p = nullptr;
+      const size_t elems = (size_t)nrec * (size_t)__builtin_popcount(ops[i]) * (size_t)h->ncol * (size_t)ld_out, bytes = elems * sizeof(double);
+      dev_buf<double> p;
       if (bytes > 0) {
-        const hipError_t e = hipMalloc(&p, bytes);
+        const hipError_t e = p.alloc(elems);
         if (e != hipSuccess) {
           (void)hipGetLastError();
-          win_cancel(h, sched);
-          win_table(h);
+          win_table(h);   // (of the other schedules)
           return fail("%s: cannot allocate %zu bytes of device memory for the %d records of field %d (%s); the schedule is "
                       "not set", who, bytes, nrec, fields[i], hipGetErrorString(e));
         }
       }
-      w.fields.push_back(fields[i]); w.ops.push_back(ops[i]); w.ld_out.push_back(ld_out); w.acc.push_back(p);
+      w.fields.push_back(fields[i]); w.ops.push_back(ops[i]); w.ld_out.push_back(ld_out); w.acc.push_back(std::move(p));
     }
+    h->wsched[sched] = std::move(w);
   }
   return win_table(h);
 }
@@ -2596,7 +2498,7 @@ static int exp_start(mckpp_hip_ctx *h, win_sched_t &w, size_t total)
   const auto &x = w.ex;
   if (!x.compact && total > 0)
     HIPCHK(mckpp_launch_export_fill(x.slots, total / exp_elem(x.dtype), x.land, x.dtype == MCKPP_EXP_F32, h->stream));
-  for (auto ev : x.ev) HIPCHK(hipEventRecord(ev, h->stream));
+  for (auto &ev : x.ev) HIPCHK(hipEventRecord(ev, h->stream));
   if (w.first_nt >= 0)
     for (int64_t rec = w.first_kept; rec <= win_last_complete(w); ++rec)
       if (exp_pack(h, w, rec)) return -1;
@@ -2631,22 +2533,19 @@ static int exp_set(mckpp_hip_ctx *h, const char *who, int sched, int dtype, doub
     tab.push_back(e);
   }
   const size_t total = (size_t)w.nrec * x.record_bytes;
-  x.ev.assign((size_t)w.nrec, nullptr);
+  x.ev.resize((size_t)w.nrec);
   hipError_t e = hipSuccess;
-  if (!h->snap_stream) e = hipStreamCreateWithFlags(&h->snap_stream, hipStreamNonBlocking);
-  if (e == hipSuccess && total > 0) e = hipMalloc(&x.slots, total);
-  if (e == hipSuccess) e = hipMalloc(&x.d_tab, tab.size() * sizeof(mckpp_pack_plane));
-  for (int i = 0; i < w.nrec && e == hipSuccess; ++i) e = hipEventCreateWithFlags(&x.ev[(size_t)i], hipEventDisableTiming);
+  if (!h->snap_stream) e = h->snap_stream.create();
+  if (e == hipSuccess && total > 0) e = x.slots.alloc(total);
+  if (e == hipSuccess) e = x.d_tab.alloc(tab.size());
+  for (int i = 0; i < w.nrec && e == hipSuccess; ++i) e = x.ev[(size_t)i].create();
   if (e == hipSuccess) e = hipMemcpy(x.d_tab, tab.data(), tab.size() * sizeof(mckpp_pack_plane), hipMemcpyHostToDevice);
   if (e != hipSuccess) {
     (void)hipGetLastError();
-    if (x.slots) hipFree(x.slots);
-    if (x.d_tab) hipFree(x.d_tab);
-    for (auto ev : x.ev) if (ev) hipEventDestroy(ev);
     return fail("%s: cannot allocate %zu bytes of device memory for the %d export slots of schedule %d (%s); the schedule "
                 "stays set, without an export", who, total, w.nrec, sched, hipGetErrorString(e));
   }
-  w.ex = x;
+  w.ex = std::move(x);
   if (exp_start(h, w, total)) {   // a failed call leaves the schedule without an export
     (void)hipStreamSynchronize(h->stream);
     exp_drop(w);
@@ -2787,9 +2686,9 @@ int mckpp_hip_eos_batch(mckpp_hip_handle h, int64_t n, const double *s, const do
   if (!h) return fail("null handle");
   if (n <= 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  double *d = nullptr;
+  dev_buf<double> d;
   const size_t nb = (size_t)n * sizeof(double);
-  HIPCHK(hipMalloc(&d, 7 * nb));
+  HIPCHK(d.alloc(7 * (size_t)n));
   HIPCHK(hipMemcpy(d, s, nb, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + n, t, nb, hipMemcpyHostToDevice));
   HIPCHK(hipMemcpy(d + 2 * n, p, nb, hipMemcpyHostToDevice));
@@ -2799,7 +2698,6 @@ int mckpp_hip_eos_batch(mckpp_hip_handle h, int64_t n, const double *s, const do
   if (e == hipSuccess) e = hipMemcpy(beta, d + 4 * n, nb, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(sig0, d + 5 * n, nb, hipMemcpyDeviceToHost);
   if (e == hipSuccess) e = hipMemcpy(cp, d + 6 * n, nb, hipMemcpyDeviceToHost);
-  hipFree(d);
   HIPCHK(e);
   return 0;
 }
@@ -2809,15 +2707,14 @@ int mckpp_hip_div_batch(mckpp_hip_handle h, int64_t n, const double *num, const 
   if (!h) return fail("null handle");
   if (n <= 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  double *d = nullptr;
+  dev_buf<double> d;
   const size_t nb = (size_t)n * sizeof(double);
-  HIPCHK(hipMalloc(&d, 6 * nb));
+  HIPCHK(d.alloc(6 * (size_t)n));
   hipError_t e = hipMemcpy(d, num, nb, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = hipMemcpy(d + n, den, nb, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = mckpp_launch_div_batch(n, d, d + n, d + 2 * n, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e == hipSuccess) e = hipMemcpy(q4, d + 2 * n, 4 * nb, hipMemcpyDeviceToHost);
-  hipFree(d);
   HIPCHK(e);
   return 0;
 }
@@ -2827,14 +2724,13 @@ int mckpp_hip_exp_batch(mckpp_hip_handle h, int64_t n, const double *x, double *
   if (!h) return fail("null handle");
   if (n <= 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  double *d = nullptr;
+  dev_buf<double> d;
   const size_t nb = (size_t)n * sizeof(double);
-  HIPCHK(hipMalloc(&d, 2 * nb));
+  HIPCHK(d.alloc(2 * (size_t)n));
   hipError_t e = hipMemcpy(d, x, nb, hipMemcpyHostToDevice);
   if (e == hipSuccess) e = mckpp_launch_exp_batch(n, d, d + n, h->stream);
   if (e == hipSuccess) e = hipStreamSynchronize(h->stream);
   if (e == hipSuccess) e = hipMemcpy(y, d + n, nb, hipMemcpyDeviceToHost);
-  hipFree(d);
   HIPCHK(e);
   return 0;
 }
@@ -2847,25 +2743,26 @@ int mckpp_hip_exp_batch(mckpp_hip_handle h, int64_t n, const double *x, double *
 // and nothing crosses devices inside a step.  The only exchange is the output gather to one root
 // device over the GPU interconnect (xGMI peer copies), relayout there, one transfer to the host.
 // ---------------------------------------------------------------------------
-struct mckpp_hip_multi {
+// root-side resources of the gather, owned by the root device of the last gather (multi_release_root drops them as a
+// whole): one stream per shard, the events that order a shard's copy behind its owner's stream and the final transfer
+// behind all shards, the 3-D image, the staging area the shards' rows arrive in, every shard's column map
+struct mckpp_multi_root {
+  int root = -1;
+  std::vector<hip_stream> gstream;          // [ndev], on the root device
+  std::vector<hip_event> ev_done;           // [ndev], on the root device
+  hip_event ev_init, ev_gcopy;              // on the root device: 3-D image ready for the shards / delivered to the host
+  dev_buf<double> d_out, d_stage;           // grow-only (multi_prepare_root)
+  dev_buf<int> d_gipt;
+  bool gipt_valid = false;                  // d_gipt holds the maps of the current upload
+};
+
+struct mckpp_hip_multi : mckpp_multi_root {
   std::vector<mckpp_hip_ctx *> ctx;
   int64_t npts = 0;
   std::vector<std::vector<int32_t>> mask;   // run_physics of each shard
-  // root-side resources of the gather (owned by the root device of the last gather): the 3-D image, the staging
-  // area the shards' rows arrive in, every shard's column map, one stream per shard and the events that order
-  // a shard's copy behind its owner's stream and the final transfer behind all shards
-  int root = -1;
-  double *d_out = nullptr, *d_stage = nullptr;
-  int *d_gipt = nullptr;
-  size_t out_elems = 0, stage_elems = 0, gipt_elems = 0;
-  bool gipt_valid = false;                  // d_gipt holds the maps of the current upload
-  std::vector<hipStream_t> gstream;         // [ndev], on the root device
-  std::vector<hipEvent_t> ev_owner;         // [ndev], each on its shard's device
-  std::vector<hipEvent_t> ev_done;          // [ndev], on the root device
-  hipEvent_t ev_init = nullptr, ev_gcopy = nullptr;   // on the root device: 3-D image ready for the shards / delivered to the host
+  std::vector<hip_event> ev_owner;          // [ndev], each on its shard's device
   // pinned staging the shards' export planes arrive in before the host merges them (mckpp_hip_multi_window_export_fetch)
-  char *h_exp = nullptr;
-  size_t h_exp_bytes = 0;
+  pinned_buf<char> h_exp;
 };
 
 // run_physics mask of shard `dev` of `ndev`: the j-th ocean point (in ipt order) goes to shard j mod ndev
@@ -2888,18 +2785,8 @@ static void multi_release_root(mckpp_hip_multi *m)
 {
   if (m->root < 0) return;
   hipSetDevice(m->ctx[m->root]->device);
-  for (auto &st : m->gstream) if (st) { hipStreamSynchronize(st); hipStreamDestroy(st); }
-  for (auto &e : m->ev_done) if (e) hipEventDestroy(e);
-  if (m->ev_init) hipEventDestroy(m->ev_init);
-  if (m->ev_gcopy) hipEventDestroy(m->ev_gcopy);
-  m->gstream.clear(); m->ev_done.clear(); m->ev_init = nullptr; m->ev_gcopy = nullptr;
-  if (m->d_out) hipFree(m->d_out);
-  if (m->d_stage) hipFree(m->d_stage);
-  if (m->d_gipt) hipFree(m->d_gipt);
-  m->d_out = m->d_stage = nullptr; m->d_gipt = nullptr;
-  m->out_elems = m->stage_elems = m->gipt_elems = 0;
-  m->gipt_valid = false;
-  m->root = -1;
+  for (auto &st : m->gstream) if (st) hipStreamSynchronize(st);   // nothing of a gather may still use the buffers
+  static_cast<mckpp_multi_root &>(*m) = mckpp_multi_root{};
 }
 
 int mckpp_hip_multi_init(const mckpp_const_c *c, int32_t ndev, const int32_t *devices, mckpp_hip_multi_handle *out)
@@ -2916,10 +2803,9 @@ int mckpp_hip_multi_init(const mckpp_const_c *c, int32_t ndev, const int32_t *de
     m->ctx.push_back(h);
   }
   m->mask.resize(ndev);
-  m->ev_owner.assign(ndev, nullptr);
+  m->ev_owner.resize(ndev);
   for (int d = 0; d < ndev; ++d) {
-    if (hipSetDevice(m->ctx[d]->device) != hipSuccess ||
-        hipEventCreateWithFlags(&m->ev_owner[d], hipEventDisableTiming) != hipSuccess) {
+    if (hipSetDevice(m->ctx[d]->device) != hipSuccess || m->ev_owner[d].create() != hipSuccess) {
       mckpp_hip_multi_finalize(m);
       return fail("mckpp_hip_multi_init: cannot create the events of shard %d", d);
     }
@@ -2932,9 +2818,8 @@ int mckpp_hip_multi_finalize(mckpp_hip_multi_handle m)
 {
   if (!m) return 0;
   multi_release_root(m);
-  if (m->h_exp) hipHostFree(m->h_exp);
   for (size_t d = 0; d < m->ev_owner.size(); ++d)
-    if (m->ev_owner[d]) { hipSetDevice(m->ctx[d]->device); hipEventDestroy(m->ev_owner[d]); }
+    if (m->ev_owner[d]) { hipSetDevice(m->ctx[d]->device); m->ev_owner[d].reset(); }
   for (auto *x : m->ctx) mckpp_hip_finalize(x);
   delete m;
   return 0;
@@ -3038,32 +2923,34 @@ static int multi_prepare_root(mckpp_hip_multi *m, int root, size_t nout, size_t 
   if (m->root != root) {
     multi_release_root(m);
     HIPCHK(hipSetDevice(r->device));
-    m->root = root;
-    m->gstream.assign(ndev, nullptr);
-    m->ev_done.assign(ndev, nullptr);
+    mckpp_multi_root n;   // built here, moved in when all of it is there
+    n.root = root;
+    n.gstream.resize(ndev);
+    n.ev_done.resize(ndev);
     for (int d = 0; d < ndev; ++d) {
-      HIPCHK(hipStreamCreateWithFlags(&m->gstream[d], hipStreamNonBlocking));
-      HIPCHK(hipEventCreateWithFlags(&m->ev_done[d], hipEventDisableTiming));
+      HIPCHK(n.gstream[d].create());
+      HIPCHK(n.ev_done[d].create());
       if (d != root && m->ctx[d]->device != r->device) {
         hipError_t e = hipDeviceEnablePeerAccess(m->ctx[d]->device, 0);
         if (e != hipSuccess && e != hipErrorPeerAccessAlreadyEnabled) (void)hipGetLastError();   // staged copies still work
       }
     }
-    HIPCHK(hipEventCreateWithFlags(&m->ev_init, hipEventDisableTiming));
-    HIPCHK(hipEventCreateWithFlags(&m->ev_gcopy, hipEventDisableTiming));
+    HIPCHK(n.ev_init.create());
+    HIPCHK(n.ev_gcopy.create());
+    static_cast<mckpp_multi_root &>(*m) = std::move(n);
   }
   HIPCHK(hipSetDevice(r->device));
   size_t ngipt = 0;
   for (auto *x : m->ctx) ngipt += (size_t)x->ncol;
-  const bool grow = nout > m->out_elems || nstage > m->stage_elems || ngipt > m->gipt_elems;
+  const bool grow = nout > m->d_out.size() || nstage > m->d_stage.size() || ngipt > m->d_gipt.size();
   if (grow) {   // nothing of an earlier gather may still be using the buffers
     for (auto &st : m->gstream) HIPCHK(hipStreamSynchronize(st));
     HIPCHK(hipStreamSynchronize(r->stream));
     HIPCHK(hipStreamSynchronize(r->copy_stream));
   }
-  if (nout > m->out_elems) { if (m->d_out) hipFree(m->d_out); m->d_out = nullptr; HIPCHK(hipMalloc(&m->d_out, nout * sizeof(double))); m->out_elems = nout; }
-  if (nstage > m->stage_elems) { if (m->d_stage) hipFree(m->d_stage); m->d_stage = nullptr; HIPCHK(hipMalloc(&m->d_stage, nstage * sizeof(double))); m->stage_elems = nstage; }
-  if (ngipt > m->gipt_elems) { if (m->d_gipt) hipFree(m->d_gipt); m->d_gipt = nullptr; HIPCHK(hipMalloc(&m->d_gipt, ngipt * sizeof(int))); m->gipt_elems = ngipt; m->gipt_valid = false; }
+  HIPCHK(m->d_out.reserve(nout));
+  HIPCHK(m->d_stage.reserve(nstage));
+  if (ngipt > m->d_gipt.size()) { m->gipt_valid = false; HIPCHK(m->d_gipt.reserve(ngipt)); }
   if (!m->gipt_valid) {   // the shards' column maps, once per upload
     size_t go = 0;
     for (auto *x : m->ctx) {
@@ -3353,12 +3240,7 @@ static int multi_exp_fetch(mckpp_hip_multi *m, const char *who, int sched, int64
       at[(size_t)d] = total;
       total += (nb[(size_t)d] + 255) & ~(size_t)255;
     }
-    if (total > m->h_exp_bytes) {
-      if (m->h_exp) hipHostFree(m->h_exp);
-      m->h_exp = nullptr; m->h_exp_bytes = 0;
-      HIPCHK(hipHostMalloc(&m->h_exp, total, hipHostMallocPortable));
-      m->h_exp_bytes = total;
-    }
+    HIPCHK(m->h_exp.reserve(total, hipHostMallocPortable));
     int rc = 0;
     for (int d = 0; d < ndev && rc == 0; ++d) {
       const auto &w = m->ctx[d]->wsched[sched];
@@ -3502,7 +3384,7 @@ int mckpp_hip_multi_step_log_fetch(mckpp_hip_multi_handle m, int64_t n, int32_t 
   try {
     std::vector<log_event> all, ev;
     for (auto *x : m->ctx) {
-      if (x->log_cap == 0) return fail("%s: no step log is set", who);
+      if (x->slog.cap == 0) return fail("%s: no step log is set", who);
       int64_t stored = 0;
       if (log_read_ctl(x, nullptr, &stored, nullptr) || log_fetch_raw(x, who, stored, ev)) return -1;
       all.insert(all.end(), ev.begin(), ev.end());

@@ -143,3 +143,15 @@ def test_shard_mask_logic(built):
         assert np.array_equal(total, rp) and max(counts) - min(counts) <= 1
     with pytest.raises(mk.MckppHipError):
         mk.host_shard_mask(np.ones(4, dtype=np.int32), 2, 2)
+
+
+def test_hip_resources_have_one_owner():
+    """The runtime creates and destroys no device block, pinned block, event or stream by hand: every such call is in
+    the owners of mckpp_own.h, so no path of the runtime can forget a release."""
+    csrc = os.path.join(ROOT, "mckpp_f90_amd", "csrc")
+    runtime = open(os.path.join(csrc, "mckpp_runtime.cpp")).read()
+    own = open(os.path.join(csrc, "mckpp_own.h")).read()
+    for call in ("hipFree(", "hipHostFree(", "hipEventDestroy(", "hipStreamDestroy(", "hipMalloc(", "hipHostMalloc(",
+                 "hipEventCreate", "hipStreamCreate"):
+        assert call not in runtime, f"{call} in mckpp_runtime.cpp: use the owners of mckpp_own.h"
+        assert call in own, call
