@@ -183,6 +183,32 @@ int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const doub
 int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtocn, int l_rest,
                          double flsn, double el);
 
+/* The flux-record ring: the forcing of a long or coupled run streamed in while earlier launches run, instead of a
+ * series that a call replaces as a whole.  What arrives is what the reference's loop reads between steps
+ * (src/mckpp_ocean_model_3D.F90:44-48) - the eight fields mckpp_fluxes assembles sflux from
+ * (src/mckpp_fluxes_mod.F90:35-89) - one record at a time.  Record r lives in slot r % nslots of device memory, a slot
+ * being [8][resident columns]; a put overwrites the oldest record.
+ *   flux_ring: a ring of nslots empty slots (nslots 0: cancels it, after waiting for the context's stream and the
+ *     ring's transfer stream).  Needs an uploaded state.  A ring in place is dropped first, and so is a series of
+ *     mckpp_hip_set_flux_series; while a ring is set, set_flux_series is refused.  upload with another column map and
+ *     load_restart cancel the ring; output, restart, step-log and ancillary schedules are left alone.
+ *   flux_ring_put: `fields`[8][npts] is record `rec` of the run, layout and field order of one record of
+ *     set_flux_series.  Records arrive in order: the first put names any rec >= 0, every later one the last plus 1.
+ *     The record is compacted to the resident columns into pinned staging and copied into its slot on a transfer stream
+ *     of the ring's own - under the launches already queued on the context's stream - behind, on the device, the
+ *     launches of the last run_forced call that needed the record the slot held.  Returns without waiting for the
+ *     device; `fields` may be rewritten at once.  (The one host wait: the staging has two turns, so a put waits for the
+ *     copy of two puts back if that is still in flight.)
+ *   flux_ring_records: the resident range, the last min(nslots, records put) records; -1, -1: the ring is empty.
+ *   mckpp_hip_run_forced with a ring set checks its flux updates against that range - a record not yet put, or
+ *     already overwritten, fails the call before anything is launched, naming steps, records and range - makes the
+ *     context's stream wait for the copies of the records it needs, and launches as ever (one launch or a launch per
+ *     step), every update step finding its record's slot itself.  A call needs at most nslots records: records must be
+ *     resident when their launch starts.  There is no release call: the residency check is the only bookkeeping. */
+int mckpp_hip_flux_ring(mckpp_hip_handle h, int nslots);
+int mckpp_hip_flux_ring_put(mckpp_hip_handle h, int rec, const double *fields);
+int mckpp_hip_flux_ring_records(mckpp_hip_handle h, int *first, int *last);
+
 /* mckpp_physics_overrides_bottomtemp (src/mckpp_physics_overrides.F90:12-24),
  * which mckpp_physics_driver calls after the column loop when
  * kpp_const_fields%L_VARY_BOTTOM_TEMP (src/mckpp_physics_driver_mod.F90:67-71):
@@ -584,6 +610,12 @@ int mckpp_hip_multi_gather(mckpp_hip_multi_handle m, int32_t field, int32_t root
 int mckpp_hip_multi_set_flux_series(mckpp_hip_multi_handle m, int rec0, int nrec, const double *fields);
 int mckpp_hip_multi_run_forced(mckpp_hip_multi_handle m, int nt_first, int nsteps, int ndtocn, int l_rest,
                                double flsn, double el);
+/* The flux-record ring (mckpp_hip_flux_ring; src/mckpp_ocean_model_3D.F90:44-48, src/mckpp_fluxes_mod.F90:35-89) over
+ * all shards: every shard keeps a ring of its own and compacts its own columns from the one caller array
+ * `fields`[8][npts]; flux_ring_records is the range common to all shards. */
+int mckpp_hip_multi_flux_ring(mckpp_hip_multi_handle m, int nslots);
+int mckpp_hip_multi_flux_ring_put(mckpp_hip_multi_handle m, int rec, const double *fields);
+int mckpp_hip_multi_flux_ring_records(mckpp_hip_multi_handle m, int *first, int *last);
 /* Output windows (src/mckpp_xios_io.F90:74-210, run/iodef.xml:88-157) over all shards: each shard reduces
  * its own columns, window_fetch gathers the reduced rows like any other field. */
 int mckpp_hip_multi_window_select(mckpp_hip_multi_handle m, const int32_t *fields, int32_t nfields);

@@ -275,6 +275,10 @@ def _bind(lib):
     lib.mckpp_hip_release_host_arrays.argtypes = [C.c_void_p]
     lib.mckpp_hip_multi_release_host_arrays.argtypes = [C.c_void_p]
     lib.mckpp_hip_multi_set_flux_series.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
+    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
+        getattr(lib, pre + "flux_ring").argtypes = [C.c_void_p, C.c_int]
+        getattr(lib, pre + "flux_ring_put").argtypes = [C.c_void_p, C.c_int, _dp]
+        getattr(lib, pre + "flux_ring_records").argtypes = [C.c_void_p, _ip, _ip]
     lib.mckpp_hip_multi_run_forced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
     lib.mckpp_hip_multi_window_select.argtypes = [C.c_void_p, _ip, C.c_int32]
     lib.mckpp_hip_multi_window_reset.argtypes = [C.c_void_p]
@@ -666,7 +670,34 @@ class _AncillarySeries:
                                                               len(ep), arr))
 
 
-class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries):
+class _FluxRing:
+    """The flux-record ring (mckpp_hip_flux_ring and its kin), for one context or for all shards of a multi handle
+    (_pre)."""
+    _pre = "mckpp_hip_"
+
+    def flux_ring(self, nslots):
+        """A ring of `nslots` flux-record slots on the device, empty; 0 cancels it.  Drops a set_flux_series series."""
+        _chk(getattr(_lib(), self._pre + "flux_ring")(self._h, int(nslots)))
+
+    def flux_ring_put(self, rec, fields):
+        """fields[8, npts] (taux, tauy, swf, lwf, lhf, shf, rain, snow) is record `rec` of the run; records arrive in
+        order.  Returns without waiting for the device: `fields` may be rewritten at once."""
+        f = np.ascontiguousarray(fields, dtype=np.float64)
+        if f.ndim != 2 or f.shape[0] != 8:
+            raise ValueError(f"flux_ring_put: a record is fields[8, npts], got {f.shape}")
+        n = getattr(self, "_npts_cache", 0) if callable(self._npts) else self._npts
+        if n and f.shape[1] != n:   # (before an upload the library refuses the call itself)
+            raise ValueError(f"flux_ring_put: a record is fields[8, npts={n}], got {f.shape}")
+        _chk(getattr(_lib(), self._pre + "flux_ring_put")(self._h, int(rec), f.ctypes.data_as(_dp)))
+
+    def flux_ring_records(self):
+        """(first, last) resident records: the last min(nslots, records put); (-1, -1): the ring is empty."""
+        a, b = C.c_int(), C.c_int()
+        _chk(getattr(_lib(), self._pre + "flux_ring_records")(self._h, C.byref(a), C.byref(b)))
+        return int(a.value), int(b.value)
+
+
+class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing):
     """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
 
     def __init__(self, kpp_const_fields, device=0):
@@ -881,7 +912,7 @@ class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries):
         return y
 
 
-class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries):
+class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing):
     """Several GPUs behind one handle (mckpp_hip_multi_*): columns dealt round-robin to the devices."""
     _pre = "mckpp_hip_multi_"
 

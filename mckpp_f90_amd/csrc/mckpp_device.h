@@ -100,6 +100,8 @@ struct mckpp_kparams_t {
   // forced run in one launch (mckpp_hip_run_forced): the flux records and how a step finds its own
   P<const double> series;   // [nrec][8][ncol]: taux, tauy, swf, lwf, lhf, shf, rain, snow; null: the forcing is what cs holds
   int series_rec0, ndtocn, l_rest;
+  int series_nring;   // > 0: `series` is a ring of that many slots [8][ncol] (mckpp_hip_flux_ring), record r in slot
+                      // r % series_nring, series_rec0 unused; 0: the linear series from record series_rec0 on
   double flsn, el;
   P<int> qowner;  // [16] per queue: 0 free, else hardware XCC id + 1 of the XCD whose workgroups serve it (zeroed per launch)
   P<int> done;    // [ncol] steps of this launch a column has completed, then [ncol] steps of it that have been started

@@ -1506,7 +1506,11 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
             // the forced run in one launch: this step is a flux update (mckpp_ocean_model_3D.F90:44-48) - mckpp_fluxes'
             // assembly of sflux(1:6) (fluxes_mod.F90:55-77; k_fluxes of the launch-per-step path, same operations) from
             // the step's record, kept in the column's record for the steps until the next update and for the host
-            const auto f8 = p.series + (size_t)((p.ntime + step - 1) / p.ndtocn - p.series_rec0) * 8 * (size_t)p.ncol + c;
+            // (a ring of record slots - mckpp_hip_flux_ring: the records of one launch may wrap, so the slot is found
+            // here, per column-step; a launch without a ring takes the linear series' index as before)
+            int irec = (p.ntime + step - 1) / p.ndtocn;
+            if (p.series_nring > 0) irec %= p.series_nring; else irec -= p.series_rec0;
+            const auto f8 = p.series + (size_t)irec * 8 * (size_t)p.ncol + c;
             const size_t n = (size_t)p.ncol;
             double taux = f8[0];
             const double tauy = f8[n], swf = f8[2 * n], lwf = f8[3 * n], lhf = f8[4 * n], shf = f8[5 * n], rain = f8[6 * n], snow = f8[7 * n];

@@ -95,6 +95,8 @@ struct mckpp_ctx_streams {
   // (hipHostRegister, once per array) so those transfers are asynchronous and run at the bus rate.
   hip_stream copy_stream;
   hip_stream snap_stream;   // transfers of snapshot_save and of the export's fetches
+  hip_stream flux_stream;   // the flux ring's host-to-device copies (mckpp_hip_flux_ring_put): they run under the launches
+                            // already queued, so not on copy_stream, whose downloads wait for the kernels
 };
 
 // Everything sized to the resident columns: free_state drops it as a whole, by one assignment.  A new feature whose
@@ -175,6 +177,18 @@ struct mckpp_ctx_resident {
   dev_buf<int> d_done;   // [2][ncol] steps of a multi-step launch each column has completed, and has started (mckpp_kparams_t::done)
   dev_buf<double> d_series;   // [nrec][8][ncol] forcing records (mckpp_hip_set_flux_series)
   int series_rec0 = 0, series_nrec = 0;
+  // the ring of flux-record slots (mckpp_hip_flux_ring): record r in slot r % nslots, each [8][ncol] compacted like a
+  // record of d_series; the records put so far are first_put .. next_put - 1, resident the last nslots of them.  Per
+  // slot two events: `arrived` behind the copy of the record it holds (flux_stream), `last_read` behind the launches of
+  // the last run_forced call that needed that record (the context's stream) - the next copy into the slot waits for it
+  // on flux_stream.  The staging: the record compacted on the host, a pinned image used in turn.  nslots 0: no ring.
+  struct flux_ring {
+    int nslots = 0;
+    int first_put = -1, next_put = -1;   // -1: nothing put yet (the first put names any record)
+    dev_buf<double> slots;
+    std::vector<hip_event> arrived, last_read;   // [nslots]
+    pinned_turns<double> stage;
+  } ring;
   dev_buf<double> d_stage;    // grow-only (ensure_stage)
   dev_buf<double> d_xfer[2];  // the staging buffers of the row transfers, grow-only (ensure_xfer)
   // pinned host images of the column records and of the forcing staging (grow-only: ensure_host_f)
@@ -482,6 +496,7 @@ static int snap_cancel(mckpp_hip_ctx *h);
 static int log_cancel(mckpp_hip_ctx *h);
 static int bt_cancel(mckpp_hip_ctx *h);
 static int anc_cancel_all(mckpp_hip_ctx *h);
+static int ring_cancel(mckpp_hip_ctx *h);
 
 // Everything sized to the resident columns goes.  No wait here: the callers have cancelled the schedules, which waits
 // for the launches that may still use their records.
@@ -503,6 +518,7 @@ int mckpp_hip_finalize(mckpp_hip_handle h)
   if (h->stream) hipStreamSynchronize(h->stream);   // nothing in flight may still use what the owners release
   if (h->copy_stream) hipStreamSynchronize(h->copy_stream);
   if (h->snap_stream) hipStreamSynchronize(h->snap_stream);
+  if (h->flux_stream) hipStreamSynchronize(h->flux_stream);
   unpin_all(h);
   delete h;
   return 0;
@@ -707,6 +723,8 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   for (int64_t i = 0; i < npts; ++i)
     if (!s->run_physics || s->run_physics[i]) ipt.push_back((int)i);
   const int64_t ncol = (int64_t)ipt.size();
+  // another column map: the flux ring's records were compacted with the previous one (it waits for what it has queued)
+  if ((ipt != h->ipt || npts != h->npts) && ring_cancel(h)) return -1;
   if (ncol != h->ncol || npts != h->npts) {
     if (alloc_state(h, npts, ncol)) return -1;
   }
@@ -1186,7 +1204,8 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
   }
 }
 
-struct forced_run { int ndtocn, l_rest; double flsn, el; };
+// the records a forced run reads: the linear series from record rec0 on, or (nring > 0) the ring's slots
+struct forced_run { int ndtocn, l_rest; double flsn, el; const double *series; int rec0, nring; };
 
 static int win_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
@@ -1247,7 +1266,8 @@ static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const f
       fill_params(h, q, ntime + i, mode);
       q.nsteps_launch = n;
       if (forced) {   // the forced run: every step finds its flux record itself (k_column_ps, M0)
-        q.series = h->d_series; q.series_rec0 = h->series_rec0; q.ndtocn = forced->ndtocn; q.l_rest = forced->l_rest;
+        q.series = forced->series; q.series_rec0 = forced->rec0; q.series_nring = forced->nring;
+        q.ndtocn = forced->ndtocn; q.l_rest = forced->l_rest;
         q.flsn = forced->flsn; q.el = forced->el;
       }
       HIPCHK(hipMemcpyAsync(h->d_params, qp, sizeof(mckpp_kparams), hipMemcpyHostToDevice, h->stream));
@@ -1266,8 +1286,9 @@ static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const f
     mckpp_kparams p;
     fill_params(h, p, ntime + i, mode);
     if (forced && (ntime + i - 1) % forced->ndtocn == 0) {   // ocean_model_3D.F90:44-48
-      const int rec = (ntime + i - 1) / forced->ndtocn - h->series_rec0;
-      HIPCHK(mckpp_launch_fluxes(p, ntime + i, h->d_series + (size_t)rec * 8 * (size_t)h->ncol, forced->l_rest,
+      const int upd = (ntime + i - 1) / forced->ndtocn;
+      const int rec = forced->nring > 0 ? upd % forced->nring : upd - forced->rec0;   // the ring's slot | the series' index
+      HIPCHK(mckpp_launch_fluxes(p, ntime + i, forced->series + (size_t)rec * 8 * (size_t)h->ncol, forced->l_rest,
                                  forced->flsn, forced->el, h->stream));
     }
     HIPCHK(hipMemsetAsync(h->d_qhead, 0, QBLOCK_INTS * sizeof(int), h->stream));
@@ -1294,6 +1315,9 @@ int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const doub
   if (!h || !fields) return fail("mckpp_hip_set_flux_series: null argument");
   if (nrec < 1 || rec0 < 0) return fail("mckpp_hip_set_flux_series: rec0=%d nrec=%d", rec0, nrec);
   if (h->npts <= 0) return fail("mckpp_hip_set_flux_series: upload the state first (the records are compacted to the resident columns)");
+  if (h->ring.nslots > 0)
+    return fail("mckpp_hip_set_flux_series: a flux ring of %d slots is set (mckpp_hip_flux_ring); the two are mutually "
+                "exclusive - cancel the ring first (mckpp_hip_flux_ring with 0 slots)", h->ring.nslots);
   HIPCHK(hipSetDevice(h->device));
   h->d_series.reset();
   h->series_rec0 = rec0;
@@ -1312,6 +1336,112 @@ int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const doub
   return 0;
 }
 
+// ---------------------------------------------------------------------------
+// The flux-record ring: forcing streamed in while earlier launches run
+// ---------------------------------------------------------------------------
+// the records the ring holds (-1, -1: none)
+static void ring_range(const mckpp_hip_ctx::flux_ring &g, int *first, int *last)
+{
+  *first = *last = -1;
+  if (g.nslots == 0 || g.next_put < 0) return;
+  *last = g.next_put - 1;
+  *first = std::max(g.first_put, g.next_put - g.nslots);
+}
+
+static int ring_cancel(mckpp_hip_ctx *h)
+{
+  if (h->ring.nslots == 0) return 0;
+  if (h->stream) HIPCHK(hipStreamSynchronize(h->stream));             // no launch in flight may still read the slots
+  if (h->flux_stream) HIPCHK(hipStreamSynchronize(h->flux_stream));   // no copy in flight may still write them, or read the staging
+  h->ring = mckpp_hip_ctx::flux_ring{};
+  return 0;
+}
+
+int mckpp_hip_flux_ring(mckpp_hip_handle h, int nslots)
+{
+  const char *who = "mckpp_hip_flux_ring";
+  if (!h) return fail("%s: null handle", who);
+  if (nslots < 0) return fail("%s: nslots=%d (0 cancels the ring)", who, nslots);
+  if (nslots > 0 && h->npts <= 0) return fail("%s: upload the state first (the slots are sized to the resident columns)", who);
+  HIPCHK(hipSetDevice(h->device));
+  if (ring_cancel(h)) return -1;
+  if (nslots == 0) return 0;
+  mckpp_hip_ctx::flux_ring g;   // built here, moved in when all of it is there
+  if (h->ncol > 0) {
+    if (!h->flux_stream) HIPCHK(h->flux_stream.create());
+    const size_t rec = 8 * (size_t)h->ncol;
+    g.arrived.resize((size_t)nslots);
+    g.last_read.resize((size_t)nslots);
+    hipError_t e = g.slots.alloc((size_t)nslots * rec);
+    for (int i = 0; i < nslots && e == hipSuccess; ++i) {
+      e = g.arrived[(size_t)i].create();
+      if (e == hipSuccess) e = g.last_read[(size_t)i].create();
+    }
+    if (e == hipSuccess) e = g.stage.prepare(rec);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return fail("%s: cannot allocate the %d slots of %zu bytes each (%s); no ring is set", who, nslots, rec * sizeof(double),
+                  hipGetErrorString(e));
+    }
+  }
+  g.nslots = nslots;
+  if (h->d_series) {   // the ring takes the series' place
+    HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read its records
+    h->d_series.reset();
+  }
+  h->series_nrec = 0;
+  h->ring = std::move(g);
+  return 0;
+}
+
+int mckpp_hip_flux_ring_put(mckpp_hip_handle h, int rec, const double *fields)
+{
+  const char *who = "mckpp_hip_flux_ring_put";
+  if (!h) return fail("%s: null handle", who);
+  if (!fields) return fail("%s: null argument", who);
+  if (h->npts <= 0) return fail("%s: upload the state and set a ring first (mckpp_hip_flux_ring)", who);
+  auto &g = h->ring;
+  if (g.nslots == 0) return fail("%s: no flux ring is set (mckpp_hip_flux_ring)", who);
+  if (g.next_put < 0 ? rec < 0 : rec != g.next_put)
+    return fail("%s: record %d, but the records arrive in order: %s%d", who, rec,
+                g.next_put < 0 ? "the first one is any record >= " : "the next one is record ", g.next_put < 0 ? 0 : g.next_put);
+  if (h->ncol > 0) {
+    HIPCHK(hipSetDevice(h->device));
+    const size_t ncol = (size_t)h->ncol, npts = (size_t)h->npts;
+    const int slot = rec % g.nslots;
+    double *st = nullptr;
+    HIPCHK(g.stage.take(8 * ncol, &st));   // (the only host wait: for the copy of two puts back, if still in flight)
+    const int *ipt = h->ipt.data();
+    for_columns(h->ncol, [=](int64_t a, int64_t b) {
+      for (int m = 0; m < 8; ++m) {
+        const double *src = fields + (size_t)m * npts;
+        double *dst = st + (size_t)m * ncol;
+        for (int64_t c = a; c < b; ++c) dst[c] = src[ipt[c]];
+      }
+    });
+    // behind the launches of the last call that needed the record the slot held - on the device, never on the host
+    HIPCHK(hipStreamWaitEvent(h->flux_stream, g.last_read[(size_t)slot], 0));
+    HIPCHK(hipMemcpyAsync(g.slots + (size_t)slot * 8 * ncol, st, 8 * ncol * sizeof(double), hipMemcpyHostToDevice, h->flux_stream));
+    HIPCHK(g.stage.queued(h->flux_stream));
+    HIPCHK(hipEventRecord(g.arrived[(size_t)slot], h->flux_stream));
+  }
+  if (g.next_put < 0) g.first_put = rec;
+  g.next_put = rec + 1;
+  return 0;
+}
+
+int mckpp_hip_flux_ring_records(mckpp_hip_handle h, int *first, int *last)
+{
+  const char *who = "mckpp_hip_flux_ring_records";
+  if (!h) return fail("%s: null handle", who);
+  if (h->ring.nslots == 0) return fail("%s: no flux ring is set (mckpp_hip_flux_ring)", who);
+  int a, b;
+  ring_range(h->ring, &a, &b);
+  if (first) *first = a;
+  if (last) *last = b;
+  return 0;
+}
+
 int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtocn, int l_rest, double flsn, double el)
 {
   if (!h) return fail("null handle");
@@ -1320,12 +1450,34 @@ int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtoc
   if (nsteps == 0) return 0;
   // every flux update of the span must be resident before anything is launched
   const int first_upd = (nt_first - 1 + ndtocn - 1) / ndtocn, last_upd = (nt_first + nsteps - 2) / ndtocn;
-  if (first_upd <= last_upd &&
+  auto &g = h->ring;
+  if (g.nslots > 0) {
+    int a, b;
+    ring_range(g, &a, &b);
+    if (first_upd <= last_upd && (b < 0 || first_upd < a || last_upd > b))
+      return fail("mckpp_hip_run_forced: steps %d..%d need flux records %d..%d, the ring of %d slots holds %d..%d", nt_first,
+                  nt_first + nsteps - 1, first_upd, last_upd, g.nslots, a, b);
+  } else if (first_upd <= last_upd &&
       (h->series_nrec == 0 || first_upd < h->series_rec0 || last_upd >= h->series_rec0 + h->series_nrec))
     return fail("mckpp_hip_run_forced: steps %d..%d need flux records %d..%d, resident are %d..%d", nt_first,
                 nt_first + nsteps - 1, first_upd, last_upd, h->series_rec0, h->series_rec0 + h->series_nrec - 1);
-  const forced_run fr{ndtocn, l_rest, flsn, el};
-  return run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr, "mckpp_hip_run_forced");
+  if (g.nslots == 0) {
+    const forced_run fr{ndtocn, l_rest, flsn, el, h->d_series, h->series_rec0, 0};
+    return run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr, "mckpp_hip_run_forced");
+  }
+  // the ring: the launches wait, on the device, for the copies of the records they need; behind them the slots are
+  // marked as read, which is what the next copy into each waits for
+  const bool live = h->ncol > 0;
+  if (live) HIPCHK(hipSetDevice(h->device));
+  for (int r = first_upd; live && r <= last_upd; ++r) HIPCHK(hipStreamWaitEvent(h->stream, g.arrived[(size_t)(r % g.nslots)], 0));
+  const forced_run fr{ndtocn, l_rest, flsn, el, g.slots, 0, g.nslots};
+  const int rc = run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr, "mckpp_hip_run_forced");
+  // (also after a failure: some of the call's launches may be queued)
+  for (int r = first_upd; live && r <= last_upd; ++r) {
+    const hipError_t e = hipEventRecord(g.last_read[(size_t)(r % g.nslots)], h->stream);
+    if (e != hipSuccess && rc == 0) HIPCHK(e);
+  }
+  return rc;
 }
 
 int mckpp_hip_synchronize(mckpp_hip_handle h)
@@ -1999,6 +2151,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
   if (log_cancel(h)) return -1;       // ... and the step log's records
   if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
   if (anc_cancel_all(h)) return -1;   // ... and the ancillary record series and their schedules (likewise)
+  if (ring_cancel(h)) return -1;      // ... and the flux ring (likewise)
   const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
   if (!same_shape) {
     if (alloc_state(h, hd.npts, hd.ncol)) return -1;
@@ -3067,6 +3220,36 @@ int mckpp_hip_multi_download(mckpp_hip_multi_handle m, mckpp_state_ptrs_c *s, ui
 int mckpp_hip_multi_set_flux_series(mckpp_hip_multi_handle m, int rec0, int nrec, const double *fields)
 {
   MULTI_EACH(mckpp_hip_set_flux_series(x, rec0, nrec, fields));
+}
+// the flux ring over all shards: every shard compacts its own columns of the one caller array into its own ring
+int mckpp_hip_multi_flux_ring(mckpp_hip_multi_handle m, int nslots)
+{
+  if (!m) return fail("mckpp_hip_multi_flux_ring: null handle");
+  MULTI_EACH(mckpp_hip_flux_ring(x, nslots));
+}
+int mckpp_hip_multi_flux_ring_put(mckpp_hip_multi_handle m, int rec, const double *fields)
+{
+  if (!m) return fail("mckpp_hip_multi_flux_ring_put: null handle");
+  MULTI_EACH(mckpp_hip_flux_ring_put(x, rec, fields));
+}
+// the range common to all shards (they are put to together: it is every shard's own)
+int mckpp_hip_multi_flux_ring_records(mckpp_hip_multi_handle m, int *first, int *last)
+{
+  if (!m) return fail("mckpp_hip_multi_flux_ring_records: null handle");
+  int a = -1, b = -1;
+  bool any = false, empty = false;
+  for (auto *x : m->ctx) {
+    int fa, fb;
+    if (mckpp_hip_flux_ring_records(x, &fa, &fb) != 0) return -1;
+    if (fb < 0) empty = true;
+    a = any ? std::max(a, fa) : fa;
+    b = any ? std::min(b, fb) : fb;
+    any = true;
+  }
+  if (empty || a > b) a = b = -1;
+  if (first) *first = a;
+  if (last) *last = b;
+  return 0;
 }
 // asynchronous on every device, like mckpp_hip_multi_step
 int mckpp_hip_multi_run_forced(mckpp_hip_multi_handle m, int nt_first, int nsteps, int ndtocn, int l_rest, double flsn, double el)

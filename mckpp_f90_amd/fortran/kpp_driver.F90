@@ -27,7 +27,8 @@ program kpp_driver
                                mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
                                mckpp_hip_all_restart_snapshot_release, mckpp_hip_all_step_log, &
                                mckpp_hip_all_set_ancillary_series, mckpp_hip_all_ancillary_schedule, &
-                               mckpp_hip_push_ancillaries, mckpp_hip_ancillaries_every_step
+                               mckpp_hip_push_ancillaries, mckpp_hip_ancillaries_every_step, &
+                               mckpp_hip_all_flux_ring, mckpp_hip_all_flux_ring_put
   implicit none
   character(len=512) :: fin, fout
   integer :: u, nt, nsteps, ncol, nlev, use_1d, ipt, flags
@@ -37,7 +38,7 @@ program kpp_driver
   real(c_double) :: t0, t1
   real(c_double), allocatable :: vm_h(:), vm_k(:), vm_difm(:,:), vm_difs(:,:), vm_dift(:,:), vm_ghat(:,:)
   real(c_double) :: hmixn
-  integer :: kmixn, snap_first, snap_last, ncut
+  integer :: kmixn, snap_first, snap_last, ncut, nrec, r, i
   real(c_double), allocatable :: exp_h(:,:), exp_t(:,:,:)   ! flag 4096: the records fetched through the export
   character(len=16) :: snap_name
   ! flag 2048: records of SST0 (npts, nrec) and ocnT_clim (npts, nzp1, nrec) and the epochs of ocnT_clim
@@ -72,6 +73,10 @@ program kpp_driver
   !           (interpolated between two records, mckpp_boundary_interpolate_temp's sum), the records made from the
   !           case's own profiles.  With 16 the one forced run reads them from resident series under schedules; with 1
   !           the per-step driver gets the same fields through mckpp_hip_push_ancillaries at those cadences
+  !        8192 with 16: ndtocn = 2 and flux records that change with their number r (from 0): swf = 200 + 25 r,
+  !           taux = 0.01 (1 + 0.1 r); all of them resident (mckpp_hip_all_set_flux_series), the time loop ONE forced run
+  !        16384 with 8192: the records through a flux ring of 2 slots instead: two records put, the forced run of their
+  !           four steps, and so on - the next pair is put while that run is queued
   flags = hdr(6)
   if (iand(flags, 64) /= 0) mckpp_hip_output_mask = MCKPP_F_SCALARS
   ! hdr(7) > 0: that many device shards; hdr(8) = 1 puts them all on HIP device 0 (one-GPU rehearsal of the
@@ -128,10 +133,18 @@ program kpp_driver
   kpp_3d_fields%sflux(:, 1:6, 5, 0) = sf6
   call cpu_time(t0)
   if (iand(flags, 48 + 256 + 512 + 1024) /= 0) then   ! the reference's loop (src/mckpp_ocean_model_3D.F90:38-58) on the devices
-    allocate (series(ncol, 8, 1))
-    series(:, 1, 1) = 0.01_c_double; series(:, 2, 1) = 0; series(:, 3, 1) = 200; series(:, 4, 1) = 0
-    series(:, 5, 1) = -150; series(:, 6, 1) = 0; series(:, 7, 1) = 6e-5_c_double; series(:, 8, 1) = 0
-    call mckpp_hip_all_set_flux_series(0, 1, series)
+    nrec = 1
+    if (iand(flags, 8192) /= 0) nrec = (nsteps + 1) / 2
+    allocate (series(ncol, 8, nrec))
+    series(:, 1, :) = 0.01_c_double; series(:, 2, :) = 0; series(:, 3, :) = 200; series(:, 4, :) = 0
+    series(:, 5, :) = -150; series(:, 6, :) = 0; series(:, 7, :) = 6e-5_c_double; series(:, 8, :) = 0
+    if (iand(flags, 8192) /= 0) then
+      do r = 0, nrec - 1
+        series(:, 3, r + 1) = 200 + 25._c_double * r
+        series(:, 1, r + 1) = 0.01_c_double * (1 + 0.1_c_double * r)
+      end do
+    end if
+    if (iand(flags, 8192 + 16384) /= 8192 + 16384) call mckpp_hip_all_set_flux_series(0, nrec, series)
     if (iand(flags, 1024) /= 0) call mckpp_hip_all_step_log(ncol * nsteps, 0)
     if (iand(flags, 2048) /= 0) then   ! the records resident, every column-step reads its own epoch's
       call mckpp_hip_all_set_ancillary_series(MCKPP_ANC_SST0, 0, size(anc_sst, 2), anc_sst)
@@ -176,6 +189,16 @@ program kpp_driver
         call mckpp_hip_all_restart_snapshot_save(nt, trim(fout)//'.rst'//trim(snap_name))
       end do
       call mckpp_hip_all_restart_snapshot_release(snap_last)
+    else if (iand(flags, 8192 + 16384) == 8192 + 16384) then   ! the records through the ring, a pair per forced run
+      call mckpp_hip_all_flux_ring(2)
+      do r = 0, nrec - 1, 2
+        do i = r, min(r + 1, nrec - 1)   ! (but for the first pair: while the run before is queued)
+          call mckpp_hip_all_flux_ring_put(i, series(:, :, i + 1))
+        end do
+        call mckpp_hip_all_run_forced(2 * r + 1, min(4, nsteps - 2 * r), 2)
+      end do
+    else if (iand(flags, 8192) /= 0) then   ! ... and all of them resident
+      call mckpp_hip_all_run_forced(1, nsteps, 2)
     else
       call mckpp_hip_all_run_forced(1, nsteps, nsteps + 1)   ! one flux update (step 1), as ndtocn > nsteps
     end if

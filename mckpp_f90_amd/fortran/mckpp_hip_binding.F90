@@ -132,6 +132,26 @@ module mckpp_hip_binding
       real(c_double), intent(in) :: fields(*)
       integer(c_int) :: rc
     end function
+    ! the flux-record ring (src/mckpp_ocean_model_3D.F90:44-48, src/mckpp_fluxes_mod.F90:35-89): fields(npts, 8) per record
+    function mckpp_hip_flux_ring(handle, nslots) bind(C, name="mckpp_hip_flux_ring") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: nslots
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_flux_ring_put(handle, rec, fields) bind(C, name="mckpp_hip_flux_ring_put") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: rec
+      real(c_double), intent(in) :: fields(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_flux_ring_records(handle, first, last) bind(C, name="mckpp_hip_flux_ring_records") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), intent(out) :: first, last
+      integer(c_int) :: rc
+    end function
     function mckpp_hip_run_forced(handle, nt_first, nsteps, ndtocn, l_rest, flsn, el) &
         bind(C, name="mckpp_hip_run_forced") result(rc)
       import :: c_int, c_ptr, c_double
@@ -328,6 +348,25 @@ module mckpp_hip_binding
       type(c_ptr), value :: handle
       integer(c_int), value :: rec0, nrec
       real(c_double), intent(in) :: fields(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_flux_ring(handle, nslots) bind(C, name="mckpp_hip_multi_flux_ring") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: nslots
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_flux_ring_put(handle, rec, fields) bind(C, name="mckpp_hip_multi_flux_ring_put") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle
+      integer(c_int), value :: rec
+      real(c_double), intent(in) :: fields(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_flux_ring_records(handle, first, last) bind(C, name="mckpp_hip_multi_flux_ring_records") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), intent(out) :: first, last
       integer(c_int) :: rc
     end function
     function mckpp_hip_multi_run_forced(handle, nt_first, nsteps, ndtocn, l_rest, flsn, el) &

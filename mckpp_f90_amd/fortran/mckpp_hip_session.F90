@@ -22,6 +22,7 @@ module mckpp_hip_session
   public :: mckpp_hip_all_restart_schedule, mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
             mckpp_hip_all_restart_snapshot_release
   public :: mckpp_hip_all_step_log
+  public :: mckpp_hip_all_flux_ring, mckpp_hip_all_flux_ring_put
   public :: mckpp_hip_all_set_bottomtemp, mckpp_hip_bottomtemp_resident
   public :: mckpp_hip_all_set_ancillary_series, mckpp_hip_all_ancillary_schedule
   public :: mckpp_hip_all_save_restart, mckpp_hip_all_load_restart, mckpp_hip_sync_host, mckpp_hip_device_advanced
@@ -339,6 +340,26 @@ contains
     call mckpp_hip_check(mckpp_hip_multi_set_flux_series(mckpp_hip_multi_handle, int(rec0, c_int), int(nrec, c_int), fields), &
                          'mckpp_hip_multi_set_flux_series')
   end subroutine mckpp_hip_all_set_flux_series
+
+  !> The flux-record ring (mckpp_hip_flux_ring of include/mckpp_hip.h) on all devices: nslots record slots, empty;
+  !! 0 cancels it.  It takes the place of mckpp_hip_all_set_flux_series for a run whose forcing arrives while it runs
+  !! (src/mckpp_ocean_model_3D.F90:44-48): put the records of the next mckpp_hip_all_run_forced right after the current
+  !! one is queued.  The state goes to the devices first (the slots are sized to the resident columns).
+  subroutine mckpp_hip_all_flux_ring(nslots)
+    integer, intent(in) :: nslots
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_flux_ring(mckpp_hip_multi_handle, int(nslots, c_int)), 'mckpp_hip_multi_flux_ring')
+  end subroutine mckpp_hip_all_flux_ring
+
+  !> Record `rec` (from 0, in order) of the eight forcing fields, fields(npts, 8) in the order taux, tauy, swf, lwf, lhf,
+  !! shf, rain, snow - what kpp_3d_fields%taux .. snow hold after the flux reader (src/mckpp_fluxes_mod.F90:35-89) - into
+  !! its slot of the ring, without waiting for the devices: `fields` may be rewritten on return.
+  subroutine mckpp_hip_all_flux_ring_put(rec, fields)
+    integer, intent(in) :: rec
+    real(c_double), intent(in) :: fields(*)
+    call mckpp_hip_check(mckpp_hip_multi_flux_ring_put(mckpp_hip_multi_handle, int(rec, c_int), fields), &
+                         'mckpp_hip_multi_flux_ring_put')
+  end subroutine mckpp_hip_all_flux_ring_put
 
   !> With kpp_const_fields%L_VARY_BOTTOM_TEMP the run ends every step with mckpp_physics_overrides_bottomtemp, as the
   !! reference's driver does (src/mckpp_physics_driver_mod.F90:67-71): kpp_3d_fields%bottom_temp as it stands now becomes
