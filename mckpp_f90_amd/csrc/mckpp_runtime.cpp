@@ -673,11 +673,23 @@ static int upload_ancillaries(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, con
       (k.L_RELAX_SST && (!s->relax_sst || !s->SST0)) || (k.L_FCORR && !s->fcorr_twod) ||
       (k.L_RELAX_SAL && !s->relax_sal) || (k.L_RELAX_OCNT && !s->relax_ocnT))
     return fail("%s: a switch is on but the field it reads is a NULL pointer", who);
+  const int mm = k.maxmodeadv;
+  // the advection slots, checked before anything is copied: a refused call leaves the resident inputs as they were
+  for (int64_t c = 0; k.L_ADVECT && s->nmodeadv && c < ncol; ++c) {
+    const int64_t i = ipt[c];
+    const int nm = s->nmodeadv[i + npts * 1];   // nmodeadv(ipt,2)
+    if (nm < 0 || nm > mm) return fail("%s: nmodeadv(%lld,2)=%d outside 0..%d", who, (long long)i + 1, nm, mm);
+    for (int j = 0; j < nm; ++j) {   // a live slot above 7: the reference aborts (solvers.F90:320-323), the kernel would skip it
+      const int mode = s->modeadv ? s->modeadv[i + npts * (j + (int64_t)mm * 1)] : 0;   // modeadv(ipt,j+1,2)
+      if (mode > 7)
+        return fail("%s: modeadv(%lld,%d,2)=%d is no mode of rhsmod (1..7; 0 or less switches a slot off)", who,
+                    (long long)i + 1, j + 1, mode);
+    }
+  }
   if (s->fcorr_withz && up_rows(h, s->fcorr_withz, nzp1, h->d_ext_in[E_FCORR_WITHZ], 0)) return -1;
   if (s->sfcorr_withz && up_rows(h, s->sfcorr_withz, nzp1, h->d_ext_in[E_SFCORR_WITHZ], 0)) return -1;
   if (s->ocnT_clim && up_rows(h, s->ocnT_clim, nzp1, h->d_ext_in[E_OCNT_CLIM], 0)) return -1;
   if (s->sal_clim && up_rows(h, s->sal_clim, nzp1, h->d_ext_in[E_SAL_CLIM], 0)) return -1;
-  const int mm = k.maxmodeadv;
   std::vector<double> xs((size_t)ncol * MCKPP_XS, 0.0), ad((size_t)ncol * (mm + 1), 0.0);
   std::vector<int> ai((size_t)ncol * (mm + 1), 0);
   for (int64_t c = 0; c < ncol; ++c) {
@@ -688,9 +700,7 @@ static int upload_ancillaries(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, con
     x[XS_FCORR_TWOD] = s->fcorr_twod ? s->fcorr_twod[i] : 0.0;
     x[XS_RELAX_SAL] = s->relax_sal ? s->relax_sal[i] : 0.0;
     x[XS_RELAX_OCNT] = s->relax_ocnT ? s->relax_ocnT[i] : 0.0;
-    int nm = (k.L_ADVECT && s->nmodeadv) ? s->nmodeadv[i + npts * 1] : 0;   // nmodeadv(ipt,2)
-    if (nm < 0 || nm > mm) return fail("%s: nmodeadv(%lld,2)=%d outside 0..%d", who, (long long)i + 1, nm, mm);
-    ai[(size_t)c * (mm + 1)] = nm;
+    ai[(size_t)c * (mm + 1)] = (k.L_ADVECT && s->nmodeadv) ? s->nmodeadv[i + npts * 1] : 0;   // nmodeadv(ipt,2)
     for (int j = 0; j < mm; ++j) {
       ai[(size_t)c * (mm + 1) + 1 + j] = s->modeadv ? s->modeadv[i + npts * (j + (int64_t)mm * 1)] : 0;
       ad[(size_t)c * (mm + 1) + j] = s->advection ? s->advection[i + npts * (j + (int64_t)mm * 1)] : 0.0;

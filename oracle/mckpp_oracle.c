@@ -1015,8 +1015,8 @@ static void vmix(const orc_const *c, orc_col *q, int ntime, double *hmixn, int *
 }
 
 /* ------------------------------------------------------------------------
- * rhsmod (prescribed advection).  mckpp_physics_solvers.F90:176-335
- * ---------------------------------------------------------------------- */
+ * rhsmod (prescribed advection).  mckpp_physics_solvers.F90:176-335.  Mode 4's search for 100 m stops at nzi + 1, as
+ * the column kernel's: on a grid with no level below 100 m the reference reads past zm (no defined behaviour) ---- */
 static void rhsmod(const orc_const *c, orc_col *q, int jsclr, int mode, double A,
                    double dto, int km, double dm, int nzi, double *rhs)
 {
@@ -1039,7 +1039,7 @@ static void rhsmod(const orc_const *c, orc_col *q, int jsclr, int mode, double A
     for (int n = 1; n <= nzi; n++) { FACT(n); rhs[n] = rhs[n] + fact / delta; }
   } else if (mode == 4) {                                 /* :253-267 */
     int nzend = nzi - 1, n1 = 0;
-    do { n1 = n1 + 1; } while (c->zm[n1] >= -100.);
+    do { n1 = n1 + 1; } while (c->zm[n1] >= -100. && n1 < nzi + 1);
     delta = 0.0;
     for (int n = n1; n <= nzend; n++) delta = delta + hm[n];
     for (int n = n1; n <= nzend; n++) { FACT(n); rhs[n] = rhs[n] + fact / delta; }
@@ -1259,7 +1259,7 @@ static void ocnstep(const orc_const *c, orc_col *q, int ntime)
     for (int k = 1; k <= NZ; k++) {                       /* :201-207 */
       if (fabs(q->U[1][k]) >= 10 || fabs(q->U[2][k]) >= 10 ||
           fabs(q->X[1][k] - q->X[1][k + 1]) >= 10) {
-        q->paths |= (fabs(q->U[1][k]) >= 10 || fabs(q->U[2][k]) >= 10) ? ORC_PATH_TRAP_U : ORC_PATH_TRAP_TJUMP;
+        q->paths |= ORC_TRAP_PATHS(q->U[1][k], q->U[2][k]);
         q->comp_flag = 1;
         q->f = q->f * 1.01;
       }

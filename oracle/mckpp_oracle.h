@@ -60,6 +60,10 @@ extern "C" {
 #define ORC_PATH_ITER_DEEPER_AT_ITERMAX 0x1000  /* ocnstep :176-181: iterating on past itermax because hmixn > hmixe */
 #define ORC_PATH_DD_FINGER       0x2000  /* ddmix :31-36 at some level */
 #define ORC_PATH_DD_DIFFCONV     0x4000  /* ddmix :39-48 at some level */
+#define ORC_PATH_TRAP_V_ALONE    0x8000  /* ocnstep :202: |V| >= 10 at a level where |U| < 10 (the V half decides) */
+/* the bits of a level that trips ocnstep :201-207, given its U and V */
+#define ORC_TRAP_PATHS(u, v) ((fabs(u) >= 10 || fabs(v) >= 10) \
+    ? (ORC_PATH_TRAP_U | (fabs(u) < 10 ? ORC_PATH_TRAP_V_ALONE : 0)) : ORC_PATH_TRAP_TJUMP)
 
 typedef struct {
   int nz;               /* layers; nzp1 = nz + 1 grid points */

@@ -28,6 +28,9 @@ ST_ZERO_PIVOT, ST_LONG_ITER, ST_RETRIED, ST_FAILED, ST_DODGY = 1, 2, 4, 8, 16
 PATHS = {name: 1 << i for i, name in enumerate((
     "HBL_SEAFLOOR", "HBL_SECOND_MIN", "HBL_NO_HIT", "HBL_MONOB", "HBL_EKMAN", "HBL_RI", "TRAP_U", "TRAP_TJUMP",
     "TRAP_RMS_U", "TRAP_RMS_V", "TRAP_RMS_T", "TRAP_RMS_S", "ITER_DEEPER_AT_ITERMAX", "DD_FINGER", "DD_DIFFCONV"))}
+# ORC_PATH_TRAP_V_ALONE: the trap fired at a level on |V| >= 10 where |U| < 10.  Not in PATHS, which is the list the
+# seeded regime sweep has to take every member of.
+PATH_TRAP_V_ALONE = 1 << 15
 
 
 def build(force=False):

@@ -20,6 +20,8 @@ def grid_for(nz, kind="uniform"):
         return synth.stretched_grid(nz, 1000.0, 4.0)
     if kind == "thin":          # a 10 m column: a wind stress of a few N/m2 moves all of it by 1 m/s in a step
         return synth.uniform_grid(nz, 10.0)
+    if kind.startswith("uniform_"):     # uniform_<depth in m>: where the 100 m level of rhsmod's modes 4 and 7 falls
+        return synth.uniform_grid(nz, float(kind[len("uniform_"):]))
     raise ValueError(kind)
 
 

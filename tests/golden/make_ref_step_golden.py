@@ -15,6 +15,10 @@ portable exp, what the oracle's exp_mode=1 and the HIP kernel use):
   <case>/pexp/val/<field>    T, hmix, kmix after the last step in full (small cases), for the diagnosis of a mismatch
   fields                     the field names, in tests/ref_step_cases.py's STEP_FIELDS order
 Digests and values are taken after -0.0 -> +0.0 and NaN -> one NaN (tests/ref_step_cases.py: canonical).
+
+Every case is recorded anew, and every array the file already held has to come out byte for byte as it was: new cases
+are added to a record, they never move it.  A case whose inputs or expected outputs are meant to change is removed
+from the file first, by hand and for a stated reason.
 """
 import os
 import sys
@@ -44,6 +48,14 @@ def main():
                 out.update({f"{tag}/{b}/val/{k}": v for k, v in values.items()})
         print(tag, "recorded", flush=True)
     path = os.path.join(HERE, "ref_step.npz")
+    if os.path.exists(path):
+        with np.load(path) as old:
+            moved = [k for k in old.files if k not in out or out[k].dtype != old[k].dtype
+                     or out[k].shape != old[k].shape or out[k].tobytes() != old[k].tobytes()]
+            kept = len(old.files)
+        if moved:
+            raise SystemExit(f"{len(moved)} recorded arrays would change, the file is left as it was: {moved[:8]} ...")
+        print(f"all {kept} arrays of the existing record are byte-identical; {len(out) - kept} added")
     np.savez_compressed(path, **out)
     print(path, os.path.getsize(path), "bytes")
 

@@ -35,6 +35,7 @@ class Case:
     pre: Optional[Callable] = None          # (ncol, nzp1, ob) -> {field: array}, before init_ocean
     post: Optional[Callable] = None         # (ncol, nzp1, ob) -> {field: array}, after init_ocean
     stress: Optional[Callable] = None       # (ncol) -> (taux, tauy) in place of the bench mix's wind stress
+    surface: Optional[Callable] = None      # (sflux rows [ncol, 6]) -> None: edits the assembled forcing in place
     land_every: int = 0                     # run_physics = l_ocean = 0 on every land_every-th column
     jerlov_mix: bool = False
     diurnal: bool = False                   # short-wave follows the sun, step by step
@@ -248,6 +249,135 @@ def _sweep_trap(ncol, nzp1, ob):
     return {"U": U}
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# prescribed advection of salinity (rhsmod, src/mckpp_physics_solvers.F90:176-335; ocnint applies it whenever
+# nmodeadv(2) > 0, src/mckpp_physics_ocnint_mod.F90:179) and the switch pairs of ocnint of which one member is
+# silently ignored.  Closed forms of the column index, like the regimes.
+#
+# What the reference's declarations allow (src/mckpp_data_fields.F90:494-496: zm(nzp1), hm(nzp1), dm(0:nz); ocnint's
+# rhs(NZtmax) with NZtmax = nz + 1), and what the cases therefore may hold:
+#   km = kmixe comes from bldepth, which leaves kbl in 2 .. km = NZ (bldepth_mod.F90:101, :105, :183; kppmix hands it
+#   km = NZ).  So km = 1 cannot occur (no hm(0), no n1 = 0 in mode 7), and a mixed layer over the full depth is
+#   km = NZ: dm(NZ), hm(NZ), hm(NZ-1) are all inside.  ocnstep's `kmixn == NZP1` (ocnstep_mod.F90:158) can never be
+#   true for the same reason: no input reaches it, and no case is named after it.
+#   Modes 6 and 7 read hm(n+1) for n <= nzi = NZ: hm(nzp1), inside.  Mode 6 always meets dmax = dm(km) - (hm(km) +
+#   hm(km-1))/2 by n = km - 1 < nzi, its depth then being dm(km); it cannot run to nzi with km <= NZ.  Mode 7 runs
+#   to nzi on a grid shallower than 100 m, inside the arrays.
+#   Mode 4 looks for the first zm(n1) < -100 without a bound: on a grid with no level below 100 m (zm(nzp1) >= -100)
+#   it reads past zm(nzp1).  No recorded column has mode 4 on such a grid (adv_edges_90m leaves it out); the column
+#   kernel and the oracle stop the search at nzp1 and are compared there on the device alone.
+#   A mode above 7 aborts the reference (solvers.F90:320-323): none is recorded, the upload refuses it.
+# ---------------------------------------------------------------------------------------------------------------
+ADV0 = 2e-5     # PSU m/s; a step's change of S is dto * A * 0.033 / (the depth it is spread over)
+
+
+def advection_inputs(ncol, slots, index1=False):
+    """{nmodeadv, modeadv, advection} of a batch - (ncol, 2), (ncol, 2, 6), (ncol, 2, 6), [:, 1] being the
+    reference's index 2 (salinity), the only one it reads.  slots(c) -> (the modes of column c's slots, how many of
+    them nmodeadv(c,2) declares live); every slot given gets a magnitude of either sign, 1 ... 5 times ADV0, the dead
+    ones included.  index1: index 1 (temperature), which the reference never reads, holds live-looking values too."""
+    nm = np.zeros((ncol, 2), dtype=np.int32)
+    mode = np.zeros((ncol, 2, 6), dtype=np.int32)
+    adv = np.zeros((ncol, 2, 6))
+    for c in range(ncol):
+        modes, live = slots(c)
+        nm[c, 1] = live
+        for j, m in enumerate(modes):
+            mode[c, 1, j] = m
+            adv[c, 1, j] = ADV0 * (1 + (c + j) % 5) * (1 if (c + j) % 2 == 0 else -1)
+        if index1:
+            nm[c, 0] = 1 + c % 6
+            mode[c, 0, :] = 1 + (c + np.arange(6)) % 7
+            adv[c, 0, :] = 40.0 * (1 + np.arange(6)) * (1 if c % 2 else -1)
+    return {"nmodeadv": nm, "modeadv": mode, "advection": adv}
+
+
+def _adv_one_mode(ncol, nzp1, ob):
+    return advection_inputs(ncol, lambda c: ((1 + c % 7,), 1))
+
+
+# (modes of the slots, nmodeadv(2)): all six slots; a mode twice; a zero and a negative mode between live ones (the
+# reference returns at mode <= 0 and goes on with the next slot); nothing live with modes and magnitudes behind it;
+# the three modes whose range follows the mixed layer, twice; two live with more behind them; all six with holes
+ADV_PATTERNS = (((1, 2, 3, 4, 5, 6), 6), ((7, 7, 2), 3), ((6, 0, 3, -2, 7), 5), ((4, 5, 1), 0),
+                ((2, 6, 7, 2, 6, 7), 6), ((5, 3, 7, 1), 2), ((3, -1, 0, 5, 2, 4), 6))
+
+
+def _adv_patterns(ncol, nzp1, ob):
+    return advection_inputs(ncol, lambda c: ADV_PATTERNS[c % 7])
+
+
+def _adv_patterns_index1(ncol, nzp1, ob):
+    return advection_inputs(ncol, lambda c: ADV_PATTERNS[c % 7], index1=True)
+
+
+def _adv_patterns_scorr(ncol, nzp1, ob):
+    """the advection term and sinc_fcorr (L_SFCORR_WITHZ, L_RELAX_SAL) in one right-hand side"""
+    d = _adv_patterns(ncol, nzp1, ob)
+    z = np.arange(nzp1)[None, :]
+    d["sfcorr_withz"] = 1e-7 * np.cos(z / 7.0) * np.linspace(-1, 1, ncol)[:, None]
+    d["sal_clim"] = ob["S"][:, 1:nzp1 + 1] + 0.05
+    d["relax_sal"] = np.full(ncol, 1.0 / (15 * 86400.0))
+    return d
+
+
+def _cooling(sf):
+    """every column loses 400 W/m2 in the dark: with `isothermal` it convects as deep as its sea floor lets it"""
+    sf[:, 2] = 0.0
+    sf[:, 3] = -400.0
+    sf[:, 5] = 6e-5 - 400.0 / cm.synth.EL
+
+
+# -ocdepth of the edge columns on the 40-level grid (5 m levels, centres at 2.5, 7.5, ...): the sea floor makes
+# km = kmix the first level whose centre lies below it - 2, 3, 13, 20 (centre 97.5 m), 21 (102.5), 22, 31 - and the
+# last lets the column mix down to km = NZ
+ADV_EDGE_FLOORS = (2.0, 9.0, 60.0, 93.0, 100.0, 103.0, 150.0, 10000.0)
+ADV_EDGE_MODES = ((2,), (6,), (7,), (2, 6, 7))
+
+
+def _adv_edges(ncol, nzp1, ob):
+    """Eight mixed-layer depths times the modes whose range follows km - 2, 6, 7 alone and together - on convecting
+    isothermal columns: km = 2 (mode 2 over one level, mode 7 from level 1, mode 6 meeting dmax on its first level);
+    km = 20 and 21, 22 (just above and below 100 m: mode 7's first `depth >= dmax` is true at once) against km = 3
+    and 13 (true only after many levels); km = 31 and NZ (mode 6 meeting dmax deep)."""
+    d = _isothermal(ncol, nzp1, ob)
+    d["ocdepth"] = -np.resize(np.array(ADV_EDGE_FLOORS), ncol)
+    def slots(c):
+        modes = ADV_EDGE_MODES[(c // len(ADV_EDGE_FLOORS)) % len(ADV_EDGE_MODES)]
+        return modes, len(modes)
+    d.update(advection_inputs(ncol, slots))
+    return d
+
+
+def _adv_small_grid(modes):
+    def hook(ncol, nzp1, ob):
+        return advection_inputs(ncol, lambda c: ((modes[c % len(modes)], modes[(c + 3) % len(modes)]), 2))
+    return hook
+
+
+def _both(*hooks):
+    def hook(ncol, nzp1, ob):
+        d = {}
+        for h in hooks:
+            d.update(h(ncol, nzp1, ob))
+        return d
+    return hook
+
+
+def _trap_v(ncol, nzp1, ob):
+    """20 m/s northward in the four top levels of every fourth column, U as the generators leave it (5 cm/s)"""
+    V = ob["V"][:, 1:nzp1 + 1].copy()
+    V[::4, 0:4] = 20.0
+    return {"V": V}
+
+
+def _trap_v_clim(ncol, nzp1, ob):
+    d = _trap_v(ncol, nzp1, ob)
+    d["ocnT_clim"] = ob["T"][:, 1:nzp1 + 1] - 0.25
+    d["sal_clim"] = ob["S"][:, 1:nzp1 + 1] + 0.01
+    return d
+
+
 CASES = {
     "nz40": Case(32, 40, 3),
     "nz60_land_jerlov": Case(30, 60, 2, land_every=4, jerlov_mix=True),
@@ -287,16 +417,54 @@ CASES = {
     "ldd_diffconv_nz40": Case(24, 40, 3, switches=dict(LDD=1), pre=_diffconv),
     # ... and all of them side by side, seeded, under the bench forcing
     "regime_sweep_nz60": Case(400, 60, 4, switches=dict(LDD=1), pre=_sweep, post=_sweep_trap, jerlov_mix=True, full=False),
+    # prescribed advection: one mode a column over a widely spread mixed layer ...
+    "adv_modes_nz40": Case(49, 40, 3, switches=dict(L_ADVECT=1), pre=_adv_one_mode, stress=_stress_ramp),
+    # ... several slots a column at the depths that have kernels with the level count as a literal; its twin with
+    # live-looking values at index 1 (temperature), which the reference never reads ...
+    "adv_modes_nz60": Case(56, 60, 3, switches=dict(L_ADVECT=1), pre=_adv_patterns, land_every=4, jerlov_mix=True,
+                           stress=_stress_ramp),
+    "adv_modes_nz60_index1": Case(56, 60, 3, switches=dict(L_ADVECT=1), pre=_adv_patterns_index1, land_every=4,
+                                  jerlov_mix=True, stress=_stress_ramp),
+    "adv_modes_nz69_stretched": Case(56, 69, 4, grid="stretched", dto=1200.0, pre=_adv_patterns_scorr, land_every=5,
+                                     jerlov_mix=True, stress=_stress_ramp,
+                                     switches=dict(L_ADVECT=1, L_SFCORR_WITHZ=1, L_RELAX_SAL=1)),
+    # ... the edges of the level ranges: the mixed layer at chosen levels of the 40-level grid; 12-level grids whose
+    # first level below 100 m is NZ-1 (mode 4 over one level: 120 m), NZ (105 m) and NZP1 (102 m: both empty, n1 >
+    # nzend) ...
+    "adv_edges_nz40": Case(32, 40, 3, switches=dict(L_ADVECT=1), pre=_adv_edges, surface=_cooling),
+    "adv_edges_120m": Case(14, 12, 2, grid="uniform_120", switches=dict(L_ADVECT=1), pre=_adv_small_grid(range(1, 8))),
+    "adv_edges_105m": Case(14, 12, 2, grid="uniform_105", switches=dict(L_ADVECT=1), pre=_adv_small_grid(range(1, 8))),
+    "adv_edges_102m": Case(14, 12, 2, grid="uniform_102", switches=dict(L_ADVECT=1), pre=_adv_small_grid(range(1, 8))),
+    # ... a grid of 8 m levels, all of its arithmetic exact: the centre of level 13 lies AT 100 m (mode 4's `zm >= -100`
+    # goes on to level 14) and mode 7's running depth comes to 100 m exactly (`depth >= dmax` stops there) ...
+    "adv_edges_128m": Case(14, 16, 2, grid="uniform_128", switches=dict(L_ADVECT=1), pre=_adv_small_grid(range(1, 8))),
+    # ... and a 90 m grid, where mode 7 runs to nzi without meeting 100 m (no mode 4 there: see above)
+    "adv_edges_90m": Case(18, 12, 2, grid="uniform_90", switches=dict(L_ADVECT=1),
+                          pre=_adv_small_grid((1, 2, 3, 5, 6, 7))),
+    # the switch pairs of ocnint of which one member (or both) is silently ignored, inputs non-zero for both ...
+    "prec_relax_sst_fcorr_withz": Case(24, 40, 2, switches=dict(L_RELAX_SST=1, L_FCORR_WITHZ=1),
+                                       pre=_both(_relax_sst, _fcorr_withz)),
+    "prec_relax_sst_fcorr": Case(24, 40, 2, switches=dict(L_RELAX_SST=1, L_FCORR=1), pre=_both(_relax_sst, _fcorr_twod)),
+    "prec_fcorr_fcorr_withz": Case(24, 40, 2, switches=dict(L_FCORR=1, L_FCORR_WITHZ=1),
+                                   pre=_both(_fcorr_twod, _fcorr_withz)),
+    "prec_sfcorr_sfcorr_withz": Case(24, 40, 2, switches=dict(L_SFCORR=1, L_SFCORR_WITHZ=1), pre=_fcorr_withz),
+    "prec_relax_sst_fcorr_withz_relax_ocnt": Case(24, 40, 2, pre=_both(_relax_sst, _fcorr_withz, _relax_ocnt_sal),
+                                                  switches=dict(L_RELAX_SST=1, L_FCORR_WITHZ=1, L_RELAX_OCNT=1)),
+    # ... and the V half of the instability trap
+    "trap_v_nz40": Case(24, 40, 2, post=_trap_v),
+    "trap_v_clim_nz40": Case(24, 40, 2, switches=dict(clim_present=1), post=_trap_v_clim),
 }
 
 
 REGIME_CASES = [t for t in CASES if t.startswith(("seafloor_", "fulldepth_", "tjump_", "rms_retry_", "ssref0_",
                                                   "ldd_diffconv_", "regime_sweep_"))]
+ADVECTION_CASES = [t for t in CASES if t.startswith("adv_")]
+PRECEDENCE_CASES = [t for t in CASES if t.startswith("prec_")]
 
 
 def _apply_batch(ob, nzp1, d):
     for k, v in d.items():
-        if ob.a[k].ndim == 2 and k not in ("sflux", "hmixd"):
+        if k in orc.LEVEL_FIELDS:
             ob.a[k][:, 1:nzp1 + 1] = v
         else:
             ob[k] = v
@@ -311,6 +479,8 @@ def apply_hip(k3, d):
             getattr(k3, a)[:, :, l] = v
         elif k == "jerlov":
             k3.jerlov[:] = v
+        elif k in ("modeadv", "advection"):     # the batch's (ncol, 2, 6) on the reference's (npts, maxmodeadv, 2)
+            getattr(k3, k)[...] = np.asarray(v).transpose(0, 2, 1)
         else:
             getattr(k3, k)[...] = v
 
@@ -321,6 +491,8 @@ def forcing(case, step):
     sf = cm.synth.forcing(case.ncol, "bench", t_seconds=t)
     if case.stress:
         sf[:, 0], sf[:, 1] = case.stress(case.ncol)
+    if case.surface:
+        case.surface(sf)
     return sf
 
 
@@ -459,10 +631,10 @@ def hip_get(k3, nz):
     return get
 
 
-def run_hip(mk, tag, golden, solver_mode=0):
-    """The HIP kernel through the case from the same start, through the C-ABI as the parity tests drive it; returns
-    [(step, Kpp3dFields copy of the fields, plus the status words and pass counts)] after asserting that its starting state is the oracle's and that the
-    oracle's is the recorded one."""
+def start_hip(mk, tag, golden, solver_mode=0):
+    """The HIP side of a case at its start, through the C-ABI as the parity tests drive it: (KppConstFields,
+    Kpp3dFields, context, the oracle's Const and Batch at the same start), after asserting that the oracle's starting
+    state is the recorded one and that the HIP one is the oracle's."""
     case = CASES[tag]
     oc, ob, pre, post = oracle_start(case, exp_mode=1, solver_mode=solver_mode)
     assert np.array_equal(input_digest(ob), golden.input_sha(tag, "pexp")), \
@@ -478,6 +650,21 @@ def run_hip(mk, tag, golden, solver_mode=0):
     act = active_columns(case)
     init = cm.compare(k3, ob, case.nz, STEP_FIELDS, act)
     assert not {k: v for k, v in init.items() if v[2]}, f"HIP starting state differs from the oracle's: {init}"
+    return kc, k3, ctx, oc, ob
+
+
+def hip_fields(k3, ctx, nz):
+    """{field: array} of STEP_FIELDS as `mismatches` takes them, plus the status words and pass counts"""
+    got = {n: np.array(hip_get(k3, nz)(n)) for n in STEP_FIELDS}
+    got["status"], _, got["npasses"] = (np.array(a) for a in ctx.status())
+    return got
+
+
+def run_hip(mk, tag, golden, solver_mode=0):
+    """The HIP kernel through the case from the same start, a launch per step; returns [(step, {field: array} of
+    STEP_FIELDS, plus the status words and pass counts)]."""
+    case = CASES[tag]
+    kc, k3, ctx, oc, ob = start_hip(mk, tag, golden, solver_mode)
     if case.bottom_temp:
         kc.L_VARY_BOTTOM_TEMP = 1
         k3.bottom_temp[:] = bottom_temp(case, ob)
@@ -485,9 +672,7 @@ def run_hip(mk, tag, golden, solver_mode=0):
     for nt in range(1, case.nsteps + 1):
         cm.set_forcing_3d(k3, forcing(case, nt))
         ctx = mk.mckpp_physics_driver(k3, kc, nt)
-        got = {n: np.array(hip_get(k3, case.nz)(n)) for n in STEP_FIELDS}
-        got["status"], _, got["npasses"] = (np.array(a) for a in ctx.status())
-        out.append((nt, got))
+        out.append((nt, hip_fields(k3, ctx, case.nz)))
     return out
 
 

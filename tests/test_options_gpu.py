@@ -430,3 +430,174 @@ def test_switches_match_the_reference_step(mk, tag):
     for nt, got in rc.run_hip(mk, tag, golden):
         bad = rc.mismatches(case, golden.digests(tag, "pexp"), golden.values(tag), nt, got.__getitem__)
         assert not bad, f"{tag} step {nt}: HIP differs from the reference's own step: {bad}"
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# prescribed advection (tests/ref_step_cases.py, "prescribed advection"): the recorded cases through the other launch
+# forms, the ancillary update, and the two inputs the reference has no defined behaviour for
+# ---------------------------------------------------------------------------------------------------------------
+_VIEWS_FORCED = {"MCKPP_SOLO_AFTER": "0", "MCKPP_SOLO_LIMIT": "1000000"}
+_ADVECTION_FORMS = (
+    [(t, {}) for t in __import__("ref_step_cases").ADVECTION_CASES]           # all steps in one call
+    + [("adv_modes_nz40", {"MCKPP_MULTISTEP": "0"}),
+       ("adv_modes_nz60", {"MCKPP_PS_FIXED_L": "0"}),                         # the general kernel at 60 levels
+       ("adv_modes_nz69_stretched", {"MCKPP_PS_FIXED_L": "0"}),
+       ("adv_modes_nz60", _VIEWS_FORCED), ("adv_modes_nz69_stretched", _VIEWS_FORCED), ("adv_edges_nz40", _VIEWS_FORCED),
+       ("adv_edges_120m", {"MCKPP_PS": "21x4x1"}), ("adv_edges_90m", {"MCKPP_PS": "21x4x1"})])   # the most slots
+
+
+@pytest.mark.parametrize("tag,env", _ADVECTION_FORMS,
+                         ids=[f"{t}-{'-'.join(f'{k[6:]}={v}' for k, v in e.items()) or 'default'}" for t, e in _ADVECTION_FORMS])
+def test_advection_cases_through_the_launch_forms(mk, monkeypatch, tag, env):
+    """All steps of an advection case in ONE call - km = kmix moves between the steps inside the launch, and the
+    per-item range tests of the kernel's rhsmod have to follow it - against the reference's recorded last step: the
+    launcher's own choice, the general kernel where the depth has one with the level count as a literal, the forced
+    views, and a forced workgroup geometry of 21 slots."""
+    import ref_step_cases as rc
+
+    for k, v in env.items():
+        monkeypatch.setenv(k, v)
+    golden = rc.Golden()
+    case = rc.CASES[tag]
+    kc, k3, ctx, oc, ob = rc.start_hip(mk, tag, golden)
+    cm.set_forcing_3d(k3, rc.forcing(case, 1))      # (the advection cases' forcing is the same at every step)
+    ctx.set_forcing(k3.sflux)
+    ctx.step(1, case.nsteps)
+    ctx.download(k3)
+    got = rc.hip_fields(k3, ctx, case.nz)
+    if "MCKPP_PS" in env:
+        assert ctx.kernel_residency()[2] == 64 * int(env["MCKPP_PS"].split("x")[1])
+    bad = rc.mismatches(case, golden.digests(tag, "pexp"), golden.values(tag), case.nsteps, got.__getitem__)
+    assert not bad, f"{tag} {env}: HIP differs from the reference's own step {case.nsteps}: {bad}"
+
+
+@pytest.mark.parametrize("tag", ["adv_modes_nz40", "adv_modes_nz60", "adv_edges_nz40"])
+def test_advection_with_the_two_ended_solver(mk, tag):
+    """Solver mode 1 on the advection cases: within rounding of the recorded reference (the same mixed-layer index,
+    T and hmix as test_two_ended_solver_within_rounding_of_the_reference_step asks), and bit for bit the oracle's
+    restatement of that mode on every field, S among them."""
+    import ref_step_cases as rc
+
+    golden = rc.Golden()
+    case, ref = rc.CASES[tag], golden.values(tag)
+    act = rc.active_columns(case)
+    oc, ob, _, _ = rc.oracle_start(case, exp_mode=1, solver_mode=1)
+    for (nt, got), _ in zip(rc.run_hip(mk, tag, golden, solver_mode=1), rc.run_oracle(case, oc, ob)):
+        bad = [n for n in rc.STEP_FIELDS if not np.array_equal(
+            rc.canonical(got[n])[act].view(np.int64), rc.canonical(rc.field_of(ob, n, case.nz))[act].view(np.int64))]
+        assert not bad, f"{tag} solver 1 step {nt}: HIP differs from the oracle in {bad}"
+        assert np.array_equal(got["status"][act], ob["status"][act]) and np.array_equal(got["npasses"][act], ob["npasses"][act])
+    assert np.array_equal(got["kmix"][act], ref["kmix"])
+    assert np.allclose(got["hmix"][act], ref["hmix"], rtol=1e-10, atol=0)
+    assert np.abs(got["T"][act] - ref["T"]).max() <= 1e-10 * np.abs(ref["T"]).max()
+
+
+def _advection_prep(hook):
+    """prep(k3, ob) for _case: a hook of tests/ref_step_cases.py on both sides"""
+    import ref_step_cases as rc
+
+    def prep(k3, ob):
+        rc.apply_both(ob, k3, ob.nzp1, hook(k3.npts, ob.nzp1, ob))
+    return prep
+
+
+@pytest.mark.parametrize("nz", [150, 200])
+def test_advection_slot_patterns_where_a_slot_spans_several_wavefronts(mk, nz):
+    """The slot patterns of the recorded cases (all six slots, a mode twice, holes, dead slots) at depths where a
+    slot's items span two and three wavefronts, three steps against the oracle."""
+    import ref_step_cases as rc
+
+    k3, ob = _case(mk, 42, nz, dict(L_ADVECT=1), _advection_prep(rc._adv_patterns), nsteps=3)
+    assert len(set(ob["kmix"].tolist())) >= 3
+
+
+def test_update_ancillaries_with_other_advection_modes(mk):
+    """Modes and magnitudes change on the host between two steps (what an ancillary reader does): after
+    update_ancillaries the next step uses the new ones, bit for bit with the oracle, and the prognostic state is
+    untouched by the update itself."""
+    import ref_step_cases as rc
+    from oracle import orc
+
+    tag = "adv_modes_nz60"
+    golden = rc.Golden()
+    case = rc.CASES[tag]
+    act = rc.active_columns(case)
+    kc, k3, ctx, oc, ob = rc.start_hip(mk, tag, golden)
+    sf = rc.forcing(case, 1)
+    cm.set_forcing_3d(k3, sf)
+    ob["sflux"] = sf
+    ctx.set_forcing(k3.sflux)
+    ctx.step(1, 1)
+    orc.physics_driver(oc, ob, 1)
+    ctx.download(k3)
+    state = ("U", "X", "Us", "Xs", "hmix", "kmix", "hmixd", "Tref", "Ssurf", "old", "new_")
+    before = {n: np.array(getattr(k3, n), copy=True) for n in state}
+    new = rc.advection_inputs(case.ncol, lambda c: rc.ADV_PATTERNS[(c + 3) % 7])
+    new["advection"] = -1.5 * new["advection"]
+    rc.apply_both(ob, k3, case.nz + 1, new)
+    ctx.update_ancillaries(k3)
+    ctx.download(k3)
+    for n, v in before.items():
+        assert np.array_equal(getattr(k3, n), v), f"update_ancillaries changed {n}"
+    ctx.step(2, 1)
+    orc.physics_driver(oc, ob, 2)
+    ctx.download(k3)
+    st, _, npass = ctx.status()
+    assert np.array_equal(st[act], ob["status"][act]) and np.array_equal(npass[act], ob["npasses"][act])
+    bad = {k: v for k, v in cm.compare(k3, ob, case.nz, rc.STEP_FIELDS, act).items() if v[2] != 0}
+    assert not bad, f"step 2 after the update: {bad}"
+    got = rc.hip_fields(k3, ctx, case.nz)
+    assert "S" in rc.mismatches(case, golden.digests(tag, "pexp"), {}, 2, got.__getitem__), \
+        "step 2 is the recorded one of the old modes: the update never reached the kernel"
+
+
+@pytest.mark.parametrize("grid", ["uniform_90", "thin"])
+def test_mode_4_on_a_grid_shallower_than_100_m_is_a_no_op(mk, grid):
+    """rhsmod's mode 4 looks for the first level below 100 m without a bound (solvers.F90:258-259): on a grid that has
+    none, the reference reads past zm - it has NO DEFINED BEHAVIOUR for this input, and no such column is recorded.
+    The column kernel stops the search at nzp1 and adds nothing; the oracle has the same guard.  Device against
+    oracle, and against an oracle that was given no advection at all on the columns that have mode 4 alone."""
+    import ref_step_cases as rc
+    from oracle import orc
+
+    ncol, nz = 28, 12
+
+    def hook(n, nzp1, ob):       # mode 4 alone on the even columns, beside each of the others on the odd ones
+        return rc.advection_inputs(n, lambda c: ((4,), 1) if c % 2 == 0 else ((4, 1 + c % 7, 4), 3))
+    k3, ob = _case(mk, ncol, nz, dict(L_ADVECT=1), _advection_prep(hook), nsteps=2, grid=grid)
+    oc, plain = cm.make_oracle(ncol, nz, init=False, exp_mode=1, grid=grid)
+    orc.init_ocean(oc, plain, 0)
+    plain["sflux"] = cm.synth.forcing(ncol, "bench")
+    for nt in (1, 2):
+        orc.physics_driver(oc, plain, nt)
+    assert np.array_equal(np.asarray(k3.X)[0::2, :, 1], plain["S"][0::2, 1:nz + 2])
+    assert not np.array_equal(np.asarray(k3.X)[1::2, :, 1], plain["S"][1::2, 1:nz + 2])
+
+
+def test_an_advection_mode_above_7_is_refused(mk):
+    """The reference aborts on a live slot whose mode is above 7 (solvers.F90:320-323); the kernel would skip it in
+    silence.  The upload and update_ancillaries refuse it, naming the point and the slot; a slot behind nmodeadv may
+    hold anything; a good upload afterwards runs to the recorded state."""
+    import ref_step_cases as rc
+
+    tag = "adv_edges_120m"
+    golden = rc.Golden()
+    case = rc.CASES[tag]
+    kc, k3, ctx, oc, ob = rc.start_hip(mk, tag, golden)
+    good = np.array(k3.modeadv, copy=True)
+    k3.modeadv[5, 1, 1] = 8                      # point 6, slot 2 of nmodeadv(6,2) = 2
+    with pytest.raises(mk.MckppHipError, match=r"mckpp_hip_upload: modeadv\(6,2,2\)=8 "):
+        ctx.upload(k3)
+    with pytest.raises(mk.MckppHipError, match=r"mckpp_hip_update_ancillaries: modeadv\(6,2,2\)=8 "):
+        ctx.update_ancillaries(k3)
+    k3.modeadv[...] = good
+    k3.modeadv[5, 2, 1] = 8                      # behind the live slots: ignored by the reference, accepted here
+    ctx.upload(k3)
+    for nt in range(1, case.nsteps + 1):
+        cm.set_forcing_3d(k3, rc.forcing(case, nt))
+        ctx.set_forcing(k3.sflux)
+        ctx.step(nt, 1)
+        ctx.download(k3)
+        bad = rc.mismatches(case, golden.digests(tag, "pexp"), golden.values(tag), nt,
+                            rc.hip_fields(k3, ctx, case.nz).__getitem__)
+        assert not bad, f"{tag} step {nt} after the refused uploads: {bad}"

@@ -10,6 +10,8 @@ functions (ddmix ... check_profile) that were never taken, with their source tex
            sweep of shapes and forcings, the two-ended-solver depths, and the cases of tests/ref_step_cases.py that
            are not regime cases (without the 2000-column one)
   after    the same plus the regime cases (rc.REGIME_CASES)
+  pinned   the same plus the advection, precedence and trap_v cases (rc.ADVECTION_CASES, rc.PRECEDENCE_CASES, trap_v_*):
+           every input of this phase is also run through the reference's own compiled step
 
     python tools/oracle_coverage.py > profiles/coverage/oracle_branches.md
 
@@ -21,6 +23,7 @@ import sys
 import tempfile
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+PHASES = ("before", "after", "pinned")
 FIRST = "static void ddmix("      # the physics: from ddmix to the end of check_profile
 
 
@@ -66,7 +69,11 @@ def drive(phase):
                 sf[:, 5] += r2.uniform(-1e-4, 1e-4, ncol)
                 ob["sflux"] = sf
                 orc.physics_driver(oc, ob, nt)
-    tags = [t for t in rc.CASES if (t in rc.REGIME_CASES) == (phase == "after") and rc.CASES[t].ncol < 2000]
+    def phase_of(t):
+        if t in rc.REGIME_CASES:
+            return "after"
+        return "pinned" if t in rc.ADVECTION_CASES + rc.PRECEDENCE_CASES or t.startswith("trap_v_") else "before"
+    tags = [t for t in rc.CASES if phase_of(t) == phase and rc.CASES[t].ncol < 2000]
     for tag in tags:
         case = rc.CASES[tag]
         oc, ob, _, _ = rc.oracle_start(case, exp_mode=1)
@@ -110,20 +117,47 @@ def main():
         subprocess.check_call(["gcc", "--coverage", "-shared", "-o", lib, "mckpp_oracle.o", "-lm"], cwd=tmp)
         env = dict(os.environ, MCKPP_ORACLE_LIBRARY=lib)
         seen = {}
-        for phase in ("before", "after"):       # the counts of `after` add to those of `before`
+        for phase in PHASES:       # the counts of a phase add to those of the phases before it
             subprocess.check_call([sys.executable, os.path.abspath(__file__), "--drive", phase], env=env,
                                   stdout=subprocess.DEVNULL, stderr=subprocess.DEVNULL)
             seen[phase] = untaken(tmp)
+    def total(phase):
+        return f"{sum(len(b) for _, _, b in seen[phase])} branches on {len(seen[phase])} lines"
+
     print("# Branches of the oracle's physics that the suite's inputs never take\n")
     print("Made by `tools/oracle_coverage.py` (gcc --coverage, gcov -b -c; line numbers of oracle/mckpp_oracle.c, from")
     print("ddmix to check_profile; a line with several conditions has several branches).  *Before*: the generators'")
-    print("inputs and the cases of tests/ref_step_cases.py other than the regime cases.  *After*: with the regime cases.\n")
-    print(f"Untaken before: {sum(len(b) for _, _, b in seen['before'])} branches on {len(seen['before'])} lines; "
-          f"after: {sum(len(b) for _, _, b in seen['after'])} on {len(seen['after'])}.\n")
-    print("| line | source | untaken before | after |\n|---|---|---|---|")
+    print("inputs and the cases of tests/ref_step_cases.py other than the regime cases.  *After*: with the regime cases.")
+    print("*Pinned*: with the advection, precedence and trap_v cases, all of them recorded from the reference's own step.\n")
+    print(f"Untaken before: {total('before')}; after: {total('after')}; pinned: {total('pinned')}.\n")
+    print("| line | source | untaken before | after | pinned |\n|---|---|---|---|---|")
     for ln, text, br in seen["before"]:
-        left = [b for l2, _, b2 in seen["after"] if l2 == ln for b in b2]
-        print(f"| {ln} | `{text.replace('|', chr(92) + '|')}` | {br} | {'taken' if not left else left} |")
+        left = {ph: [b for l2, _, b2 in seen[ph] if l2 == ln for b in b2] for ph in PHASES[1:]}
+        cells = " | ".join("taken" if not left[ph] else str(left[ph]) for ph in PHASES[1:])
+        print(f"| {ln} | `{text.replace('|', chr(92) + '|')}` | {br} | {cells} |")
+    print(NOTES)
+
+
+NOTES = """
+## What is left of rhsmod and of the precedence conditions, and why
+
+- `FACT(n)` (1030, 1035, 1039, 1045, 1047, 1077): two branches each are `jsclr == 1` true and `jsclr == 2` false.  The
+  reference's ocnint calls rhsmod for salinity alone (`jsclr = 2`, src/mckpp_physics_ocnint_mod.F90:182), and so does
+  the oracle's: no input reaches them.
+- 1042, the guard `n1 < nzi + 1` of mode 4's search: false only on a grid with no level below 100 m, where the
+  reference reads past `zm` (src/mckpp_physics_solvers.F90:258-259).  The only input that reaches the branch is out
+  of bounds in the reference, so it is not recorded; the device and the oracle are compared on it
+  (tests/test_options_gpu.py, test_mode_4_on_a_grid_shallower_than_100_m_is_a_no_op).
+- 1057 and 1068, the loops of modes 6 and 7 ending at nzi: mode 7 does (a 90 m grid); mode 6 cannot with km <= NZ,
+  it meets dmax by n = km - 1 (tests/ref_step_cases.py, "prescribed advection").
+- 1063, `mode == 7` false, which is a mode above 7: the reference aborts (solvers.F90:320-323), so none is recorded;
+  the upload refuses such a mode (test_an_advection_mode_above_7_is_refused).
+- 1237, `kmixn == NZP1`: bldepth leaves kbl in 2 .. NZ (bldepth_mod.F90:101-183 with km = NZ), so no input makes it
+  true, in the reference or here.
+- 1025 `mode <= 0`, 1120, 1129, 1132, 1151, 1158 and the V half of 1260 are taken by the pinned cases.
+- The totals of *before* and *after* are three above those of the record made before the pinned cases (96 and 89):
+  the guard gave line 1042 two more branches, the bit for the V half gave 1262 one more.
+"""
 
 
 if __name__ == "__main__":
