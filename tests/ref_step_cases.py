@@ -378,6 +378,293 @@ def _trap_v_clim(ncol, nzp1, ob):
     return d
 
 
+# ---------------------------------------------------------------------------------------------------------------
+# the edge cases: inputs that put a comparison of the step AT equality (tools/oracle_boundaries.py,
+# profiles/coverage/oracle_boundaries.md).  The columns of a case come in triples (below, at, above): three columns
+# alike in every input - profiles, Coriolis parameter, forcing - but the one that controls the comparison, which the
+# middle column has at the compared value and the outer two one np.nextafter to either side of it (where one ulp of
+# the input is lost before it reaches the comparison, the smallest step that is not; said at the hook).  Plain columns
+# stand beside them.  EDGE_TRIPLES[tag] lists the triples of a case; a lost equality makes two columns of one alike.
+# ---------------------------------------------------------------------------------------------------------------
+def _state(ob, nzp1):
+    """{T, S, U, V, f} of a batch before init_ocean, for the edge hooks to edit in place"""
+    T, S, U, V = _profiles(ob, nzp1)
+    return {"T": T, "S": S, "U": U, "V": V, "f": ob["f"].copy()}
+
+
+def triples(first, n):
+    return [(first + 3 * j, first + 3 * j + 1, first + 3 * j + 2) for j in range(n)]
+
+
+def _alike(d, trio):
+    """the outer columns of a triple take the middle one's inputs"""
+    lo, eq, hi = trio
+    for v in d.values():
+        v[lo] = v[eq]
+        v[hi] = v[eq]
+
+
+def _around(x):
+    return np.nextafter(x, -np.inf), x, np.nextafter(x, np.inf)
+
+
+def _dd_edges(d, first, k):
+    """Three triples from column `first`, LDD: salinity bit-equal at the levels k+1 and k+2 (Fortran), betaDS = 0
+    there, with temperature falling with depth across them (alphaDT > 0: ddmix's `betaDS > 0.` of the salt-finger arm,
+    ddmix_mod.F90:32) and rising by half a kelvin (alphaDT < 0: `betaDS < 0.0` of the diffusive-convection arm, :40);
+    the outer columns have S(k+2) one ulp either side.  The third triple has T and S both bit-equal at the two levels:
+    dbloc = 0 and Rig = 0 exactly, z121's `V < vlo` with vlo = 0 (z121_mod.F90:28); one ulp of T does not move
+    sigma0, so its outer columns have T(k+2) 64 ulps either side."""
+    out = triples(first, 3)
+    for j, trio in enumerate(out):
+        _alike(d, trio)
+        T, S = d["T"], d["S"]
+        if j == 1:
+            for c in trio:
+                T[c, k + 1:] += 0.5
+        if j < 2:
+            for c, s in zip(trio, _around(S[trio[1], k])):
+                S[c, k + 1] = s
+        else:
+            t = T[trio[1], k]
+            for c, n in zip(trio, (-64, 0, 64)):
+                S[c, k + 1] = S[c, k]
+                T[c, k + 1] = t + n * np.spacing(t)
+    return out
+
+
+RELAX_EDGE = 1.e-10      # ocnint's `relax_sst .gt. 1.e-10` (ocnint_mod.F90:98)
+
+
+def _relax_edges(d, ob, first, ncol):
+    """Two triples from column `first`, L_RELAX_SST: relax_sst at 1.e-10 and one ulp either side; 1/(5 days) on the
+    other columns, none on every fourth"""
+    r = np.full(ncol, 1.0 / (5 * 86400.0))
+    r[::4] = 0.0
+    out = triples(first, 2)
+    for trio in out:
+        _alike(d, trio)
+        r[list(trio)] = _around(RELAX_EDGE)
+    d["relax_sst"] = r
+    d["SST0"] = d["T"][:, 0] + 1.5
+    return out
+
+
+def _ldd_equal(ncol, nzp1, ob):
+    d = _state(ob, nzp1)
+    _dd_edges(d, 3, nzp1 // 3)
+    return d
+
+
+def _relax_edge(ncol, nzp1, ob):
+    d = _state(ob, nzp1)
+    _relax_edges(d, ob, 3, ncol)
+    return d
+
+
+def _some_bathymetry(ncol, nzp1, ob):
+    """a sea floor between 3 and 40 m under every third column: hbl is -ocdepth pass after pass, hmixn == hmixe"""
+    return {"ocdepth": bathymetry(ncol, 3.0, 40.0, every=3)}
+
+
+ZERO_FLUX_STEP = 1e-300    # W/m2: one ulp from zero is a subnormal that the division by rho cp flushes to zero
+
+
+def _zero_flux_columns(ncol, nzp1, ob):
+    """Two triples from column 3, alike in all but the non-solar heat flux (_zero_flux): the second is a column of
+    -1.8 degC and one salinity at every level (L_NO_FREEZE's `X < -1.8`, overrides.F90:87; with L_NO_ISOTHERM and
+    iso_thresh = 0, `ABS(dtdz_total) < iso_thresh` at 0, :112)"""
+    d = _state(ob, nzp1)
+    d["ocdepth"] = np.full(ncol, -10000.0)
+    for j, trio in enumerate(triples(3, 5)):
+        eq = trio[1]
+        if j == 1:
+            d["T"][eq, :], d["S"][eq, :] = -1.8, 0.0
+        if j >= 2:
+            d["T"][eq, :], d["S"][eq, :], d["f"][eq] = 15.0, 0.0, EKMAN_F
+        _alike(d, trio)
+        if j == 2:
+            d["ocdepth"][list(trio)] = [-x for x in _around(7.5)]
+        if j == 3:
+            d["ocdepth"][list(trio)] = -7.0
+            d["f"][list(trio)] = _around(EKMAN_F_EDGE)
+    d["ocnT_clim"] = 5.0 + 0 * d["T"]
+    d["sal_clim"] = 0.1 + 0 * d["S"]
+    return d
+
+
+# Coriolis parameters of the Ekman triples (60 N; 1 / s) and the wind stress over them (N/m2): hekman = 0.7 ustar / (|f| +
+# 1e-16) is 1.7 m at EKMAN_F and, bit for bit, 2.5 m - the centre of level 1 of the 40-level grid - at EKMAN_F_EDGE
+EKMAN_F = float(cm.synth.coriolis(60.0))
+EKMAN_F_EDGE = 8.740752130227744e-05
+EKMAN_STRESS = 1e-4
+# wind stress and heating (W/m2) under which the Monin-Obukhov depth ustar^3 / vonk / (bfsfc + 1e-16) over the uniform
+# water of those triples is 7.5 m, the centre of level 2, bit for bit
+MONOB_STRESS, MONOB_HEAT = 0.02, 55.73046706341893
+
+
+def _zero_flux(sf):
+    """No solar, no heat, no ice melt, no fresh water on the middle columns: the surface buoyancy flux is exactly zero
+    (wscale's `zehat <= zmax` at zehat = 0, wscale_mod.F90:63; bfsfc = 0 in bldepth, blmix and `stable`); -1e-300 and
+    +1e-300 W/m2 of heat on the outer ones of the first two triples, under a stress of 0.3 N/m2 on the first (the
+    boundary layer ends where the bulk Richardson number says, which the velocity scales enter).
+    The third and fourth triples have no buoyancy flux on any column and a light wind over uniform water: the Ekman
+    depth, 1.7 m, is the shallowest limit and lies above the centre of level 1, so bldepth takes its second minimum,
+    without the Ekman depth (bldepth_mod.F90:173-180).  Third: that minimum is the sea floor at 7.5 m, the centre of
+    level 2 (`hmin2 < -zm(kl)` at equality), 7.5 m -+ one ulp on the outer columns.  Fourth: the Coriolis parameter
+    puts the Ekman depth itself at 2.5 m, the centre of level 1 (`hmin < -zm(kl-1)` at equality), over a sea floor at
+    7 m; f one ulp either side on the outer columns.  The fifth is heated under a wind of 0.02 N/m2: the Monin-Obukhov
+    depth is 7.5 m (`dmo(ku) <= -zm(kl)` at equality, bldepth_mod.F90:148), the heating one ulp either side."""
+    for j, trio in enumerate(triples(3, 5)):
+        for c, q in zip(trio, (-ZERO_FLUX_STEP, 0.0, ZERO_FLUX_STEP)):
+            sf[c] = sf[trio[1]]
+            sf[c, 2:6] = 0.0
+            if j < 2:
+                sf[c, 3] = q
+            if j == 0:
+                sf[c, 0] = 0.3
+            if j >= 2:
+                sf[c, 0:2] = EKMAN_STRESS, 0.0
+        if j == 4:
+            sf[list(trio), 0] = MONOB_STRESS
+            sf[list(trio), 3] = _around(MONOB_HEAT)
+
+
+def _mixed_edges(ncol, nzp1, ob):
+    """the double-diffusion and the relaxation triples side by side, over some bathymetry (the 60- and 69-level
+    cases: the kernels with the level count as a literal, workgroups of more than one slot)"""
+    d = _state(ob, nzp1)
+    _dd_edges(d, 3, nzp1 // 3)
+    _relax_edges(d, ob, 12, ncol)
+    floor = np.arange(18, ncol, 3)
+    d["ocdepth"] = np.full(ncol, -10000.0)
+    d["ocdepth"][floor] = -np.linspace(3.0, 40.0, len(floor))
+    return d
+
+
+def _retry_columns(ncol, nzp1, ob):
+    """every column the same closed form at 30 S, moving at 2 m/s in U and V (as _moving): the wind stress alone
+    decides how many tries of ocnstep's trap a column takes"""
+    k = np.arange(nzp1)[None, :] + np.zeros((ncol, 1))
+    return {"T": 20.0 - 0.01 * k, "S": 0.001 * k, "U": 2.0 + 0 * k, "V": 2.0 + 0 * k,
+            "f": np.full(ncol, float(cm.synth.coriolis(-30.0)))}
+
+
+# Values at which a quantity at the end of a rounding chain meets its threshold bit for bit, each found by bisecting
+# the oracle on the input named, over a few hundred second inputs an ulp apart, until one of them landed on equality.
+# tests/test_boundaries_cpu.py fails when generator drift takes a column off its equality.
+EXACT_K = 13                                   # the levels EXACT_K + 1 and EXACT_K + 2 (Fortran)
+EXACT_FINGER = (198, 0.0034566584223760426)    # T(k) raised by 198 ulps; S(k) - S(k+1): alphaDT == betaDS > 0
+EXACT_DIFFCONV = (39, 0.0034885944406148387)   # likewise, S(k+1) - S(k): alphaDT == betaDS < 0
+EXACT_RIG = (222, 0.014424298321962993)        # U(k) - U(k+1): Rig == Riinfty = 0.8
+EXACT_RMS = (9, 4.6370233105856125)            # T raised by 9e-3 K; taux: the rms change of U over a step == 1 m/s
+EXACT_U10 = 9.999693559642605                  # U at every level: U(1) == 10 m/s after a step under 1e-4 N/m2
+EXACT_V10 = 9.999999999999998                  # V at every level: V(k) == 10 m/s after a step
+EXACT_T10 = 10.0187298883641                   # a temperature step at 40 m: T(8) - T(9) == 10 K after a step
+
+
+def _exact_edges(ncol, nzp1, ob):
+    """Three triples from column 3 on the closed-form columns of _retry_columns, LDD: ddmix's `alphaDT > betaDS`
+    (ddmix_mod.F90:32) and `alphaDT < betaDS` (:41) with both sides equal, and rimix's Rig equal to Riinfty, z121's
+    `V > vhi` (z121_mod.F90:28), among levels whose Rig is near 0.25.  The outer columns have S(k+1) (U(k+1)) one ulp
+    either side."""
+    d = _retry_columns(ncol, nzp1, ob)
+    K = EXACT_K
+    k = np.arange(nzp1)
+    ulp = np.spacing(20.0)
+    for j, (lo, eq, hi) in enumerate(triples(3, 3)):
+        trio = [lo, eq, hi]
+        n, p = (EXACT_FINGER, EXACT_DIFFCONV, EXACT_RIG)[j]
+        sgn = -1.0 if j == 1 else 1.0
+        if j < 2:
+            d["S"][trio] = -sgn * d["S"][trio]
+            d["T"][trio] = 20.0 + sgn * (d["T"][trio] - 20.0)
+        else:
+            d["U"][trio] = np.where(k == K, 0.5 - 0.01 * K, (0.5 - 0.01 * K) - 0.025 * (k - K))
+            d["V"][trio] = 0.0
+        d["T"][trio, K] = d["T"][trio, K] + np.arange(512)[n] * ulp
+        name = "S" if j < 2 else "U"
+        d[name][trio, K + 1] = _around(d[name][eq, K] - sgn * p)
+    return d
+
+
+def _trap_uv_columns(ncol, nzp1, ob):
+    """Two triples from column 3: no Coriolis term, no buoyancy flux, 1e-4 N/m2 of wind over a uniform current of
+    EXACT_U10 in U (the second: EXACT_V10 in V), 0.25 m/s in the other component: after the step the largest |U|
+    (|V|) of the column is 10 m/s bit for bit, the trap's `>= 10` at equality (ocnstep_mod.F90:202); the current one
+    ulp either side on the outer columns.  f = 0 is an input the reference's step takes like any other; its own
+    geography never yields it (the Coriolis parameter is that of 2.5 degrees inside 2.5 degrees of the equator)."""
+    d = _retry_columns(ncol, nzp1, ob)
+    for j, trio in enumerate(triples(3, 2)):
+        for c, q in zip(trio, _around((EXACT_U10, EXACT_V10)[j])):
+            d["f"][c] = 0.0
+            d["U" if j == 0 else "V"][c] = q
+            d["V" if j == 0 else "U"][c] = 0.25
+    return d
+
+
+def _trap_t_columns(ncol, nzp1, ob):
+    """One triple from column 3: likewise at rest, a temperature step of EXACT_T10 down between levels 8 and 9: after
+    the step T(8) - T(9) is 10 K bit for bit (ocnstep_mod.F90:203)"""
+    d = _retry_columns(ncol, nzp1, ob)
+    for c, q in zip((3, 4, 5), _around(EXACT_T10)):
+        d["f"][c] = 0.0
+        d["U"][c], d["V"][c] = 0.0, 0.0
+        d["T"][c, 8:] -= q
+    # and a column at rest but for 15 m/s at level NZ and below it: the deepest level the trap looks at is the only
+    # one past 10 m/s after the step (the bound of its loop, ocnstep_mod.F90:201)
+    d["f"][8], d["U"][8], d["V"][8] = 0.0, 0.0, 0.0
+    d["U"][8, nzp1 - 2:] = 15.0
+    return d
+
+
+def _light_wind(first, n):
+    def stress(ncol):
+        taux = np.full(ncol, 0.01)
+        taux[first:first + 3 * n] = 1e-4
+        return taux, np.zeros(ncol)
+    return stress
+
+
+def _no_buoyancy(sf):
+    """no solar, no heat, no ice melt, no fresh water: the wind alone works on the column"""
+    sf[:, 2:6] = 0.0
+
+
+RETRY_ON_THE_BOUND, RETRY_PAST_THE_BOUND = 20, 22
+
+
+def _retry_stress(ncol):
+    """4.60, 4.61, ... N/m2 eastward: on the 10 m grid at 30 S the rms change of U is 1 m/s near 4.64 N/m2, and every
+    retry's f * 1.01 takes the Coriolis term further against the stress: each 0.02 N/m2 more costs one more try.
+    Column 20 (4.80) is accepted on its 10th try, reset_flag = comp_iter_max (`reset_flag > comp_iter_max` at
+    equality, ocnstep_mod.F90:229); column 22 (4.82) is still trapped on its 11th and fails, one past it."""
+    return 4.6 + 0.01 * np.arange(ncol), np.zeros(ncol)
+
+
+def _retry_and_rms_columns(ncol, nzp1, ob):
+    """_retry_columns; the columns 0, 1, 2 a little warmer: the triple of the rms threshold (_rms_edge)"""
+    d = _retry_columns(ncol, nzp1, ob)
+    d["T"][0:3] = d["T"][0:3] + 1e-3 * EXACT_RMS[0]
+    return d
+
+
+def _rms_edge(sf):
+    """columns 0, 1, 2 under column 0's heat and fresh water and a stress of EXACT_RMS[1] and one ulp either side: the
+    rms change of U over the step is 1 m/s bit for bit on column 1 (`rmsd >= rmsd_threshold`, ocnstep_mod.F90:222)"""
+    for c, q in zip((0, 1, 2), _around(EXACT_RMS[1])):
+        sf[c] = sf[0]
+        sf[c, 0] = q
+
+
+def _alike_forcing(first, n):
+    def hook(sf):
+        for lo, eq, hi in triples(first, n):
+            sf[lo] = sf[eq]
+            sf[hi] = sf[eq]
+    return hook
+
+
 CASES = {
     "nz40": Case(32, 40, 3),
     "nz60_land_jerlov": Case(30, 60, 2, land_every=4, jerlov_mix=True),
@@ -453,6 +740,29 @@ CASES = {
     # ... and the V half of the instability trap
     "trap_v_nz40": Case(24, 40, 2, post=_trap_v),
     "trap_v_clim_nz40": Case(24, 40, 2, switches=dict(clim_present=1), post=_trap_v_clim),
+    # the edge cases: comparisons AT equality, the two neighbours beside them (EDGE_TRIPLES) ...
+    "edge_ldd_equal_nz40": Case(24, 40, 2, switches=dict(LDD=1), pre=_ldd_equal, surface=_alike_forcing(3, 3)),
+    "edge_relax_sst_nz40": Case(24, 40, 2, switches=dict(L_RELAX_SST=1), pre=_relax_edge, surface=_alike_forcing(3, 2)),
+    "edge_zero_flux_nz40": Case(24, 40, 3, switches=dict(L_NO_FREEZE=1, L_NO_ISOTHERM=1, iso_thresh=0.0),
+                                pre=_zero_flux_columns, surface=_zero_flux),
+    # ... the integer counters of ocnstep: with itermax = 3 a column that does not deepen leaves the iteration at
+    # iter = itermax + 1 (`iter > itermax + 1` at equality), one that deepens once leaves one past it; over a sea
+    # floor hmixn == hmixe (`hmixn > hmixe`), and with hmixtolfrac = 0 that is `|hmixn - hmixe| > tol` at 0 = 0 ...
+    "edge_itermax3_nz40": Case(30, 40, 4, switches=dict(itermax=3), pre=_some_bathymetry, diurnal=True),
+    "edge_tol0_seafloor_nz40": Case(30, 40, 2, switches=dict(hmixtolfrac=0.0, itermax=8), pre=_some_bathymetry),
+    "edge_retry_count_thin": Case(24, 12, 2, grid="thin", pre=_retry_and_rms_columns, stress=_retry_stress,
+                                  surface=_rms_edge),
+    # ... quantities at the end of a rounding chain, met bit for bit (EXACT_*): alphaDT == betaDS of either sign and
+    # Rig == Riinfty; the trap's 10 m/s in U and in V, and its 10 K between two levels ...
+    "edge_exact_dd_rig_nz40": Case(24, 40, 2, switches=dict(LDD=1), pre=_exact_edges, surface=_alike_forcing(3, 3)),
+    "edge_trap_uv_thin": Case(24, 12, 2, grid="thin", pre=_trap_uv_columns, stress=_light_wind(3, 2),
+                              surface=_no_buoyancy),
+    "edge_trap_tjump_nz40": Case(12, 40, 2, pre=_trap_t_columns, stress=_light_wind(3, 1), surface=_no_buoyancy),
+    # ... and several of them side by side at the depths that have kernels with the level count as a literal
+    "edge_mixed_nz60": Case(48, 60, 3, switches=dict(LDD=1, L_RELAX_SST=1, itermax=3), pre=_mixed_edges,
+                            surface=_alike_forcing(3, 5), jerlov_mix=False),
+    "edge_mixed_nz69_stretched": Case(48, 69, 3, grid="stretched", dto=1200.0, pre=_mixed_edges,
+                                      switches=dict(LDD=1, L_RELAX_SST=1, itermax=3), surface=_alike_forcing(3, 5)),
 }
 
 
@@ -460,6 +770,21 @@ REGIME_CASES = [t for t in CASES if t.startswith(("seafloor_", "fulldepth_", "tj
                                                   "ldd_diffconv_", "regime_sweep_"))]
 ADVECTION_CASES = [t for t in CASES if t.startswith("adv_")]
 PRECEDENCE_CASES = [t for t in CASES if t.startswith("prec_")]
+EDGE_CASES = [t for t in CASES if t.startswith("edge_")]
+# (below, at, above) columns of each edge case; the cases of the integer counters have none
+EDGE_TRIPLES = {
+    "edge_ldd_equal_nz40": triples(3, 3),
+    "edge_relax_sst_nz40": triples(3, 2),
+    "edge_zero_flux_nz40": triples(3, 5),
+    "edge_itermax3_nz40": [],
+    "edge_tol0_seafloor_nz40": [],
+    "edge_retry_count_thin": triples(0, 1),
+    "edge_exact_dd_rig_nz40": triples(3, 3),
+    "edge_trap_uv_thin": triples(3, 2),
+    "edge_trap_tjump_nz40": triples(3, 1),
+    "edge_mixed_nz60": triples(3, 5),
+    "edge_mixed_nz69_stretched": triples(3, 5),
+}
 
 
 def _apply_batch(ob, nzp1, d):
