@@ -14,6 +14,10 @@ Arrays are numpy arrays in Fortran order with the reference's shapes
 (src/mckpp_data_fields.F90:353-447), so `U[ipt, k-1, l-1]` is the reference's
 `U(ipt,k,l)`; arrays with a 0 lower bound (rho, cp, difm, wU, ...) are indexed
 with the reference index directly.  All compute happens in libmckpp_hip.so.
+
+A new entry point of include/mckpp_hip.h takes two lines here: its signature in _SIGNATURES (twin=True when a
+mckpp_hip_multi_ form with the same signature exists) and, for a handle function, one method on _Handle that calls
+self._call(name, ...) - MckppHip and MckppHipMulti then both have it.
 """
 import ctypes as C
 
@@ -200,121 +204,111 @@ class MckppHipError(RuntimeError):
     pass
 
 
+def _sig(*argtypes, res=C.c_int, twin=False):
+    return res, list(argtypes), twin
+
+
+_H = C.c_void_p                     # mckpp_hip_handle, mckpp_hip_multi_handle
+_i, _i32, _i64, _d = C.c_int, C.c_int32, C.c_int64, C.c_double
+_i64p = C.POINTER(C.c_int64)
+_constp, _statep = C.POINTER(_ConstC), C.POINTER(_StateC)
+
+# Every function of include/mckpp_hip.h, once: (restype, argtypes, twin).  twin: the header also declares
+# mckpp_hip_multi_<name> with the same return type and the same parameters after the handle; _signatures() spells it
+# out.  tests/test_abi_cpu.py holds this table to the header, type by type.
+_SIGNATURES = {
+    "mckpp_hip_last_error": _sig(res=C.c_char_p),
+    "mckpp_hip_build_id": _sig(res=C.c_char_p),
+    "mckpp_hip_build_compiler": _sig(res=C.c_char_p),
+    "mckpp_hip_device_count": _sig(),
+    "mckpp_host_lookup": _sig(_d, _dp, _dp, res=None),
+    "mckpp_host_tri": _sig(_i32, _i32, _d, _dp, _dp, _dp, res=None),
+    "mckpp_host_interp_weights": _sig(_d, _i32, _d, _d, _i32, _ip, _ip, _dp, _dp, res=None),
+    "mckpp_host_shard_mask": _sig(_i64, _ip, _i32, _i32, _ip, res=_i64),
+    "mckpp_host_export_merge": _sig(_i64, _i32, _i32, _d, _i32, _i64p, C.POINTER(C.c_void_p), C.POINTER(C.c_void_p),
+                                    C.c_void_p),
+    "mckpp_hip_init": _sig(_constp, _i, C.POINTER(_H)),
+    "mckpp_hip_multi_init": _sig(_constp, _i32, _ip, C.POINTER(_H)),
+    "mckpp_hip_finalize": _sig(_H, twin=True),
+    "mckpp_hip_upload": _sig(_H, _statep, twin=True),
+    "mckpp_hip_set_forcing": _sig(_H, _dp, twin=True),
+    "mckpp_hip_fluxes": _sig(_H, _i, *[_dp] * 8, _i, _d, _d, twin=True),
+    "mckpp_hip_set_flux_series": _sig(_H, _i, _i, _dp, twin=True),
+    "mckpp_hip_run_forced": _sig(_H, _i, _i, _i, _i, _d, _d, twin=True),
+    "mckpp_hip_flux_ring": _sig(_H, _i, twin=True),
+    "mckpp_hip_flux_ring_put": _sig(_H, _i, _dp, twin=True),
+    "mckpp_hip_flux_ring_records": _sig(_H, _ip, _ip, twin=True),
+    "mckpp_hip_bottomtemp": _sig(_H, _dp, twin=True),
+    "mckpp_hip_set_bottomtemp": _sig(_H, _dp, twin=True),
+    "mckpp_hip_set_ancillary_series": _sig(_H, _i, _i, _i, _dp, twin=True),
+    "mckpp_hip_ancillary_schedule": _sig(_H, _i, _i, _i, _i, _i, C.POINTER(_AncEpochC), twin=True),
+    "mckpp_hip_update_ancillaries": _sig(_H, _statep, twin=True),
+    "mckpp_hip_set_diagnostics": _sig(_H, _i, twin=True),
+    "mckpp_hip_set_solver_mode": _sig(_H, _i, twin=True),
+    "mckpp_hip_get_solver_mode": _sig(_H),
+    "mckpp_hip_init_ocean": _sig(_H, _i, twin=True),
+    "mckpp_hip_step": _sig(_H, _i, _i, twin=True),
+    "mckpp_hip_vmix_pass": _sig(_H, _i),
+    "mckpp_hip_vmix_only": _sig(_H, _i),
+    "mckpp_hip_synchronize": _sig(_H, twin=True),
+    "mckpp_hip_download": _sig(_H, _statep, C.c_uint32, twin=True),
+    "mckpp_hip_release_host_arrays": _sig(_H, twin=True),
+    "mckpp_hip_save_restart": _sig(_H, C.c_char_p, twin=True),
+    "mckpp_hip_load_restart": _sig(_H, C.c_char_p, twin=True),
+    "mckpp_hip_restart_schedule": _sig(_H, _i, _i, _i, twin=True),
+    "mckpp_hip_restart_snapshots": _sig(_H, _i64p, _i64p, twin=True),
+    "mckpp_hip_restart_snapshot_save": _sig(_H, _i64, C.c_char_p, twin=True),
+    "mckpp_hip_restart_snapshot_release": _sig(_H, _i64, twin=True),
+    "mckpp_hip_step_log": _sig(_H, _i64, _i, twin=True),
+    "mckpp_hip_step_log_count": _sig(_H, _i64p, _i64p, _ip, twin=True),
+    "mckpp_hip_step_log_fetch": _sig(_H, _i64, _ip, _ip, _ip, _ip, twin=True),
+    "mckpp_hip_step_log_clear": _sig(_H, twin=True),
+    "mckpp_hip_window_select": _sig(_H, _ip, _i32, twin=True),
+    "mckpp_hip_window_reset": _sig(_H, twin=True),
+    "mckpp_hip_window_accumulate": _sig(_H, twin=True),
+    "mckpp_hip_window_fetch": _sig(_H, _i, _i, _dp, twin=True),
+    "mckpp_hip_window_schedule": _sig(_H, _i, _i, _i, _i, _ip, C.POINTER(C.c_uint32), _i32, twin=True),
+    "mckpp_hip_window_record_fetch": _sig(_H, _i, _i64, _i, _i, _dp, twin=True),
+    "mckpp_hip_window_record_release": _sig(_H, _i, _i64, twin=True),
+    "mckpp_hip_window_records": _sig(_H, _i, _i64p, _i64p, twin=True),
+    "mckpp_hip_window_export": _sig(_H, _i, _i, _d, twin=True),
+    "mckpp_hip_window_export_layout": _sig(_H, _i, _ip, _ip, _ip, _ip, _i64p, _i64p, twin=True),
+    "mckpp_hip_window_export_fetch": _sig(_H, _i, _i64, _i, _i, C.c_void_p, twin=True),
+    "mckpp_hip_window_export_fetch_record": _sig(_H, _i, _i64, C.c_void_p, _i64, twin=True),
+    "mckpp_hip_status": _sig(_H, _ip, _i64p, _ip, twin=True),
+    "mckpp_hip_ncolumns": _sig(_H, res=_i64, twin=True),
+    "mckpp_hip_last_kernel_ms": _sig(_H, _dp, _ip),
+    "mckpp_hip_last_launch_count": _sig(_H, res=_i32),
+    "mckpp_hip_kernel_name": _sig(_H, res=C.c_char_p),
+    "mckpp_hip_kernel_residency": _sig(_H, _ip, _ip, _ip, _i64p),
+    "mckpp_hip_eos_batch": _sig(_H, _i64, *[_dp] * 7),
+    "mckpp_hip_exp_batch": _sig(_H, _i64, _dp, _dp),
+    "mckpp_hip_div_batch": _sig(_H, _i64, _dp, _dp, _dp),
+    "mckpp_hip_multi_ndev": _sig(_H, res=_i32),
+    "mckpp_hip_multi_ctx": _sig(_H, _i32, res=_H),
+    "mckpp_hip_multi_gather": _sig(_H, _i32, _i32, _dp),
+}
+
+
+def _signatures():
+    """C name -> (restype, argtypes) of every function of the header: _SIGNATURES with the multi_ twins spelled out."""
+    out = {}
+    for name, (res, argtypes, twin) in _SIGNATURES.items():
+        out[name] = (res, argtypes)
+        if twin:
+            out["mckpp_hip_multi_" + name[len("mckpp_hip_"):]] = (res, argtypes)
+    return out
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
-    lib.mckpp_hip_last_error.restype = C.c_char_p
-    lib.mckpp_hip_device_count.restype = C.c_int
-    lib.mckpp_hip_build_id.restype = C.c_char_p
-    lib.mckpp_hip_init.argtypes = [C.POINTER(_ConstC), C.c_int, C.POINTER(C.c_void_p)]
-    lib.mckpp_hip_finalize.argtypes = [C.c_void_p]
-    lib.mckpp_host_lookup.argtypes = [C.c_double, _dp, _dp]
-    lib.mckpp_host_lookup.restype = None
-    lib.mckpp_host_tri.argtypes = [C.c_int32, C.c_int32, C.c_double, _dp, _dp, _dp]
-    lib.mckpp_host_tri.restype = None
-    lib.mckpp_hip_upload.argtypes = [C.c_void_p, C.POINTER(_StateC)]
-    lib.mckpp_hip_set_forcing.argtypes = [C.c_void_p, _dp]
-    lib.mckpp_hip_set_diagnostics.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_last_launch_count.argtypes = [C.c_void_p]
-    lib.mckpp_hip_last_launch_count.restype = C.c_int32
-    lib.mckpp_hip_set_solver_mode.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_get_solver_mode.argtypes = [C.c_void_p]
-    lib.mckpp_hip_window_reset.argtypes = [C.c_void_p]
-    lib.mckpp_hip_window_select.argtypes = [C.c_void_p, _ip, C.c_int32]
-    lib.mckpp_hip_window_accumulate.argtypes = [C.c_void_p]
-    lib.mckpp_hip_window_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
-    lib.mckpp_hip_save_restart.argtypes = [C.c_void_p, C.c_char_p]
-    lib.mckpp_hip_load_restart.argtypes = [C.c_void_p, C.c_char_p]
-    lib.mckpp_hip_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
-    lib.mckpp_hip_fluxes.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8 + [C.c_int, C.c_double, C.c_double]
-    lib.mckpp_hip_bottomtemp.argtypes = [C.c_void_p, _dp]
-    lib.mckpp_hip_set_bottomtemp.argtypes = [C.c_void_p, _dp]
-    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
-        getattr(lib, pre + "set_ancillary_series").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, _dp]
-        getattr(lib, pre + "ancillary_schedule").argtypes = [C.c_void_p] + [C.c_int] * 5 + [C.POINTER(_AncEpochC)]
-    lib.mckpp_host_interp_weights.argtypes = [C.c_double, C.c_int32, C.c_double, C.c_double, C.c_int32,
-                                              C.POINTER(C.c_int32), C.POINTER(C.c_int32), _dp, _dp]
-    lib.mckpp_host_interp_weights.restype = None
-    lib.mckpp_hip_set_flux_series.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
-    lib.mckpp_hip_run_forced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
-    lib.mckpp_hip_init_ocean.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_step.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.mckpp_hip_vmix_pass.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_vmix_only.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_synchronize.argtypes = [C.c_void_p]
-    lib.mckpp_hip_download.argtypes = [C.c_void_p, C.POINTER(_StateC), C.c_uint32]
-    lib.mckpp_hip_status.argtypes = [C.c_void_p, _ip, C.POINTER(C.c_int64), _ip]
-    lib.mckpp_hip_last_kernel_ms.argtypes = [C.c_void_p, _dp, _ip]
-    lib.mckpp_hip_kernel_residency.argtypes = [C.c_void_p, _ip, _ip, _ip, C.POINTER(C.c_int64)]
-    lib.mckpp_hip_kernel_name.argtypes = [C.c_void_p]
-    lib.mckpp_hip_kernel_name.restype = C.c_char_p
-    lib.mckpp_hip_ncolumns.argtypes = [C.c_void_p]
-    lib.mckpp_hip_ncolumns.restype = C.c_int64
-    lib.mckpp_hip_eos_batch.argtypes = [C.c_void_p, C.c_int64] + [_dp] * 7
-    lib.mckpp_hip_exp_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp]
-    lib.mckpp_hip_div_batch.argtypes = [C.c_void_p, C.c_int64, _dp, _dp, _dp]
-    lib.mckpp_host_shard_mask.argtypes = [C.c_int64, _ip, C.c_int32, C.c_int32, _ip]
-    lib.mckpp_host_shard_mask.restype = C.c_int64
-    lib.mckpp_hip_multi_init.argtypes = [C.POINTER(_ConstC), C.c_int32, _ip, C.POINTER(C.c_void_p)]
-    lib.mckpp_hip_multi_finalize.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_ndev.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_ctx.argtypes = [C.c_void_p, C.c_int32]
-    lib.mckpp_hip_multi_ctx.restype = C.c_void_p
-    lib.mckpp_hip_multi_upload.argtypes = [C.c_void_p, C.POINTER(_StateC)]
-    lib.mckpp_hip_multi_set_forcing.argtypes = [C.c_void_p, _dp]
-    lib.mckpp_hip_multi_set_diagnostics.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_multi_set_solver_mode.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_multi_init_ocean.argtypes = [C.c_void_p, C.c_int]
-    lib.mckpp_hip_multi_step.argtypes = [C.c_void_p, C.c_int, C.c_int]
-    lib.mckpp_hip_multi_synchronize.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_download.argtypes = [C.c_void_p, C.POINTER(_StateC), C.c_uint32]
-    lib.mckpp_hip_multi_status.argtypes = [C.c_void_p, _ip, C.POINTER(C.c_int64), _ip]
-    lib.mckpp_hip_multi_ncolumns.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_ncolumns.restype = C.c_int64
-    lib.mckpp_hip_multi_gather.argtypes = [C.c_void_p, C.c_int32, C.c_int32, _dp]
-    lib.mckpp_hip_release_host_arrays.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_release_host_arrays.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_set_flux_series.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
-    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
-        getattr(lib, pre + "flux_ring").argtypes = [C.c_void_p, C.c_int]
-        getattr(lib, pre + "flux_ring_put").argtypes = [C.c_void_p, C.c_int, _dp]
-        getattr(lib, pre + "flux_ring_records").argtypes = [C.c_void_p, _ip, _ip]
-    lib.mckpp_hip_multi_run_forced.argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, C.c_double, C.c_double]
-    lib.mckpp_hip_multi_window_select.argtypes = [C.c_void_p, _ip, C.c_int32]
-    lib.mckpp_hip_multi_window_reset.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_window_accumulate.argtypes = [C.c_void_p]
-    lib.mckpp_hip_multi_window_fetch.argtypes = [C.c_void_p, C.c_int, C.c_int, _dp]
-    _up = C.POINTER(C.c_uint32)
-    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
-        getattr(lib, pre + "window_schedule").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_int, _ip, _up, C.c_int32]
-        getattr(lib, pre + "window_record_fetch").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, _dp]
-        getattr(lib, pre + "window_record_release").argtypes = [C.c_void_p, C.c_int, C.c_int64]
-        getattr(lib, pre + "window_records").argtypes = [C.c_void_p, C.c_int, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        if hasattr(lib, pre + "window_export"):   # (MCKPP_HIP_LIBRARY may name an older build, tools/export_rate.py --lib:
-            # everything else works with it, and a call of the export fails there by name)
-            getattr(lib, pre + "window_export").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_double]
-            getattr(lib, pre + "window_export_layout").argtypes = [C.c_void_p, C.c_int, _ip, _ip, _ip, _ip, C.POINTER(C.c_int64),
-                                                                   C.POINTER(C.c_int64)]
-            getattr(lib, pre + "window_export_fetch").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_int, C.c_int, C.c_void_p]
-            getattr(lib, pre + "window_export_fetch_record").argtypes = [C.c_void_p, C.c_int, C.c_int64, C.c_void_p, C.c_int64]
-        getattr(lib, pre + "restart_schedule").argtypes = [C.c_void_p, C.c_int, C.c_int, C.c_int]
-        getattr(lib, pre + "restart_snapshots").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64)]
-        getattr(lib, pre + "restart_snapshot_save").argtypes = [C.c_void_p, C.c_int64, C.c_char_p]
-        getattr(lib, pre + "restart_snapshot_release").argtypes = [C.c_void_p, C.c_int64]
-        getattr(lib, pre + "step_log").argtypes = [C.c_void_p, C.c_int64, C.c_int]
-        getattr(lib, pre + "step_log_count").argtypes = [C.c_void_p, C.POINTER(C.c_int64), C.POINTER(C.c_int64),
-                                                         C.POINTER(C.c_int32)]
-        getattr(lib, pre + "step_log_fetch").argtypes = [C.c_void_p, C.c_int64] + [C.POINTER(C.c_int32)] * 4
-        getattr(lib, pre + "step_log_clear").argtypes = [C.c_void_p]
-    if hasattr(lib, "mckpp_host_export_merge"):
-        lib.mckpp_host_export_merge.argtypes = [C.c_int64, C.c_int32, C.c_int32, C.c_double, C.c_int32, C.POINTER(C.c_int64),
-                                                C.POINTER(C.c_void_p), C.POINTER(C.c_void_p), C.c_void_p]
-    lib.mckpp_hip_multi_save_restart.argtypes = [C.c_void_p, C.c_char_p]
-    lib.mckpp_hip_multi_load_restart.argtypes = [C.c_void_p, C.c_char_p]
-    lib.mckpp_hip_multi_update_ancillaries.argtypes = [C.c_void_p, C.POINTER(_StateC)]
-    lib.mckpp_hip_multi_bottomtemp.argtypes = [C.c_void_p, _dp]
-    lib.mckpp_hip_multi_set_bottomtemp.argtypes = [C.c_void_p, _dp]
-    lib.mckpp_hip_multi_fluxes.argtypes = [C.c_void_p, C.c_int] + [_dp] * 8 + [C.c_int, C.c_double, C.c_double]
+    # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
+    # everything else works with it, and a call of that name fails there by name
+    for name, (res, argtypes) in _signatures().items():
+        fn = getattr(lib, name, None)
+        if fn is not None:
+            fn.restype, fn.argtypes = res, argtypes
     lib._mckpp_bound = True
     return lib
 
@@ -326,9 +320,7 @@ def _lib():
 
 
 def build_compiler():
-    lib = _lib()
-    lib.mckpp_hip_build_compiler.restype = C.c_char_p
-    return lib.mckpp_hip_build_compiler().decode()
+    return _lib().mckpp_hip_build_compiler().decode()
 
 
 def build_id():
@@ -461,11 +453,12 @@ class Kpp3dFields:
         return s
 
 
+# The five feature groups of _Handle below, each stated once for one context and for all shards of a multi handle:
+# they reach the library through the handle's _call / _raw and know its point count as self._npts.
 class _WindowSchedules:
-    """Output windows accumulated inside the step launches (mckpp_hip_window_schedule and its kin), for one context or
-    for all shards of a multi handle (_pre).  The schedules this object set are kept here so that a fetch of a field or
-    an op a schedule does not keep is refused before the library is called."""
-    _pre = "mckpp_hip_"
+    """Output windows accumulated inside the step launches (mckpp_hip_window_schedule and its kin).  The schedules this
+    object set are kept here so that a fetch of a field or an op a schedule does not keep is refused before the library
+    is called."""
 
     def _scheds(self):
         return self.__dict__.setdefault("_wsched", {})
@@ -474,12 +467,11 @@ class _WindowSchedules:
         """Schedule `sched` (0..WIN_SCHEDULES-1): window w covers steps nt_origin + w*period .. + period-1, nrec records
         in a ring; fields are OUT_* indices or names, ops one WIN_* mask for all or one per field.  No fields: cancel."""
         f, o = _win_args(fields, ops)
-        lib = _lib()
-        if getattr(lib, self._pre + "window_schedule")(self._h, int(sched), int(nt_origin), int(period), int(nrec),
-                                                       f.ctypes.data_as(_ip), o.ctypes.data_as(C.POINTER(C.c_uint32)), len(f)) != 0:
-            err = lib.mckpp_hip_last_error().decode()
+        if self._raw("window_schedule", int(sched), int(nt_origin), int(period), int(nrec), f.ctypes.data_as(_ip),
+                     o.ctypes.data_as(C.POINTER(C.c_uint32)), len(f)) != 0:
+            err = _lib().mckpp_hip_last_error().decode()
             a = C.c_int64()
-            if getattr(lib, self._pre + "window_records")(self._h, int(sched), C.byref(a), C.byref(a)) != 0:
+            if self._raw("window_records", int(sched), C.byref(a), C.byref(a)) != 0:
                 self._scheds().pop(int(sched), None)   # (a refused schedule leaves the one in place; memory that could
             raise MckppHipError(err)                    # not be had leaves none)
         self.__dict__.get("_wexport", {}).pop(int(sched), None)   # (a schedule set anew has no export)
@@ -494,17 +486,17 @@ class _WindowSchedules:
         f = _win_check_fetch(self._scheds(), sched, field, op)
         assert out.flags["F_CONTIGUOUS"] and out.dtype == np.float64
         self._hold(out)
-        _chk(getattr(_lib(), self._pre + "window_record_fetch")(self._h, int(sched), int(rec), f, int(op), out.ctypes.data_as(_dp)))
+        self._call("window_record_fetch", int(sched), int(rec), f, int(op), out.ctypes.data_as(_dp))
         return out
 
     def window_record_release(self, sched, upto_rec):
         """Release the records of `sched` up to and including upto_rec (their ring slots are free again)."""
-        _chk(getattr(_lib(), self._pre + "window_record_release")(self._h, int(sched), int(upto_rec)))
+        self._call("window_record_release", int(sched), int(upto_rec))
 
     def window_records(self, sched):
         """(first_kept, last_complete): records first_kept .. last_complete of `sched` can be fetched."""
         a, b = C.c_int64(), C.c_int64()
-        _chk(getattr(_lib(), self._pre + "window_records")(self._h, int(sched), C.byref(a), C.byref(b)))
+        self._call("window_records", int(sched), C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     # The export of a schedule's records (mckpp_hip_window_export): every step-launch call packs the records it completed
@@ -522,21 +514,19 @@ class _WindowSchedules:
         export.  Land points of every plane hold land_value.  Records already complete are packed at once."""
         code = _exp_dtype(dtype)
         self._exports().pop(int(sched), None)
-        _chk(getattr(_lib(), self._pre + "window_export")(self._h, int(sched), code, float(land_value)))
+        self._call("window_export", int(sched), code, float(land_value))
         if code != EXP_OFF:
             self._exports()[int(sched)] = code
 
     def window_export_layout(self, sched):
         """(planes, record_bytes): planes is a list of (field, op, nlev, offset_bytes) in the order of a record - the
         schedule's fields in its order, the kept ops of each in the order mean, min, max, last."""
-        lib = _lib()
-        f = getattr(lib, self._pre + "window_export_layout")
         n, rb = C.c_int32(), C.c_int64()
-        _chk(f(self._h, int(sched), C.byref(n), None, None, None, None, C.byref(rb)))
+        self._call("window_export_layout", int(sched), C.byref(n), None, None, None, None, C.byref(rb))
         fld, op, nlev = (np.zeros(n.value, dtype=np.int32) for _ in range(3))
         off = np.zeros(n.value, dtype=np.int64)
-        _chk(f(self._h, int(sched), C.byref(n), fld.ctypes.data_as(_ip), op.ctypes.data_as(_ip), nlev.ctypes.data_as(_ip),
-               off.ctypes.data_as(C.POINTER(C.c_int64)), C.byref(rb)))
+        self._call("window_export_layout", int(sched), C.byref(n), fld.ctypes.data_as(_ip), op.ctypes.data_as(_ip),
+                   nlev.ctypes.data_as(_ip), off.ctypes.data_as(_i64p), C.byref(rb))
         return [(int(a), int(b), int(c), int(d)) for a, b, c, d in zip(fld, op, nlev, off)], int(rb.value)
 
     def window_export_fetch(self, sched, rec, field, op, out):
@@ -545,7 +535,7 @@ class _WindowSchedules:
         f = _win_check_fetch(self._scheds(), sched, field, op)
         _exp_check_out(self._exports(), sched, out)
         self._hold(out)
-        _chk(getattr(_lib(), self._pre + "window_export_fetch")(self._h, int(sched), int(rec), f, int(op), out.ctypes.data))
+        self._call("window_export_fetch", int(sched), int(rec), f, int(op), out.ctypes.data)
         return out
 
     def window_export_fetch_record(self, sched, rec, out):
@@ -555,16 +545,13 @@ class _WindowSchedules:
         if out.ndim != 1:
             raise ValueError("the array of a whole-record fetch is one-dimensional")
         self._hold(out)
-        _chk(getattr(_lib(), self._pre + "window_export_fetch_record")(self._h, int(sched), int(rec), out.ctypes.data,
-                                                                       int(out.nbytes)))
+        self._call("window_export_fetch_record", int(sched), int(rec), out.ctypes.data, int(out.nbytes))
         return out
 
 
 class _RestartSchedule:
-    """Restart snapshots taken inside the step launches (mckpp_hip_restart_schedule and its kin), for one context or
-    for all shards of a multi handle (_pre).  restart_scheduled is (nt_origin, period, nslots) of the schedule this
-    object set, or None."""
-    _pre = "mckpp_hip_"
+    """Restart snapshots taken inside the step launches (mckpp_hip_restart_schedule and its kin).  restart_scheduled is
+    (nt_origin, period, nslots) of the schedule this object set, or None."""
     restart_scheduled = None
 
     def restart_schedule(self, nt_origin, period, nslots):
@@ -576,30 +563,29 @@ class _RestartSchedule:
         if period > 0 and (nt_origin < 1 or nslots < 1):
             raise ValueError(f"restart_schedule: nt_origin={nt_origin} nslots={nslots} (each at least 1)")
         self.restart_scheduled = None   # (the library drops the schedule in place before it sets the new one)
-        _chk(getattr(_lib(), self._pre + "restart_schedule")(self._h, nt_origin, period, nslots))
+        self._call("restart_schedule", nt_origin, period, nslots)
         if period > 0:
             self.restart_scheduled = (nt_origin, period, nslots)
 
     def restart_snapshots(self):
         """(first_kept, last_complete): snapshots first_kept .. last_complete can be saved."""
         a, b = C.c_int64(), C.c_int64()
-        _chk(getattr(_lib(), self._pre + "restart_snapshots")(self._h, C.byref(a), C.byref(b)))
+        self._call("restart_snapshots", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
     def restart_snapshot_save(self, snap, path):
         """Snapshot `snap` as the file save_restart would have written after the snapshot's step (a multi handle: one
         file per shard, <path>.<shard>of<ndev>).  Launches queued behind the snapshot's keep running meanwhile."""
-        _chk(getattr(_lib(), self._pre + "restart_snapshot_save")(self._h, int(snap), str(path).encode()))
+        self._call("restart_snapshot_save", int(snap), str(path).encode())
 
     def restart_snapshot_release(self, upto_snap):
         """Release the snapshots up to and including upto_snap (their ring slots are free again)."""
-        _chk(getattr(_lib(), self._pre + "restart_snapshot_release")(self._h, int(upto_snap)))
+        self._call("restart_snapshot_release", int(upto_snap))
 
 
 class _StepLog:
-    """The step log of the step launches (mckpp_hip_step_log and its kin), for one context or for all shards of a multi
-    handle (_pre).  step_logged is (capacity, min_passes) of the log this object set, or None."""
-    _pre = "mckpp_hip_"
+    """The step log of the step launches (mckpp_hip_step_log and its kin).  step_logged is (capacity, min_passes) of
+    the log this object set, or None."""
     step_logged = None
 
     def step_log(self, capacity, min_passes=0):
@@ -610,7 +596,7 @@ class _StepLog:
             raise ValueError(f"step_log: capacity={capacity} min_passes={min_passes} (0 cancels the log / logs flagged "
                              "steps only)")
         self.step_logged = None   # (the library drops the log in place before it sets the new one)
-        _chk(getattr(_lib(), self._pre + "step_log")(self._h, capacity, min_passes))
+        self._call("step_log", capacity, min_passes)
         if capacity > 0:
             self.step_logged = (capacity, min_passes)
 
@@ -618,7 +604,7 @@ class _StepLog:
         """(n_events, n_stored, status_or) since the log was set or cleared; status_or covers the events that found no
         room too."""
         a, b, c = C.c_int64(), C.c_int64(), C.c_int32()
-        _chk(getattr(_lib(), self._pre + "step_log_count")(self._h, C.byref(a), C.byref(b), C.byref(c)))
+        self._call("step_log_count", C.byref(a), C.byref(b), C.byref(c))
         return int(a.value), int(b.value), int(c.value)
 
     def step_log_fetch(self):
@@ -626,18 +612,16 @@ class _StepLog:
         index in the caller's 3-D ordering, as status() numbers its words."""
         n = self.step_log_count()[1]
         out = [np.zeros(n, np.int32) for _ in range(4)]
-        _chk(getattr(_lib(), self._pre + "step_log_fetch")(self._h, n, *[a.ctypes.data_as(C.POINTER(C.c_int32)) for a in out]))
+        self._call("step_log_fetch", n, *[a.ctypes.data_as(_ip) for a in out])
         return tuple(out)
 
     def step_log_clear(self):
         """Keep the log; the event count and the OR of the status words are zero again."""
-        _chk(getattr(_lib(), self._pre + "step_log_clear")(self._h))
+        self._call("step_log_clear")
 
 
 class _AncillarySeries:
-    """Ancillary record series and their schedules (mckpp_hip_set_ancillary_series, mckpp_hip_ancillary_schedule), for
-    one context or for all shards of a multi handle (_pre)."""
-    _pre = "mckpp_hip_"
+    """Ancillary record series and their schedules (mckpp_hip_set_ancillary_series, mckpp_hip_ancillary_schedule)."""
     interp_weights = staticmethod(interp_weights)
 
     def set_ancillary_series(self, kind, rec0, records):
@@ -645,15 +629,14 @@ class _AncillarySeries:
         the kind's resident records, number rec0 of the run first; None or an empty array frees them."""
         kind = int(kind)
         if records is None or len(records) == 0:
-            _chk(getattr(_lib(), self._pre + "set_ancillary_series")(self._h, kind, int(rec0), 0, None))
+            self._call("set_ancillary_series", kind, int(rec0), 0, None)
             return
         r = np.ascontiguousarray(records, dtype=np.float64)
-        n = self._npts() if callable(self._npts) else self._npts
-        if r.ndim != (3 if kind in ANC_3D else 2) or r.shape[-1] != n:
+        if r.ndim != (3 if kind in ANC_3D else 2) or r.shape[-1] != self._npts:
             raise ValueError(f"set_ancillary_series: kind {kind} takes records[nrec{', nzp1' if kind in ANC_3D else ''}, "
-                             f"npts={n}], got {r.shape}")
+                             f"npts={self._npts}], got {r.shape}")
         self._hold(r)
-        _chk(getattr(_lib(), self._pre + "set_ancillary_series")(self._h, kind, int(rec0), int(r.shape[0]), r.ctypes.data_as(_dp)))
+        self._call("set_ancillary_series", kind, int(rec0), int(r.shape[0]), r.ctypes.data_as(_dp))
 
     def ancillary_schedule(self, kind, nt_origin, cadence, epochs, epoch0=0):
         """Step nt is in epoch (nt - nt_origin) // cadence; epochs[i] describes epoch epoch0 + i: a record number (the
@@ -666,18 +649,15 @@ class _AncillarySeries:
                 arr[i] = _AncEpochC(int(e), -1, 0.0, 0.0)
             else:
                 arr[i] = _AncEpochC(int(e[0]), int(e[1]), float(e[2]), float(e[3]))
-        _chk(getattr(_lib(), self._pre + "ancillary_schedule")(self._h, int(kind), int(nt_origin), int(cadence), int(epoch0),
-                                                              len(ep), arr))
+        self._call("ancillary_schedule", int(kind), int(nt_origin), int(cadence), int(epoch0), len(ep), arr)
 
 
 class _FluxRing:
-    """The flux-record ring (mckpp_hip_flux_ring and its kin), for one context or for all shards of a multi handle
-    (_pre)."""
-    _pre = "mckpp_hip_"
+    """The flux-record ring (mckpp_hip_flux_ring and its kin)."""
 
     def flux_ring(self, nslots):
         """A ring of `nslots` flux-record slots on the device, empty; 0 cancels it.  Drops a set_flux_series series."""
-        _chk(getattr(_lib(), self._pre + "flux_ring")(self._h, int(nslots)))
+        self._call("flux_ring", int(nslots))
 
     def flux_ring_put(self, rec, fields):
         """fields[8, npts] (taux, tauy, swf, lwf, lhf, shf, rain, snow) is record `rec` of the run; records arrive in
@@ -685,32 +665,41 @@ class _FluxRing:
         f = np.ascontiguousarray(fields, dtype=np.float64)
         if f.ndim != 2 or f.shape[0] != 8:
             raise ValueError(f"flux_ring_put: a record is fields[8, npts], got {f.shape}")
-        n = getattr(self, "_npts_cache", 0) if callable(self._npts) else self._npts
-        if n and f.shape[1] != n:   # (before an upload the library refuses the call itself)
-            raise ValueError(f"flux_ring_put: a record is fields[8, npts={n}], got {f.shape}")
-        _chk(getattr(_lib(), self._pre + "flux_ring_put")(self._h, int(rec), f.ctypes.data_as(_dp)))
+        if self._npts and f.shape[1] != self._npts:   # (before an upload the library refuses the call itself)
+            raise ValueError(f"flux_ring_put: a record is fields[8, npts={self._npts}], got {f.shape}")
+        self._call("flux_ring_put", int(rec), f.ctypes.data_as(_dp))
 
     def flux_ring_records(self):
         """(first, last) resident records: the last min(nslots, records put); (-1, -1): the ring is empty."""
         a, b = C.c_int(), C.c_int()
-        _chk(getattr(_lib(), self._pre + "flux_ring_records")(self._h, C.byref(a), C.byref(b)))
+        self._call("flux_ring_records", C.byref(a), C.byref(b))
         return int(a.value), int(b.value)
 
 
-class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing):
-    """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
+class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing):
+    """What one device context and several GPUs behind one handle have in common: everything but how they are made.
+    Method `name` is the C function self._pre + name applied to the handle self._h."""
+    _pre = "mckpp_hip_"
+    _npts = 0   # points of the resident state (3-D ordering, land included); 0 before upload / load_restart
 
-    def __init__(self, kpp_const_fields, device=0):
+    def _open(self, kpp_const_fields, *args):
         self._h = C.c_void_p()
-        self._const = kpp_const_fields
         # The library pins (hipHostRegister) every large host array it transfers from or into and keeps the
         # registration until release_host_arrays() / close(): an array must not be freed while it is registered (a new
         # array at the same address would be transferred through stale page mappings).  So every array - or object
         # holding arrays - handed to upload / download / set_forcing / gather / window_fetch stays referenced here
         # for exactly that long.
         self._held = {}
-        cc = kpp_const_fields.as_c()
-        _chk(_lib().mckpp_hip_init(C.byref(cc), int(device), C.byref(self._h)))
+        cc = kpp_const_fields.as_c()   # (the library copies what it points to: the constants are not kept)
+        _chk(getattr(_lib(), self._pre + "init")(C.byref(cc), *args, C.byref(self._h)))
+
+    def _raw(self, name, *args):
+        """self._pre + name on the handle: what it returns."""
+        return getattr(_lib(), self._pre + name)(self._h, *args)
+
+    def _call(self, name, *args):
+        """self._pre + name on the handle; a non-zero return code raises MckppHipError with the library's text."""
+        _chk(self._raw(name, *args))
 
     def _hold(self, obj):
         """Keep `obj` referenced while the library may have it pinned.  Arrays are keyed by their address range (the
@@ -729,7 +718,7 @@ class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _
 
     def close(self):
         if self._h:
-            _lib().mckpp_hip_finalize(self._h)
+            self._raw("finalize")
             self._h = C.c_void_p()
         self._held = {}
 
@@ -739,311 +728,198 @@ class MckppHip(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _
         except Exception:
             pass
 
+    def release_host_arrays(self):
+        """Un-pin the caller's arrays this handle registered (before they are freed while the handle lives);
+        the references this object holds on them go with the registrations."""
+        self._call("release_host_arrays")
+        self._held = {}
+
+    def _new_state(self, npts):
+        """after upload / load_restart: they cancel every output schedule, the restart schedule and the step log"""
+        self._npts = npts
+        self._scheds().clear()
+        self.restart_scheduled = None
+        self.step_logged = None
+
     def upload(self, kpp_3d_fields):
         self._hold(kpp_3d_fields)
         s = kpp_3d_fields.as_c()
-        _chk(_lib().mckpp_hip_upload(self._h, C.byref(s)))
-        self._npts_cache = kpp_3d_fields.npts
-        self._scheds().clear()   # (upload cancels every output schedule, the restart schedule and the step log)
-        self.restart_scheduled = None
-        self.step_logged = None
+        self._call("upload", C.byref(s))
+        self._new_state(kpp_3d_fields.npts)
+
+    def download(self, kpp_3d_fields, mask=F_ALL):
+        self._hold(kpp_3d_fields)
+        s = kpp_3d_fields.as_c()
+        self._call("download", C.byref(s), int(mask))
+
+    def update_ancillaries(self, kpp_3d_fields):
+        """Re-upload what mckpp_boundary_update rewrites between steps (optional-physics inputs only)."""
+        self._hold(kpp_3d_fields)
+        s = kpp_3d_fields.as_c()
+        self._call("update_ancillaries", C.byref(s))
+
+    def save_restart(self, path):
+        """The restart set into `path` (a multi handle: one file per shard, <path>.<shard>of<ndev>)."""
+        self._call("save_restart", str(path).encode())
+
+    def load_restart(self, path, npts=None):
+        """The restart set of save_restart.  npts: the points of the state the file was written from, for a handle that
+        has had no upload of as many points (a multi handle needs that upload anyway: it deals the columns)."""
+        self._call("load_restart", str(path).encode())
+        self._new_state(self._npts if npts is None else npts)
 
     def set_forcing(self, sflux):
         assert sflux.flags["F_CONTIGUOUS"]
         self._hold(sflux)
-        _chk(_lib().mckpp_hip_set_forcing(self._h, sflux.ctypes.data_as(_dp)))
+        self._call("set_forcing", sflux.ctypes.data_as(_dp))
 
     def fluxes(self, ntime, taux, tauy, swf, lwf, lhf, shf, rain, snow, l_rest=0, flsn=334000.0, el=2.5e6):
         arrs = [np.ascontiguousarray(a, dtype=np.float64) for a in (taux, tauy, swf, lwf, lhf, shf, rain, snow)]
-        _chk(_lib().mckpp_hip_fluxes(self._h, int(ntime), *[a.ctypes.data_as(_dp) for a in arrs], int(l_rest),
-                                     float(flsn), float(el)))
+        self._call("fluxes", int(ntime), *[a.ctypes.data_as(_dp) for a in arrs], int(l_rest), float(flsn), float(el))
 
     def set_flux_series(self, rec0, fields):
-        """fields[nrec, 8, npts]: taux, tauy, swf, lwf, lhf, shf, rain, snow at successive flux updates."""
+        """fields[nrec, 8, npts]: taux, tauy, swf, lwf, lhf, shf, rain, snow at successive flux updates; record 0 of the
+        array is flux update rec0 of the run."""
         f = np.ascontiguousarray(fields, dtype=np.float64)
-        assert f.ndim == 3 and f.shape[1] == 8 and f.shape[2] == self._npts_cache
+        assert f.ndim == 3 and f.shape[1] == 8 and f.shape[2] == self._npts
         self._hold(f)
-        _chk(_lib().mckpp_hip_set_flux_series(self._h, int(rec0), int(f.shape[0]), f.ctypes.data_as(_dp)))
+        self._call("set_flux_series", int(rec0), int(f.shape[0]), f.ctypes.data_as(_dp))
 
     def run_forced(self, nt_first, nsteps, ndtocn, l_rest=0, flsn=334000.0, el=2.5e6):
-        _chk(_lib().mckpp_hip_run_forced(self._h, int(nt_first), int(nsteps), int(ndtocn), int(l_rest),
-                                         float(flsn), float(el)))
+        self._call("run_forced", int(nt_first), int(nsteps), int(ndtocn), int(l_rest), float(flsn), float(el))
 
     def bottomtemp(self, bottom_temp):
         bt = np.ascontiguousarray(bottom_temp, dtype=np.float64)
-        assert bt.shape == (self._npts_cache,)
-        _chk(_lib().mckpp_hip_bottomtemp(self._h, bt.ctypes.data_as(_dp)))
+        assert bt.shape == (self._npts,)
+        self._call("bottomtemp", bt.ctypes.data_as(_dp))
 
     def set_bottomtemp(self, bottom_temp):
         """bottom_temp(npts) becomes resident: from now on every step launch ends each column-step with the
         L_VARY_BOTTOM_TEMP override (src/mckpp_physics_overrides.F90:12-24); None cancels it.  Do not also call
         bottomtemp(): it is refused while a field is resident."""
         if bottom_temp is None:
-            _chk(_lib().mckpp_hip_set_bottomtemp(self._h, None))
+            self._call("set_bottomtemp", None)
             return
         bt = np.ascontiguousarray(bottom_temp, dtype=np.float64)
-        assert bt.shape == (self._npts_cache,)
-        _chk(_lib().mckpp_hip_set_bottomtemp(self._h, bt.ctypes.data_as(_dp)))
-
-    def save_restart(self, path):
-        _chk(_lib().mckpp_hip_save_restart(self._h, str(path).encode()))
-
-    def load_restart(self, path, npts):
-        _chk(_lib().mckpp_hip_load_restart(self._h, str(path).encode()))
-        self._npts_cache = npts
-        self._scheds().clear()
-        self.restart_scheduled = None
-        self.step_logged = None
-
-    def update_ancillaries(self, kpp_3d_fields):
-        """Re-upload what mckpp_boundary_update rewrites between steps (optional-physics inputs only)."""
-        self._hold(kpp_3d_fields)
-        sc = kpp_3d_fields.as_c()
-        _chk(_lib().mckpp_hip_update_ancillaries(self._h, C.byref(sc)))
+        assert bt.shape == (self._npts,)
+        self._call("set_bottomtemp", bt.ctypes.data_as(_dp))
 
     def window_reset(self):
-        _chk(_lib().mckpp_hip_window_reset(self._h))
+        self._call("window_reset")
 
     def window_accumulate(self):
-        _chk(_lib().mckpp_hip_window_accumulate(self._h))
+        self._call("window_accumulate")
 
     def window_select(self, fields):
         """Choose the OUT_* fields window_accumulate reduces (resets the window)."""
         f = np.ascontiguousarray(fields, dtype=np.int32)
-        _chk(_lib().mckpp_hip_window_select(self._h, f.ctypes.data_as(_ip), len(f)))
+        self._call("window_select", f.ctypes.data_as(_ip), len(f))
 
     def window_fetch(self, field, op, out):
         assert out.flags["F_CONTIGUOUS"] and out.dtype == np.float64
         self._hold(out)
-        _chk(_lib().mckpp_hip_window_fetch(self._h, int(field), int(op), out.ctypes.data_as(_dp)))
+        self._call("window_fetch", int(field), int(op), out.ctypes.data_as(_dp))
         return out
 
     def set_diagnostics(self, on):
-        _chk(_lib().mckpp_hip_set_diagnostics(self._h, int(on)))
+        self._call("set_diagnostics", int(on))
 
     def set_solver_mode(self, mode):
         """0: tridmat's order of operations (default); 1: two-ended elimination (mckpp_hip_set_solver_mode)."""
-        _chk(_lib().mckpp_hip_set_solver_mode(self._h, int(mode)))
+        self._call("set_solver_mode", int(mode))
+
+    def init_ocean(self, ntime=0):
+        self._call("init_ocean", int(ntime))
+
+    def step(self, ntime, nsteps=1):
+        self._call("step", int(ntime), int(nsteps))
+
+    def synchronize(self):
+        self._call("synchronize")
+
+    def status(self):
+        st = np.zeros(self._npts, dtype=np.int32)
+        npass = np.zeros(self._npts, dtype=np.int32)
+        nf = C.c_int64(0)
+        self._call("status", st.ctypes.data_as(_ip), C.byref(nf), npass.ctypes.data_as(_ip))
+        return st, int(nf.value), npass
+
+    @property
+    def ncolumns(self):
+        return int(self._raw("ncolumns"))
+
+
+class MckppHip(_Handle):
+    """One device context (mckpp_hip_init ... mckpp_hip_finalize)."""
+
+    def __init__(self, kpp_const_fields, device=0):
+        self._open(kpp_const_fields, int(device))
 
     @property
     def solver_mode(self):
-        return int(_lib().mckpp_hip_get_solver_mode(self._h))
-
-    def release_host_arrays(self):
-        """Un-pin the caller's arrays this context registered (before they are freed while the context lives);
-        the references this object holds on them go with the registrations."""
-        _chk(_lib().mckpp_hip_release_host_arrays(self._h))
-        self._held = {}
-
-    def init_ocean(self, ntime=0):
-        _chk(_lib().mckpp_hip_init_ocean(self._h, int(ntime)))
-
-    def step(self, ntime, nsteps=1):
-        _chk(_lib().mckpp_hip_step(self._h, int(ntime), int(nsteps)))
+        return int(self._raw("get_solver_mode"))
 
     def vmix_pass(self, ntime):
-        _chk(_lib().mckpp_hip_vmix_pass(self._h, int(ntime)))
+        self._call("vmix_pass", int(ntime))
 
     def vmix_only(self, ntime):
-        _chk(_lib().mckpp_hip_vmix_only(self._h, int(ntime)))
-
-    def synchronize(self):
-        _chk(_lib().mckpp_hip_synchronize(self._h))
-
-    def download(self, kpp_3d_fields, mask=F_ALL):
-        self._hold(kpp_3d_fields)
-        s = kpp_3d_fields.as_c()
-        _chk(_lib().mckpp_hip_download(self._h, C.byref(s), int(mask)))
-
-    def status(self):
-        n = self._npts()
-        st = np.zeros(n, dtype=np.int32)
-        npass = np.zeros(n, dtype=np.int32)
-        nf = C.c_int64(0)
-        _chk(_lib().mckpp_hip_status(self._h, st.ctypes.data_as(_ip), C.byref(nf), npass.ctypes.data_as(_ip)))
-        return st, int(nf.value), npass
-
-    def _npts(self):
-        return self._npts_cache
+        self._call("vmix_only", int(ntime))
 
     def last_kernel_ms(self):
         ms = C.c_double(0)
         nl = C.c_int32(0)
-        _chk(_lib().mckpp_hip_last_kernel_ms(self._h, C.byref(ms), C.byref(nl)))
+        self._call("last_kernel_ms", C.byref(ms), C.byref(nl))
         return ms.value, nl.value
 
     def last_launch_count(self):
         """kernel launches of the last step/init/vmix_pass call (step(nt, n > 1) is one launch for all n steps)"""
-        return int(_lib().mckpp_hip_last_launch_count(self._h))
+        return int(self._raw("last_launch_count"))
 
     def kernel_residency(self):
         """(blocks per CU asked for, blocks per CU that fit, threads per block, LDS bytes per block)"""
         b, m, t = C.c_int32(0), C.c_int32(0), C.c_int32(0)
         l = C.c_int64(0)
-        _chk(_lib().mckpp_hip_kernel_residency(self._h, C.byref(b), C.byref(m), C.byref(t), C.byref(l)))
+        self._call("kernel_residency", C.byref(b), C.byref(m), C.byref(t), C.byref(l))
         return b.value, m.value, t.value, l.value
 
     @property
     def kernel_name(self):
-        return _lib().mckpp_hip_kernel_name(self._h).decode()
-
-    @property
-    def ncolumns(self):
-        return int(_lib().mckpp_hip_ncolumns(self._h))
+        return self._raw("kernel_name").decode()
 
     def eos_batch(self, s, t, p):
         n = len(s)
         out = [np.zeros(n) for _ in range(4)]
-        _chk(_lib().mckpp_hip_eos_batch(self._h, n, *[np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(_dp) for a in (s, t, p)],
-                                        *[o.ctypes.data_as(_dp) for o in out]))
+        self._call("eos_batch", n, *[np.ascontiguousarray(a, dtype=np.float64).ctypes.data_as(_dp) for a in (s, t, p)],
+                   *[o.ctypes.data_as(_dp) for o in out])
         return out
 
     def div_batch(self, num, den):
         num = np.ascontiguousarray(num, dtype=np.float64)
         den = np.ascontiguousarray(den, dtype=np.float64)
         q = np.zeros((4, len(num)))
-        _chk(_lib().mckpp_hip_div_batch(self._h, len(num), num.ctypes.data_as(_dp), den.ctypes.data_as(_dp), q.ctypes.data_as(_dp)))
+        self._call("div_batch", len(num), num.ctypes.data_as(_dp), den.ctypes.data_as(_dp), q.ctypes.data_as(_dp))
         return q
 
     def exp_batch(self, x):
         x = np.ascontiguousarray(x, dtype=np.float64)
         y = np.zeros_like(x)
-        _chk(_lib().mckpp_hip_exp_batch(self._h, len(x), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp)))
+        self._call("exp_batch", len(x), x.ctypes.data_as(_dp), y.ctypes.data_as(_dp))
         return y
 
 
-class MckppHipMulti(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing):
+class MckppHipMulti(_Handle):
     """Several GPUs behind one handle (mckpp_hip_multi_*): columns dealt round-robin to the devices."""
     _pre = "mckpp_hip_multi_"
 
     def __init__(self, kpp_const_fields, devices):
-        self._h = C.c_void_p()
-        self._c = kpp_const_fields
-        cc = kpp_const_fields.as_c()
         dev = np.ascontiguousarray(devices, dtype=np.int32)
-        _chk(_lib().mckpp_hip_multi_init(C.byref(cc), len(dev), dev.ctypes.data_as(_ip), C.byref(self._h)))
-        self._npts = 0
-        self._held = {}   # host arrays the shards have pinned: referenced until close() / release_host_arrays() (see MckppHip)
-
-    def _hold(self, obj):
-        """Keep `obj` referenced while the library may have it pinned.  Arrays are keyed by their address range (the
-        library pins arrays of at least 256 KiB only: smaller ones are not kept), objects holding arrays by identity;
-        a loop that hands over fresh arrays step after step is bounded: at 64 entries everything is unpinned and
-        released first (a caller that wants no re-pinning reuses its arrays, or calls release_host_arrays() itself)."""
-        if isinstance(obj, np.ndarray):
-            if obj.nbytes < 256 * 1024:
-                return
-            key = (obj.ctypes.data, obj.nbytes)
-        else:
-            key = id(obj)
-        if key not in self._held and len(self._held) >= 64:
-            self.release_host_arrays()
-        self._held[key] = obj
-
-    def close(self):
-        if self._h:
-            _lib().mckpp_hip_multi_finalize(self._h)
-            self._h = C.c_void_p()
-        self._held = {}
-
-    def upload(self, k3):
-        self._hold(k3)
-        sc = k3.as_c()
-        _chk(_lib().mckpp_hip_multi_upload(self._h, C.byref(sc)))
-        self._npts = k3.npts
-        self._scheds().clear()   # (upload cancels every output schedule, the restart schedule and the step log)
-        self.restart_scheduled = None
-        self.step_logged = None
-
-    def set_forcing(self, sflux):
-        self._hold(sflux)
-        _chk(_lib().mckpp_hip_multi_set_forcing(self._h, sflux.ctypes.data_as(_dp)))
-
-    def init_ocean(self, ntime=0):
-        _chk(_lib().mckpp_hip_multi_init_ocean(self._h, int(ntime)))
-
-    def step(self, ntime, nsteps=1):
-        _chk(_lib().mckpp_hip_multi_step(self._h, int(ntime), int(nsteps)))
-
-    def synchronize(self):
-        _chk(_lib().mckpp_hip_multi_synchronize(self._h))
-
-    def download(self, k3, mask=F_ALL):
-        self._hold(k3)
-        sc = k3.as_c()
-        _chk(_lib().mckpp_hip_multi_download(self._h, C.byref(sc), mask))
-
-    def status(self):
-        st = np.zeros(self._npts, dtype=np.int32)
-        npass = np.zeros(self._npts, dtype=np.int32)
-        nf = C.c_int64()
-        _chk(_lib().mckpp_hip_multi_status(self._h, st.ctypes.data_as(_ip), C.byref(nf), npass.ctypes.data_as(_ip)))
-        return st, nf.value, npass
-
-    @property
-    def ncolumns(self):
-        return _lib().mckpp_hip_multi_ncolumns(self._h)
+        self._open(kpp_const_fields, len(dev), dev.ctypes.data_as(_ip))
 
     def gather(self, field, root, out):
         """field 0 U, 1 V, 2 T, 3 S -> out(npts, nzp1) Fortran order; 4 hmix -> out(npts)."""
         assert out.flags["F_CONTIGUOUS"] and out.dtype == np.float64
         self._hold(out)
-        _chk(_lib().mckpp_hip_multi_gather(self._h, int(field), int(root), out.ctypes.data_as(_dp)))
-
-    def set_diagnostics(self, on):
-        _chk(_lib().mckpp_hip_multi_set_diagnostics(self._h, int(on)))
-
-    def set_solver_mode(self, mode):
-        _chk(_lib().mckpp_hip_multi_set_solver_mode(self._h, int(mode)))
-
-    def set_flux_series(self, rec0, fields):
-        """fields[nrec][8][npts] (taux,tauy,swf,lwf,lhf,shf,rain,snow); record 0 is flux update rec0."""
-        f = np.ascontiguousarray(fields, dtype=np.float64)
-        assert f.ndim == 3 and f.shape[1] == 8 and f.shape[2] == self._npts
-        self._hold(f)
-        _chk(_lib().mckpp_hip_multi_set_flux_series(self._h, int(rec0), f.shape[0], f.ctypes.data_as(_dp)))
-
-    def run_forced(self, nt_first, nsteps, ndtocn, l_rest=0, flsn=334000.0, el=2.5e6):
-        _chk(_lib().mckpp_hip_multi_run_forced(self._h, int(nt_first), int(nsteps), int(ndtocn), int(l_rest),
-                                               float(flsn), float(el)))
-
-    def window_select(self, fields):
-        f = np.ascontiguousarray(fields, dtype=np.int32)
-        _chk(_lib().mckpp_hip_multi_window_select(self._h, f.ctypes.data_as(_ip), len(f)))
-
-    def window_reset(self):
-        _chk(_lib().mckpp_hip_multi_window_reset(self._h))
-
-    def window_accumulate(self):
-        _chk(_lib().mckpp_hip_multi_window_accumulate(self._h))
-
-    def window_fetch(self, field, op, out):
-        assert out.flags["F_CONTIGUOUS"] and out.dtype == np.float64
-        self._hold(out)
-        _chk(_lib().mckpp_hip_multi_window_fetch(self._h, int(field), int(op), out.ctypes.data_as(_dp)))
-        return out
-
-    def set_bottomtemp(self, bottom_temp):
-        """As MckppHip.set_bottomtemp, on every shard."""
-        if bottom_temp is None:
-            _chk(_lib().mckpp_hip_multi_set_bottomtemp(self._h, None))
-            return
-        bt = np.ascontiguousarray(bottom_temp, dtype=np.float64)
-        assert bt.shape == (self._npts,)
-        _chk(_lib().mckpp_hip_multi_set_bottomtemp(self._h, bt.ctypes.data_as(_dp)))
-
-    def save_restart(self, path):
-        _chk(_lib().mckpp_hip_multi_save_restart(self._h, str(path).encode()))
-
-    def load_restart(self, path):
-        _chk(_lib().mckpp_hip_multi_load_restart(self._h, str(path).encode()))
-        self._scheds().clear()
-        self.restart_scheduled = None
-        self.step_logged = None
-
-    def release_host_arrays(self):
-        _chk(_lib().mckpp_hip_multi_release_host_arrays(self._h))
-        self._held = {}
+        self._call("gather", int(field), int(root), out.ctypes.data_as(_dp))
 
 
 def host_shard_mask(run_physics, ndev, dev):
@@ -1059,7 +935,8 @@ def host_shard_mask(run_physics, ndev, dev):
 # ---------------------------------------------------------------------------
 # The reference's call surface.  The reference operates on module globals; the
 # Python mirror passes them explicitly and keeps the device context on the
-# const-fields object (one context per kpp_const_fields, created on first use).
+# const-fields object (one context per kpp_const_fields, created on first use;
+# the context holds no reference back, so it dies with its constants).
 # ---------------------------------------------------------------------------
 def _ctx(kpp_3d_fields, kpp_const_fields, device=0):
     ctx = getattr(kpp_const_fields, "_hip_ctx", None)

@@ -34,6 +34,145 @@ def test_library_exports_every_declared_symbol(built):
         assert hasattr(lib, n), f"{n} declared in mckpp_hip.h but not exported"
 
 
+HANDLES = ("mckpp_hip_handle", "mckpp_hip_multi_handle")
+
+
+def _ctype(decl):
+    """The type of a parameter declaration or a return type as the header writes it, without the parameter's name:
+    "ptr" for any pointer or handle, else the type's one word."""
+    words = decl.replace("*", " * ").split()
+    if "*" in words or words[0] in HANDLES:
+        return "const char *" if words[:3] == ["const", "char", "*"] else "ptr"
+    return [w for w in words if w != "const"][0]
+
+
+def _prototypes():
+    """name -> (return type, [parameter types]) of every function the header declares, types as _ctype gives them."""
+    src = open(HEADER).read()
+    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
+    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
+    src = re.sub(r"\{[^{}]*\}", "", src.replace('extern "C" {', ""))   # bodies of structs and enums
+    out = {}
+    for stmt in src.split(";"):
+        m = re.fullmatch(r"\s*(.*?)\b(mckpp_h(?:ip|ost)_[a-z_0-9]+)\s*\((.*)\)\s*", stmt, flags=re.S)
+        if m:
+            ret, name, params = m.groups()
+            assert name not in out, name
+            out[name] = (_ctype(ret), [] if params.strip() == "void" else [_ctype(p) for p in params.split(",")])
+    return out
+
+
+def _bound_as(header_type, t, returned=False):
+    """Is the ctypes type `t` what the header's type is bound as?"""
+    if header_type == "const char *":
+        return t is C.c_char_p if returned else _bound_as("ptr", t)
+    if header_type == "ptr":
+        return isinstance(t, type) and (issubclass(t, C._Pointer) or t in (C.c_void_p, C.c_char_p)) \
+            and C.sizeof(t) == C.sizeof(C.c_void_p)
+    if header_type == "void":
+        return returned and t is None
+    if header_type in ("int", "int32_t"):
+        return t in (C.c_int, C.c_int32) and C.sizeof(t) == 4
+    return t is {"double": C.c_double, "int64_t": C.c_int64, "uint32_t": C.c_uint32}[header_type]
+
+
+def test_ctypes_signatures_match_the_header(built):
+    """Every function of include/mckpp_hip.h is in api.py's signature table with the header's parameter count, each
+    parameter and the return type bound as a ctypes type of the header type's class, and the loaded library carries
+    exactly that; every mckpp_hip_multi_X is its mckpp_hip_X after the handle, which is what the table's twin mark
+    relies on."""
+    from mckpp_f90_amd import api
+
+    protos = _prototypes()
+    assert sorted(protos) == _declared_functions() and len(protos) == 114
+    table = api._signatures()
+    assert sorted(table) == sorted(protos)
+    lib = api._lib()
+    for name, (ret, params) in protos.items():
+        restype, argtypes = table[name]
+        assert _bound_as(ret, restype, returned=True), f"{name} returns {ret}, bound as {restype}"
+        assert len(argtypes) == len(params), f"{name} takes {len(params)} parameters, {len(argtypes)} bound"
+        for i, (p, t) in enumerate(zip(params, argtypes)):
+            assert _bound_as(p, t), f"{name}: parameter {i} is {p}, bound as {t}"
+        fn = getattr(lib, name)
+        assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: _bind left another signature"
+    # the twins: the same return type and the same parameters after the handle; init, which takes no handle, is the
+    # only pair that differs, and every other pair is stated once in the table
+    pairs = {n: "mckpp_hip_multi_" + n[len("mckpp_hip_"):] for n in protos if not n.startswith("mckpp_hip_multi_")}
+    pairs = {n: m for n, m in pairs.items() if m in protos}
+    assert len(pairs) == 46
+    src = re.sub(r"/\*.*?\*/", "", open(HEADER).read(), flags=re.S)
+    for n, m in pairs.items():
+        if n == "mckpp_hip_init":
+            assert protos[n] != protos[m] and not api._SIGNATURES[n][2] and m in api._SIGNATURES
+            continue
+        assert re.search(r"\b%s\s*\(\s*mckpp_hip_handle\s" % n, src), f"{n} takes no handle"
+        assert re.search(r"\b%s\s*\(\s*mckpp_hip_multi_handle\s" % m, src), f"{m} takes no multi handle"
+        assert protos[n][0] == protos[m][0] and protos[n][1][1:] == protos[m][1][1:], f"{m} is not {n} after the handle"
+        assert api._SIGNATURES[n][2] and m not in api._SIGNATURES, f"{n} / {m}: one entry with the twin mark"
+    assert sum(1 for s in api._SIGNATURES.values() if s[2]) == len(pairs) - 1
+
+
+SINGLE_ONLY = {"vmix_pass", "vmix_only", "solver_mode", "last_kernel_ms", "last_launch_count", "kernel_residency",
+               "kernel_name", "eos_batch", "exp_batch", "div_batch"}
+MULTI_ONLY = {"gather"}
+
+
+def test_both_handles_have_the_same_methods():
+    """What one context can be asked, several GPUs behind one handle can be asked too, and the other way round, apart
+    from the two lists above: a method added to one class alone fails here."""
+    from mckpp_f90_amd import api
+
+    def public(cls):
+        return {n for n in dir(cls) if not n.startswith("_")
+                and (callable(getattr(cls, n)) or isinstance(getattr(cls, n), property))}
+
+    one, multi = public(api.MckppHip), public(api.MckppHipMulti)
+    assert one - multi == SINGLE_ONLY
+    assert multi - one == MULTI_ONLY
+    assert {"upload", "step", "status", "ncolumns", "fluxes", "bottomtemp", "update_ancillaries", "load_restart",
+            "window_schedule", "flux_ring_put", "close"} <= one & multi
+
+
+def test_driver_context_dies_with_its_constants(built, monkeypatch):
+    """The context that mckpp_initialize_ocean_model parks on its kpp_const_fields is finalized when the constants go,
+    by reference counting alone: no cycle through the context keeps it (and the arrays it holds pinned) for the
+    cyclic collector."""
+    import gc
+    import weakref
+
+    import mckpp_f90_amd as mk
+    from mckpp_f90_amd import api
+
+    calls = []
+
+    class Stub:
+        """a library whose entry points all succeed"""
+
+        def __getattr__(self, name):
+            def entry(*args):
+                calls.append(name)
+                if name == "mckpp_hip_init":
+                    args[-1]._obj.value = 0x1000   # (a handle: close() finalizes no null one)
+                return 0
+            return entry
+
+    kc, k3 = cm.make_hip_case(4, 10)
+    stub = Stub()
+    gc.collect()
+    gc.disable()
+    try:
+        monkeypatch.setattr(api, "_lib", lambda: stub)
+        ctx = mk.mckpp_initialize_ocean_model(k3, kc, download=False)
+        assert calls == ["mckpp_hip_init", "mckpp_hip_upload", "mckpp_hip_init_ocean"]
+        alive = weakref.ref(ctx)
+        del kc, k3, ctx
+        assert alive() is None, "the driver's context outlives its kpp_const_fields"
+        assert calls.count("mckpp_hip_finalize") == 1
+    finally:
+        gc.enable()
+
+
 def test_struct_layout_matches_header(built, tmp_path):
     """sizeof/offsetof from a C compile of the header vs the ctypes mirror in api.py."""
     from mckpp_f90_amd import api

@@ -63,9 +63,7 @@ def test_new_entry_points_fail_with_a_message_without_a_context(api):
         h = cls.__new__(cls)
         h._h = C.c_void_p()
         h._held = {}
-        h._npts_cache = 4
-        if cls is api.MckppHipMulti:
-            h._npts = 4
+        h._npts = 4
         with pytest.raises(api.MckppHipError, match="null"):
             h.set_ancillary_series(api.ANC_SST0, 0, np.zeros((2, 4)))
         with pytest.raises(api.MckppHipError, match="null"):

@@ -44,10 +44,7 @@ def test_python_wrappers_check_the_record_first(api, cls):
     h = getattr(api, cls).__new__(getattr(api, cls))
     h._h = C.c_void_p()
     h._held = {}
-    if cls == "MckppHip":
-        h._npts_cache = 4
-    else:
-        h._npts = 4
+    h._npts = 4
     for bad in (np.zeros(32), np.zeros((4, 8)), np.zeros((8, 5)), np.zeros((2, 8, 4))):
         with pytest.raises(ValueError, match=r"a record is fields\[8, npts"):
             h.flux_ring_put(0, bad)

@@ -114,6 +114,70 @@ def test_forced_loop_windows_restart_through_the_multi_handle(mk, nz, shards, tm
         h.close()
 
 
+def _fluxes_then_two_steps(h, k3):
+    rng = np.random.default_rng(5)
+    n = k3.npts
+    eight = [rng.uniform(-0.2, 0.3, n), rng.uniform(-0.1, 0.1, n), rng.uniform(0, 600, n), rng.uniform(-80, -20, n),
+             rng.uniform(-300, 0, n), rng.uniform(-40, 10, n), rng.uniform(0, 1e-4, n), rng.uniform(0, 1e-5, n)]
+    h.fluxes(1, *eight)
+    h.step(1, 1)
+    h.step(2, 1)
+
+
+def _sst0_changed_between_two_steps(h, k3):
+    h.set_forcing(k3.sflux)
+    h.step(1, 1)
+    k3.SST0[:] += 0.75 * np.cos(np.arange(k3.npts))
+    h.update_ancillaries(k3)
+    h.step(2, 1)
+
+
+def _bottomtemp_after_a_step(h, k3):
+    h.set_forcing(k3.sflux)
+    h.step(1, 1)
+    h.bottomtemp(k3.bottom_temp)
+
+
+@pytest.mark.parametrize("switch,sequence", [(None, _fluxes_then_two_steps), ("L_RELAX_SST", _sst0_changed_between_two_steps),
+                                             ("L_VARY_BOTTOM_TEMP", _bottomtemp_after_a_step)],
+                         ids=["fluxes", "update_ancillaries", "bottomtemp"])
+def test_entry_points_the_multi_handle_gained_equal_the_single_context(mk, switch, sequence):
+    """mckpp_hip_multi_fluxes (src/mckpp_fluxes_mod.F90:35-89), _update_ancillaries (what mckpp_boundary_update rewrites,
+    src/mckpp_ocean_model_3D.F90:51-55) and _bottomtemp (src/mckpp_physics_overrides.F90:12-24) through MckppHipMulti:
+    the same calls on one context and on three unequal shards (7, 6 and 6 of the 19 ocean columns of 23 points) leave
+    every downloaded field - tests/common.py's set is views of these arrays - and status() equal bit for bit."""
+    ncol, nz = 23, 20
+    got = []
+    for make in (lambda kc: mk.MckppHip(kc), lambda kc: mk.MckppHipMulti(kc, [0, 0, 0])):
+        kc, k3 = cm.make_hip_case(ncol, nz, land_every=7)
+        if switch:
+            setattr(kc, switch, 1)
+        k3.relax_sst[:] = 1.0 / (5 * 86400.0)
+        k3.SST0[:] = k3.X[:, 0, 0] + 1.5
+        k3.bottom_temp[:] = k3.X[:, nz, 0] + 0.25 * np.sin(np.arange(ncol))
+        cm.set_forcing_3d(k3, cm.synth.forcing(ncol, "bench"))
+        h = make(kc)
+        h.upload(k3)
+        h.init_ocean(0)
+        sequence(h, k3)
+        h.download(k3)
+        got.append((k3, h.status(), h.ncolumns))
+        h.close()
+    (k31, st1, n1), (k3m, stm, nm) = got
+    assert n1 == nm == 19
+    names = [n for n, a in vars(k31).items() if isinstance(a, np.ndarray)]
+    assert set(STATE + DIAG + ("tinc_fcorr", "ocnTcorr", "fcorr", "freeze_flag")) <= set(names)
+    for n in names:
+        assert getattr(k31, n).tobytes(order="A") == getattr(k3m, n).tobytes(order="A"), f"{sequence.__name__}: {n}"
+    assert np.array_equal(st1[0], stm[0]) and st1[1] == stm[1] and np.array_equal(st1[2], stm[2])
+    assert np.any(k31.X[:, :, 0] != cm.make_hip_case(ncol, nz, land_every=7)[1].X[:, :, 0])   # (the steps ran)
+    if switch == "L_RELAX_SST":
+        assert np.any(k31.fcorr != 0)
+    if switch == "L_VARY_BOTTOM_TEMP":
+        ocean = k31.run_physics != 0
+        assert np.array_equal(k31.X[ocean, nz, 0], k31.bottom_temp[ocean]) and np.any(k31.ocnTcorr[ocean, nz] != 0)
+
+
 def test_transfers_with_and_without_pinned_host_arrays(mk, monkeypatch):
     """Upload / download go through pinned caller arrays (hipHostRegister, double-buffered) by default and through
     pageable memory with MCKPP_HIP_NO_HOST_REGISTER=1 or for small arrays: same bytes either way, also after the
