@@ -25,6 +25,10 @@
  *    mckpp_hip_last_error()).  Numerical conditions never abort: they are
  *    reported per column through the status bitmask.
  *  - not re-entrant; call from one host thread per handle.
+ *
+ * Every array pointer here is a host pointer.  The companion header
+ * mckpp_hip_device.h is the device-array interface: forcing from, and output
+ * fields into, arrays in device memory, ordered on the caller's stream.
  */
 #ifndef MCKPP_HIP_H
 #define MCKPP_HIP_H

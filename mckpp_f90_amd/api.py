@@ -17,9 +17,11 @@ with the reference index directly.  All compute happens in libmckpp_hip.so.
 
 A new entry point of include/mckpp_hip.h takes two lines here: its signature in _SIGNATURES (twin=True when a
 mckpp_hip_multi_ form with the same signature exists) and, for a handle function, one method on _Handle that calls
-self._call(name, ...) - MckppHip and MckppHipMulti then both have it.
+self._call(name, ...) - MckppHip and MckppHipMulti then both have it.  The device-array interface of
+include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its methods are the mixin _DeviceArrays.
 """
 import ctypes as C
+import sys
 
 import numpy as np
 
@@ -290,14 +292,41 @@ _SIGNATURES = {
 }
 
 
-def _signatures():
-    """C name -> (restype, argtypes) of every function of the header: _SIGNATURES with the multi_ twins spelled out."""
+class _DevPlaneC(C.Structure):
+    """mckpp_dev_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "lev0", "nlev", "dtype", "fill_land")] + \
+               [("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_device.h, the device-array interface, in the same form; tests/test_device_arrays_cpu.py
+# holds this table to that header.  Kept out of _signatures(), which describes mckpp_hip.h.
+_voidpp = C.POINTER(C.c_void_p)     # const double *const fields[8]
+_SIGNATURES_DEVICE = {
+    "mckpp_hip_fluxes_dev": _sig(_H, _i, _voidpp, _i, _d, _d, C.c_void_p, twin=True),
+    "mckpp_hip_flux_ring_put_dev": _sig(_H, _i, _voidpp, C.c_void_p, twin=True),
+    "mckpp_hip_fetch_dev": _sig(_H, _i32, C.POINTER(_DevPlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_dev_fence": _sig(_H, C.c_void_p, twin=True),
+}
+
+
+def _spelled(table):
+    """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
-    for name, (res, argtypes, twin) in _SIGNATURES.items():
+    for name, (res, argtypes, twin) in table.items():
         out[name] = (res, argtypes)
         if twin:
             out["mckpp_hip_multi_" + name[len("mckpp_hip_"):]] = (res, argtypes)
     return out
+
+
+def _signatures():
+    """C name -> (restype, argtypes) of every function of mckpp_hip.h: _SIGNATURES with the multi_ twins spelled out."""
+    return _spelled(_SIGNATURES)
+
+
+def _signatures_device():
+    """... and of every function of mckpp_hip_device.h."""
+    return _spelled(_SIGNATURES_DEVICE)
 
 
 def _bind(lib):
@@ -305,7 +334,7 @@ def _bind(lib):
         return lib
     # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
     # everything else works with it, and a call of that name fails there by name
-    for name, (res, argtypes) in _signatures().items():
+    for name, (res, argtypes) in {**_signatures(), **_signatures_device()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -676,13 +705,135 @@ class _FluxRing:
         return int(a.value), int(b.value)
 
 
-class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing):
+# output fields with one value per point (the others have nzp1 levels: mckpp_hip_window_fetch's axes)
+_OUT_2D = frozenset([OUT["hmix"]]) | frozenset(range(OUT["fcorr"], len(OUT_FIELDS)))
+_DEV_TYPESTR = {"<f8": EXP_F64, "<f4": EXP_F32}
+
+
+def _dev_array(a, what, count, typestrs=("<f8",)):
+    """(address, typestr) of the device array `a` - anything exposing __cuda_array_interface__, which torch's ROCm tensors
+    do - after the checks the library cannot make: element type, C-contiguity, element count.  ValueError otherwise; a
+    host array is refused here."""
+    try:
+        cai = None if isinstance(a, np.ndarray) else a.__cuda_array_interface__
+    except (AttributeError, TypeError):     # (a torch tensor in host memory has the attribute, and raises TypeError)
+        cai = None
+    if cai is None:
+        raise ValueError(f"{what}: a host array ({type(a).__module__}.{type(a).__name__}); the call takes arrays in device "
+                         "memory that expose __cuda_array_interface__ (the methods without _dev take host arrays)")
+    shape, typestr = tuple(int(n) for n in cai["shape"]), cai["typestr"]
+    if typestr not in typestrs:
+        raise ValueError(f"{what}: element type {typestr}, the call takes {' or '.join(typestrs)}")
+    itemsize, strides = int(typestr[2:]), cai.get("strides")
+    if strides is not None:
+        want, step = [], itemsize
+        for n in reversed(shape):
+            want.insert(0, step)
+            step *= max(n, 1)
+        if any(n > 1 and int(s) != w for n, s, w in zip(shape, strides, want)):
+            raise ValueError(f"{what}: not C-contiguous (shape {shape}, strides {tuple(strides)})")
+    if int(np.prod(shape, dtype=np.int64)) != count:
+        raise ValueError(f"{what}: shape {shape}, the call takes {count} elements")
+    return int(cai["data"][0]), typestr
+
+
+def _dev_stream(stream):
+    """A caller's stream as the void * the library takes: an integer handle, an object with torch's cuda_stream, or
+    None - torch's current stream where torch is loaded and has initialised its device, else the null stream."""
+    if stream is None:
+        torch = sys.modules.get("torch")
+        if torch is None or not torch.cuda.is_initialized():
+            return C.c_void_p(None)
+        stream = torch.cuda.current_stream()
+    if isinstance(stream, int):
+        return C.c_void_p(stream or None)
+    if not hasattr(stream, "cuda_stream"):
+        raise ValueError(f"stream {stream!r}: an integer hipStream_t, an object with .cuda_stream, or None")
+    return C.c_void_p(int(stream.cuda_stream) or None)
+
+
+class _DeviceArrays:
+    """The device-array interface (include/mckpp_hip_device.h): forcing from arrays in device memory, output fields into
+    them, ordered by events on the caller's stream and never by a host wait.  Arrays handed to fluxes_dev or
+    flux_ring_put_dev must stay unchanged until a dev_fence on the stream that next writes them (fence=True queues it at
+    once on `stream`), or until synchronize()."""
+
+    def _hold_dev(self, obj):
+        """Keep a device array referenced while the library's queued kernels may touch it: the last 64 handed over (a
+        coupled loop makes fresh ones every interval, and the fence orders their reuse on the device; _hold would end
+        such a loop's 64th call with release_host_arrays, which waits for the device)."""
+        held = self.__dict__.setdefault("_dev_held", [])
+        held.append(obj)
+        del held[:-64]
+
+    def _dev_fields(self, who, fields):
+        """fields as the (void *)[8] the library takes: eight arrays of npts, or one of (8, npts)"""
+        n = self._npts
+        if not isinstance(fields, (list, tuple)):
+            base, _ = _dev_array(fields, f"{who}: fields", 8 * n)
+            ptrs = [base + 8 * n * m for m in range(8)]
+        else:
+            if len(fields) != 8:
+                raise ValueError(f"{who}: {len(fields)} fields; a record is taux, tauy, swf, lwf, lhf, shf, rain, snow")
+            ptrs = [_dev_array(a, f"{who}: fields[{m}]", n)[0] for m, a in enumerate(fields)]
+        self._hold_dev(fields)
+        return (C.c_void_p * 8)(*ptrs)
+
+    def fluxes_dev(self, ntime, fields, l_rest=0, flsn=334000.0, el=2.5e6, stream=None, fence=True):
+        """fluxes() with the eight fields in device memory, produced on `stream`: the library's stream waits for what
+        `stream` has queued, on the device.  fence: `stream` then waits for the library's read, so that its next kernels
+        may rewrite the arrays."""
+        ptrs, s = self._dev_fields("fluxes_dev", fields), _dev_stream(stream)
+        self._call("fluxes_dev", int(ntime), ptrs, int(l_rest), float(flsn), float(el), s)
+        if fence:
+            self._call("dev_fence", s)
+
+    def flux_ring_put_dev(self, rec, fields, stream=None, fence=False):
+        """flux_ring_put() from device arrays produced on `stream`; host puts and device puts may alternate."""
+        ptrs, s = self._dev_fields("flux_ring_put_dev", fields), _dev_stream(stream)
+        self._call("flux_ring_put_dev", int(rec), ptrs, s)
+        if fence:
+            self._call("dev_fence", s)
+
+    def fetch_dev(self, planes, stream=None, land_value=1e20, fill_land=True):
+        """Output fields as they stand on the device - window_fetch(field, OP_INSTANT)'s values - into device arrays, one
+        launch for all planes; `stream` waits for the delivery on the device.  A plane is (field, out, lev0, nlev): levels
+        lev0 .. lev0 + nlev - 1 (0-based) of the field into out, nlev * npts elements, points fastest - a tensor of shape
+        (nlev, npts) - of float64 or float32; (field, out) is the levels from 0 that out has room for.  fill_land: the
+        points that are no resident column get land_value, otherwise they keep what out held."""
+        n, arr = self._npts, (_DevPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            if len(p) not in (2, 4):
+                raise ValueError(f"fetch_dev: planes[{k}] is (field, out) or (field, out, lev0, nlev)")
+            f, out = _win_field(p[0]), p[1]
+            axis = 1 if f in _OUT_2D else self._nzp1
+            if len(p) == 4:
+                lev0, nlev = int(p[2]), int(p[3])
+            else:
+                shape = getattr(out, "shape", ())
+                lev0, nlev = 0, (int(np.prod(shape, dtype=np.int64)) // n if n and len(shape) else 0)
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > axis:
+                raise ValueError(f"fetch_dev: planes[{k}]: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, whose "
+                                 f"axis has {axis}")
+            ptr, typestr = _dev_array(out, f"fetch_dev: planes[{k}] out", nlev * n, tuple(_DEV_TYPESTR))
+            arr[k] = _DevPlaneC(f, lev0, nlev, _DEV_TYPESTR[typestr], int(bool(fill_land)), float(land_value), ptr)
+            self._hold_dev(out)
+        self._call("fetch_dev", len(planes), arr, _dev_stream(stream))
+
+    def dev_fence(self, stream=None):
+        """`stream` waits, on the device, for every read of caller arrays this handle has queued so far."""
+        self._call("dev_fence", _dev_stream(stream))
+
+
+class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays):
     """What one device context and several GPUs behind one handle have in common: everything but how they are made.
     Method `name` is the C function self._pre + name applied to the handle self._h."""
     _pre = "mckpp_hip_"
     _npts = 0   # points of the resident state (3-D ordering, land included); 0 before upload / load_restart
+    _nzp1 = 0   # grid points of a column (the vertical axis of the 3-D output fields)
 
     def _open(self, kpp_const_fields, *args):
+        self._nzp1 = int(kpp_const_fields.nzp1)
         self._h = C.c_void_p()
         # The library pins (hipHostRegister) every large host array it transfers from or into and keeps the
         # registration until release_host_arrays() / close(): an array must not be freed while it is registered (a new
@@ -721,6 +872,7 @@ class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _F
             self._raw("finalize")
             self._h = C.c_void_p()
         self._held = {}
+        self.__dict__.pop("_dev_held", None)
 
     def __del__(self):
         try:

@@ -218,6 +218,28 @@ struct mckpp_pack_plane {
 hipError_t mckpp_launch_record_pack(const mckpp_pack_plane *tab, int nplanes, int maxlev, int ring_slot, double period,
                                     const int *ipt, int64_t ncol, int64_t npts, void *dst_slot, int f32, hipStream_t stream);
 hipError_t mckpp_launch_export_fill(void *p, size_t nelem, double v, int f32, hipStream_t stream);
+// The device-array interface (include/mckpp_hip_device.h).  The eight forcing fields as the caller's (npts) device
+// arrays: taux, tauy, swf, lwf, lhf, shf, rain, snow.
+struct mckpp_dev_fields { const double *f[8]; };
+// k_fluxes with the eight values read from `f` through the column map
+hipError_t mckpp_launch_fluxes_dev(const mckpp_kparams &p, int ntime, const mckpp_dev_fields &f, const int *ipt, int l_rest,
+                                   double flsn, double el, hipStream_t stream);
+// `f` through the column map into one slot [8][ncol] of the flux ring
+hipError_t mckpp_launch_flux_gather(const mckpp_dev_fields &f, const int *ipt, int64_t ncol, double *slot, hipStream_t stream);
+// One plane of mckpp_hip_fetch_dev (k_fetch_planes): elements off .. off + nlev - 1 of the rows [ncol][ld] at src (plus
+// the column's Sref: add_sref) go to out(npts, nlev) as doubles or (f32) floats; fill_land: the points of the launch's
+// land list get land_value at every level of the plane.
+struct mckpp_fetch_plane {
+  const double *src;
+  void *out;
+  double land_value;
+  int ld, off, nlev, add_sref, f32, fill_land;
+};
+#define MCKPP_FETCH_PLANES 64   // most planes of one call (the device table's size)
+// all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane; land[nland]: the points that are
+// no resident column (nland 0: no plane fills them)
+hipError_t mckpp_launch_fetch_planes(const mckpp_fetch_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
+                                     int64_t npts, const double *cs, const int *land, int64_t nland, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

@@ -102,17 +102,14 @@ __global__ __launch_bounds__(256) void k_scatter_rows(const double *__restrict__
 // src/mckpp_fluxes_mod.F90:35-89, and its ntflux call (:93-118).  One thread
 // per column; inputs are the eight forcing fields compacted to resident columns.
 // ---------------------------------------------------------------------------
-__global__ void k_fluxes(mckpp_kparams p, int ntime, const double *__restrict__ f8, int l_rest, double flsn,
-                         double el)
+// The arithmetic, stated once as a function of the column's eight values: k_fluxes loads them from the compacted
+// staging, k_fluxes_dev from the caller's device arrays through the column map.
+__device__ __forceinline__ void fluxes_column(const mckpp_kparams &p, int c, int ntime, double taux, double tauy, double swf,
+                                              double lwf, double lhf, double shf, double rain, double snow, int l_rest,
+                                              double flsn, double el)
 {
-  const int c = blockIdx.x * blockDim.x + threadIdx.x;
-  if (c >= p.ncol) return;
   double *cs = p.cs + (size_t)c * MCKPP_CS;
   const int *ci = p.ci + (size_t)c * MCKPP_CI;
-  if (!ci[CI_LOCEAN]) return;                                   // fluxes_mod.F90:55
-  const size_t n = (size_t)p.ncol;
-  double taux = f8[c], tauy = f8[n + c], swf = f8[2 * n + c], lwf = f8[3 * n + c], lhf = f8[4 * n + c],
-         shf = f8[5 * n + c], rain = f8[6 * n + c], snow = f8[7 * n + c];
   if ((taux == 0.0) && (tauy == 0.0)) taux = 1.e-10;            // :57-58
   double s1, s2, s3, s4, s5, s6;
   if (!l_rest) {                                                // :60-69
@@ -131,6 +128,41 @@ __global__ void k_fluxes(mckpp_kparams p, int ntime, const double *__restrict__ 
     const int jer = ci[CI_JERLOV];
     for (int k = 0; k <= p.nz; ++k) p.wXNT1[ro + k] = -s3 * p.swdk_tab[jer * p.ldc + k] / (rho0 * cp0);
   }
+}
+
+__global__ void k_fluxes(mckpp_kparams p, int ntime, const double *__restrict__ f8, int l_rest, double flsn,
+                         double el)
+{
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= p.ncol) return;
+  if (!p.ci[(size_t)c * MCKPP_CI + CI_LOCEAN]) return;          // fluxes_mod.F90:55
+  const size_t n = (size_t)p.ncol;
+  fluxes_column(p, c, ntime, f8[c], f8[n + c], f8[2 * n + c], f8[3 * n + c], f8[4 * n + c], f8[5 * n + c], f8[6 * n + c],
+                f8[7 * n + c], l_rest, flsn, el);
+}
+
+// mckpp_hip_fluxes_dev: the eight fields are (npts) device arrays of the caller's, read through the column map
+__global__ void k_fluxes_dev(mckpp_kparams p, int ntime, mckpp_dev_fields f, const int *__restrict__ ipt, int l_rest,
+                             double flsn, double el)
+{
+  const int c = blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= p.ncol) return;
+  if (!p.ci[(size_t)c * MCKPP_CI + CI_LOCEAN]) return;          // fluxes_mod.F90:55
+  const int64_t i = ipt[c];
+  fluxes_column(p, c, ntime, f.f[0][i], f.f[1][i], f.f[2][i], f.f[3][i], f.f[4][i], f.f[5][i], f.f[6][i], f.f[7][i],
+                l_rest, flsn, el);
+}
+
+// mckpp_hip_flux_ring_put_dev: the same arrays compacted into a slot of the flux ring, [8][ncol] like a record that
+// mckpp_hip_flux_ring_put compacts on the host; a thread per column, the eight loads independent of one another
+__global__ __launch_bounds__(256) void k_flux_gather(mckpp_dev_fields f, const int *__restrict__ ipt, int64_t ncol,
+                                                     double *__restrict__ slot)
+{
+  const int64_t c = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (c >= ncol) return;
+  const int64_t i = ipt[c];
+#pragma unroll
+  for (int m = 0; m < 8; ++m) slot[(int64_t)m * ncol + c] = f.f[m][i];
 }
 
 // ---------------------------------------------------------------------------
@@ -243,7 +275,104 @@ __global__ void k_export_fill(T *__restrict__ p, size_t n, T v)
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
+// ---------------------------------------------------------------------------
+// Delivery of output fields into the caller's device arrays (mckpp_hip_fetch_dev): k_record_pack's sibling.  One
+// launch writes every plane of the call - levels off .. off + nlev - 1 of a field as it stands on the device,
+// k_out_sample's value (plus the column's Sref where the field is S) - as out(npts, nlev), points fastest, through
+// the column map, as double or narrowed by one round-to-nearest-even conversion.  The planes go on blockIdx.z, and
+// the element type is a plane's own.  The first `coltiles` workgroups in x take 64 resident columns each: a column
+// per thread where the plane has one level, otherwise the 64x64 tile through LDS, so that both sides move whole
+// segments.  The workgroups after them take 64 entries each of the list of non-resident points and, where the plane
+// asks for it, write its land value there: a thread per point, the levels of the tile in turn.
+// ---------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ void fetch_plane(const mckpp_fetch_plane &e, double (*tile)[65], const int *__restrict__ ipt,
+                                            int64_t ncol, int64_t npts, const double *__restrict__ cs,
+                                            const int *__restrict__ land, int64_t nland, int coltiles)
+{
+  const int l0 = blockIdx.y * 64;
+  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  T *__restrict__ dst = static_cast<T *>(e.out);
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  if ((int)blockIdx.x >= coltiles) {
+    if (!e.fill_land) return;
+    const int64_t i = (int64_t)((int)blockIdx.x - coltiles) * 64 + tx;
+    if (i >= nland) return;
+    const int64_t pt = land[i];
+    const T v = (T)e.land_value;
+    for (int l = ty; l < 64; l += 4)
+      if (l0 + l < e.nlev) dst[(int64_t)(l0 + l) * npts + pt] = v;
+    return;
+  }
+  const int64_t c0 = (int64_t)blockIdx.x * 64;
+  if (e.nlev == 1) {   // nothing to transpose: every fourth workgroup takes 256 columns and the others leave
+    if (blockIdx.x & 3) return;
+    const int64_t c = c0 + threadIdx.x;
+    if (c < ncol) {
+      double v = e.src[c * e.ld + e.off];
+      if (e.add_sref) v = v + cs[c * MCKPP_CS + CS_SREF];
+      dst[ipt[c]] = (T)v;
+    }
+    return;
+  }
+  for (int cc = ty; cc < 64; cc += 4) {       // read: levels fastest
+    const int64_t c = c0 + cc;
+    const int lev = l0 + tx;
+    double v = 0.0;
+    if (c < ncol && lev < e.nlev) {
+      v = e.src[c * e.ld + e.off + lev];
+      if (e.add_sref) v = v + cs[c * MCKPP_CS + CS_SREF];
+    }
+    tile[tx][cc] = v;
+  }
+  __syncthreads();
+  const int64_t c = c0 + tx;
+  if (c >= ncol) return;
+  const int64_t pt = ipt[c];
+  for (int l = ty; l < 64; l += 4) {          // write: points fastest
+    const int lev = l0 + l;
+    if (lev < e.nlev) dst[(int64_t)lev * npts + pt] = (T)tile[l][tx];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_fetch_planes(const mckpp_fetch_plane *__restrict__ tab, const int *__restrict__ ipt,
+                                                      int64_t ncol, int64_t npts, const double *__restrict__ cs,
+                                                      const int *__restrict__ land, int64_t nland, int coltiles)
+{
+  __shared__ double tile[64][65];
+  const mckpp_fetch_plane e = tab[blockIdx.z];
+  if (e.f32) fetch_plane<float>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
+  else fetch_plane<double>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
+}
+
 }  // namespace
+
+hipError_t mckpp_launch_fluxes_dev(const mckpp_kparams &p, int ntime, const mckpp_dev_fields &f, const int *ipt, int l_rest,
+                                   double flsn, double el, hipStream_t stream)
+{
+  if (p.ncol <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_fluxes_dev, dim3((unsigned)((p.ncol + 255) / 256)), dim3(256), 0, stream, p, ntime, f, ipt, l_rest,
+                     flsn, el);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_flux_gather(const mckpp_dev_fields &f, const int *ipt, int64_t ncol, double *slot, hipStream_t stream)
+{
+  if (ncol <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_flux_gather, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, stream, f, ipt, ncol, slot);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_fetch_planes(const mckpp_fetch_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
+                                     int64_t npts, const double *cs, const int *land, int64_t nland, hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0) return hipSuccess;
+  const int coltiles = (int)((ncol + 63) / 64), landtiles = (int)((nland + 63) / 64);
+  if (coltiles + landtiles == 0) return hipSuccess;
+  dim3 grid((unsigned)(coltiles + landtiles), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_fetch_planes, grid, dim3(256), 0, stream, tab, ipt, ncol, npts, cs, land, nland, coltiles);
+  return hipGetLastError();
+}
 
 hipError_t mckpp_launch_record_pack(const mckpp_pack_plane *tab, int nplanes, int maxlev, int ring_slot, double period,
                                     const int *ipt, int64_t ncol, int64_t npts, void *dst_slot, int f32, hipStream_t stream)

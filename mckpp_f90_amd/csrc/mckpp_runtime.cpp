@@ -1,11 +1,11 @@
-// mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h.
+// mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companion mckpp_hip_device.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
 // and a pair of events per context.  No CPU fallback exists: every entry
 // point that computes does so by launching the gfx950 kernels of
 // mckpp_kernels.hip, and fails with an error code if HIP is unavailable.
-#include "../../include/mckpp_hip.h"
+#include "../../include/mckpp_hip_device.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -189,6 +189,12 @@ struct mckpp_ctx_resident {
     std::vector<hip_event> arrived, last_read;   // [nslots]
     pinned_turns<double> stage;
   } ring;
+  // the grid points that are no resident column, for the planes of mckpp_hip_fetch_dev that fill them.  land_kind 0: not
+  // built (first use builds it; a new column map drops it: land_drop); 1: the complement of this context's column map; 2: a
+  // shard of a multi handle, given its list - shard 0 the points no shard holds, the others none
+  dev_buf<int> d_land;
+  int64_t nland = 0;
+  int land_kind = 0;
   dev_buf<double> d_stage;    // grow-only (ensure_stage)
   dev_buf<double> d_xfer[2];  // the staging buffers of the row transfers, grow-only (ensure_xfer)
   // pinned host images of the column records and of the forcing staging (grow-only: ensure_host_f)
@@ -247,6 +253,15 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   std::vector<std::pair<const void *, size_t>> pinned;   // caller arrays this context registered
   std::vector<std::pair<const void *, size_t>> unpinnable;   // ... and those it could not (not tried again)
   hip_event ev_f;   // the forcing staging has been read
+  // The device-array interface (include/mckpp_hip_device.h), everything created on first use.  ev_caller: recorded on the
+  // caller's stream, what the library's stream then waits for; ev_delivered: behind the launch of mckpp_hip_fetch_dev, what
+  // the consumer's stream waits for; ev_read / ev_read_flux: behind the last kernel on the context's stream / the flux
+  // ring's that reads caller arrays (mckpp_hip_dev_fence; null: no such kernel yet).  The plane table of fetch_dev:
+  // MCKPP_FETCH_PLANES entries on the device, written on the stream ahead of the launch from a pinned image used in turn.
+  hip_event ev_caller, ev_delivered, ev_read, ev_read_flux;
+  dev_buf<mckpp_fetch_plane> d_fetch_tab;
+  pinned_turns<mckpp_fetch_plane> h_fetch_tab;
+  std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
   // update_ancillaries); load_restart does not carry them, so stepping is refused until they are there
@@ -742,6 +757,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
     h->d_series.reset();
     h->series_nrec = 0;
   }
+  if (ipt != h->ipt) h->land_kind = 0;   // the list of non-resident points was of the previous column map
   h->ipt = ipt;
   if (ncol == 0) return 0;
   HIPCHK(hipMemcpyAsync(h->d_ipt, ipt.data(), (size_t)ncol * sizeof(int), hipMemcpyHostToDevice, h->stream));
@@ -1404,17 +1420,32 @@ int mckpp_hip_flux_ring(mckpp_hip_handle h, int nslots)
   return 0;
 }
 
+// what a put - from host or from device arrays - needs before it queues anything: a state, a ring, the next record
+static int ring_put_check(mckpp_hip_ctx *h, const char *who, int rec)
+{
+  if (h->npts <= 0) return fail("%s: upload the state and set a ring first (mckpp_hip_flux_ring)", who);
+  const auto &g = h->ring;
+  if (g.nslots == 0) return fail("%s: no flux ring is set (mckpp_hip_flux_ring)", who);
+  if (g.next_put < 0 ? rec < 0 : rec != g.next_put)
+    return fail("%s: record %d, but the records arrive in order: %s%d", who, rec,
+                g.next_put < 0 ? "the first one is any record >= " : "the next one is record ", g.next_put < 0 ? 0 : g.next_put);
+  return 0;
+}
+
+// ... and its bookkeeping, once the record's arrival is queued
+static void ring_put_done(mckpp_hip_ctx::flux_ring &g, int rec)
+{
+  if (g.next_put < 0) g.first_put = rec;
+  g.next_put = rec + 1;
+}
+
 int mckpp_hip_flux_ring_put(mckpp_hip_handle h, int rec, const double *fields)
 {
   const char *who = "mckpp_hip_flux_ring_put";
   if (!h) return fail("%s: null handle", who);
   if (!fields) return fail("%s: null argument", who);
-  if (h->npts <= 0) return fail("%s: upload the state and set a ring first (mckpp_hip_flux_ring)", who);
+  if (ring_put_check(h, who, rec)) return -1;
   auto &g = h->ring;
-  if (g.nslots == 0) return fail("%s: no flux ring is set (mckpp_hip_flux_ring)", who);
-  if (g.next_put < 0 ? rec < 0 : rec != g.next_put)
-    return fail("%s: record %d, but the records arrive in order: %s%d", who, rec,
-                g.next_put < 0 ? "the first one is any record >= " : "the next one is record ", g.next_put < 0 ? 0 : g.next_put);
   if (h->ncol > 0) {
     HIPCHK(hipSetDevice(h->device));
     const size_t ncol = (size_t)h->ncol, npts = (size_t)h->npts;
@@ -1435,8 +1466,7 @@ int mckpp_hip_flux_ring_put(mckpp_hip_handle h, int rec, const double *fields)
     HIPCHK(g.stage.queued(h->flux_stream));
     HIPCHK(hipEventRecord(g.arrived[(size_t)slot], h->flux_stream));
   }
-  if (g.next_put < 0) g.first_put = rec;
-  g.next_put = rec + 1;
+  ring_put_done(g, rec);
   return 0;
 }
 
@@ -1495,6 +1525,9 @@ int mckpp_hip_synchronize(mckpp_hip_handle h)
   if (!h) return fail("null handle");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
+  // (the contract of mckpp_hip_device.h: after this call the caller's device arrays are its own again - also those of a
+  // put from device arrays that no launch has waited for yet)
+  if (h->ev_read_flux) HIPCHK(hipEventSynchronize(h->ev_read_flux));
   if (getenv("MCKPP_LIST_DEBUG") && h->d_qhead) {   // after the last launch: the queues' heads, and (stamp builds) the stragglers' passes
     int qb[QBLOCK_INTS];
     HIPCHK(hipMemcpy(qb, h->d_qhead, sizeof qb, hipMemcpyDeviceToHost));
@@ -2172,6 +2205,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
     }
     h->ext_inputs_resident = false;   // and so were the optional-physics inputs
   }
+  if (ipt != h->ipt) h->land_kind = 0;   // the list of non-resident points was of the previous column map
   h->ipt = ipt;
   HIPCHK(hipMemcpy(h->d_ipt, ipt.data(), ipt.size() * sizeof(int), hipMemcpyHostToDevice));
   for (int i = 0; i < P_COUNT; ++i)
@@ -2344,6 +2378,240 @@ int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
   if (h->ncol == 0) return 0;
   if (down_rows(h, src, ld_out, 0, nlev, out)) return -1;
   return xfer_finish(h);
+}
+
+// ---------------------------------------------------------------------------
+// The device-array interface (include/mckpp_hip_device.h): forcing from the caller's device arrays, output fields into
+// them, ordered by events on the caller's stream.  Every call is a check, which queues nothing, and a part that queues:
+// a multi handle checks all its shards before any of them queues.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+const char *const flux_field_names[8] = {"taux", "tauy", "swf", "lwf", "lhf", "shf", "rain", "snow"};
+
+// Is `p` device memory with room for `bytes` that the context's device reaches?  (The context's device is current.)
+int dev_ptr_check(mckpp_hip_ctx *h, const char *who, const char *arg, const void *p, size_t bytes, int *dev_out = nullptr)
+{
+  if (!p) return fail("%s: %s is null (the context is on device %d, the pointer on no device)", who, arg, h->device);
+  hipPointerAttribute_t a;
+  memset(&a, 0, sizeof a);
+  const hipError_t e = hipPointerGetAttributes(&a, p);
+  if (e != hipSuccess) (void)hipGetLastError();   // (runtimes that know no unregistered host memory report it as an error)
+  if (e != hipSuccess || a.type != hipMemoryTypeDevice) {
+    const char *what = e != hipSuccess || a.type == hipMemoryTypeUnregistered ? "host memory"
+                       : a.type == hipMemoryTypeHost ? "pinned host memory"
+                       : a.type == hipMemoryTypeManaged ? "managed memory" : "no device allocation";
+    return fail("%s: %s is %s: the call takes device arrays (the context is on device %d, the pointer on no device); the "
+                "host forms are in mckpp_hip.h", who, arg, what, h->device);
+  }
+  if (a.device != h->device && std::find(h->peers.begin(), h->peers.end(), a.device) == h->peers.end()) {
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, h->device, a.device) != hipSuccess) { (void)hipGetLastError(); can = 0; }
+    hipError_t pe = can ? hipDeviceEnablePeerAccess(a.device, 0) : hipErrorInvalidDevice;
+    if (pe == hipErrorPeerAccessAlreadyEnabled) { (void)hipGetLastError(); pe = hipSuccess; }
+    if (pe != hipSuccess) {
+      (void)hipGetLastError();
+      return fail("%s: %s is memory of device %d, which the context's device %d cannot reach (no peer access)", who, arg,
+                  a.device, h->device);
+    }
+    h->peers.push_back(a.device);
+  }
+  void *base = nullptr;
+  size_t size = 0;
+  if (hipMemGetAddressRange(&base, &size, const_cast<void *>(p)) != hipSuccess) (void)hipGetLastError();
+  else if (static_cast<const char *>(p) + bytes > static_cast<const char *>(base) + size)
+    return fail("%s: %s: the allocation holds %zu bytes from the pointer on, the call needs %zu (the context is on device %d, "
+                "the pointer on device %d)", who, arg, (size_t)(static_cast<const char *>(base) + size - static_cast<const char *>(p)),
+                bytes, h->device, a.device);
+  if (dev_out) *dev_out = a.device;
+  return 0;
+}
+
+// the eight fields of a forcing record; *dev (where asked for): the device they - the first of them - live on
+int dev_fields_check(mckpp_hip_ctx *h, const char *who, const double *const fields[8], int *dev)
+{
+  if (!fields) return fail("%s: null argument", who);
+  HIPCHK(hipSetDevice(h->device));
+  for (int m = 0; m < 8; ++m) {
+    char arg[48];
+    snprintf(arg, sizeof arg, "fields[%d] (%s)", m, flux_field_names[m]);
+    if (dev_ptr_check(h, who, arg, fields[m], (size_t)h->npts * sizeof(double), m == 0 ? dev : nullptr)) return -1;
+  }
+  return 0;
+}
+
+// An event on the caller's stream, recorded now: what the library's streams wait for.  `ev` lives on `device`, the
+// device of the caller's stream (taken to be that of its arrays).
+int caller_event(hip_event &ev, int device, void *stream)
+{
+  HIPCHK(hipSetDevice(device));
+  if (!ev) HIPCHK(ev.create());
+  HIPCHK(hipEventRecord(ev, static_cast<hipStream_t>(stream)));
+  return 0;
+}
+
+int fluxes_dev_queue(mckpp_hip_ctx *h, int ntime, const double *const fields[8], int l_rest, double flsn, double el,
+                     hipEvent_t produced)
+{
+  if (h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamWaitEvent(h->stream, produced, 0));
+  mckpp_kparams p;
+  fill_params(h, p, ntime, MCKPP_MODE_STEP);
+  mckpp_dev_fields f;
+  for (int m = 0; m < 8; ++m) f.f[m] = fields[m];
+  HIPCHK(mckpp_launch_fluxes_dev(p, ntime, f, h->d_ipt, l_rest, flsn, el, h->stream));
+  if (!h->ev_read) HIPCHK(h->ev_read.create());
+  HIPCHK(hipEventRecord(h->ev_read, h->stream));
+  return 0;
+}
+
+int ring_put_dev_queue(mckpp_hip_ctx *h, int rec, const double *const fields[8], hipEvent_t produced)
+{
+  auto &g = h->ring;
+  if (h->ncol > 0) {
+    HIPCHK(hipSetDevice(h->device));
+    const size_t slot = (size_t)(rec % g.nslots);
+    mckpp_dev_fields f;
+    for (int m = 0; m < 8; ++m) f.f[m] = fields[m];
+    HIPCHK(hipStreamWaitEvent(h->flux_stream, produced, 0));
+    // behind the launches of the last call that needed the record the slot held - on the device, never on the host
+    HIPCHK(hipStreamWaitEvent(h->flux_stream, g.last_read[slot], 0));
+    HIPCHK(mckpp_launch_flux_gather(f, h->d_ipt, h->ncol, g.slots + slot * 8 * (size_t)h->ncol, h->flux_stream));
+    HIPCHK(hipEventRecord(g.arrived[slot], h->flux_stream));
+    if (!h->ev_read_flux) HIPCHK(h->ev_read_flux.create());
+    HIPCHK(hipEventRecord(h->ev_read_flux, h->flux_stream));
+  }
+  ring_put_done(g, rec);
+  return 0;
+}
+
+// The planes of a delivery, checked and resolved into the kernel's table; *any_fill: a plane fills the land points
+int fetch_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_dev_plane_c *planes,
+                    std::vector<mckpp_fetch_plane> &tab, int *maxlev, bool *any_fill, int *dev)
+{
+  if (nplanes < 0 || nplanes > MCKPP_DEV_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_DEV_PLANES_MAX);
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  HIPCHK(hipSetDevice(h->device));
+  tab.clear();
+  *maxlev = 0;
+  *any_fill = false;
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_dev_plane_c &q = planes[k];
+    out_desc d;
+    if (out_field(h, q.field, d)) return -1;
+    if (q.lev0 < 0 || q.nlev < 1 || (int64_t)q.lev0 + q.nlev > d.nlev)
+      return fail("%s: planes[%d]: lev0=%d nlev=%d is no range of levels of field %d, whose axis has %d (lev0 >= 0, nlev >= 1)",
+                  who, k, q.lev0, q.nlev, q.field, d.nlev);
+    if (q.dtype != MCKPP_EXP_F64 && q.dtype != MCKPP_EXP_F32)
+      return fail("%s: planes[%d]: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, k, q.dtype);
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    const size_t elem = q.dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
+    if (dev_ptr_check(h, who, arg, q.out, (size_t)h->npts * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
+    tab.push_back(mckpp_fetch_plane{d.src, q.out, q.land_value, d.ld, d.off + q.lev0, q.nlev, d.add_sref,
+                                    q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.fill_land ? 1 : 0});
+    *maxlev = std::max(*maxlev, (int)q.nlev);
+    *any_fill = *any_fill || q.fill_land;
+  }
+  return 0;
+}
+
+// the list of points a context's planes fill with their land value (mckpp_ctx_resident::d_land)
+int land_set(mckpp_hip_ctx *h, const std::vector<int> &land, int kind)
+{
+  HIPCHK(hipStreamSynchronize(h->stream));   // (first use, or a new column map: a launch in flight may read the old list)
+  HIPCHK(h->d_land.reserve(std::max<size_t>(land.size(), 1)));
+  if (!land.empty()) HIPCHK(hipMemcpy(h->d_land, land.data(), land.size() * sizeof(int), hipMemcpyHostToDevice));
+  h->nland = (int64_t)land.size();
+  h->land_kind = kind;
+  return 0;
+}
+
+// the points in 0 .. npts-1 that `covered` does not mark
+std::vector<int> points_not(const std::vector<unsigned char> &covered)
+{
+  std::vector<int> out;
+  for (size_t i = 0; i < covered.size(); ++i)
+    if (!covered[i]) out.push_back((int)i);
+  return out;
+}
+
+int fetch_dev_queue(mckpp_hip_ctx *h, const std::vector<mckpp_fetch_plane> &tab, int maxlev, bool any_fill, hipEvent_t before,
+                    void *consumer_stream)
+{
+  if (tab.empty()) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (any_fill && h->land_kind == 0) {   // a context of its own: everything its column map leaves out
+    std::vector<unsigned char> covered((size_t)h->npts, 0);
+    for (int i : h->ipt) covered[(size_t)i] = 1;
+    if (land_set(h, points_not(covered), 1)) return -1;
+  }
+  if (!h->d_fetch_tab) HIPCHK(h->d_fetch_tab.alloc(MCKPP_FETCH_PLANES));
+  mckpp_fetch_plane *q = nullptr;
+  HIPCHK(h->h_fetch_tab.take(MCKPP_FETCH_PLANES, &q));
+  std::copy(tab.begin(), tab.end(), q);
+  HIPCHK(hipMemcpyAsync(h->d_fetch_tab, q, tab.size() * sizeof(mckpp_fetch_plane), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h->h_fetch_tab.queued(h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
+  HIPCHK(mckpp_launch_fetch_planes(h->d_fetch_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
+                                   any_fill ? h->d_land.get() : nullptr, any_fill ? h->nland : 0, h->stream));
+  if (!h->ev_delivered) HIPCHK(h->ev_delivered.create());
+  HIPCHK(hipEventRecord(h->ev_delivered, h->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+
+int dev_fence_queue(mckpp_hip_ctx *h, void *stream)
+{
+  if (h->ev_read) HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_read, 0));
+  if (h->ev_read_flux) HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_read_flux, 0));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_fluxes_dev(mckpp_hip_handle h, int ntime, const double *const fields[8], int l_rest, double flsn, double el,
+                         void *producer_stream)
+{
+  const char *who = "mckpp_hip_fluxes_dev";
+  if (!h) return fail("%s: null handle", who);
+  if (dev_fields_check(h, who, fields, nullptr)) return -1;
+  if (h->ncol == 0) return 0;
+  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return fluxes_dev_queue(h, ntime, fields, l_rest, flsn, el, h->ev_caller);
+}
+
+int mckpp_hip_flux_ring_put_dev(mckpp_hip_handle h, int rec, const double *const fields[8], void *producer_stream)
+{
+  const char *who = "mckpp_hip_flux_ring_put_dev";
+  if (!h) return fail("%s: null handle", who);
+  if (!fields) return fail("%s: null argument", who);
+  if (ring_put_check(h, who, rec)) return -1;
+  if (dev_fields_check(h, who, fields, nullptr)) return -1;
+  if (h->ncol > 0 && caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return ring_put_dev_queue(h, rec, fields, h->ev_caller);
+}
+
+int mckpp_hip_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
+{
+  const char *who = "mckpp_hip_fetch_dev";
+  if (!h) return fail("%s: null handle", who);
+  std::vector<mckpp_fetch_plane> tab;
+  int maxlev = 0;
+  bool any_fill = false;
+  if (fetch_dev_check(h, who, nplanes, planes, tab, &maxlev, &any_fill, nullptr)) return -1;
+  if (tab.empty()) return 0;
+  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complement again)
+  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
+  return fetch_dev_queue(h, tab, maxlev, any_fill, h->ev_caller, consumer_stream);
+}
+
+int mckpp_hip_dev_fence(mckpp_hip_handle h, void *stream)
+{
+  if (!h) return fail("mckpp_hip_dev_fence: null handle");
+  return dev_fence_queue(h, stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -2926,6 +3194,9 @@ struct mckpp_hip_multi : mckpp_multi_root {
   std::vector<hip_event> ev_owner;          // [ndev], each on its shard's device
   // pinned staging the shards' export planes arrive in before the host merges them (mckpp_hip_multi_window_export_fetch)
   pinned_buf<char> h_exp;
+  // the event on the caller's stream that orders every shard's part of a device-array call, on device ev_caller_dev
+  hip_event ev_caller;
+  int ev_caller_dev = -1;
 };
 
 // run_physics mask of shard `dev` of `ndev`: the j-th ocean point (in ipt order) goes to shard j mod ndev
@@ -3009,6 +3280,7 @@ int mckpp_hip_multi_upload(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s
     if (mckpp_hip_upload(m->ctx[d], &sd) != 0) return -1;
   }
   m->gipt_valid = false;   // the root's copy of the column maps is of the previous upload
+  for (auto *x : m->ctx) x->land_kind = 0;   // ... and so is shard 0's list of the points that no shard holds
   return 0;
 }
 
@@ -3598,6 +3870,82 @@ int mckpp_hip_multi_step_log_clear(mckpp_hip_multi_handle m)
 }
 
 // the caller's arrays pinned on behalf of this handle go back to pageable memory (before the caller frees them)
+// ---- the device-array interface (mckpp_hip_device.h) over all shards: every shard is checked before any of them
+// queues, and one event on the caller's stream - created on the device of the caller's arrays - orders them all
+static int multi_caller_event(mckpp_hip_multi *m, int dev, void *stream)
+{
+  if (m->ev_caller_dev != dev) { m->ev_caller.reset(); m->ev_caller_dev = dev; }
+  return caller_event(m->ev_caller, dev, stream);
+}
+
+int mckpp_hip_multi_fluxes_dev(mckpp_hip_multi_handle m, int ntime, const double *const fields[8], int l_rest, double flsn,
+                               double el, void *producer_stream)
+{
+  const char *who = "mckpp_hip_multi_fluxes_dev";
+  if (!m) return fail("%s: null handle", who);
+  int dev = -1;
+  for (auto *x : m->ctx)
+    if (dev_fields_check(x, who, fields, &dev)) return -1;
+  if (dev < 0) return 0;
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (auto *x : m->ctx)
+    if (fluxes_dev_queue(x, ntime, fields, l_rest, flsn, el, m->ev_caller)) return -1;
+  return 0;
+}
+
+int mckpp_hip_multi_flux_ring_put_dev(mckpp_hip_multi_handle m, int rec, const double *const fields[8], void *producer_stream)
+{
+  const char *who = "mckpp_hip_multi_flux_ring_put_dev";
+  if (!m) return fail("%s: null handle", who);
+  if (!fields) return fail("%s: null argument", who);
+  int dev = -1;
+  for (auto *x : m->ctx)
+    if (ring_put_check(x, who, rec) || dev_fields_check(x, who, fields, &dev)) return -1;
+  if (dev < 0) return 0;
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (auto *x : m->ctx)
+    if (ring_put_dev_queue(x, rec, fields, m->ev_caller)) return -1;
+  return 0;
+}
+
+int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
+{
+  const char *who = "mckpp_hip_multi_fetch_dev";
+  if (!m) return fail("%s: null handle", who);
+  const int ndev = (int)m->ctx.size();
+  std::vector<std::vector<mckpp_fetch_plane>> tabs((size_t)ndev);
+  int maxlev = 0, dev = -1;
+  bool any_fill = false;
+  for (int d = 0; d < ndev; ++d)
+    if (fetch_dev_check(m->ctx[d], who, nplanes, planes, tabs[(size_t)d], &maxlev, &any_fill, &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (any_fill) {   // shard 0 fills the points that no shard holds, the others fill none: every point is written once
+    for (int d = 1; d < ndev; ++d)
+      for (auto &e : tabs[(size_t)d]) e.fill_land = 0;
+    if (m->ctx[0]->land_kind != 2) {
+      std::vector<int64_t> ncol;
+      std::vector<const int32_t *> points;
+      for (auto *x : m->ctx) { ncol.push_back(x->ncol); points.push_back(x->ipt.data()); }
+      std::vector<unsigned char> covered;
+      if (export_covered(m->npts, ndev, ncol.data(), points.data(), covered)) return fail("%s: a column map names a point outside the grid", who);
+      HIPCHK(hipSetDevice(m->ctx[0]->device));
+      if (land_set(m->ctx[0], points_not(covered), 2)) return -1;
+    }
+  }
+  if (multi_caller_event(m, dev, consumer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (fetch_dev_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
+  return 0;
+}
+
+int mckpp_hip_multi_dev_fence(mckpp_hip_multi_handle m, void *stream)
+{
+  if (!m) return fail("mckpp_hip_multi_dev_fence: null handle");
+  for (auto *x : m->ctx)
+    if (dev_fence_queue(x, stream)) return -1;
+  return 0;
+}
+
 int mckpp_hip_multi_release_host_arrays(mckpp_hip_multi_handle m)
 {
   if (!m) return fail("null multi handle");

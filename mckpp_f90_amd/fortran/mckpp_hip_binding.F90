@@ -1,5 +1,5 @@
-!> iso_c_binding view of include/mckpp_hip.h: the only place the Fortran host
-!! touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!> iso_c_binding view of include/mckpp_hip.h and of its companion
+!! mckpp_hip_device.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -35,6 +35,14 @@ module mckpp_hip_binding
     integer(c_int32_t) :: rec_prev, rec_next
     real(c_double) :: w_prev, w_next
   end type mckpp_anc_epoch_c
+
+  !> one plane of mckpp_hip_fetch_dev (include/mckpp_hip_device.h): levels lev0 .. lev0+nlev-1 (0-based) of output field
+  !! `field` into the device array at `out`, as MCKPP_EXP_F64 or MCKPP_EXP_F32; fill_land /= 0: land points get land_value
+  type, bind(C) :: mckpp_dev_plane_c
+    integer(c_int32_t) :: field, lev0, nlev, dtype, fill_land
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_dev_plane_c
 
   type, bind(C) :: mckpp_const_c
     integer(c_int32_t) :: nz, nztmax, nsflxs, njdt, itermax
@@ -655,6 +663,67 @@ module mckpp_hip_binding
       type(c_ptr), value :: handle
       real(c_double), intent(out) :: ms
       integer(c_int32_t), intent(out) :: nlaunch
+      integer(c_int) :: rc
+    end function
+    ! The device-array interface (include/mckpp_hip_device.h).  fields(8): the device addresses of taux, tauy, swf, lwf,
+    ! lhf, shf, rain, snow (npts doubles each) - c_loc of the arrays inside an OpenMP `target data use_device_ptr` or an
+    ! OpenACC `host_data use_device` region; streams: the caller's hipStream_t, c_null_ptr for the null stream.
+    function mckpp_hip_fluxes_dev(handle, ntime, fields, l_rest, flsn, el, producer_stream) &
+        bind(C, name="mckpp_hip_fluxes_dev") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int), value :: ntime, l_rest
+      type(c_ptr), intent(in) :: fields(8)
+      real(c_double), value :: flsn, el
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_flux_ring_put_dev(handle, rec, fields, producer_stream) &
+        bind(C, name="mckpp_hip_flux_ring_put_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int), value :: rec
+      type(c_ptr), intent(in) :: fields(8)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_fetch_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_dev_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_dev_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_dev_fence(handle, stream) bind(C, name="mckpp_hip_dev_fence") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, stream
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_fluxes_dev(m, ntime, fields, l_rest, flsn, el, producer_stream) &
+        bind(C, name="mckpp_hip_multi_fluxes_dev") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int), value :: ntime, l_rest
+      type(c_ptr), intent(in) :: fields(8)
+      real(c_double), value :: flsn, el
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_flux_ring_put_dev(m, rec, fields, producer_stream) &
+        bind(C, name="mckpp_hip_multi_flux_ring_put_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int), value :: rec
+      type(c_ptr), intent(in) :: fields(8)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_fetch_dev(m, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_multi_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_dev_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_dev_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_dev_fence(m, stream) bind(C, name="mckpp_hip_multi_dev_fence") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: m, stream
       integer(c_int) :: rc
     end function
   end interface
