@@ -94,15 +94,7 @@ def special_records(pre, name, r, rec, T):
 def both(ncol, nz, grid="uniform", land_every=7, pre="rates", solver_mode=None, itermax=None, **switches):
     """Oracle const + batch and the HIP side's constants + fields of one case, before initialisation; and the starting
     profiles the records are made from."""
-    sm = {} if solver_mode is None else {"solver_mode": solver_mode}
-    if itermax is not None:
-        sm["itermax"] = itermax
-    oc, ob = cm.make_oracle(ncol, nz, init=False, exp_mode=1, grid=grid, **sm, **switches)
-    kc, k3 = cm.make_hip_case(ncol, nz, grid=grid, land_every=land_every)
-    for k, v in switches.items():
-        setattr(kc, k, v)
-    if itermax is not None:
-        kc.itermax = itermax
+    oc, ob, kc, k3 = cm.make_both(ncol, nz, grid, land_every, solver_mode, itermax, **switches)
     T, S = ob["T"][:, 1:nz + 2].copy(), ob["S"][:, 1:nz + 2].copy()
     rc.apply_both(ob, k3, nz + 1, PRE[pre](ncol, nz + 1, ob))
     return oc, ob, kc, k3, (T, S)

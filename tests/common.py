@@ -73,6 +73,22 @@ def make_hip_case(ncol, nz, grid="uniform", dto=3600.0, land_every=0, index=None
     return kc, k3
 
 
+def make_both(ncol, nz, grid="uniform", land_every=0, solver_mode=None, itermax=None, **switches):
+    """One case on both sides, before initialisation: the oracle's const + batch (portable-exp mode) and the HIP side's
+    constants + fields, with the same switches (and iteration limit) set on both.  solver_mode goes to the oracle alone:
+    a context gets it from set_solver_mode."""
+    sm = {} if solver_mode is None else {"solver_mode": solver_mode}
+    if itermax is not None:
+        sm["itermax"] = itermax
+    oc, ob = make_oracle(ncol, nz, init=False, exp_mode=1, grid=grid, **sm, **switches)
+    kc, k3 = make_hip_case(ncol, nz, grid=grid, land_every=land_every)
+    for k, v in switches.items():
+        setattr(kc, k, v)
+    if itermax is not None:
+        kc.itermax = itermax
+    return oc, ob, kc, k3
+
+
 def set_forcing_3d(k3, sflux6):
     k3.sflux[:, 0:6, 4, 0] = sflux6
 

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import bound_as, prototypes
 from oracle import orc
 
 ROOT = cm.ROOT
@@ -34,48 +35,6 @@ def test_library_exports_every_declared_symbol(built):
         assert hasattr(lib, n), f"{n} declared in mckpp_hip.h but not exported"
 
 
-HANDLES = ("mckpp_hip_handle", "mckpp_hip_multi_handle")
-
-
-def _ctype(decl):
-    """The type of a parameter declaration or a return type as the header writes it, without the parameter's name:
-    "ptr" for any pointer or handle, else the type's one word."""
-    words = decl.replace("*", " * ").split()
-    if "*" in words or words[0] in HANDLES:
-        return "const char *" if words[:3] == ["const", "char", "*"] else "ptr"
-    return [w for w in words if w != "const"][0]
-
-
-def _prototypes():
-    """name -> (return type, [parameter types]) of every function the header declares, types as _ctype gives them."""
-    src = open(HEADER).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    src = re.sub(r"\{[^{}]*\}", "", src.replace('extern "C" {', ""))   # bodies of structs and enums
-    out = {}
-    for stmt in src.split(";"):
-        m = re.fullmatch(r"\s*(.*?)\b(mckpp_h(?:ip|ost)_[a-z_0-9]+)\s*\((.*)\)\s*", stmt, flags=re.S)
-        if m:
-            ret, name, params = m.groups()
-            assert name not in out, name
-            out[name] = (_ctype(ret), [] if params.strip() == "void" else [_ctype(p) for p in params.split(",")])
-    return out
-
-
-def _bound_as(header_type, t, returned=False):
-    """Is the ctypes type `t` what the header's type is bound as?"""
-    if header_type == "const char *":
-        return t is C.c_char_p if returned else _bound_as("ptr", t)
-    if header_type == "ptr":
-        return isinstance(t, type) and (issubclass(t, C._Pointer) or t in (C.c_void_p, C.c_char_p)) \
-            and C.sizeof(t) == C.sizeof(C.c_void_p)
-    if header_type == "void":
-        return returned and t is None
-    if header_type in ("int", "int32_t"):
-        return t in (C.c_int, C.c_int32) and C.sizeof(t) == 4
-    return t is {"double": C.c_double, "int64_t": C.c_int64, "uint32_t": C.c_uint32}[header_type]
-
-
 def test_ctypes_signatures_match_the_header(built):
     """Every function of include/mckpp_hip.h is in api.py's signature table with the header's parameter count, each
     parameter and the return type bound as a ctypes type of the header type's class, and the loaded library carries
@@ -83,17 +42,17 @@ def test_ctypes_signatures_match_the_header(built):
     relies on."""
     from mckpp_f90_amd import api
 
-    protos = _prototypes()
+    protos = prototypes(HEADER)
     assert sorted(protos) == _declared_functions() and len(protos) == 114
     table = api._signatures()
     assert sorted(table) == sorted(protos)
     lib = api._lib()
     for name, (ret, params) in protos.items():
         restype, argtypes = table[name]
-        assert _bound_as(ret, restype, returned=True), f"{name} returns {ret}, bound as {restype}"
+        assert bound_as(ret, restype, returned=True), f"{name} returns {ret}, bound as {restype}"
         assert len(argtypes) == len(params), f"{name} takes {len(params)} parameters, {len(argtypes)} bound"
         for i, (p, t) in enumerate(zip(params, argtypes)):
-            assert _bound_as(p, t), f"{name}: parameter {i} is {p}, bound as {t}"
+            assert bound_as(p, t), f"{name}: parameter {i} is {p}, bound as {t}"
         fn = getattr(lib, name)
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: _bind left another signature"
     # the twins: the same return type and the same parameters after the handle; init, which takes no handle, is the

@@ -12,18 +12,11 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import api  # noqa: F401
 
 FDIR = os.path.join(cm.ROOT, "mckpp_f90_amd", "fortran")
 FC = "/opt/rocm/bin/amdflang"
 HEADER = os.path.join(cm.ROOT, "include", "mckpp_hip.h")
-
-
-@pytest.fixture(scope="module")
-def api(built):
-    import mckpp_f90_amd as mk
-
-    mk.load_library()
-    return mk.api
 
 
 def test_epoch_struct_and_kinds_match_the_header(api, tmp_path):

@@ -15,30 +15,14 @@ import pytest
 import anc_cases as ac
 import common as cm
 import ref_step_cases as rc
+from harness import cleared, force_bench, initialised, is_the_oracles, mk  # noqa: F401
 from mckpp_f90_amd import api as A
 
 pytestmark = pytest.mark.gpu
 
 ENV = ("MCKPP_MULTISTEP", "MCKPP_SOLO_AFTER", "MCKPP_SOLO_LIMIT", "MCKPP_XCC_DROP", "MCKPP_PS_FIXED_L", "MCKPP_L3_CAP")
 NCOL, NZ, NSTEPS = 96, 40, 12
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
+_clean_env = cleared(ENV)
 
 
 # ---------------------------------------------------------------------------
@@ -47,14 +31,11 @@ def _clean_env(monkeypatch):
 def _hip(mk, ncol, nz, shards=0, series=None, **case):
     """The HIP side of a case, initialised and forced (bench forcing, or a resident flux series), ready to step."""
     oc, ob, kc, k3, TS = ac.both(ncol, nz, **case)
-    h = mk.MckppHipMulti(kc, [0] * shards) if shards else mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
+    h = initialised(mk, kc, k3, shards)
     if case.get("solver_mode") is not None:
         h.set_solver_mode(case["solver_mode"])
     if series is None:
-        cm.set_forcing_3d(k3, cm.synth.forcing(ncol, "bench"))
-        h.set_forcing(k3.sflux)
+        force_bench(h, k3)
     else:
         h.set_flux_series(0, series)
     return h, kc, k3
@@ -69,15 +50,6 @@ def _schedule(h, sched, recs, origin=1):
     for n, (cad, ep) in sched.items():
         h.set_ancillary_series(ac.KINDS[n][0], 0, _as_series(n, recs[n]))
         h.ancillary_schedule(ac.KINDS[n][0], origin, cad, ep)
-
-
-def _is_the_oracles(h, k3, ob, nz, active, tag):
-    h.download(k3)
-    st, nf, npass = h.status()
-    assert np.array_equal(st[active], ob["status"][active]), tag
-    assert np.array_equal(npass[active], ob["npasses"][active]), tag
-    bad = {k: v for k, v in cm.compare(k3, ob, nz, rc.STEP_FIELDS, active).items() if v[2] != 0}
-    assert not bad, f"{tag}: fields differing from the oracle (max_abs, max_rel, n_values): {bad}"
 
 
 def _fields(h, k3, nz):
@@ -137,7 +109,7 @@ def test_each_kind_alone_stepwise(mk, case):
     _schedule(h, sched, want.recs)
     h.step(1, NSTEPS)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, case)
+    is_the_oracles(h, k3, want.ob, NZ, want.active, case)
     one = _fields(h, k3, NZ)
     h.close()
     h, kc, k3 = _hip(mk, NCOL, NZ, **sw)
@@ -168,7 +140,7 @@ def test_interpolated_climatologies_every_step(mk, monkeypatch, table, nz, grid,
     _schedule(h, sched, want.recs)
     h.step(1, NSTEPS)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, want.ob, nz, want.active, f"{table} nz={nz} {env}")
+    is_the_oracles(h, k3, want.ob, nz, want.active, f"{table} nz={nz} {env}")
     h.close()
 
 
@@ -193,7 +165,7 @@ def test_all_seven_kinds_different_cadences(mk, solver_mode, shards):
     _schedule(h, ALL7, want.recs)
     h.step(1, NSTEPS)
     h.synchronize()
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, f"all kinds, mode {solver_mode}, shards {shards}")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, f"all kinds, mode {solver_mode}, shards {shards}")
     h.close()
 
 
@@ -210,7 +182,7 @@ def test_sst0_and_fcorr_twod_beside_each_other_kinds(mk):
         h, kc, k3 = _hip(mk, NCOL, NZ, **sw)
         _schedule(h, sched, want.recs)
         h.step(1, NSTEPS)
-        _is_the_oracles(h, k3, want.ob, NZ, want.active, twod)
+        is_the_oracles(h, k3, want.ob, NZ, want.active, twod)
         h.close()
 
 
@@ -240,7 +212,7 @@ def test_columns_at_different_epochs_at_once(mk, monkeypatch, form):
     _schedule(h, AT_ONCE, want.recs)
     h.step(1, nsteps)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, form)
+    is_the_oracles(h, k3, want.ob, NZ, want.active, form)
     one = _fields(h, k3, NZ)
     h.close()
     monkeypatch.setenv("MCKPP_MULTISTEP", "0")
@@ -267,7 +239,7 @@ def test_flagged_steps_inside_the_launch_at_itermax_4(mk, monkeypatch):
     assert h.last_launch_count() == 1
     nt_, pt, st, npass = h.step_log_fetch()
     assert list(zip(nt_.tolist(), pt.tolist(), st.tolist(), npass.tolist())) == log
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "itermax 4")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "itermax 4")
     one = _fields(h, k3, NZ)
     h.close()
     monkeypatch.setenv("MCKPP_MULTISTEP", "0")
@@ -305,7 +277,7 @@ def test_a_retried_step_resets_to_the_steps_own_climatology(mk, kernel):
     _schedule(h, sched, want.recs)
     h.step(1, nsteps)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "tjump + scheduled climatology")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "tjump + scheduled climatology")
     h.close()
 
 
@@ -322,7 +294,7 @@ def test_an_isotherm_reset_reads_the_steps_own_climatology(mk):
     _schedule(h, sched, want.recs)
     h.step(1, nsteps)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "isotherm reset + scheduled climatology")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "isotherm reset + scheduled climatology")
     h.close()
 
 
@@ -368,7 +340,7 @@ def test_beside_flux_series_windows_snapshots_and_log(mk, tmp_path):
             h.restart_snapshot_save(s, files[-1])
         lg = h.step_log_fetch()
         if not cut:
-            _is_the_oracles(h, k3, want.ob, nz, want.active, "beside the schedules")
+            is_the_oracles(h, k3, want.ob, nz, want.active, "beside the schedules")
         h.close()
         return rec, [open(f, "rb").read() for f in files], list(zip(*[a.tolist() for a in lg]))
 
@@ -394,7 +366,7 @@ def test_five_plus_seven_steps_with_the_schedule_kept(mk):
     _schedule(h, SPLIT, want.recs)
     h.step(1, 5)
     h.step(6, 7)
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "5 + 7")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "5 + 7")
     h.close()
 
 
@@ -413,7 +385,7 @@ def test_series_replaced_between_launches_holding_the_later_records(mk):
     with pytest.raises(mk.MckppHipError, match=r"mckpp_hip_step: SST0: step 6 \(epoch 1\) needs record 1, resident are 2\.\.3"):
         h.step(6, 2)
     h.step(7, 6)
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "later records only")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "later records only")
     h.close()
 
 
@@ -483,7 +455,7 @@ def test_refusals_leave_the_state_unchanged(mk):
     _same(before, _fields(h, k3, NZ), want.active, "nothing was launched")
     # ... and the good launch
     h.step(1, NSTEPS)
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "after the refusals")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "after the refusals")
     h.close()
 
 
@@ -502,7 +474,7 @@ def test_other_kinds_are_refused_on_a_default_physics_context(mk):
             h.ancillary_schedule(kind, 1, 3, (0, 1))
     _schedule(h, sched, want.recs)
     h.step(1, NSTEPS)
-    _is_the_oracles(h, k3, want.ob, NZ, want.active, "bottom temperature on the default physics")
+    is_the_oracles(h, k3, want.ob, NZ, want.active, "bottom temperature on the default physics")
     h.close()
 
 
@@ -521,7 +493,7 @@ def test_cancel_and_upload_return_to_the_plain_resident_field(mk):
     for n in both:
         h.ancillary_schedule(ac.KINDS[n][0], 1, 3, None)
     h.step(1, NSTEPS)
-    _is_the_oracles(h, k3, held.ob, NZ, held.active, "cancelled by nepochs = 0")
+    is_the_oracles(h, k3, held.ob, NZ, held.active, "cancelled by nepochs = 0")
     h.close()
     h, kc, k3 = _hip(mk, NCOL, NZ, **sw)
     _schedule(h, both, recs)
@@ -531,7 +503,7 @@ def test_cancel_and_upload_return_to_the_plain_resident_field(mk):
     cm.set_forcing_3d(k3, cm.synth.forcing(NCOL, "bench"))
     h.set_forcing(k3.sflux)
     h.step(1, NSTEPS)
-    _is_the_oracles(h, k3, held.ob, NZ, held.active, "cancelled by upload")
+    is_the_oracles(h, k3, held.ob, NZ, held.active, "cancelled by upload")
     with pytest.raises(mk.MckppHipError, match=r"needs record 0, none is resident"):   # the records went with the schedules
         h.ancillary_schedule(ac.KINDS["SST0"][0], 1, 3, sched["SST0"][1])
         h.step(1, 1)

@@ -15,6 +15,7 @@ import pytest
 
 import common as cm
 import ref_step_cases as rc
+from harness import api  # noqa: F401
 from oracle import orc
 
 FDIR = os.path.join(cm.ROOT, "mckpp_f90_amd", "fortran")
@@ -45,14 +46,6 @@ def test_oracle_with_the_override_after_every_step_is_the_reference_driver(built
         assert np.all((ob["ocnTcorr"][act, CASE.nz + 1] != 0) == (nt == 1))
     # ... and the correction switch wrote the levels above
     assert np.any(ob["tinc_fcorr"][act, 1:CASE.nz] != 0)
-
-
-@pytest.fixture(scope="module")
-def api(built):
-    import mckpp_f90_amd as mk
-
-    mk.load_library()
-    return mk.api
 
 
 def test_ctypes_signatures_match_the_header(api):

@@ -13,33 +13,13 @@ import pytest
 
 import common as cm
 import ref_step_cases as rc
+from harness import cleared, force_bench, initialised, is_the_oracles, mk  # noqa: F401
+from harness import step_golden as golden  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ENV = ("MCKPP_MULTISTEP", "MCKPP_SOLO_AFTER", "MCKPP_SOLO_LIMIT", "MCKPP_XCC_DROP", "MCKPP_PS_FIXED_L", "MCKPP_L3_CAP")
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
-def golden():
-    return rc.Golden()
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
+_clean_env = cleared(ENV)
 
 
 # ---------------------------------------------------------------------------
@@ -57,11 +37,7 @@ PRE = {None: None, "fcorr_withz": rc._fcorr_withz, "relax_ocnt": rc._relax_ocnt_
 
 def _both(ncol, nz, grid="uniform", land_every=0, pre=None, solver_mode=None, **switches):
     """Oracle const + batch and the HIP side's constants + fields of one case, before initialisation."""
-    sm = {} if solver_mode is None else {"solver_mode": solver_mode}
-    oc, ob = cm.make_oracle(ncol, nz, init=False, exp_mode=1, grid=grid, **sm, **switches)
-    kc, k3 = cm.make_hip_case(ncol, nz, grid=grid, land_every=land_every)
-    for k, v in switches.items():
-        setattr(kc, k, v)
+    oc, ob, kc, k3 = cm.make_both(ncol, nz, grid, land_every, solver_mode, **switches)
     if PRE[pre]:
         rc.apply_both(ob, k3, nz + 1, PRE[pre](ncol, nz + 1, ob))
     return oc, ob, kc, k3
@@ -99,23 +75,11 @@ def _oracle(ncol, nz, nsteps, change_at=0, **case):
 def _hip(mk, ncol, nz, shards=0, **case):
     """The HIP side of the same case, initialised and forced, ready to step."""
     oc, ob, kc, k3 = _both(ncol, nz, **case)
-    h = mk.MckppHipMulti(kc, [0] * shards) if shards else mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
+    h = initialised(mk, kc, k3, shards)
     if case.get("solver_mode") is not None:
         h.set_solver_mode(case["solver_mode"])
-    cm.set_forcing_3d(k3, cm.synth.forcing(ncol, "bench"))
-    h.set_forcing(k3.sflux)
+    force_bench(h, k3)
     return h, kc, k3
-
-
-def _is_the_oracles(h, k3, ob, nz, active, tag):
-    h.download(k3)
-    st, nf, npass = h.status()
-    assert np.array_equal(st[active], ob["status"][active]), tag
-    assert np.array_equal(npass[active], ob["npasses"][active]), tag
-    bad = {k: v for k, v in cm.compare(k3, ob, nz, rc.STEP_FIELDS, active).items() if v[2] != 0}
-    assert not bad, f"{tag}: fields differing from the oracle (max_abs, max_rel, n_values): {bad}"
 
 
 def _fields(k3, nz):
@@ -183,7 +147,7 @@ def test_one_launch_equals_the_oracle_and_the_host_override(mk, nz, grid, solver
     h.set_bottomtemp(bt)
     h.step(1, nsteps)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, ob, nz, active, f"one launch nz={nz} mode={solver_mode}")
+    is_the_oracles(h, k3, ob, nz, active, f"one launch nz={nz} mode={solver_mode}")
     assert np.array_equal(k3.X[active, nz, 0], bt[active])
     land = np.nonzero(k3.run_physics == 0)[0]
     assert len(land) and np.all(k3.tinc_fcorr[land] == 0)
@@ -203,7 +167,7 @@ def test_one_launch_equals_the_oracle_and_the_host_override(mk, nz, grid, solver
     for nt in range(1, nsteps + 1):
         h.step(nt, 1)
         h.bottomtemp(bt)
-    _is_the_oracles(h, k3, ob, nz, active, f"launch per step + host override nz={nz} mode={solver_mode}")
+    is_the_oracles(h, k3, ob, nz, active, f"launch per step + host override nz={nz} mode={solver_mode}")
     per_step = _fields(k3, nz)
     for n in rc.STEP_FIELDS:
         assert np.array_equal(one[n][active], per_step[n][active], equal_nan=True), n
@@ -238,7 +202,7 @@ def test_optional_physics_kernels(mk, variant):
     h.set_bottomtemp(bts[0])
     h.step(1, nsteps)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, ob, nz, active, variant)
+    is_the_oracles(h, k3, ob, nz, active, variant)
     assert np.array_equal(k3.X[:, nz, 0], bts[0])
     h.close()
 
@@ -257,7 +221,7 @@ def test_a_retried_step_and_a_climatology_reset(mk):
     h.set_bottomtemp(bts[0])
     h.step(1, nsteps)
     assert h.last_launch_count() == 1
-    _is_the_oracles(h, k3, ob, nz, active, "tjump + climatology")
+    is_the_oracles(h, k3, ob, nz, active, "tjump + climatology")
     assert np.array_equal(k3.X[:, nz, 0], bts[0])
     h.close()
 
@@ -291,7 +255,7 @@ def test_launch_forms(mk, monkeypatch, form):
     h.set_bottomtemp(bts[0])
     h.step(1, nsteps)
     assert h.last_launch_count() == (nsteps if form == "launch_per_step" else 1)
-    _is_the_oracles(h, k3, ob, nz, active, form)
+    is_the_oracles(h, k3, ob, nz, active, form)
     assert np.array_equal(k3.X[active, nz, 0], bts[0][active])
     h.close()
 
@@ -318,7 +282,7 @@ def test_a_new_field_between_launches_and_none(mk):
     h.step(1, 3)
     h.set_bottomtemp(bts[1])
     h.step(4, 3)
-    _is_the_oracles(h, k3, ob, nz, active, "bt1 for steps 1-3, bt2 for steps 4-6")
+    is_the_oracles(h, k3, ob, nz, active, "bt1 for steps 1-3, bt2 for steps 4-6")
     assert np.array_equal(k3.X[active, nz, 0], bts[1][active])
     h.set_bottomtemp(None)
     h.step(7, 1)
@@ -413,7 +377,7 @@ def test_beside_window_restart_and_log_schedules(mk, tmp_path):
         assert open(f, "rb").read() == open(ref, "rb").read(), f"snapshot {s}"
     nt_, pt, st, npass = h.step_log_fetch()
     assert list(zip(nt_.tolist(), pt.tolist(), st.tolist(), npass.tolist())) == want
-    _is_the_oracles(h, k3, ob, nz, active, "beside the schedules")
+    is_the_oracles(h, k3, ob, nz, active, "beside the schedules")
     h.close()
 
 
@@ -470,7 +434,7 @@ def test_three_shards_equal_the_single_context(mk):
     h.set_bottomtemp(bts[0])
     h.step(1, nsteps)
     h.synchronize()
-    _is_the_oracles(h, k3, ob, nz, active, "3 shards")
+    is_the_oracles(h, k3, ob, nz, active, "3 shards")
     multi = _fields(k3, nz)
     h.set_bottomtemp(None)
     h.close()

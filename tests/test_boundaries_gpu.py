@@ -13,41 +13,13 @@ import pytest
 
 import common as cm
 import ref_step_cases as rc
+from harness import assert_equal_to_oracle, differing, mk  # noqa: F401
+from harness import step_golden as golden  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 VMIX_FIELDS = ["hmix", "kmix", "uref", "vref", "rho", "cp", "buoy", "difm", "difs", "dift", "ghat", "Rig", "dbloc",
                "Shsq", "wXNT1"]
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
-def golden(built):
-    return rc.Golden()
-
-
-def _differing(k3, ob, nz, active, fields=rc.STEP_FIELDS):
-    return {k: v for k, v in cm.compare(k3, ob, nz, fields, active).items() if v[2] != 0}
-
-
-def _assert_equal_to_oracle(ctx, k3, ob, nz, active, what):
-    ctx.download(k3)
-    st, nf, npass = ctx.status()
-    assert np.array_equal(st[active], ob["status"][active]), f"{what}: status words"
-    assert np.array_equal(npass[active], ob["npasses"][active]), f"{what}: pass counts"
-    bad = _differing(k3, ob, nz, active)
-    assert not bad, f"{what}: fields differing from the oracle (max_abs, max_rel, n_values): {bad}"
 
 
 @pytest.mark.parametrize("solver", [0, 1])
@@ -109,8 +81,8 @@ def test_edges_through_the_launch_forms(mk, golden, monkeypatch, tag, env, one_c
         orc.physics_driver(oc, ob, nt)
         if not one_call:
             ctx.step(nt, 1)
-            _assert_equal_to_oracle(ctx, k3, ob, case.nz, act, f"{what} step {nt}")
-    _assert_equal_to_oracle(ctx, k3, ob, case.nz, act, what)
+            assert_equal_to_oracle(ctx, k3, ob, case.nz, act, f"{what} step {nt}")
+    assert_equal_to_oracle(ctx, k3, ob, case.nz, act, what)
     if "MCKPP_PS" in env:
         assert ctx.kernel_residency()[2] == 64 * int(env["MCKPP_PS"].split("x")[1])
     ctx.close()
@@ -133,13 +105,13 @@ def test_verticalmixing_alone_on_the_edges(mk, golden, tag):
         ctx.set_forcing(k3.sflux)
         ctx.step(nt, 1)
         orc.physics_driver(oc, ob, nt)
-    _assert_equal_to_oracle(ctx, k3, ob, case.nz, act, f"{tag} before vmix_only")
+    assert_equal_to_oracle(ctx, k3, ob, case.nz, act, f"{tag} before vmix_only")
     before = {n: np.array(getattr(k3, n), copy=True) for n in ("U", "X", "Us", "Xs", "hmixd", "Tref", "Ssurf")}
     ctx.vmix_only(case.nsteps + 1)
     orc.vmix_only(oc, ob, case.nsteps + 1)
     ctx.download(k3)
     ctx.close()
-    bad = _differing(k3, ob, case.nz, act, VMIX_FIELDS)
+    bad = differing(k3, ob, case.nz, act, VMIX_FIELDS)
     assert not bad, f"vmix only on {tag}: {bad}"
     for n, v in before.items():
         assert np.array_equal(getattr(k3, n), v, equal_nan=True), n

@@ -2,8 +2,9 @@
 
 The launcher's geometry (16 waves per CU) assumes at most 128 VGPRs per lane, and the kernel's speed depends on
 nothing being spilled to scratch memory - it is one 1,500-line persistent loop compiled with
--mllvm -disable-machine-licm, close to the limit, so a compiler update can tip it over.  `make resources` recompiles
-the kernel with the library's own flags and prints the code-object metadata."""
+-mllvm -disable-machine-licm, close to the limit, so a compiler update can tip it over.  `make resources` prints the
+code-object metadata from the assembly that the library's own compilation left (mckpp_kernels_ps.s), and compiles only
+if that file is missing or older than its sources."""
 import os
 import re
 import shutil

@@ -12,61 +12,18 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import api, bound_as, prototypes  # noqa: F401
 
 ROOT = cm.ROOT
 HEADER = os.path.join(ROOT, "include", "mckpp_hip.h")
 DEVICE_HEADER = os.path.join(ROOT, "include", "mckpp_hip_device.h")
 FDIR = os.path.join(ROOT, "mckpp_f90_amd", "fortran")
 FC = "/opt/rocm/bin/amdflang"
-HANDLES = ("mckpp_hip_handle", "mckpp_hip_multi_handle")
 NEW = ("fluxes_dev", "flux_ring_put_dev", "fetch_dev", "dev_fence")
 
 
-def _ctype(decl):
-    """The type of a parameter declaration or a return type without the parameter's name: "ptr" for any pointer, array
-    parameter or handle, else the type's one word."""
-    words = decl.replace("*", " * ").replace("[", " [ ").split()
-    if "*" in words or "[" in words or words[0] in HANDLES:
-        return "const char *" if words[:3] == ["const", "char", "*"] else "ptr"
-    return [w for w in words if w != "const"][0]
-
-
-def _prototypes(header):
-    """name -> (return type, [parameter types]) of every function `header` itself declares"""
-    src = open(header).read()
-    src = re.sub(r"/\*.*?\*/", "", src, flags=re.S)
-    src = re.sub(r"^\s*#.*$", "", src, flags=re.M)
-    src = re.sub(r"\{[^{}]*\}", "", src.replace('extern "C" {', ""))   # bodies of structs and enums
-    out = {}
-    for stmt in src.split(";"):
-        m = re.fullmatch(r"\s*(.*?)\b(mckpp_h(?:ip|ost)_[a-z_0-9]+)\s*\((.*)\)\s*", stmt, flags=re.S)
-        if m:
-            ret, name, params = m.groups()
-            assert name not in out, name
-            out[name] = (_ctype(ret), [] if params.strip() == "void" else [_ctype(p) for p in params.split(",")])
-    return out
-
-
-def _bound_as(header_type, t, returned=False):
-    """Is the ctypes type `t` what the header's type is bound as?"""
-    if header_type == "ptr":
-        return isinstance(t, type) and (issubclass(t, C._Pointer) or t in (C.c_void_p, C.c_char_p)) \
-            and C.sizeof(t) == C.sizeof(C.c_void_p)
-    if header_type in ("int", "int32_t"):
-        return t in (C.c_int, C.c_int32) and C.sizeof(t) == 4
-    return t is {"double": C.c_double, "int64_t": C.c_int64, "uint32_t": C.c_uint32}[header_type]
-
-
-@pytest.fixture(scope="module")
-def api(built):
-    import mckpp_f90_amd as mk
-
-    mk.load_library()
-    return mk.api
-
-
 def test_library_exports_every_function_of_the_companion_header(api):
-    protos = _prototypes(DEVICE_HEADER)
+    protos = prototypes(DEVICE_HEADER)
     assert sorted(protos) == sorted(pre + n for pre in ("mckpp_hip_", "mckpp_hip_multi_") for n in NEW)
     lib = api._lib()
     for name in protos:
@@ -74,7 +31,7 @@ def test_library_exports_every_function_of_the_companion_header(api):
 
 
 def test_device_signatures_match_the_companion_header(api):
-    protos = _prototypes(DEVICE_HEADER)
+    protos = prototypes(DEVICE_HEADER)
     table = api._signatures_device()
     assert sorted(table) == sorted(protos)
     lib = api._lib()
@@ -83,7 +40,7 @@ def test_device_signatures_match_the_companion_header(api):
         assert ret == "int" and restype is C.c_int, name
         assert len(argtypes) == len(params), f"{name} takes {len(params)} parameters, {len(argtypes)} bound"
         for i, (p, t) in enumerate(zip(params, argtypes)):
-            assert _bound_as(p, t), f"{name}: parameter {i} is {p}, bound as {t}"
+            assert bound_as(p, t), f"{name}: parameter {i} is {p}, bound as {t}"
         fn = getattr(lib, name)
         assert fn.restype is restype and list(fn.argtypes) == list(argtypes), f"{name}: _bind left another signature"
     # every function has its twin, which is the single form after the handle, and is stated once in the table
@@ -97,10 +54,10 @@ def test_device_signatures_match_the_companion_header(api):
 
 
 def test_the_first_table_still_describes_the_first_header(api):
-    protos = _prototypes(HEADER)
+    protos = prototypes(HEADER)
     assert sorted(api._signatures()) == sorted(protos)
     assert not set(api._signatures()) & set(api._signatures_device())
-    assert not set(_prototypes(DEVICE_HEADER)) & set(protos), "a device-array function declared in mckpp_hip.h"
+    assert not set(prototypes(DEVICE_HEADER)) & set(protos), "a device-array function declared in mckpp_hip.h"
 
 
 def test_plane_struct_layout_matches_the_header(api, tmp_path):

@@ -13,28 +13,13 @@ import pytest
 
 import anc_cases as ac
 import ref_loop_cases as lc
+from harness import assert_loop_step, assert_same, flux_args, loop_state, mk, resident  # noqa: F401
+from harness import loop_golden as golden  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 LAND = 1e20
 PER_CALL = 2
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch   # before the library: both bring a HIP runtime, the process must end up with one
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
-def golden(built):
-    return lc.Golden()
 
 
 def _dev(a):
@@ -43,40 +28,15 @@ def _dev(a):
     return torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 
-def _flux_args(case):
-    return dict(l_rest=case.l_rest, flsn=lc.FLSN, el=lc.EL)
-
-
-def _resident(mk, case, shards=0):
-    kc, k3 = lc.hip_raw(case)
-    h = mk.MckppHipMulti(kc, [0] * shards) if shards else mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
-    return h, kc, k3
-
-
 def _assert_golden(golden, tag, nt, h, k3, kc, what):
-    case = lc.CASES[tag]
     h.synchronize()
     h.download(k3)
-    values = golden.values(tag, "pexp") if nt == case.nsteps else None
-    bad = lc.mismatches(case, lc.LOOP_FIELDS, golden.sha(tag, "pexp")[nt - 1], lc.hip_get(k3, kc, case.nz), values)
-    assert not bad, f"{tag} step {nt}, {what}: differs from the recorded reference: {bad}"
+    assert_loop_step(golden, tag, nt, k3, kc, what)
 
 
 def _state(h, k3, kc, nz):
     h.synchronize()
-    h.download(k3)
-    get = lc.hip_get(k3, kc, nz)
-    st, nf, npass = h.status()
-    d = {n: np.array(get(n)) for n in lc.LOOP_FIELDS}
-    d["status"], d["npasses"] = np.array(st), np.array(npass)
-    return d
-
-
-def _assert_same(got, want, active, what):
-    for n in want:
-        assert np.array_equal(got[n][active], want[n][active], equal_nan=True), (what, n)
+    return loop_state(h, k3, kc, nz)
 
 
 def _bits(a):
@@ -100,7 +60,7 @@ def _ring_run(h, case, nslots, put, after_call):
         assert h.flux_ring_records() == (max(0, r0 + count - nslots), r0 + count - 1)
         wraps += r0 % nslots + count > nslots
         nt0, nt1 = r0 * nd + 1, min((r0 + count) * nd, case.nsteps)
-        h.run_forced(nt0, nt1 - nt0 + 1, nd, **_flux_args(case))
+        h.run_forced(nt0, nt1 - nt0 + 1, nd, **flux_args(case))
         after_call(nt1)
     return wraps
 
@@ -119,7 +79,7 @@ def test_the_ring_cases_reach_their_paths():
 def test_golden_cases_through_the_ring_from_device_arrays(mk, golden, tag, nslots):
     case = lc.CASES[tag]
     recd = _dev(lc.flux_records(case))
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(nslots)
     assert h.flux_ring_records() == (-1, -1)
     wraps = _ring_run(h, case, nslots, lambda r: h.flux_ring_put_dev(r, recd[r]),
@@ -136,7 +96,7 @@ def test_host_and_device_puts_alternate_in_one_ring(mk, golden, nslots):
     case = lc.CASES[tag]
     rec = lc.flux_records(case)
     recd = _dev(rec)
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(nslots)
 
     def put(r):
@@ -162,17 +122,17 @@ def _host_and_device_paths(mk, golden, tag, shards=0):
     """One context fed through fluxes, one through fluxes_dev (`shards` > 0: a multi handle), a launch per update
     interval: after every interval the same state bit for bit, and the golden digests."""
     case = lc.CASES[tag]
-    rec, args, active = lc.flux_records(case), _flux_args(case), lc.active_columns(case)
+    rec, args, active = lc.flux_records(case), flux_args(case), lc.active_columns(case)
     recd = _dev(rec)
-    a, kca, k3a = _resident(mk, case)
-    b, kcb, k3b = _resident(mk, case, shards)
+    a, kca, k3a = resident(mk, case)
+    b, kcb, k3b = resident(mk, case, shards)
     for r, nt, n in _intervals(case):
         a.fluxes(nt, *rec[r], **args)
         a.step(nt, n)
         b.fluxes_dev(nt, recd[r], **args)
         b.step(nt, n)
         want, got = _state(a, k3a, kca, case.nz), _state(b, k3b, kcb, case.nz)
-        _assert_same(got, want, active, f"{tag}: fluxes_dev against fluxes after step {nt + n - 1}")
+        assert_same(got, want, active, f"{tag}: fluxes_dev against fluxes after step {nt + n - 1}")
         _assert_golden(golden, tag, nt + n - 1, b, k3b, kcb, "fluxes_dev")
     a.close()
     b.close()
@@ -199,7 +159,7 @@ def test_fluxes_dev_waits_for_its_producer_and_the_fence_holds_the_overwrite(mk,
     tag = "every_step_nz40"
     case = lc.CASES[tag]
     recd = _dev(lc.flux_records(case))
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     side = torch.cuda.Stream()
     big = torch.empty(FILL_BYTES // 8, dtype=torch.float64, device="cuda")
     t = torch.full((8, case.ncol), float("nan"), dtype=torch.float64, device="cuda")
@@ -209,7 +169,7 @@ def test_fluxes_dev_waits_for_its_producer_and_the_fence_holds_the_overwrite(mk,
             for i in range(FILLS):
                 big.fill_(float(i))
             t.copy_(recd[r])
-        h.fluxes_dev(nt, t, stream=side, fence=True, **_flux_args(case))
+        h.fluxes_dev(nt, t, stream=side, fence=True, **flux_args(case))
         with torch.cuda.stream(side):
             t.fill_(float("nan"))
         h.step(nt, n)
@@ -224,7 +184,7 @@ def test_ring_put_dev_waits_for_its_producer_and_dev_fence_holds_the_overwrite(m
     tag = "every_step_nz40"
     case = lc.CASES[tag]
     recd = _dev(lc.flux_records(case))
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(2)
     side = torch.cuda.Stream()
     big = torch.empty(FILL_BYTES // 8, dtype=torch.float64, device="cuda")
@@ -276,8 +236,8 @@ def stepped(mk):
     def get(tag):
         if tag not in made:
             case = lc.CASES[tag]
-            h, kc, k3 = _resident(mk, case)
-            h.fluxes(1, *lc.flux_records(case)[0], **_flux_args(case))
+            h, kc, k3 = resident(mk, case)
+            h.fluxes(1, *lc.flux_records(case)[0], **flux_args(case))
             h.step(1, case.ndtocn)
             made[tag] = (h, kc, case)
         return made[tag]
@@ -355,9 +315,9 @@ def test_refusals_leave_everything_as_it_was(mk, golden):
     A, E = mk.api, mk.MckppHipError
     tag = "namelist_nz69_nd2"
     case = lc.CASES[tag]
-    nd, args, npts = case.ndtocn, _flux_args(case), case.ncol
+    nd, args, npts = case.ndtocn, flux_args(case), case.ncol
     recd = _dev(lc.flux_records(case))
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     lib, err = A._lib(), lambda: A._lib().mckpp_hip_last_error().decode()
     before = _state(h, k3, kc, case.nz)
 
@@ -401,7 +361,7 @@ def test_refusals_leave_everything_as_it_was(mk, golden):
     plane[0] = A._DevPlaneC(99, 0, 1, A.EXP_F64, 1, LAND, out.data_ptr())
     assert lib.mckpp_hip_fetch_dev(h._h, 1, plane, None) < 0 and "unknown output field 99" in err()
     assert np.array_equal(out.cpu().numpy(), np.full((1, npts), -7.0)), "a refused delivery wrote"
-    _assert_same(_state(h, k3, kc, case.nz), before, slice(None), "after the refusals")
+    assert_same(_state(h, k3, kc, case.nz), before, slice(None), "after the refusals")
     # ... and good calls then end in the golden state
     for r in range(1, lc.nrec(case)):
         h.flux_ring_put_dev(r, recd[r])
@@ -418,7 +378,7 @@ def test_two_shards_ring_from_device_arrays(mk, golden):
     tag = "sweep_nd3"
     case = lc.CASES[tag]
     recd = _dev(lc.flux_records(case))
-    h, kc, k3 = _resident(mk, case, shards=2)
+    h, kc, k3 = resident(mk, case, shards=2)
     h.flux_ring(3)
     wraps = _ring_run(h, case, 3, lambda r: h.flux_ring_put_dev(r, recd[r]),
                       lambda nt: _assert_golden(golden, tag, nt, h, k3, kc, "2 shards, device puts"))
@@ -439,8 +399,8 @@ def test_two_shards_fetch_dev(mk, stepped):
 
     A = mk.api
     one, kc, case = stepped("sweep_nd3")
-    m, kcm, k3m = _resident(mk, case, shards=2)
-    m.fluxes(1, *lc.flux_records(case)[0], **_flux_args(case))
+    m, kcm, k3m = resident(mk, case, shards=2)
+    m.fluxes(1, *lc.flux_records(case)[0], **flux_args(case))
     m.step(1, case.ndtocn)
     npts, ocean = case.ncol, lc.ocean(case).astype(bool)
     planes = [("T", 0, 1), ("hmix", 0, 1), ("u", 0, 41), ("S", 3, 30), ("wT", 0, 41)]
@@ -475,13 +435,13 @@ def test_coupled_loop_on_the_device(mk, shards):
 
     A = mk.api
     case = lc.CASES["every_step_nz40"]
-    npts, nzp1, args = case.ncol, case.nz + 1, _flux_args(case)
+    npts, nzp1, args = case.ncol, case.nz + 1, flux_args(case)
     rec = lc.flux_records(case)
     tair = 18.0 + 4.0 * np.sin(np.arange(npts) / 3.0)
     n2d = [f for f in COUPLED if A.OUT[f] in A._OUT_2D]
 
     # the host loop
-    a, kca, k3a = _resident(mk, case)
+    a, kca, k3a = resident(mk, case)
     want = []
     for nt in range(1, case.nsteps + 1):
         sst = _want(a, A, npts, nzp1, "T", 0, 1)[0]
@@ -494,7 +454,7 @@ def test_coupled_loop_on_the_device(mk, shards):
     a.close()
 
     # the device loop
-    b, kcb, k3b = _resident(mk, case, shards)
+    b, kcb, k3b = resident(mk, case, shards)
     recd, taird = _dev(rec), _dev(tair)
     sstd = torch.empty((1, npts), dtype=torch.float64, device="cuda")
     kept = [{n: torch.empty((1 if n in n2d else nzp1, npts), dtype=torch.float64, device="cuda") for n in COUPLED}
@@ -512,16 +472,16 @@ def test_coupled_loop_on_the_device(mk, shards):
     for nt, (w, k) in enumerate(zip(want, kept), 1):
         for n in COUPLED:
             assert np.array_equal(_bits(k[n].cpu().numpy()), _bits(w[n])), (n, "after interval", nt)
-    _assert_same(end_b, end_a, lc.active_columns(case), "the coupled loop's end state")
+    assert_same(end_b, end_a, lc.active_columns(case), "the coupled loop's end state")
     assert not np.array_equal(end_a["T"], _unforced_T(mk, case)), "the toy atmosphere changes nothing"
     b.close()
 
 
 def _unforced_T(mk, case):
     """T after the case's steps under its own records: what the coupled loop must differ from"""
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.set_flux_series(0, lc.flux_records(case))
-    h.run_forced(1, case.nsteps, case.ndtocn, **_flux_args(case))
+    h.run_forced(1, case.nsteps, case.ndtocn, **flux_args(case))
     out = _state(h, k3, kc, case.nz)["T"]
     h.close()
     return out

@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,18 +23,6 @@ OLD_RULES = {"MCKPP_FIRST_GUESS": "0"}
 # the library's default first margin (mckpp_runtime.cpp: FIRST_MARGIN_DEFAULT), set explicitly where a reach condition
 # is stated in terms of it
 FIRST_MARGIN = 12
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
 
 
 def _bench(ncol):

@@ -9,17 +9,10 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import api  # noqa: F401
 
 FDIR = os.path.join(cm.ROOT, "mckpp_f90_amd", "fortran")
 FC = "/opt/rocm/bin/amdflang"
-
-
-@pytest.fixture(scope="module")
-def api(built):
-    import mckpp_f90_amd as mk
-
-    mk.load_library()
-    return mk.api
 
 
 def test_new_entry_points_refuse_a_null_handle(api):

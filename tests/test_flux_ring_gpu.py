@@ -18,54 +18,19 @@ import pytest
 import anc_cases as ac
 import ref_loop_cases as lc
 import ref_step_cases as rc
+from harness import assert_loop_step, assert_same, cleared, flux_args, initialised, loop_state, mk, resident  # noqa: F401
+from harness import loop_golden as golden  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ENV = ("MCKPP_MULTISTEP", "MCKPP_SOLO_AFTER", "MCKPP_SOLO_LIMIT", "MCKPP_XCC_DROP", "MCKPP_PS_FIXED_L", "MCKPP_SOLVER_MODE")
 PER_CALL = 2
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch   # before the library: both bring a HIP runtime, the process must end up with one
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
-def golden(built):
-    return lc.Golden()
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
-
-
-def _flux_args(case):
-    return dict(l_rest=case.l_rest, flsn=lc.FLSN, el=lc.EL)
-
-
-def _resident(mk, case, shards=0):
-    kc, k3 = lc.hip_raw(case)
-    h = mk.MckppHipMulti(kc, [0] * shards) if shards else mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
-    return h, kc, k3
+_clean_env = cleared(ENV)
 
 
 def _assert_golden(golden, tag, nt, h, k3, kc, what):
-    case = lc.CASES[tag]
     h.download(k3)
-    values = golden.values(tag, "pexp") if nt == case.nsteps else None
-    bad = lc.mismatches(case, lc.LOOP_FIELDS, golden.sha(tag, "pexp")[nt - 1], lc.hip_get(k3, kc, case.nz), values)
-    assert not bad, f"{tag} step {nt}, {what}: differs from the recorded reference: {bad}"
+    assert_loop_step(golden, tag, nt, k3, kc, what)
 
 
 def _through_the_ring(h, rec, nsteps, nd, nslots, run=None, after_call=None, **args):
@@ -113,12 +78,12 @@ def test_the_cases_that_reach_a_path_are_in_the_list():
 def test_golden_cases_through_the_ring(mk, golden, tag, nslots):
     """The digest after the last step of every call, not only of the run; with 3 slots, launches whose records wrap."""
     case = lc.CASES[tag]
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(nslots)
     assert h.flux_ring_records() == (-1, -1)
     wraps = _through_the_ring(h, lc.flux_records(case), case.nsteps, case.ndtocn, nslots,
                               after_call=lambda nt: _assert_golden(golden, tag, nt, h, k3, kc, f"ring of {nslots}"),
-                              **_flux_args(case))
+                              **flux_args(case))
     assert wraps == _expect_wraps(lc.nrec(case), nslots)
     if nslots == 2:
         assert wraps == 0
@@ -137,7 +102,7 @@ def test_puts_and_launches_are_ordered_on_the_device(mk, golden):
     tag = "sweep_nd3"
     case = lc.CASES[tag]
     rec = lc.flux_records(case)
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(2)
     buf = np.empty((8, case.ncol))
     for r0 in range(0, len(rec), 2):
@@ -145,7 +110,7 @@ def test_puts_and_launches_are_ordered_on_the_device(mk, golden):
             buf[...] = rec[r]
             h.flux_ring_put(r, buf)
             buf.fill(np.nan)
-        h.run_forced(r0 * case.ndtocn + 1, 2 * case.ndtocn, case.ndtocn, **_flux_args(case))
+        h.run_forced(r0 * case.ndtocn + 1, 2 * case.ndtocn, case.ndtocn, **flux_args(case))
     _assert_golden(golden, tag, case.nsteps, h, k3, kc, "puts and launches back to back")
     h.close()
 
@@ -153,20 +118,6 @@ def test_puts_and_launches_are_ordered_on_the_device(mk, golden):
 # ---------------------------------------------------------------------------
 # 3. launch forms
 # ---------------------------------------------------------------------------
-def _state(h, k3, kc, nz, names=lc.LOOP_FIELDS):
-    h.download(k3)
-    get = lc.hip_get(k3, kc, nz)
-    st, nf, npass = h.status()
-    d = {n: np.array(get(n)) for n in names}
-    d["status"], d["npasses"] = np.array(st), np.array(npass)
-    return d
-
-
-def _assert_same(got, want, active, what):
-    for n in want:
-        assert np.array_equal(got[n][active], want[n][active], equal_nan=True), (what, n)
-
-
 def _series_run(mk, make, rec, nsteps, nd, nz, mode=None, **args):
     """set_flux_series of all records plus one run_forced"""
     h, kc, k3 = make()
@@ -174,7 +125,7 @@ def _series_run(mk, make, rec, nsteps, nd, nz, mode=None, **args):
         h.set_solver_mode(mode)
     h.set_flux_series(0, rec)
     h.run_forced(1, nsteps, nd, **args)
-    out = _state(h, k3, kc, nz)
+    out = loop_state(h, k3, kc, nz)
     h.close()
     return out
 
@@ -195,12 +146,12 @@ def test_launch_forms_against_the_golden_record(mk, golden, monkeypatch, form):
     case = lc.CASES[tag]
     for k, v in GOLDEN_FORMS[form].items():
         monkeypatch.setenv(k, v)
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(3)
     counts = []
 
     def run(nt0, n):
-        h.run_forced(nt0, n, case.ndtocn, **_flux_args(case))
+        h.run_forced(nt0, n, case.ndtocn, **flux_args(case))
         counts.append((n, h.last_launch_count()))
 
     wraps = _through_the_ring(h, lc.flux_records(case), case.nsteps, case.ndtocn, 3, run=run,
@@ -213,9 +164,9 @@ def test_launch_forms_against_the_golden_record(mk, golden, monkeypatch, form):
 def test_one_step_per_call(mk):
     """run_forced(nt, 1, ...) in a loop - k_fluxes is handed the slot's pointer - against the series run."""
     case = lc.CASES["diurnal_nz60_nd3"]
-    rec, args, active = lc.flux_records(case), _flux_args(case), lc.active_columns(case)
-    want = _series_run(mk, lambda: _resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
-    h, kc, k3 = _resident(mk, case)
+    rec, args, active = lc.flux_records(case), flux_args(case), lc.active_columns(case)
+    want = _series_run(mk, lambda: resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(3)
 
     def run(nt0, n):
@@ -223,41 +174,38 @@ def test_one_step_per_call(mk):
             h.run_forced(nt, 1, case.ndtocn, **args)
 
     assert _through_the_ring(h, rec, case.nsteps, case.ndtocn, 3, run=run) >= 1
-    _assert_same(_state(h, k3, kc, case.nz), want, active, "a step per call")
+    assert_same(loop_state(h, k3, kc, case.nz), want, active, "a step per call")
     h.close()
 
 
 def test_fewer_columns_than_slots(mk):
     """8 columns over 20 steps, records made as flux_records makes them."""
     case = lc.LoopCase(8, 40, 20, 3, seed=211, sun=True, land_every=5, calm_every=3)
-    rec, args, active = lc.flux_records(case), _flux_args(case), lc.active_columns(case)
+    rec, args, active = lc.flux_records(case), flux_args(case), lc.active_columns(case)
     assert len(rec) == 7
-    want = _series_run(mk, lambda: _resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
-    h, kc, k3 = _resident(mk, case)
+    want = _series_run(mk, lambda: resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(3)
     assert _through_the_ring(h, rec, case.nsteps, case.ndtocn, 3, **args) >= 1
-    _assert_same(_state(h, k3, kc, case.nz), want, active, "8 columns")
+    assert_same(loop_state(h, k3, kc, case.nz), want, active, "8 columns")
     h.close()
 
 
 def test_double_diffusion_kernel(mk):
     case = lc.CASES["ldd_nz60"]
-    rec, args, active = lc.flux_records(case), _flux_args(case), lc.active_columns(case)
-    want = _series_run(mk, lambda: _resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
-    h, kc, k3 = _resident(mk, case)
+    rec, args, active = lc.flux_records(case), flux_args(case), lc.active_columns(case)
+    want = _series_run(mk, lambda: resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
+    h, kc, k3 = resident(mk, case)
     assert h.kernel_name == "k_column_ps<EXT>"
     h.flux_ring(3)
     assert _through_the_ring(h, rec, case.nsteps, case.ndtocn, 3, **args) >= 1
-    _assert_same(_state(h, k3, kc, case.nz), want, active, "LDD")
+    assert_same(loop_state(h, k3, kc, case.nz), want, active, "LDD")
     h.close()
 
 
 def _relax_sst(mk, ncol=77, nz=40, **kw):
     oc, ob, kc, k3, TS = ac.both(ncol, nz, L_RELAX_SST=1, **kw)
-    h = mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
-    return h, kc, k3
+    return initialised(mk, kc, k3), kc, k3
 
 
 def test_optional_physics_kernel(mk):
@@ -270,7 +218,7 @@ def test_optional_physics_kernel(mk):
     active = np.nonzero(k3.run_physics)[0]
     h.flux_ring(3)
     assert _through_the_ring(h, rec, nsteps, nd, 3) >= 1
-    _assert_same(_state(h, k3, kc, nz), want, active, "L_RELAX_SST")
+    assert_same(loop_state(h, k3, kc, nz), want, active, "L_RELAX_SST")
     h.close()
 
 
@@ -279,13 +227,13 @@ def test_two_ended_solver(mk, monkeypatch):
     than any tolerance: the two runs do the same arithmetic on the same records)."""
     monkeypatch.setenv("MCKPP_SOLVER_MODE", "1")
     case = lc.CASES["diurnal_nz60_nd3"]
-    rec, args, active = lc.flux_records(case), _flux_args(case), lc.active_columns(case)
-    want = _series_run(mk, lambda: _resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
-    h, kc, k3 = _resident(mk, case)
+    rec, args, active = lc.flux_records(case), flux_args(case), lc.active_columns(case)
+    want = _series_run(mk, lambda: resident(mk, case), rec, case.nsteps, case.ndtocn, case.nz, **args)
+    h, kc, k3 = resident(mk, case)
     assert h.solver_mode == 1
     h.flux_ring(3)
     assert _through_the_ring(h, rec, case.nsteps, case.ndtocn, 3, **args) >= 1
-    _assert_same(_state(h, k3, kc, case.nz), want, active, "solver mode 1")
+    assert_same(loop_state(h, k3, kc, case.nz), want, active, "solver mode 1")
     h.close()
 
 
@@ -333,7 +281,7 @@ def test_beside_windows_export_snapshots_log_and_ancillary_schedule(mk, tmp_path
             files.append(tmp_path / f"snap{int(ring)}_{s}")
             h.restart_snapshot_save(s, files[-1])
         lg = h.step_log_fetch()
-        end = _state(h, k3, kc, nz, rc.STEP_FIELDS)
+        end = loop_state(h, k3, kc, nz, rc.STEP_FIELDS)
         h.close()
         return out, exp, [open(f, "rb").read() for f in files], list(zip(*[a.tolist() for a in lg])), end
 
@@ -344,21 +292,21 @@ def test_beside_windows_export_snapshots_log_and_ancillary_schedule(mk, tmp_path
         assert np.array_equal(got[1][k].view(np.uint64), want[1][k].view(np.uint64)), ("exported plane", k)
     assert got[2] == want[2], "snapshot files"
     assert got[3] == want[3], "step log"
-    _assert_same(got[4], want[4], slice(None), "end state")
+    assert_same(got[4], want[4], slice(None), "end state")
 
 
 # ---------------------------------------------------------------------------
 # 5. refusals, each followed by good calls that end in the golden state
 # ---------------------------------------------------------------------------
 def _raw_state(h, k3, kc, nz):
-    d = _state(h, k3, kc, nz)
+    d = loop_state(h, k3, kc, nz)
     return {n: v.copy() for n, v in d.items()}
 
 
 def test_refusals_leave_everything_as_it_was(mk, golden):
     tag = "namelist_nz69_nd2"
     case = lc.CASES[tag]
-    nd, args, E = case.ndtocn, _flux_args(case), mk.MckppHipError
+    nd, args, E = case.ndtocn, flux_args(case), mk.MckppHipError
     rec = lc.flux_records(case)
     assert len(rec) == 4 and case.nsteps == 8
     kc, k3 = lc.hip_raw(case)
@@ -391,7 +339,7 @@ def test_refusals_leave_everything_as_it_was(mk, golden):
     before = _raw_state(h, k3, kc, case.nz)
     with pytest.raises(E, match=r"mckpp_hip_run_forced: steps 1\.\.6 need flux records 0\.\.2, the ring of 2 slots holds 0\.\.1"):
         h.run_forced(1, 3 * nd, nd, **args)
-    _assert_same(_raw_state(h, k3, kc, case.nz), before, slice(None), "after the refused launch (record not yet put)")
+    assert_same(_raw_state(h, k3, kc, case.nz), before, slice(None), "after the refused launch (record not yet put)")
     h.run_forced(1, 2 * nd, nd, **args)
     _assert_golden(golden, tag, 2 * nd, h, k3, kc, "after the refusals")
     h.flux_ring_put(2, rec[2])
@@ -401,7 +349,7 @@ def test_refusals_leave_everything_as_it_was(mk, golden):
     before = _raw_state(h, k3, kc, case.nz)
     with pytest.raises(E, match=r"mckpp_hip_run_forced: steps 3\.\.6 need flux records 1\.\.2, the ring of 2 slots holds 2\.\.3"):
         h.run_forced(nd + 1, 2 * nd, nd, **args)
-    _assert_same(_raw_state(h, k3, kc, case.nz), before, slice(None), "after the refused launch (record overwritten)")
+    assert_same(_raw_state(h, k3, kc, case.nz), before, slice(None), "after the refused launch (record overwritten)")
     h.run_forced(2 * nd + 1, 2 * nd, nd, **args)
     _assert_golden(golden, tag, case.nsteps, h, k3, kc, "after all refusals")
     h.close()
@@ -413,12 +361,12 @@ def test_refusals_leave_everything_as_it_was(mk, golden):
 def test_cancel_and_what_cancels(mk, golden, tmp_path):
     tag = "namelist_nz69_nd2"
     case = lc.CASES[tag]
-    nd, args, E = case.ndtocn, _flux_args(case), mk.MckppHipError
+    nd, args, E = case.ndtocn, flux_args(case), mk.MckppHipError
     rec = lc.flux_records(case)
     none = "no flux ring is set"
 
     # flux_ring(0), then set_flux_series works again
-    h, kc, k3 = _resident(mk, case)
+    h, kc, k3 = resident(mk, case)
     h.flux_ring(2)
     h.flux_ring_put(0, rec[0])
     h.flux_ring(0)
@@ -474,10 +422,10 @@ def test_cancel_and_what_cancels(mk, golden, tmp_path):
 def test_three_shards(mk, golden):
     tag = "sweep_nd3"
     case = lc.CASES[tag]
-    h, kc, k3 = _resident(mk, case, shards=3)
+    h, kc, k3 = resident(mk, case, shards=3)
     h.flux_ring(3)
     assert h.flux_ring_records() == (-1, -1)
-    wraps = _through_the_ring(h, lc.flux_records(case), case.nsteps, case.ndtocn, 3, **_flux_args(case))
+    wraps = _through_the_ring(h, lc.flux_records(case), case.nsteps, case.ndtocn, 3, **flux_args(case))
     assert wraps >= 1
     h.synchronize()
     _assert_golden(golden, tag, case.nsteps, h, k3, kc, "3 shards, ring of 3")

@@ -3,25 +3,16 @@ ocnT_clim, interpolated between two records, every 2.  With flag 16 the time loo
 reads the fields from resident series (mckpp_hip_all_set_ancillary_series, mckpp_hip_all_ancillary_schedule); with flag
 1 it is the per-step driver, which forms the same fields on the host and sends them with mckpp_hip_push_ancillaries at
 those cadences.  The two are held to equality, on one device and on three shards."""
-import subprocess
-
 import numpy as np
 import pytest
 
 import common as cm
-from test_fortran_host import DRIVER, _read_out, _write_case
+from harness import drive
+from test_fortran_host import _read_out
 
 pytestmark = pytest.mark.gpu
 
 OUT = ("U", "X", "Us", "Xs", "hmix", "kmix", "hmixd", "Tref", "Ssurf", "old", "new_", "difm", "ghat", "rho")
-
-
-def _drive(tmp_path, name, kc, k3, sf, nsteps, flags, shards):
-    case, out = tmp_path / f"{name}.case", tmp_path / f"{name}.out"
-    _write_case(case, kc, k3, sf, nsteps, 0, flags=flags, shards=shards)
-    r = subprocess.run([DRIVER, str(case), str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return out
 
 
 @pytest.mark.parametrize("shards", [0, 3])
@@ -29,11 +20,11 @@ def test_one_forced_run_under_schedules_equals_the_per_step_driver(built, tmp_pa
     ncol, nz, nsteps = 77, 40, 12
     kc, k3 = cm.make_hip_case(ncol, nz, land_every=6)
     sf = cm.synth.forcing(ncol, "bench")
-    one = _read_out(_drive(tmp_path, "one", kc, k3, sf, nsteps, 2048 + 16, shards), kc, ncol)
-    per_step = _read_out(_drive(tmp_path, "per_step", kc, k3, sf, nsteps, 2048 + 1, shards), kc, ncol)
+    one = _read_out(drive(tmp_path, "one", kc, k3, sf, nsteps, 2048 + 16, shards), kc, ncol)
+    per_step = _read_out(drive(tmp_path, "per_step", kc, k3, sf, nsteps, 2048 + 1, shards), kc, ncol)
     for n in OUT:
         assert np.array_equal(one[n], per_step[n]), n
     # reach: without the relaxations the same forced run ends elsewhere, on every ocean column
-    plain = _read_out(_drive(tmp_path, "plain", kc, k3, sf, nsteps, 16, shards), kc, ncol)
+    plain = _read_out(drive(tmp_path, "plain", kc, k3, sf, nsteps, 16, shards), kc, ncol)
     act = np.nonzero(k3.run_physics)[0]
     assert np.all(np.any(plain["X"][act, :, 0] != one["X"][act, :, 0], axis=1))

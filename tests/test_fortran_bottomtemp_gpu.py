@@ -6,25 +6,17 @@ The forced run's forcing is what mckpp_fluxes assembles from the driver's consta
 held to is flags 2 + 1 (mckpp_fluxes every step, then mckpp_physics_driver with its override after the launch): flag 2
 alone steps with the case file's own sflux, which is another forcing."""
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import common as cm
-from test_fortran_host import DRIVER, _read_out, _write_case
+from harness import drive
+from test_fortran_host import _read_out
 
 pytestmark = pytest.mark.gpu
 
 OUT = ("U", "X", "Us", "Xs", "hmix", "kmix", "hmixd", "Tref", "Ssurf", "old", "new_", "difm", "ghat", "rho")
-
-
-def _drive(tmp_path, name, kc, k3, sf, nsteps, flags, shards):
-    case, out = tmp_path / f"{name}.case", tmp_path / f"{name}.out"
-    _write_case(case, kc, k3, sf, nsteps, 0, flags=flags, shards=shards)
-    r = subprocess.run([DRIVER, str(case), str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return out
 
 
 @pytest.mark.parametrize("shards", [0, 3])
@@ -32,14 +24,14 @@ def test_one_forced_run_equals_the_per_step_driver(built, tmp_path, shards):
     ncol, nz, nsteps = 77, 40, 4
     kc, k3 = cm.make_hip_case(ncol, nz, land_every=6)
     sf = cm.synth.forcing(ncol, "bench")
-    one = _read_out(_drive(tmp_path, "one", kc, k3, sf, nsteps, 2 + 16, shards), kc, ncol)
-    per_step = _read_out(_drive(tmp_path, "per_step", kc, k3, sf, nsteps, 2 + 1, shards), kc, ncol)
+    one = _read_out(drive(tmp_path, "one", kc, k3, sf, nsteps, 2 + 16, shards), kc, ncol)
+    per_step = _read_out(drive(tmp_path, "per_step", kc, k3, sf, nsteps, 2 + 1, shards), kc, ncol)
     for n in OUT:
         assert np.array_equal(one[n], per_step[n]), n
     act = np.nonzero(k3.run_physics)[0]
     assert np.array_equal(one["X"][act, nz, 0], np.asarray(k3.X[act, nz, 0]) + 0.125)   # the driver's bottom_temp
     # ... and without the switch the same forced run ends elsewhere
-    plain = _read_out(_drive(tmp_path, "plain", kc, k3, sf, nsteps, 16, shards), kc, ncol)
+    plain = _read_out(drive(tmp_path, "plain", kc, k3, sf, nsteps, 16, shards), kc, ncol)
     assert not np.array_equal(plain["X"], one["X"])
 
 
@@ -51,7 +43,7 @@ def test_snapshots_carry_the_override(built, tmp_path, shards):
     ncol, nz, nsteps = 77, 40, 4
     kc, k3 = cm.make_hip_case(ncol, nz, land_every=6)
     sf = cm.synth.forcing(ncol, "bench")
-    out = _drive(tmp_path, "snap", kc, k3, sf, nsteps, 2 + 512, shards)
+    out = drive(tmp_path, "snap", kc, k3, sf, nsteps, 2 + 512, shards)
     got = _read_out(out, kc, ncol)
     ndev, nsnap = max(1, shards), nsteps // 2
     bt = np.asarray(k3.X[:, nz, 0]) + 0.125

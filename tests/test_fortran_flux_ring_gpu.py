@@ -3,22 +3,16 @@ records go through a flux ring of 2 slots (mckpp_hip_all_flux_ring, mckpp_hip_al
 forced run of their four steps, the next pair put while that run is queued - and must leave, byte for byte, the output
 file of flag 8192 alone, whose records are all resident (mckpp_hip_all_set_flux_series) under one forced run.  On one
 device and on three shards.  And the records do change the run: the output differs from that of flag 16 alone."""
-import subprocess
-
 import pytest
 
 import common as cm
-from test_fortran_host import DRIVER, _write_case
+from harness import drive
 
 pytestmark = pytest.mark.gpu
 
 
 def _drive(tmp_path, name, kc, k3, sf, nsteps, flags, shards):
-    case, out = tmp_path / f"{name}.case", tmp_path / f"{name}.out"
-    _write_case(case, kc, k3, sf, nsteps, 0, flags=flags, shards=shards)
-    r = subprocess.run([DRIVER, str(case), str(out)], capture_output=True, text=True)
-    assert r.returncode == 0, r.stderr + r.stdout
-    return out.read_bytes()
+    return drive(tmp_path, name, kc, k3, sf, nsteps, flags, shards).read_bytes()
 
 
 @pytest.mark.parametrize("shards,nz,nsteps", [(0, 60, 12), (3, 69, 10)])

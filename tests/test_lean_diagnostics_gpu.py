@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import cleared, mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -21,24 +22,7 @@ SENTINEL = 12345.0
 SPINUP = 3
 DIAG_ARRAYS = ("rho", "cp", "buoy", "difm", "difs", "dift", "wU", "wX", "wXNT", "ghat", "Rig", "Shsq", "dbloc")
 ENV = ("MCKPP_MULTISTEP", "MCKPP_PS_FIXED_L", "MCKPP_SOLO_AFTER", "MCKPP_SOLO_LIMIT", "MCKPP_L3_CAP")
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
+_clean_env = cleared(ENV)
 
 
 def _context(mk, ncol=2000, nz=40, physics="default", solver_mode=0, trap=False, spinup=SPINUP):

@@ -14,6 +14,7 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
@@ -22,18 +23,6 @@ LAND = (4, 5)                       # land every 4th point (300 columns), then e
 NREC, NSLOTS, LOG_CAP = 64, 16, 1 << 20
 LAST, RED = ("T", "S"), ("T", "difm")
 STEPS = ((1, 3), (4, 3))            # two calls: steps 1..3, 4..6
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
 
 
 def _half_bytes(ncol):

@@ -6,20 +6,9 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch   # before the library: both bring a HIP runtime, the process must end up with one
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
 
 
 STATE = ("U", "X", "Us", "Xs", "hmixd", "hmix", "kmix", "Tref", "uref", "vref", "Ssurf", "old", "new_", "reset_flag")

@@ -7,21 +7,11 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 FIELDS = cm.PROFILE_FIELDS + cm.SCALAR_FIELDS + ["hmixd0", "hmixd1"] + list(cm.DIAG_FIELDS.keys()) + cm.EXT_SCALARS
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    return m
 
 
 def _case(mk, ncol, nz, switches, prep, nsteps=2, grid="uniform"):

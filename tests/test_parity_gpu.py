@@ -15,22 +15,11 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ALL_FIELDS = cm.PROFILE_FIELDS + cm.SCALAR_FIELDS + ["hmixd0", "hmixd1"] + list(cm.DIAG_FIELDS.keys())
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
 
 
 def _assert_bitexact(res, tag=""):

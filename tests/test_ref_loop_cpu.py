@@ -28,14 +28,10 @@ import numpy as np
 import pytest
 
 import ref_loop_cases as lc
+from harness import loop_golden as golden  # noqa: F401
 from oracle import orc
 
 BUILDS = lc.BUILDS
-
-
-@pytest.fixture(scope="module")
-def golden(built):
-    return lc.Golden()
 
 
 def test_every_case_is_recorded(golden):

@@ -10,45 +10,15 @@ import numpy as np
 import pytest
 
 import ref_loop_cases as lc
+from harness import assert_loop_step, flux_args, mk, resident  # noqa: F401
+from harness import loop_golden as golden  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch   # before the library: both bring a HIP runtime, the process must end up with one
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(scope="module")
-def golden(built):
-    return lc.Golden()
-
-
-def _assert_step(golden, tag, nt, k3, kc, what):
-    case = lc.CASES[tag]
-    values = golden.values(tag, "pexp") if nt == case.nsteps else None
-    bad = lc.mismatches(case, lc.LOOP_FIELDS, golden.sha(tag, "pexp")[nt - 1], lc.hip_get(k3, kc, case.nz), values)
-    assert not bad, f"{tag} step {nt}, {what}: differs from the recorded reference: {bad}"
-
-
-def _flux_args(case):
-    return dict(l_rest=case.l_rest, flsn=lc.FLSN, el=lc.EL)
-
-
 def _resident(mk, tag):
     """(context, KppConstFields, Kpp3dFields): the raw columns of the case uploaded and initialised on the device"""
-    kc, k3 = lc.hip_raw(lc.CASES[tag])
-    h = mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
-    return h, kc, k3
+    return resident(mk, lc.CASES[tag])
 
 
 @pytest.mark.parametrize("tag", list(lc.CASES))
@@ -63,10 +33,10 @@ def test_init_fluxes_and_steps_one_by_one(mk, golden, tag):
     rec = lc.flux_records(case)
     for nt in range(1, case.nsteps + 1):
         if (nt - 1) % case.ndtocn == 0:
-            ctx.fluxes(nt, **dict(zip(lc.FLUX_NAMES, rec[(nt - 1) // case.ndtocn])), **_flux_args(case))
+            ctx.fluxes(nt, **dict(zip(lc.FLUX_NAMES, rec[(nt - 1) // case.ndtocn])), **flux_args(case))
         ctx.step(nt, 1)
         ctx.download(k3)
-        _assert_step(golden, tag, nt, k3, kc, "fluxes + step")
+        assert_loop_step(golden, tag, nt, k3, kc, "fluxes + step")
 
 
 @pytest.mark.parametrize("tag", list(lc.CASES))
@@ -75,10 +45,10 @@ def test_forced_run_in_one_launch(mk, golden, tag):
     case = lc.CASES[tag]
     h, kc, k3 = _resident(mk, tag)
     h.set_flux_series(0, lc.flux_records(case))
-    h.run_forced(1, case.nsteps, case.ndtocn, **_flux_args(case))
+    h.run_forced(1, case.nsteps, case.ndtocn, **flux_args(case))
     assert h.last_launch_count() == 1
     h.download(k3)
-    _assert_step(golden, tag, case.nsteps, k3, kc, "one launch")
+    assert_loop_step(golden, tag, case.nsteps, k3, kc, "one launch")
 
 
 # cases with a step nd + 1 inside their second flux interval to split at; and, of those, the ones whose second call
@@ -99,16 +69,16 @@ def test_forced_run_split_inside_a_flux_interval(mk, golden, tag, later_records_
     rec = lc.flux_records(case)
     h, kc, k3 = _resident(mk, tag)
     h.set_flux_series(0, rec)
-    h.run_forced(1, first, nd, **_flux_args(case))
+    h.run_forced(1, first, nd, **flux_args(case))
     h.download(k3)
-    _assert_step(golden, tag, first, k3, kc, "first of two calls")
+    assert_loop_step(golden, tag, first, k3, kc, "first of two calls")
     if later_records_only:
         rec0 = (first + nd - 1) // nd                # the first update of steps first+1 ..
         assert 0 < rec0 < len(rec)
         h.set_flux_series(rec0, rec[rec0:])
-    h.run_forced(first + 1, case.nsteps - first, nd, **_flux_args(case))
+    h.run_forced(first + 1, case.nsteps - first, nd, **flux_args(case))
     h.download(k3)
-    _assert_step(golden, tag, case.nsteps, k3, kc, "second of two calls")
+    assert_loop_step(golden, tag, case.nsteps, k3, kc, "second of two calls")
 
 
 def test_forced_run_through_the_multi_handle(mk, golden):
@@ -123,8 +93,8 @@ def test_forced_run_through_the_multi_handle(mk, golden):
     bad = lc.mismatches(case, lc.INIT_FIELDS, golden.init_sha(tag, "pexp"), lc.hip_get(k3, kc, case.nz))
     assert not bad, f"{tag} after init, 3 shards: differs from the recorded reference: {bad}"
     m.set_flux_series(0, lc.flux_records(case))
-    m.run_forced(1, case.nsteps, case.ndtocn, **_flux_args(case))
+    m.run_forced(1, case.nsteps, case.ndtocn, **flux_args(case))
     m.synchronize()
     m.download(k3)
-    _assert_step(golden, tag, case.nsteps, k3, kc, "3 shards")
+    assert_loop_step(golden, tag, case.nsteps, k3, kc, "3 shards")
     m.close()

@@ -10,14 +10,10 @@ import numpy as np
 import pytest
 
 import ref_step_cases as rc
+from harness import step_golden as golden  # noqa: F401
 from oracle import orc
 
 BUILDS = {"libm": 0, "pexp": 1}
-
-
-@pytest.fixture(scope="module")
-def golden(built):
-    return rc.Golden()
 
 
 def _batch_get(ob, nz):

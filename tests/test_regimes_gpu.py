@@ -16,26 +16,11 @@ import pytest
 
 import common as cm
 import ref_step_cases as rc
+from harness import assert_equal_to_oracle, differing, mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 VIEWS_FORCED = {"MCKPP_SOLO_AFTER": "0", "MCKPP_SOLO_LIMIT": "1000000"}
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-def _differing(k3, ob, nz, active, fields=rc.STEP_FIELDS):
-    return {k: v for k, v in cm.compare(k3, ob, nz, fields, active).items() if v[2] != 0}
 
 
 def _start(mk, ncol, nz, grid="uniform", dto=3600.0, solver=0, switches=None, hook=rc.regime_mix, land=None, shards=0):
@@ -60,22 +45,13 @@ def _start(mk, ncol, nz, grid="uniform", dto=3600.0, solver=0, switches=None, ho
     ctx.download(k3)
     orc.init_ocean(oc, ob, 0)
     active = np.nonzero(k3.run_physics)[0]
-    bad = _differing(k3, ob, nz, active)
+    bad = differing(k3, ob, nz, active)
     assert not bad, f"init: {bad}"
     sf = cm.synth.forcing(ncol, "bench")
     ob["sflux"] = sf
     cm.set_forcing_3d(k3, sf)
     ctx.set_forcing(k3.sflux)
     return oc, ob, kc, k3, ctx, active
-
-
-def _assert_equal_to_oracle(ctx, k3, ob, nz, active, what):
-    ctx.download(k3)
-    st, nf, npass = ctx.status()
-    assert np.array_equal(st[active], ob["status"][active]), f"{what}: status words"
-    assert np.array_equal(npass[active], ob["npasses"][active]), f"{what}: pass counts"
-    bad = _differing(k3, ob, nz, active)
-    assert not bad, f"{what}: fields differing from the oracle (max_abs, max_rel, n_values): {bad}"
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -148,8 +124,8 @@ def test_regimes_through_the_launch_forms(mk, monkeypatch, nz, grid, dto, env, o
         orc.physics_driver(oc, ob, nt)
         if not one_call:
             ctx.step(nt, 1)
-            _assert_equal_to_oracle(ctx, k3, ob, nz, active, f"{what} step {nt}")
-    _assert_equal_to_oracle(ctx, k3, ob, nz, active, what)
+            assert_equal_to_oracle(ctx, k3, ob, nz, active, f"{what} step {nt}")
+    assert_equal_to_oracle(ctx, k3, ob, nz, active, what)
     if "MCKPP_PS" in env:
         assert ctx.kernel_residency()[2] == 64 * int(env["MCKPP_PS"].split("x")[1])
     ctx.close()
@@ -177,13 +153,13 @@ def test_verticalmixing_alone_over_bathymetry(mk, nz, grid):
     for nt in (1, 2):
         ctx.step(nt, 1)
         orc.physics_driver(oc, ob, nt)
-    _assert_equal_to_oracle(ctx, k3, ob, nz, active, f"nz={nz} before vmix_only")
+    assert_equal_to_oracle(ctx, k3, ob, nz, active, f"nz={nz} before vmix_only")
     before = {n: np.array(getattr(k3, n), copy=True) for n in ("U", "X", "Us", "Xs", "hmixd", "Tref", "Ssurf", "old", "new_")}
     ctx.vmix_only(3)
     orc.vmix_only(oc, ob, 3)
     ctx.download(k3)
     ctx.close()
-    bad = _differing(k3, ob, nz, active, VMIX_FIELDS)
+    bad = differing(k3, ob, nz, active, VMIX_FIELDS)
     assert not bad, f"vmix only nz={nz}: {bad}"
     for n, v in before.items():
         assert np.array_equal(getattr(k3, n), v), n
@@ -208,7 +184,7 @@ def test_kppmix_tridiag_pass_over_bathymetry(mk, nz, grid):
     ctx.download(k3)
     ctx.close()
     orc.vmix_batch(oc, ob, 1)
-    bad = _differing(k3, ob, nz, None, ["U", "V", "T", "S"] + VMIX_FIELDS)
+    bad = differing(k3, ob, nz, None, ["U", "V", "T", "S"] + VMIX_FIELDS)
     assert not bad, f"vmix pass nz={nz}: {bad}"
     assert (ob["hmix"] == -ob["ocdepth"]).sum() >= 0.05 * ncol
 
@@ -252,7 +228,7 @@ def test_forced_day_over_a_coast(mk, shards):
             orc.fluxes(oc, ob, nt, **dict(zip(cm.synth.FLUX_NAMES, series[(nt - 1) // ndtocn])))
         orc.physics_driver(oc, ob, nt)
         clamped |= ob["hmix"] == -ob["ocdepth"]
-    _assert_equal_to_oracle(ctx, k3, ob, nz, active, f"forced day, shards={shards}")
+    assert_equal_to_oracle(ctx, k3, ob, nz, active, f"forced day, shards={shards}")
     assert np.array_equal(k3.sflux[active, 0:6, 4, 0], ob["sflux"][active])
     ctx.close()
     assert clamped[active].sum() >= 0.1 * len(active), "the sea floor clamps too few columns of the coast"
@@ -274,7 +250,7 @@ def test_surface_salinity_follows_the_column(mk, nz, switches):
     for nt in (1, 2, 3):
         ctx.step(nt, 1)
         orc.physics_driver(oc, ob, nt)
-        _assert_equal_to_oracle(ctx, k3, ob, nz, active, f"{switches} nz={nz} step {nt}")
+        assert_equal_to_oracle(ctx, k3, ob, nz, active, f"{switches} nz={nz} step {nt}")
     ctx.close()
     assert np.array_equal(k3.Ssurf, k3.X[:, 0, 1] + k3.Sref) and not np.array_equal(k3.Ssurf, k3.SSref)
 

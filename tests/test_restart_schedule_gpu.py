@@ -6,22 +6,11 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 NSTEPS, P = 36, 12
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
 
 
 def _make(mk, ncol, nz, grid, nsteps=NSTEPS, land_every=7, diag=True, ext=False, shards=0):

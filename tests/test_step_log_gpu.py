@@ -11,29 +11,13 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import cleared, force_bench, initialised, is_the_oracles, mk  # noqa: F401
 
 pytestmark = pytest.mark.gpu
 
 ALL_FIELDS = cm.PROFILE_FIELDS + cm.SCALAR_FIELDS + ["hmixd0", "hmixd1"] + list(cm.DIAG_FIELDS.keys())
 ENV = ("MCKPP_MULTISTEP", "MCKPP_SOLO_AFTER", "MCKPP_SOLO_LIMIT", "MCKPP_XCC_DROP", "MCKPP_PS_FIXED_L")
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-@pytest.fixture(autouse=True)
-def _clean_env(monkeypatch):
-    for k in ENV:
-        monkeypatch.delenv(k, raising=False)
+_clean_env = cleared(ENV)
 
 
 # ---------------------------------------------------------------------------
@@ -72,14 +56,7 @@ PREP = {"none": _prep_none, "relax_sst": _prep_relax_sst, "ldd": _prep_ldd, "tra
 
 def _both(ncol, nz, itermax=200, land_every=7, prep="none", prep_after_init=False, solver_mode=None, tri_nz=None, **switches):
     """Oracle const + batch and the HIP side's constants + fields of one case, before initialisation."""
-    from oracle import orc  # noqa: F401
-
-    sm = {} if solver_mode is None else {"solver_mode": solver_mode}
-    oc, ob = cm.make_oracle(ncol, nz, init=False, exp_mode=1, itermax=itermax, **sm, **switches)
-    kc, k3 = cm.make_hip_case(ncol, nz, land_every=land_every)
-    kc.itermax = itermax
-    for k, v in switches.items():
-        setattr(kc, k, v)
+    oc, ob, kc, k3 = cm.make_both(ncol, nz, "uniform", land_every, solver_mode, itermax, **switches)
     if tri_nz is not None:   # test_zero_pivot_on_device, last level: cc(nz) = 1 + (-1e4)(1e-4) + 0 = 0
         kc.tri[nz, 0, 0], kc.tri[nz, 1, 0] = 0.0, tri_nz
         oc.tri0[nz], oc.tri1[nz] = 0.0, tri_nz
@@ -118,17 +95,14 @@ def _hip(mk, ncol, nz, shards=0, **case):
     """The HIP side of the same case, initialised and forced, ready to step."""
     case = dict(case)
     oc, ob, kc, k3 = _both(ncol, nz, **case)
-    h = mk.MckppHipMulti(kc, [0] * shards) if shards else mk.MckppHip(kc)
-    h.upload(k3)
-    h.init_ocean(0)
+    h = initialised(mk, kc, k3, shards)
     if case.get("prep_after_init"):
         h.download(k3)
         PREP[case["prep"]](k3, ob)
         h.upload(k3)
     if case.get("solver_mode") is not None:
         h.set_solver_mode(case["solver_mode"])
-    cm.set_forcing_3d(k3, cm.synth.forcing(ncol, "bench"))
-    h.set_forcing(k3.sflux)
+    force_bench(h, k3)
     return h, kc, k3
 
 
@@ -146,13 +120,7 @@ def _status_or(events):
     return int(np.bitwise_or.reduce([e[2] for e in events] or [0]))
 
 
-def _end_state_is_the_oracles(h, k3, ob, nz, active, tag):
-    h.download(k3)
-    st, nf, npass = h.status()
-    assert np.array_equal(st[active], ob["status"][active]), tag
-    assert np.array_equal(npass[active], ob["npasses"][active]), tag
-    bad = {k: v for k, v in cm.compare(k3, ob, nz, ALL_FIELDS, active).items() if v[2] != 0}
-    assert not bad, f"{tag}: fields differing from the oracle (max_abs, max_rel, n_values): {bad}"
+_end_state_is_the_oracles = functools.partial(is_the_oracles, fields=ALL_FIELDS)
 
 
 CASE1 = dict(itermax=4)   # bench forcing from the analytic start, land_every = 7: point != resident column

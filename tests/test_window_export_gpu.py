@@ -10,6 +10,8 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
+from harness import shape as _shape
 
 pytestmark = pytest.mark.gpu
 
@@ -19,25 +21,6 @@ LAND = 1e20
 NP = {"f8": np.float64, "f4": np.float32}
 BITS = {"f8": np.uint64, "f4": np.uint32}
 ENV = ("MCKPP_MULTISTEP", "MCKPP_PS_FIXED_L", "MCKPP_SOLO_AFTER", "MCKPP_SOLO_LIMIT")
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-def _shape(kc, npts, name):
-    from mckpp_f90_amd import api
-
-    two_d = name == "hmix" or api.OUT[name] >= api.OUT["fcorr"]   # (the 2-D fields: hmix, fcorr .. dampv_flag)
-    return (npts,) if two_d else (npts, kc.nzp1)
 
 
 def _ops(mask):

@@ -10,17 +10,10 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import api, null_ctx  # noqa: F401
 
 FDIR = os.path.join(cm.ROOT, "mckpp_f90_amd", "fortran")
 FC = "/opt/rocm/bin/amdflang"
-
-
-@pytest.fixture(scope="module")
-def api(built):
-    import mckpp_f90_amd as mk
-
-    mk.load_library()
-    return mk.api
 
 
 def test_new_entry_points_refuse_a_null_handle(api):
@@ -44,17 +37,9 @@ def test_new_entry_points_refuse_a_null_handle(api):
             assert entry.encode() in lib.mckpp_hip_last_error(), (entry, lib.mckpp_hip_last_error())
 
 
-def _null_ctx(api, cls):
-    """A wrapper object without a device context: whatever reaches the library fails there with "null handle"."""
-    h = cls.__new__(cls)
-    h._h = C.c_void_p()
-    h._held = {}
-    return h
-
-
 @pytest.mark.parametrize("cls", ["MckppHip", "MckppHipMulti"])
 def test_python_wrappers_check_fields_and_ops_first(api, cls):
-    h = _null_ctx(api, getattr(api, cls))
+    h = null_ctx(api, getattr(api, cls))
     out = np.zeros(4, order="F")
     # refused by the wrapper: ValueError, the library is not called
     with pytest.raises(ValueError, match="unknown output field"):

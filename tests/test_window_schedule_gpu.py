@@ -7,30 +7,13 @@ import numpy as np
 import pytest
 
 import common as cm
+from harness import mk  # noqa: F401
+from harness import shape as _shape
 
 pytestmark = pytest.mark.gpu
 
 LAST_FIELDS = ("T", "S", "hmix")
 RED_FIELDS = ("T", "S", "hmix", "difm", "wT", "rho", "Rig", "solar_in")
-
-
-@pytest.fixture(scope="module")
-def mk(built):
-    import torch
-
-    if not torch.cuda.is_available():
-        pytest.fail("GPU tests need an MI355X (no HIP device visible)")
-    import mckpp_f90_amd as m
-
-    m.load_library()
-    return m
-
-
-def _shape(kc, npts, name):
-    from mckpp_f90_amd import api
-
-    two_d = name == "hmix" or api.OUT[name] >= api.OUT["fcorr"]   # (the 2-D fields: hmix, fcorr .. dampv_flag)
-    return (npts,) if two_d else (npts, kc.nzp1)
 
 
 def _cut(kc, name, a):

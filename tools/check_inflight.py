@@ -10,7 +10,8 @@ order; an s_waitcnt lgkmcnt(N) leaves the youngest N), and reports every instruc
 a register with a read still outstanding.  It is a forward data-flow analysis over the basic blocks of every
 function: where paths merge, a read counts as outstanding if it is on any of them.
 
-    python tools/check_inflight.py            (compiles mckpp_kernels_ps.hip with the library's flags)
+    python tools/check_inflight.py            (the assembly the library's build left: `make isa`, which compiles
+                                               mckpp_kernels_ps.hip only if that file is missing or stale)
     python tools/check_inflight.py file.s
 """
 import os
