@@ -672,6 +672,153 @@ static int alloc_state(mckpp_hip_ctx *h, int64_t npts, int64_t ncol)
   return 0;
 }
 
+// A new state arrives (upload, load_restart) for the resident columns `ipt` of `npts` grid points: whatever was built
+// on the old state goes, the device state is allocated anew if its shape changes, the column map is handed over.  The
+// two callers differ in this: an upload keeps the flux ring when the column map and npts are unchanged, a restart load
+// always cancels it; and a restart load under another column map marks the optional-physics inputs as not resident -
+// they were compacted with the old map and the file carries none - where an upload sends its own right afterwards.
+static int new_state(mckpp_hip_ctx *h, int64_t npts, const std::vector<int> &ipt, bool from_restart)
+{
+  if (win_cancel_all(h)) return -1;   // the output schedules' records are of the old state
+  if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
+  if (log_cancel(h)) return -1;       // ... and the step log's records (they name resident columns)
+  if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
+  if (anc_cancel_all(h)) return -1;   // ... and the ancillary record series and their schedules (likewise)
+  const bool new_map = ipt != h->ipt;
+  // the flux ring's records were compacted with the previous column map (it waits for what it has queued)
+  if ((from_restart || new_map || npts != h->npts) && ring_cancel(h)) return -1;
+  if ((int64_t)ipt.size() != h->ncol || npts != h->npts) {
+    if (alloc_state(h, npts, (int64_t)ipt.size())) return -1;
+  }
+  if (new_map) {
+    if (h->d_series) {   // resident flux records were compacted with the previous land mask
+      h->d_series.reset();
+      h->series_nrec = 0;
+    }
+    h->land_kind = 0;   // the list of non-resident points was of the previous column map
+    if (from_restart) h->ext_inputs_resident = false;
+    h->ipt = ipt;
+  }
+  return 0;
+}
+
+// ---------------------------------------------------------------------------
+// The caller's mckpp_state_ptrs_c <-> the device-resident state, stated once: upload, download and the restart set
+// (restart_segments) read it here.
+// ---------------------------------------------------------------------------
+namespace {
+using host_state = mckpp_state_ptrs_c;
+enum { A_PROF, A_DIAG, A_CORR };        // d_prof, d_diag, d_ext_out: the correction rows, where the context carries them
+enum { L_NZP1, L_NZP2, L_NZ, L_NZ1 };   // level counts: nzp1, nzp1 + 1, nz, nz + 1
+enum { T_UP = 1, T_DOWN = 2 };
+
+// Row fields.  Slab `slab` of the `nslabs` of the member's array that the library reads or writes (transferred one by
+// one, pinned as a whole) is `lev` levels from element `off` of row `row` of the device array `arr`; a slab is nzp1
+// levels long, or (tmax) nztmax + 1.  The order is that of the transfers of an upload and of a download.
+struct row_field { double *host_state::*member; int slab, nslabs; bool tmax; int arr, row, off, lev; uint32_t group; int dir; };
+const row_field row_fields[] = {
+  {&host_state::U,  0, 2, false, A_PROF, P_U,   0, L_NZP1, MCKPP_F_PROFILES, T_UP | T_DOWN},
+  {&host_state::U,  1, 2, false, A_PROF, P_V,   0, L_NZP1, MCKPP_F_PROFILES, T_UP | T_DOWN},
+  {&host_state::X,  0, 2, false, A_PROF, P_T,   0, L_NZP1, MCKPP_F_PROFILES, T_UP | T_DOWN},
+  {&host_state::X,  1, 2, false, A_PROF, P_S,   0, L_NZP1, MCKPP_F_PROFILES, T_UP | T_DOWN},
+  {&host_state::Us, 0, 4, false, A_PROF, P_US0, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},   // Us(npts,nzp1,nvel,0:1)
+  {&host_state::Us, 1, 4, false, A_PROF, P_VS0, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::Us, 2, 4, false, A_PROF, P_US1, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::Us, 3, 4, false, A_PROF, P_VS1, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::Xs, 0, 4, false, A_PROF, P_TS0, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::Xs, 1, 4, false, A_PROF, P_SS0, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::Xs, 2, 4, false, A_PROF, P_TS1, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::Xs, 3, 4, false, A_PROF, P_SS1, 0, L_NZP1, MCKPP_F_SAVED, T_UP | T_DOWN},
+  {&host_state::U_init, 0, 2, false, A_PROF, P_UINIT, 0, L_NZP1, 0, T_UP},
+  {&host_state::U_init, 1, 2, false, A_PROF, P_VINIT, 0, L_NZP1, 0, T_UP},
+  {&host_state::rho,   0, 1, false, A_DIAG, D_RHO,   0, L_NZP2, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::cp,    0, 1, false, A_DIAG, D_CP,    0, L_NZP2, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::buoy,  0, 1, false, A_DIAG, D_BUOY,  1, L_NZP1, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::difm,  0, 1, false, A_DIAG, D_DIFM,  0, L_NZP2, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::difs,  0, 1, false, A_DIAG, D_DIFS,  0, L_NZP2, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::dift,  0, 1, false, A_DIAG, D_DIFT,  0, L_NZP2, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::ghat,  0, 1, false, A_DIAG, D_GHAT,  1, L_NZ,   MCKPP_F_DIAG, T_DOWN},
+  {&host_state::wU,    0, 2, true,  A_DIAG, D_WU1,   0, L_NZ1,  MCKPP_F_DIAG, T_DOWN},
+  {&host_state::wU,    1, 2, true,  A_DIAG, D_WU2,   0, L_NZ1,  MCKPP_F_DIAG, T_DOWN},
+  {&host_state::wX,    0, 3, true,  A_DIAG, D_WX1,   0, L_NZ1,  MCKPP_F_DIAG, T_DOWN},
+  {&host_state::wX,    1, 3, true,  A_DIAG, D_WX2,   0, L_NZ1,  MCKPP_F_DIAG, T_DOWN},
+  {&host_state::wX,    2, 3, true,  A_DIAG, D_WX3,   0, L_NZ1,  MCKPP_F_DIAG, T_DOWN},
+  {&host_state::wXNT,  0, 1, true,  A_DIAG, D_WXNT1, 0, L_NZ1,  MCKPP_F_DIAG, T_DOWN},
+  {&host_state::Rig,   0, 1, false, A_DIAG, D_RIG,   1, L_NZ,   MCKPP_F_DIAG, T_DOWN},
+  {&host_state::Shsq,  0, 1, false, A_DIAG, D_SHSQ,  1, L_NZ,   MCKPP_F_DIAG, T_DOWN},
+  {&host_state::dbloc, 0, 1, false, A_DIAG, D_DBLOC, 1, L_NZ,   MCKPP_F_DIAG, T_DOWN},
+  {&host_state::tinc_fcorr, 0, 1, false, A_CORR, O_TINC,     1, L_NZP1, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::sinc_fcorr, 0, 1, false, A_CORR, O_SINC,     1, L_NZP1, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::ocnTcorr,   0, 1, false, A_CORR, O_OCNTCORR, 1, L_NZP1, MCKPP_F_DIAG, T_DOWN},
+  {&host_state::scorr,      0, 1, false, A_CORR, O_SCORR,    1, L_NZP1, MCKPP_F_DIAG, T_DOWN},
+};
+
+// Per-column records.  The member's entry at npts * (off + off_nsflxs * nsflxs) - sflux(:,1:6,5,0) lies four times
+// (npts,nsflxs) in - is slot `slot`; an upload stores `def` for a NULL member; a download of `group` brings the slot
+// back (0: it never comes back), ext_only: on a context with the optional physics alone.  The order is that of a
+// download's packed slabs.
+struct rec_double { double *host_state::*member; int off, off_nsflxs, slot; double def; uint32_t group; bool ext_only; };
+struct rec_int { int32_t *host_state::*member; int slot, def; uint32_t group; };
+constexpr rec_double rec_doubles[] = {
+  {&host_state::hmixd, 0, 0, CS_HMIXD0, 0.0, MCKPP_F_SAVED},
+  {&host_state::hmixd, 1, 0, CS_HMIXD1, 0.0, MCKPP_F_SAVED},
+  {&host_state::hmix, 0, 0, CS_HMIX, 0.0, MCKPP_F_SCALARS},
+  {&host_state::kmix, 0, 0, CS_KMIX, 0.0, MCKPP_F_SCALARS},
+  {&host_state::Tref, 0, 0, CS_TREF, 0.0, MCKPP_F_SCALARS},
+  {&host_state::uref, 0, 0, CS_UREF, 0.0, MCKPP_F_SCALARS},
+  {&host_state::vref, 0, 0, CS_VREF, 0.0, MCKPP_F_SCALARS},
+  {&host_state::Ssurf, 0, 0, CS_SSURF, 0.0, MCKPP_F_SCALARS},
+  {&host_state::reset_flag, 0, 0, CS_RESET, 0.0, MCKPP_F_SCALARS},
+  {&host_state::dampu_flag, 0, 0, CS_DAMPU, 0.0, MCKPP_F_SCALARS},
+  {&host_state::dampv_flag, 0, 0, CS_DAMPV, 0.0, MCKPP_F_SCALARS},
+  {&host_state::freeze_flag, 0, 0, CS_FREEZE, 0.0, MCKPP_F_SCALARS},
+  {&host_state::fcorr, 0, 0, CS_FCORR, 0.0, MCKPP_F_SCALARS, true},
+  {&host_state::sflux, 0, 4, CS_SFLUX1, 0.0, MCKPP_F_SCALARS},   // sflux(:,1:6,5,0)
+  {&host_state::sflux, 1, 4, CS_SFLUX2, 0.0, MCKPP_F_SCALARS},
+  {&host_state::sflux, 2, 4, CS_SFLUX3, 0.0, MCKPP_F_SCALARS},
+  {&host_state::sflux, 3, 4, CS_SFLUX4, 0.0, MCKPP_F_SCALARS},
+  {&host_state::sflux, 4, 4, CS_SFLUX5, 0.0, MCKPP_F_SCALARS},
+  {&host_state::sflux, 5, 4, CS_SFLUX6, 0.0, MCKPP_F_SCALARS},
+  {&host_state::f, 0, 0, CS_F, 0.0, 0},
+  {&host_state::Sref, 0, 0, CS_SREF, 0.0, 0},
+  {&host_state::SSref, 0, 0, CS_SSREF, 0.0, 0},
+  {&host_state::ocdepth, 0, 0, CS_OCDEPTH, -10000.0, 0},
+};
+constexpr rec_int rec_ints[] = {
+  {&host_state::old, CI_OLD, 0, MCKPP_F_SAVED},
+  {&host_state::new_, CI_NEW, 1, MCKPP_F_SAVED},
+  {&host_state::l_initflag, CI_INITFLAG, 0, MCKPP_F_SCALARS},
+  {&host_state::jerlov, CI_JERLOV, 3, 0},
+  {&host_state::l_ocean, CI_LOCEAN, 1, 0},
+};
+static_assert(std::size(rec_doubles) <= MCKPP_CS && std::size(rec_ints) <= MCKPP_CI, "a slot per entry at the most");
+
+// where the entry lies in the member's array
+static int64_t rec_offset(const mckpp_hip_ctx *h, const rec_double &e)
+{
+  return h->npts * (e.off + (int64_t)e.off_nsflxs * h->c.nsflxs);
+}
+
+// One row field of a state view on one context: the device rows, the first element taken and the level count, the slab
+// in the caller's array, and that array as a whole with its size - what gets pinned (null: the slab alone)
+struct row_xfer { double *dev; int off, nlev; double *host; const double *whole; size_t whole_elems; };
+
+// The row fields of direction `dir` and of the groups in `mask` whose member `s` sets.  The list depends on these and
+// the pointers only, so the contexts of a multi-device handle produce lists that correspond entry by entry.
+static void row_plan(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, int dir, uint32_t mask, std::vector<row_xfer> &plan)
+{
+  const int levels[] = {h->nzp1, h->nzp1 + 1, h->nz, h->nz + 1};
+  for (const row_field &f : row_fields) {
+    double *a = s->*f.member;
+    if (!(f.dir & dir) || !a || (dir == T_DOWN && !(f.group & mask))) continue;
+    if (f.arr == A_CORR && !h->d_ext_out[O_TINC]) continue;   // (a context of the default physics has them only once something needed them)
+    double *dev = f.arr == A_PROF ? h->d_prof[f.row] : f.arr == A_DIAG ? h->d_diag[f.row] : h->d_ext_out[f.row];
+    const size_t slab = (size_t)h->npts * (f.tmax ? h->c.nztmax + 1 : h->nzp1);
+    plan.push_back({dev, f.off, levels[f.lev], a + f.slab * slab, f.nslabs > 1 ? a : nullptr, f.nslabs * slab});
+  }
+}
+}  // namespace
+
 // Inputs of the optional physics: what mckpp_boundary_update and the ancillary readers
 // rewrite on the host between steps (src/mckpp_ocean_model_3D.F90:51-55) - relaxation times and targets,
 // flux corrections, climatologies, prescribed advection.  Rows go through the staging buffer; the
@@ -736,86 +883,36 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   if (s->npts <= 0) return fail("mckpp_hip_upload: npts=%lld", (long long)s->npts);
   if (!s->U || !s->X) return fail("mckpp_hip_upload: U and X are required");
   HIPCHK(hipSetDevice(h->device));
-  if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
-  if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
-  if (log_cancel(h)) return -1;       // ... and the step log's records (they name resident columns)
-  if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
-  if (anc_cancel_all(h)) return -1;   // ... and the ancillary record series and their schedules (likewise)
   const int64_t npts = s->npts;
-  const int nzp1 = h->nzp1;
   std::vector<int> ipt;
   ipt.reserve(npts);
   for (int64_t i = 0; i < npts; ++i)
     if (!s->run_physics || s->run_physics[i]) ipt.push_back((int)i);
   const int64_t ncol = (int64_t)ipt.size();
-  // another column map: the flux ring's records were compacted with the previous one (it waits for what it has queued)
-  if ((ipt != h->ipt || npts != h->npts) && ring_cancel(h)) return -1;
-  if (ncol != h->ncol || npts != h->npts) {
-    if (alloc_state(h, npts, ncol)) return -1;
-  }
-  if (ipt != h->ipt && h->d_series) {   // resident flux records were compacted with the previous land mask
-    h->d_series.reset();
-    h->series_nrec = 0;
-  }
-  if (ipt != h->ipt) h->land_kind = 0;   // the list of non-resident points was of the previous column map
-  h->ipt = ipt;
+  if (new_state(h, npts, ipt, false)) return -1;
   if (ncol == 0) return 0;
   HIPCHK(hipMemcpyAsync(h->d_ipt, ipt.data(), (size_t)ncol * sizeof(int), hipMemcpyHostToDevice, h->stream));
-  const size_t slab = (size_t)npts * nzp1;
-  if (up_rows(h, s->U, nzp1, h->d_prof[P_U], 0, s->U, 2 * slab)) return -1;
-  if (up_rows(h, s->U + slab, nzp1, h->d_prof[P_V], 0, s->U, 2 * slab)) return -1;
-  if (up_rows(h, s->X, nzp1, h->d_prof[P_T], 0, s->X, 2 * slab)) return -1;
-  if (up_rows(h, s->X + slab, nzp1, h->d_prof[P_S], 0, s->X, 2 * slab)) return -1;
-  if (s->Us) {   // Us(npts,nzp1,nvel,0:1)
-    if (up_rows(h, s->Us + 0 * slab, nzp1, h->d_prof[P_US0], 0, s->Us, 4 * slab)) return -1;
-    if (up_rows(h, s->Us + 1 * slab, nzp1, h->d_prof[P_VS0], 0, s->Us, 4 * slab)) return -1;
-    if (up_rows(h, s->Us + 2 * slab, nzp1, h->d_prof[P_US1], 0, s->Us, 4 * slab)) return -1;
-    if (up_rows(h, s->Us + 3 * slab, nzp1, h->d_prof[P_VS1], 0, s->Us, 4 * slab)) return -1;
-  }
-  if (s->Xs) {
-    if (up_rows(h, s->Xs + 0 * slab, nzp1, h->d_prof[P_TS0], 0, s->Xs, 4 * slab)) return -1;
-    if (up_rows(h, s->Xs + 1 * slab, nzp1, h->d_prof[P_SS0], 0, s->Xs, 4 * slab)) return -1;
-    if (up_rows(h, s->Xs + 2 * slab, nzp1, h->d_prof[P_TS1], 0, s->Xs, 4 * slab)) return -1;
-    if (up_rows(h, s->Xs + 3 * slab, nzp1, h->d_prof[P_SS1], 0, s->Xs, 4 * slab)) return -1;
-  }
-  if (s->U_init) {
-    if (up_rows(h, s->U_init, nzp1, h->d_prof[P_UINIT], 0, s->U_init, 2 * slab)) return -1;
-    if (up_rows(h, s->U_init + slab, nzp1, h->d_prof[P_VINIT], 0, s->U_init, 2 * slab)) return -1;
-  }
+  std::vector<row_xfer> plan;
+  row_plan(h, s, T_UP, ~0u, plan);
+  for (const row_xfer &x : plan)
+    if (up_rows(h, x.host, x.nlev, x.dev, x.off, x.whole, x.whole_elems)) return -1;
   if (h->ext && upload_ancillaries(h, s)) return -1;
   std::vector<double> cs((size_t)ncol * MCKPP_CS, 0.0);
   std::vector<int> ci((size_t)ncol * MCKPP_CI, 0);
-  const int64_t fl_i = npts;                                        // stride of the flux index
-  const int64_t fl_5 = npts * (int64_t)h->c.nsflxs * (5 - 1);       // offset of (:,:,5,0)
+  const double *srcd[std::size(rec_doubles)];   // the members' entries, resolved outside the loop over the columns
+  const int32_t *srci[std::size(rec_ints)];
+  for (size_t j = 0; j < std::size(rec_doubles); ++j)
+    srcd[j] = s->*rec_doubles[j].member ? s->*rec_doubles[j].member + rec_offset(h, rec_doubles[j]) : nullptr;
+  for (size_t j = 0; j < std::size(rec_ints); ++j) srci[j] = s->*rec_ints[j].member;
   for (int64_t c = 0; c < ncol; ++c) {
     const int64_t i = ipt[c];
     double *r = &cs[(size_t)c * MCKPP_CS];
     int *q = &ci[(size_t)c * MCKPP_CI];
-    auto g = [&](const double *a, double def) { return a ? a[i] : def; };
-    r[CS_F] = g(s->f, 0.0);
-    r[CS_SSURF] = g(s->Ssurf, 0.0);
-    r[CS_SREF] = g(s->Sref, 0.0);
-    r[CS_SSREF] = g(s->SSref, 0.0);
-    r[CS_OCDEPTH] = g(s->ocdepth, -10000.0);
-    for (int m = 0; m < 6; ++m) r[CS_SFLUX1 + m] = s->sflux ? s->sflux[i + fl_i * m + fl_5] : 0.0;
-    r[CS_HMIXD0] = s->hmixd ? s->hmixd[i] : 0.0;
-    r[CS_HMIXD1] = s->hmixd ? s->hmixd[i + npts] : 0.0;
-    r[CS_HMIX] = g(s->hmix, 0.0);
-    r[CS_KMIX] = g(s->kmix, 0.0);
-    r[CS_UREF] = g(s->uref, 0.0);
-    r[CS_VREF] = g(s->vref, 0.0);
-    r[CS_TREF] = g(s->Tref, 0.0);
-    r[CS_RESET] = g(s->reset_flag, 0.0);
-    r[CS_DAMPU] = g(s->dampu_flag, 0.0);
-    r[CS_DAMPV] = g(s->dampv_flag, 0.0);
-    r[CS_FREEZE] = g(s->freeze_flag, 0.0);
-    r[CS_FCORR] = g(s->fcorr, 0.0);
-    q[CI_OLD] = s->old ? s->old[i] : 0;
-    q[CI_NEW] = s->new_ ? s->new_[i] : 1;
-    q[CI_JERLOV] = s->jerlov ? s->jerlov[i] : 3;
+    for (size_t j = 0; j < std::size(rec_doubles); ++j) r[rec_doubles[j].slot] = srcd[j] ? srcd[j][i] : rec_doubles[j].def;
+    for (size_t j = 0; j < std::size(rec_ints); ++j) q[rec_ints[j].slot] = srci[j] ? srci[j][i] : rec_ints[j].def;
     if (q[CI_JERLOV] < 1 || q[CI_JERLOV] > 5) return fail("mckpp_hip_upload: jerlov(%lld)=%d outside 1..5", (long long)i + 1, q[CI_JERLOV]);
-    q[CI_INITFLAG] = s->l_initflag ? (s->l_initflag[i] != 0) : 0;
-    q[CI_LOCEAN] = s->l_ocean ? (s->l_ocean[i] != 0) : 1;
+    q[CI_INITFLAG] = q[CI_INITFLAG] != 0;   // the LOGICALs: any non-zero word is .TRUE.
+    q[CI_LOCEAN] = q[CI_LOCEAN] != 0;
     q[CI_IPT] = (int)i;
   }
   HIPCHK(hipMemcpyAsync(h->d_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice, h->stream));
@@ -1606,68 +1703,6 @@ int mckpp_hip_last_kernel_ms(mckpp_hip_handle h, double *ms, int32_t *nlaunch)
 
 int32_t mckpp_hip_last_launch_count(mckpp_hip_handle h) { return h && h->timed ? h->nkernels : 0; }
 
-// What a download moves, as a list: every row field of `mask` whose host pointer is set - the device rows it
-// comes from (of THIS context), the offset of its first element in them, its number of levels, and where it goes
-// in the caller's arrays.  The list depends on the mask and the pointers only, so the contexts of a multi-device
-// handle produce lists that correspond entry by entry.
-namespace {
-struct row_xfer { const double *dev; int src_off, nlev; double *host; const double *whole; size_t whole_elems; };
-}
-
-static void download_plan(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, uint32_t mask, std::vector<row_xfer> &plan)
-{
-  const int nzp1 = h->nzp1, nz = h->nz;
-  const size_t slab = (size_t)h->npts * nzp1;
-  const double *whole = nullptr;   // the array the next slabs belong to, and its size: what gets pinned
-  size_t whole_elems = 0;
-  auto add = [&](const double *dev, int off, int nlev, double *host) { plan.push_back({dev, off, nlev, host, whole, whole_elems}); };
-  if ((mask & MCKPP_F_PROFILES)) {
-    if (s->U) { whole = s->U; whole_elems = 2 * slab; add(h->d_prof[P_U], 0, nzp1, s->U); add(h->d_prof[P_V], 0, nzp1, s->U + slab); }
-    if (s->X) { whole = s->X; whole_elems = 2 * slab; add(h->d_prof[P_T], 0, nzp1, s->X); add(h->d_prof[P_S], 0, nzp1, s->X + slab); }
-  }
-  if ((mask & MCKPP_F_SAVED)) {
-    if (s->Us) {
-      whole = s->Us; whole_elems = 4 * slab;
-      add(h->d_prof[P_US0], 0, nzp1, s->Us + 0 * slab); add(h->d_prof[P_VS0], 0, nzp1, s->Us + 1 * slab);
-      add(h->d_prof[P_US1], 0, nzp1, s->Us + 2 * slab); add(h->d_prof[P_VS1], 0, nzp1, s->Us + 3 * slab);
-    }
-    if (s->Xs) {
-      whole = s->Xs; whole_elems = 4 * slab;
-      add(h->d_prof[P_TS0], 0, nzp1, s->Xs + 0 * slab); add(h->d_prof[P_SS0], 0, nzp1, s->Xs + 1 * slab);
-      add(h->d_prof[P_TS1], 0, nzp1, s->Xs + 2 * slab); add(h->d_prof[P_SS1], 0, nzp1, s->Xs + 3 * slab);
-    }
-  }
-  whole = nullptr; whole_elems = 0;
-  if ((mask & MCKPP_F_DIAG)) {
-    const int n1 = h->c.nztmax + 1;        // extent of (0:nztmax)
-    const size_t s1 = (size_t)h->npts * n1;
-    if (s->rho) add(h->d_diag[D_RHO], 0, nzp1 + 1, s->rho);
-    if (s->cp) add(h->d_diag[D_CP], 0, nzp1 + 1, s->cp);
-    if (s->buoy) add(h->d_diag[D_BUOY], 1, nzp1, s->buoy);
-    if (s->difm) add(h->d_diag[D_DIFM], 0, nzp1 + 1, s->difm);
-    if (s->difs) add(h->d_diag[D_DIFS], 0, nzp1 + 1, s->difs);
-    if (s->dift) add(h->d_diag[D_DIFT], 0, nzp1 + 1, s->dift);
-    if (s->ghat) add(h->d_diag[D_GHAT], 1, nz, s->ghat);
-    if (s->wU) { whole = s->wU; whole_elems = 2 * s1; add(h->d_diag[D_WU1], 0, nz + 1, s->wU); add(h->d_diag[D_WU2], 0, nz + 1, s->wU + s1); }
-    if (s->wX) {
-      whole = s->wX; whole_elems = 3 * s1;
-      add(h->d_diag[D_WX1], 0, nz + 1, s->wX); add(h->d_diag[D_WX2], 0, nz + 1, s->wX + s1);
-      add(h->d_diag[D_WX3], 0, nz + 1, s->wX + 2 * s1);
-    }
-    whole = nullptr; whole_elems = 0;
-    if (s->wXNT) add(h->d_diag[D_WXNT1], 0, nz + 1, s->wXNT);
-    if (s->Rig) add(h->d_diag[D_RIG], 1, nz, s->Rig);
-    if (s->Shsq) add(h->d_diag[D_SHSQ], 1, nz, s->Shsq);
-    if (s->dbloc) add(h->d_diag[D_DBLOC], 1, nz, s->dbloc);
-    if (h->d_ext_out[O_TINC]) {
-      if (s->tinc_fcorr) add(h->d_ext_out[O_TINC], 1, nzp1, s->tinc_fcorr);
-      if (s->sinc_fcorr) add(h->d_ext_out[O_SINC], 1, nzp1, s->sinc_fcorr);
-      if (s->ocnTcorr) add(h->d_ext_out[O_OCNTCORR], 1, nzp1, s->ocnTcorr);
-      if (s->scorr) add(h->d_ext_out[O_SCORR], 1, nzp1, s->scorr);
-    }
-  }
-}
-
 // The per-column records of one context -> the caller's (npts) arrays: one transfer of each record array into
 // pinned memory, then a host loop over the context's columns.
 static int download_records(mckpp_hip_ctx *h, mckpp_state_ptrs_c *s, uint32_t mask)
@@ -1676,29 +1711,22 @@ static int download_records(mckpp_hip_ctx *h, mckpp_state_ptrs_c *s, uint32_t ma
   const int64_t npts = h->npts, ncol = h->ncol;
   const bool want_tabs = (mask & MCKPP_F_DIAG) && (s->swfrac || s->swdk_opt);
   if (!(mask & (MCKPP_F_SAVED | MCKPP_F_SCALARS)) && !want_tabs) return 0;
+  // where each entry of the record tables goes in the caller's arrays (null: not wanted), resolved once: both paths
+  // below work from it
+  constexpr int ND = (int)std::size(rec_doubles), NI = (int)std::size(rec_ints);
+  double *dd[ND];
+  int32_t *di[NI];
+  for (int j = 0; j < ND; ++j) {
+    const rec_double &e = rec_doubles[j];
+    dd[j] = (e.group & mask) && s->*e.member && (!e.ext_only || h->ext) ? s->*e.member + rec_offset(h, e) : nullptr;
+  }
+  for (int j = 0; j < NI; ++j) di[j] = (rec_ints[j].group & mask) ? s->*rec_ints[j].member : nullptr;
   if (ncol == npts && !want_tabs) {
+    mckpp_pack_list l{};   // the wanted slots, in the tables' order
+    for (int j = 0; j < ND; ++j) if (dd[j]) l.dslot[l.nd++] = rec_doubles[j].slot;
+    for (int j = 0; j < NI; ++j) if (di[j]) l.islot[l.ni++] = rec_ints[j].slot;
     // every grid point is a resident column: the wanted record slots are packed into (npts) slabs on the device and
-    // land in the caller's arrays as they are - no host loop, half the bytes
-    struct dst_d { double *p; };
-    struct dst_i { int32_t *p; };
-    mckpp_pack_list l{};
-    dst_d dd[MCKPP_CS];
-    dst_i di[MCKPP_CI];
-    auto addd = [&](double *p, int slot) { if (p) { dd[l.nd].p = p; l.dslot[l.nd++] = slot; } };
-    auto addi = [&](int32_t *p, int slot) { if (p) { di[l.ni].p = p; l.islot[l.ni++] = slot; } };
-    if (mask & MCKPP_F_SAVED) {
-      if (s->hmixd) { addd(s->hmixd, CS_HMIXD0); addd(s->hmixd + npts, CS_HMIXD1); }
-      addi(s->old, CI_OLD); addi(s->new_, CI_NEW);
-    }
-    if (mask & MCKPP_F_SCALARS) {
-      addd(s->hmix, CS_HMIX); addd(s->kmix, CS_KMIX); addd(s->Tref, CS_TREF); addd(s->uref, CS_UREF); addd(s->vref, CS_VREF);
-      addd(s->Ssurf, CS_SSURF); addd(s->reset_flag, CS_RESET); addd(s->dampu_flag, CS_DAMPU); addd(s->dampv_flag, CS_DAMPV);
-      addd(s->freeze_flag, CS_FREEZE);
-      if (h->ext) addd(s->fcorr, CS_FCORR);
-      addi(s->l_initflag, CI_INITFLAG);
-      if (s->sflux)
-        for (int m = 0; m < 6; ++m) addd(s->sflux + npts * m + npts * (int64_t)h->c.nsflxs * 4, CS_SFLUX1 + m);
-    }
+    // land in the caller's arrays as they are - no host loop, half the bytes.
     // One device block (the double slabs, then the int slabs right behind them) and ONE transfer of it into a pinned
     // block of the library's own; the caller's arrays - a dozen of them, anywhere - are filled from there by the host
     // threads.  (A transfer per array costs a round trip each: 1.8 ms of a 4.7 ms drop-in step on a link that has
@@ -1714,8 +1742,8 @@ static int download_records(mckpp_hip_ctx *h, mckpp_state_ptrs_c *s, uint32_t ma
     const double *hd = h->h_pack;
     const int *hi = reinterpret_cast<const int *>(h->h_pack + (size_t)npts * l.nd);
     for_columns(npts, [&](int64_t c0, int64_t c1) {
-      for (int j = 0; j < l.nd; ++j) memcpy(dd[j].p + c0, hd + (size_t)npts * j + c0, (size_t)(c1 - c0) * sizeof(double));
-      for (int j = 0; j < l.ni; ++j) memcpy(di[j].p + c0, hi + (size_t)npts * j + c0, (size_t)(c1 - c0) * sizeof(int));
+      for (int j = 0, k = 0; j < ND; ++j) if (dd[j]) memcpy(dd[j] + c0, hd + (size_t)npts * k++ + c0, (size_t)(c1 - c0) * sizeof(double));
+      for (int j = 0, k = 0; j < NI; ++j) if (di[j]) memcpy(di[j] + c0, hi + (size_t)npts * k++ + c0, (size_t)(c1 - c0) * sizeof(int));
     });
     return 0;
   }
@@ -1725,35 +1753,16 @@ static int download_records(mckpp_hip_ctx *h, mckpp_state_ptrs_c *s, uint32_t ma
   HIPCHK(hipStreamSynchronize(h->stream));
   const double *cs = h->h_cs;
   const int *ci = h->h_ci;
-  const bool saved = mask & MCKPP_F_SAVED, scal = mask & MCKPP_F_SCALARS;
-  const bool fc = scal && s->fcorr && h->ext;
-  double *sfl = (scal && s->sflux) ? s->sflux + npts * (int64_t)h->c.nsflxs * 4 : nullptr;   // sflux(:,1:6,5,0)
   const int *ipt = h->ipt.data();
   for_columns(ncol, [&](int64_t c0, int64_t c1) {
+    // one pass over each record; the loops over the tables have constant bounds and constant slots, so they compile to
+    // the straight lines one would write by hand: a test of the destination and a store per entry
     for (int64_t c = c0; c < c1; ++c) {
       const int64_t i = ipt[c];
       const double *r = &cs[(size_t)c * MCKPP_CS];
       const int *q = &ci[(size_t)c * MCKPP_CI];
-      if (saved) {
-        if (s->hmixd) { s->hmixd[i] = r[CS_HMIXD0]; s->hmixd[i + npts] = r[CS_HMIXD1]; }
-        if (s->old) s->old[i] = q[CI_OLD];
-        if (s->new_) s->new_[i] = q[CI_NEW];
-      }
-      if (scal) {
-        if (s->hmix) s->hmix[i] = r[CS_HMIX];
-        if (s->kmix) s->kmix[i] = r[CS_KMIX];
-        if (s->Tref) s->Tref[i] = r[CS_TREF];
-        if (s->uref) s->uref[i] = r[CS_UREF];
-        if (s->vref) s->vref[i] = r[CS_VREF];
-        if (s->Ssurf) s->Ssurf[i] = r[CS_SSURF];
-        if (s->reset_flag) s->reset_flag[i] = r[CS_RESET];
-        if (s->dampu_flag) s->dampu_flag[i] = r[CS_DAMPU];
-        if (s->dampv_flag) s->dampv_flag[i] = r[CS_DAMPV];
-        if (s->freeze_flag) s->freeze_flag[i] = r[CS_FREEZE];
-        if (s->l_initflag) s->l_initflag[i] = q[CI_INITFLAG];
-        if (fc) s->fcorr[i] = r[CS_FCORR];
-        if (sfl) for (int m = 0; m < 6; ++m) sfl[i + npts * m] = r[CS_SFLUX1 + m];
-      }
+      for (int j = 0; j < ND; ++j) if (dd[j]) dd[j][i] = r[rec_doubles[j].slot];
+      for (int j = 0; j < NI; ++j) if (di[j]) di[j][i] = q[rec_ints[j].slot];
     }
   });
   if (want_tabs) {   // level by level within a block of columns: every destination slab is written front to back
@@ -1782,9 +1791,9 @@ int mckpp_hip_download(mckpp_hip_handle h, mckpp_state_ptrs_c *s, uint32_t mask)
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   std::vector<row_xfer> plan;
-  download_plan(h, s, mask, plan);
+  row_plan(h, s, T_DOWN, mask, plan);
   for (const row_xfer &x : plan)
-    if (down_rows(h, x.dev, h->ld, x.src_off, x.nlev, x.host, x.whole, x.whole_elems)) return -1;
+    if (down_rows(h, x.dev, h->ld, x.off, x.nlev, x.host, x.whole, x.whole_elems)) return -1;
   if (download_records(h, s, mask)) return -1;   // (waits for the context's stream: the last step has finished)
   return xfer_finish(h);
 }
@@ -1802,16 +1811,36 @@ struct restart_header {
 };
 const char kRestartMagic[8] = {'M', 'C', 'K', 'P', 'P', 'R', 'S', '1'};
 
+// The payload of a restart file as device segments in file order: RESTART_ROWS whole rows (ncol * ld doubles each: the
+// profile rows in the order of the P_ enumeration, cp, rho), the cs records, the ci records.  Their source is the live
+// state, or (slot >= 0) a slot of the restart schedule's ring: the same rows in the same order but U_init / V_init, which
+// no step writes and the live rows give (k_column_ps, finish round: planes 0 .. P_UINIT - 1, then cp, rho).
+enum { RESTART_ROWS = P_COUNT + 2 };   // restart_header::nprof
+static_assert(P_UINIT == P_COUNT - 2 && P_VINIT == P_COUNT - 1 && MCKPP_SNAP_ROWS == RESTART_ROWS - 2,
+              "a snapshot slot: the profile rows, which U_init and V_init end, without those two; cp; rho");
+struct restart_seg { char *dev; size_t bytes; };
+static void restart_segments(mckpp_hip_ctx *h, int64_t slot, std::vector<restart_seg> &segs)
+{
+  const size_t rowelems = (size_t)h->ncol * h->ld, ncs = (size_t)h->ncol * MCKPP_CS, nci = (size_t)h->ncol * MCKPP_CI;
+  double *snap = slot < 0 ? nullptr : h->rs.rows + (size_t)slot * MCKPP_SNAP_ROWS * rowelems;   // the slot's next plane
+  for (int i = 0; i < RESTART_ROWS; ++i) {
+    double *row = i < P_COUNT ? h->d_prof[i] : h->d_diag[i == P_COUNT ? D_CP : D_RHO];
+    if (snap && i != P_UINIT && i != P_VINIT) { row = snap; snap += rowelems; }
+    segs.push_back({reinterpret_cast<char *>(row), rowelems * sizeof(double)});
+  }
+  segs.push_back({reinterpret_cast<char *>(slot < 0 ? h->d_cs.get() : h->rs.cs + (size_t)slot * ncs), ncs * sizeof(double)});
+  segs.push_back({reinterpret_cast<char *>(slot < 0 ? h->d_ci.get() : h->rs.ci + (size_t)slot * nci), nci * sizeof(int)});
+}
+
 // The file of a restart set - the one writer of mckpp_hip_save_restart and mckpp_hip_restart_snapshot_save: the
-// header, the column map, then what `payload` writes: P_COUNT + 2 whole rows (ncol * ld doubles each: the profile rows
-// in the order of the P_ enumeration, cp, rho), the cs records, the ci records.
+// header, the column map, then what `payload` writes: the segments of restart_segments.
 int restart_write(mckpp_hip_ctx *h, const char *who, const char *path, const std::function<bool(FILE *)> &payload)
 {
   FILE *f = fopen(path, "wb");
   if (!f) return fail("%s: cannot open %s", who, path);
   restart_header hd{};
   memcpy(hd.magic, kRestartMagic, 8);
-  hd.version = 1; hd.nz = h->nz; hd.ld = h->ld; hd.cs = MCKPP_CS; hd.ci = MCKPP_CI; hd.nprof = P_COUNT + 2;
+  hd.version = 1; hd.nz = h->nz; hd.ld = h->ld; hd.cs = MCKPP_CS; hd.ci = MCKPP_CI; hd.nprof = RESTART_ROWS;
   hd.npts = h->npts; hd.ncol = h->ncol;
   bool ok = fwrite(&hd, sizeof hd, 1, f) == 1;
   ok = ok && fwrite(h->ipt.data(), sizeof(int), (size_t)h->ncol, f) == (size_t)h->ncol;
@@ -1829,21 +1858,15 @@ int mckpp_hip_save_restart(mckpp_hip_handle h, const char *path)
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   return restart_write(h, "mckpp_hip_save_restart", path, [&](FILE *f) {
-    const size_t rowelems = (size_t)h->ncol * h->ld;
-    std::vector<double> buf(rowelems);
-    auto dump = [&](const double *d, size_t n) -> int {
-      if (n > buf.size()) buf.resize(n);
-      if (hipMemcpy(buf.data(), d, n * sizeof(double), hipMemcpyDeviceToHost) != hipSuccess) return -1;
-      return fwrite(buf.data(), sizeof(double), n, f) == n ? 0 : -1;
-    };
-    bool ok = true;
-    for (int i = 0; i < P_COUNT && ok; ++i) ok = dump(h->d_prof[i], rowelems) == 0;
-    ok = ok && dump(h->d_diag[D_CP], rowelems) == 0 && dump(h->d_diag[D_RHO], rowelems) == 0;
-    ok = ok && dump(h->d_cs, (size_t)h->ncol * MCKPP_CS) == 0;
-    std::vector<int> ci((size_t)h->ncol * MCKPP_CI);
-    ok = ok && hipMemcpy(ci.data(), h->d_ci, ci.size() * sizeof(int), hipMemcpyDeviceToHost) == hipSuccess;
-    ok = ok && fwrite(ci.data(), sizeof(int), ci.size(), f) == ci.size();
-    return ok;
+    std::vector<char> buf;
+    std::vector<restart_seg> segs;
+    restart_segments(h, -1, segs);
+    for (const restart_seg &g : segs) {
+      if (g.bytes > buf.size()) buf.resize(g.bytes);
+      if (hipMemcpy(buf.data(), g.dev, g.bytes, hipMemcpyDeviceToHost) != hipSuccess) return false;
+      if (fwrite(buf.data(), 1, g.bytes, f) != g.bytes) return false;
+    }
+    return true;
   });
 }
 
@@ -1997,22 +2020,10 @@ int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char
     if (!h->h_snap[b]) HIPCHK(h->h_snap[b].alloc(chunk));
     if (!h->ev_snap[b]) HIPCHK(h->ev_snap[b].create());
   }
-  // the file's payload as device segments: the snapshot's planes, with U_init / V_init - never written by a step -
-  // from the live rows
-  const size_t slot = (size_t)(snap % r.nslots), rowbytes = (size_t)h->ncol * h->ld * sizeof(double);
-  struct seg { const char *dev; size_t bytes; };
-  std::vector<seg> segs;
-  const double *planes = r.rows + slot * MCKPP_SNAP_ROWS * (size_t)h->ncol * h->ld;
-  auto plane = [&](int i) { return reinterpret_cast<const char *>(planes + (size_t)i * h->ncol * h->ld); };
-  for (int i = 0; i < P_UINIT; ++i) segs.push_back({plane(i), rowbytes});
-  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_UINIT].get()), rowbytes});
-  segs.push_back({reinterpret_cast<const char *>(h->d_prof[P_VINIT].get()), rowbytes});
-  segs.push_back({plane(P_UINIT), rowbytes});       // cp
-  segs.push_back({plane(P_UINIT + 1), rowbytes});   // rho
-  segs.push_back({reinterpret_cast<const char *>(r.cs + slot * (size_t)h->ncol * MCKPP_CS), (size_t)h->ncol * MCKPP_CS * sizeof(double)});
-  segs.push_back({reinterpret_cast<const char *>(r.ci + slot * (size_t)h->ncol * MCKPP_CI), (size_t)h->ncol * MCKPP_CI * sizeof(int)});
-  std::vector<seg> chunks;
-  for (const seg &g : segs)
+  const size_t slot = (size_t)(snap % r.nslots);
+  std::vector<restart_seg> segs, chunks;
+  restart_segments(h, (int64_t)slot, segs);
+  for (const restart_seg &g : segs)
     for (size_t o = 0; o < g.bytes; o += chunk) chunks.push_back({g.dev + o, std::min(chunk, g.bytes - o)});
   HIPCHK(hipStreamWaitEvent(h->snap_stream, r.ev[slot], 0));
   hipError_t herr = hipSuccess;
@@ -2170,18 +2181,18 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
   restart_header hd{};
   if (fread(&hd, sizeof hd, 1, f) != 1 || memcmp(hd.magic, kRestartMagic, 8) != 0 || hd.version != 1)
     return fail("mckpp_hip_load_restart: %s is not a restart file of this library", path);
-  if (hd.nz != h->nz || hd.ld != h->ld || hd.cs != MCKPP_CS || hd.ci != MCKPP_CI || hd.nprof != P_COUNT + 2 ||
+  if (hd.nz != h->nz || hd.ld != h->ld || hd.cs != MCKPP_CS || hd.ci != MCKPP_CI || hd.nprof != RESTART_ROWS ||
       hd.ncol <= 0 || hd.ncol > hd.npts)
     return fail("mckpp_hip_load_restart: %s was written for nz=%d (context has nz=%d) or another layout", path,
                 hd.nz, h->nz);
-  const size_t ncol = (size_t)hd.ncol, rowelems = ncol * h->ld;
-  std::vector<int> ipt(ncol), ci(ncol * MCKPP_CI);
-  std::vector<double> rows((size_t)(P_COUNT + 2) * rowelems), cs(ncol * MCKPP_CS);
-  bool ok = fread(ipt.data(), sizeof(int), ipt.size(), f) == ipt.size();
-  ok = ok && fread(rows.data(), sizeof(double), rows.size(), f) == rows.size();
-  ok = ok && fread(cs.data(), sizeof(double), cs.size(), f) == cs.size();
-  ok = ok && fread(ci.data(), sizeof(int), ci.size(), f) == ci.size();
-  if (!ok) return fail("mckpp_hip_load_restart: %s is truncated or unreadable", path);
+  const size_t ncol = (size_t)hd.ncol;
+  // the payload as the file holds it (restart_segments): the rows and the cs records, then the ci records
+  const size_t ndoubles = ncol * ((size_t)RESTART_ROWS * h->ld + MCKPP_CS), nbytes = ndoubles * sizeof(double) + ncol * MCKPP_CI * sizeof(int);
+  std::vector<int> ipt(ncol);
+  std::vector<double> payload((nbytes + 7) / sizeof(double));
+  const int *ci = reinterpret_cast<const int *>(payload.data() + ndoubles);
+  if (fread(ipt.data(), sizeof(int), ipt.size(), f) != ipt.size() || fread(payload.data(), 1, nbytes, f) != nbytes)
+    return fail("mckpp_hip_load_restart: %s is truncated or unreadable", path);
   for (size_t c = 0; c < ncol; ++c) {   // the column map scatters into (npts) arrays at download
     if (ipt[c] < 0 || ipt[c] >= hd.npts || (c > 0 && ipt[c] <= ipt[c - 1]))
       return fail("mckpp_hip_load_restart: %s has a corrupt column map (entry %zu = %d, npts = %lld)", path, c,
@@ -2189,31 +2200,15 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
     const int jw = ci[c * MCKPP_CI + CI_JERLOV];
     if (jw < 1 || jw > 5) return fail("mckpp_hip_load_restart: %s: jerlov=%d in column %zu", path, jw, c);
   }
-  if (win_cancel_all(h)) return -1;   // a new state: the output schedules' records are of the old one
-  if (snap_cancel(h)) return -1;      // ... and the restart schedule's snapshots
-  if (log_cancel(h)) return -1;       // ... and the step log's records
-  if (bt_cancel(h)) return -1;        // ... and the resident bottom temperature (the column map may change)
-  if (anc_cancel_all(h)) return -1;   // ... and the ancillary record series and their schedules (likewise)
-  if (ring_cancel(h)) return -1;      // ... and the flux ring (likewise)
-  const bool same_shape = hd.ncol == h->ncol && hd.npts == h->npts;
-  if (!same_shape) {
-    if (alloc_state(h, hd.npts, hd.ncol)) return -1;
-  } else if (ipt != h->ipt) {
-    if (h->d_series) {   // resident flux records were compacted with the previous land mask
-      h->d_series.reset();
-      h->series_nrec = 0;
-    }
-    h->ext_inputs_resident = false;   // and so were the optional-physics inputs
-  }
-  if (ipt != h->ipt) h->land_kind = 0;   // the list of non-resident points was of the previous column map
-  h->ipt = ipt;
+  if (new_state(h, hd.npts, ipt, true)) return -1;
   HIPCHK(hipMemcpy(h->d_ipt, ipt.data(), ipt.size() * sizeof(int), hipMemcpyHostToDevice));
-  for (int i = 0; i < P_COUNT; ++i)
-    HIPCHK(hipMemcpy(h->d_prof[i], rows.data() + (size_t)i * rowelems, rowelems * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_diag[D_CP], rows.data() + (size_t)P_COUNT * rowelems, rowelems * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_diag[D_RHO], rows.data() + (size_t)(P_COUNT + 1) * rowelems, rowelems * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_cs, cs.data(), cs.size() * sizeof(double), hipMemcpyHostToDevice));
-  HIPCHK(hipMemcpy(h->d_ci, ci.data(), ci.size() * sizeof(int), hipMemcpyHostToDevice));
+  const char *src = reinterpret_cast<const char *>(payload.data());
+  std::vector<restart_seg> segs;
+  restart_segments(h, -1, segs);
+  for (const restart_seg &g : segs) {
+    HIPCHK(hipMemcpy(g.dev, src, g.bytes, hipMemcpyHostToDevice));
+    src += g.bytes;
+  }
   return 0;
 }
 
@@ -3483,12 +3478,12 @@ int mckpp_hip_multi_download(mckpp_hip_multi_handle m, mckpp_state_ptrs_c *s, ui
   if (s->npts != m->npts) return fail("mckpp_hip_multi_download: npts=%lld but %lld were uploaded", (long long)s->npts, (long long)m->npts);
   const int ndev = (int)m->ctx.size();
   std::vector<std::vector<row_xfer>> plans(ndev);
-  for (int d = 0; d < ndev; ++d) download_plan(m->ctx[d], s, mask, plans[d]);
+  for (int d = 0; d < ndev; ++d) row_plan(m->ctx[d], s, T_DOWN, mask, plans[d]);
   std::vector<const double *> src(ndev);
   for (size_t e = 0; e < plans[0].size(); ++e) {
     for (int d = 0; d < ndev; ++d) src[d] = plans[d][e].dev;
     const row_xfer &x = plans[0][e];
-    if (multi_gather_rows(m, 0, src, m->ctx[0]->ld, x.src_off, x.nlev, x.host, x.whole, x.whole_elems)) return -1;
+    if (multi_gather_rows(m, 0, src, m->ctx[0]->ld, x.off, x.nlev, x.host, x.whole, x.whole_elems)) return -1;
   }
   for (auto *x : m->ctx) {
     if (x->ncol == 0) continue;
