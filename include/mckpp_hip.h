@@ -24,6 +24,9 @@
  *  - all functions return 0 on success, <0 on error (text from
  *    mckpp_hip_last_error()).  Numerical conditions never abort: they are
  *    reported per column through the status bitmask.
+ *  - no C++ exception leaves the library - it is an error like any other -
+ *    and every error text begins with the function's name (a failed HIP call
+ *    is named instead, with its source line).
  *  - not re-entrant; call from one host thread per handle.
  *
  * Every array pointer here is a host pointer.  The companion header

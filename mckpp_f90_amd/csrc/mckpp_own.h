@@ -1,13 +1,108 @@
-// mckpp_own.h - move-only owners of the HIP resources of the host runtime (mckpp_runtime.cpp): device blocks, pinned
-// host blocks, events, streams.  Host code only.
+// mckpp_own.h - what the host runtime (mckpp_runtime.cpp) owns at its C boundary.  Host code only.
 //
-// An owner never synchronises and never reports an error from its destructor: whoever drops a buffer that queued work
-// may still use waits first, at the call site.  (The one wait in this file is pinned_turns::take, which is that type's
-// purpose.)
+// The error state: the thread's last error text (g_err, fail, HIPCHK) and the one guard every extern "C" function goes
+// through (entry): a null pointer for the handle is refused by the function's name, and no C++ exception leaves the
+// library - it becomes -1 and a text.  for_columns, the host's loop over the columns on a few threads, is here because
+// the guard must be able to guard it: it joins what it started and brings a worker's exception back to the caller's
+// thread.
+//
+// The resources: move-only owners of device blocks, pinned host blocks, events and streams, and half_built, the owner
+// of an object until its init function hands it out.  An owner never synchronises and never reports an error from its
+// destructor: whoever drops a buffer that queued work may still use waits first, at the call site.  (The one wait in
+// this file is pinned_turns::take, which is that type's purpose.)
 #ifndef MCKPP_OWN_H
 #define MCKPP_OWN_H
 
 #include <hip/hip_runtime.h>
+
+#include <cstdarg>
+#include <cstdint>
+#include <cstdio>
+#include <cstdlib>
+#include <exception>
+#include <memory>
+#include <string>
+#include <thread>
+#include <vector>
+
+inline thread_local std::string g_err;
+
+inline int fail(const char *fmt, ...)
+{
+  char buf[512];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(buf, sizeof buf, fmt, ap);
+  va_end(ap);
+  g_err = buf;
+  return -1;
+}
+
+#define HIPCHK(expr)                                                                     \
+  do {                                                                                   \
+    hipError_t e_ = (expr);                                                              \
+    if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+  } while (0)
+
+// The guard of an extern "C" function that returns an error code: `who` is its __func__ (evaluated there, not in the
+// body's lambda), `body` its code, which returns what the function returns - HIPCHK inside it returns from it.
+template <class F>
+int entry(const char *who, F &&body) noexcept
+{
+  try {
+    return body();
+  } catch (const std::exception &e) {
+    return fail("%s: %s", who, e.what());
+  } catch (...) {
+    return fail("%s: unknown exception", who);
+  }
+}
+
+// ... of one that takes a handle
+template <class H, class F>
+int entry(const char *who, H *h, F &&body) noexcept
+{
+  return entry(who, [&]() -> int { return h ? body() : fail("%s: null handle", who); });
+}
+
+// An object between `new` and the end of its init function: finalized by Fin unless release() hands it out.
+template <class T, int (*Fin)(T *)>
+struct finalizes {
+  void operator()(T *p) const { (void)Fin(p); }
+};
+template <class T, int (*Fin)(T *)>
+using half_built = std::unique_ptr<T, finalizes<T, Fin>>;
+
+// The host loops over the columns (compaction of the forcing, scatter of the per-column records) on a few
+// threads: at 1e5 columns they are milliseconds of a 3.4 ms step otherwise.  MCKPP_HIP_HOST_THREADS sets the count
+// (default: the machine's, at most 8).  Every thread started is joined before the call is left, by return or by
+// exception; the first chunk's exception (in chunk order) is rethrown on the caller's thread once all have been.
+template <class F>
+void for_columns(int64_t n, F &&body)
+{
+  static const int want = [] {
+    const char *e = getenv("MCKPP_HIP_HOST_THREADS");
+    int t = e ? atoi(e) : (int)std::thread::hardware_concurrency();
+    return t < 1 ? 1 : t > 8 ? 8 : t;
+  }();
+  const int nt = n < 32768 ? 1 : want;
+  if (nt == 1) { body((int64_t)0, n); return; }
+  const int64_t chunk = (n + nt - 1) / nt;
+  std::vector<std::exception_ptr> thrown((size_t)nt);   // a slot per chunk: nothing to lock
+  auto run = [&](int t, int64_t a, int64_t b) noexcept {
+    try { body(a, b); } catch (...) { thrown[(size_t)t] = std::current_exception(); }
+  };
+  {
+    struct joined { std::vector<std::thread> th; ~joined() { for (auto &x : th) x.join(); } } j;
+    j.th.reserve((size_t)nt - 1);
+    for (int t = 1; t < nt; ++t) {
+      const int64_t a = t * chunk, b = a + chunk < n ? a + chunk : n;
+      if (a < b) j.th.emplace_back([&run, t, a, b] { run(t, a, b); });
+    }
+    run(0, (int64_t)0, chunk < n ? chunk : n);
+  }
+  for (auto &e : thrown) if (e) std::rethrow_exception(e);
+}
 
 // a hipMalloc block of n elements
 template <class T>

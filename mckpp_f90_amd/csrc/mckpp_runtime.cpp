@@ -5,6 +5,13 @@
 // and a pair of events per context.  No CPU fallback exists: every entry
 // point that computes does so by launching the gfx950 kernels of
 // mckpp_kernels.hip, and fails with an error code if HIP is unavailable.
+//
+// Every extern "C" function that returns an error code is `return entry(__func__, handle, body)` (mckpp_own.h): a null
+// pointer for the handle and any C++ exception become -1 and a text that begins with the function's name (the body
+// keeps the function's indentation: the lambda is the function).  The few that return something else - the
+// finalizers, a count, a name, the void host helpers - keep their documented result for no handle and hold nothing
+// that can throw (no allocation, no container growth, no call of fail); mckpp_hip_multi_ctx, which does report
+// through fail, has the barrier.  (The header declares them without noexcept, so their definitions cannot carry it.)
 #include "../../include/mckpp_hip_device.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
@@ -12,59 +19,14 @@
 
 #include <algorithm>
 #include <cmath>
-#include <cstdarg>
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
-#include <exception>
 #include <functional>
 #include <string>
-#include <thread>
 #include <vector>
 
 namespace {
-
-thread_local std::string g_err;
-
-int fail(const char *fmt, ...)
-{
-  char buf[512];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(buf, sizeof buf, fmt, ap);
-  va_end(ap);
-  g_err = buf;
-  return -1;
-}
-
-#define HIPCHK(expr)                                                                     \
-  do {                                                                                   \
-    hipError_t e_ = (expr);                                                              \
-    if (e_ != hipSuccess) return fail("%s: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
-  } while (0)
-
-// The host loops over the columns (compaction of the forcing, scatter of the per-column records) on a few
-// threads: at 1e5 columns they are milliseconds of a 3.4 ms step otherwise.  MCKPP_HIP_HOST_THREADS sets the count
-// (default: the machine's, at most 8).
-template <class F>
-void for_columns(int64_t n, F &&body)
-{
-  static const int want = [] {
-    const char *e = getenv("MCKPP_HIP_HOST_THREADS");
-    int t = e ? atoi(e) : (int)std::thread::hardware_concurrency();
-    return t < 1 ? 1 : t > 8 ? 8 : t;
-  }();
-  const int nt = n < 32768 ? 1 : want;
-  if (nt == 1) { body((int64_t)0, n); return; }
-  std::vector<std::thread> th;
-  const int64_t chunk = (n + nt - 1) / nt;
-  for (int t = 1; t < nt; ++t) {
-    const int64_t a = t * chunk, b = a + chunk < n ? a + chunk : n;
-    if (a < b) th.emplace_back([&body, a, b] { body(a, b); });
-  }
-  body((int64_t)0, chunk < n ? chunk : n);
-  for (auto &x : th) x.join();
-}
 
 // profile rows (element j <-> level j+1)
 enum { P_U = 0, P_V, P_T, P_S, P_US0, P_US1, P_VS0, P_VS1, P_TS0, P_TS1, P_SS0, P_SS1, P_UINIT, P_VINIT, P_COUNT };
@@ -283,10 +245,12 @@ const char *mckpp_hip_build_compiler(void) { return MCKPP_BUILD_COMPILER; }
 
 int mckpp_hip_device_count(void)
 {
+  return entry(__func__, [&]() -> int {
   int n = 0;
   hipError_t e = hipGetDeviceCount(&n);
   if (e != hipSuccess) return fail("hipGetDeviceCount: %s", hipGetErrorString(e));
   return n;
+  });
 }
 
 // mckpp_physics_lookup, src/mckpp_physics_lookup_mod.F90:11-66 (host, libm pow).
@@ -339,6 +303,7 @@ void mckpp_host_tri(int32_t nz, int32_t nztmax, double dto, const double *zm, co
 
 int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
 {
+  return entry(__func__, [&]() -> int {
   if (!c || !out) return fail("mckpp_hip_init: null argument");
   if (c->nz < 2) return fail("mckpp_hip_init: nz=%d (need >= 2)", c->nz);
   if (c->nztmax < c->nz + 1) return fail("mckpp_hip_init: nztmax=%d < nzp1=%d", c->nztmax, c->nz + 1);
@@ -368,9 +333,9 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   if (strncmp(prop.gcnArchName, "gfx950", 6) != 0)
     return fail("mckpp_hip_init: device %d is %s; this library carries gfx950 code only", device, prop.gcnArchName);
 
-  mckpp_hip_ctx *h = new mckpp_hip_ctx();
-  // any failure below releases what has been created so far (the HIPCHK returns included)
-  struct guard { mckpp_hip_ctx *p; ~guard() { if (p) mckpp_hip_finalize(p); } } g{h};
+  // any failure below releases what has been created so far (the HIPCHK returns and a throw included)
+  half_built<mckpp_hip_ctx, mckpp_hip_finalize> g(new mckpp_hip_ctx());
+  mckpp_hip_ctx *h = g.get();
   h->device = device;
   h->c = *c;
   h->nz = c->nz;
@@ -501,9 +466,9 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   HIPCHK(hipMemcpy(h->d_wtab, wtab.data(), nt * sizeof(double2), hipMemcpyHostToDevice));
   // the host pointers are not kept
   h->c.zm = h->c.hm = h->c.dm = h->c.tri = h->c.wmt = h->c.wst = nullptr;
-  g.p = nullptr;
-  *out = h;
+  *out = g.release();
   return 0;
+  });
 }
 
 static int win_cancel_all(mckpp_hip_ctx *h);
@@ -633,7 +598,6 @@ static int xfer_finish(mckpp_hip_ctx *h)
   HIPCHK(hipStreamSynchronize(h->copy_stream));
   return 0;
 }
-
 
 // Device buffers of the column state for `ncol` resident columns out of `npts` grid points (every
 // row zeroed).  Used by upload and by load_restart, so a context with the optional physics gets
@@ -823,7 +787,7 @@ static void row_plan(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, int dir, uin
 // rewrite on the host between steps (src/mckpp_ocean_model_3D.F90:51-55) - relaxation times and targets,
 // flux corrections, climatologies, prescribed advection.  Rows go through the staging buffer; the
 // per-column scalars are compacted on the host.
-static int upload_ancillaries(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, const char *who = "mckpp_hip_upload")
+static int upload_ancillaries(mckpp_hip_ctx *h, const mckpp_state_ptrs_c *s, const char *who)
 {
   const mckpp_const_c &k = h->c;
   const int64_t npts = h->npts, ncol = h->ncol;
@@ -879,7 +843,8 @@ static void fill_params(mckpp_hip_ctx *h, mckpp_kparams &p, int ntime, int mode)
 
 int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
 {
-  if (!h || !s) return fail("mckpp_hip_upload: null argument");
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  if (!s) return fail("mckpp_hip_upload: null argument");
   if (s->npts <= 0) return fail("mckpp_hip_upload: npts=%lld", (long long)s->npts);
   if (!s->U || !s->X) return fail("mckpp_hip_upload: U and X are required");
   HIPCHK(hipSetDevice(h->device));
@@ -896,7 +861,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   row_plan(h, s, T_UP, ~0u, plan);
   for (const row_xfer &x : plan)
     if (up_rows(h, x.host, x.nlev, x.dev, x.off, x.whole, x.whole_elems)) return -1;
-  if (h->ext && upload_ancillaries(h, s)) return -1;
+  if (h->ext && upload_ancillaries(h, s, who)) return -1;
   std::vector<double> cs((size_t)ncol * MCKPP_CS, 0.0);
   std::vector<int> ci((size_t)ncol * MCKPP_CI, 0);
   const double *srcd[std::size(rec_doubles)];   // the members' entries, resolved outside the loop over the columns
@@ -919,6 +884,7 @@ int mckpp_hip_upload(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
   HIPCHK(hipMemcpyAsync(h->d_ci, ci.data(), ci.size() * sizeof(int), hipMemcpyHostToDevice, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
+  });
 }
 
 static int ensure_host_f(mckpp_hip_ctx *h, size_t elems)
@@ -931,7 +897,8 @@ static int ensure_host_f(mckpp_hip_ctx *h, size_t elems)
 
 int mckpp_hip_set_forcing(mckpp_hip_handle h, const double *sflux)
 {
-  if (!h || !sflux) return fail("mckpp_hip_set_forcing: null argument");
+  return entry(__func__, h, [&]() -> int {
+  if (!sflux) return fail("mckpp_hip_set_forcing: null argument");
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   // sflux(:,1:6,5,0) is six contiguous (npts) slabs: up as they are (from the caller's array, pinned on first
@@ -946,6 +913,7 @@ int mckpp_hip_set_forcing(mckpp_hip_handle h, const double *sflux)
   HIPCHK(mckpp_launch_unpack_sflux(h->d_stage, h->d_ipt, h->d_cs, h->ncol, h->npts, h->stream));
   HIPCHK(hipEventSynchronize(h->ev_f));
   return 0;
+  });
 }
 
 // mckpp_fluxes (src/mckpp_fluxes_mod.F90:35-89) on the device: eight forcing fields (npts each, 3D
@@ -954,7 +922,8 @@ int mckpp_hip_fluxes(mckpp_hip_handle h, int ntime, const double *taux, const do
                      const double *lwf, const double *lhf, const double *shf, const double *rain,
                      const double *snow, int l_rest, double flsn, double el)
 {
-  if (!h || !taux || !tauy || !swf || !lwf || !lhf || !shf || !rain || !snow)
+  return entry(__func__, h, [&]() -> int {
+  if (!taux || !tauy || !swf || !lwf || !lhf || !shf || !rain || !snow)
     return fail("mckpp_hip_fluxes: null argument");
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
@@ -970,6 +939,7 @@ int mckpp_hip_fluxes(mckpp_hip_handle h, int ntime, const double *taux, const do
   fill_params(h, p, ntime, MCKPP_MODE_STEP);
   HIPCHK(mckpp_launch_fluxes(p, ntime, h->d_stage, l_rest, flsn, el, h->stream));
   return 0;
+  });
 }
 
 // default-physics contexts carry no correction rows until someone needs them
@@ -985,7 +955,8 @@ static int ensure_correction_rows(mckpp_hip_ctx *h)
 
 int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
 {
-  if (!h || !bottom_temp) return fail("mckpp_hip_bottomtemp: null argument");
+  return entry(__func__, h, [&]() -> int {
+  if (!bottom_temp) return fail("mckpp_hip_bottomtemp: null argument");
   if (h->d_bot_temp)
     return fail("mckpp_hip_bottomtemp: a bottom temperature is resident (mckpp_hip_set_bottomtemp) and every step launch "
                 "already applies the override; a second one would zero tinc_fcorr and ocnTcorr of the bottom level - drop "
@@ -1007,6 +978,7 @@ int mckpp_hip_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
   HIPCHK(mckpp_launch_bottomtemp(p, h->d_stage, h->stream));
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
+  });
 }
 
 static int bt_cancel(mckpp_hip_ctx *h)
@@ -1021,8 +993,7 @@ static int bt_cancel(mckpp_hip_ctx *h)
 // (k_column_ps, finish round).  Output, restart and step-log schedules are left alone.
 int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
 {
-  const char *who = "mckpp_hip_set_bottomtemp";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   HIPCHK(hipSetDevice(h->device));
   if (!bottom_temp) return bt_cancel(h);
   if (!h->anc[MCKPP_ANC_BOTTOM_TEMP].ep.empty())
@@ -1041,6 +1012,7 @@ int mckpp_hip_set_bottomtemp(mckpp_hip_handle h, const double *bottom_temp)
   HIPCHK(hipStreamSynchronize(h->stream));
   if (first) h->d_bot_temp = std::move(first);
   return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1075,7 +1047,6 @@ static int anc_cancel_all(mckpp_hip_ctx *h)
 
 static int anc_check_kind(mckpp_hip_ctx *h, int kind, const char *who)
 {
-  if (!h) return fail("%s: null handle", who);
   if (kind < 0 || kind >= MCKPP_ANC_COUNT) return fail("%s: kind=%d (0..%d)", who, kind, MCKPP_ANC_COUNT - 1);
   if (kind != MCKPP_ANC_BOTTOM_TEMP && !h->ext)
     return fail("%s: %s on a context of the default physics: nothing there reads it (the switch that does is off: "
@@ -1086,7 +1057,7 @@ static int anc_check_kind(mckpp_hip_ctx *h, int kind, const char *who)
 
 int mckpp_hip_set_ancillary_series(mckpp_hip_handle h, int kind, int rec0, int nrec, const double *records)
 {
-  const char *who = "mckpp_hip_set_ancillary_series";
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (anc_check_kind(h, kind, who)) return -1;
   if (nrec < 0 || rec0 < 0 || (nrec > 0 && !records))
     return fail("%s: %s rec0=%d nrec=%d records=%s", who, anc_names[kind], rec0, nrec, records ? "set" : "NULL");
@@ -1118,12 +1089,13 @@ int mckpp_hip_set_ancillary_series(mckpp_hip_handle h, int kind, int rec0, int n
   a.rec0 = rec0;
   a.nrec = nrec;
   return 0;
+  });
 }
 
 int mckpp_hip_ancillary_schedule(mckpp_hip_handle h, int kind, int nt_origin, int cadence, int epoch0, int nepochs,
                                  const mckpp_anc_epoch_c *epochs)
 {
-  const char *who = "mckpp_hip_ancillary_schedule";
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (anc_check_kind(h, kind, who)) return -1;
   if (nepochs < 0) return fail("%s: %s nepochs=%d", who, anc_names[kind], nepochs);
   if (nepochs == 0) { h->anc[kind].ep.clear(); return 0; }
@@ -1149,6 +1121,7 @@ int mckpp_hip_ancillary_schedule(mckpp_hip_handle h, int kind, int nt_origin, in
   a.origin = nt_origin; a.cadence = cadence; a.epoch0 = epoch0;
   a.ep.assign(epochs, epochs + nepochs);
   return 0;
+  });
 }
 
 // A step launch call under ancillary schedules: every step's selection of every scheduled kind, checked - nothing is
@@ -1230,29 +1203,32 @@ void mckpp_host_interp_weights(double time, int32_t ndtupd, double dto, double s
 // the caller's arrays pinned on behalf of this context go back to pageable memory (before the caller frees them)
 int mckpp_hip_release_host_arrays(mckpp_hip_handle h)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   HIPCHK(hipSetDevice(h->device));
   if (xfer_finish(h)) return -1;
   unpin_all(h);
   return 0;
+  });
 }
 
 int mckpp_hip_set_diagnostics(mckpp_hip_handle h, int on)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   h->diag = on ? 1 : 0;
   return 0;
+  });
 }
 
 int mckpp_hip_set_solver_mode(mckpp_hip_handle h, int mode)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (mode < 0 || mode > 1) return fail("mckpp_hip_set_solver_mode: unknown solver mode (0: the reference's order, 1: two-ended)");
   h->solver_mode = mode;
   return 0;
+  });
 }
 
-int mckpp_hip_get_solver_mode(mckpp_hip_handle h) { return h ? h->solver_mode : fail("null handle"); }
+int mckpp_hip_get_solver_mode(mckpp_hip_handle h) { return entry(__func__, h, [&]() -> int { return h->solver_mode; }); }
 
 // output fields that are diagnostics of the last vmix (or correction rows): need mckpp_hip_set_diagnostics on
 static bool win_is_diag(int f) { return f >= MCKPP_OUT_B && f <= MCKPP_OUT_SINC_FCORR; }
@@ -1336,14 +1312,11 @@ static int exp_advance(mckpp_hip_ctx *h, int nt0);
 static int snap_check_launch(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 static int snap_advance(mckpp_hip_ctx *h, int nt0, int nsteps);
 static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced);
-static int anc_prepare(mckpp_hip_ctx *h, int nt0, int nsteps, const char *who);
 
 // A step launch under output schedules and the restart schedule: checked against them before anything is launched,
 // then the schedules know which steps have run (and so which of their records and snapshots are complete)
-static int run(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const forced_run *forced = nullptr,
-               const char *who = "mckpp_hip_step")
+static int run(mckpp_hip_ctx *h, const char *who, int ntime, int nsteps, int mode, const forced_run *forced = nullptr)
 {
-  if (!h) return fail("null handle");
   const bool sched = mode == MCKPP_MODE_STEP && nsteps > 0;
   if (sched && h->d_bot_temp && !h->diag)
     return fail("%s: a bottom temperature is resident (mckpp_hip_set_bottomtemp) and the diagnostics are switched off "
@@ -1424,18 +1397,25 @@ static int run_launch(mckpp_hip_ctx *h, int ntime, int nsteps, int mode, const f
   return 0;
 }
 
-int mckpp_hip_init_ocean(mckpp_hip_handle h, int ntime) { return run(h, ntime, 1, MCKPP_MODE_INIT); }
+static int run_one(const char *who, mckpp_hip_ctx *h, int ntime, int mode)
+{
+  return entry(who, h, [&]() -> int { return run(h, who, ntime, 1, mode); });
+}
+int mckpp_hip_init_ocean(mckpp_hip_handle h, int ntime) { return run_one(__func__, h, ntime, MCKPP_MODE_INIT); }
 int mckpp_hip_step(mckpp_hip_handle h, int ntime, int nsteps)
 {
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (nsteps < 0) return fail("mckpp_hip_step: nsteps=%d", nsteps);
-  return run(h, ntime, nsteps, MCKPP_MODE_STEP);
+  return run(h, who, ntime, nsteps, MCKPP_MODE_STEP);
+  });
 }
-int mckpp_hip_vmix_pass(mckpp_hip_handle h, int ntime) { return run(h, ntime, 1, MCKPP_MODE_PASS); }
-int mckpp_hip_vmix_only(mckpp_hip_handle h, int ntime) { return run(h, ntime, 1, MCKPP_MODE_VMIX); }
+int mckpp_hip_vmix_pass(mckpp_hip_handle h, int ntime) { return run_one(__func__, h, ntime, MCKPP_MODE_PASS); }
+int mckpp_hip_vmix_only(mckpp_hip_handle h, int ntime) { return run_one(__func__, h, ntime, MCKPP_MODE_VMIX); }
 
 int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const double *fields)
 {
-  if (!h || !fields) return fail("mckpp_hip_set_flux_series: null argument");
+  return entry(__func__, h, [&]() -> int {
+  if (!fields) return fail("mckpp_hip_set_flux_series: null argument");
   if (nrec < 1 || rec0 < 0) return fail("mckpp_hip_set_flux_series: rec0=%d nrec=%d", rec0, nrec);
   if (h->npts <= 0) return fail("mckpp_hip_set_flux_series: upload the state first (the records are compacted to the resident columns)");
   if (h->ring.nslots > 0)
@@ -1457,6 +1437,7 @@ int mckpp_hip_set_flux_series(mckpp_hip_handle h, int rec0, int nrec, const doub
   HIPCHK(h->d_series.alloc(n));
   HIPCHK(hipMemcpy(h->d_series, f.data(), n * sizeof(double), hipMemcpyHostToDevice));
   return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1482,8 +1463,7 @@ static int ring_cancel(mckpp_hip_ctx *h)
 
 int mckpp_hip_flux_ring(mckpp_hip_handle h, int nslots)
 {
-  const char *who = "mckpp_hip_flux_ring";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (nslots < 0) return fail("%s: nslots=%d (0 cancels the ring)", who, nslots);
   if (nslots > 0 && h->npts <= 0) return fail("%s: upload the state first (the slots are sized to the resident columns)", who);
   HIPCHK(hipSetDevice(h->device));
@@ -1515,6 +1495,7 @@ int mckpp_hip_flux_ring(mckpp_hip_handle h, int nslots)
   h->series_nrec = 0;
   h->ring = std::move(g);
   return 0;
+  });
 }
 
 // what a put - from host or from device arrays - needs before it queues anything: a state, a ring, the next record
@@ -1538,8 +1519,7 @@ static void ring_put_done(mckpp_hip_ctx::flux_ring &g, int rec)
 
 int mckpp_hip_flux_ring_put(mckpp_hip_handle h, int rec, const double *fields)
 {
-  const char *who = "mckpp_hip_flux_ring_put";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (!fields) return fail("%s: null argument", who);
   if (ring_put_check(h, who, rec)) return -1;
   auto &g = h->ring;
@@ -1565,23 +1545,24 @@ int mckpp_hip_flux_ring_put(mckpp_hip_handle h, int rec, const double *fields)
   }
   ring_put_done(g, rec);
   return 0;
+  });
 }
 
 int mckpp_hip_flux_ring_records(mckpp_hip_handle h, int *first, int *last)
 {
-  const char *who = "mckpp_hip_flux_ring_records";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (h->ring.nslots == 0) return fail("%s: no flux ring is set (mckpp_hip_flux_ring)", who);
   int a, b;
   ring_range(h->ring, &a, &b);
   if (first) *first = a;
   if (last) *last = b;
   return 0;
+  });
 }
 
 int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtocn, int l_rest, double flsn, double el)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (nt_first < 1 || nsteps < 0 || ndtocn < 1)
     return fail("mckpp_hip_run_forced: nt_first=%d nsteps=%d ndtocn=%d", nt_first, nsteps, ndtocn);
   if (nsteps == 0) return 0;
@@ -1600,7 +1581,7 @@ int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtoc
                 nt_first + nsteps - 1, first_upd, last_upd, h->series_rec0, h->series_rec0 + h->series_nrec - 1);
   if (g.nslots == 0) {
     const forced_run fr{ndtocn, l_rest, flsn, el, h->d_series, h->series_rec0, 0};
-    return run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr, "mckpp_hip_run_forced");
+    return run(h, who, nt_first, nsteps, MCKPP_MODE_STEP, &fr);
   }
   // the ring: the launches wait, on the device, for the copies of the records they need; behind them the slots are
   // marked as read, which is what the next copy into each waits for
@@ -1608,18 +1589,19 @@ int mckpp_hip_run_forced(mckpp_hip_handle h, int nt_first, int nsteps, int ndtoc
   if (live) HIPCHK(hipSetDevice(h->device));
   for (int r = first_upd; live && r <= last_upd; ++r) HIPCHK(hipStreamWaitEvent(h->stream, g.arrived[(size_t)(r % g.nslots)], 0));
   const forced_run fr{ndtocn, l_rest, flsn, el, g.slots, 0, g.nslots};
-  const int rc = run(h, nt_first, nsteps, MCKPP_MODE_STEP, &fr, "mckpp_hip_run_forced");
+  const int rc = run(h, who, nt_first, nsteps, MCKPP_MODE_STEP, &fr);
   // (also after a failure: some of the call's launches may be queued)
   for (int r = first_upd; live && r <= last_upd; ++r) {
     const hipError_t e = hipEventRecord(g.last_read[(size_t)(r % g.nslots)], h->stream);
     if (e != hipSuccess && rc == 0) HIPCHK(e);
   }
   return rc;
+  });
 }
 
 int mckpp_hip_synchronize(mckpp_hip_handle h)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
   // (the contract of mckpp_hip_device.h: after this call the caller's device arrays are its own again - also those of a
@@ -1667,6 +1649,7 @@ int mckpp_hip_synchronize(mckpp_hip_handle h)
     }
   }
   return 0;
+  });
 }
 
 const char *mckpp_hip_kernel_name(mckpp_hip_handle h)
@@ -1678,7 +1661,7 @@ const char *mckpp_hip_kernel_name(mckpp_hip_handle h)
 int mckpp_hip_kernel_residency(mckpp_hip_handle h, int32_t *blocks_per_cu, int32_t *max_blocks_per_cu,
                                int32_t *threads_per_block, int64_t *lds_bytes_per_block)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (h->last_launch.threads == 0)
     return fail("mckpp_hip_kernel_residency: no cooperative-kernel launch yet");
   if (blocks_per_cu) *blocks_per_cu = (h->last_launch.nblocks + h->num_cu - 1) / h->num_cu;
@@ -1686,11 +1669,12 @@ int mckpp_hip_kernel_residency(mckpp_hip_handle h, int32_t *blocks_per_cu, int32
   if (threads_per_block) *threads_per_block = h->last_launch.threads;
   if (lds_bytes_per_block) *lds_bytes_per_block = (int64_t)h->last_launch.lds_bytes;
   return 0;
+  });
 }
 
 int mckpp_hip_last_kernel_ms(mckpp_hip_handle h, double *ms, int32_t *nlaunch)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (!h->timed) { if (ms) *ms = 0.0; if (nlaunch) *nlaunch = 0; return 0; }
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipEventSynchronize(h->ev1));
@@ -1699,6 +1683,7 @@ int mckpp_hip_last_kernel_ms(mckpp_hip_handle h, double *ms, int32_t *nlaunch)
   if (ms) *ms = (double)t;
   if (nlaunch) *nlaunch = h->nlaunch;
   return 0;
+  });
 }
 
 int32_t mckpp_hip_last_launch_count(mckpp_hip_handle h) { return h && h->timed ? h->nkernels : 0; }
@@ -1786,7 +1771,8 @@ static int download_records(mckpp_hip_ctx *h, mckpp_state_ptrs_c *s, uint32_t ma
 
 int mckpp_hip_download(mckpp_hip_handle h, mckpp_state_ptrs_c *s, uint32_t mask)
 {
-  if (!h || !s) return fail("mckpp_hip_download: null argument");
+  return entry(__func__, h, [&]() -> int {
+  if (!s) return fail("mckpp_hip_download: null argument");
   if (s->npts != h->npts) return fail("mckpp_hip_download: npts=%lld but %lld were uploaded", (long long)s->npts, (long long)h->npts);
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
@@ -1796,6 +1782,7 @@ int mckpp_hip_download(mckpp_hip_handle h, mckpp_state_ptrs_c *s, uint32_t mask)
     if (down_rows(h, x.dev, h->ld, x.off, x.nlev, x.host, x.whole, x.whole_elems)) return -1;
   if (download_records(h, s, mask)) return -1;   // (waits for the context's stream: the last step has finished)
   return xfer_finish(h);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -1853,11 +1840,12 @@ int restart_write(mckpp_hip_ctx *h, const char *who, const char *path, const std
 
 int mckpp_hip_save_restart(mckpp_hip_handle h, const char *path)
 {
-  if (!h || !path) return fail("mckpp_hip_save_restart: null argument");
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  if (!path) return fail("mckpp_hip_save_restart: null argument");
   if (h->ncol <= 0) return fail("mckpp_hip_save_restart: no resident columns");
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  return restart_write(h, "mckpp_hip_save_restart", path, [&](FILE *f) {
+  return restart_write(h, who, path, [&](FILE *f) {
     std::vector<char> buf;
     std::vector<restart_seg> segs;
     restart_segments(h, -1, segs);
@@ -1867,6 +1855,7 @@ int mckpp_hip_save_restart(mckpp_hip_handle h, const char *path)
       if (fwrite(buf.data(), 1, g.bytes, f) != g.bytes) return false;
     }
     return true;
+  });
   });
 }
 
@@ -1938,8 +1927,7 @@ static int snap_advance(mckpp_hip_ctx *h, int nt0, int nsteps)
 
 int mckpp_hip_restart_schedule(mckpp_hip_handle h, int nt_origin, int period, int nslots)
 {
-  const char *who = "mckpp_hip_restart_schedule";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (period < 0) return fail("%s: period=%d (0 cancels the schedule)", who, period);
   if (period > 0) {   // everything is checked before the schedule in place is touched
     if (nt_origin < 1 || nslots < 1) return fail("%s: nt_origin=%d nslots=%d (each at least 1)", who, nt_origin, nslots);
@@ -1967,22 +1955,22 @@ int mckpp_hip_restart_schedule(mckpp_hip_handle h, int nt_origin, int period, in
   r.origin = nt_origin; r.period = period; r.nslots = nslots;
   h->rs = std::move(r);
   return 0;
+  });
 }
 
 int mckpp_hip_restart_snapshots(mckpp_hip_handle h, int64_t *first_kept, int64_t *last_complete)
 {
-  const char *who = "mckpp_hip_restart_snapshots";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (h->rs.period == 0) return fail("%s: no restart schedule is set", who);
   if (first_kept) *first_kept = h->rs.first_kept;
   if (last_complete) *last_complete = snap_last_complete(h->rs);
   return 0;
+  });
 }
 
 int mckpp_hip_restart_snapshot_release(mckpp_hip_handle h, int64_t upto_snap)
 {
-  const char *who = "mckpp_hip_restart_snapshot_release";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   auto &r = h->rs;
   if (r.period == 0) return fail("%s: no restart schedule is set", who);
   const int64_t lc = snap_last_complete(r);
@@ -1991,6 +1979,7 @@ int mckpp_hip_restart_snapshot_release(mckpp_hip_handle h, int64_t upto_snap)
                 (long long)upto_snap, snap_step(r, upto_snap), (long long)lc);
   if (upto_snap + 1 > r.first_kept) r.first_kept = upto_snap + 1;
   return 0;
+  });
 }
 
 // Snapshot `snap` as the file mckpp_hip_save_restart would have written after the snapshot's step.  Waits for the
@@ -1999,8 +1988,7 @@ int mckpp_hip_restart_snapshot_release(mckpp_hip_handle h, int64_t upto_snap)
 // through two pinned staging blocks: the next chunk crosses the bus while the previous one is written to the file.
 int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char *path)
 {
-  const char *who = "mckpp_hip_restart_snapshot_save";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (!path) return fail("%s: null argument", who);
   const auto &r = h->rs;
   if (r.period == 0) return fail("%s: no restart schedule is set", who);
@@ -2047,6 +2035,7 @@ int mckpp_hip_restart_snapshot_save(mckpp_hip_handle h, int64_t snap, const char
     return fail("%s: copy of snapshot %lld (after step %lld) failed: %s", who, (long long)snap, st, hipGetErrorString(herr));
   }
   return rc;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -2065,8 +2054,7 @@ static int log_cancel(mckpp_hip_ctx *h)
 
 int mckpp_hip_step_log(mckpp_hip_handle h, int64_t capacity, int min_passes)
 {
-  const char *who = "mckpp_hip_step_log";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (capacity < 0 || min_passes < 0)
     return fail("%s: capacity=%lld min_passes=%d (capacity 0 cancels the log, min_passes 0 logs flagged steps only)", who,
                 (long long)capacity, min_passes);
@@ -2087,6 +2075,7 @@ int mckpp_hip_step_log(mckpp_hip_handle h, int64_t capacity, int min_passes)
   l.cap = capacity; l.min_passes = min_passes;
   h->slog = std::move(l);
   return 0;
+  });
 }
 
 // events so far (the device counts them in 32 bits), how many of them are stored, the OR of all their status words
@@ -2105,10 +2094,10 @@ static int log_read_ctl(mckpp_hip_ctx *h, int64_t *n_events, int64_t *n_stored, 
 
 int mckpp_hip_step_log_count(mckpp_hip_handle h, int64_t *n_events, int64_t *n_stored, int32_t *status_or)
 {
-  const char *who = "mckpp_hip_step_log_count";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (h->slog.cap == 0) return fail("%s: no step log is set", who);
   return log_read_ctl(h, n_events, n_stored, status_or);
+  });
 }
 
 namespace {
@@ -2147,31 +2136,28 @@ int log_deliver(std::vector<log_event> &ev, int32_t *nt, int32_t *point, int32_t
 
 int mckpp_hip_step_log_fetch(mckpp_hip_handle h, int64_t n, int32_t *nt, int32_t *point, int32_t *status, int32_t *npasses)
 {
-  const char *who = "mckpp_hip_step_log_fetch";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (h->slog.cap == 0) return fail("%s: no step log is set", who);
-  try {
-    std::vector<log_event> ev;
-    if (log_fetch_raw(h, who, n, ev)) return -1;
-    return log_deliver(ev, nt, point, status, npasses);
-  } catch (const std::exception &e) {
-    return fail("%s: %s", who, e.what());
-  }
+  std::vector<log_event> ev;
+  if (log_fetch_raw(h, who, n, ev)) return -1;
+  return log_deliver(ev, nt, point, status, npasses);
+  });
 }
 
 int mckpp_hip_step_log_clear(mckpp_hip_handle h)
 {
-  const char *who = "mckpp_hip_step_log_clear";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (h->slog.cap == 0) return fail("%s: no step log is set", who);
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipMemsetAsync(h->slog.ctl, 0, 2 * sizeof(int), h->stream));   // (behind the launches already queued)
   return 0;
+  });
 }
 
 int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
 {
-  if (!h || !path) return fail("mckpp_hip_load_restart: null argument");
+  return entry(__func__, h, [&]() -> int {
+  if (!path) return fail("mckpp_hip_load_restart: null argument");
   HIPCHK(hipSetDevice(h->device));
   // The whole file is read and checked on the host first; the resident state is replaced only
   // once everything is known to be there and consistent.
@@ -2210,6 +2196,7 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
     src += g.bytes;
   }
   return 0;
+  });
 }
 
 // Re-upload of what the host rewrites between steps for the optional physics
@@ -2217,13 +2204,15 @@ int mckpp_hip_load_restart(mckpp_hip_handle h, const char *path)
 // corrections, climatologies, prescribed advection.  Prognostic state is not touched.
 int mckpp_hip_update_ancillaries(mckpp_hip_handle h, const mckpp_state_ptrs_c *s)
 {
-  if (!h || !s) return fail("mckpp_hip_update_ancillaries: null argument");
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  if (!s) return fail("mckpp_hip_update_ancillaries: null argument");
   if (h->npts <= 0) return fail("mckpp_hip_update_ancillaries: no resident state (upload or load_restart first)");
   if (s->npts != h->npts) return fail("mckpp_hip_update_ancillaries: npts=%lld but %lld are resident", (long long)s->npts, (long long)h->npts);
   if (!h->ext || h->ncol == 0) return 0;   // the default physics reads none of them
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));
-  return upload_ancillaries(h, s, "mckpp_hip_update_ancillaries");
+  return upload_ancillaries(h, s, who);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -2289,7 +2278,8 @@ int out_field(mckpp_hip_ctx *h, int f, out_desc &d)
 
 int mckpp_hip_window_select(mckpp_hip_handle h, const int32_t *fields, int32_t nfields)
 {
-  if (!h || (nfields > 0 && !fields) || nfields < 0) return fail("mckpp_hip_window_select: bad argument");
+  return entry(__func__, h, [&]() -> int {
+  if ((nfields > 0 && !fields) || nfields < 0) return fail("mckpp_hip_window_select: bad argument");
   for (int i = 0; i < nfields; ++i)
     if (fields[i] < 0 || fields[i] >= MCKPP_OUT_COUNT) return fail("mckpp_hip_window_select: unknown output field %d", fields[i]);
   HIPCHK(hipSetDevice(h->device));
@@ -2298,18 +2288,20 @@ int mckpp_hip_window_select(mckpp_hip_handle h, const int32_t *fields, int32_t n
   h->wsel.assign(fields, fields + nfields);
   h->window_count = 0;
   return 0;
+  });
 }
 
 int mckpp_hip_window_reset(mckpp_hip_handle h)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   h->window_count = 0;
   return 0;
+  });
 }
 
 int mckpp_hip_window_accumulate(mckpp_hip_handle h)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   if (h->d_wacc.size() != h->wsel.size()) h->d_wacc = std::vector<dev_buf<double>>(h->wsel.size());
@@ -2326,6 +2318,7 @@ int mckpp_hip_window_accumulate(mckpp_hip_handle h)
   }
   h->window_count += 1;
   return 0;
+  });
 }
 
 // The reduced (or sampled) field of this context's columns, compacted, left in device memory: `src` rows of
@@ -2366,13 +2359,15 @@ static int window_prepare(mckpp_hip_ctx *h, int field, int op, const double **sr
 
 int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
 {
-  if (!h || !out) return fail("mckpp_hip_window_fetch: null argument");
+  return entry(__func__, h, [&]() -> int {
+  if (!out) return fail("mckpp_hip_window_fetch: null argument");
   const double *src = nullptr;
   int ld_out = 0, nlev = 0;
   if (window_prepare(h, field, op, &src, &ld_out, &nlev)) return -1;
   if (h->ncol == 0) return 0;
   if (down_rows(h, src, ld_out, 0, nlev, out)) return -1;
   return xfer_finish(h);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -2570,29 +2565,28 @@ int dev_fence_queue(mckpp_hip_ctx *h, void *stream)
 int mckpp_hip_fluxes_dev(mckpp_hip_handle h, int ntime, const double *const fields[8], int l_rest, double flsn, double el,
                          void *producer_stream)
 {
-  const char *who = "mckpp_hip_fluxes_dev";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (dev_fields_check(h, who, fields, nullptr)) return -1;
   if (h->ncol == 0) return 0;
   if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
   return fluxes_dev_queue(h, ntime, fields, l_rest, flsn, el, h->ev_caller);
+  });
 }
 
 int mckpp_hip_flux_ring_put_dev(mckpp_hip_handle h, int rec, const double *const fields[8], void *producer_stream)
 {
-  const char *who = "mckpp_hip_flux_ring_put_dev";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (!fields) return fail("%s: null argument", who);
   if (ring_put_check(h, who, rec)) return -1;
   if (dev_fields_check(h, who, fields, nullptr)) return -1;
   if (h->ncol > 0 && caller_event(h->ev_caller, h->device, producer_stream)) return -1;
   return ring_put_dev_queue(h, rec, fields, h->ev_caller);
+  });
 }
 
 int mckpp_hip_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
 {
-  const char *who = "mckpp_hip_fetch_dev";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   std::vector<mckpp_fetch_plane> tab;
   int maxlev = 0;
   bool any_fill = false;
@@ -2601,12 +2595,12 @@ int mckpp_hip_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_pla
   if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complement again)
   if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
   return fetch_dev_queue(h, tab, maxlev, any_fill, h->ev_caller, consumer_stream);
+  });
 }
 
 int mckpp_hip_dev_fence(mckpp_hip_handle h, void *stream)
 {
-  if (!h) return fail("mckpp_hip_dev_fence: null handle");
-  return dev_fence_queue(h, stream);
+  return entry(__func__, h, [&]() -> int { return dev_fence_queue(h, stream); });
 }
 
 // ---------------------------------------------------------------------------
@@ -2707,8 +2701,7 @@ static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps)
 int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int period, int nrec, const int32_t *fields,
                               const uint32_t *ops, int32_t nfields)
 {
-  const char *who = "mckpp_hip_window_schedule";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
   if (nfields < 0 || (nfields > 0 && (!fields || !ops))) return fail("%s: bad argument (nfields=%d)", who, nfields);
   if (nfields > 0) {   // everything is checked before the schedule in place is touched
@@ -2757,6 +2750,7 @@ int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int 
     h->wsched[sched] = std::move(w);
   }
   return win_table(h);
+  });
 }
 
 // may record `rec` of the schedule be fetched - all of it (plane false), or its plane of `field` and `op`, whose index
@@ -2815,8 +2809,7 @@ static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec,
 
 int mckpp_hip_window_record_fetch(mckpp_hip_handle h, int sched, int64_t rec, int field, int op, double *out)
 {
-  const char *who = "mckpp_hip_window_record_fetch";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (!out) return fail("%s: null argument", who);
   const double *src = nullptr;
   int ld_out = 0, nlev = 0;
@@ -2824,12 +2817,12 @@ int mckpp_hip_window_record_fetch(mckpp_hip_handle h, int sched, int64_t rec, in
   if (h->ncol == 0) return 0;
   if (down_rows(h, src, ld_out, 0, nlev, out)) return -1;
   return xfer_finish(h);
+  });
 }
 
 int mckpp_hip_window_record_release(mckpp_hip_handle h, int sched, int64_t upto_rec)
 {
-  const char *who = "mckpp_hip_window_record_release";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
   auto &w = h->wsched[sched];
   if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
@@ -2840,18 +2833,19 @@ int mckpp_hip_window_record_release(mckpp_hip_handle h, int sched, int64_t upto_
                 (long long)(w.origin + (upto_rec + 1) * w.period - 1), (long long)lc);
   if (upto_rec + 1 > w.first_kept) w.first_kept = upto_rec + 1;
   return 0;
+  });
 }
 
 int mckpp_hip_window_records(mckpp_hip_handle h, int sched, int64_t *first_kept, int64_t *last_complete)
 {
-  const char *who = "mckpp_hip_window_records";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
   const auto &w = h->wsched[sched];
   if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
   if (first_kept) *first_kept = w.first_kept;
   if (last_complete) *last_complete = win_last_complete(w);
   return 0;
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -2982,9 +2976,7 @@ static int exp_set(mckpp_hip_ctx *h, const char *who, int sched, int dtype, doub
 
 int mckpp_hip_window_export(mckpp_hip_handle h, int sched, int dtype, double land_value)
 {
-  const char *who = "mckpp_hip_window_export";
-  if (!h) return fail("%s: null handle", who);
-  return exp_set(h, who, sched, dtype, land_value, false);
+  return entry(__func__, h, [&, who = __func__]() -> int { return exp_set(h, who, sched, dtype, land_value, false); });
 }
 
 // the layout of a record of the schedule's export over npts points
@@ -3013,9 +3005,9 @@ static int exp_layout_out(mckpp_hip_ctx *h, const char *who, int sched, int64_t 
 int mckpp_hip_window_export_layout(mckpp_hip_handle h, int sched, int32_t *nplanes, int32_t *field, int32_t *op, int32_t *nlev,
                                    int64_t *offset_bytes, int64_t *record_bytes)
 {
-  const char *who = "mckpp_hip_window_export_layout";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   return exp_layout_out(h, who, sched, h->npts, nplanes, field, op, nlev, offset_bytes, record_bytes);
+  });
 }
 
 // may record `rec` (plane: its plane of field and op, whose index among the export's planes comes back) be fetched
@@ -3069,23 +3061,23 @@ static int exp_fetch(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec, 
 
 int mckpp_hip_window_export_fetch(mckpp_hip_handle h, int sched, int64_t rec, int field, int op, void *out)
 {
-  const char *who = "mckpp_hip_window_export_fetch";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (!out) return fail("%s: null argument", who);
   return exp_fetch(h, who, sched, rec, true, field, op, out, 0);
+  });
 }
 
 int mckpp_hip_window_export_fetch_record(mckpp_hip_handle h, int sched, int64_t rec, void *out, int64_t out_bytes)
 {
-  const char *who = "mckpp_hip_window_export_fetch_record";
-  if (!h) return fail("%s: null handle", who);
+  return entry(__func__, h, [&, who = __func__]() -> int {
   if (!out) return fail("%s: null argument", who);
   return exp_fetch(h, who, sched, rec, false, 0, 0, out, out_bytes);
+  });
 }
 
 int mckpp_hip_status(mckpp_hip_handle h, int32_t *per_col, int64_t *n_flagged, int32_t *npasses)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (per_col) for (int64_t i = 0; i < h->npts; ++i) per_col[i] = 0;
   if (npasses) for (int64_t i = 0; i < h->npts; ++i) npasses[i] = 0;
   int64_t nf = 0;
@@ -3104,12 +3096,13 @@ int mckpp_hip_status(mckpp_hip_handle h, int32_t *per_col, int64_t *n_flagged, i
   }
   if (n_flagged) *n_flagged = nf;
   return 0;
+  });
 }
 
 int mckpp_hip_eos_batch(mckpp_hip_handle h, int64_t n, const double *s, const double *t, const double *p,
                         double *alpha, double *beta, double *sig0, double *cp)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (n <= 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   dev_buf<double> d;
@@ -3126,11 +3119,12 @@ int mckpp_hip_eos_batch(mckpp_hip_handle h, int64_t n, const double *s, const do
   if (e == hipSuccess) e = hipMemcpy(cp, d + 6 * n, nb, hipMemcpyDeviceToHost);
   HIPCHK(e);
   return 0;
+  });
 }
 
 int mckpp_hip_div_batch(mckpp_hip_handle h, int64_t n, const double *num, const double *den, double *q4)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (n <= 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   dev_buf<double> d;
@@ -3143,11 +3137,12 @@ int mckpp_hip_div_batch(mckpp_hip_handle h, int64_t n, const double *num, const 
   if (e == hipSuccess) e = hipMemcpy(q4, d + 2 * n, 4 * nb, hipMemcpyDeviceToHost);
   HIPCHK(e);
   return 0;
+  });
 }
 
 int mckpp_hip_exp_batch(mckpp_hip_handle h, int64_t n, const double *x, double *y)
 {
-  if (!h) return fail("null handle");
+  return entry(__func__, h, [&]() -> int {
   if (n <= 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   dev_buf<double> d;
@@ -3159,8 +3154,8 @@ int mckpp_hip_exp_batch(mckpp_hip_handle h, int64_t n, const double *x, double *
   if (e == hipSuccess) e = hipMemcpy(y, d + n, nb, hipMemcpyDeviceToHost);
   HIPCHK(e);
   return 0;
+  });
 }
-
 
 // ---------------------------------------------------------------------------
 // Several GPUs behind one handle: the run_physics columns are dealt round-robin to the
@@ -3207,8 +3202,6 @@ int64_t mckpp_host_shard_mask(int64_t npts, const int32_t *run_physics, int32_t 
   return mine;
 }
 
-int mckpp_hip_multi_finalize(mckpp_hip_multi_handle m);
-
 // the root-side buffers, streams and events go with the root device they were created on
 static void multi_release_root(mckpp_hip_multi *m)
 {
@@ -3220,27 +3213,24 @@ static void multi_release_root(mckpp_hip_multi *m)
 
 int mckpp_hip_multi_init(const mckpp_const_c *c, int32_t ndev, const int32_t *devices, mckpp_hip_multi_handle *out)
 {
+  return entry(__func__, [&]() -> int {
   if (!c || !out || ndev < 1) return fail("mckpp_hip_multi_init: bad argument (ndev=%d)", ndev);
-  mckpp_hip_multi *m = new mckpp_hip_multi();
+  // any return or throw below finalizes the shards made so far, once (mckpp_hip_multi_finalize takes any stage of this)
+  half_built<mckpp_hip_multi, mckpp_hip_multi_finalize> m(new mckpp_hip_multi());
+  m->ctx.reserve((size_t)ndev);   // (so that no context can be made and then not be kept)
   for (int d = 0; d < ndev; ++d) {
     mckpp_hip_handle h = nullptr;
-    if (mckpp_hip_init(c, devices ? devices[d] : d, &h) != 0) {
-      for (auto *x : m->ctx) mckpp_hip_finalize(x);
-      delete m;
-      return -1;   // message of mckpp_hip_init
-    }
+    if (mckpp_hip_init(c, devices ? devices[d] : d, &h) != 0) return -1;   // message of mckpp_hip_init
     m->ctx.push_back(h);
   }
   m->mask.resize(ndev);
   m->ev_owner.resize(ndev);
-  for (int d = 0; d < ndev; ++d) {
-    if (hipSetDevice(m->ctx[d]->device) != hipSuccess || m->ev_owner[d].create() != hipSuccess) {
-      mckpp_hip_multi_finalize(m);
+  for (int d = 0; d < ndev; ++d)
+    if (hipSetDevice(m->ctx[d]->device) != hipSuccess || m->ev_owner[d].create() != hipSuccess)
       return fail("mckpp_hip_multi_init: cannot create the events of shard %d", d);
-    }
-  }
-  *out = m;
+  *out = m.release();
   return 0;
+  });
 }
 
 int mckpp_hip_multi_finalize(mckpp_hip_multi_handle m)
@@ -3257,13 +3247,15 @@ int mckpp_hip_multi_finalize(mckpp_hip_multi_handle m)
 int32_t mckpp_hip_multi_ndev(mckpp_hip_multi_handle m) { return m ? (int32_t)m->ctx.size() : -1; }
 mckpp_hip_handle mckpp_hip_multi_ctx(mckpp_hip_multi_handle m, int32_t i)
 {
-  if (!m || i < 0 || i >= (int)m->ctx.size()) { fail("mckpp_hip_multi_ctx: shard %d", i); return nullptr; }
-  return m->ctx[i];
+  const bool ok = m && i >= 0 && i < (int)m->ctx.size();
+  if (!ok) entry(__func__, [&]() -> int { return fail("mckpp_hip_multi_ctx: shard %d", i); });
+  return ok ? m->ctx[i] : nullptr;
 }
 
 int mckpp_hip_multi_upload(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s)
 {
-  if (!m || !s) return fail("mckpp_hip_multi_upload: null argument");
+  return entry(__func__, m, [&]() -> int {
+  if (!s) return fail("mckpp_hip_multi_upload: null argument");
   if (s->npts <= 0) return fail("mckpp_hip_multi_upload: npts=%lld", (long long)s->npts);
   const int ndev = (int)m->ctx.size();
   m->npts = s->npts;
@@ -3277,39 +3269,43 @@ int mckpp_hip_multi_upload(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s
   m->gipt_valid = false;   // the root's copy of the column maps is of the previous upload
   for (auto *x : m->ctx) x->land_kind = 0;   // ... and so is shard 0's list of the points that no shard holds
   return 0;
+  });
 }
 
-#define MULTI_EACH(call)                                           \
-  do {                                                             \
-    if (!m) return fail("null multi handle");                      \
-    for (auto *x : m->ctx) { if ((call) != 0) return -1; }         \
-    return 0;                                                      \
-  } while (0)
+// the entry points that are the same call on every shard: the first failure ends them, with the shard's text
+extern "C++" template <class F>
+int multi_each(const char *who, mckpp_hip_multi *m, F &&call) noexcept
+{
+  return entry(who, m, [&]() -> int {
+  for (auto *x : m->ctx) if (call(x) != 0) return -1;
+  return 0;
+  });
+}
 
-int mckpp_hip_multi_set_forcing(mckpp_hip_multi_handle m, const double *sflux) { MULTI_EACH(mckpp_hip_set_forcing(x, sflux)); }
-int mckpp_hip_multi_set_diagnostics(mckpp_hip_multi_handle m, int on) { MULTI_EACH(mckpp_hip_set_diagnostics(x, on)); }
-int mckpp_hip_multi_set_solver_mode(mckpp_hip_multi_handle m, int mode) { MULTI_EACH(mckpp_hip_set_solver_mode(x, mode)); }
-int mckpp_hip_multi_init_ocean(mckpp_hip_multi_handle m, int ntime) { MULTI_EACH(mckpp_hip_init_ocean(x, ntime)); }
+int mckpp_hip_multi_set_forcing(mckpp_hip_multi_handle m, const double *sflux) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_set_forcing(x, sflux); }); }
+int mckpp_hip_multi_set_diagnostics(mckpp_hip_multi_handle m, int on) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_set_diagnostics(x, on); }); }
+int mckpp_hip_multi_set_solver_mode(mckpp_hip_multi_handle m, int mode) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_set_solver_mode(x, mode); }); }
+int mckpp_hip_multi_init_ocean(mckpp_hip_multi_handle m, int ntime) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_init_ocean(x, ntime); }); }
 // asynchronous on every device: all shards are launched before the caller can wait on any of them
-int mckpp_hip_multi_step(mckpp_hip_multi_handle m, int ntime, int nsteps) { MULTI_EACH(mckpp_hip_step(x, ntime, nsteps)); }
-int mckpp_hip_multi_synchronize(mckpp_hip_multi_handle m) { MULTI_EACH(mckpp_hip_synchronize(x)); }
-int mckpp_hip_multi_update_ancillaries(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s) { MULTI_EACH(mckpp_hip_update_ancillaries(x, s)); }
-int mckpp_hip_multi_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { MULTI_EACH(mckpp_hip_bottomtemp(x, bottom_temp)); }
-int mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { MULTI_EACH(mckpp_hip_set_bottomtemp(x, bottom_temp)); }
+int mckpp_hip_multi_step(mckpp_hip_multi_handle m, int ntime, int nsteps) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_step(x, ntime, nsteps); }); }
+int mckpp_hip_multi_synchronize(mckpp_hip_multi_handle m) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_synchronize(x); }); }
+int mckpp_hip_multi_update_ancillaries(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_update_ancillaries(x, s); }); }
+int mckpp_hip_multi_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_bottomtemp(x, bottom_temp); }); }
+int mckpp_hip_multi_set_bottomtemp(mckpp_hip_multi_handle m, const double *bottom_temp) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_set_bottomtemp(x, bottom_temp); }); }
 int mckpp_hip_multi_set_ancillary_series(mckpp_hip_multi_handle m, int kind, int rec0, int nrec, const double *records)
 {
-  MULTI_EACH(mckpp_hip_set_ancillary_series(x, kind, rec0, nrec, records));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_set_ancillary_series(x, kind, rec0, nrec, records); });
 }
 int mckpp_hip_multi_ancillary_schedule(mckpp_hip_multi_handle m, int kind, int nt_origin, int cadence, int epoch0, int nepochs,
                                        const mckpp_anc_epoch_c *epochs)
 {
-  MULTI_EACH(mckpp_hip_ancillary_schedule(x, kind, nt_origin, cadence, epoch0, nepochs, epochs));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_ancillary_schedule(x, kind, nt_origin, cadence, epoch0, nepochs, epochs); });
 }
 int mckpp_hip_multi_fluxes(mckpp_hip_multi_handle m, int ntime, const double *taux, const double *tauy, const double *swf,
                            const double *lwf, const double *lhf, const double *shf, const double *rain, const double *snow,
                            int l_rest, double flsn, double el)
 {
-  MULTI_EACH(mckpp_hip_fluxes(x, ntime, taux, tauy, swf, lwf, lhf, shf, rain, snow, l_rest, flsn, el));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_fluxes(x, ntime, taux, tauy, swf, lwf, lhf, shf, rain, snow, l_rest, flsn, el); });
 }
 int64_t mckpp_hip_multi_ncolumns(mckpp_hip_multi_handle m)
 {
@@ -3321,7 +3317,7 @@ int64_t mckpp_hip_multi_ncolumns(mckpp_hip_multi_handle m)
 
 int mckpp_hip_multi_status(mckpp_hip_multi_handle m, int32_t *per_col, int64_t *n_flagged, int32_t *npasses)
 {
-  if (!m) return fail("null multi handle");
+  return entry(__func__, m, [&]() -> int {
   int64_t nf = 0;
   std::vector<int32_t> st, np_;
   if (per_col) { st.assign((size_t)m->npts, 0); for (int64_t i = 0; i < m->npts; ++i) per_col[i] = 0; }
@@ -3338,6 +3334,7 @@ int mckpp_hip_multi_status(mckpp_hip_multi_handle m, int32_t *per_col, int64_t *
   }
   if (n_flagged) *n_flagged = nf;
   return 0;
+  });
 }
 
 // ---- The gather.  One row field of every shard -> the caller's (npts, nlev) array in the Fortran
@@ -3452,7 +3449,8 @@ static int multi_gather_finish(mckpp_hip_multi *m)
 // `field` 0 U, 1 V, 2 T, 3 S -> out(npts,nzp1), 4 hmix -> out(npts)
 int mckpp_hip_multi_gather(mckpp_hip_multi_handle m, int32_t field, int32_t root, double *out)
 {
-  if (!m || !out) return fail("mckpp_hip_multi_gather: null argument");
+  return entry(__func__, m, [&]() -> int {
+  if (!out) return fail("mckpp_hip_multi_gather: null argument");
   const int ndev = (int)m->ctx.size();
   if (root < 0 || root >= ndev) return fail("mckpp_hip_multi_gather: root %d of %d", root, ndev);
   if (field < 0 || field > 4) return fail("mckpp_hip_multi_gather: field %d", field);
@@ -3467,6 +3465,7 @@ int mckpp_hip_multi_gather(mckpp_hip_multi_handle m, int32_t field, int32_t root
   if (multi_gather_rows(m, root, src, field < 4 ? r->ld : MCKPP_CS, field < 4 ? 0 : CS_HMIX, field < 4 ? r->nzp1 : 1, out))
     return -1;
   return multi_gather_finish(m);
+  });
 }
 
 // mckpp_hip_download for all shards: the per-column records of every shard come to the host on their own (each
@@ -3474,7 +3473,8 @@ int mckpp_hip_multi_gather(mckpp_hip_multi_handle m, int32_t field, int32_t root
 // of devices.
 int mckpp_hip_multi_download(mckpp_hip_multi_handle m, mckpp_state_ptrs_c *s, uint32_t mask)
 {
-  if (!m || !s) return fail("mckpp_hip_multi_download: null argument");
+  return entry(__func__, m, [&]() -> int {
+  if (!s) return fail("mckpp_hip_multi_download: null argument");
   if (s->npts != m->npts) return fail("mckpp_hip_multi_download: npts=%lld but %lld were uploaded", (long long)s->npts, (long long)m->npts);
   const int ndev = (int)m->ctx.size();
   std::vector<std::vector<row_xfer>> plans(ndev);
@@ -3491,28 +3491,27 @@ int mckpp_hip_multi_download(mckpp_hip_multi_handle m, mckpp_state_ptrs_c *s, ui
     if (download_records(x, s, mask)) return -1;
   }
   return multi_gather_finish(m);
+  });
 }
 
 // ---- the forced time loop, the output windows and the restart set for all shards
 int mckpp_hip_multi_set_flux_series(mckpp_hip_multi_handle m, int rec0, int nrec, const double *fields)
 {
-  MULTI_EACH(mckpp_hip_set_flux_series(x, rec0, nrec, fields));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_set_flux_series(x, rec0, nrec, fields); });
 }
 // the flux ring over all shards: every shard compacts its own columns of the one caller array into its own ring
 int mckpp_hip_multi_flux_ring(mckpp_hip_multi_handle m, int nslots)
 {
-  if (!m) return fail("mckpp_hip_multi_flux_ring: null handle");
-  MULTI_EACH(mckpp_hip_flux_ring(x, nslots));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_flux_ring(x, nslots); });
 }
 int mckpp_hip_multi_flux_ring_put(mckpp_hip_multi_handle m, int rec, const double *fields)
 {
-  if (!m) return fail("mckpp_hip_multi_flux_ring_put: null handle");
-  MULTI_EACH(mckpp_hip_flux_ring_put(x, rec, fields));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_flux_ring_put(x, rec, fields); });
 }
 // the range common to all shards (they are put to together: it is every shard's own)
 int mckpp_hip_multi_flux_ring_records(mckpp_hip_multi_handle m, int *first, int *last)
 {
-  if (!m) return fail("mckpp_hip_multi_flux_ring_records: null handle");
+  return entry(__func__, m, [&]() -> int {
   int a = -1, b = -1;
   bool any = false, empty = false;
   for (auto *x : m->ctx) {
@@ -3527,20 +3526,22 @@ int mckpp_hip_multi_flux_ring_records(mckpp_hip_multi_handle m, int *first, int 
   if (first) *first = a;
   if (last) *last = b;
   return 0;
+  });
 }
 // asynchronous on every device, like mckpp_hip_multi_step
 int mckpp_hip_multi_run_forced(mckpp_hip_multi_handle m, int nt_first, int nsteps, int ndtocn, int l_rest, double flsn, double el)
 {
-  MULTI_EACH(mckpp_hip_run_forced(x, nt_first, nsteps, ndtocn, l_rest, flsn, el));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_run_forced(x, nt_first, nsteps, ndtocn, l_rest, flsn, el); });
 }
-int mckpp_hip_multi_window_select(mckpp_hip_multi_handle m, const int32_t *fields, int32_t nfields) { MULTI_EACH(mckpp_hip_window_select(x, fields, nfields)); }
-int mckpp_hip_multi_window_reset(mckpp_hip_multi_handle m) { MULTI_EACH(mckpp_hip_window_reset(x)); }
-int mckpp_hip_multi_window_accumulate(mckpp_hip_multi_handle m) { MULTI_EACH(mckpp_hip_window_accumulate(x)); }
+int mckpp_hip_multi_window_select(mckpp_hip_multi_handle m, const int32_t *fields, int32_t nfields) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_select(x, fields, nfields); }); }
+int mckpp_hip_multi_window_reset(mckpp_hip_multi_handle m) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_reset(x); }); }
+int mckpp_hip_multi_window_accumulate(mckpp_hip_multi_handle m) { return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_accumulate(x); }); }
 
 // every shard reduces its own columns; the reduced rows are gathered like any other field
 int mckpp_hip_multi_window_fetch(mckpp_hip_multi_handle m, int field, int op, double *out)
 {
-  if (!m || !out) return fail("mckpp_hip_multi_window_fetch: null argument");
+  return entry(__func__, m, [&]() -> int {
+  if (!out) return fail("mckpp_hip_multi_window_fetch: null argument");
   if (m->npts <= 0) return fail("mckpp_hip_multi_window_fetch: nothing uploaded");
   const int ndev = (int)m->ctx.size();
   std::vector<const double *> src(ndev, nullptr);
@@ -3549,6 +3550,7 @@ int mckpp_hip_multi_window_fetch(mckpp_hip_multi_handle m, int field, int op, do
     if (window_prepare(m->ctx[d], field, op, &src[d], &ld_out, &nlev)) return -1;
   if (multi_gather_rows(m, 0, src, ld_out, 0, nlev, out)) return -1;
   return multi_gather_finish(m);
+  });
 }
 
 // output windows inside the step launches: every shard keeps its columns' records (and the same bookkeeping: the
@@ -3556,13 +3558,11 @@ int mckpp_hip_multi_window_fetch(mckpp_hip_multi_handle m, int field, int op, do
 int mckpp_hip_multi_window_schedule(mckpp_hip_multi_handle m, int sched, int nt_origin, int period, int nrec,
                                     const int32_t *fields, const uint32_t *ops, int32_t nfields)
 {
-  if (!m) return fail("mckpp_hip_multi_window_schedule: null handle");
-  MULTI_EACH(mckpp_hip_window_schedule(x, sched, nt_origin, period, nrec, fields, ops, nfields));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_schedule(x, sched, nt_origin, period, nrec, fields, ops, nfields); });
 }
 int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, double *out)
 {
-  const char *who = "mckpp_hip_multi_window_record_fetch";
-  if (!m) return fail("%s: null handle", who);
+  return entry(__func__, m, [&, who = __func__]() -> int {
   if (!out) return fail("%s: null argument", who);
   if (m->npts <= 0) return fail("%s: nothing uploaded", who);
   const int ndev = (int)m->ctx.size();
@@ -3572,16 +3572,15 @@ int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int
     if (win_record(m->ctx[d], who, sched, rec, field, op, &src[d], &ld_out, &nlev)) return -1;
   if (multi_gather_rows(m, 0, src, ld_out, 0, nlev, out)) return -1;
   return multi_gather_finish(m);
+  });
 }
 int mckpp_hip_multi_window_record_release(mckpp_hip_multi_handle m, int sched, int64_t upto_rec)
 {
-  if (!m) return fail("mckpp_hip_multi_window_record_release: null handle");
-  MULTI_EACH(mckpp_hip_window_record_release(x, sched, upto_rec));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_record_release(x, sched, upto_rec); });
 }
 int mckpp_hip_multi_window_records(mckpp_hip_multi_handle m, int sched, int64_t *first_kept, int64_t *last_complete)
 {
-  if (!m) return fail("mckpp_hip_multi_window_records: null handle");
-  return mckpp_hip_window_records(m->ctx[0], sched, first_kept, last_complete);
+  return entry(__func__, m, [&]() -> int { return mckpp_hip_window_records(m->ctx[0], sched, first_kept, last_complete); });
 }
 
 // ---- the export (mckpp_hip_window_export) over all shards
@@ -3632,26 +3631,22 @@ int export_covered(int64_t npts, int nsh, const int64_t *ncol, const int32_t *co
 int mckpp_host_export_merge(int64_t npts, int32_t nlev, int32_t dtype, double land_value, int32_t nshards, const int64_t *ncol,
                             const int32_t *const *points, const void *const *planes, void *out)
 {
-  const char *who = "mckpp_host_export_merge";
+  return entry(__func__, [&, who = __func__]() -> int {
   if (npts < 0 || nlev < 1 || nshards < 0 || (nshards > 0 && (!ncol || !points || !planes)) || (npts > 0 && !out))
     return fail("%s: bad argument (npts=%lld nlev=%d nshards=%d)", who, (long long)npts, nlev, nshards);
   if (dtype != MCKPP_EXP_F64 && dtype != MCKPP_EXP_F32) return fail("%s: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, dtype);
   for (int d = 0; d < nshards; ++d)
     if (ncol[d] < 0 || (ncol[d] > 0 && (!points[d] || !planes[d]))) return fail("%s: shard %d: bad argument (ncol=%lld)", who, d, (long long)ncol[d]);
-  try {
-    std::vector<unsigned char> covered;
-    if (export_covered(npts, nshards, ncol, points, covered)) return fail("%s: a point outside 0..%lld", who, (long long)npts - 1);
-    export_merge(npts, nlev, dtype, land_value, nshards, ncol, points, planes, out, covered.data());
-  } catch (const std::exception &e) {
-    return fail("%s: %s", who, e.what());
-  }
+  std::vector<unsigned char> covered;
+  if (export_covered(npts, nshards, ncol, points, covered)) return fail("%s: a point outside 0..%lld", who, (long long)npts - 1);
+  export_merge(npts, nlev, dtype, land_value, nshards, ncol, points, planes, out, covered.data());
   return 0;
+  });
 }
 
 int mckpp_hip_multi_window_export(mckpp_hip_multi_handle m, int sched, int dtype, double land_value)
 {
-  const char *who = "mckpp_hip_multi_window_export";
-  if (!m) return fail("%s: null handle", who);
+  return entry(__func__, m, [&, who = __func__]() -> int {
   const bool compact = m->ctx.size() > 1;
   for (auto *x : m->ctx)
     if (exp_set(x, who, sched, dtype, land_value, compact) != 0) {   // all shards or none
@@ -3661,21 +3656,21 @@ int mckpp_hip_multi_window_export(mckpp_hip_multi_handle m, int sched, int dtype
       return fail("%s", why.c_str());
     }
   return 0;
+  });
 }
 
 int mckpp_hip_multi_window_export_layout(mckpp_hip_multi_handle m, int sched, int32_t *nplanes, int32_t *field, int32_t *op,
                                          int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes)
 {
-  const char *who = "mckpp_hip_multi_window_export_layout";
-  if (!m) return fail("%s: null handle", who);
+  return entry(__func__, m, [&, who = __func__]() -> int {
   return exp_layout_out(m->ctx[0], who, sched, m->npts, nplanes, field, op, nlev, offset_bytes, record_bytes);
+  });
 }
 
 // every shard's copy into the pinned staging is started before any is waited for; the host then merges
 static int multi_exp_fetch(mckpp_hip_multi *m, const char *who, int sched, int64_t rec, bool plane, int field, int op, void *out,
                            int64_t out_bytes)
 {
-  if (!m) return fail("%s: null handle", who);
   if (!out) return fail("%s: null argument", who);
   const int ndev = (int)m->ctx.size();
   if (ndev == 1) return exp_fetch(m->ctx[0], who, sched, rec, plane, field, op, out, out_bytes);
@@ -3691,48 +3686,44 @@ static int multi_exp_fetch(mckpp_hip_multi *m, const char *who, int sched, int64
   if (exp_layout(m->ctx[0], w0, m->npts, dtype, gp, grb, maxlev)) return -1;
   if (!plane && out_bytes < (int64_t)grb)
     return fail("%s: out_bytes %lld, but a record of schedule %d takes %zu bytes", who, (long long)out_bytes, sched, grb);
-  try {
-    std::vector<size_t> at((size_t)ndev, 0), nb((size_t)ndev, 0);
-    size_t total = 0;
-    for (int d = 0; d < ndev; ++d) {
-      const auto &x = m->ctx[d]->wsched[sched].ex;
-      nb[(size_t)d] = plane ? (size_t)x.npts * (size_t)x.planes[k].nlev * exp_elem(dtype) : x.record_bytes;
-      at[(size_t)d] = total;
-      total += (nb[(size_t)d] + 255) & ~(size_t)255;
-    }
-    HIPCHK(m->h_exp.reserve(total, hipHostMallocPortable));
-    int rc = 0;
-    for (int d = 0; d < ndev && rc == 0; ++d) {
-      const auto &w = m->ctx[d]->wsched[sched];
-      rc = exp_copy_start(m->ctx[d], w, rec, plane ? (size_t)w.ex.planes[k].offset : 0, nb[(size_t)d], m->h_exp + at[(size_t)d]);
-    }
-    for (auto *x : m->ctx) if (exp_copy_finish(x)) return -1;
-    if (rc) return -1;
-    std::vector<int64_t> ncol((size_t)ndev);
-    std::vector<const int32_t *> points((size_t)ndev);
-    std::vector<const void *> planes((size_t)ndev);
-    for (int d = 0; d < ndev; ++d) { ncol[(size_t)d] = m->ctx[d]->ncol; points[(size_t)d] = m->ctx[d]->ipt.data(); }
-    std::vector<unsigned char> covered;
-    if (export_covered(m->npts, ndev, ncol.data(), points.data(), covered)) return fail("%s: a shard's point outside the grid", who);
-    for (size_t q = plane ? k : 0; q < (plane ? k + 1 : gp.size()); ++q) {
-      for (int d = 0; d < ndev; ++d)
-        planes[(size_t)d] = m->h_exp + at[(size_t)d] + (plane ? 0 : (size_t)m->ctx[d]->wsched[sched].ex.planes[q].offset);
-      export_merge(m->npts, gp[q].nlev, dtype, w0.ex.land, ndev, ncol.data(), points.data(), planes.data(),
-                   static_cast<char *>(out) + (plane ? 0 : (size_t)gp[q].offset), covered.data());
-    }
-  } catch (const std::exception &e) {
-    return fail("%s: %s", who, e.what());
+  std::vector<size_t> at((size_t)ndev, 0), nb((size_t)ndev, 0);
+  size_t total = 0;
+  for (int d = 0; d < ndev; ++d) {
+    const auto &x = m->ctx[d]->wsched[sched].ex;
+    nb[(size_t)d] = plane ? (size_t)x.npts * (size_t)x.planes[k].nlev * exp_elem(dtype) : x.record_bytes;
+    at[(size_t)d] = total;
+    total += (nb[(size_t)d] + 255) & ~(size_t)255;
+  }
+  HIPCHK(m->h_exp.reserve(total, hipHostMallocPortable));
+  int rc = 0;
+  for (int d = 0; d < ndev && rc == 0; ++d) {
+    const auto &w = m->ctx[d]->wsched[sched];
+    rc = exp_copy_start(m->ctx[d], w, rec, plane ? (size_t)w.ex.planes[k].offset : 0, nb[(size_t)d], m->h_exp + at[(size_t)d]);
+  }
+  for (auto *x : m->ctx) if (exp_copy_finish(x)) return -1;
+  if (rc) return -1;
+  std::vector<int64_t> ncol((size_t)ndev);
+  std::vector<const int32_t *> points((size_t)ndev);
+  std::vector<const void *> planes((size_t)ndev);
+  for (int d = 0; d < ndev; ++d) { ncol[(size_t)d] = m->ctx[d]->ncol; points[(size_t)d] = m->ctx[d]->ipt.data(); }
+  std::vector<unsigned char> covered;
+  if (export_covered(m->npts, ndev, ncol.data(), points.data(), covered)) return fail("%s: a shard's point outside the grid", who);
+  for (size_t q = plane ? k : 0; q < (plane ? k + 1 : gp.size()); ++q) {
+    for (int d = 0; d < ndev; ++d)
+      planes[(size_t)d] = m->h_exp + at[(size_t)d] + (plane ? 0 : (size_t)m->ctx[d]->wsched[sched].ex.planes[q].offset);
+    export_merge(m->npts, gp[q].nlev, dtype, w0.ex.land, ndev, ncol.data(), points.data(), planes.data(),
+                 static_cast<char *>(out) + (plane ? 0 : (size_t)gp[q].offset), covered.data());
   }
   return 0;
 }
 
 int mckpp_hip_multi_window_export_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, void *out)
 {
-  return multi_exp_fetch(m, "mckpp_hip_multi_window_export_fetch", sched, rec, true, field, op, out, 0);
+  return entry(__func__, m, [&, who = __func__]() -> int { return multi_exp_fetch(m, who, sched, rec, true, field, op, out, 0); });
 }
 int mckpp_hip_multi_window_export_fetch_record(mckpp_hip_multi_handle m, int sched, int64_t rec, void *out, int64_t out_bytes)
 {
-  return multi_exp_fetch(m, "mckpp_hip_multi_window_export_fetch_record", sched, rec, false, 0, 0, out, out_bytes);
+  return entry(__func__, m, [&, who = __func__]() -> int { return multi_exp_fetch(m, who, sched, rec, false, 0, 0, out, out_bytes); });
 }
 
 // one file per shard: <path>.<d>of<ndev>
@@ -3742,17 +3733,20 @@ static std::string shard_path(const char *path, int d, int ndev)
 }
 int mckpp_hip_multi_save_restart(mckpp_hip_multi_handle m, const char *path)
 {
-  if (!m || !path) return fail("mckpp_hip_multi_save_restart: null argument");
+  return entry(__func__, m, [&]() -> int {
+  if (!path) return fail("mckpp_hip_multi_save_restart: null argument");
   const int ndev = (int)m->ctx.size();
   for (int d = 0; d < ndev; ++d)
     if (m->ctx[d]->ncol > 0 && mckpp_hip_save_restart(m->ctx[d], shard_path(path, d, ndev).c_str()) != 0) return -1;
   return 0;
+  });
 }
 // the files must have been written by a handle with the same number of shards over the same land mask: every
 // shard's column map is checked against the one the current upload gave it before anything is replaced
 int mckpp_hip_multi_load_restart(mckpp_hip_multi_handle m, const char *path)
 {
-  if (!m || !path) return fail("mckpp_hip_multi_load_restart: null argument");
+  return entry(__func__, m, [&]() -> int {
+  if (!path) return fail("mckpp_hip_multi_load_restart: null argument");
   if (m->npts <= 0) return fail("mckpp_hip_multi_load_restart: upload the state first (the shards' column maps come from it)");
   const int ndev = (int)m->ctx.size();
   for (int d = 0; d < ndev; ++d) {   // pass 1: headers and column maps only
@@ -3771,6 +3765,7 @@ int mckpp_hip_multi_load_restart(mckpp_hip_multi_handle m, const char *path)
   for (int d = 0; d < ndev; ++d)
     if (m->ctx[d]->ncol > 0 && mckpp_hip_load_restart(m->ctx[d], shard_path(path, d, ndev).c_str()) != 0) return -1;
   return 0;
+  });
 }
 
 // restart snapshots inside the step launches (mckpp_hip_restart_schedule) over all shards: every shard keeps the
@@ -3778,7 +3773,7 @@ int mckpp_hip_multi_load_restart(mckpp_hip_multi_handle m, const char *path)
 // shard, named as multi_save_restart names them, and multi_load_restart reads them
 int mckpp_hip_multi_restart_schedule(mckpp_hip_multi_handle m, int nt_origin, int period, int nslots)
 {
-  if (!m) return fail("mckpp_hip_multi_restart_schedule: null handle");
+  return entry(__func__, m, [&]() -> int {
   for (auto *x : m->ctx)
     if (mckpp_hip_restart_schedule(x, nt_origin, period, nslots) != 0) {   // all shards or none
       const std::string why = g_err;
@@ -3786,32 +3781,32 @@ int mckpp_hip_multi_restart_schedule(mckpp_hip_multi_handle m, int nt_origin, in
       return fail("%s", why.c_str());
     }
   return 0;
+  });
 }
 int mckpp_hip_multi_restart_snapshots(mckpp_hip_multi_handle m, int64_t *first_kept, int64_t *last_complete)
 {
-  if (!m) return fail("mckpp_hip_multi_restart_snapshots: null handle");
-  return mckpp_hip_restart_snapshots(m->ctx[0], first_kept, last_complete);
+  return entry(__func__, m, [&]() -> int { return mckpp_hip_restart_snapshots(m->ctx[0], first_kept, last_complete); });
 }
 int mckpp_hip_multi_restart_snapshot_save(mckpp_hip_multi_handle m, int64_t snap, const char *path)
 {
-  if (!m) return fail("mckpp_hip_multi_restart_snapshot_save: null handle");
+  return entry(__func__, m, [&]() -> int {
   if (!path) return fail("mckpp_hip_multi_restart_snapshot_save: null argument");
   const int ndev = (int)m->ctx.size();
   for (int d = 0; d < ndev; ++d)
     if (m->ctx[d]->ncol > 0 && mckpp_hip_restart_snapshot_save(m->ctx[d], snap, shard_path(path, d, ndev).c_str()) != 0) return -1;
   return 0;
+  });
 }
 int mckpp_hip_multi_restart_snapshot_release(mckpp_hip_multi_handle m, int64_t upto_snap)
 {
-  if (!m) return fail("mckpp_hip_multi_restart_snapshot_release: null handle");
-  MULTI_EACH(mckpp_hip_restart_snapshot_release(x, upto_snap));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_restart_snapshot_release(x, upto_snap); });
 }
 
 // the step log (mckpp_hip_step_log) over all shards: one log of `capacity` records per shard; the counts add up, the
 // ORs are ORed, and fetch merges the shards' records (their points are the caller's already) and sorts them
 int mckpp_hip_multi_step_log(mckpp_hip_multi_handle m, int64_t capacity, int min_passes)
 {
-  if (!m) return fail("mckpp_hip_multi_step_log: null handle");
+  return entry(__func__, m, [&]() -> int {
   for (auto *x : m->ctx)
     if (mckpp_hip_step_log(x, capacity, min_passes) != 0) {   // all shards or none
       const std::string why = g_err;
@@ -3819,10 +3814,11 @@ int mckpp_hip_multi_step_log(mckpp_hip_multi_handle m, int64_t capacity, int min
       return fail("%s", why.c_str());
     }
   return 0;
+  });
 }
 int mckpp_hip_multi_step_log_count(mckpp_hip_multi_handle m, int64_t *n_events, int64_t *n_stored, int32_t *status_or)
 {
-  if (!m) return fail("mckpp_hip_multi_step_log_count: null handle");
+  return entry(__func__, m, [&]() -> int {
   int64_t ne = 0, ns = 0;
   int32_t so = 0;
   for (auto *x : m->ctx) {
@@ -3835,33 +3831,29 @@ int mckpp_hip_multi_step_log_count(mckpp_hip_multi_handle m, int64_t *n_events, 
   if (n_stored) *n_stored = ns;
   if (status_or) *status_or = so;
   return 0;
+  });
 }
 int mckpp_hip_multi_step_log_fetch(mckpp_hip_multi_handle m, int64_t n, int32_t *nt, int32_t *point, int32_t *status,
                                    int32_t *npasses)
 {
-  const char *who = "mckpp_hip_multi_step_log_fetch";
-  if (!m) return fail("%s: null handle", who);
-  try {
-    std::vector<log_event> all, ev;
-    for (auto *x : m->ctx) {
-      if (x->slog.cap == 0) return fail("%s: no step log is set", who);
-      int64_t stored = 0;
-      if (log_read_ctl(x, nullptr, &stored, nullptr) || log_fetch_raw(x, who, stored, ev)) return -1;
-      all.insert(all.end(), ev.begin(), ev.end());
-    }
-    if (n < 0 || n > (int64_t)all.size())
-      return fail("%s: n=%lld (%lld records are stored)", who, (long long)n, (long long)all.size());
-    std::sort(all.begin(), all.end(), log_before);
-    all.resize((size_t)n);
-    return log_deliver(all, nt, point, status, npasses);
-  } catch (const std::exception &e) {
-    return fail("%s: %s", who, e.what());
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  std::vector<log_event> all, ev;
+  for (auto *x : m->ctx) {
+    if (x->slog.cap == 0) return fail("%s: no step log is set", who);
+    int64_t stored = 0;
+    if (log_read_ctl(x, nullptr, &stored, nullptr) || log_fetch_raw(x, who, stored, ev)) return -1;
+    all.insert(all.end(), ev.begin(), ev.end());
   }
+  if (n < 0 || n > (int64_t)all.size())
+    return fail("%s: n=%lld (%lld records are stored)", who, (long long)n, (long long)all.size());
+  std::sort(all.begin(), all.end(), log_before);
+  all.resize((size_t)n);
+  return log_deliver(all, nt, point, status, npasses);
+  });
 }
 int mckpp_hip_multi_step_log_clear(mckpp_hip_multi_handle m)
 {
-  if (!m) return fail("mckpp_hip_multi_step_log_clear: null handle");
-  MULTI_EACH(mckpp_hip_step_log_clear(x));
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_step_log_clear(x); });
 }
 
 // the caller's arrays pinned on behalf of this handle go back to pageable memory (before the caller frees them)
@@ -3876,8 +3868,7 @@ static int multi_caller_event(mckpp_hip_multi *m, int dev, void *stream)
 int mckpp_hip_multi_fluxes_dev(mckpp_hip_multi_handle m, int ntime, const double *const fields[8], int l_rest, double flsn,
                                double el, void *producer_stream)
 {
-  const char *who = "mckpp_hip_multi_fluxes_dev";
-  if (!m) return fail("%s: null handle", who);
+  return entry(__func__, m, [&, who = __func__]() -> int {
   int dev = -1;
   for (auto *x : m->ctx)
     if (dev_fields_check(x, who, fields, &dev)) return -1;
@@ -3886,12 +3877,12 @@ int mckpp_hip_multi_fluxes_dev(mckpp_hip_multi_handle m, int ntime, const double
   for (auto *x : m->ctx)
     if (fluxes_dev_queue(x, ntime, fields, l_rest, flsn, el, m->ev_caller)) return -1;
   return 0;
+  });
 }
 
 int mckpp_hip_multi_flux_ring_put_dev(mckpp_hip_multi_handle m, int rec, const double *const fields[8], void *producer_stream)
 {
-  const char *who = "mckpp_hip_multi_flux_ring_put_dev";
-  if (!m) return fail("%s: null handle", who);
+  return entry(__func__, m, [&, who = __func__]() -> int {
   if (!fields) return fail("%s: null argument", who);
   int dev = -1;
   for (auto *x : m->ctx)
@@ -3901,12 +3892,12 @@ int mckpp_hip_multi_flux_ring_put_dev(mckpp_hip_multi_handle m, int rec, const d
   for (auto *x : m->ctx)
     if (ring_put_dev_queue(x, rec, fields, m->ev_caller)) return -1;
   return 0;
+  });
 }
 
 int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
 {
-  const char *who = "mckpp_hip_multi_fetch_dev";
-  if (!m) return fail("%s: null handle", who);
+  return entry(__func__, m, [&, who = __func__]() -> int {
   const int ndev = (int)m->ctx.size();
   std::vector<std::vector<mckpp_fetch_plane>> tabs((size_t)ndev);
   int maxlev = 0, dev = -1;
@@ -3931,21 +3922,24 @@ int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const m
   for (int d = 0; d < ndev; ++d)
     if (fetch_dev_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
   return 0;
+  });
 }
 
 int mckpp_hip_multi_dev_fence(mckpp_hip_multi_handle m, void *stream)
 {
-  if (!m) return fail("mckpp_hip_multi_dev_fence: null handle");
+  return entry(__func__, m, [&]() -> int {
   for (auto *x : m->ctx)
     if (dev_fence_queue(x, stream)) return -1;
   return 0;
+  });
 }
 
 int mckpp_hip_multi_release_host_arrays(mckpp_hip_multi_handle m)
 {
-  if (!m) return fail("null multi handle");
+  return entry(__func__, m, [&]() -> int {
   for (auto *x : m->ctx) { HIPCHK(hipSetDevice(x->device)); if (xfer_finish(x)) return -1; unpin_all(x); }
   return 0;
+  });
 }
 
 }  // extern "C"

@@ -43,15 +43,17 @@ def test_new_entry_points_fail_with_a_message_without_a_context(api):
     lib = api._lib()
     v = (C.c_double * 8)()
     ep = (api._AncEpochC * 2)()
-    for pre, msg in (("mckpp_hip_", b": null handle"), ("mckpp_hip_multi_", b"null multi handle")):
+    for pre in ("mckpp_hip_", "mckpp_hip_multi_"):
+        msg = (pre + "set_ancillary_series: null handle").encode()
         assert getattr(lib, pre + "set_ancillary_series")(None, api.ANC_SST0, 0, 2, v) < 0
-        assert msg in lib.mckpp_hip_last_error()
+        assert msg == lib.mckpp_hip_last_error()
         assert getattr(lib, pre + "set_ancillary_series")(None, api.ANC_SST0, 0, 0, None) < 0
-        assert msg in lib.mckpp_hip_last_error()
+        assert msg == lib.mckpp_hip_last_error()
+        msg = (pre + "ancillary_schedule: null handle").encode()
         assert getattr(lib, pre + "ancillary_schedule")(None, api.ANC_OCNT_CLIM, 1, 2, 0, 2, ep) < 0
-        assert msg in lib.mckpp_hip_last_error()
+        assert msg == lib.mckpp_hip_last_error()
         assert getattr(lib, pre + "ancillary_schedule")(None, api.ANC_OCNT_CLIM, 1, 2, 0, 0, None) < 0
-        assert msg in lib.mckpp_hip_last_error()
+        assert msg == lib.mckpp_hip_last_error()
     for cls in (api.MckppHip, api.MckppHipMulti):
         h = cls.__new__(cls)
         h._h = C.c_void_p()

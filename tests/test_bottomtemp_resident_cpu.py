@@ -72,7 +72,7 @@ def test_new_entry_points_refuse_a_null_handle(api):
     assert lib.mckpp_hip_set_bottomtemp(None, None) < 0   # (a cancel)
     assert b"mckpp_hip_set_bottomtemp: null handle" in lib.mckpp_hip_last_error()
     assert lib.mckpp_hip_multi_set_bottomtemp(None, v) < 0
-    assert b"null multi handle" in lib.mckpp_hip_last_error()
+    assert b"mckpp_hip_multi_set_bottomtemp: null handle" == lib.mckpp_hip_last_error()
     for cls in (api.MckppHip, api.MckppHipMulti):
         h = cls.__new__(cls)
         h._h = C.c_void_p()
