@@ -18,7 +18,8 @@ with the reference index directly.  All compute happens in libmckpp_hip.so.
 A new entry point of include/mckpp_hip.h takes two lines here: its signature in _SIGNATURES (twin=True when a
 mckpp_hip_multi_ form with the same signature exists) and, for a handle function, one method on _Handle that calls
 self._call(name, ...) - MckppHip and MckppHipMulti then both have it.  The device-array interface of
-include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its methods are the mixin _DeviceArrays.
+include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its methods are the mixin _DeviceArrays; so
+have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, and their methods are _WindowSchedules'.
 """
 import ctypes as C
 import sys
@@ -130,6 +131,62 @@ def _win_check_fetch(scheds, sched, field, op):
     if not (kept[f] >> int(op)) & 1:
         raise ValueError(f"output schedule {sched} keeps no op {op} of field {OUT_FIELDS[f]} (operations {kept[f]:#x})")
     return f
+
+
+class _Kept(dict):
+    """What a schedule keeps, field -> operation mask, as _WindowSchedules records it; `zoom` is None, or
+    (npoints, nlev) of a zoomed schedule: the point axis of its records and the levels of its 3-D fields."""
+    zoom = None
+
+
+def _win_zoom_args(points, levels, npts, nzp1):
+    """(points, levels) of window_schedule_zoom as (the int32 array or None, lev0, nlev): a point outside the grid or
+    given twice, an empty list and a level range outside the axis are refused here.  npts / nzp1 0: not known yet (no
+    upload: the library refuses the call itself)."""
+    pts = None
+    if points is not None:
+        pts = np.ascontiguousarray(points)
+        if pts.size < 1:
+            raise ValueError("zoom: an empty point list (None: every point)")
+        if pts.ndim != 1 or pts.dtype.kind not in "iu":
+            raise ValueError("zoom: points is a one-dimensional list of integer point numbers")
+        bad = (pts < 0) | (pts >= npts) if npts else pts < 0
+        if bad.any():
+            i = int(np.argmax(bad))
+            raise ValueError(f"zoom: point {int(pts[i])} at position {i} is outside 0..{npts - 1 if npts else ''}")
+        order = np.argsort(pts, kind="stable")
+        same = np.nonzero(pts[order][1:] == pts[order][:-1])[0]
+        if len(same):
+            a, b = int(order[same[0]]), int(order[same[0] + 1])
+            raise ValueError(f"zoom: point {int(pts[a])} twice, at positions {a} and {b}")
+        pts = np.ascontiguousarray(pts, dtype=np.int32)
+    lev0, nlev = (0, 0) if levels is None else (int(levels[0]), int(levels[1]))
+    if nlev < 0 or lev0 < 0 or (nzp1 and lev0 + nlev > nzp1) or (nlev == 0 and lev0 != 0):
+        raise ValueError(f"zoom: levels (lev0={lev0}, nlev={nlev}): a range within 0..{nzp1 or ''} ((0, 0) or None: the whole axis)")
+    return pts, lev0, nlev
+
+
+def _win_check_out(scheds, sched, field, out):
+    """the array of a fetch from a zoomed schedule against the zoom's shape: out(npoints[, nlev])"""
+    kept = scheds.get(int(sched))
+    zoom = getattr(kept, "zoom", None)
+    if zoom is None:
+        return
+    npoints, nlev = zoom
+    two_d = OUT_FIELDS[field] == "hmix" or field >= OUT["fcorr"]
+    want = npoints * (1 if two_d else nlev)
+    if out.size != want:
+        raise ValueError(f"output schedule {sched} is zoomed: a plane of {OUT_FIELDS[field]} is out({npoints}"
+                         f"{'' if two_d else f', {nlev}'}), {want} values, not {out.size}")
+
+
+def zoom_box(nx, ny, ibegin, ni, jbegin, nj):
+    """mckpp_host_zoom_box: the point numbers (int32, i fastest) of the box of ni x nj points from (ibegin, jbegin),
+    0-based, of an nx x ny grid - an XIOS zoom_domain as the `points` of window_schedule_zoom."""
+    nx, ny, ibegin, ni, jbegin, nj = (int(v) for v in (nx, ny, ibegin, ni, jbegin, nj))
+    pts = np.zeros(max(ni, 0) * max(nj, 0), dtype=np.int32)
+    _chk(_lib().mckpp_host_zoom_box(nx, ny, ibegin, ni, jbegin, nj, pts.ctypes.data_as(_ip)))
+    return pts
 
 
 # element types of an export (mckpp_hip_window_export): MCKPP_EXP_* of mckpp_hip.h
@@ -309,6 +366,21 @@ _SIGNATURES_DEVICE = {
 }
 
 
+class _WinZoomC(C.Structure):
+    """mckpp_win_zoom_c"""
+    _fields_ = [("points", _ip), ("npoints", C.c_int64), ("lev0", C.c_int32), ("nlev", C.c_int32)]
+
+
+# Every function of include/mckpp_hip_zoom.h, output schedules over chosen points and levels, in the same form;
+# tests/test_window_zoom_cpu.py holds this table to that header.
+_SIGNATURES_ZOOM = {
+    "mckpp_hip_window_schedule_zoom": _sig(_H, _i, _i, _i, _i, _ip, C.POINTER(C.c_uint32), _i32, C.POINTER(_WinZoomC),
+                                           twin=True),
+    "mckpp_hip_window_zoom": _sig(_H, _i, _i64p, _ip, _ip, _i64p, twin=True),
+    "mckpp_host_zoom_box": _sig(_i64, _i64, _i64, _i64, _i64, _i64, _ip),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -329,12 +401,17 @@ def _signatures_device():
     return _spelled(_SIGNATURES_DEVICE)
 
 
+def _signatures_zoom():
+    """... and of every function of mckpp_hip_zoom.h."""
+    return _spelled(_SIGNATURES_ZOOM)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
     # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
     # everything else works with it, and a call of that name fails there by name
-    for name, (res, argtypes) in {**_signatures(), **_signatures_device()}.items():
+    for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -496,8 +573,29 @@ class _WindowSchedules:
         """Schedule `sched` (0..WIN_SCHEDULES-1): window w covers steps nt_origin + w*period .. + period-1, nrec records
         in a ring; fields are OUT_* indices or names, ops one WIN_* mask for all or one per field.  No fields: cancel."""
         f, o = _win_args(fields, ops)
-        if self._raw("window_schedule", int(sched), int(nt_origin), int(period), int(nrec), f.ctypes.data_as(_ip),
-                     o.ctypes.data_as(C.POINTER(C.c_uint32)), len(f)) != 0:
+        self._win_set("window_schedule", sched, (int(nt_origin), int(period), int(nrec)), f, o, (), None)
+
+    def window_schedule_zoom(self, sched, nt_origin, period, nrec, fields, ops, points=None, levels=None):
+        """window_schedule restricted to `points` - distinct 0-based point numbers of the 3-D ordering in any order, land
+        allowed; None: every point - and to levels = (lev0, nlev) of each 3-D field's own axis (None: the whole axis).
+        The records, the export and the fetches have the zoom's shape: out(len(points)[, nlev]), in list order."""
+        f, o = _win_args(fields, ops)
+        pts, lev0, nlev = _win_zoom_args(points, levels, self._npts, self._nzp1)
+        z = _WinZoomC(pts.ctypes.data_as(_ip) if pts is not None else None, 0 if pts is None else len(pts), lev0, nlev)
+        shape = (self._npts if pts is None else len(pts), nlev or self._nzp1)
+        self._win_set("window_schedule_zoom", sched, (int(nt_origin), int(period), int(nrec)), f, o, (C.byref(z),), shape)
+
+    def window_zoom(self, sched):
+        """(npoints, lev0, nlev, ring_bytes) of schedule `sched`, zoomed or not: the point axis of its records, the level
+        range of its 3-D fields, the device bytes of its record ring (all shards'; without the export)."""
+        n, l0, nl, rb = C.c_int64(), C.c_int32(), C.c_int32(), C.c_int64()
+        self._call("window_zoom", int(sched), C.byref(n), C.byref(l0), C.byref(nl), C.byref(rb))
+        return int(n.value), int(l0.value), int(nl.value), int(rb.value)
+
+    def _win_set(self, name, sched, when, f, o, more, shape):
+        """the call that sets or cancels a schedule, and this object's record of what the schedule keeps"""
+        if self._raw(name, int(sched), *when, f.ctypes.data_as(_ip), o.ctypes.data_as(C.POINTER(C.c_uint32)), len(f),
+                     *more) != 0:
             err = _lib().mckpp_hip_last_error().decode()
             a = C.c_int64()
             if self._raw("window_records", int(sched), C.byref(a), C.byref(a)) != 0:
@@ -505,7 +603,9 @@ class _WindowSchedules:
             raise MckppHipError(err)                    # not be had leaves none)
         self.__dict__.get("_wexport", {}).pop(int(sched), None)   # (a schedule set anew has no export)
         if len(f):
-            self._scheds()[int(sched)] = {int(a): int(b) for a, b in zip(f, o)}
+            kept = _Kept((int(a), int(b)) for a, b in zip(f, o))
+            kept.zoom = shape
+            self._scheds()[int(sched)] = kept
         else:
             self._scheds().pop(int(sched), None)
 
@@ -514,6 +614,7 @@ class _WindowSchedules:
         (Fortran order; land points keep what out held)."""
         f = _win_check_fetch(self._scheds(), sched, field, op)
         assert out.flags["F_CONTIGUOUS"] and out.dtype == np.float64
+        _win_check_out(self._scheds(), sched, f, out)
         self._hold(out)
         self._call("window_record_fetch", int(sched), int(rec), f, int(op), out.ctypes.data_as(_dp))
         return out
@@ -563,6 +664,7 @@ class _WindowSchedules:
         as the export was set): what window_record_fetch gives into an array pre-filled with land_value."""
         f = _win_check_fetch(self._scheds(), sched, field, op)
         _exp_check_out(self._exports(), sched, out)
+        _win_check_out(self._scheds(), sched, f, out)
         self._hold(out)
         self._call("window_export_fetch", int(sched), int(rec), f, int(op), out.ctypes.data)
         return out

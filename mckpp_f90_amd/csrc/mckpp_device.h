@@ -41,13 +41,17 @@ template <class T> using mckpp_ptr_global = __attribute__((address_space(1))) T 
 // The field is read as k_out_sample reads it - element off + l of row c (row length ld), plus the column's Sref if
 // add_sref - and folded into the record of the window the step belongs to: window w = (nt - origin) / period, ring slot
 // w % nrec; operation j of the entry (the j-th set bit of ops: sum for the mean, min, max, last) at
-// acc + (slot * nops + j) * plane + c * ld_out + l.
+// acc + (slot * nops + j) * plane + r * ld_out + l, r the column's row of the record.
+// A zoomed schedule (mckpp_hip_window_schedule_zoom) keeps rows for its listed columns only: `row` is its table
+// int[ncol], resident column -> row, or -1 for a column outside the list, whose items pass the entry by.  Null: row =
+// column.  Its level range needs nothing here: the host adds lev0 to `off` and gives the zoomed count as nlev.
 #define MCKPP_WIN_ENTRIES 64
 template <template <class> class P>
 struct mckpp_win_t {
   P<const double> src;
   P<double> acc;
-  long long plane;        // doubles of one operation's record: ncol * ld_out
+  P<const int> row;       // null, or the zoom's table: column -> row of the record, -1: not kept
+  long long plane;        // doubles of one operation's record: rows * ld_out
   int ld, off, nlev, add_sref, ld_out;
   int ops, nops;          // MCKPP_WIN_* mask and its number of bits
   int origin, period, nrec;

@@ -2997,11 +2997,16 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         for (int e = 0; e < p.nwin; ++e) {
           const auto &d = p.win[e];
           if (l >= d.nlev || nt < d.origin) continue;
+          int rw = col;   // the column's row of the record: the column itself, or what a zoomed schedule's table says
+          if (d.row) { rw = d.row[col]; if (rw < 0) continue; }   // (the branch on the pointer is uniform: so is the entry loop)
+          // nothing more of the entry is loaded ahead of that skip: a load still in flight when a skipped item is back in
+          // the pass loop costs every pass a wait for it there
+          asm volatile("" ::: "memory");
           const int q = nt - d.origin, w = q / d.period;
           const bool first = q == w * d.period;   // the window's first step initialises its record
           double v = d.src[(size_t)col * d.ld + d.off + l];
           if (d.add_sref) v = v + p.cs[(size_t)col * MCKPP_CS + CS_SREF];
-          auto r = d.acc + ((size_t)(w % d.nrec) * (size_t)d.nops * (size_t)d.plane + (size_t)col * d.ld_out + l);
+          auto r = d.acc + ((size_t)(w % d.nrec) * (size_t)d.nops * (size_t)d.plane + (size_t)rw * d.ld_out + l);
           const int ops = d.ops;
           if (ops & 1) { const double s_ = first ? 0.0 : r[0]; r[0] = s_ + v; r += d.plane; }
           if (ops & 2) { const double a = first ? v : r[0]; r[0] = v < a ? v : a; r += d.plane; }

@@ -13,6 +13,7 @@
 // that can throw (no allocation, no container growth, no call of fail); mckpp_hip_multi_ctx, which does report
 // through fail, has the barrier.  (The header declares them without noexcept, so their definitions cannot carry it.)
 #include "../../include/mckpp_hip_device.h"
+#include "../../include/mckpp_hip_zoom.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -81,9 +82,22 @@ struct mckpp_ctx_resident {
     std::vector<int> fields;        // empty: no schedule
     std::vector<unsigned> ops;
     std::vector<int> ld_out;
-    std::vector<dev_buf<double>> acc;   // [field]: nrec records of popcount(ops) planes of ncol * ld_out doubles
+    std::vector<dev_buf<double>> acc;   // [field]: nrec records of popcount(ops) planes of nrow * ld_out doubles
     int64_t origin = 1, period = 1;
     int nrec = 1;
+    // The shape of a record (mckpp_hip_window_schedule_zoom; win_set).  A record plane is nrow rows, row r at position
+    // map[r] of the record's point axis of npoints points: an unzoomed schedule has the resident columns as rows, the
+    // column map as map and the grid's points as axis; a schedule with a point list has the listed resident columns, in
+    // list order, their list positions (rowpos) and the list.  So a record is fetched and packed like a field of a
+    // state of nrow columns among npoints points, by the kernels that do that.  [field] nlev levels from lev_off on of
+    // the field's axis are kept (two-dimensional fields: their one value).
+    bool zoomed = false;               // set through a non-null zoom (what mckpp_hip_window_zoom reports)
+    bool listed = false;               // ... with a point list
+    int64_t npoints = 0, nrow = 0;
+    int lev0 = 0, znlev = 0;           // the level range as given
+    std::vector<int> nlev, lev_off;
+    std::vector<int> rowpos;           // listed: row -> list position
+    dev_buf<int> d_rowpos, d_colrow;   // listed: rowpos; resident column -> row, -1 outside the list (mckpp_win_t::row)
     int64_t first_nt = -1, next_nt = -1;   // the first step run under the schedule, the step the next launch must start at (-1: none yet)
     int64_t first_kept = 0;                // the records before it are released, or began before first_nt
     // its export (mckpp_hip_window_export; dtype MCKPP_EXP_OFF: none): nrec slots of record_bytes each, record w in slot
@@ -573,23 +587,30 @@ static int up_rows(mckpp_hip_ctx *h, const double *src, int nlev, double *dst, i
 // device rows -> host Fortran slab; entries of non-resident (land) columns keep their host values.  Queued: the
 // layout kernel on the context's stream, the copy to the host behind it on the copy stream; xfer_finish() before
 // the caller reads `dst`.
-static int down_rows(mckpp_hip_ctx *h, const double *src, int src_ld, int src_off, int nlev, double *dst,
-                     const double *whole = nullptr, size_t whole_elems = 0)
+// The general form: `nrow` rows, row r at point map[r] (a device array) of `npts` points.
+static int down_rows_map(mckpp_hip_ctx *h, const double *src, int src_ld, int src_off, int nlev, double *dst, const int *map,
+                         int64_t nrow, int64_t npts, const double *whole = nullptr, size_t whole_elems = 0)
 {
-  const size_t n = (size_t)h->npts * nlev;
+  const size_t n = (size_t)npts * nlev;
   const unsigned b = h->xfer_seq++ & 1u;
   if (ensure_xfer(h, b, n)) return -1;
   if (whole) pin_host(h, whole, whole_elems * sizeof(double));
   else pin_host(h, dst, n * sizeof(double));
   HIPCHK(hipStreamWaitEvent(h->stream, h->ev_copy[b], 0));   // the transfer that last read this buffer
-  if (h->ncol < h->npts)
+  if (nrow < npts)
     HIPCHK(hipMemcpyAsync(h->d_xfer[b], dst, n * sizeof(double), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(mckpp_launch_scatter_rows(src, src_ld, src_off, h->d_ipt, h->ncol, h->d_xfer[b], h->npts, nlev, 0, h->stream));
+  HIPCHK(mckpp_launch_scatter_rows(src, src_ld, src_off, map, nrow, h->d_xfer[b], npts, nlev, 0, h->stream));
   HIPCHK(hipEventRecord(h->ev_lay[b], h->stream));
   HIPCHK(hipStreamWaitEvent(h->copy_stream, h->ev_lay[b], 0));
   HIPCHK(hipMemcpyAsync(dst, h->d_xfer[b], n * sizeof(double), hipMemcpyDeviceToHost, h->copy_stream));
   HIPCHK(hipEventRecord(h->ev_copy[b], h->copy_stream));
   return 0;
+}
+
+static int down_rows(mckpp_hip_ctx *h, const double *src, int src_ld, int src_off, int nlev, double *dst,
+                     const double *whole = nullptr, size_t whole_elems = 0)
+{
+  return down_rows_map(h, src, src_ld, src_off, nlev, dst, h->d_ipt, h->ncol, h->npts, whole, whole_elems);
 }
 
 static int xfer_finish(mckpp_hip_ctx *h)
@@ -2637,8 +2658,8 @@ static int win_table(mckpp_hip_ctx *h)
       out_desc d;
       if (out_field(h, w.fields[i], d)) return -1;
       mckpp_win e{};
-      e.src = d.src; e.acc = w.acc[i]; e.plane = (long long)h->ncol * w.ld_out[i];
-      e.ld = d.ld; e.off = d.off; e.nlev = d.nlev; e.add_sref = d.add_sref; e.ld_out = w.ld_out[i];
+      e.src = d.src; e.acc = w.acc[i]; e.row = w.d_colrow; e.plane = (long long)w.nrow * w.ld_out[i];
+      e.ld = d.ld; e.off = d.off + w.lev_off[i]; e.nlev = w.nlev[i]; e.add_sref = d.add_sref; e.ld_out = w.ld_out[i];
       e.ops = (int)w.ops[i]; e.nops = __builtin_popcount(w.ops[i]);
       e.origin = (int)w.origin; e.period = (int)w.period; e.nrec = w.nrec;
       t.push_back(e);
@@ -2698,12 +2719,27 @@ static void win_advance(mckpp_hip_ctx *h, int nt0, int nsteps)
   }
 }
 
-int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int period, int nrec, const int32_t *fields,
-                              const uint32_t *ops, int32_t nfields)
+// the levels a field keeps under a level range (znlev 0: the whole axis; a two-dimensional field: its one value)
+static void win_levels(int axis, int lev0, int znlev, int &off, int &nlev)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
+  off = 0; nlev = axis;
+  if (axis > 1 && znlev > 0) { off = lev0; nlev = znlev; }
+}
+
+// A row of a record plane: one double for a single level, else the smallest multiple of 8 doubles (a 64-byte line)
+// that holds the levels; an unzoomed schedule keeps the rows of the state, ld doubles.
+static int win_ld_out(const mckpp_hip_ctx *h, bool zoomed, int nlev)
+{
+  return nlev == 1 ? 1 : zoomed ? (nlev + 7) / 8 * 8 : h->ld;
+}
+
+// The body of mckpp_hip_window_schedule and mckpp_hip_window_schedule_zoom: a schedule is set here and nowhere else.
+static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, int period, int nrec, const int32_t *fields,
+                   const uint32_t *ops, int32_t nfields, const mckpp_win_zoom_c *zoom)
+{
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
   if (nfields < 0 || (nfields > 0 && (!fields || !ops))) return fail("%s: bad argument (nfields=%d)", who, nfields);
+  std::vector<int> colrow, rowpos;   // of a point list
   if (nfields > 0) {   // everything is checked before the schedule in place is touched
     if (nt_origin < 1 || period < 1 || nrec < 1)
       return fail("%s: nt_origin=%d period=%d nrec=%d (each at least 1)", who, nt_origin, period, nrec);
@@ -2723,6 +2759,32 @@ int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int 
       if (out_field(h, f, d)) return -1;   // (the message of window_accumulate: a correction field without the rows)
       if (win_is_diag(f) && !h->diag) return fail("%s: field %d is a diagnostic, and diagnostics are switched off", who, f);
     }
+    if (zoom) {
+      if (zoom->nlev < 0 || zoom->lev0 < 0 || (int64_t)zoom->lev0 + zoom->nlev > h->nzp1 || (zoom->nlev == 0 && zoom->lev0 != 0))
+        return fail("%s: zoom: levels lev0=%d nlev=%d (a range within 0..%d; 0, 0: the whole axis)", who, zoom->lev0, zoom->nlev, h->nzp1);
+      if (zoom->points) {
+        if (zoom->npoints < 1) return fail("%s: zoom: npoints=%lld with a point list (at least 1)", who, (long long)zoom->npoints);
+        std::vector<int64_t> at((size_t)h->npts, -1);   // point -> its position in the list
+        for (int64_t i = 0; i < zoom->npoints; ++i) {
+          const int64_t pt = zoom->points[i];
+          if (pt < 0 || pt >= h->npts)
+            return fail("%s: zoom: point %lld at position %lld is outside 0..%lld", who, (long long)pt, (long long)i, (long long)h->npts - 1);
+          if (at[(size_t)pt] >= 0)
+            return fail("%s: zoom: point %lld twice, at positions %lld and %lld", who, (long long)pt, (long long)at[(size_t)pt], (long long)i);
+          at[(size_t)pt] = i;
+        }
+        // rows in list order: the listed points that are resident columns
+        std::vector<int> colof((size_t)h->npts, -1);
+        for (int64_t c = 0; c < h->ncol; ++c) colof[(size_t)h->ipt[(size_t)c]] = (int)c;
+        colrow.assign((size_t)h->ncol, -1);
+        for (int64_t i = 0; i < zoom->npoints; ++i) {
+          const int c = colof[(size_t)zoom->points[i]];
+          if (c < 0) continue;
+          colrow[(size_t)c] = (int)rowpos.size();
+          rowpos.push_back((int)i);
+        }
+      }
+    }
   }
   HIPCHK(hipSetDevice(h->device));
   HIPCHK(hipStreamSynchronize(h->stream));   // no launch in flight may still read the table or write the records
@@ -2730,28 +2792,109 @@ int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int 
   if (nfields > 0) {
     mckpp_hip_ctx::win_sched w;   // built here, moved in when every ring is there
     w.origin = nt_origin; w.period = period; w.nrec = nrec;
-    for (int i = 0; i < nfields; ++i) {
+    w.zoomed = zoom != nullptr;
+    w.listed = zoom && zoom->points;
+    w.npoints = w.listed ? zoom->npoints : h->npts;
+    w.nrow = w.listed ? (int64_t)rowpos.size() : h->ncol;
+    if (zoom) { w.lev0 = zoom->lev0; w.znlev = zoom->nlev; }
+    hipError_t e = hipSuccess;
+    size_t bytes = 0;
+    int failed = -1;
+    if (w.listed && h->ncol > 0) {
+      bytes = (colrow.size() + rowpos.size()) * sizeof(int);
+      e = w.d_colrow.alloc(colrow.size());
+      if (e == hipSuccess) e = hipMemcpy(w.d_colrow, colrow.data(), colrow.size() * sizeof(int), hipMemcpyHostToDevice);
+      if (e == hipSuccess && w.nrow > 0) e = w.d_rowpos.alloc(rowpos.size());
+      if (e == hipSuccess && w.nrow > 0) e = hipMemcpy(w.d_rowpos, rowpos.data(), rowpos.size() * sizeof(int), hipMemcpyHostToDevice);
+    }
+    w.rowpos = std::move(rowpos);
+    for (int i = 0; i < nfields && e == hipSuccess; ++i) {
       out_desc d;
       out_field(h, fields[i], d);
-      const int ld_out = d.nlev == 1 ? 1 : h->ld;
-      const size_t elems = (size_t)nrec * (size_t)__builtin_popcount(ops[i]) * (size_t)h->ncol * (size_t)ld_out, bytes = elems * sizeof(double);
+      int off = 0, nlev = 0;
+      win_levels(d.nlev, w.lev0, w.znlev, off, nlev);
+      const int ld_out = win_ld_out(h, w.zoomed, nlev);
+      const size_t elems = (size_t)nrec * (size_t)__builtin_popcount(ops[i]) * (size_t)w.nrow * (size_t)ld_out;
+      bytes = elems * sizeof(double);
       dev_buf<double> p;
-      if (bytes > 0) {
-        const hipError_t e = p.alloc(elems);
-        if (e != hipSuccess) {
-          (void)hipGetLastError();
-          win_table(h);   // (of the other schedules)
-          return fail("%s: cannot allocate %zu bytes of device memory for the %d records of field %d (%s); the schedule is "
-                      "not set", who, bytes, nrec, fields[i], hipGetErrorString(e));
-        }
-      }
+      if (bytes > 0) e = p.alloc(elems);
+      if (e != hipSuccess) failed = fields[i];
       w.fields.push_back(fields[i]); w.ops.push_back(ops[i]); w.ld_out.push_back(ld_out); w.acc.push_back(std::move(p));
+      w.nlev.push_back(nlev); w.lev_off.push_back(off);
+    }
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      win_table(h);   // (of the other schedules)
+      if (failed < 0)
+        return fail("%s: cannot set up the %zu bytes of the zoom's tables on the device (%s); the schedule is not set", who, bytes,
+                    hipGetErrorString(e));
+      return fail("%s: cannot allocate %zu bytes of device memory for the %d records of field %d (%s); the schedule is "
+                  "not set", who, bytes, nrec, failed, hipGetErrorString(e));
     }
     h->wsched[sched] = std::move(w);
   }
   return win_table(h);
+}
+
+int mckpp_hip_window_schedule(mckpp_hip_handle h, int sched, int nt_origin, int period, int nrec, const int32_t *fields,
+                              const uint32_t *ops, int32_t nfields)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  return win_set(h, who, sched, nt_origin, period, nrec, fields, ops, nfields, nullptr);
   });
 }
+
+int mckpp_hip_window_schedule_zoom(mckpp_hip_handle h, int sched, int nt_origin, int period, int nrec, const int32_t *fields,
+                                   const uint32_t *ops, int32_t nfields, const mckpp_win_zoom_c *zoom)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  return win_set(h, who, sched, nt_origin, period, nrec, fields, ops, nfields, zoom);
+  });
+}
+
+// the device bytes of a schedule's record ring (without its export and without the zoom's two small tables)
+static int64_t win_ring_bytes(const mckpp_hip_ctx::win_sched &w)
+{
+  int64_t b = 0;
+  for (size_t i = 0; i < w.fields.size(); ++i)
+    b += (int64_t)w.nrec * __builtin_popcount(w.ops[i]) * w.nrow * w.ld_out[i] * (int64_t)sizeof(double);
+  return b;
+}
+
+int mckpp_hip_window_zoom(mckpp_hip_handle h, int sched, int64_t *npoints, int32_t *lev0, int32_t *nlev, int64_t *ring_bytes)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
+  const auto &w = h->wsched[sched];
+  if (w.fields.empty()) return fail("%s: schedule %d is not set", who, sched);
+  if (npoints) *npoints = w.npoints;
+  if (lev0) *lev0 = w.znlev > 0 ? w.lev0 : 0;
+  if (nlev) *nlev = w.znlev > 0 ? w.znlev : h->nzp1;
+  if (ring_bytes) *ring_bytes = win_ring_bytes(w);
+  return 0;
+  });
+}
+
+// XIOS zoom_domain: the box ibegin .. ibegin + ni - 1, jbegin .. jbegin + nj - 1 (0-based) of an nx x ny grid as point
+// numbers of the 3-D ordering, i fastest: ni * nj of them
+int mckpp_host_zoom_box(int64_t nx, int64_t ny, int64_t ibegin, int64_t ni, int64_t jbegin, int64_t nj, int32_t *points)
+{
+  return entry(__func__, [&, who = __func__]() -> int {
+  if (!points) return fail("%s: null argument", who);
+  if (nx < 1 || ny < 1 || nx * ny > INT32_MAX) return fail("%s: grid %lld x %lld", who, (long long)nx, (long long)ny);
+  if (ni < 1 || nj < 1 || ibegin < 0 || jbegin < 0 || ibegin + ni > nx || jbegin + nj > ny)
+    return fail("%s: box i %lld..%lld, j %lld..%lld is not within the grid of %lld x %lld points", who, (long long)ibegin,
+                (long long)(ibegin + ni - 1), (long long)jbegin, (long long)(jbegin + nj - 1), (long long)nx, (long long)ny);
+  int64_t n = 0;
+  for (int64_t j = jbegin; j < jbegin + nj; ++j)
+    for (int64_t i = ibegin; i < ibegin + ni; ++i) points[n++] = (int32_t)(j * nx + i);
+  return 0;
+  });
+}
+
+// row -> position on the record's point axis: on the device, and on the host
+static const int *win_map(const mckpp_hip_ctx *h, const mckpp_hip_ctx::win_sched &w) { return w.listed ? w.d_rowpos.get() : h->d_ipt.get(); }
+static const std::vector<int> &win_host_map(const mckpp_hip_ctx *h, const mckpp_hip_ctx::win_sched &w) { return w.listed ? w.rowpos : h->ipt; }
 
 // may record `rec` of the schedule be fetched - all of it (plane false), or its plane of `field` and `op`, whose index
 // among the schedule's fields comes back in *fi?  Otherwise an error that names the record's steps.
@@ -2791,11 +2934,11 @@ static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec,
   out_desc d;
   if (out_field(h, field, d)) return -1;
   *ld_out = w.ld_out[i];
-  *nlev = d.nlev;
+  *nlev = w.nlev[i];
   *src_out = nullptr;
-  if (h->ncol == 0) return 0;
+  if (w.nrow == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  const size_t n = (size_t)h->ncol * w.ld_out[i];
+  const size_t n = (size_t)w.nrow * w.ld_out[i];
   const int j = __builtin_popcount(w.ops[i] & ((1u << op) - 1u));
   const double *src = w.acc[i] + ((size_t)(rec % w.nrec) * (size_t)__builtin_popcount(w.ops[i]) + (size_t)j) * n;
   if (op == 0) {   // the mean: window_fetch's sum / count, the count a whole window's
@@ -2814,8 +2957,9 @@ int mckpp_hip_window_record_fetch(mckpp_hip_handle h, int sched, int64_t rec, in
   const double *src = nullptr;
   int ld_out = 0, nlev = 0;
   if (win_record(h, who, sched, rec, field, op, &src, &ld_out, &nlev)) return -1;
-  if (h->ncol == 0) return 0;
-  if (down_rows(h, src, ld_out, 0, nlev, out)) return -1;
+  const auto &w = h->wsched[sched];
+  if (w.nrow == 0) return 0;   // (no listed point is a resident column: `out` stays as it is)
+  if (down_rows_map(h, src, ld_out, 0, nlev, out, win_map(h, w), w.nrow, w.npoints)) return -1;
   return xfer_finish(h);
   });
 }
@@ -2869,14 +3013,12 @@ static int exp_layout(mckpp_hip_ctx *h, const win_sched_t &w, int64_t npts, int 
   size_t off = 0;
   maxlev = 0;
   for (size_t i = 0; i < w.fields.size(); ++i) {
-    out_desc d;
-    if (out_field(h, w.fields[i], d)) return -1;
     for (int op = 0; op < 4; ++op) {
       if (!((w.ops[i] >> op) & 1u)) continue;
-      planes.push_back({w.fields[i], op, d.nlev, (int64_t)off});
-      off += (size_t)npts * (size_t)d.nlev * exp_elem(dtype);
+      planes.push_back({w.fields[i], op, w.nlev[i], (int64_t)off});
+      off += (size_t)npts * (size_t)w.nlev[i] * exp_elem(dtype);
       off = (off + 255) & ~(size_t)255;
-      maxlev = std::max(maxlev, d.nlev);
+      maxlev = std::max(maxlev, w.nlev[i]);
     }
   }
   record_bytes = off;
@@ -2888,9 +3030,9 @@ static int exp_pack(mckpp_hip_ctx *h, win_sched_t &w, int64_t rec)
 {
   auto &x = w.ex;
   const size_t slot = (size_t)(rec % w.nrec);
-  if (x.slots && h->ncol > 0)
+  if (x.slots && w.nrow > 0)
     HIPCHK(mckpp_launch_record_pack(x.d_tab, (int)x.planes.size(), x.maxlev, (int)slot, (double)w.period,
-                                    x.compact ? nullptr : h->d_ipt, h->ncol, x.npts, x.slots + slot * x.record_bytes,
+                                    x.compact ? nullptr : win_map(h, w), w.nrow, x.npts, x.slots + slot * x.record_bytes,
                                     x.dtype == MCKPP_EXP_F32, h->stream));
   HIPCHK(hipEventRecord(x.ev[slot], h->stream));
   return 0;
@@ -2938,13 +3080,13 @@ static int exp_set(mckpp_hip_ctx *h, const char *who, int sched, int dtype, doub
   if (dtype == MCKPP_EXP_OFF) return 0;
   win_sched_t::win_export x;
   x.dtype = dtype; x.compact = compact; x.land = land_value;
-  x.npts = compact ? h->ncol : h->npts;
+  x.npts = compact ? w.nrow : w.npoints;
   if (exp_layout(h, w, x.npts, dtype, x.planes, x.record_bytes, x.maxlev)) return -1;
   std::vector<mckpp_pack_plane> tab;
   for (const auto &p : x.planes) {
     size_t i = 0;
     while (w.fields[i] != p.field) ++i;
-    const long long n = (long long)h->ncol * w.ld_out[i];
+    const long long n = (long long)w.nrow * w.ld_out[i];
     mckpp_pack_plane e{};
     e.src = w.acc[i] + (long long)__builtin_popcount(w.ops[i] & ((1u << p.op) - 1u)) * n;
     e.slot_stride = (long long)__builtin_popcount(w.ops[i]) * n;
@@ -2979,8 +3121,8 @@ int mckpp_hip_window_export(mckpp_hip_handle h, int sched, int dtype, double lan
   return entry(__func__, h, [&, who = __func__]() -> int { return exp_set(h, who, sched, dtype, land_value, false); });
 }
 
-// the layout of a record of the schedule's export over npts points
-static int exp_layout_out(mckpp_hip_ctx *h, const char *who, int sched, int64_t npts, int32_t *nplanes, int32_t *field, int32_t *op,
+// the layout of a record of the schedule's export over the points of its point axis (a shard's: of all shards')
+static int exp_layout_out(mckpp_hip_ctx *h, const char *who, int sched, int32_t *nplanes, int32_t *field, int32_t *op,
                           int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes)
 {
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
@@ -2990,7 +3132,7 @@ static int exp_layout_out(mckpp_hip_ctx *h, const char *who, int sched, int64_t 
   std::vector<win_sched_t::exp_plane> planes;
   size_t rb = 0;
   int maxlev = 0;
-  if (exp_layout(h, w, npts, w.ex.dtype, planes, rb, maxlev)) return -1;
+  if (exp_layout(h, w, w.npoints, w.ex.dtype, planes, rb, maxlev)) return -1;
   if (nplanes) *nplanes = (int32_t)planes.size();
   for (size_t k = 0; k < planes.size(); ++k) {
     if (field) field[k] = planes[k].field;
@@ -3006,7 +3148,7 @@ int mckpp_hip_window_export_layout(mckpp_hip_handle h, int sched, int32_t *nplan
                                    int64_t *offset_bytes, int64_t *record_bytes)
 {
   return entry(__func__, h, [&, who = __func__]() -> int {
-  return exp_layout_out(h, who, sched, h->npts, nplanes, field, op, nlev, offset_bytes, record_bytes);
+  return exp_layout_out(h, who, sched, nplanes, field, op, nlev, offset_bytes, record_bytes);
   });
 }
 
@@ -3175,6 +3317,7 @@ struct mckpp_multi_root {
   dev_buf<double> d_out, d_stage;           // grow-only (multi_prepare_root)
   dev_buf<int> d_gipt;
   bool gipt_valid = false;                  // d_gipt holds the maps of the current upload
+  dev_buf<int> d_zmap;                      // grow-only: the shards' row maps of the zoomed record being gathered
 };
 
 struct mckpp_hip_multi : mckpp_multi_root {
@@ -3389,29 +3532,49 @@ static int multi_prepare_root(mckpp_hip_multi *m, int root, size_t nout, size_t 
   return 0;
 }
 
+// The shards' rows gathered into out(npts, nlev).  `z` null: a shard's rows are its resident columns, at the points of
+// its column map.  Otherwise the rows of a record with a point list (mckpp_hip_window_schedule_zoom): shard d has
+// z->nrow[d] of them, row r at position z->map[d][r] of the list's z->npoints points.
+struct multi_rows { int64_t npoints; std::vector<int64_t> nrow; std::vector<const std::vector<int> *> map; };
+
 static int multi_gather_rows(mckpp_hip_multi *m, int root, const std::vector<const double *> &src, int ld, int src_off,
-                             int nlev, double *out, const double *whole = nullptr, size_t whole_elems = 0)
+                             int nlev, double *out, const double *whole = nullptr, size_t whole_elems = 0,
+                             const multi_rows *z = nullptr)
 {
   const int ndev = (int)m->ctx.size();
   mckpp_hip_ctx *r = m->ctx[root];
-  const size_t nout = (size_t)m->npts * nlev;
+  const int64_t npts = z ? z->npoints : m->npts;
+  auto rows_of = [&](int d) { return z ? z->nrow[(size_t)d] : m->ctx[d]->ncol; };
+  const size_t nout = (size_t)npts * nlev;
   size_t nstage = 0, ncols = 0;
   for (int d = 0; d < ndev; ++d) {
-    ncols += (size_t)m->ctx[d]->ncol;
-    if (d != root) nstage += (size_t)m->ctx[d]->ncol * ld;   // the root's own rows are read where they are
+    ncols += (size_t)rows_of(d);
+    if (d != root) nstage += (size_t)rows_of(d) * ld;   // the root's own rows are read where they are
   }
+  if (z && ncols == 0) return 0;   // (no listed point is a resident column: `out` stays as it is)
   if (multi_prepare_root(m, root, nout, nstage ? nstage : 1)) return -1;
+  const int *map = m->d_gipt;
+  if (z) {   // (the gathers before this one have delivered: multi_gather_finish)
+    HIPCHK(m->d_zmap.reserve(ncols));
+    size_t go = 0;
+    for (int d = 0; d < ndev; ++d) {
+      if (rows_of(d)) HIPCHK(hipMemcpy(m->d_zmap + go, z->map[(size_t)d]->data(), (size_t)rows_of(d) * sizeof(int), hipMemcpyHostToDevice));
+      go += (size_t)rows_of(d);
+    }
+    map = m->d_zmap;
+  }
   if (whole) pin_host(r, whole, whole_elems * sizeof(double));
   else pin_host(r, out, nout * sizeof(double));
   // the 3-D image: behind the transfer of the previous gather; land points keep the caller's values
   HIPCHK(hipStreamWaitEvent(r->stream, m->ev_gcopy, 0));
-  if (ncols < (size_t)m->npts) HIPCHK(hipMemcpyAsync(m->d_out, out, nout * sizeof(double), hipMemcpyHostToDevice, r->stream));
+  if (ncols < (size_t)npts) HIPCHK(hipMemcpyAsync(m->d_out, out, nout * sizeof(double), hipMemcpyHostToDevice, r->stream));
   HIPCHK(hipEventRecord(m->ev_init, r->stream));
   size_t so = 0, go = 0;
   for (int d = 0; d < ndev; ++d) {
     mckpp_hip_ctx *x = m->ctx[d];
-    if (x->ncol == 0) continue;
-    const size_t n = (size_t)x->ncol * ld;
+    const int64_t nrow = rows_of(d);
+    if (nrow == 0) continue;
+    const size_t n = (size_t)nrow * ld;
     hipStream_t gs = m->gstream[d];
     HIPCHK(hipSetDevice(x->device));
     HIPCHK(hipEventRecord(m->ev_owner[d], x->stream));   // whatever the owner's stream still has queued
@@ -3425,10 +3588,10 @@ static int multi_gather_rows(mckpp_hip_multi *m, int root, const std::vector<con
       rows = m->d_stage + so;
       so += n;
     }
-    HIPCHK(mckpp_launch_scatter_rows(rows, ld, src_off, m->d_gipt + go, x->ncol, m->d_out, m->npts, nlev, 0, gs));
+    HIPCHK(mckpp_launch_scatter_rows(rows, ld, src_off, map + go, nrow, m->d_out, npts, nlev, 0, gs));
     HIPCHK(hipEventRecord(m->ev_done[d], gs));
     HIPCHK(hipStreamWaitEvent(r->copy_stream, m->ev_done[d], 0));
-    go += (size_t)x->ncol;
+    go += (size_t)nrow;
   }
   HIPCHK(hipStreamWaitEvent(r->copy_stream, m->ev_init, 0));
   HIPCHK(hipMemcpyAsync(out, m->d_out, nout * sizeof(double), hipMemcpyDeviceToHost, r->copy_stream));
@@ -3560,6 +3723,26 @@ int mckpp_hip_multi_window_schedule(mckpp_hip_multi_handle m, int sched, int nt_
 {
   return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_schedule(x, sched, nt_origin, period, nrec, fields, ops, nfields); });
 }
+// a zoomed schedule: every shard checks the whole zoom and keeps rows for the listed points it owns
+int mckpp_hip_multi_window_schedule_zoom(mckpp_hip_multi_handle m, int sched, int nt_origin, int period, int nrec,
+                                         const int32_t *fields, const uint32_t *ops, int32_t nfields, const mckpp_win_zoom_c *zoom)
+{
+  return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_window_schedule_zoom(x, sched, nt_origin, period, nrec, fields, ops, nfields, zoom); });
+}
+// the zoom of shard 0 (every shard's), ring_bytes summed over the shards
+int mckpp_hip_multi_window_zoom(mckpp_hip_multi_handle m, int sched, int64_t *npoints, int32_t *lev0, int32_t *nlev, int64_t *ring_bytes)
+{
+  return entry(__func__, m, [&]() -> int {
+  int64_t sum = 0;
+  for (auto *x : m->ctx) {
+    int64_t b = 0;
+    if (mckpp_hip_window_zoom(x, sched, npoints, lev0, nlev, &b)) return -1;
+    sum += b;
+  }
+  if (ring_bytes) *ring_bytes = sum;
+  return 0;
+  });
+}
 int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int64_t rec, int field, int op, double *out)
 {
   return entry(__func__, m, [&, who = __func__]() -> int {
@@ -3570,7 +3753,12 @@ int mckpp_hip_multi_window_record_fetch(mckpp_hip_multi_handle m, int sched, int
   int ld_out = 0, nlev = 0;
   for (int d = 0; d < ndev; ++d)
     if (win_record(m->ctx[d], who, sched, rec, field, op, &src[d], &ld_out, &nlev)) return -1;
-  if (multi_gather_rows(m, 0, src, ld_out, 0, nlev, out)) return -1;
+  multi_rows z;
+  if (m->ctx[0]->wsched[sched].listed) {
+    z.npoints = m->ctx[0]->wsched[sched].npoints;
+    for (auto *x : m->ctx) { z.nrow.push_back(x->wsched[sched].nrow); z.map.push_back(&x->wsched[sched].rowpos); }
+  }
+  if (multi_gather_rows(m, 0, src, ld_out, 0, nlev, out, nullptr, 0, z.map.empty() ? nullptr : &z)) return -1;
   return multi_gather_finish(m);
   });
 }
@@ -3663,7 +3851,7 @@ int mckpp_hip_multi_window_export_layout(mckpp_hip_multi_handle m, int sched, in
                                          int32_t *nlev, int64_t *offset_bytes, int64_t *record_bytes)
 {
   return entry(__func__, m, [&, who = __func__]() -> int {
-  return exp_layout_out(m->ctx[0], who, sched, m->npts, nplanes, field, op, nlev, offset_bytes, record_bytes);
+  return exp_layout_out(m->ctx[0], who, sched, nplanes, field, op, nlev, offset_bytes, record_bytes);
   });
 }
 
@@ -3683,7 +3871,8 @@ static int multi_exp_fetch(mckpp_hip_multi *m, const char *who, int sched, int64
   std::vector<win_sched_t::exp_plane> gp;   // the layout over all points
   size_t grb = 0;
   int maxlev = 0;
-  if (exp_layout(m->ctx[0], w0, m->npts, dtype, gp, grb, maxlev)) return -1;
+  const int64_t npoints = w0.npoints;   // (the same list on every shard)
+  if (exp_layout(m->ctx[0], w0, npoints, dtype, gp, grb, maxlev)) return -1;
   if (!plane && out_bytes < (int64_t)grb)
     return fail("%s: out_bytes %lld, but a record of schedule %d takes %zu bytes", who, (long long)out_bytes, sched, grb);
   std::vector<size_t> at((size_t)ndev, 0), nb((size_t)ndev, 0);
@@ -3705,13 +3894,16 @@ static int multi_exp_fetch(mckpp_hip_multi *m, const char *who, int sched, int64
   std::vector<int64_t> ncol((size_t)ndev);
   std::vector<const int32_t *> points((size_t)ndev);
   std::vector<const void *> planes((size_t)ndev);
-  for (int d = 0; d < ndev; ++d) { ncol[(size_t)d] = m->ctx[d]->ncol; points[(size_t)d] = m->ctx[d]->ipt.data(); }
+  for (int d = 0; d < ndev; ++d) {   // a shard's rows and where they go on the point axis
+    const auto &w = m->ctx[d]->wsched[sched];
+    ncol[(size_t)d] = w.nrow; points[(size_t)d] = win_host_map(m->ctx[d], w).data();
+  }
   std::vector<unsigned char> covered;
-  if (export_covered(m->npts, ndev, ncol.data(), points.data(), covered)) return fail("%s: a shard's point outside the grid", who);
+  if (export_covered(npoints, ndev, ncol.data(), points.data(), covered)) return fail("%s: a shard's point outside the grid", who);
   for (size_t q = plane ? k : 0; q < (plane ? k + 1 : gp.size()); ++q) {
     for (int d = 0; d < ndev; ++d)
       planes[(size_t)d] = m->h_exp + at[(size_t)d] + (plane ? 0 : (size_t)m->ctx[d]->wsched[sched].ex.planes[q].offset);
-    export_merge(m->npts, gp[q].nlev, dtype, w0.ex.land, ndev, ncol.data(), points.data(), planes.data(),
+    export_merge(npoints, gp[q].nlev, dtype, w0.ex.land, ndev, ncol.data(), points.data(), planes.data(),
                  static_cast<char *>(out) + (plane ? 0 : (size_t)gp[q].offset), covered.data());
   }
   return 0;

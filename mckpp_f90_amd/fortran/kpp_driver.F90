@@ -22,6 +22,7 @@ program kpp_driver
                                mckpp_hip_all_set_flux_series, mckpp_hip_all_run_forced, mckpp_hip_all_window_select, &
                                mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch, &
                                mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, &
+                               mckpp_hip_all_window_schedule_zoom, mckpp_hip_all_window_zoom, &
                                mckpp_hip_all_window_record_release, mckpp_hip_all_window_export, &
                                mckpp_hip_all_window_export_fetch, mckpp_hip_all_restart_schedule, &
                                mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
@@ -41,6 +42,9 @@ program kpp_driver
   integer :: kmixn, snap_first, snap_last, ncut, nrec, r, i
   real(c_double), allocatable :: exp_h(:,:), exp_t(:,:,:)   ! flag 4096: the records fetched through the export
   character(len=16) :: snap_name
+  integer(c_int32_t), allocatable :: zoom_pts(:)   ! flag 32768: the schedule's points
+  integer(c_int64_t) :: zoom_npoints, zoom_bytes
+  integer :: zoom_lev0, zoom_nlev
   ! flag 2048: records of SST0 (npts, nrec) and ocnT_clim (npts, nzp1, nrec) and the epochs of ocnT_clim
   integer, parameter :: anc_cad_sst = 3, anc_cad_ocnt = 2
   real(c_double), allocatable :: anc_sst(:,:), anc_ocnt(:,:,:)
@@ -77,6 +81,8 @@ program kpp_driver
   !           taux = 0.01 (1 + 0.1 r); all of them resident (mckpp_hip_all_set_flux_series), the time loop ONE forced run
   !        16384 with 8192: the records through a flux ring of 2 slots instead: two records put, the forced run of their
   !           four steps, and so on - the next pair is put while that run is queued
+  !        32768 with 256: the schedule zoomed to every third point in descending order (the last point first) and to
+  !           levels 0..1; its records out(npoints) and out(npoints, 2) appended as flag 256's are
   flags = hdr(6)
   if (iand(flags, 64) /= 0) mckpp_hip_output_mask = MCKPP_F_SCALARS
   ! hdr(7) > 0: that many device shards; hdr(8) = 1 puts them all on HIP device 0 (one-GPU rehearsal of the
@@ -160,9 +166,18 @@ program kpp_driver
         call mckpp_hip_all_window_accumulate()
       end do
     else if (iand(flags, 256) /= 0) then   ! the same output, accumulated inside the one forced run
+      if (iand(flags, 32768) /= 0) then
+        zoom_pts = [(int(ipt, c_int32_t), ipt = ncol - 1, 0, -3)]
+        call mckpp_hip_all_window_schedule_zoom(0, 1, 2, nsteps / 2, [4_c_int32_t, 2_c_int32_t], [1_c_int32_t, 4_c_int32_t], &
+                                                points=zoom_pts, lev0=0, nlev=2)
+        call mckpp_hip_all_window_zoom(0, zoom_npoints, zoom_lev0, zoom_nlev, zoom_bytes)
+        write (*, '(a,i0,a,i0,a,i0,a,i0,a)') 'kpp_driver: schedule 0 zoomed to ', zoom_npoints, ' points, levels ', zoom_lev0, &
+              '..', zoom_lev0 + zoom_nlev - 1, ', ', zoom_bytes, ' bytes of records'
+      else
       call mckpp_hip_all_window_schedule(0, 1, 2, nsteps / 2, [4_c_int32_t, 2_c_int32_t], &   ! MCKPP_OUT_HMIX, MCKPP_OUT_T
                                          [1_c_int32_t, 4_c_int32_t])                          ! MCKPP_WIN_MEAN, MCKPP_WIN_MAX
-      if (iand(flags, 4096) /= 0 .and. nsteps >= 4) then
+      end if
+      if (iand(flags, 4096) /= 0 .and. nsteps >= 4 .and. iand(flags, 32768) == 0) then
         allocate (exp_h(ncol, nsteps / 2), exp_t(ncol, nzp1, nsteps / 2))
         call mckpp_hip_all_window_export(0, MCKPP_EXP_F64, -1._c_double)
         ncut = ior(nsteps / 2, 1)   ! odd: the window of steps ncut, ncut + 1 is cut by the two runs
@@ -258,7 +273,11 @@ program kpp_driver
     deallocate (vm_h, vm_difm)
   end if
   if (iand(flags, 256) /= 0) then
-    allocate (vm_h(ncol), vm_difm(ncol, nzp1))
+    if (allocated(zoom_pts)) then
+      allocate (vm_h(size(zoom_pts)), vm_difm(size(zoom_pts), 2))
+    else
+      allocate (vm_h(ncol), vm_difm(ncol, nzp1))
+    end if
     do nt = 0, hdr(3) / 2 - 1
       if (allocated(exp_h)) then
         write (u) exp_h(:, nt + 1), exp_t(:, :, nt + 1)

@@ -1,5 +1,5 @@
-!> iso_c_binding view of include/mckpp_hip.h and of its companion
-!! mckpp_hip_device.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!> iso_c_binding view of include/mckpp_hip.h and of its companions
+!! mckpp_hip_device.h and mckpp_hip_zoom.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -43,6 +43,14 @@ module mckpp_hip_binding
     real(c_double) :: land_value
     type(c_ptr) :: out
   end type mckpp_dev_plane_c
+
+  !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
+  !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
+  type, bind(C) :: mckpp_win_zoom_c
+    type(c_ptr) :: points
+    integer(c_int64_t) :: npoints
+    integer(c_int32_t) :: lev0, nlev
+  end type mckpp_win_zoom_c
 
   type, bind(C) :: mckpp_const_c
     integer(c_int32_t) :: nz, nztmax, nsflxs, njdt, itermax
@@ -417,6 +425,32 @@ module mckpp_hip_binding
       integer(c_int), value :: sched, nt_origin, period, nrec
       integer(c_int32_t), intent(in) :: fields(*), ops(*)
       integer(c_int32_t), value :: nfields
+      integer(c_int) :: rc
+    end function
+    ! ... over chosen points and levels (include/mckpp_hip_zoom.h); zoom c_null_ptr: the unzoomed schedule
+    function mckpp_hip_multi_window_schedule_zoom(handle, sched, nt_origin, period, nrec, fields, ops, nfields, zoom) &
+        bind(C, name="mckpp_hip_multi_window_schedule_zoom") result(rc)
+      import :: c_int, c_int32_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched, nt_origin, period, nrec
+      integer(c_int32_t), intent(in) :: fields(*), ops(*)
+      integer(c_int32_t), value :: nfields
+      type(c_ptr), value :: zoom   ! c_loc of a mckpp_win_zoom_c
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_window_zoom(handle, sched, npoints, lev0, nlev, ring_bytes) &
+        bind(C, name="mckpp_hip_multi_window_zoom") result(rc)
+      import :: c_int, c_int32_t, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: sched
+      integer(c_int64_t), intent(out) :: npoints, ring_bytes
+      integer(c_int32_t), intent(out) :: lev0, nlev
+      integer(c_int) :: rc
+    end function
+    function mckpp_host_zoom_box(nx, ny, ibegin, ni, jbegin, nj, points) bind(C, name="mckpp_host_zoom_box") result(rc)
+      import :: c_int, c_int32_t, c_int64_t
+      integer(c_int64_t), value :: nx, ny, ibegin, ni, jbegin, nj
+      integer(c_int32_t), intent(out) :: points(*)
       integer(c_int) :: rc
     end function
     function mckpp_hip_multi_window_record_fetch(handle, sched, rec, field, op, out) &

@@ -19,6 +19,7 @@ module mckpp_hip_session
   public :: mckpp_hip_all_window_reset, mckpp_hip_all_window_accumulate, mckpp_hip_all_window_fetch
   public :: mckpp_hip_all_window_schedule, mckpp_hip_all_window_record_fetch, mckpp_hip_all_window_record_release
   public :: mckpp_hip_all_window_export, mckpp_hip_all_window_export_fetch, mckpp_hip_all_window_export_fetch_record
+  public :: mckpp_hip_all_window_schedule_zoom, mckpp_hip_all_window_zoom
   public :: mckpp_hip_all_restart_schedule, mckpp_hip_all_restart_snapshots, mckpp_hip_all_restart_snapshot_save, &
             mckpp_hip_all_restart_snapshot_release
   public :: mckpp_hip_all_step_log
@@ -505,6 +506,44 @@ contains
                          int(period, c_int), int(nrec, c_int), fields, ops, int(size(fields), c_int32_t)), &
                          'mckpp_hip_multi_window_schedule')
   end subroutine mckpp_hip_all_window_schedule
+  !> mckpp_hip_all_window_schedule over chosen points and levels (an iodef.xml <file> with zoom_domain / zoom_axis):
+  !! `points` are distinct 0-based point numbers of the 3-D ordering in any order, land allowed (absent: every point);
+  !! levels lev0 .. lev0+nlev-1, 0-based, of each 3-D field's own axis (absent, or 0 and 0: the whole axis).  A record's
+  !! plane is then out(size(points)[, nlev]) in the order of the list, for the record fetches and the export alike.
+  subroutine mckpp_hip_all_window_schedule_zoom(sched, nt_origin, period, nrec, fields, ops, points, lev0, nlev)
+    integer, intent(in) :: sched, nt_origin, period, nrec
+    integer(c_int32_t), intent(in) :: fields(:), ops(:)
+    integer(c_int32_t), intent(in), target, optional :: points(:)
+    integer, intent(in), optional :: lev0, nlev
+    type(mckpp_win_zoom_c), target :: zoom
+    if (size(ops) /= size(fields)) then
+      write (0, '(a)') 'MCKPP-HIP ERROR in mckpp_hip_all_window_schedule_zoom: one operations mask per field'
+      error stop 1
+    end if
+    zoom = mckpp_win_zoom_c(c_null_ptr, 0_c_int64_t, 0_c_int32_t, 0_c_int32_t)
+    if (present(points)) then
+      zoom%npoints = size(points, kind=c_int64_t)
+      if (size(points) > 0) zoom%points = c_loc(points(1))
+      if (size(points) == 0) zoom%points = c_loc(zoom)   ! (an empty list is the library's to refuse: not "every point")
+    end if
+    if (present(lev0)) zoom%lev0 = int(lev0, c_int32_t)
+    if (present(nlev)) zoom%nlev = int(nlev, c_int32_t)
+    call mckpp_hip_push_state()
+    call mckpp_hip_check(mckpp_hip_multi_window_schedule_zoom(mckpp_hip_multi_handle, int(sched, c_int), &
+                         int(nt_origin, c_int), int(period, c_int), int(nrec, c_int), fields, ops, &
+                         int(size(fields), c_int32_t), c_loc(zoom)), 'mckpp_hip_multi_window_schedule_zoom')
+  end subroutine mckpp_hip_all_window_schedule_zoom
+  !> the zoom of schedule `sched`, zoomed or not: the points of its records' point axis, the level range of its 3-D
+  !! fields, and the device bytes of its record ring over all devices (without the export)
+  subroutine mckpp_hip_all_window_zoom(sched, npoints, lev0, nlev, ring_bytes)
+    integer, intent(in) :: sched
+    integer(c_int64_t), intent(out) :: npoints, ring_bytes
+    integer, intent(out) :: lev0, nlev
+    integer(c_int32_t) :: l0, nl
+    call mckpp_hip_check(mckpp_hip_multi_window_zoom(mckpp_hip_multi_handle, int(sched, c_int), npoints, l0, nl, ring_bytes), &
+                         'mckpp_hip_multi_window_zoom')
+    lev0 = l0; nlev = nl
+  end subroutine mckpp_hip_all_window_zoom
   !> record `rec` (0: the window from nt_origin) of schedule `sched`, op 0 mean / 1 min / 2 max / 3 last, into
   !! out(npts[,nzp1]); land points keep what out held
   subroutine mckpp_hip_all_window_record_fetch(sched, rec, field, op, out)
