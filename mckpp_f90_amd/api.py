@@ -19,7 +19,8 @@ A new entry point of include/mckpp_hip.h takes two lines here: its signature in 
 mckpp_hip_multi_ form with the same signature exists) and, for a handle function, one method on _Handle that calls
 self._call(name, ...) - MckppHip and MckppHipMulti then both have it.  The device-array interface of
 include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its methods are the mixin _DeviceArrays; so
-have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, and their methods are _WindowSchedules'.
+have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, and their methods are _WindowSchedules'.  The records of a schedule into device arrays
+(include/mckpp_hip_device_records.h) are the fourth table, _SIGNATURES_RECORDS, and one more method of _DeviceArrays.
 """
 import ctypes as C
 import sys
@@ -381,6 +382,19 @@ _SIGNATURES_ZOOM = {
 }
 
 
+class _DevRecordPlaneC(C.Structure):
+    """mckpp_dev_record_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("sched", "field", "op", "lev0", "nlev", "dtype", "fill_land")] + \
+               [("rec", C.c_int64), ("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_device_records.h, records of output schedules into device arrays, in the same
+# form; tests/test_device_records_cpu.py holds this table to that header.
+_SIGNATURES_RECORDS = {
+    "mckpp_hip_records_dev": _sig(_H, _i32, C.POINTER(_DevRecordPlaneC), C.c_void_p, twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -406,12 +420,18 @@ def _signatures_zoom():
     return _spelled(_SIGNATURES_ZOOM)
 
 
+def _signatures_records():
+    """... and of every function of mckpp_hip_device_records.h."""
+    return _spelled(_SIGNATURES_RECORDS)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
     # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
     # everything else works with it, and a call of that name fails there by name
-    for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom()}.items():
+    for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
+                                  **_signatures_records()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -921,6 +941,47 @@ class _DeviceArrays:
             arr[k] = _DevPlaneC(f, lev0, nlev, _DEV_TYPESTR[typestr], int(bool(fill_land)), float(land_value), ptr)
             self._hold_dev(out)
         self._call("fetch_dev", len(planes), arr, _dev_stream(stream))
+
+    def records_dev(self, planes, stream=None, land_value=1e20, fill_land=True):
+        """Completed records of output schedules - window_record_fetch's values - into device arrays, one launch for all
+        planes (include/mckpp_hip_device_records.h); `stream` waits for the delivery on the device.  A plane is
+        (sched, rec, field, op, out, lev0, nlev): op OP_MEAN / OP_MIN / OP_MAX / OP_LAST of `field` in record `rec` of
+        schedule `sched`, levels lev0 .. lev0 + nlev - 1 (0-based) of the levels the schedule keeps, into out, nlev *
+        npoints elements, points fastest - a tensor of shape (nlev, npoints), npoints the record's point axis - of
+        float64 or float32; (sched, rec, field, op, out) is the levels from 0 that out has room for.  fill_land: the
+        positions that are no row of the record get land_value, otherwise they keep what out held.  The delivery is on
+        the context's stream: window_record_release and the next launch may follow at once."""
+        arr = (_DevRecordPlaneC * max(1, len(planes)))()
+        if len(planes) > 64:
+            raise ValueError(f"records_dev: {len(planes)} planes, at most 64 in one call")
+        for k, p in enumerate(planes):
+            who = f"records_dev: planes[{k}]"
+            if len(p) not in (5, 7):
+                raise ValueError(f"{who} is (sched, rec, field, op, out) or (sched, rec, field, op, out, lev0, nlev)")
+            sched, rec, op, out = int(p[0]), int(p[1]), int(p[3]), p[4]
+            try:
+                f = _win_check_fetch(self._scheds(), sched, p[2], op)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            if rec < 0:
+                raise ValueError(f"{who}: record {rec}")
+            zoom = self._scheds()[sched].zoom
+            n, axis = zoom if zoom is not None else (self._npts, self._nzp1)
+            if f in _OUT_2D:
+                axis = 1
+            if len(p) == 7:
+                lev0, nlev = int(p[5]), int(p[6])
+            else:
+                shape = getattr(out, "shape", ())
+                lev0, nlev = 0, (int(np.prod(shape, dtype=np.int64)) // n if n and len(shape) else 0)
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > axis:
+                raise ValueError(f"{who}: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, of which output "
+                                 f"schedule {sched} keeps {axis}")
+            ptr, typestr = _dev_array(out, f"{who} out", nlev * n, tuple(_DEV_TYPESTR))
+            arr[k] = _DevRecordPlaneC(sched, f, op, lev0, nlev, _DEV_TYPESTR[typestr], int(bool(fill_land)), rec,
+                                      float(land_value), ptr)
+            self._hold_dev(out)
+        self._call("records_dev", len(planes), arr, _dev_stream(stream))
 
     def dev_fence(self, stream=None):
         """`stream` waits, on the device, for every read of caller arrays this handle has queued so far."""

@@ -244,6 +244,23 @@ struct mckpp_fetch_plane {
 // no resident column (nland 0: no plane fills them)
 hipError_t mckpp_launch_fetch_planes(const mckpp_fetch_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
                                      int64_t npts, const double *cs, const int *land, int64_t nland, hipStream_t stream);
+// One plane of mckpp_hip_records_dev (k_record_planes): a plane of a schedule's record with its own geometry.  src:
+// the rows [nrow][ld] of the operation's plane in the record's ring slot; elements off .. off + nlev - 1 of row r go
+// to position map[r] of out(npoints, nlev), doubles or (f32) floats; mean: divided by `period` first (k_window_mean's
+// division).  fill: the nnorow positions at norow - those of the point axis that are no row - get land_value at
+// every level of the plane.
+struct mckpp_rec_plane {
+  const double *src;
+  void *out;
+  const int *map;
+  const int *norow;
+  double period, land_value;
+  long long nrow, npoints, nnorow;
+  int ld, off, nlev, mean, f32, fill;
+};
+// all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane; xtiles: the most 64-entry tiles
+// of a plane, rows and - where it fills - non-row positions together
+hipError_t mckpp_launch_record_planes(const mckpp_rec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

@@ -345,7 +345,82 @@ __global__ __launch_bounds__(256) void k_fetch_planes(const mckpp_fetch_plane *_
   else fetch_plane<double>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
 }
 
+// ---------------------------------------------------------------------------
+// Delivery of completed records of output schedules into the caller's device arrays (mckpp_hip_records_dev): the
+// sibling of k_record_pack and k_fetch_planes.  One launch writes every plane of the call, and the planes may come
+// from any schedules and records, so - unlike either sibling - a plane carries its own geometry in the table: its
+// rows (ring slot and operation resolved by the host), their number, the map row -> position of its point axis, the
+// axis' length, and the list of positions that are no row.  The mean is k_window_mean's one division, formed here;
+// the narrowing, after it, is one round-to-nearest-even conversion.  The planes go on blockIdx.z; the grid's x extent
+// is the largest plane's, and a workgroup beyond a plane's own tiles leaves before it touches memory.  A plane's
+// first ceil(nrow / 64) workgroups in x take 64 rows each: a row per thread where the plane has one level, otherwise
+// the 64x64 tile through LDS, so that both sides move whole segments.  The workgroups after them take 64 entries each
+// of the non-row list and, where the plane fills, write its land value there.
+// ---------------------------------------------------------------------------
+template <class T>
+__device__ __forceinline__ void record_plane(const mckpp_rec_plane &e, double (*tile)[65])
+{
+  const int l0 = blockIdx.y * 64;
+  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  T *__restrict__ dst = static_cast<T *>(e.out);
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t rowtiles = (e.nrow + 63) / 64;
+  if ((int64_t)blockIdx.x >= rowtiles) {
+    if (!e.fill) return;
+    const int64_t i = ((int64_t)blockIdx.x - rowtiles) * 64 + tx;
+    if (i >= e.nnorow) return;
+    const int64_t pos = e.norow[i];
+    const T v = (T)e.land_value;
+    for (int l = ty; l < 64; l += 4)
+      if (l0 + l < e.nlev) dst[(int64_t)(l0 + l) * e.npoints + pos] = v;
+    return;
+  }
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  if (e.nlev == 1) {   // nothing to transpose: every fourth workgroup takes 256 rows and the others leave
+    if (blockIdx.x & 3) return;
+    const int64_t r = r0 + threadIdx.x;
+    if (r < e.nrow) {
+      double v = e.src[r * e.ld + e.off];
+      if (e.mean) v = v / e.period;
+      dst[e.map[r]] = (T)v;
+    }
+    return;
+  }
+  for (int rr = ty; rr < 64; rr += 4) {       // read: levels fastest
+    const int64_t r = r0 + rr;
+    const int lev = l0 + tx;
+    double v = 0.0;
+    if (r < e.nrow && lev < e.nlev) v = e.src[r * e.ld + e.off + lev];
+    if (e.mean) v = v / e.period;
+    tile[tx][rr] = v;
+  }
+  __syncthreads();
+  const int64_t r = r0 + tx;
+  if (r >= e.nrow) return;
+  const int64_t pos = e.map[r];
+  for (int l = ty; l < 64; l += 4) {          // write: points fastest
+    const int lev = l0 + l;
+    if (lev < e.nlev) dst[(int64_t)lev * e.npoints + pos] = (T)tile[l][tx];
+  }
+}
+
+__global__ __launch_bounds__(256) void k_record_planes(const mckpp_rec_plane *__restrict__ tab)
+{
+  __shared__ double tile[64][65];
+  const mckpp_rec_plane e = tab[blockIdx.z];
+  if (e.f32) record_plane<float>(e, tile);
+  else record_plane<double>(e, tile);
+}
+
 }  // namespace
+
+hipError_t mckpp_launch_record_planes(const mckpp_rec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0 || xtiles <= 0) return hipSuccess;
+  dim3 grid((unsigned)xtiles, (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_record_planes, grid, dim3(256), 0, stream, tab);
+  return hipGetLastError();
+}
 
 hipError_t mckpp_launch_fluxes_dev(const mckpp_kparams &p, int ntime, const mckpp_dev_fields &f, const int *ipt, int l_rest,
                                    double flsn, double el, hipStream_t stream)

@@ -1,4 +1,5 @@
-// mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companion mckpp_hip_device.h.
+// mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companions mckpp_hip_device.h,
+// mckpp_hip_zoom.h and mckpp_hip_device_records.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
@@ -14,6 +15,7 @@
 // through fail, has the barrier.  (The header declares them without noexcept, so their definitions cannot carry it.)
 #include "../../include/mckpp_hip_device.h"
 #include "../../include/mckpp_hip_zoom.h"
+#include "../../include/mckpp_hip_device_records.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -98,6 +100,14 @@ struct mckpp_ctx_resident {
     std::vector<int> nlev, lev_off;
     std::vector<int> rowpos;           // listed: row -> list position
     dev_buf<int> d_rowpos, d_colrow;   // listed: rowpos; resident column -> row, -1 outside the list (mckpp_win_t::row)
+    // listed: the list positions that are no row, for the planes of mckpp_hip_records_dev that fill them (an unlisted
+    // schedule's are the context's d_land).  norow is this context's own, set with the schedule; d_norow holds nnorow
+    // positions: norow itself (norow_kind 1), or - shard 0 of a multi handle - those no shard has a row for, the other
+    // shards filling none (2; win_norow_set)
+    std::vector<int> norow;
+    dev_buf<int> d_norow;
+    int64_t nnorow = 0;
+    int norow_kind = 1;
     int64_t first_nt = -1, next_nt = -1;   // the first step run under the schedule, the step the next launch must start at (-1: none yet)
     int64_t first_kept = 0;                // the records before it are released, or began before first_nt
     // its export (mckpp_hip_window_export; dtype MCKPP_EXP_OFF: none): nrec slots of record_bytes each, record w in slot
@@ -237,6 +247,9 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   hip_event ev_caller, ev_delivered, ev_read, ev_read_flux;
   dev_buf<mckpp_fetch_plane> d_fetch_tab;
   pinned_turns<mckpp_fetch_plane> h_fetch_tab;
+  // ... and that of mckpp_hip_records_dev, in the same way (its event behind the launch is ev_delivered too)
+  dev_buf<mckpp_rec_plane> d_rec_tab;
+  pinned_turns<mckpp_rec_plane> h_rec_tab;
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -2549,16 +2562,21 @@ std::vector<int> points_not(const std::vector<unsigned char> &covered)
   return out;
 }
 
+// ... of a context of its own, where none is built: everything its column map leaves out
+int land_own(mckpp_hip_ctx *h)
+{
+  if (h->land_kind != 0) return 0;
+  std::vector<unsigned char> covered((size_t)h->npts, 0);
+  for (int i : h->ipt) covered[(size_t)i] = 1;
+  return land_set(h, points_not(covered), 1);
+}
+
 int fetch_dev_queue(mckpp_hip_ctx *h, const std::vector<mckpp_fetch_plane> &tab, int maxlev, bool any_fill, hipEvent_t before,
                     void *consumer_stream)
 {
   if (tab.empty()) return 0;
   HIPCHK(hipSetDevice(h->device));
-  if (any_fill && h->land_kind == 0) {   // a context of its own: everything its column map leaves out
-    std::vector<unsigned char> covered((size_t)h->npts, 0);
-    for (int i : h->ipt) covered[(size_t)i] = 1;
-    if (land_set(h, points_not(covered), 1)) return -1;
-  }
+  if (any_fill && land_own(h)) return -1;
   if (!h->d_fetch_tab) HIPCHK(h->d_fetch_tab.alloc(MCKPP_FETCH_PLANES));
   mckpp_fetch_plane *q = nullptr;
   HIPCHK(h->h_fetch_tab.take(MCKPP_FETCH_PLANES, &q));
@@ -2739,7 +2757,7 @@ static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, 
 {
   if (sched < 0 || sched >= MCKPP_WIN_SCHEDULES) return fail("%s: schedule %d (0..%d)", who, sched, MCKPP_WIN_SCHEDULES - 1);
   if (nfields < 0 || (nfields > 0 && (!fields || !ops))) return fail("%s: bad argument (nfields=%d)", who, nfields);
-  std::vector<int> colrow, rowpos;   // of a point list
+  std::vector<int> colrow, rowpos, norow;   // of a point list
   if (nfields > 0) {   // everything is checked before the schedule in place is touched
     if (nt_origin < 1 || period < 1 || nrec < 1)
       return fail("%s: nt_origin=%d period=%d nrec=%d (each at least 1)", who, nt_origin, period, nrec);
@@ -2779,7 +2797,7 @@ static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, 
         colrow.assign((size_t)h->ncol, -1);
         for (int64_t i = 0; i < zoom->npoints; ++i) {
           const int c = colof[(size_t)zoom->points[i]];
-          if (c < 0) continue;
+          if (c < 0) { norow.push_back((int)i); continue; }
           colrow[(size_t)c] = (int)rowpos.size();
           rowpos.push_back((int)i);
         }
@@ -2807,7 +2825,14 @@ static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, 
       if (e == hipSuccess && w.nrow > 0) e = w.d_rowpos.alloc(rowpos.size());
       if (e == hipSuccess && w.nrow > 0) e = hipMemcpy(w.d_rowpos, rowpos.data(), rowpos.size() * sizeof(int), hipMemcpyHostToDevice);
     }
+    if (e == hipSuccess && !norow.empty()) {
+      bytes += norow.size() * sizeof(int);
+      e = w.d_norow.alloc(norow.size());
+      if (e == hipSuccess) e = hipMemcpy(w.d_norow, norow.data(), norow.size() * sizeof(int), hipMemcpyHostToDevice);
+    }
+    w.nnorow = (int64_t)norow.size();
     w.rowpos = std::move(rowpos);
+    w.norow = std::move(norow);
     for (int i = 0; i < nfields && e == hipSuccess; ++i) {
       out_desc d;
       out_field(h, fields[i], d);
@@ -2852,7 +2877,7 @@ int mckpp_hip_window_schedule_zoom(mckpp_hip_handle h, int sched, int nt_origin,
   });
 }
 
-// the device bytes of a schedule's record ring (without its export and without the zoom's two small tables)
+// the device bytes of a schedule's record ring (without its export and without the zoom's three small tables)
 static int64_t win_ring_bytes(const mckpp_hip_ctx::win_sched &w)
 {
   int64_t b = 0;
@@ -2989,6 +3014,119 @@ int mckpp_hip_window_records(mckpp_hip_handle h, int sched, int64_t *first_kept,
   if (first_kept) *first_kept = w.first_kept;
   if (last_complete) *last_complete = win_last_complete(w);
   return 0;
+  });
+}
+
+// ---------------------------------------------------------------------------
+// Records into the caller's device arrays (include/mckpp_hip_device_records.h): a check, which queues nothing, and a
+// part that queues in fetch_dev_queue's order; a multi handle checks all its shards before any of them queues.  The
+// mean is formed by the delivery's kernel (k_record_planes), not through d_stage: nothing here waits for the device.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// the planes of a delivery resolved into the kernel's table, but for their non-row lists; [plane] its schedule
+struct rec_planes {
+  std::vector<mckpp_rec_plane> tab;
+  std::vector<int> sched;
+  int maxlev = 0;
+};
+
+int records_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_dev_record_plane_c *planes, rec_planes &r,
+                      int *dev)
+{
+  if (nplanes < 0 || nplanes > MCKPP_DEV_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_DEV_PLANES_MAX);
+  HIPCHK(hipSetDevice(h->device));
+  r = rec_planes{};
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_dev_record_plane_c &q = planes[k];
+    char at[96], arg[32];
+    snprintf(at, sizeof at, "%s: planes[%d]", who, k);
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    size_t i = 0;
+    if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
+    const auto &w = h->wsched[q.sched];
+    if (q.lev0 < 0 || q.nlev < 1 || (int64_t)q.lev0 + q.nlev > w.nlev[i])
+      return fail("%s: lev0=%d nlev=%d is no range of the levels schedule %d keeps of field %d, which are %d (lev0 >= 0, "
+                  "nlev >= 1)", at, q.lev0, q.nlev, q.sched, q.field, w.nlev[i]);
+    if (q.dtype != MCKPP_EXP_F64 && q.dtype != MCKPP_EXP_F32)
+      return fail("%s: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", at, q.dtype);
+    const size_t elem = q.dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
+    if (dev_ptr_check(h, who, arg, q.out, (size_t)w.npoints * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
+    const size_t nops = (size_t)__builtin_popcount(w.ops[i]), j = (size_t)__builtin_popcount(w.ops[i] & ((1u << q.op) - 1u));
+    const size_t n = (size_t)w.nrow * (size_t)w.ld_out[i];
+    mckpp_rec_plane e{};
+    e.src = w.nrow > 0 ? w.acc[i] + ((size_t)(q.rec % w.nrec) * nops + j) * n : nullptr;
+    e.out = q.out;
+    e.map = win_map(h, w);
+    e.period = (double)w.period; e.land_value = q.land_value;
+    e.nrow = w.nrow; e.npoints = w.npoints;
+    e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
+    e.mean = q.op == 0; e.f32 = q.dtype == MCKPP_EXP_F32; e.fill = q.fill_land != 0;
+    r.tab.push_back(e);
+    r.sched.push_back(q.sched);
+    r.maxlev = std::max(r.maxlev, (int)q.nlev);
+  }
+  return 0;
+}
+
+// the non-row list a listed schedule's planes fill (win_sched::d_norow): as land_set
+int win_norow_set(mckpp_hip_ctx *h, mckpp_hip_ctx::win_sched &w, const std::vector<int> &list, int kind)
+{
+  HIPCHK(hipStreamSynchronize(h->stream));   // (a change of who addresses the shard: a delivery in flight may read the old list)
+  HIPCHK(w.d_norow.reserve(std::max<size_t>(list.size(), 1)));
+  if (!list.empty()) HIPCHK(hipMemcpy(w.d_norow, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
+  w.nnorow = (int64_t)list.size();
+  w.norow_kind = kind;
+  return 0;
+}
+
+// fill: this context writes the land values the planes ask for (a shard other than 0 of a multi handle writes none)
+int records_dev_queue(mckpp_hip_ctx *h, rec_planes &r, bool fill, hipEvent_t before, void *consumer_stream)
+{
+  if (r.tab.empty()) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  int64_t xtiles = 0;
+  for (size_t k = 0; k < r.tab.size(); ++k) {
+    mckpp_rec_plane &e = r.tab[k];
+    const auto &w = h->wsched[r.sched[k]];
+    e.fill = e.fill && fill;
+    if (e.fill && w.listed) { e.norow = w.d_norow; e.nnorow = w.nnorow; }
+    else if (e.fill) {
+      if (land_own(h)) return -1;
+      e.norow = h->d_land; e.nnorow = h->nland;
+    }
+    xtiles = std::max<int64_t>(xtiles, (e.nrow + 63) / 64 + (e.nnorow + 63) / 64);
+  }
+  if (!h->d_rec_tab) HIPCHK(h->d_rec_tab.alloc(MCKPP_DEV_PLANES_MAX));
+  mckpp_rec_plane *q = nullptr;
+  HIPCHK(h->h_rec_tab.take(MCKPP_DEV_PLANES_MAX, &q));
+  std::copy(r.tab.begin(), r.tab.end(), q);
+  HIPCHK(hipMemcpyAsync(h->d_rec_tab, q, r.tab.size() * sizeof(mckpp_rec_plane), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h->h_rec_tab.queued(h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
+  HIPCHK(mckpp_launch_record_planes(h->d_rec_tab, (int)r.tab.size(), r.maxlev, xtiles, h->stream));
+  if (!h->ev_delivered) HIPCHK(h->ev_delivered.create());
+  HIPCHK(hipEventRecord(h->ev_delivered, h->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_record_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  rec_planes r;
+  if (records_dev_check(h, who, nplanes, planes, r, nullptr)) return -1;
+  if (r.tab.empty()) return 0;
+  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complements again)
+  for (int s : r.sched) {
+    auto &w = h->wsched[s];
+    if (w.norow_kind == 2 && win_norow_set(h, w, w.norow, 1)) return -1;
+  }
+  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
+  return records_dev_queue(h, r, true, h->ev_caller, consumer_stream);
   });
 }
 
@@ -4087,6 +4225,20 @@ int mckpp_hip_multi_flux_ring_put_dev(mckpp_hip_multi_handle m, int rec, const d
   });
 }
 
+// shard 0's land list as the points that no shard holds (land_kind 2), where it is not that already
+static int multi_land(mckpp_hip_multi *m, const char *who)
+{
+  if (m->ctx[0]->land_kind == 2) return 0;
+  std::vector<int64_t> ncol;
+  std::vector<const int32_t *> points;
+  for (auto *x : m->ctx) { ncol.push_back(x->ncol); points.push_back(x->ipt.data()); }
+  std::vector<unsigned char> covered;
+  if (export_covered(m->npts, (int)m->ctx.size(), ncol.data(), points.data(), covered))
+    return fail("%s: a column map names a point outside the grid", who);
+  HIPCHK(hipSetDevice(m->ctx[0]->device));
+  return land_set(m->ctx[0], points_not(covered), 2);
+}
+
 int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
 {
   return entry(__func__, m, [&, who = __func__]() -> int {
@@ -4100,19 +4252,42 @@ int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const m
   if (any_fill) {   // shard 0 fills the points that no shard holds, the others fill none: every point is written once
     for (int d = 1; d < ndev; ++d)
       for (auto &e : tabs[(size_t)d]) e.fill_land = 0;
-    if (m->ctx[0]->land_kind != 2) {
-      std::vector<int64_t> ncol;
-      std::vector<const int32_t *> points;
-      for (auto *x : m->ctx) { ncol.push_back(x->ncol); points.push_back(x->ipt.data()); }
-      std::vector<unsigned char> covered;
-      if (export_covered(m->npts, ndev, ncol.data(), points.data(), covered)) return fail("%s: a column map names a point outside the grid", who);
-      HIPCHK(hipSetDevice(m->ctx[0]->device));
-      if (land_set(m->ctx[0], points_not(covered), 2)) return -1;
-    }
+    if (multi_land(m, who)) return -1;
   }
   if (multi_caller_event(m, dev, consumer_stream)) return -1;
   for (int d = 0; d < ndev; ++d)
     if (fetch_dev_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
+  return 0;
+  });
+}
+
+// mckpp_hip_records_dev over all shards: a shard writes its own rows of every plane, shard 0 the land values - at the
+// grid points, or the positions of a schedule's point list, that no shard has a row for
+int mckpp_hip_multi_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_record_plane_c *planes,
+                                void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<rec_planes> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (records_dev_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  const rec_planes &r0 = rs[0];
+  for (size_t k = 0; k < r0.tab.size(); ++k) {
+    if (!r0.tab[k].fill) continue;
+    auto &w = m->ctx[0]->wsched[r0.sched[k]];
+    if (!w.listed) { if (multi_land(m, who)) return -1; continue; }
+    if (w.norow_kind == 2) continue;
+    std::vector<unsigned char> held((size_t)w.npoints, 0);
+    for (auto *x : m->ctx)
+      for (int p : x->wsched[r0.sched[k]].rowpos) held[(size_t)p] = 1;
+    HIPCHK(hipSetDevice(m->ctx[0]->device));
+    if (win_norow_set(m->ctx[0], w, points_not(held), 2)) return -1;
+  }
+  if (multi_caller_event(m, dev, consumer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (records_dev_queue(m->ctx[d], rs[(size_t)d], d == 0, m->ev_caller, consumer_stream)) return -1;
   return 0;
   });
 }

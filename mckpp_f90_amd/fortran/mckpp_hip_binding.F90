@@ -1,5 +1,5 @@
 !> iso_c_binding view of include/mckpp_hip.h and of its companions
-!! mckpp_hip_device.h and mckpp_hip_zoom.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!! mckpp_hip_device.h, mckpp_hip_zoom.h and mckpp_hip_device_records.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -43,6 +43,16 @@ module mckpp_hip_binding
     real(c_double) :: land_value
     type(c_ptr) :: out
   end type mckpp_dev_plane_c
+
+  !> one plane of mckpp_hip_records_dev (include/mckpp_hip_device_records.h): operation `op` (0 mean, 1 min, 2 max, 3 last)
+  !! of output field `field` in record `rec` of schedule `sched`, levels lev0 .. lev0+nlev-1 (0-based) of those the schedule
+  !! keeps, into the device array at `out`; fill_land /= 0: the positions that are no row of the record get land_value
+  type, bind(C) :: mckpp_dev_record_plane_c
+    integer(c_int32_t) :: sched, field, op, lev0, nlev, dtype, fill_land
+    integer(c_int64_t) :: rec
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_dev_record_plane_c
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -758,6 +768,23 @@ module mckpp_hip_binding
     function mckpp_hip_multi_dev_fence(m, stream) bind(C, name="mckpp_hip_multi_dev_fence") result(rc)
       import :: c_int, c_ptr
       type(c_ptr), value :: m, stream
+      integer(c_int) :: rc
+    end function
+    ! records of output schedules into device arrays (include/mckpp_hip_device_records.h): one launch for all planes on
+    ! the context's stream, so mckpp_hip_window_record_release may follow at once
+    function mckpp_hip_records_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_records_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_dev_record_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_dev_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_records_dev(m, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_multi_records_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_dev_record_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_dev_record_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
