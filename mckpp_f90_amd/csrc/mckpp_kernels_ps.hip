@@ -2801,22 +2801,13 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
         cs[CS_UREF] = U; cs[CS_VREF] = V; cs[CS_TREF] = T;
         cs[CS_SSURF] = p.L_SSref ? cs[CS_SSREF] : S + sc[C_SREF];
       }
-      if constexpr (EXT) {
-        if (fstep && p.L_DAMP_CURR && act) {   // ocnstep_mod.F90:317-340
-          const double rr = (double)p.dt_uvdamp * (86400. / p.dto);
-          double a = 0.99 * __builtin_fabs(U), b = (U * U) / rr;
-          if (b < a) atomicAdd(&si[I_NU], 1);
-          row(Q_YU)[k] = U - dsign(dmin2(a, b), U);
-          a = 0.99 * __builtin_fabs(V); b = (V * V) / rr;
-          if (b < a) atomicAdd(&si[I_NV], 1);
-          row(Q_YV)[k] = V - dsign(dmin2(a, b), V);
-        }
-      }
     END_ITEMS
-    __syncthreads();   // the k+1 neighbours above are read from the rows that check_profile rewrites below
+    __syncthreads();   // the k+1 neighbours above are read from the rows that current damping and check_profile rewrite below
     STAMP(28);
-    // ---- STEP: new time level, check_profile (overrides.F90:42-125); the optional parts count over all
-    // levels of the column: LDS counters between workgroup barriers (EXT build).
+    // ---- STEP: (optional physics) current damping, new time level, check_profile (overrides.F90:42-125); the
+    // optional parts count over all levels of the column: LDS counters between workgroup barriers (EXT build).
+    // The damping rewrites an item's U and V in the solution rows, which the fluxes above read at k+1 - the
+    // neighbour's item, in another wave at a wave boundary and in another trip of the item loop: so behind the barrier.
     FOR_ITEMS
       if (!act) continue;   // the two equation-of-state items exist for L1 only
       if (!(si[I_FIN] == F_FINAL && p.mode == MCKPP_MODE_STEP)) continue;
@@ -2824,6 +2815,19 @@ __global__ __launch_bounds__(1024, MCKPP_PS_MINW) void k_column_ps(const mckpp_k
       const int newi = 1 - si[I_NEW];   // old = new; new = 1 - old
       double U = 0, V = 0, T = 0, S = 0;
       if (act) { U = row(Q_YU)[k]; V = row(Q_YV)[k]; T = row(Q_YT)[k]; S = row(Q_YS)[k]; }
+      if constexpr (EXT) {
+        if (p.L_DAMP_CURR && act) {   // ocnstep_mod.F90:317-340
+          const double rr = (double)p.dt_uvdamp * (86400. / p.dto);
+          double a = 0.99 * __builtin_fabs(U), b = (U * U) / rr;
+          if (b < a) atomicAdd(&si[I_NU], 1);
+          U = U - dsign(dmin2(a, b), U);
+          row(Q_YU)[k] = U;
+          a = 0.99 * __builtin_fabs(V); b = (V * V) / rr;
+          if (b < a) atomicAdd(&si[I_NV], 1);
+          V = V - dsign(dmin2(a, b), V);
+          row(Q_YV)[k] = V;
+        }
+      }
       if (act) { p.Us[newi][o] = U; p.Vs[newi][o] = V; p.Ts[newi][o] = T; p.Ss[newi][o] = S; }
       if (si[I_COMP] && act) {   // overrides.F90:57-78
         if (p.clim_present) {   // (the step's own climatology)
