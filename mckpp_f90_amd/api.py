@@ -20,7 +20,8 @@ mckpp_hip_multi_ form with the same signature exists) and, for a handle function
 self._call(name, ...) - MckppHip and MckppHipMulti then both have it.  The device-array interface of
 include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its methods are the mixin _DeviceArrays; so
 have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, and their methods are _WindowSchedules'.  The records of a schedule into device arrays
-(include/mckpp_hip_device_records.h) are the fourth table, _SIGNATURES_RECORDS, and one more method of _DeviceArrays.
+(include/mckpp_hip_device_records.h) are the fourth table, _SIGNATURES_RECORDS, and one more method of _DeviceArrays;
+the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _SIGNATURES_PUT, and two more methods there.
 """
 import ctypes as C
 import sys
@@ -395,6 +396,20 @@ _SIGNATURES_RECORDS = {
 }
 
 
+class _PutPlaneC(C.Structure):
+    """mckpp_put_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "lev0", "nlev", "dtype", "op", "flags")] + \
+               [("skip_value", C.c_double), ("in", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_put.h, the prognostic state set or incremented in place, in the same form;
+# tests/test_put_cpu.py holds this table to that header.
+_SIGNATURES_PUT = {
+    "mckpp_hip_put_dev": _sig(_H, _i32, C.POINTER(_PutPlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_put_host": _sig(_H, _i32, C.POINTER(_PutPlaneC), twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -425,13 +440,18 @@ def _signatures_records():
     return _spelled(_SIGNATURES_RECORDS)
 
 
+def _signatures_put():
+    """... and of every function of mckpp_hip_put.h."""
+    return _spelled(_SIGNATURES_PUT)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
     # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
     # everything else works with it, and a call of that name fails there by name
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
-                                  **_signatures_records()}.items():
+                                  **_signatures_records(), **_signatures_put()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -874,6 +894,30 @@ def _dev_stream(stream):
     return C.c_void_p(int(stream.cuda_stream) or None)
 
 
+# mckpp_hip_put_dev / _put_host (MCKPP_PUT_* of mckpp_hip_put.h): the operations, the flag bits, the state fields
+PUT_SET, PUT_ADD = 0, 1
+PUT_SKIP, PUT_TIME_LEVELS = 1, 2
+_PUT_OPS = {"set": PUT_SET, "add": PUT_ADD, PUT_SET: PUT_SET, PUT_ADD: PUT_ADD}
+_PUT_FIELDS = {OUT["u"]: "u", OUT["v"]: "v", OUT["T"]: "T", OUT["S_anom"]: "S", OUT["S"]: "S"}   # field -> what it writes
+
+
+def _host_plane(a, what, count):
+    """(address, typestr) of the numpy array `a` handed to put_host: float64 or float32, C-contiguous, `count` elements.
+    ValueError otherwise; an array in device memory is refused here."""
+    if not isinstance(a, np.ndarray):
+        kind = "an array in device memory" if hasattr(a, "__cuda_array_interface__") else "no numpy array"
+        raise ValueError(f"{what}: {kind} ({type(a).__module__}.{type(a).__name__}); put_host takes numpy arrays (put_dev "
+                         "takes arrays in device memory)")
+    typestr = a.dtype.str
+    if typestr not in _DEV_TYPESTR:
+        raise ValueError(f"{what}: element type {typestr}, the call takes {' or '.join(_DEV_TYPESTR)}")
+    if not a.flags["C_CONTIGUOUS"]:
+        raise ValueError(f"{what}: not C-contiguous (shape {a.shape}, strides {a.strides})")
+    if a.size != count:
+        raise ValueError(f"{what}: shape {a.shape}, the call takes {count} elements")
+    return a.ctypes.data, typestr
+
+
 class _DeviceArrays:
     """The device-array interface (include/mckpp_hip_device.h): forcing from arrays in device memory, output fields into
     them, ordered by events on the caller's stream and never by a host wait.  Arrays handed to fluxes_dev or
@@ -982,6 +1026,72 @@ class _DeviceArrays:
                                       float(land_value), ptr)
             self._hold_dev(out)
         self._call("records_dev", len(planes), arr, _dev_stream(stream))
+
+    def _put_table(self, who, planes, op, time_levels, skip, array):
+        """the planes of put_dev / put_host as the table the library takes, after every check that needs no library;
+        array(a, what, count) -> (address, typestr) is the form's own check of a plane's array"""
+        if op not in _PUT_OPS or isinstance(op, bool):
+            raise ValueError(f"{who}: op {op!r} (\"set\" or \"add\")")
+        flags, skip_value = (PUT_TIME_LEVELS if time_levels else 0), 0.0
+        if skip is not None:
+            flags, skip_value = flags | PUT_SKIP, float(skip)
+            if skip_value != skip_value:
+                raise ValueError(f"{who}: skip is NaN, which no element compares equal to")
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"{who}: {len(planes)} planes, at most 64 in one call")
+        n, arr, seen = self._npts, (_PutPlaneC * max(1, len(planes)))(), []
+        for k, p in enumerate(planes):
+            if not 2 <= len(p) <= 4:
+                raise ValueError(f"{who}: planes[{k}] is (field, array), (field, array, lev0) or (field, array, lev0, nlev)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: planes[{k}]: {e}") from None
+            if f not in _PUT_FIELDS:
+                raise ValueError(f"{who}: planes[{k}]: field {OUT_FIELDS[f]} is an output of the step, not state (u, v, T, "
+                                 "S_anom, S)")
+            a, lev0 = p[1], (int(p[2]) if len(p) > 2 else 0)
+            if len(p) > 3:
+                nlev = int(p[3])
+            else:
+                shape = getattr(a, "shape", ())
+                nlev = int(np.prod(shape, dtype=np.int64)) // n if n and len(shape) else 0
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > self._nzp1:
+                raise ValueError(f"{who}: planes[{k}]: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, whose axis "
+                                 f"has {self._nzp1}")
+            for j, (g, a0, a1) in enumerate(seen):
+                if g == _PUT_FIELDS[f] and lev0 < a1 and a0 < lev0 + nlev:
+                    raise ValueError(f"{who}: planes[{k}] and planes[{j}] write {g} at overlapping levels {lev0} .. "
+                                     f"{lev0 + nlev - 1} and {a0} .. {a1 - 1}: the planes of a call have no order")
+            seen.append((_PUT_FIELDS[f], lev0, lev0 + nlev))
+            ptr, typestr = array(a, f"{who}: planes[{k}] array", nlev * n)
+            arr[k] = _PutPlaneC(f, lev0, nlev, _DEV_TYPESTR[typestr], _PUT_OPS[op], flags, skip_value, ptr)
+        return len(planes), arr
+
+    def put_dev(self, planes, op="set", time_levels=False, skip=None, stream=None, fence=False):
+        """U, V, T, S of the resident state set (op "set") or incremented ("add") in place from device arrays produced on
+        `stream`, one launch for all planes (include/mckpp_hip_put.h): fetch_dev's inverse.  A plane is (field, array[,
+        lev0[, nlev]]): the array's nlev * npts elements, points fastest - a tensor of shape (nlev, npts) - of float64 or
+        float32, for levels lev0 .. lev0 + nlev - 1 (0-based) of field u, v, T, S_anom or S; lev0 defaults to 0, nlev to
+        what the array holds.  time_levels: the two saved time levels of the field take the same operation.  skip: an
+        element equal to this value leaves its state element untouched.  No two planes of a call may write the same
+        levels of a field.  Nothing is cancelled: schedules, exports, rings and series stay as they are.  The arrays
+        must stay unchanged until a dev_fence on the stream that next writes them (fence=True queues it on `stream`)."""
+        planes = list(planes)
+        n, arr = self._put_table("put_dev", planes, op, time_levels, skip,
+                                 lambda a, what, count: _dev_array(a, what, count, tuple(_DEV_TYPESTR)))
+        s = _dev_stream(stream)
+        for p in planes:
+            self._hold_dev(p[1])
+        self._call("put_dev", n, arr, s)
+        if fence:
+            self._call("dev_fence", s)
+
+    def put_host(self, planes, op="set", time_levels=False, skip=None):
+        """put_dev from numpy arrays of float64 or float32, shape (nlev, npts); returns when the state is written."""
+        n, arr = self._put_table("put_host", planes, op, time_levels, skip, _host_plane)
+        self._call("put_host", n, arr)
 
     def dev_fence(self, stream=None):
         """`stream` waits, on the device, for every read of caller arrays this handle has queued so far."""

@@ -261,6 +261,21 @@ struct mckpp_rec_plane {
 // all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane; xtiles: the most 64-entry tiles
 // of a plane, rows and - where it fills - non-row positions together
 hipError_t mckpp_launch_record_planes(const mckpp_rec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream);
+// One plane of mckpp_hip_put_dev / _put_host (k_put_planes), mckpp_fetch_plane turned round: in(npts, nlev), doubles or
+// (f32) floats, is set into (add: added to) elements off .. off + nlev - 1 of the rows [ncol][ld] at row; sub_sref: a
+// set writes the value minus the column's Sref; skip: a value == skip_value leaves its element alone; lv0 / lv1: the
+// field's two saved time levels, written too (null: they stay).  ref_slot >= 0: the plane holds level 0, and the thread
+// that writes a column's element there restates cs[ref_slot] from it - plus the column's Sref where ref_sref (Ssurf).
+struct mckpp_put_plane {
+  const void *in;
+  double *row, *lv0, *lv1;
+  double skip_value;
+  int ld, off, nlev, f32, add, skip, sub_sref, ref_slot, ref_sref;
+};
+#define MCKPP_PUT_PLANES 64   // most planes of one call (the device table's size)
+// all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane
+hipError_t mckpp_launch_put_planes(const mckpp_put_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
+                                   int64_t npts, double *cs, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

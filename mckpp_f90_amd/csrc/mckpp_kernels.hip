@@ -412,7 +412,87 @@ __global__ __launch_bounds__(256) void k_record_planes(const mckpp_rec_plane *__
   else record_plane<double>(e, tile);
 }
 
+// ---------------------------------------------------------------------------
+// The prognostic state set or incremented from the caller's arrays (mckpp_hip_put_dev, mckpp_hip_put_host):
+// k_fetch_planes' mirror image.  One launch applies every plane of the call - in(npts, nlev), points fastest, doubles or
+// floats widened exactly, through the column map - to elements off .. off + nlev - 1 of a profile's rows and, where
+// the plane asks for it, of the field's two saved time levels.  The planes go on blockIdx.z; element type, operation and
+// flags are a plane's own.  A plane of one level takes a column per thread; otherwise the 64x64 tile through LDS, in the
+// opposite direction to the fetch: the points-fastest read of `in` into the tile, then the levels-fastest
+// read-modify-write of the rows, so that both sides move whole segments.  The value itself travels through the tile,
+// and the skip decision is its comparison on the row side: no sentinel, no second tile.  No atomics: the host refused
+// overlapping planes and a column is in the map once, so every state element has one writer.  Each operation below is
+// one fp64 operation, in the order include/mckpp_hip_put.h states (built with -ffp-contract=off).
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ void put_element(const mckpp_put_plane &e, double *__restrict__ cs, int64_t c, int lev, double v)
+{
+  if (e.skip && v == e.skip_value) return;
+  const int64_t i = c * e.ld + e.off + lev;
+  double x;
+  if (e.add) x = e.row[i] + v;
+  else x = e.sub_sref ? v - cs[c * MCKPP_CS + CS_SREF] : v;
+  e.row[i] = x;
+  if (e.lv0) {
+    if (e.add) { e.lv0[i] = e.lv0[i] + v; e.lv1[i] = e.lv1[i] + v; }
+    else { e.lv0[i] = x; e.lv1[i] = x; }
+  }
+  // ocnstep_mod.F90:307-314 for this field: the column's level-1 value is now x
+  if (e.ref_slot >= 0 && lev == 0) cs[c * MCKPP_CS + e.ref_slot] = e.ref_sref ? x + cs[c * MCKPP_CS + CS_SREF] : x;
+}
+
+template <class T>
+__device__ __forceinline__ void put_plane(const mckpp_put_plane &e, double (*tile)[65], const int *__restrict__ ipt,
+                                          int64_t ncol, int64_t npts, double *__restrict__ cs)
+{
+  const int l0 = blockIdx.y * 64;
+  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  const T *__restrict__ src = static_cast<const T *>(e.in);
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t c0 = (int64_t)blockIdx.x * 64;
+  if (e.nlev == 1) {   // nothing to transpose: every fourth workgroup takes 256 columns and the others leave
+    if (blockIdx.x & 3) return;
+    const int64_t c = c0 + threadIdx.x;
+    if (c < ncol) put_element(e, cs, c, 0, (double)src[ipt[c]]);
+    return;
+  }
+  {
+    const int64_t c = c0 + tx;
+    const int64_t pt = c < ncol ? (int64_t)ipt[c] : 0;
+    for (int l = ty; l < 64; l += 4) {          // read: points fastest
+      const int lev = l0 + l;
+      double v = 0.0;
+      if (c < ncol && lev < e.nlev) v = (double)src[(int64_t)lev * npts + pt];
+      tile[l][tx] = v;
+    }
+  }
+  __syncthreads();
+  const int lev = l0 + tx;
+  if (lev >= e.nlev) return;
+  for (int cc = ty; cc < 64; cc += 4) {         // read-modify-write: levels fastest
+    const int64_t c = c0 + cc;
+    if (c < ncol) put_element(e, cs, c, lev, tile[tx][cc]);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_put_planes(const mckpp_put_plane *__restrict__ tab, const int *__restrict__ ipt,
+                                                    int64_t ncol, int64_t npts, double *__restrict__ cs)
+{
+  __shared__ double tile[64][65];
+  const mckpp_put_plane e = tab[blockIdx.z];
+  if (e.f32) put_plane<float>(e, tile, ipt, ncol, npts, cs);
+  else put_plane<double>(e, tile, ipt, ncol, npts, cs);
+}
+
 }  // namespace
+
+hipError_t mckpp_launch_put_planes(const mckpp_put_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
+                                   int64_t npts, double *cs, hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0 || ncol <= 0) return hipSuccess;
+  dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_put_planes, grid, dim3(256), 0, stream, tab, ipt, ncol, npts, cs);
+  return hipGetLastError();
+}
 
 hipError_t mckpp_launch_record_planes(const mckpp_rec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream)
 {

@@ -1,5 +1,5 @@
 // mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companions mckpp_hip_device.h,
-// mckpp_hip_zoom.h and mckpp_hip_device_records.h.
+// mckpp_hip_zoom.h, mckpp_hip_device_records.h and mckpp_hip_put.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
@@ -16,6 +16,7 @@
 #include "../../include/mckpp_hip_device.h"
 #include "../../include/mckpp_hip_zoom.h"
 #include "../../include/mckpp_hip_device_records.h"
+#include "../../include/mckpp_hip_put.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -182,6 +183,7 @@ struct mckpp_ctx_resident {
   int64_t nland = 0;
   int land_kind = 0;
   dev_buf<double> d_stage;    // grow-only (ensure_stage)
+  dev_buf<char> d_put_stage;  // the planes of mckpp_hip_put_host, grow-only: the call ends with a wait, so nothing reads it between calls
   dev_buf<double> d_xfer[2];  // the staging buffers of the row transfers, grow-only (ensure_xfer)
   // pinned host images of the column records and of the forcing staging (grow-only: ensure_host_f)
   pinned_buf<double> h_cs, h_f;
@@ -250,6 +252,9 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   // ... and that of mckpp_hip_records_dev, in the same way (its event behind the launch is ev_delivered too)
   dev_buf<mckpp_rec_plane> d_rec_tab;
   pinned_turns<mckpp_rec_plane> h_rec_tab;
+  // ... and that of mckpp_hip_put_dev / _put_host (include/mckpp_hip_put.h; the event behind its launch is ev_read)
+  dev_buf<mckpp_put_plane> d_put_tab;
+  pinned_turns<mckpp_put_plane> h_put_tab;
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -2643,6 +2648,144 @@ int mckpp_hip_dev_fence(mckpp_hip_handle h, void *stream)
 }
 
 // ---------------------------------------------------------------------------
+// State in from the caller's arrays (include/mckpp_hip_put.h): U, V, T, S set or incremented in place by one launch of
+// k_put_planes.  A check, which queues nothing, and a part that queues in fluxes_dev_queue's order; a multi handle
+// checks all its shards before any of them queues.  Nothing of the context's bookkeeping is touched: a put is an edit
+// of the profile rows (and of the reference slots of cs that follow level 1), which the column kernel reads at the
+// start of every step.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// The planes of a put, checked and resolved into the kernel's table.  dev_form: `in` is device memory (*dev, where asked
+// for: the device of the first plane's); otherwise host memory, and the table's `in` is set by put_host_queue.
+int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_put_plane_c *planes, bool dev_form,
+              std::vector<mckpp_put_plane> &tab, int *maxlev, int *dev)
+{
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (nplanes < 0 || nplanes > MCKPP_PUT_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_PUT_PLANES_MAX);
+  HIPCHK(hipSetDevice(h->device));
+  tab.clear();
+  *maxlev = 0;
+  int prof[MCKPP_PUT_PLANES_MAX];
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_put_plane_c &q = planes[k];
+    int row, lv0, lv1, ref;
+    switch (q.field) {
+      case MCKPP_OUT_U: row = P_U; lv0 = P_US0; lv1 = P_US1; ref = CS_UREF; break;
+      case MCKPP_OUT_V: row = P_V; lv0 = P_VS0; lv1 = P_VS1; ref = CS_VREF; break;
+      case MCKPP_OUT_T: row = P_T; lv0 = P_TS0; lv1 = P_TS1; ref = CS_TREF; break;
+      case MCKPP_OUT_S_ANOM:
+      case MCKPP_OUT_S: row = P_S; lv0 = P_SS0; lv1 = P_SS1; ref = h->c.L_SSref ? -1 : CS_SSURF; break;   // L_SSref: Ssurf stays SSref
+      default:
+        if (q.field < 0 || q.field >= MCKPP_OUT_COUNT) return fail("%s: planes[%d]: unknown output field %d", who, k, q.field);
+        return fail("%s: planes[%d]: field %d is an output of the step, not state (MCKPP_OUT_U %d, _V %d, _T %d, _S_ANOM %d, _S %d)",
+                    who, k, q.field, MCKPP_OUT_U, MCKPP_OUT_V, MCKPP_OUT_T, MCKPP_OUT_S_ANOM, MCKPP_OUT_S);
+    }
+    out_desc d;
+    if (out_field(h, q.field, d)) return -1;
+    if (q.lev0 < 0 || q.nlev < 1 || (int64_t)q.lev0 + q.nlev > d.nlev)
+      return fail("%s: planes[%d]: lev0=%d nlev=%d is no range of levels of field %d, whose axis has %d (lev0 >= 0, nlev >= 1)",
+                  who, k, q.lev0, q.nlev, q.field, d.nlev);
+    if (q.dtype != MCKPP_EXP_F64 && q.dtype != MCKPP_EXP_F32)
+      return fail("%s: planes[%d]: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, k, q.dtype);
+    if (q.op != MCKPP_PUT_SET && q.op != MCKPP_PUT_ADD)
+      return fail("%s: planes[%d]: op %d (MCKPP_PUT_SET 0, MCKPP_PUT_ADD 1)", who, k, q.op);
+    if (q.flags & ~(MCKPP_PUT_SKIP | MCKPP_PUT_TIME_LEVELS))
+      return fail("%s: planes[%d]: flags %#x (a mask of MCKPP_PUT_SKIP 1, MCKPP_PUT_TIME_LEVELS 2)", who, k, (unsigned)q.flags);
+    const bool skip = q.flags & MCKPP_PUT_SKIP, levels = q.flags & MCKPP_PUT_TIME_LEVELS;
+    if (skip && std::isnan(q.skip_value))
+      return fail("%s: planes[%d]: the skip value is NaN, which no element compares equal to", who, k);
+    for (int j = 0; j < k; ++j)
+      if (prof[j] == row && q.lev0 < planes[j].lev0 + planes[j].nlev && planes[j].lev0 < q.lev0 + q.nlev)
+        return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d) at overlapping levels %d..%d and %d..%d: the "
+                    "planes of a call have no order", who, k, j, q.field, planes[j].field, q.lev0, q.lev0 + q.nlev - 1,
+                    planes[j].lev0, planes[j].lev0 + planes[j].nlev - 1);
+    prof[k] = row;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d].in", k);
+    const size_t elem = q.dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
+    if (!dev_form) {
+      if (!q.in) return fail("%s: %s is null", who, arg);
+    } else if (dev_ptr_check(h, who, arg, q.in, (size_t)h->npts * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) {
+      return -1;
+    }
+    const bool add = q.op == MCKPP_PUT_ADD;
+    tab.push_back(mckpp_put_plane{q.in, h->d_prof[row].get(), levels ? h->d_prof[lv0].get() : nullptr,
+                                  levels ? h->d_prof[lv1].get() : nullptr, q.skip_value, d.ld, d.off + q.lev0, q.nlev,
+                                  q.dtype == MCKPP_EXP_F32 ? 1 : 0, add ? 1 : 0, skip ? 1 : 0, (!add && d.add_sref) ? 1 : 0,
+                                  q.lev0 == 0 ? ref : -1, ref == CS_SSURF ? 1 : 0});
+    *maxlev = std::max(*maxlev, (int)q.nlev);
+  }
+  return 0;
+}
+
+// the table onto the device on the context's stream, a wait for `produced` (null: none), the launch, ev_read behind it
+int put_queue(mckpp_hip_ctx *h, const std::vector<mckpp_put_plane> &tab, int maxlev, hipEvent_t produced)
+{
+  if (tab.empty() || h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (!h->d_put_tab) HIPCHK(h->d_put_tab.alloc(MCKPP_PUT_PLANES));
+  mckpp_put_plane *q = nullptr;
+  HIPCHK(h->h_put_tab.take(MCKPP_PUT_PLANES, &q));
+  std::copy(tab.begin(), tab.end(), q);
+  HIPCHK(hipMemcpyAsync(h->d_put_tab, q, tab.size() * sizeof(mckpp_put_plane), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(h->h_put_tab.queued(h->stream));
+  if (produced) HIPCHK(hipStreamWaitEvent(h->stream, produced, 0));
+  HIPCHK(mckpp_launch_put_planes(h->d_put_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs, h->stream));
+  if (!h->ev_read) HIPCHK(h->ev_read.create());
+  HIPCHK(hipEventRecord(h->ev_read, h->stream));
+  return 0;
+}
+
+// the host form: every plane as it is into the context's staging (each at a multiple of 256 bytes) on the context's
+// stream, the launch, and the wait that lets the caller rewrite its arrays and the staging be reused
+int put_host_queue(mckpp_hip_ctx *h, std::vector<mckpp_put_plane> &tab, int maxlev)
+{
+  if (tab.empty() || h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<size_t> at(tab.size()), bytes(tab.size());
+  size_t total = 0;
+  for (size_t k = 0; k < tab.size(); ++k) {
+    bytes[k] = (size_t)h->npts * (size_t)tab[k].nlev * (tab[k].f32 ? sizeof(float) : sizeof(double));
+    at[k] = total;
+    total += (bytes[k] + 255) / 256 * 256;
+  }
+  HIPCHK(h->d_put_stage.reserve(total));
+  for (size_t k = 0; k < tab.size(); ++k) {
+    HIPCHK(hipMemcpyAsync(h->d_put_stage + at[k], tab[k].in, bytes[k], hipMemcpyHostToDevice, h->stream));
+    tab[k].in = h->d_put_stage + at[k];
+  }
+  if (put_queue(h, tab, maxlev, nullptr)) return -1;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  std::vector<mckpp_put_plane> tab;
+  int maxlev = 0;
+  if (put_check(h, who, nplanes, planes, true, tab, &maxlev, nullptr)) return -1;
+  if (tab.empty() || h->ncol == 0) return 0;
+  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return put_queue(h, tab, maxlev, h->ev_caller);
+  });
+}
+
+int mckpp_hip_put_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_put_plane_c *planes)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  std::vector<mckpp_put_plane> tab;
+  int maxlev = 0;
+  if (put_check(h, who, nplanes, planes, false, tab, &maxlev, nullptr)) return -1;
+  return put_host_queue(h, tab, maxlev);
+  });
+}
+
+// ---------------------------------------------------------------------------
 // Output windows accumulated inside the step launches (mckpp_hip_window_schedule): k_column_ps samples every field
 // of every schedule after each column's step, into the record of the step's window (see mckpp_win_t).  The host
 // keeps the bookkeeping: which steps have run under a schedule, so which records are complete, and which are
@@ -4288,6 +4431,37 @@ int mckpp_hip_multi_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const
   if (multi_caller_event(m, dev, consumer_stream)) return -1;
   for (int d = 0; d < ndev; ++d)
     if (records_dev_queue(m->ctx[d], rs[(size_t)d], d == 0, m->ev_caller, consumer_stream)) return -1;
+  return 0;
+  });
+}
+
+// mckpp_hip_put_dev / _put_host over all shards: the same planes for every shard, which writes its own columns only
+int mckpp_hip_multi_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<std::vector<mckpp_put_plane>> tabs((size_t)ndev);
+  int maxlev = 0, dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (put_check(m->ctx[d], who, nplanes, planes, true, tabs[(size_t)d], &maxlev, &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (put_queue(m->ctx[d], tabs[(size_t)d], maxlev, m->ev_caller)) return -1;
+  return 0;
+  });
+}
+
+int mckpp_hip_multi_put_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_put_plane_c *planes)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<std::vector<mckpp_put_plane>> tabs((size_t)ndev);
+  int maxlev = 0;
+  for (int d = 0; d < ndev; ++d)
+    if (put_check(m->ctx[d], who, nplanes, planes, false, tabs[(size_t)d], &maxlev, nullptr)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (put_host_queue(m->ctx[d], tabs[(size_t)d], maxlev)) return -1;
   return 0;
   });
 }

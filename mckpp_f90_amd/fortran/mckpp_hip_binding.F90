@@ -1,5 +1,5 @@
 !> iso_c_binding view of include/mckpp_hip.h and of its companions
-!! mckpp_hip_device.h, mckpp_hip_zoom.h and mckpp_hip_device_records.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h and mckpp_hip_put.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -53,6 +53,19 @@ module mckpp_hip_binding
     real(c_double) :: land_value
     type(c_ptr) :: out
   end type mckpp_dev_record_plane_c
+
+  !> one plane of mckpp_hip_put_dev / mckpp_hip_put_host (include/mckpp_hip_put.h): the array at `in`, (npts, nlev) of
+  !! MCKPP_EXP_F64 or MCKPP_EXP_F32, is set into (op MCKPP_PUT_SET) or added to (MCKPP_PUT_ADD) levels lev0 .. lev0+nlev-1
+  !! (0-based) of state field `field` (MCKPP_OUT_U, _V, _T, _S_ANOM, _S); flags: MCKPP_PUT_SKIP - elements equal to
+  !! skip_value leave the state alone -, MCKPP_PUT_TIME_LEVELS - Us / Xs(:,:,0:1) take the same operation
+  type, bind(C) :: mckpp_put_plane_c
+    integer(c_int32_t) :: field, lev0, nlev, dtype, op, flags
+    real(c_double) :: skip_value
+    type(c_ptr) :: in
+  end type mckpp_put_plane_c
+  integer(c_int32_t), parameter :: MCKPP_PUT_SET = 0, MCKPP_PUT_ADD = 1
+  integer(c_int32_t), parameter :: MCKPP_PUT_SKIP = 1, MCKPP_PUT_TIME_LEVELS = 2
+  integer(c_int32_t), parameter :: MCKPP_PUT_PLANES_MAX = 64
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -785,6 +798,37 @@ module mckpp_hip_binding
       type(c_ptr), value :: m, consumer_stream
       integer(c_int32_t), value :: nplanes
       type(mckpp_dev_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! the prognostic state set or incremented in place (include/mckpp_hip_put.h): one launch for all planes on the
+    ! context's stream, between launches; nothing the context has scheduled is cancelled.  A put through these raw
+    ! interfaces leaves the host's kpp_3d_fields copy of U, X, Us, Xs stale, and the session layer does not see it
+    function mckpp_hip_put_dev(handle, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_put_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_put_plane_c
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_put_host(handle, nplanes, planes) bind(C, name="mckpp_hip_put_host") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_put_plane_c
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_put_dev(m, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_multi_put_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_put_plane_c
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_put_host(m, nplanes, planes) bind(C, name="mckpp_hip_multi_put_host") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_put_plane_c
+      type(c_ptr), value :: m
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_put_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
