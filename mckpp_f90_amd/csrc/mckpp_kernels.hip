@@ -45,57 +45,129 @@ __global__ void k_exp_batch(int64_t n, const double *x, double *y)
 }
 
 // ---------------------------------------------------------------------------
-// layout kernels: Fortran column-fastest A(npts, nlev) <-> device rows.
-// 64x64 tile through LDS so both sides move whole 512-B segments.
+// The move between device rows and caller planes, stated once for the six kernels that make it (k_gather_rows,
+// k_scatter_rows, k_record_pack, k_fetch_planes, k_record_planes, k_put_planes; k_fetch_planes alone has the routines
+// below written out in its body, for the reason given there).
+//
+// Rows are [nrow][ld] doubles with a row's levels contiguous; a plane is plane(npoints, nlev) with points fastest, and
+// row r belongs at position map[r] of it.  A workgroup of 256 threads takes 64 rows (blockIdx.x) by 64 levels
+// (blockIdx.y, origin l0) through `__shared__ double tile[64][65]`, which the kernel declares: tx = thread & 63 runs
+// along whichever side is being read or written, ty = thread >> 6 strides the other side by 4, so both sides move
+// whole 512-B segments, and the 65th column keeps the transposed access off one LDS bank.  A tile lane outside
+// nrow x nlev holds 0.0 and is never written out, so what a kernel's arithmetic makes of that zero is of no account.
+//
+// The barrier rule: every thread of a workgroup that reaches the tile reaches its __syncthreads().  Exits before the
+// barrier depend on blockIdx and on the plane alone (the level tile beyond the plane, the one-level path and its idle
+// workgroups, the fill); exits that depend on the thread (a row or a level past the end) come after it.
+//
+// ONE_LEVEL: a plane of one level has nothing to transpose and takes a row per thread.  The grid's x extent is that of
+// 64-row tiles, so every fourth workgroup takes 256 rows and the others leave.  The four plane kernels set it;
+// k_gather_rows and k_scatter_rows send one level through the tile like any other.
 // ---------------------------------------------------------------------------
+
+// Rows to points.  load(r, lev, in_range) is the kernel's value of row r at level lev of the plane, formed in fp64, 0.0
+// for a lane out of range; the one conversion to T is at the write.  map == nullptr: row r is position r.
+template <bool ONE_LEVEL, class T, class Load>
+__device__ __forceinline__ void tile_rows_to_points(double (*tile)[65], int64_t nrow, int nlev, int l0,
+                                                    const int *__restrict__ map, int64_t npoints, T *__restrict__ dst,
+                                                    Load load)
+{
+  if (l0 >= nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  if (ONE_LEVEL && nlev == 1) {
+    if (blockIdx.x & 3) return;
+    const int64_t r = r0 + threadIdx.x;
+    if (r < nrow) dst[map ? (int64_t)map[r] : r] = (T)load(r, 0, true);
+    return;
+  }
+  for (int rr = ty; rr < 64; rr += 4) {       // read: levels fastest
+    const int64_t r = r0 + rr;
+    const int lev = l0 + tx;
+    tile[tx][rr] = load(r, lev, r < nrow && lev < nlev);
+  }
+  __syncthreads();
+  const int64_t r = r0 + tx;
+  if (r >= nrow) return;
+  const int64_t pos = map ? (int64_t)map[r] : r;
+  for (int l = ty; l < 64; l += 4) {          // write: points fastest
+    const int lev = l0 + l;
+    if (lev < nlev) dst[(int64_t)lev * npoints + pos] = (T)tile[l][tx];
+  }
+}
+
+// Points to rows: the opposite direction.  The plane's element, widened exactly, travels through the tile, and
+// store(r, lev, v) is what the kernel does with it on the row side.  The map is read as it is: it must not be null.
+template <bool ONE_LEVEL, class T, class Store>
+__device__ __forceinline__ void tile_points_to_rows(double (*tile)[65], int64_t nrow, int nlev, int l0,
+                                                    const int *__restrict__ map, int64_t npoints, const T *__restrict__ src,
+                                                    Store store)
+{
+  if (l0 >= nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  if (ONE_LEVEL && nlev == 1) {
+    if (blockIdx.x & 3) return;
+    const int64_t r = r0 + threadIdx.x;
+    if (r < nrow) store(r, 0, (double)src[map[r]]);
+    return;
+  }
+  {
+    const int64_t r = r0 + tx;
+    const int64_t pos = r < nrow ? (int64_t)map[r] : 0;
+    for (int l = ty; l < 64; l += 4) {        // read: points fastest
+      const int lev = l0 + l;
+      double v = 0.0;
+      if (r < nrow && lev < nlev) v = (double)src[(int64_t)lev * npoints + pos];
+      tile[l][tx] = v;
+    }
+  }
+  __syncthreads();
+  const int lev = l0 + tx;
+  if (lev >= nlev) return;
+  for (int rr = ty; rr < 64; rr += 4) {       // write: levels fastest
+    const int64_t r = r0 + rr;
+    if (r < nrow) store(r, lev, tile[tx][rr]);
+  }
+}
+
+// The fill of a position list: workgroup `ftile` of those behind a plane's row tiles takes 64 entries of the list of
+// positions that are no row and writes v there, a thread per position, the levels of its level tile in turn.  No tile,
+// no barrier.
+template <class T>
+__device__ __forceinline__ void fill_positions(int64_t ftile, int nlev, int l0, const int *__restrict__ list, int64_t n,
+                                               int64_t npoints, T *__restrict__ dst, T v)
+{
+  if (l0 >= nlev) return;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t i = ftile * 64 + tx;
+  if (i >= n) return;
+  const int64_t pos = list[i];
+  for (int l = ty; l < 64; l += 4)
+    if (l0 + l < nlev) dst[(int64_t)(l0 + l) * npoints + pos] = v;
+}
+
+// Upload: the Fortran slab A(npts, nlev), as it is.
 __global__ __launch_bounds__(256) void k_gather_rows(const double *__restrict__ src3d, int64_t npts,
                                                      int nlev, int lev_off, const int *__restrict__ ipt,
                                                      int64_t ncol, double *__restrict__ dst, int ld,
                                                      int dst_off)
 {
   __shared__ double tile[64][65];
-  const int64_t c0 = (int64_t)blockIdx.x * 64;
-  const int l0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int l = ty; l < 64; l += 4) {          // read: columns fastest
-    int64_t c = c0 + tx;
-    int lev = l0 + l;
-    double v = 0.0;
-    if (c < ncol && lev < nlev) v = src3d[(int64_t)(lev + lev_off) * npts + ipt[c]];
-    tile[l][tx] = v;
-  }
-  __syncthreads();
-  for (int cc = ty; cc < 64; cc += 4) {       // write: levels fastest
-    int64_t c = c0 + cc;
-    int lev = l0 + tx;
-    if (c < ncol && lev < nlev) dst[c * ld + dst_off + lev] = tile[tx][cc];
-  }
+  tile_points_to_rows<false>(tile, ncol, nlev, blockIdx.y * 64, ipt, npts, src3d + (int64_t)lev_off * npts,
+                             [&](int64_t c, int lev, double v) { dst[c * ld + dst_off + lev] = v; });
 }
 
+// Download, and window_fetch / window_record_fetch through a map of their own: the row's element, as it is.
 __global__ __launch_bounds__(256) void k_scatter_rows(const double *__restrict__ src, int ld, int src_off,
                                                       const int *__restrict__ ipt, int64_t ncol,
                                                       double *__restrict__ dst3d, int64_t npts, int nlev,
                                                       int lev_off)
 {
   __shared__ double tile[64][65];
-  const int64_t c0 = (int64_t)blockIdx.x * 64;
-  const int l0 = blockIdx.y * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  for (int cc = ty; cc < 64; cc += 4) {
-    int64_t c = c0 + cc;
-    int lev = l0 + tx;
-    double v = 0.0;
-    if (c < ncol && lev < nlev) v = src[c * ld + src_off + lev];
-    tile[tx][cc] = v;
-  }
-  __syncthreads();
-  for (int l = ty; l < 64; l += 4) {
-    int64_t c = c0 + tx;
-    int lev = l0 + l;
-    if (c < ncol && lev < nlev) dst3d[(int64_t)(lev + lev_off) * npts + ipt[c]] = tile[l][tx];
-  }
+  tile_rows_to_points<false>(tile, ncol, nlev, blockIdx.y * 64, ipt, npts, dst3d + (int64_t)lev_off * npts,
+                             [&](int64_t c, int lev, bool in) { return in ? src[c * ld + src_off + lev] : 0.0; });
 }
-
 
 // ---------------------------------------------------------------------------
 // Surface-flux assembly + non-turbulent flux: mckpp_fluxes,
@@ -219,14 +291,16 @@ __global__ void k_window_mean(const double *__restrict__ sum, double *__restrict
 }
 
 // ---------------------------------------------------------------------------
-// Export of an output schedule's records (mckpp_hip_window_export): one launch packs every plane of one record into
-// an export slot, in the layout the host wants - plane(point, level) with points fastest, no ld padding, through the
-// column map (null: the columns themselves, a shard's compact form), as double or narrowed to float - so that the
-// fetch is a plain copy.  The planes go on blockIdx.z and are described by the table the export built.  The mean is
-// k_window_mean's one division; the narrowing, after it, is one round-to-nearest-even conversion.  The 64x64 tile
-// through LDS is k_scatter_rows': both sides move whole segments.  Only resident columns are written: the slot's
-// land points were filled when the export was set.
+// The plane kernels: one launch moves every plane of a call, the planes on blockIdx.z and described by a device
+// table; the grid's level tiles are those of the deepest plane.  The move is the one stated above (rows to points, or
+// points to rows for the put); what follows says what each kernel's value is.
 // ---------------------------------------------------------------------------
+
+// Export of an output schedule's records (mckpp_hip_window_export): every plane of one record into its export slot,
+// in the layout the host wants - no ld padding, through the column map (null: the columns themselves, a shard's
+// compact form) - so that the fetch is a plain copy.  The value: the ring row's element, of a mean divided by the
+// period (k_window_mean's one division), then narrowed where T is float.  Only resident columns are written: the
+// slot's land points were filled when the export was set.
 template <class T>
 __global__ __launch_bounds__(256) void k_record_pack(const mckpp_pack_plane *__restrict__ tab, int ring_slot, double period,
                                                      const int *__restrict__ ipt, int64_t ncol, int64_t npts,
@@ -234,39 +308,14 @@ __global__ __launch_bounds__(256) void k_record_pack(const mckpp_pack_plane *__r
 {
   __shared__ double tile[64][65];
   const mckpp_pack_plane e = tab[blockIdx.z];
-  const int l0 = blockIdx.y * 64;
-  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
   const bool mean = e.op == 0;
   const double *__restrict__ src = e.src + (long long)ring_slot * e.slot_stride;
-  T *__restrict__ dst = reinterpret_cast<T *>(dst_slot + e.dst_off);
-  const int64_t c0 = (int64_t)blockIdx.x * 64;
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  if (e.nlev == 1) {   // a two-dimensional field: nothing to transpose, a column per thread; the grid's x extent is
-    // that of 64-column tiles, so every fourth workgroup takes 256 columns and the others leave
-    if (blockIdx.x & 3) return;
-    const int64_t c = c0 + threadIdx.x;
-    if (c < ncol) {
-      double v = src[c * e.ld + e.off];
-      if (mean) v = v / period;
-      dst[ipt ? (int64_t)ipt[c] : c] = (T)v;
-    }
-    return;
-  }
-  for (int cc = ty; cc < 64; cc += 4) {       // read: levels fastest
-    const int64_t c = c0 + cc;
-    const int lev = l0 + tx;
-    double v = 0.0;
-    if (c < ncol && lev < e.nlev) v = src[c * e.ld + e.off + lev];
-    if (mean) v = v / period;
-    tile[tx][cc] = v;
-  }
-  __syncthreads();
-  const int64_t c = c0 + tx;
-  const int64_t pt = c < ncol ? (ipt ? (int64_t)ipt[c] : c) : 0;
-  for (int l = ty; l < 64; l += 4) {          // write: points fastest
-    const int lev = l0 + l;
-    if (c < ncol && lev < e.nlev) dst[(int64_t)lev * npts + pt] = (T)tile[l][tx];
-  }
+  tile_rows_to_points<true>(tile, ncol, e.nlev, blockIdx.y * 64, ipt, npts, reinterpret_cast<T *>(dst_slot + e.dst_off),
+                            [&](int64_t c, int lev, bool in) {
+                              double v = in ? src[c * e.ld + e.off + lev] : 0.0;
+                              if (mean) v = v / period;
+                              return v;
+                            });
 }
 
 template <class T>
@@ -275,16 +324,15 @@ __global__ void k_export_fill(T *__restrict__ p, size_t n, T v)
   for (size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) p[i] = v;
 }
 
-// ---------------------------------------------------------------------------
-// Delivery of output fields into the caller's device arrays (mckpp_hip_fetch_dev): k_record_pack's sibling.  One
-// launch writes every plane of the call - levels off .. off + nlev - 1 of a field as it stands on the device,
-// k_out_sample's value (plus the column's Sref where the field is S) - as out(npts, nlev), points fastest, through
-// the column map, as double or narrowed by one round-to-nearest-even conversion.  The planes go on blockIdx.z, and
-// the element type is a plane's own.  The first `coltiles` workgroups in x take 64 resident columns each: a column
-// per thread where the plane has one level, otherwise the 64x64 tile through LDS, so that both sides move whole
-// segments.  The workgroups after them take 64 entries each of the list of non-resident points and, where the plane
-// asks for it, write its land value there: a thread per point, the levels of the tile in turn.
-// ---------------------------------------------------------------------------
+// Delivery of output fields into the caller's device arrays (mckpp_hip_fetch_dev): levels off .. off + nlev - 1 of a
+// field as it stands on the device, as out(npts, nlev) through the column map; the element type is a plane's own.
+// The value: k_out_sample's - the row's element, plus the column's Sref where the field is S - then narrowed where T is
+// float.  The first `coltiles` workgroups in x take the resident columns; those after them fill the list of
+// non-resident points with the plane's land value, where it asks for that.
+//
+// This kernel keeps a body of its own: it is tile_rows_to_points<true> and fill_positions written out, with the
+// value formed in place.  Through the shared routines the compiler's code for it measured 4 % slower
+// (profiles/tiles/README.md), so the text below is what is held to the barrier rule above by hand.
 template <class T>
 __device__ __forceinline__ void fetch_plane(const mckpp_fetch_plane &e, double (*tile)[65], const int *__restrict__ ipt,
                                             int64_t ncol, int64_t npts, const double *__restrict__ cs,
@@ -305,7 +353,7 @@ __device__ __forceinline__ void fetch_plane(const mckpp_fetch_plane &e, double (
     return;
   }
   const int64_t c0 = (int64_t)blockIdx.x * 64;
-  if (e.nlev == 1) {   // nothing to transpose: every fourth workgroup takes 256 columns and the others leave
+  if (e.nlev == 1) {   // the one-level path
     if (blockIdx.x & 3) return;
     const int64_t c = c0 + threadIdx.x;
     if (c < ncol) {
@@ -345,63 +393,28 @@ __global__ __launch_bounds__(256) void k_fetch_planes(const mckpp_fetch_plane *_
   else fetch_plane<double>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
 }
 
-// ---------------------------------------------------------------------------
-// Delivery of completed records of output schedules into the caller's device arrays (mckpp_hip_records_dev): the
-// sibling of k_record_pack and k_fetch_planes.  One launch writes every plane of the call, and the planes may come
-// from any schedules and records, so - unlike either sibling - a plane carries its own geometry in the table: its
-// rows (ring slot and operation resolved by the host), their number, the map row -> position of its point axis, the
-// axis' length, and the list of positions that are no row.  The mean is k_window_mean's one division, formed here;
-// the narrowing, after it, is one round-to-nearest-even conversion.  The planes go on blockIdx.z; the grid's x extent
-// is the largest plane's, and a workgroup beyond a plane's own tiles leaves before it touches memory.  A plane's
-// first ceil(nrow / 64) workgroups in x take 64 rows each: a row per thread where the plane has one level, otherwise
-// the 64x64 tile through LDS, so that both sides move whole segments.  The workgroups after them take 64 entries each
-// of the non-row list and, where the plane fills, write its land value there.
-// ---------------------------------------------------------------------------
+// Delivery of completed records of output schedules into the caller's device arrays (mckpp_hip_records_dev).  The
+// planes may come from any schedules and records, so a plane carries its own geometry in the table: its rows (ring
+// slot and operation resolved by the host), their number, the map row -> position of its point axis, the axis' length,
+// and the list of positions that are no row.  The value: k_record_pack's - the row's element, of a mean divided by the
+// period, then narrowed where T is float.  The grid's x extent is the largest plane's; a plane's first ceil(nrow / 64)
+// workgroups in x take its rows, those after them fill its non-row list where it asks for that, and a workgroup beyond
+// both leaves before it touches memory.
 template <class T>
 __device__ __forceinline__ void record_plane(const mckpp_rec_plane &e, double (*tile)[65])
 {
   const int l0 = blockIdx.y * 64;
-  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
   T *__restrict__ dst = static_cast<T *>(e.out);
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
   const int64_t rowtiles = (e.nrow + 63) / 64;
   if ((int64_t)blockIdx.x >= rowtiles) {
-    if (!e.fill) return;
-    const int64_t i = ((int64_t)blockIdx.x - rowtiles) * 64 + tx;
-    if (i >= e.nnorow) return;
-    const int64_t pos = e.norow[i];
-    const T v = (T)e.land_value;
-    for (int l = ty; l < 64; l += 4)
-      if (l0 + l < e.nlev) dst[(int64_t)(l0 + l) * e.npoints + pos] = v;
+    if (e.fill) fill_positions((int64_t)blockIdx.x - rowtiles, e.nlev, l0, e.norow, e.nnorow, e.npoints, dst, (T)e.land_value);
     return;
   }
-  const int64_t r0 = (int64_t)blockIdx.x * 64;
-  if (e.nlev == 1) {   // nothing to transpose: every fourth workgroup takes 256 rows and the others leave
-    if (blockIdx.x & 3) return;
-    const int64_t r = r0 + threadIdx.x;
-    if (r < e.nrow) {
-      double v = e.src[r * e.ld + e.off];
-      if (e.mean) v = v / e.period;
-      dst[e.map[r]] = (T)v;
-    }
-    return;
-  }
-  for (int rr = ty; rr < 64; rr += 4) {       // read: levels fastest
-    const int64_t r = r0 + rr;
-    const int lev = l0 + tx;
-    double v = 0.0;
-    if (r < e.nrow && lev < e.nlev) v = e.src[r * e.ld + e.off + lev];
+  tile_rows_to_points<true>(tile, e.nrow, e.nlev, l0, e.map, e.npoints, dst, [&](int64_t r, int lev, bool in) {
+    double v = in ? e.src[r * e.ld + e.off + lev] : 0.0;
     if (e.mean) v = v / e.period;
-    tile[tx][rr] = v;
-  }
-  __syncthreads();
-  const int64_t r = r0 + tx;
-  if (r >= e.nrow) return;
-  const int64_t pos = e.map[r];
-  for (int l = ty; l < 64; l += 4) {          // write: points fastest
-    const int lev = l0 + l;
-    if (lev < e.nlev) dst[(int64_t)lev * e.npoints + pos] = (T)tile[l][tx];
-  }
+    return v;
+  });
 }
 
 __global__ __launch_bounds__(256) void k_record_planes(const mckpp_rec_plane *__restrict__ tab)
@@ -412,18 +425,13 @@ __global__ __launch_bounds__(256) void k_record_planes(const mckpp_rec_plane *__
   else record_plane<double>(e, tile);
 }
 
-// ---------------------------------------------------------------------------
-// The prognostic state set or incremented from the caller's arrays (mckpp_hip_put_dev, mckpp_hip_put_host):
-// k_fetch_planes' mirror image.  One launch applies every plane of the call - in(npts, nlev), points fastest, doubles or
-// floats widened exactly, through the column map - to elements off .. off + nlev - 1 of a profile's rows and, where
-// the plane asks for it, of the field's two saved time levels.  The planes go on blockIdx.z; element type, operation and
-// flags are a plane's own.  A plane of one level takes a column per thread; otherwise the 64x64 tile through LDS, in the
-// opposite direction to the fetch: the points-fastest read of `in` into the tile, then the levels-fastest
-// read-modify-write of the rows, so that both sides move whole segments.  The value itself travels through the tile,
-// and the skip decision is its comparison on the row side: no sentinel, no second tile.  No atomics: the host refused
-// overlapping planes and a column is in the map once, so every state element has one writer.  Each operation below is
-// one fp64 operation, in the order include/mckpp_hip_put.h states (built with -ffp-contract=off).
-// ---------------------------------------------------------------------------
+// The prognostic state set or incremented from the caller's arrays (mckpp_hip_put_dev, mckpp_hip_put_host): every plane
+// - in(npts, nlev), doubles or floats widened exactly, through the column map - applied to elements off .. off + nlev - 1
+// of a profile's rows and, where the plane asks for it, of the field's two saved time levels.  Element type, operation
+// and flags are a plane's own.  The value travels through the tile as it is, and put_element is what happens to it on
+// the row side, the skip decision included: no sentinel, no second tile.  No atomics: the host refused overlapping
+// planes and a column is in the map once, so every state element has one writer.  Each operation below is one fp64
+// operation, in the order include/mckpp_hip_put.h states (built with -ffp-contract=off).
 __device__ __forceinline__ void put_element(const mckpp_put_plane &e, double *__restrict__ cs, int64_t c, int lev, double v)
 {
   if (e.skip && v == e.skip_value) return;
@@ -440,47 +448,15 @@ __device__ __forceinline__ void put_element(const mckpp_put_plane &e, double *__
   if (e.ref_slot >= 0 && lev == 0) cs[c * MCKPP_CS + e.ref_slot] = e.ref_sref ? x + cs[c * MCKPP_CS + CS_SREF] : x;
 }
 
-template <class T>
-__device__ __forceinline__ void put_plane(const mckpp_put_plane &e, double (*tile)[65], const int *__restrict__ ipt,
-                                          int64_t ncol, int64_t npts, double *__restrict__ cs)
-{
-  const int l0 = blockIdx.y * 64;
-  if (l0 >= e.nlev) return;   // (the grid's level tiles are those of the deepest plane)
-  const T *__restrict__ src = static_cast<const T *>(e.in);
-  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
-  const int64_t c0 = (int64_t)blockIdx.x * 64;
-  if (e.nlev == 1) {   // nothing to transpose: every fourth workgroup takes 256 columns and the others leave
-    if (blockIdx.x & 3) return;
-    const int64_t c = c0 + threadIdx.x;
-    if (c < ncol) put_element(e, cs, c, 0, (double)src[ipt[c]]);
-    return;
-  }
-  {
-    const int64_t c = c0 + tx;
-    const int64_t pt = c < ncol ? (int64_t)ipt[c] : 0;
-    for (int l = ty; l < 64; l += 4) {          // read: points fastest
-      const int lev = l0 + l;
-      double v = 0.0;
-      if (c < ncol && lev < e.nlev) v = (double)src[(int64_t)lev * npts + pt];
-      tile[l][tx] = v;
-    }
-  }
-  __syncthreads();
-  const int lev = l0 + tx;
-  if (lev >= e.nlev) return;
-  for (int cc = ty; cc < 64; cc += 4) {         // read-modify-write: levels fastest
-    const int64_t c = c0 + cc;
-    if (c < ncol) put_element(e, cs, c, lev, tile[tx][cc]);
-  }
-}
-
 __global__ __launch_bounds__(256) void k_put_planes(const mckpp_put_plane *__restrict__ tab, const int *__restrict__ ipt,
                                                     int64_t ncol, int64_t npts, double *__restrict__ cs)
 {
   __shared__ double tile[64][65];
   const mckpp_put_plane e = tab[blockIdx.z];
-  if (e.f32) put_plane<float>(e, tile, ipt, ncol, npts, cs);
-  else put_plane<double>(e, tile, ipt, ncol, npts, cs);
+  const int l0 = blockIdx.y * 64;
+  const auto put = [&](int64_t c, int lev, double v) { put_element(e, cs, c, lev, v); };
+  if (e.f32) tile_points_to_rows<true>(tile, ncol, e.nlev, l0, ipt, npts, static_cast<const float *>(e.in), put);
+  else tile_points_to_rows<true>(tile, ncol, e.nlev, l0, ipt, npts, static_cast<const double *>(e.in), put);
 }
 
 }  // namespace

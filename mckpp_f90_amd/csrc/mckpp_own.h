@@ -6,10 +6,10 @@
 // the guard must be able to guard it: it joins what it started and brings a worker's exception back to the caller's
 // thread.
 //
-// The resources: move-only owners of device blocks, pinned host blocks, events and streams, and half_built, the owner
-// of an object until its init function hands it out.  An owner never synchronises and never reports an error from its
-// destructor: whoever drops a buffer that queued work may still use waits first, at the call site.  (The one wait in
-// this file is pinned_turns::take, which is that type's purpose.)
+// The resources: move-only owners of device blocks, pinned host blocks, events, streams and plane tables, and
+// half_built, the owner of an object until its init function hands it out.  An owner never synchronises and never
+// reports an error from its destructor: whoever drops a buffer that queued work may still use waits first, at the
+// call site.  (The one wait in this file is pinned_turns::take, which is that type's purpose.)
 #ifndef MCKPP_OWN_H
 #define MCKPP_OWN_H
 
@@ -164,6 +164,8 @@ class hip_event {
   void reset() { if (e_) (void)hipEventDestroy(e_); e_ = nullptr; }
   // an ordering event by default; hipEventDefault for one that is timed
   hipError_t create(unsigned flags = hipEventDisableTiming) { reset(); return hipEventCreateWithFlags(&e_, flags); }
+  // recorded on `s`; an ordering event is created on first use
+  hipError_t record(hipStream_t s) { const hipError_t e = e_ ? hipSuccess : create(); return e == hipSuccess ? hipEventRecord(e_, s) : e; }
   operator hipEvent_t() const { return e_; }
 };
 
@@ -207,6 +209,27 @@ class pinned_turns {
   }
   // the copy of the slot taken last has been queued on `s`
   hipError_t queued(hipStream_t s) { return hipEventRecord(ev_[(seq_ - 1) & 1u], s); }
+};
+
+// A table of planes onto the device on a stream (the plane kernels of mckpp_device.h read theirs there): the device
+// block of CAP entries, allocated on first use, and the pinned image it is written from, used in turn - so a call
+// never waits for its own copy, and the copy is ordered on the stream ahead of the launch that reads the table.
+template <class T, size_t CAP>
+class plane_table {
+  dev_buf<T> dev_;
+  pinned_turns<T> host_;
+ public:
+  // tab (at most CAP entries) to the device behind what `s` holds
+  hipError_t put(const std::vector<T> &tab, hipStream_t s)
+  {
+    T *q = nullptr;
+    hipError_t e = dev_ ? hipSuccess : dev_.alloc(CAP);
+    if (e == hipSuccess) e = host_.take(CAP, &q);
+    for (size_t i = 0; e == hipSuccess && i < tab.size(); ++i) q[i] = tab[i];
+    if (e == hipSuccess) e = hipMemcpyAsync(dev_, q, tab.size() * sizeof(T), hipMemcpyHostToDevice, s);
+    return e == hipSuccess ? host_.queued(s) : e;
+  }
+  operator const T *() const { return dev_; }
 };
 
 #endif

@@ -244,17 +244,13 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   // The device-array interface (include/mckpp_hip_device.h), everything created on first use.  ev_caller: recorded on the
   // caller's stream, what the library's stream then waits for; ev_delivered: behind the launch of mckpp_hip_fetch_dev, what
   // the consumer's stream waits for; ev_read / ev_read_flux: behind the last kernel on the context's stream / the flux
-  // ring's that reads caller arrays (mckpp_hip_dev_fence; null: no such kernel yet).  The plane table of fetch_dev:
-  // MCKPP_FETCH_PLANES entries on the device, written on the stream ahead of the launch from a pinned image used in turn.
+  // ring's that reads caller arrays (mckpp_hip_dev_fence; null: no such kernel yet).  The plane tables (mckpp_own.h) of
+  // fetch_dev, of mckpp_hip_records_dev (its event behind the launch is ev_delivered too) and of mckpp_hip_put_dev /
+  // _put_host (include/mckpp_hip_put.h; the event behind its launch is ev_read).
   hip_event ev_caller, ev_delivered, ev_read, ev_read_flux;
-  dev_buf<mckpp_fetch_plane> d_fetch_tab;
-  pinned_turns<mckpp_fetch_plane> h_fetch_tab;
-  // ... and that of mckpp_hip_records_dev, in the same way (its event behind the launch is ev_delivered too)
-  dev_buf<mckpp_rec_plane> d_rec_tab;
-  pinned_turns<mckpp_rec_plane> h_rec_tab;
-  // ... and that of mckpp_hip_put_dev / _put_host (include/mckpp_hip_put.h; the event behind its launch is ev_read)
-  dev_buf<mckpp_put_plane> d_put_tab;
-  pinned_turns<mckpp_put_plane> h_put_tab;
+  plane_table<mckpp_fetch_plane, MCKPP_FETCH_PLANES> fetch_tab;
+  plane_table<mckpp_rec_plane, MCKPP_DEV_PLANES_MAX> rec_tab;
+  plane_table<mckpp_put_plane, MCKPP_PUT_PLANES> put_tab;
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -2474,8 +2470,7 @@ int dev_fields_check(mckpp_hip_ctx *h, const char *who, const double *const fiel
 int caller_event(hip_event &ev, int device, void *stream)
 {
   HIPCHK(hipSetDevice(device));
-  if (!ev) HIPCHK(ev.create());
-  HIPCHK(hipEventRecord(ev, static_cast<hipStream_t>(stream)));
+  HIPCHK(ev.record(static_cast<hipStream_t>(stream)));
   return 0;
 }
 
@@ -2490,8 +2485,7 @@ int fluxes_dev_queue(mckpp_hip_ctx *h, int ntime, const double *const fields[8],
   mckpp_dev_fields f;
   for (int m = 0; m < 8; ++m) f.f[m] = fields[m];
   HIPCHK(mckpp_launch_fluxes_dev(p, ntime, f, h->d_ipt, l_rest, flsn, el, h->stream));
-  if (!h->ev_read) HIPCHK(h->ev_read.create());
-  HIPCHK(hipEventRecord(h->ev_read, h->stream));
+  HIPCHK(h->ev_read.record(h->stream));
   return 0;
 }
 
@@ -2508,10 +2502,29 @@ int ring_put_dev_queue(mckpp_hip_ctx *h, int rec, const double *const fields[8],
     HIPCHK(hipStreamWaitEvent(h->flux_stream, g.last_read[slot], 0));
     HIPCHK(mckpp_launch_flux_gather(f, h->d_ipt, h->ncol, g.slots + slot * 8 * (size_t)h->ncol, h->flux_stream));
     HIPCHK(hipEventRecord(g.arrived[slot], h->flux_stream));
-    if (!h->ev_read_flux) HIPCHK(h->ev_read_flux.create());
-    HIPCHK(hipEventRecord(h->ev_read_flux, h->flux_stream));
+    HIPCHK(h->ev_read_flux.record(h->flux_stream));
   }
   ring_put_done(g, rec);
+  return 0;
+}
+
+// What the checks of the plane tables share (fetch_dev_check, put_check, records_dev_check), for planes[k] of entry `who`.
+// Levels lev0 .. lev0 + nlev - 1 of a field's axis of `axis` levels; sched >= 0: the axis is what that schedule keeps.
+int plane_levels_check(const char *who, int k, int lev0, int nlev, int field, int axis, int sched = -1)
+{
+  if (lev0 >= 0 && nlev >= 1 && (int64_t)lev0 + nlev <= axis) return 0;
+  if (sched < 0)
+    return fail("%s: planes[%d]: lev0=%d nlev=%d is no range of levels of field %d, whose axis has %d (lev0 >= 0, nlev >= 1)",
+                who, k, lev0, nlev, field, axis);
+  return fail("%s: planes[%d]: lev0=%d nlev=%d is no range of the levels schedule %d keeps of field %d, which are %d (lev0 >= 0, "
+              "nlev >= 1)", who, k, lev0, nlev, sched, field, axis);
+}
+
+// the size of an element of the plane's dtype; 0, and the refusal, where it is neither of the two
+size_t plane_elem(const char *who, int k, int dtype)
+{
+  if (dtype == MCKPP_EXP_F64 || dtype == MCKPP_EXP_F32) return dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
+  fail("%s: planes[%d]: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, k, dtype);
   return 0;
 }
 
@@ -2530,15 +2543,11 @@ int fetch_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mc
     const mckpp_dev_plane_c &q = planes[k];
     out_desc d;
     if (out_field(h, q.field, d)) return -1;
-    if (q.lev0 < 0 || q.nlev < 1 || (int64_t)q.lev0 + q.nlev > d.nlev)
-      return fail("%s: planes[%d]: lev0=%d nlev=%d is no range of levels of field %d, whose axis has %d (lev0 >= 0, nlev >= 1)",
-                  who, k, q.lev0, q.nlev, q.field, d.nlev);
-    if (q.dtype != MCKPP_EXP_F64 && q.dtype != MCKPP_EXP_F32)
-      return fail("%s: planes[%d]: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, k, q.dtype);
+    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, d.nlev)) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
     char arg[32];
     snprintf(arg, sizeof arg, "planes[%d].out", k);
-    const size_t elem = q.dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
-    if (dev_ptr_check(h, who, arg, q.out, (size_t)h->npts * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
+    if (!elem || dev_ptr_check(h, who, arg, q.out, (size_t)h->npts * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
     tab.push_back(mckpp_fetch_plane{d.src, q.out, q.land_value, d.ld, d.off + q.lev0, q.nlev, d.add_sref,
                                     q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.fill_land ? 1 : 0});
     *maxlev = std::max(*maxlev, (int)q.nlev);
@@ -2582,17 +2591,11 @@ int fetch_dev_queue(mckpp_hip_ctx *h, const std::vector<mckpp_fetch_plane> &tab,
   if (tab.empty()) return 0;
   HIPCHK(hipSetDevice(h->device));
   if (any_fill && land_own(h)) return -1;
-  if (!h->d_fetch_tab) HIPCHK(h->d_fetch_tab.alloc(MCKPP_FETCH_PLANES));
-  mckpp_fetch_plane *q = nullptr;
-  HIPCHK(h->h_fetch_tab.take(MCKPP_FETCH_PLANES, &q));
-  std::copy(tab.begin(), tab.end(), q);
-  HIPCHK(hipMemcpyAsync(h->d_fetch_tab, q, tab.size() * sizeof(mckpp_fetch_plane), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h->h_fetch_tab.queued(h->stream));
+  HIPCHK(h->fetch_tab.put(tab, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
-  HIPCHK(mckpp_launch_fetch_planes(h->d_fetch_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
+  HIPCHK(mckpp_launch_fetch_planes(h->fetch_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
                                    any_fill ? h->d_land.get() : nullptr, any_fill ? h->nland : 0, h->stream));
-  if (!h->ev_delivered) HIPCHK(h->ev_delivered.create());
-  HIPCHK(hipEventRecord(h->ev_delivered, h->stream));
+  HIPCHK(h->ev_delivered.record(h->stream));
   HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
   return 0;
 }
@@ -2684,11 +2687,9 @@ int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_pu
     }
     out_desc d;
     if (out_field(h, q.field, d)) return -1;
-    if (q.lev0 < 0 || q.nlev < 1 || (int64_t)q.lev0 + q.nlev > d.nlev)
-      return fail("%s: planes[%d]: lev0=%d nlev=%d is no range of levels of field %d, whose axis has %d (lev0 >= 0, nlev >= 1)",
-                  who, k, q.lev0, q.nlev, q.field, d.nlev);
-    if (q.dtype != MCKPP_EXP_F64 && q.dtype != MCKPP_EXP_F32)
-      return fail("%s: planes[%d]: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, k, q.dtype);
+    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, d.nlev)) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem) return -1;
     if (q.op != MCKPP_PUT_SET && q.op != MCKPP_PUT_ADD)
       return fail("%s: planes[%d]: op %d (MCKPP_PUT_SET 0, MCKPP_PUT_ADD 1)", who, k, q.op);
     if (q.flags & ~(MCKPP_PUT_SKIP | MCKPP_PUT_TIME_LEVELS))
@@ -2704,7 +2705,6 @@ int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_pu
     prof[k] = row;
     char arg[32];
     snprintf(arg, sizeof arg, "planes[%d].in", k);
-    const size_t elem = q.dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
     if (!dev_form) {
       if (!q.in) return fail("%s: %s is null", who, arg);
     } else if (dev_ptr_check(h, who, arg, q.in, (size_t)h->npts * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) {
@@ -2725,16 +2725,10 @@ int put_queue(mckpp_hip_ctx *h, const std::vector<mckpp_put_plane> &tab, int max
 {
   if (tab.empty() || h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
-  if (!h->d_put_tab) HIPCHK(h->d_put_tab.alloc(MCKPP_PUT_PLANES));
-  mckpp_put_plane *q = nullptr;
-  HIPCHK(h->h_put_tab.take(MCKPP_PUT_PLANES, &q));
-  std::copy(tab.begin(), tab.end(), q);
-  HIPCHK(hipMemcpyAsync(h->d_put_tab, q, tab.size() * sizeof(mckpp_put_plane), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h->h_put_tab.queued(h->stream));
+  HIPCHK(h->put_tab.put(tab, h->stream));
   if (produced) HIPCHK(hipStreamWaitEvent(h->stream, produced, 0));
-  HIPCHK(mckpp_launch_put_planes(h->d_put_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs, h->stream));
-  if (!h->ev_read) HIPCHK(h->ev_read.create());
-  HIPCHK(hipEventRecord(h->ev_read, h->stream));
+  HIPCHK(mckpp_launch_put_planes(h->put_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs, h->stream));
+  HIPCHK(h->ev_read.record(h->stream));
   return 0;
 }
 
@@ -3189,13 +3183,9 @@ int records_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const 
     size_t i = 0;
     if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
     const auto &w = h->wsched[q.sched];
-    if (q.lev0 < 0 || q.nlev < 1 || (int64_t)q.lev0 + q.nlev > w.nlev[i])
-      return fail("%s: lev0=%d nlev=%d is no range of the levels schedule %d keeps of field %d, which are %d (lev0 >= 0, "
-                  "nlev >= 1)", at, q.lev0, q.nlev, q.sched, q.field, w.nlev[i]);
-    if (q.dtype != MCKPP_EXP_F64 && q.dtype != MCKPP_EXP_F32)
-      return fail("%s: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", at, q.dtype);
-    const size_t elem = q.dtype == MCKPP_EXP_F32 ? sizeof(float) : sizeof(double);
-    if (dev_ptr_check(h, who, arg, q.out, (size_t)w.npoints * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
+    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem || dev_ptr_check(h, who, arg, q.out, (size_t)w.npoints * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
     const size_t nops = (size_t)__builtin_popcount(w.ops[i]), j = (size_t)__builtin_popcount(w.ops[i] & ((1u << q.op) - 1u));
     const size_t n = (size_t)w.nrow * (size_t)w.ld_out[i];
     mckpp_rec_plane e{};
@@ -3241,16 +3231,10 @@ int records_dev_queue(mckpp_hip_ctx *h, rec_planes &r, bool fill, hipEvent_t bef
     }
     xtiles = std::max<int64_t>(xtiles, (e.nrow + 63) / 64 + (e.nnorow + 63) / 64);
   }
-  if (!h->d_rec_tab) HIPCHK(h->d_rec_tab.alloc(MCKPP_DEV_PLANES_MAX));
-  mckpp_rec_plane *q = nullptr;
-  HIPCHK(h->h_rec_tab.take(MCKPP_DEV_PLANES_MAX, &q));
-  std::copy(r.tab.begin(), r.tab.end(), q);
-  HIPCHK(hipMemcpyAsync(h->d_rec_tab, q, r.tab.size() * sizeof(mckpp_rec_plane), hipMemcpyHostToDevice, h->stream));
-  HIPCHK(h->h_rec_tab.queued(h->stream));
+  HIPCHK(h->rec_tab.put(r.tab, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
-  HIPCHK(mckpp_launch_record_planes(h->d_rec_tab, (int)r.tab.size(), r.maxlev, xtiles, h->stream));
-  if (!h->ev_delivered) HIPCHK(h->ev_delivered.create());
-  HIPCHK(hipEventRecord(h->ev_delivered, h->stream));
+  HIPCHK(mckpp_launch_record_planes(h->rec_tab, (int)r.tab.size(), r.maxlev, xtiles, h->stream));
+  HIPCHK(h->ev_delivered.record(h->stream));
   HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
   return 0;
 }

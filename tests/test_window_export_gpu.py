@@ -103,6 +103,21 @@ def test_export_equals_record_fetch_where_the_tiles_can_go_wrong(mk, nz, grid, n
     h.close()
 
 
+def test_one_level_planes_of_more_than_256_columns_narrowed(mk):
+    """321 points, every 40th land: 312 resident columns, 256 and a tail of 56.  The column-per-thread path of a
+    two-dimensional field then takes two workgroups, the second with a tail in its last 64 columns; float32, which the
+    shapes above reach with one workgroup only.  T beside it goes through the tile in five column tiles."""
+    ncol = 321
+    h, kc, k3 = _start(mk, ncol, 40, land_every=40)
+    assert h.ncolumns == 312
+    scheds = _schedule(mk, h, red=("hmix", "T"), last=("hmix", "solar_in"))
+    for s in scheds:
+        h.window_export(s, "f4", LAND)
+    h.run_forced(1, 12, 1)
+    assert _check(h, kc, ncol, scheds, "f4") == 4 * 2 + 3 * 2 * 3
+    h.close()
+
+
 def test_ring_wrap_and_records_cut_by_calls(mk):
     """Calls of 5 + 7 + 12 steps with releases between; the mean/min/max schedule (period 4) has nrec = 3, the "last"
     schedule (period 3) nrec = 4 - the last call completes four of its records, which a ring of three refuses.  A
