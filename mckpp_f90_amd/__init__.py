@@ -38,6 +38,7 @@ from .api import (  # noqa: E402,F401
     MckppHip,
     MckppHipMulti,
     MckppHipError,
+    host_reduce_tree,
     host_shard_mask,
     interp_weights,
     mckpp_initialize_ocean_model,

@@ -21,7 +21,8 @@ self._call(name, ...) - MckppHip and MckppHipMulti then both have it.  The devic
 include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its methods are the mixin _DeviceArrays; so
 have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, and their methods are _WindowSchedules'.  The records of a schedule into device arrays
 (include/mckpp_hip_device_records.h) are the fourth table, _SIGNATURES_RECORDS, and one more method of _DeviceArrays;
-the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _SIGNATURES_PUT, and two more methods there.
+the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _SIGNATURES_PUT, and two more methods there;
+records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixth, _SIGNATURES_REDUCE, and three more.
 """
 import ctypes as C
 import sys
@@ -410,6 +411,22 @@ _SIGNATURES_PUT = {
 }
 
 
+class _ReducePlaneC(C.Structure):
+    """mckpp_reduce_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("sched", "field", "op", "lev0", "nlev", "axis_op", "domain_op", "weighted")] + \
+               [("rec", C.c_int64), ("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_reduce.h, records reduced over levels and points, in the same form;
+# tests/test_reduce_cpu.py holds this table to that header.
+_SIGNATURES_REDUCE = {
+    "mckpp_hip_reduce_weights": _sig(_H, _dp, _dp, _dp, twin=True),
+    "mckpp_hip_records_reduce_dev": _sig(_H, _i32, C.POINTER(_ReducePlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_records_reduce_host": _sig(_H, _i32, C.POINTER(_ReducePlaneC), twin=True),
+    "mckpp_host_reduce_tree": _sig(_dp, _i64, res=_d),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -445,13 +462,18 @@ def _signatures_put():
     return _spelled(_SIGNATURES_PUT)
 
 
+def _signatures_reduce():
+    """... and of every function of mckpp_hip_reduce.h."""
+    return _spelled(_SIGNATURES_REDUCE)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
     # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
     # everything else works with it, and a call of that name fails there by name
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
-                                  **_signatures_records(), **_signatures_put()}.items():
+                                  **_signatures_records(), **_signatures_put(), **_signatures_reduce()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -918,6 +940,27 @@ def _host_plane(a, what, count):
     return a.ctypes.data, typestr
 
 
+# mckpp_hip_records_reduce_dev / _host (MCKPP_RED_* of mckpp_hip_reduce.h): the reductions, the bits of `weighted`
+RED_NONE, RED_SUM, RED_AVERAGE, RED_MIN, RED_MAX = range(5)
+RED_W_LEVELS, RED_W_POINTS = 1, 2
+_RED_OPS = {"none": RED_NONE, "sum": RED_SUM, "average": RED_AVERAGE, "min": RED_MIN, "max": RED_MAX}
+
+
+def _red_op(op):
+    if isinstance(op, str) and op in _RED_OPS:
+        return _RED_OPS[op]
+    if isinstance(op, (int, np.integer)) and not isinstance(op, bool) and 0 <= int(op) <= 4:
+        return int(op)
+    raise ValueError(f"reduction {op!r} (\"none\", \"sum\", \"average\", \"min\", \"max\", or RED_NONE .. RED_MAX)")
+
+
+def host_reduce_tree(terms):
+    """The sum of `terms` in the order the device reduces a domain in (include/mckpp_hip_reduce.h, c): what a run with
+    one process per GPU calls on its gathered terms to get the double a single handle delivers.  No GPU."""
+    a = np.ascontiguousarray(terms, dtype=np.float64).ravel()
+    return float(_lib().mckpp_host_reduce_tree(a.ctypes.data_as(_dp), a.size))
+
+
 class _DeviceArrays:
     """The device-array interface (include/mckpp_hip_device.h): forcing from arrays in device memory, output fields into
     them, ordered by events on the caller's stream and never by a host wait.  Arrays handed to fluxes_dev or
@@ -1092,6 +1135,91 @@ class _DeviceArrays:
         """put_dev from numpy arrays of float64 or float32, shape (nlev, npts); returns when the state is written."""
         n, arr = self._put_table("put_host", planes, op, time_levels, skip, _host_plane)
         self._call("put_host", n, arr)
+
+    def reduce_weights(self, point_w=None, level_w=None, iface_w=None):
+        """The weights of records_reduce_dev / _host (include/mckpp_hip_reduce.h): point_w, npts values by point number
+        of the 3-D ordering; level_w, nzp1 values for fields on the level axis (hm, for a heat content); iface_w, nzp1
+        for fields on the interface axis.  None: not set; a call replaces all three.  Every weight is finite and >= 0.
+        The handle keeps them until they are replaced: upload and load_restart leave them alone."""
+        ptrs = []
+        for name, w, n in (("point_w", point_w, self._npts), ("level_w", level_w, self._nzp1), ("iface_w", iface_w, self._nzp1)):
+            if w is None:
+                ptrs.append(None)
+                continue
+            a = np.ascontiguousarray(w, dtype=np.float64)
+            if a.ndim != 1 or a.size != n:
+                raise ValueError(f"reduce_weights: {name} has shape {a.shape}, the call takes {n} values")
+            ptrs.append(a)
+        self._call("reduce_weights", *[None if a is None else a.ctypes.data_as(_dp) for a in ptrs])
+
+    def _reduce_table(self, who, planes, land_value, array):
+        """the planes of records_reduce_dev / _host as the table the library takes, after every check that needs no
+        library; array(a, what, count) -> address is the form's own check of a plane's result array"""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"{who}: {len(planes)} planes, at most 64 in one call")
+        arr = (_ReducePlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            at = f"{who}: planes[{k}]"
+            if len(p) not in (7, 8, 10):
+                raise ValueError(f"{at} is (sched, rec, field, op, out, axis_op, domain_op[, weighted[, lev0, nlev]])")
+            sched, rec, op, out = int(p[0]), int(p[1]), int(p[3]), p[4]
+            try:
+                f = _win_check_fetch(self._scheds(), sched, p[2], op)
+                axis_op, domain_op = _red_op(p[5]), _red_op(p[6])
+            except ValueError as e:
+                raise ValueError(f"{at}: {e}") from None
+            if rec < 0:
+                raise ValueError(f"{at}: record {rec}")
+            if axis_op == RED_NONE and domain_op == RED_NONE:
+                raise ValueError(f"{at}: axis_op and domain_op are both none: a plane that is not reduced is records_dev's")
+            weighted = int(p[7]) if len(p) > 7 else 0
+            if weighted & ~3:
+                raise ValueError(f"{at}: weighted {weighted} (RED_W_LEVELS 1, RED_W_POINTS 2)")
+            zoom = self._scheds()[sched].zoom
+            n, axis = zoom if zoom is not None else (self._npts, self._nzp1)
+            if f in _OUT_2D:
+                axis = 1
+            lev0, nlev = (int(p[8]), int(p[9])) if len(p) == 10 else (0, axis)
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > axis:
+                raise ValueError(f"{at}: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, of which output "
+                                 f"schedule {sched} keeps {axis}")
+            count = n if domain_op == RED_NONE else nlev if axis_op == RED_NONE else 1
+            arr[k] = _ReducePlaneC(sched, f, op, lev0, nlev, axis_op, domain_op, weighted, rec, float(land_value),
+                                   array(out, f"{at} out", count))
+        return len(planes), arr
+
+    def records_reduce_dev(self, planes, stream=None, land_value=1e20):
+        """Completed records of output schedules reduced over their levels, their points or both, into device arrays
+        (include/mckpp_hip_reduce.h states the arithmetic and its order); ordered like records_dev: `stream` waits for
+        the delivery on the device, window_record_release and the next launch may follow at once.  A plane is (sched,
+        rec, field, op, out, axis_op, domain_op[, weighted[, lev0, nlev]]): the plane records_dev names by sched, rec,
+        field, op, lev0, nlev - default: every level the schedule keeps -, reduced by axis_op over its levels and by
+        domain_op over its points ("none", "sum", "average", "min", "max" or RED_*; not both none), with the weights of
+        reduce_weights where `weighted` has RED_W_LEVELS / RED_W_POINTS.  out: float64 in device memory - npoints
+        elements (domain_op none), nlev (axis_op none), or one.  land_value: what an element without a row, or an
+        average without weight, is."""
+        held = []
+
+        def array(a, what, count):
+            held.append(a)
+            return _dev_array(a, what, count)[0]
+
+        n, arr = self._reduce_table("records_reduce_dev", planes, land_value, array)
+        for a in held:
+            self._hold_dev(a)
+        self._call("records_reduce_dev", n, arr, _dev_stream(stream))
+
+    def records_reduce_host(self, planes, land_value=1e20):
+        """records_reduce_dev into numpy arrays of float64; returns when they hold the results."""
+        def array(a, what, count):
+            ptr, typestr = _host_plane(a, what, count)
+            if typestr != "<f8":
+                raise ValueError(f"{what}: element type {typestr}, the call takes <f8")
+            return ptr
+
+        n, arr = self._reduce_table("records_reduce_host", planes, land_value, array)
+        self._call("records_reduce_host", n, arr)
 
     def dev_fence(self, stream=None):
         """`stream` waits, on the device, for every read of caller arrays this handle has queued so far."""

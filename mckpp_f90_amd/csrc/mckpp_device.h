@@ -261,6 +261,33 @@ struct mckpp_rec_plane {
 // all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane; xtiles: the most 64-entry tiles
 // of a plane, rows and - where it fills - non-row positions together
 hipError_t mckpp_launch_record_planes(const mckpp_rec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream);
+// One plane of mckpp_hip_records_reduce_dev / _host (include/mckpp_hip_reduce.h states the arithmetic; k_reduce_fill,
+// k_reduce_terms, k_reduce_halve, k_reduce_finish): mckpp_rec_plane's rows and geometry, reduced.  axis_op / domain_op:
+// MCKPP_RED_*.  wl: the level weights of elements off .. off + nlev - 1 (null: 1.0), wsum their sum W in ascending
+// order ((double)nlev without weights), formed by the host; wp: the point weights by point number (null: 1.0), point:
+// row -> point number.  A domain-reduced plane sends its terms through `terms`: nslab slabs of n2 doubles - n2 the
+// smallest power of two >= the points of the plane's axis -, one per level (one in all behind an axis reduction), and behind them, for an
+// average, the slab of the denominator's terms.  `terms` is shard 0's block and `out` the one array under a multi
+// handle; fill: this context writes what no row does - the slabs' padding and non-row terms, and land_value at the
+// nnorow positions of an axis-only plane.  norows: no shard has a row, every element is land_value.
+enum { RED_NONE = 0, RED_SUM, RED_AVERAGE, RED_MIN, RED_MAX };   // MCKPP_RED_* of the header
+struct mckpp_red_plane {
+  const double *src;
+  double *out, *terms;
+  const int *map, *point, *norow;
+  const double *wl, *wp;
+  double period, land_value, wsum;
+  long long nrow, nnorow, n2;
+  int ld, off, nlev, mean, axis_op, domain_op, nslab, fill, norows;
+};
+// Most partials of a plane's tree that one workgroup finishes (k_reduce_finish's LDS); the launches take m, a power of
+// two 64 .. MCKPP_RED_M: the tree of a slab of more than m terms is halved down to m in place first (k_reduce_halve).
+#define MCKPP_RED_M 1024
+// one kernel (`phase`) over all `nplanes` planes of the device table `tab`; maxlev: the most results of a domain-reduced
+// plane, maxslab: the most slabs, xtiles: the most 64-row tiles of a plane
+hipError_t mckpp_launch_reduce(const mckpp_red_plane *tab, int nplanes, int phase, int maxlev, int maxslab, int64_t xtiles,
+                               int m, hipStream_t stream);
+enum { MCKPP_RED_PHASE_FILL = 0, MCKPP_RED_PHASE_TERMS, MCKPP_RED_PHASE_HALVE, MCKPP_RED_PHASE_FINISH };
 // One plane of mckpp_hip_put_dev / _put_host (k_put_planes), mckpp_fetch_plane turned round: in(npts, nlev), doubles or
 // (f32) floats, is set into (add: added to) elements off .. off + nlev - 1 of the rows [ncol][ld] at row; sub_sref: a
 // set writes the value minus the column's Sref; skip: a value == skip_value leaves its element alone; lv0 / lv1: the

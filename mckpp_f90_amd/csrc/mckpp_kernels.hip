@@ -459,7 +459,175 @@ __global__ __launch_bounds__(256) void k_put_planes(const mckpp_put_plane *__res
   else tile_points_to_rows<true>(tile, ncol, e.nlev, l0, ipt, npts, static_cast<const double *>(e.in), put);
 }
 
+// ---------------------------------------------------------------------------
+// Records reduced over levels and points (mckpp_hip_records_reduce_dev / _host).  include/mckpp_hip_reduce.h states the
+// arithmetic and its order; the four kernels below are that statement, each one launch for all planes of a call
+// (blockIdx.z, the table of mckpp_red_plane).  No atomics: every element of `terms` and of `out` has one writer per
+// kernel, and the order of a sum does not depend on the grid.
+//
+//   k_reduce_fill    what no row writes: a slab's non-row terms and padding (+0.0; +-infinity for min / max), the
+//                    land value of an axis-only plane's non-row positions
+//   k_reduce_terms   64 rows per workgroup, their levels through the relayout tile 64 at a time, so the ring rows are
+//                    read as whole 512-B segments whatever the plane reduces (a plane of one level: a row per thread): an axis reduction continues down the
+//                    level tiles on the row's own thread in ascending order; a domain-only plane writes its level
+//                    slabs points fastest.  Result to `out` (axis only) or, times the point weight, to the slab
+//   k_reduce_halve   a slab of n2 > m terms halved in place down to m: thread j owns the elements j, j + m, ... - the
+//                    steps t[i] = t[i] + t[i + n], n >= m, never leave a residue, so no thread reads another's
+//   k_reduce_finish  the last m (or n2) terms of a level's slab - and of the denominator's - through LDS: the same
+//                    halving steps with a barrier between, then the division and the one store
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double red_combine(int op, double a, double b)   // t[i] and t[i + n]
+{
+  if (op == RED_MIN) return b < a ? b : a;
+  if (op == RED_MAX) return b > a ? b : a;
+  return a + b;
+}
+
+__global__ __launch_bounds__(256) void k_reduce_fill(const mckpp_red_plane *__restrict__ tab)
+{
+  const mckpp_red_plane e = tab[blockIdx.z];
+  if (!e.fill) return;
+  const int64_t i0 = (int64_t)blockIdx.x * 256 + threadIdx.x, step = (int64_t)gridDim.x * 256;
+  if (e.domain_op == RED_NONE) {
+    for (int64_t i = i0; i < e.nnorow; i += step) e.out[e.norow[i]] = e.land_value;
+    return;
+  }
+  const int64_t all = (int64_t)e.nslab * e.n2, valued = e.domain_op == RED_AVERAGE ? all - e.n2 : all;
+  const double id = e.domain_op == RED_MIN ? __builtin_inf() : e.domain_op == RED_MAX ? -__builtin_inf() : 0.0;
+  for (int64_t i = i0; i < all; i += step) e.terms[i] = i < valued ? id : 0.0;
+}
+
+__global__ __launch_bounds__(256) void k_reduce_terms(const mckpp_red_plane *__restrict__ tab)
+{
+  __shared__ double tile[64][65];
+  const mckpp_red_plane e = tab[blockIdx.z];
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  if (r0 >= e.nrow) return;   // (the grid's row tiles are those of the plane with most rows)
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int64_t r = r0 + tx;
+  const bool mine = r < e.nrow;   // on the point side, tx is a row
+  const int64_t pos = mine ? (int64_t)e.map[r] : 0;
+  const double wp = mine && e.wp ? e.wp[e.point[r]] : 1.0;
+  double a = 0.0;
+  if (e.nlev == 1) {   // one level: nothing to transpose, a row per thread of the first wave, no barrier on this path
+    if (ty != 0 || !mine) return;
+    double x = e.src[r * e.ld + e.off];
+    if (e.mean) x = x / e.period;
+    if (e.axis_op == RED_NONE) e.terms[pos] = e.domain_op <= RED_AVERAGE ? wp * x : x;
+    else a = e.axis_op <= RED_AVERAGE && e.wl ? e.wl[0] * x : x;
+  }
+  for (int l0 = 0; e.nlev > 1 && l0 < e.nlev; l0 += 64) {
+    for (int rr = ty; rr < 64; rr += 4) {       // read: levels fastest
+      const int64_t q = r0 + rr;
+      const int lev = l0 + tx;
+      double v = 0.0;
+      if (q < e.nrow && lev < e.nlev) {
+        v = e.src[q * e.ld + e.off + lev];
+        if (e.mean) v = v / e.period;
+      }
+      tile[tx][rr] = v;
+    }
+    __syncthreads();
+    if (e.axis_op == RED_NONE) {
+      if (mine)
+        for (int l = ty; l < 64; l += 4)        // write: points fastest
+          if (l0 + l < e.nlev) {
+            const double x = tile[l][tx];
+            e.terms[(int64_t)(l0 + l) * e.n2 + pos] = e.domain_op <= RED_AVERAGE ? wp * x : x;
+          }
+    } else if (ty == 0 && mine) {               // the row's levels of this tile, ascending
+      const int n = e.nlev - l0 < 64 ? e.nlev - l0 : 64;
+      for (int l = 0; l < n; ++l) {
+        const double x = tile[l][tx];
+        if (e.axis_op <= RED_AVERAGE) {
+          const double t = e.wl ? e.wl[l0 + l] * x : x;
+          a = l0 + l == 0 ? t : a + t;
+        } else if (e.axis_op == RED_MIN) {
+          a = l0 + l == 0 ? x : (x < a ? x : a);
+        } else {
+          a = l0 + l == 0 ? x : (x > a ? x : a);
+        }
+      }
+    }
+    __syncthreads();   // (the next level tile overwrites this one)
+  }
+  if (ty != 0 || !mine) return;
+  if (e.domain_op == RED_AVERAGE) e.terms[(int64_t)(e.nslab - 1) * e.n2 + pos] = wp;
+  if (e.axis_op == RED_NONE) return;
+  if (e.axis_op == RED_AVERAGE) a = e.wsum == 0.0 ? e.land_value : a / e.wsum;
+  if (e.domain_op == RED_NONE) e.out[pos] = a;
+  else e.terms[pos] = e.domain_op <= RED_AVERAGE ? wp * a : a;
+}
+
+__global__ __launch_bounds__(256) void k_reduce_halve(const mckpp_red_plane *__restrict__ tab, int m)
+{
+  const mckpp_red_plane e = tab[blockIdx.z];
+  if (e.domain_op == RED_NONE || (int)blockIdx.y >= e.nslab || e.n2 <= m) return;
+  double *t = e.terms + (int64_t)blockIdx.y * e.n2;
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;   // < m
+  // A step's elements are independent of one another; eight of a thread's are loaded before any is stored, so the
+  // thread waits for memory once per eight, not once per element (the compiler may not reorder them: t aliases itself).
+  for (int64_t n = e.n2 >> 1; n >= m; n >>= 1) {
+    int64_t i = j;
+    for (; i + 7 * (int64_t)m < n; i += 8 * (int64_t)m) {
+      double a[8], b[8];
+#pragma unroll
+      for (int u = 0; u < 8; ++u) { a[u] = t[i + u * (int64_t)m]; b[u] = t[i + u * (int64_t)m + n]; }
+#pragma unroll
+      for (int u = 0; u < 8; ++u) t[i + u * (int64_t)m] = red_combine(e.domain_op, a[u], b[u]);
+    }
+    for (; i < n; i += m) t[i] = red_combine(e.domain_op, t[i], t[i + n]);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_reduce_finish(const mckpp_red_plane *__restrict__ tab, int m)
+{
+  __shared__ double sh[2][MCKPP_RED_M];
+  const mckpp_red_plane e = tab[blockIdx.z];
+  if (e.domain_op == RED_NONE || (int)blockIdx.x >= (e.axis_op == RED_NONE ? e.nlev : 1)) return;
+  if (e.norows) {
+    if (threadIdx.x == 0) e.out[blockIdx.x] = e.land_value;
+    return;
+  }
+  const bool avg = e.domain_op == RED_AVERAGE;
+  const int n0 = (int)(e.n2 < m ? e.n2 : m);
+  const double *t = e.terms + (int64_t)blockIdx.x * e.n2, *w = e.terms + (int64_t)(e.nslab - 1) * e.n2;
+  for (int i = threadIdx.x; i < n0; i += 256) {
+    sh[0][i] = t[i];
+    if (avg) sh[1][i] = w[i];
+  }
+  __syncthreads();
+  for (int n = n0 >> 1; n >= 1; n >>= 1) {      // (the barriers of a workgroup depend on the plane alone)
+    for (int i = threadIdx.x; i < n; i += 256) {
+      sh[0][i] = red_combine(e.domain_op, sh[0][i], sh[0][i + n]);
+      if (avg) sh[1][i] = sh[1][i] + sh[1][i + n];
+    }
+    __syncthreads();
+  }
+  if (threadIdx.x != 0) return;
+  double v = sh[0][0];
+  if (avg) v = sh[1][0] == 0.0 ? e.land_value : v / sh[1][0];
+  e.out[blockIdx.x] = v;
+}
+
 }  // namespace
+
+hipError_t mckpp_launch_reduce(const mckpp_red_plane *tab, int nplanes, int phase, int maxlev, int maxslab, int64_t xtiles,
+                               int m, hipStream_t stream)
+{
+  if (nplanes <= 0) return hipSuccess;
+  const unsigned z = (unsigned)nplanes;
+  if (phase == MCKPP_RED_PHASE_FILL)
+    hipLaunchKernelGGL(k_reduce_fill, dim3(256, 1, z), dim3(256), 0, stream, tab);
+  else if (phase == MCKPP_RED_PHASE_TERMS && xtiles > 0)
+    hipLaunchKernelGGL(k_reduce_terms, dim3((unsigned)xtiles, 1, z), dim3(256), 0, stream, tab);
+  else if (phase == MCKPP_RED_PHASE_HALVE && maxslab > 0)
+    hipLaunchKernelGGL(k_reduce_halve, dim3((unsigned)(m / 256 > 0 ? m / 256 : 1), (unsigned)maxslab, z), dim3(m < 256 ? m : 256), 0,
+                       stream, tab, m);
+  else if (phase == MCKPP_RED_PHASE_FINISH && maxlev > 0)
+    hipLaunchKernelGGL(k_reduce_finish, dim3((unsigned)maxlev, 1, z), dim3(256), 0, stream, tab, m);
+  return hipGetLastError();
+}
 
 hipError_t mckpp_launch_put_planes(const mckpp_put_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
                                    int64_t npts, double *cs, hipStream_t stream)

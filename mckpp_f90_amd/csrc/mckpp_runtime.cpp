@@ -17,6 +17,7 @@
 #include "../../include/mckpp_hip_zoom.h"
 #include "../../include/mckpp_hip_device_records.h"
 #include "../../include/mckpp_hip_put.h"
+#include "../../include/mckpp_hip_reduce.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -101,6 +102,7 @@ struct mckpp_ctx_resident {
     std::vector<int> nlev, lev_off;
     std::vector<int> rowpos;           // listed: row -> list position
     dev_buf<int> d_rowpos, d_colrow;   // listed: rowpos; resident column -> row, -1 outside the list (mckpp_win_t::row)
+    dev_buf<int> d_rowpt;              // listed: row -> point number, where the reductions look a row's point weight up
     // listed: the list positions that are no row, for the planes of mckpp_hip_records_dev that fill them (an unlisted
     // schedule's are the context's d_land).  norow is this context's own, set with the schedule; d_norow holds nnorow
     // positions: norow itself (norow_kind 1), or - shard 0 of a multi handle - those no shard has a row for, the other
@@ -251,6 +253,22 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   plane_table<mckpp_fetch_plane, MCKPP_FETCH_PLANES> fetch_tab;
   plane_table<mckpp_rec_plane, MCKPP_DEV_PLANES_MAX> rec_tab;
   plane_table<mckpp_put_plane, MCKPP_PUT_PLANES> put_tab;
+  // Records reduced over levels and points (include/mckpp_hip_reduce.h).  The weights are indexed by point and by
+  // level, not by resident column, so they live as long as the context and no upload touches them: on the device
+  // (empty: not set), the two level arrays on the host too, where a plane's W is summed.  The scratch of the
+  // reductions, each block grow-only: the slabs of terms (under a multi handle shard 0's serves every shard), and for
+  // the host form the results on the device and the pinned block they are copied through.  m: the terms a workgroup
+  // finishes (MCKPP_RED_M; MCKPP_REDUCE_M, tests: the halving pass on small planes).  ev_fill / ev_terms: behind shard
+  // 0's fill, which the other shards' terms wait for, and behind a shard's terms, which shard 0's tree waits for.
+  struct reduce_state {
+    dev_buf<double> d_wp, d_wl, d_wi;
+    std::vector<double> wl, wi;
+    dev_buf<double> d_terms, d_out;
+    pinned_buf<double> h_out;
+    hip_event ev_fill, ev_terms;
+    int m = MCKPP_RED_M;
+  } red;
+  plane_table<mckpp_red_plane, MCKPP_DEV_PLANES_MAX> red_tab;
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -436,6 +454,10 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
     h->l2pre = (nref >= 16 && !c->LDD) ? 1 : 0;
     if (const char *e = getenv("MCKPP_L2PRE")) h->l2pre = (atoi(e) != 0 && !c->LDD) ? 1 : 0;
     if (const char *e = getenv("MCKPP_L3_CAP")) h->l3cap = atoi(e) > 0 ? atoi(e) : 0;
+    if (const char *e = getenv("MCKPP_REDUCE_M")) {   // a power of two 64 .. MCKPP_RED_M, else the default
+      const int v = atoi(e);
+      if (v >= 64 && v <= MCKPP_RED_M && (v & (v - 1)) == 0) h->red.m = v;
+    }
     // the guesses L3 works from (profiles/r06: the margins' sweep).  MCKPP_FIRST_GUESS=0 is the rule before them: every
     // level in a column's first pass, the scan's end plus eight after it (A/B runs, tests)
     if (const char *e = getenv("MCKPP_FIRST_MARGIN")) h->first_margin = std::min(std::max(0, atoi(e)), 0xffff);
@@ -2961,6 +2983,11 @@ static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, 
       if (e == hipSuccess) e = hipMemcpy(w.d_colrow, colrow.data(), colrow.size() * sizeof(int), hipMemcpyHostToDevice);
       if (e == hipSuccess && w.nrow > 0) e = w.d_rowpos.alloc(rowpos.size());
       if (e == hipSuccess && w.nrow > 0) e = hipMemcpy(w.d_rowpos, rowpos.data(), rowpos.size() * sizeof(int), hipMemcpyHostToDevice);
+      std::vector<int> rowpt;
+      for (int p : rowpos) rowpt.push_back(zoom->points[p]);
+      bytes += rowpt.size() * sizeof(int);
+      if (e == hipSuccess && w.nrow > 0) e = w.d_rowpt.alloc(rowpt.size());
+      if (e == hipSuccess && w.nrow > 0) e = hipMemcpy(w.d_rowpt, rowpt.data(), rowpt.size() * sizeof(int), hipMemcpyHostToDevice);
     }
     if (e == hipSuccess && !norow.empty()) {
       bytes += norow.size() * sizeof(int);
@@ -3014,7 +3041,7 @@ int mckpp_hip_window_schedule_zoom(mckpp_hip_handle h, int sched, int nt_origin,
   });
 }
 
-// the device bytes of a schedule's record ring (without its export and without the zoom's three small tables)
+// the device bytes of a schedule's record ring (without its export and without the small tables of a point list)
 static int64_t win_ring_bytes(const mckpp_hip_ctx::win_sched &w)
 {
   int64_t b = 0;
@@ -3057,6 +3084,14 @@ int mckpp_host_zoom_box(int64_t nx, int64_t ny, int64_t ibegin, int64_t ni, int6
 // row -> position on the record's point axis: on the device, and on the host
 static const int *win_map(const mckpp_hip_ctx *h, const mckpp_hip_ctx::win_sched &w) { return w.listed ? w.d_rowpos.get() : h->d_ipt.get(); }
 static const std::vector<int> &win_host_map(const mckpp_hip_ctx *h, const mckpp_hip_ctx::win_sched &w) { return w.listed ? w.rowpos : h->ipt; }
+
+// the rows [nrow][ld_out] of operation `op` of field i of the schedule in the ring slot of record `rec` (no row: null)
+static const double *win_plane_rows(const mckpp_hip_ctx::win_sched &w, size_t i, int64_t rec, int op)
+{
+  const size_t nops = (size_t)__builtin_popcount(w.ops[i]), j = (size_t)__builtin_popcount(w.ops[i] & ((1u << op) - 1u));
+  const size_t n = (size_t)w.nrow * (size_t)w.ld_out[i];
+  return w.nrow > 0 ? w.acc[i] + ((size_t)(rec % w.nrec) * nops + j) * n : nullptr;
+}
 
 // may record `rec` of the schedule be fetched - all of it (plane false), or its plane of `field` and `op`, whose index
 // among the schedule's fields comes back in *fi?  Otherwise an error that names the record's steps.
@@ -3101,8 +3136,7 @@ static int win_record(mckpp_hip_ctx *h, const char *who, int sched, int64_t rec,
   if (w.nrow == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
   const size_t n = (size_t)w.nrow * w.ld_out[i];
-  const int j = __builtin_popcount(w.ops[i] & ((1u << op) - 1u));
-  const double *src = w.acc[i] + ((size_t)(rec % w.nrec) * (size_t)__builtin_popcount(w.ops[i]) + (size_t)j) * n;
+  const double *src = win_plane_rows(w, i, rec, op);
   if (op == 0) {   // the mean: window_fetch's sum / count, the count a whole window's
     if (ensure_stage(h, n)) return -1;
     HIPCHK(mckpp_launch_window_mean(src, h->d_stage, n, (double)w.period, h->stream));
@@ -3186,10 +3220,8 @@ int records_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const 
     if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
     const size_t elem = plane_elem(who, k, q.dtype);
     if (!elem || dev_ptr_check(h, who, arg, q.out, (size_t)w.npoints * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
-    const size_t nops = (size_t)__builtin_popcount(w.ops[i]), j = (size_t)__builtin_popcount(w.ops[i] & ((1u << q.op) - 1u));
-    const size_t n = (size_t)w.nrow * (size_t)w.ld_out[i];
     mckpp_rec_plane e{};
-    e.src = w.nrow > 0 ? w.acc[i] + ((size_t)(q.rec % w.nrec) * nops + j) * n : nullptr;
+    e.src = win_plane_rows(w, i, q.rec, q.op);
     e.out = q.out;
     e.map = win_map(h, w);
     e.period = (double)w.period; e.land_value = q.land_value;
@@ -3255,6 +3287,269 @@ int mckpp_hip_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_r
   if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
   return records_dev_queue(h, r, true, h->ev_caller, consumer_stream);
   });
+}
+
+// ---------------------------------------------------------------------------
+// Records reduced over levels and points (include/mckpp_hip_reduce.h, which states the arithmetic).  A plane is resolved
+// by the code that resolves a plane of mckpp_hip_records_dev; as there, a check that queues nothing and a part that
+// queues.  Four launches on the context's stream - fill, terms, halve, finish (mckpp_kernels.hip) - and no host wait in
+// the device form.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// the planes of a reduction resolved into the kernel's table, but for the blocks of the queueing context: [plane] its
+// schedule, where its slabs begin in the block of terms, where its results do in the host form's block, their number
+struct red_planes {
+  std::vector<mckpp_red_plane> tab;
+  std::vector<int> sched;
+  std::vector<size_t> terms_off, out_off, nout;
+  std::vector<void *> host_out;
+  size_t terms = 0, outs = 0;
+  int maxout = 0, maxslab = 0;
+  int64_t xtiles = 0;
+  bool halve = false, domain = false;
+};
+
+// fields whose axis is the interfaces 0 .. nz (the others with an axis are on the levels 1 .. nzp1)
+bool on_interfaces(int f)
+{
+  switch (f) {
+    case MCKPP_OUT_WU: case MCKPP_OUT_WV: case MCKPP_OUT_WT: case MCKPP_OUT_WS: case MCKPP_OUT_WB: case MCKPP_OUT_WTNT:
+    case MCKPP_OUT_DIFM: case MCKPP_OUT_DIFT: case MCKPP_OUT_DIFS: return true;
+    default: return false;
+  }
+}
+
+int reduce_weights_check(const char *who, const char *name, const double *w, int64_t n)
+{
+  for (int64_t i = 0; w && i < n; ++i)
+    if (!(w[i] >= 0.0) || !std::isfinite(w[i]))
+      return fail("%s: %s[%lld] = %g: every weight must be finite and >= 0", who, name, (long long)i, w[i]);
+  return 0;
+}
+
+int reduce_weights_set(mckpp_hip_ctx *h, const char *who, const double *point_w, const double *level_w, const double *iface_w)
+{
+  if (h->npts <= 0) return fail("%s: upload the state first (point_w is sized to the grid's points)", who);
+  if (reduce_weights_check(who, "point_w", point_w, h->npts) || reduce_weights_check(who, "level_w", level_w, h->nzp1) ||
+      reduce_weights_check(who, "iface_w", iface_w, h->nzp1))
+    return -1;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(hipStreamSynchronize(h->stream));   // a reduction in flight may read the weights in place
+  auto &s = h->red;
+  auto set = [](dev_buf<double> &d, const double *w, size_t n) -> hipError_t {
+    if (!w) { d.reset(); return hipSuccess; }
+    const hipError_t e = d.size() == n ? hipSuccess : d.alloc(n);
+    return e == hipSuccess ? hipMemcpy(d, w, n * sizeof(double), hipMemcpyHostToDevice) : e;
+  };
+  HIPCHK(set(s.d_wp, point_w, (size_t)h->npts));
+  HIPCHK(set(s.d_wl, level_w, (size_t)h->nzp1));
+  HIPCHK(set(s.d_wi, iface_w, (size_t)h->nzp1));
+  s.wl.assign(level_w, level_w ? level_w + h->nzp1 : level_w);
+  s.wi.assign(iface_w, iface_w ? iface_w + h->nzp1 : iface_w);
+  return 0;
+}
+
+const char *const red_op_names = "0 none, 1 sum, 2 average, 3 min, 4 max";
+
+// dev: `out` is device memory, checked as mckpp_hip_records_dev checks it; otherwise host memory, refused if null
+int reduce_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
+                 red_planes &r, int *dev)
+{
+  if (nplanes < 0 || nplanes > MCKPP_DEV_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_DEV_PLANES_MAX);
+  HIPCHK(hipSetDevice(h->device));
+  r = red_planes{};
+  const auto &s = h->red;
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_reduce_plane_c &q = planes[k];
+    char at[96], arg[32];
+    snprintf(at, sizeof at, "%s: planes[%d]", who, k);
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    size_t i = 0;
+    if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
+    const auto &w = h->wsched[q.sched];
+    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
+    if (q.axis_op < 0 || q.axis_op > 4) return fail("%s: axis_op %d (%s)", at, q.axis_op, red_op_names);
+    if (q.domain_op < 0 || q.domain_op > 4) return fail("%s: domain_op %d (%s)", at, q.domain_op, red_op_names);
+    if (q.axis_op == 0 && q.domain_op == 0)
+      return fail("%s: axis_op and domain_op are both 0 (none): a plane that is not reduced is mckpp_hip_records_dev's", at);
+    if (q.weighted & ~3) return fail("%s: weighted 0x%x (bit 0: level weights, bit 1: point weights)", at, q.weighted);
+    const double *wl = nullptr, *wp = nullptr;
+    double wsum = (double)q.nlev;
+    if (q.weighted & MCKPP_RED_W_LEVELS) {
+      if (q.axis_op != MCKPP_RED_SUM && q.axis_op != MCKPP_RED_AVERAGE)
+        return fail("%s: weighted bit 0 (level weights) with axis_op %d, a reduction that takes no weights (%s)", at, q.axis_op,
+                    red_op_names);
+      out_desc d;
+      if (out_field(h, q.field, d)) return -1;
+      if (d.nlev == 1) return fail("%s: weighted bit 0 (level weights), but field %d is two-dimensional", at, q.field);
+      const bool iface = on_interfaces(q.field);
+      const auto &hw = iface ? s.wi : s.wl;
+      if (hw.empty())
+        return fail("%s: weighted bit 0 (level weights), but no %s is set (mckpp_hip_reduce_weights; field %d is on the %s axis)", at,
+                    iface ? "iface_w" : "level_w", q.field, iface ? "interface" : "level");
+      const int first = w.lev_off[i] + q.lev0;
+      wl = (iface ? s.d_wi.get() : s.d_wl.get()) + first;
+      wsum = hw[(size_t)first];
+      for (int l = 1; l < q.nlev; ++l) wsum = wsum + hw[(size_t)(first + l)];
+    }
+    if (q.weighted & MCKPP_RED_W_POINTS) {
+      if (q.domain_op != MCKPP_RED_SUM && q.domain_op != MCKPP_RED_AVERAGE)
+        return fail("%s: weighted bit 1 (point weights) with domain_op %d, a reduction that takes no weights (%s)", at, q.domain_op,
+                    red_op_names);
+      if (!s.d_wp) return fail("%s: weighted bit 1 (point weights), but no point_w is set (mckpp_hip_reduce_weights)", at);
+      if ((int64_t)s.d_wp.size() != h->npts)
+        return fail("%s: weighted bit 1 (point weights): point_w was set for %zu points, the grid has %lld", at, s.d_wp.size(),
+                    (long long)h->npts);
+      wp = s.d_wp;
+    }
+    const size_t nout = q.domain_op == 0 ? (size_t)w.npoints : q.axis_op == 0 ? (size_t)q.nlev : 1;
+    if (!dev_form && !q.out) return fail("%s: %s is null", who, arg);
+    if (dev_form && dev_ptr_check(h, who, arg, q.out, nout * sizeof(double), k == 0 ? dev : nullptr)) return -1;
+    mckpp_red_plane e{};
+    e.src = win_plane_rows(w, i, q.rec, q.op);
+    e.out = static_cast<double *>(q.out);
+    e.map = win_map(h, w);
+    e.point = w.listed ? w.d_rowpt.get() : h->d_ipt.get();
+    e.wl = wl; e.wp = wp;
+    e.period = (double)w.period; e.land_value = q.land_value; e.wsum = wsum;
+    e.nrow = w.nrow;
+    e.n2 = 1;
+    while (e.n2 < w.npoints) e.n2 *= 2;
+    e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
+    e.mean = q.op == 0; e.axis_op = q.axis_op; e.domain_op = q.domain_op;
+    e.nslab = q.domain_op == 0 ? 0 : (q.axis_op == 0 ? q.nlev : 1) + (q.domain_op == MCKPP_RED_AVERAGE ? 1 : 0);
+    r.tab.push_back(e);
+    r.sched.push_back(q.sched);
+    r.terms_off.push_back(r.terms);
+    r.out_off.push_back(r.outs);
+    r.nout.push_back(nout);
+    r.host_out.push_back(q.out);
+    r.terms += (size_t)e.nslab * (size_t)e.n2;
+    r.outs += nout;
+    r.maxslab = std::max(r.maxslab, e.nslab);
+    if (q.domain_op != 0) r.maxout = std::max(r.maxout, (int)nout);
+    r.xtiles = std::max<int64_t>(r.xtiles, (e.nrow + 63) / 64);
+    r.domain = r.domain || q.domain_op != 0;
+    r.halve = r.halve || (q.domain_op != 0 && e.n2 > h->red.m);
+  }
+  return 0;
+}
+
+// the blocks of `owner` (this context, or shard 0 of its multi handle) with room for the call; a block that grows may
+// still be read by a reduction in flight, and everything that touches one is ordered on the owner's stream
+int reduce_reserve(mckpp_hip_ctx *owner, const red_planes &r, bool dev_form)
+{
+  auto &s = owner->red;
+  const size_t outs = dev_form ? 0 : r.outs;
+  if (r.terms <= s.d_terms.size() && outs <= s.d_out.size()) return 0;
+  HIPCHK(hipSetDevice(owner->device));
+  HIPCHK(hipStreamSynchronize(owner->stream));
+  HIPCHK(s.d_terms.reserve(r.terms));
+  HIPCHK(s.d_out.reserve(outs));
+  HIPCHK(s.h_out.reserve(outs));
+  return 0;
+}
+
+// the table's blocks and lists: fill - this context writes what no row does; rows[k]: the rows all shards hold of plane k
+int reduce_bind(mckpp_hip_ctx *h, mckpp_hip_ctx *owner, red_planes &r, bool dev_form, bool fill, const std::vector<int64_t> &rows)
+{
+  for (size_t k = 0; k < r.tab.size(); ++k) {
+    mckpp_red_plane &e = r.tab[k];
+    const auto &w = h->wsched[r.sched[k]];
+    e.terms = owner->red.d_terms.get() + r.terms_off[k];
+    if (!dev_form) e.out = owner->red.d_out.get() + r.out_off[k];
+    e.fill = fill;
+    e.norows = rows[k] == 0;
+    if (fill && e.domain_op == 0) {
+      if (w.listed) { e.norow = w.d_norow; e.nnorow = w.nnorow; }
+      else {
+        if (land_own(h)) return -1;
+        e.norow = h->d_land; e.nnorow = h->nland;
+      }
+    }
+  }
+  return 0;
+}
+
+int reduce_launch(mckpp_hip_ctx *h, const red_planes &r, int phase)
+{
+  HIPCHK(mckpp_launch_reduce(h->red_tab, (int)r.tab.size(), phase, r.maxout, r.maxslab, r.xtiles, h->red.m, h->stream));
+  return 0;
+}
+
+// the host form's end on the owner's stream: one copy of all results through the pinned block, a wait, and out they go
+int reduce_host_deliver(mckpp_hip_ctx *owner, const red_planes &r)
+{
+  auto &s = owner->red;
+  HIPCHK(hipMemcpyAsync(s.h_out, s.d_out, r.outs * sizeof(double), hipMemcpyDeviceToHost, owner->stream));
+  HIPCHK(hipStreamSynchronize(owner->stream));
+  for (size_t k = 0; k < r.tab.size(); ++k) memcpy(r.host_out[k], s.h_out.get() + r.out_off[k], r.nout[k] * sizeof(double));
+  return 0;
+}
+
+int reduce_single(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
+                  void *consumer_stream)
+{
+  red_planes r;
+  if (reduce_check(h, who, nplanes, planes, dev_form, r, nullptr)) return -1;
+  if (r.tab.empty()) return 0;
+  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complements again)
+  for (int s : r.sched) {
+    auto &w = h->wsched[s];
+    if (w.norow_kind == 2 && win_norow_set(h, w, w.norow, 1)) return -1;
+  }
+  if (reduce_reserve(h, r, dev_form)) return -1;
+  std::vector<int64_t> rows;
+  for (const auto &e : r.tab) rows.push_back(e.nrow);
+  if (reduce_bind(h, h, r, dev_form, true, rows)) return -1;
+  if (dev_form && caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(h->red_tab.put(r.tab, h->stream));
+  if (dev_form) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_caller, 0));   // what the consumer had queued on the arrays
+  if (reduce_launch(h, r, MCKPP_RED_PHASE_FILL) || reduce_launch(h, r, MCKPP_RED_PHASE_TERMS)) return -1;
+  if (r.halve && reduce_launch(h, r, MCKPP_RED_PHASE_HALVE)) return -1;
+  if (r.domain && reduce_launch(h, r, MCKPP_RED_PHASE_FINISH)) return -1;
+  if (!dev_form) return reduce_host_deliver(h, r);
+  HIPCHK(h->ev_delivered.record(h->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_reduce_weights(mckpp_hip_handle h, const double *point_w, const double *level_w, const double *iface_w)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return reduce_weights_set(h, who, point_w, level_w, iface_w); });
+}
+
+int mckpp_hip_records_reduce_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_reduce_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return reduce_single(h, who, nplanes, planes, true, consumer_stream); });
+}
+
+int mckpp_hip_records_reduce_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_reduce_plane_c *planes)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return reduce_single(h, who, nplanes, planes, false, nullptr); });
+}
+
+// the tree of include/mckpp_hip_reduce.h, c, as it is written there
+double mckpp_host_reduce_tree(const double *t, int64_t n)
+{
+  double out = 0.0;
+  (void)entry(__func__, [&]() -> int {
+    if (!t || n <= 0) return 0;
+    size_t n2 = 1;
+    while (n2 < (size_t)n) n2 *= 2;
+    std::vector<double> v(n2, 0.0);
+    std::copy(t, t + n, v.begin());
+    for (size_t m = n2 / 2; m >= 1; m /= 2)
+      for (size_t i = 0; i < m; ++i) v[i] = v[i] + v[i + m];
+    out = v[0];
+    return 0;
+  });
+  return out;
 }
 
 // ---------------------------------------------------------------------------
@@ -4388,6 +4683,20 @@ int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const m
   });
 }
 
+// shard 0's list of the positions of schedule `sched`'s point axis that no shard has a row for - the grid's land list, or
+// the point list's own -, where it is not that already
+static int multi_norow(mckpp_hip_multi *m, const char *who, int sched)
+{
+  auto &w = m->ctx[0]->wsched[sched];
+  if (!w.listed) return multi_land(m, who);
+  if (w.norow_kind == 2) return 0;
+  std::vector<unsigned char> held((size_t)w.npoints, 0);
+  for (auto *x : m->ctx)
+    for (int p : x->wsched[sched].rowpos) held[(size_t)p] = 1;
+  HIPCHK(hipSetDevice(m->ctx[0]->device));
+  return win_norow_set(m->ctx[0], w, points_not(held), 2);
+}
+
 // mckpp_hip_records_dev over all shards: a shard writes its own rows of every plane, shard 0 the land values - at the
 // grid points, or the positions of a schedule's point list, that no shard has a row for
 int mckpp_hip_multi_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_record_plane_c *planes,
@@ -4401,22 +4710,89 @@ int mckpp_hip_multi_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const
     if (records_dev_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
   if (dev < 0) return 0;   // (no plane)
   const rec_planes &r0 = rs[0];
-  for (size_t k = 0; k < r0.tab.size(); ++k) {
-    if (!r0.tab[k].fill) continue;
-    auto &w = m->ctx[0]->wsched[r0.sched[k]];
-    if (!w.listed) { if (multi_land(m, who)) return -1; continue; }
-    if (w.norow_kind == 2) continue;
-    std::vector<unsigned char> held((size_t)w.npoints, 0);
-    for (auto *x : m->ctx)
-      for (int p : x->wsched[r0.sched[k]].rowpos) held[(size_t)p] = 1;
-    HIPCHK(hipSetDevice(m->ctx[0]->device));
-    if (win_norow_set(m->ctx[0], w, points_not(held), 2)) return -1;
-  }
+  for (size_t k = 0; k < r0.tab.size(); ++k)
+    if (r0.tab[k].fill && multi_norow(m, who, r0.sched[k])) return -1;
   if (multi_caller_event(m, dev, consumer_stream)) return -1;
   for (int d = 0; d < ndev; ++d)
     if (records_dev_queue(m->ctx[d], rs[(size_t)d], d == 0, m->ev_caller, consumer_stream)) return -1;
   return 0;
   });
+}
+
+// The reductions of include/mckpp_hip_reduce.h over all shards.  Per-shard sums combined afterwards would not be the single
+// context's bits, so the shards deliver terms and shard 0 reduces: shard 0 fills its slabs (and the land values of the
+// axis-only planes), every shard then writes the terms - or, axis only, the results - of its own rows, and behind all of
+// them shard 0 runs the tree and delivers.
+static int multi_reduce(mckpp_hip_multi *m, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
+                        void *consumer_stream)
+{
+  const int ndev = (int)m->ctx.size();
+  mckpp_hip_ctx *root = m->ctx[0];
+  std::vector<red_planes> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (reduce_check(m->ctx[d], who, nplanes, planes, dev_form, rs[(size_t)d], &dev)) return -1;
+  red_planes &r0 = rs[0];
+  if (r0.tab.empty()) return 0;
+  std::vector<int64_t> rows(r0.tab.size(), 0);
+  for (size_t k = 0; k < r0.tab.size(); ++k) {
+    for (int d = 0; d < ndev; ++d) rows[k] += rs[(size_t)d].tab[k].nrow;
+    // axis only: shard 0 writes the land value where no shard has a row
+    if (r0.tab[k].domain_op == 0 && multi_norow(m, who, r0.sched[k])) return -1;
+  }
+  if (reduce_reserve(root, r0, dev_form)) return -1;
+  for (int d = 1; d < ndev; ++d) {   // the other shards write into shard 0's blocks
+    HIPCHK(hipSetDevice(m->ctx[d]->device));
+    if (r0.terms > 0 && dev_ptr_check(m->ctx[d], who, "shard 0's block of terms", root->red.d_terms, r0.terms * sizeof(double)))
+      return -1;
+    if (!dev_form && dev_ptr_check(m->ctx[d], who, "shard 0's block of results", root->red.d_out, r0.outs * sizeof(double)))
+      return -1;
+  }
+  for (int d = 0; d < ndev; ++d)
+    if (reduce_bind(m->ctx[d], root, rs[(size_t)d], dev_form, d == 0, rows)) return -1;
+  if (dev_form && multi_caller_event(m, dev, consumer_stream)) return -1;
+  HIPCHK(hipSetDevice(root->device));
+  HIPCHK(root->red_tab.put(r0.tab, root->stream));
+  if (dev_form) HIPCHK(hipStreamWaitEvent(root->stream, m->ev_caller, 0));
+  if (reduce_launch(root, r0, MCKPP_RED_PHASE_FILL)) return -1;
+  HIPCHK(root->red.ev_fill.record(root->stream));
+  for (int d = 1; d < ndev; ++d) {
+    mckpp_hip_ctx *x = m->ctx[d];
+    HIPCHK(hipSetDevice(x->device));
+    HIPCHK(x->red_tab.put(rs[(size_t)d].tab, x->stream));
+    HIPCHK(hipStreamWaitEvent(x->stream, root->red.ev_fill, 0));
+    if (reduce_launch(x, rs[(size_t)d], MCKPP_RED_PHASE_TERMS)) return -1;
+    HIPCHK(x->red.ev_terms.record(x->stream));
+  }
+  HIPCHK(hipSetDevice(root->device));
+  if (reduce_launch(root, r0, MCKPP_RED_PHASE_TERMS)) return -1;
+  for (int d = 1; d < ndev; ++d) HIPCHK(hipStreamWaitEvent(root->stream, m->ctx[d]->red.ev_terms, 0));
+  if (r0.halve && reduce_launch(root, r0, MCKPP_RED_PHASE_HALVE)) return -1;
+  if (r0.domain && reduce_launch(root, r0, MCKPP_RED_PHASE_FINISH)) return -1;
+  if (!dev_form) return reduce_host_deliver(root, r0);
+  HIPCHK(root->ev_delivered.record(root->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), root->ev_delivered, 0));
+  return 0;
+}
+
+int mckpp_hip_multi_reduce_weights(mckpp_hip_multi_handle m, const double *point_w, const double *level_w, const double *iface_w)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  for (auto *x : m->ctx)   // (the first shard's checks are every shard's: nothing is replaced unless all can be)
+    if (reduce_weights_set(x, who, point_w, level_w, iface_w)) return -1;
+  return 0;
+  });
+}
+
+int mckpp_hip_multi_records_reduce_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_reduce_plane_c *planes,
+                                       void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return multi_reduce(m, who, nplanes, planes, true, consumer_stream); });
+}
+
+int mckpp_hip_multi_records_reduce_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_reduce_plane_c *planes)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return multi_reduce(m, who, nplanes, planes, false, nullptr); });
 }
 
 // mckpp_hip_put_dev / _put_host over all shards: the same planes for every shard, which writes its own columns only

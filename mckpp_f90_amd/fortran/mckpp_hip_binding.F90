@@ -54,6 +54,20 @@ module mckpp_hip_binding
     type(c_ptr) :: out
   end type mckpp_dev_record_plane_c
 
+  !> one plane of mckpp_hip_records_reduce_dev / _host (include/mckpp_hip_reduce.h): the plane mckpp_dev_record_plane_c
+  !! names by sched, field, op, lev0, nlev and rec, reduced by axis_op over its levels and by domain_op over its points
+  !! (MCKPP_RED_*; not both none), with the weights of mckpp_hip_reduce_weights where `weighted` has MCKPP_RED_W_LEVELS /
+  !! MCKPP_RED_W_POINTS; out: doubles - npoints (domain_op none), nlev (axis_op none), or one
+  type, bind(C) :: mckpp_reduce_plane_c
+    integer(c_int32_t) :: sched, field, op, lev0, nlev, axis_op, domain_op, weighted
+    integer(c_int64_t) :: rec
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_reduce_plane_c
+  integer(c_int32_t), parameter :: MCKPP_RED_NONE = 0, MCKPP_RED_SUM = 1, MCKPP_RED_AVERAGE = 2, MCKPP_RED_MIN = 3, &
+    MCKPP_RED_MAX = 4
+  integer(c_int32_t), parameter :: MCKPP_RED_W_LEVELS = 1, MCKPP_RED_W_POINTS = 2
+
   !> one plane of mckpp_hip_put_dev / mckpp_hip_put_host (include/mckpp_hip_put.h): the array at `in`, (npts, nlev) of
   !! MCKPP_EXP_F64 or MCKPP_EXP_F32, is set into (op MCKPP_PUT_SET) or added to (MCKPP_PUT_ADD) levels lev0 .. lev0+nlev-1
   !! (0-based) of state field `field` (MCKPP_OUT_U, _V, _T, _S_ANOM, _S); flags: MCKPP_PUT_SKIP - elements equal to
@@ -798,6 +812,56 @@ module mckpp_hip_binding
       type(c_ptr), value :: m, consumer_stream
       integer(c_int32_t), value :: nplanes
       type(mckpp_dev_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! records reduced over levels and points (include/mckpp_hip_reduce.h, which states the arithmetic and its order);
+    ! the weight arrays are host arrays, c_null_ptr: not set
+    function mckpp_hip_reduce_weights(handle, point_w, level_w, iface_w) bind(C, name="mckpp_hip_reduce_weights") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, point_w, level_w, iface_w
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_records_reduce_dev(handle, nplanes, planes, consumer_stream) &
+        bind(C, name="mckpp_hip_records_reduce_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_reduce_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_reduce_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_records_reduce_host(handle, nplanes, planes) bind(C, name="mckpp_hip_records_reduce_host") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_reduce_plane_c
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_reduce_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_host_reduce_tree(t, n) bind(C, name="mckpp_host_reduce_tree") result(s)
+      import :: c_double, c_int64_t
+      real(c_double), intent(in) :: t(*)
+      integer(c_int64_t), value :: n
+      real(c_double) :: s
+    end function
+    function mckpp_hip_multi_reduce_weights(m, point_w, level_w, iface_w) bind(C, name="mckpp_hip_multi_reduce_weights") &
+        result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: m, point_w, level_w, iface_w
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_records_reduce_dev(m, nplanes, planes, consumer_stream) &
+        bind(C, name="mckpp_hip_multi_records_reduce_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_reduce_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_reduce_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_records_reduce_host(m, nplanes, planes) bind(C, name="mckpp_hip_multi_records_reduce_host") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_reduce_plane_c
+      type(c_ptr), value :: m
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_reduce_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
     ! the prognostic state set or incremented in place (include/mckpp_hip_put.h): one launch for all planes on the
