@@ -22,7 +22,8 @@ include/mckpp_hip_device.h has a table of its own, _SIGNATURES_DEVICE, and its m
 have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, and their methods are _WindowSchedules'.  The records of a schedule into device arrays
 (include/mckpp_hip_device_records.h) are the fourth table, _SIGNATURES_RECORDS, and one more method of _DeviceArrays;
 the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _SIGNATURES_PUT, and two more methods there;
-records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixth, _SIGNATURES_REDUCE, and three more.
+records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixth, _SIGNATURES_REDUCE, and three more;
+the caller's vertical axes (include/mckpp_hip_vaxis.h) are the seventh, _SIGNATURES_VAXIS, and the mixin _VerticalAxes.
 """
 import ctypes as C
 import sys
@@ -427,6 +428,37 @@ _SIGNATURES_REDUCE = {
 }
 
 
+class _VaxisPutPlaneC(C.Structure):
+    """mckpp_vaxis_put_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "axis", "dtype", "op", "flags")] + \
+               [("skip_value", C.c_double), ("in", C.c_void_p)]
+
+
+class _VaxisProfilesC(C.Structure):
+    """mckpp_vaxis_profiles_c"""
+    _fields_ = [(n, C.c_int32) for n in ("axis_vel", "axis_temp", "axis_sal", "dtype")] + [("tk0", C.c_double)] + \
+               [(n, C.c_void_p) for n in ("u", "v", "temp", "sal")]
+
+
+class _VaxisDevPlaneC(C.Structure):
+    """mckpp_vaxis_dev_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "axis", "dtype", "fill_land")] + \
+               [("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_vaxis.h, the caller's vertical axes, in the same form; tests/test_vaxis_cpu.py
+# holds this table to that header.
+_SIGNATURES_VAXIS = {
+    "mckpp_host_vaxis_map": _sig(_i32, _dp, _i32, _dp, _ip, _ip, _dp, _dp),
+    "mckpp_hip_vaxis_define": _sig(_H, _i, _i32, _dp, twin=True),
+    "mckpp_hip_vaxis_put_dev": _sig(_H, _i32, C.POINTER(_VaxisPutPlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_vaxis_put_host": _sig(_H, _i32, C.POINTER(_VaxisPutPlaneC), twin=True),
+    "mckpp_hip_vaxis_init_profiles_dev": _sig(_H, C.POINTER(_VaxisProfilesC), C.c_void_p, twin=True),
+    "mckpp_hip_vaxis_init_profiles_host": _sig(_H, C.POINTER(_VaxisProfilesC), twin=True),
+    "mckpp_hip_vaxis_fetch_dev": _sig(_H, _i32, C.POINTER(_VaxisDevPlaneC), C.c_void_p, twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -467,13 +499,19 @@ def _signatures_reduce():
     return _spelled(_SIGNATURES_REDUCE)
 
 
+def _signatures_vaxis():
+    """... and of every function of mckpp_hip_vaxis.h."""
+    return _spelled(_SIGNATURES_VAXIS)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
     # MCKPP_HIP_LIBRARY may name an older build (tools/export_rate.py --lib): a name it does not export is skipped -
     # everything else works with it, and a call of that name fails there by name
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
-                                  **_signatures_records(), **_signatures_put(), **_signatures_reduce()}.items():
+                                  **_signatures_records(), **_signatures_put(), **_signatures_reduce(),
+                                  **_signatures_vaxis()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -1226,7 +1264,169 @@ class _DeviceArrays:
         self._call("dev_fence", _dev_stream(stream))
 
 
-class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays):
+# the caller's vertical axes (MCKPP_VAXES, MCKPP_VAXIS_* of mckpp_hip_vaxis.h)
+VAXES, VAXIS_LEVELS_MAX = 8, 1024
+VAXIS_ABOVE, VAXIS_BELOW, VAXIS_BRACKET = 0, 1, 2
+# output fields on the interface axis 0..nz, which no axis of heights like zm describes
+_OUT_INTERFACE = frozenset(OUT[n] for n in ("wu", "wv", "wT", "wS", "wB", "wTnt", "difm", "dift", "difs"))
+
+
+def host_vaxis_map(zs, zt):
+    """(branch, kin, t, dz) of the vertical interpolation from the source levels zs onto the targets zt, both heights,
+    strictly decreasing: mckpp_host_vaxis_map, the table a caller's axis carries (include/mckpp_hip_vaxis.h).  No GPU."""
+    zs = np.ascontiguousarray(zs, dtype=np.float64).ravel()
+    zt = np.ascontiguousarray(zt, dtype=np.float64).ravel()
+    branch, kin = np.zeros(zt.size, dtype=np.int32), np.zeros(zt.size, dtype=np.int32)
+    t, dz = np.zeros(zt.size), np.zeros(zt.size)
+    rc = _lib().mckpp_host_vaxis_map(zs.size, zs.ctypes.data_as(_dp), zt.size, zt.ctypes.data_as(_dp), branch.ctypes.data_as(_ip),
+                                     kin.ctypes.data_as(_ip), t.ctypes.data_as(_dp), dz.ctypes.data_as(_dp))
+    if rc != 0:
+        raise ValueError("host_vaxis_map: an axis has fewer than two source levels, no target, a value that is not finite, "
+                         "or does not strictly decrease")
+    return branch, kin, t, dz
+
+
+class _VerticalAxes:
+    """The caller's vertical axes (include/mckpp_hip_vaxis.h): state in, the reference's initial profiles and fields out
+    on levels that are not the model's.  An array on axis a is (n_a, npts): points fastest, the whole axis."""
+
+    def _vaxes(self):
+        return self.__dict__.setdefault("_vaxis_n", {})
+
+    def _vaxis(self, who, axis):
+        """the number of levels of a defined axis"""
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or int(axis) not in self._vaxes():
+            raise ValueError(f"{who}: axis {axis!r} is not defined (vaxis_define; axes are 0 .. {VAXES - 1})")
+        return self._vaxes()[int(axis)]
+
+    def vaxis_define(self, axis, z):
+        """Caller axis `axis` (0 .. VAXES - 1): the heights z, at least two, finite and strictly decreasing like zm; None
+        or an empty z drops the axis.  The handle keeps it over upload and load_restart."""
+        if isinstance(axis, bool) or not isinstance(axis, (int, np.integer)) or not 0 <= int(axis) < VAXES:
+            raise ValueError(f"vaxis_define: axis {axis!r} (0 .. {VAXES - 1})")
+        a = np.zeros(0) if z is None else np.ascontiguousarray(z, dtype=np.float64)
+        if a.ndim != 1 or a.size == 1 or a.size > VAXIS_LEVELS_MAX:
+            raise ValueError(f"vaxis_define: z has shape {a.shape}; an axis has 2 .. {VAXIS_LEVELS_MAX} levels (none drops it)")
+        if not np.isfinite(a).all():
+            raise ValueError("vaxis_define: z holds a value that is not finite")
+        if a.size and not (a[1:] < a[:-1]).all():
+            raise ValueError("vaxis_define: z does not strictly decrease (an axis holds heights, like zm)")
+        self._call("vaxis_define", int(axis), a.size, a.ctypes.data_as(_dp))
+        if a.size:
+            self._vaxes()[int(axis)] = int(a.size)
+        else:
+            self._vaxes().pop(int(axis), None)
+
+    def _vaxis_put_table(self, who, planes, op, time_levels, skip, array):
+        """the planes of vaxis_put_dev / _put_host as the table the library takes, after every check that needs no library"""
+        if op not in _PUT_OPS or isinstance(op, bool):
+            raise ValueError(f"{who}: op {op!r} (\"set\" or \"add\")")
+        flags, skip_value = (PUT_TIME_LEVELS if time_levels else 0), 0.0
+        if skip is not None:
+            flags, skip_value = flags | PUT_SKIP, float(skip)
+            if skip_value != skip_value:
+                raise ValueError(f"{who}: skip is NaN, which no element compares equal to")
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"{who}: {len(planes)} planes, at most 64 in one call")
+        n, arr, seen = self._npts, (_VaxisPutPlaneC * max(1, len(planes)))(), []
+        for k, p in enumerate(planes):
+            if len(p) != 3:
+                raise ValueError(f"{who}: planes[{k}] is (field, axis, array)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: planes[{k}]: {e}") from None
+            if f not in _PUT_FIELDS:
+                raise ValueError(f"{who}: planes[{k}]: field {OUT_FIELDS[f]} is an output of the step, not state (u, v, T, "
+                                 "S_anom, S)")
+            nax = self._vaxis(f"{who}: planes[{k}]", p[1])
+            if _PUT_FIELDS[f] in seen:
+                raise ValueError(f"{who}: planes[{k}] and planes[{seen.index(_PUT_FIELDS[f])}] write {_PUT_FIELDS[f]}: a plane "
+                                 "writes the whole profile, and the planes of a call have no order")
+            seen.append(_PUT_FIELDS[f])
+            ptr, typestr = array(p[2], f"{who}: planes[{k}] array", nax * n)
+            arr[k] = _VaxisPutPlaneC(f, int(p[1]), _DEV_TYPESTR[typestr], _PUT_OPS[op], flags, skip_value, ptr)
+        return len(planes), arr
+
+    def vaxis_put_dev(self, planes, op="set", time_levels=False, skip=None, stream=None, fence=False):
+        """put_dev from arrays on caller axes: a plane is (field, axis, array), the array's n_axis * npts elements - a
+        tensor of shape (n_axis, npts) - of float64 or float32, and writes every model level of u, v, T, S_anom or S with
+        the interpolated value (include/mckpp_hip_vaxis.h).  op, time_levels, stream and fence are put_dev's; skip: a
+        model level stays untouched if an input value it is interpolated from equals this value."""
+        planes = list(planes)
+        n, arr = self._vaxis_put_table("vaxis_put_dev", planes, op, time_levels, skip,
+                                       lambda a, what, count: _dev_array(a, what, count, tuple(_DEV_TYPESTR)))
+        s = _dev_stream(stream)
+        for p in planes:
+            self._hold_dev(p[2])
+        self._call("vaxis_put_dev", n, arr, s)
+        if fence:
+            self._call("dev_fence", s)
+
+    def vaxis_put_host(self, planes, op="set", time_levels=False, skip=None):
+        """vaxis_put_dev from numpy arrays of float64 or float32, shape (n_axis, npts); returns when the state is written."""
+        n, arr = self._vaxis_put_table("vaxis_put_host", planes, op, time_levels, skip, _host_plane)
+        self._call("vaxis_put_host", n, arr)
+
+    def _vaxis_profiles(self, who, u, v, temp, sal, axis_vel, axis_temp, axis_sal, tk0, array):
+        tk0 = float(tk0)
+        if not np.isfinite(tk0):
+            raise ValueError(f"{who}: tk0 is not finite")
+        ptrs, types = [], set()
+        for name, a, axis in (("u", u, axis_vel), ("v", v, axis_vel), ("temp", temp, axis_temp), ("sal", sal, axis_sal)):
+            nax = self._vaxis(f"{who}: {name}", axis)
+            ptr, typestr = array(a, f"{who}: {name}", nax * self._npts)
+            ptrs.append(ptr)
+            types.add(typestr)
+        if len(types) != 1:
+            raise ValueError(f"{who}: u, v, temp and sal have element types {sorted(types)}; the call takes one")
+        return _VaxisProfilesC(int(axis_vel), int(axis_temp), int(axis_sal), _DEV_TYPESTR[types.pop()], tk0, *ptrs)
+
+    def vaxis_init_profiles_dev(self, u, v, temp, sal, axis_vel, axis_temp, axis_sal, tk0=273.15, stream=None):
+        """The reference's initial profiles (mckpp_initialize_ocean_profiles) from device arrays on caller axes: u, v on
+        axis_vel, temp on axis_temp, sal on axis_sal, each (n_axis, npts) of one element type.  Writes U, V, U_init, T
+        (less tk0 everywhere if any resident value lies strictly between 200 and 400), X2 = S - Sref, Sref, SSref,
+        Tref and Ssurf of the resident columns; upload comes before it, init_ocean after.  Returns when it is done."""
+        p = self._vaxis_profiles("vaxis_init_profiles_dev", u, v, temp, sal, axis_vel, axis_temp, axis_sal, tk0,
+                                 lambda a, what, count: _dev_array(a, what, count, tuple(_DEV_TYPESTR)))
+        self._call("vaxis_init_profiles_dev", C.byref(p), _dev_stream(stream))
+
+    def vaxis_init_profiles_host(self, u, v, temp, sal, axis_vel, axis_temp, axis_sal, tk0=273.15):
+        """vaxis_init_profiles_dev from numpy arrays."""
+        p = self._vaxis_profiles("vaxis_init_profiles_host", u, v, temp, sal, axis_vel, axis_temp, axis_sal, tk0, _host_plane)
+        self._call("vaxis_init_profiles_host", C.byref(p))
+
+    def vaxis_fetch_dev(self, planes, stream=None, land_value=1e20, fill_land=True):
+        """fetch_dev onto caller axes: a plane is (field, axis, out), out of n_axis * npts elements - a tensor of shape
+        (n_axis, npts) - of float64 or float32, and takes the field as it stands, interpolated from the model's levels
+        (include/mckpp_hip_vaxis.h).  Fields on the levels 1..nzp1 only: two-dimensional fields and those on the
+        interface axis are refused.  stream, land_value and fill_land are fetch_dev's."""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"vaxis_fetch_dev: {len(planes)} planes, at most 64 in one call")
+        n, arr = self._npts, (_VaxisDevPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            who = f"vaxis_fetch_dev: planes[{k}]"
+            if len(p) != 3:
+                raise ValueError(f"{who} is (field, axis, out)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            if f in _OUT_2D:
+                raise ValueError(f"{who}: field {OUT_FIELDS[f]} is two-dimensional: it has no vertical axis to interpolate")
+            if f in _OUT_INTERFACE:
+                raise ValueError(f"{who}: field {OUT_FIELDS[f]} lives on the interface axis 0..nz, not on the levels a "
+                                 "caller's axis is interpolated from")
+            nax = self._vaxis(who, p[1])
+            ptr, typestr = _dev_array(p[2], f"{who} out", nax * n, tuple(_DEV_TYPESTR))
+            arr[k] = _VaxisDevPlaneC(f, int(p[1]), _DEV_TYPESTR[typestr], int(bool(fill_land)), float(land_value), ptr)
+            self._hold_dev(p[2])
+        self._call("vaxis_fetch_dev", len(planes), arr, _dev_stream(stream))
+
+
+class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays, _VerticalAxes):
     """What one device context and several GPUs behind one handle have in common: everything but how they are made.
     Method `name` is the C function self._pre + name applied to the handle self._h."""
     _pre = "mckpp_hip_"

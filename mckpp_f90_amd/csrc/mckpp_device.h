@@ -303,6 +303,38 @@ struct mckpp_put_plane {
 // all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane
 hipError_t mckpp_launch_put_planes(const mckpp_put_plane *tab, int nplanes, int maxlev, const int *ipt, int64_t ncol,
                                    int64_t npts, double *cs, hipStream_t stream);
+// The caller's vertical axes (include/mckpp_hip_vaxis.h states the interpolation).  One entry of an axis table, built
+// by mckpp_host_vaxis_map: which source levels a target level reads - kin alone (branch 0 above the axis, 1 below it)
+// or kin and kin + 1 (branch 2) - and the two numbers of the bracket that depend on the axes alone.
+struct mckpp_vaxis_ent { int branch, kin; double t, dz; };
+// One plane of mckpp_hip_vaxis_put_dev / _put_host and of the profiles of mckpp_hip_vaxis_init_profiles
+// (k_vaxis_put_planes): put.in is in(npts, n_axis) and put.nlev the model's nzp1; level lev of a column takes vinterp of
+// the column's input through tab[lev], and put_element does with it what `put` says - whose own skip is 0: `skip` is
+// decided on the input side, where the values the branch reads are.  row2 (null: none): rows that take the value too
+// (U_init); kelvin (null: none): the word that gets bit 0 where a value written is > 200 and < 400.
+struct mckpp_vaxis_put_plane {
+  mckpp_put_plane put;
+  const mckpp_vaxis_ent *tab;
+  double *row2;
+  unsigned *kelvin;
+  int skip;
+};
+// One plane of mckpp_hip_vaxis_fetch_dev (k_vaxis_fetch_planes): f.nlev is the caller axis' n, level j of out takes
+// vinterp of the row's elements f.off .. f.off + nzp1 - 1 (plus Sref first: f.add_sref) through tab[j].
+struct mckpp_vaxis_fetch_plane {
+  mckpp_fetch_plane f;
+  const mckpp_vaxis_ent *tab;
+};
+#define MCKPP_VAXIS_PLANES 64   // most planes of one call (the device tables' size)
+hipError_t mckpp_launch_vaxis_put_planes(const mckpp_vaxis_put_plane *tab, int nplanes, int nzp1, const int *ipt, int64_t ncol,
+                                         int64_t npts, double *cs, hipStream_t stream);
+hipError_t mckpp_launch_vaxis_fetch_planes(const mckpp_vaxis_fetch_plane *tab, int nplanes, int maxlev, const int *ipt,
+                                           int64_t ncol, int64_t npts, const double *cs, const int *land, int64_t nland,
+                                           hipStream_t stream);
+// the end of mckpp_hip_vaxis_init_profiles, behind the profiles' planes: the Kelvin rule where *kelvin is set, Sref,
+// SSref, X2 = S - Sref, Tref and Ssurf, a wave per column
+hipError_t mckpp_launch_vaxis_init_finish(double *T, double *S, int ld, int nzp1, int64_t ncol, double *cs,
+                                          const unsigned *kelvin, double tk0, int l_ssref, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

@@ -45,9 +45,10 @@ __global__ void k_exp_batch(int64_t n, const double *x, double *y)
 }
 
 // ---------------------------------------------------------------------------
-// The move between device rows and caller planes, stated once for the six kernels that make it (k_gather_rows,
-// k_scatter_rows, k_record_pack, k_fetch_planes, k_record_planes, k_put_planes; k_fetch_planes alone has the routines
-// below written out in its body, for the reason given there).
+// The move between device rows and caller planes, stated once for the eight kernels that make it (k_gather_rows,
+// k_scatter_rows, k_record_pack, k_fetch_planes, k_record_planes, k_put_planes, k_vaxis_fetch_planes,
+// k_vaxis_put_planes; k_fetch_planes and k_vaxis_put_planes have the routines below written out in their bodies, for
+// the reasons given there).
 //
 // Rows are [nrow][ld] doubles with a row's levels contiguous; a plane is plane(npoints, nlev) with points fastest, and
 // row r belongs at position map[r] of it.  A workgroup of 256 threads takes 64 rows (blockIdx.x) by 64 levels
@@ -460,6 +461,159 @@ __global__ __launch_bounds__(256) void k_put_planes(const mckpp_put_plane *__res
 }
 
 // ---------------------------------------------------------------------------
+// The caller's vertical axes (include/mckpp_hip_vaxis.h): planes on levels that are not the model's.  The interpolation
+// is stated there; vaxis_value is its per-element part - one subtraction, one product, one quotient, one sum, each a
+// rounded fp64 operation (-ffp-contract=off, the compiler's IEEE divide) - on the one or two source values an entry of
+// the axis table names.  The table is indexed by the target level, which a wave shares on the side where it is read.
+// ---------------------------------------------------------------------------
+__device__ __forceinline__ double vaxis_value(const mckpp_vaxis_ent &a, double va, double vb)
+{
+  if (a.branch != 2) return va;
+  const double dv = va - vb;
+  const double p = dv * a.t;
+  const double q = p / a.dz;
+  return va + q;
+}
+
+// State in on a caller's axis (mckpp_hip_vaxis_put_dev / _put_host, and the four profiles of
+// mckpp_hip_vaxis_init_profiles).  The relayout tile of k_put_planes, with the value formed on the point side: there
+// tx is a column and a wave shares the model level, so the loads of the bracket's two input levels are whole segments
+// along the points and the table entry is the wave's.  The value travels through the tile and a byte beside it says
+// whether a value the branch read was the skip value; put_element is what happens to it on the row side.  A body of
+// its own for that byte; the barrier rule above is kept by hand: the one exit before the barrier depends on blockIdx
+// and the plane alone.
+template <class T>
+__device__ __forceinline__ void vaxis_put_plane(const mckpp_vaxis_put_plane &e, double (*tile)[65], unsigned char (*hold)[68],
+                                                const int *__restrict__ ipt, int64_t ncol, int64_t npts,
+                                                double *__restrict__ cs)
+{
+  const int l0 = blockIdx.y * 64, nlev = e.put.nlev;
+  if (l0 >= nlev) return;
+  const T *__restrict__ src = static_cast<const T *>(e.put.in);
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  {
+    const int64_t r = r0 + tx;
+    const int64_t pos = r < ncol ? (int64_t)ipt[r] : 0;
+    for (int l = ty; l < 64; l += 4) {        // read: points fastest, a model level per wave
+      const int lev = l0 + l;
+      double v = 0.0;
+      bool skipped = false;
+      if (r < ncol && lev < nlev) {
+        const mckpp_vaxis_ent a = e.tab[lev];
+        const double va = (double)src[(int64_t)a.kin * npts + pos];
+        double vb = va;
+        if (a.branch == 2) vb = (double)src[(int64_t)(a.kin + 1) * npts + pos];
+        skipped = e.skip && (va == e.put.skip_value || vb == e.put.skip_value);
+        v = vaxis_value(a, va, vb);
+      }
+      tile[l][tx] = v;
+      hold[l][tx] = skipped;
+    }
+  }
+  __syncthreads();
+  const int lev = l0 + tx;
+  if (lev >= nlev) return;
+  bool kelvin = false;
+  for (int rr = ty; rr < 64; rr += 4) {       // write: levels fastest
+    const int64_t r = r0 + rr;
+    if (r >= ncol || hold[tx][rr]) continue;
+    const double v = tile[tx][rr];
+    put_element(e.put, cs, r, lev, v);
+    if (e.row2) e.row2[r * e.put.ld + e.put.off + lev] = v;
+    if (e.kelvin) kelvin = kelvin || (v > 200.0 && v < 400.0);   // initialize_ocean_profiles_mod.F90:83-84, the temperature plane of the profiles alone
+  }
+  if (kelvin) atomicOr(e.kelvin, 1u);
+}
+
+__global__ __launch_bounds__(256) void k_vaxis_put_planes(const mckpp_vaxis_put_plane *__restrict__ tab,
+                                                          const int *__restrict__ ipt, int64_t ncol, int64_t npts,
+                                                          double *__restrict__ cs)
+{
+  __shared__ double tile[64][65];
+  __shared__ unsigned char hold[64][68];
+  const mckpp_vaxis_put_plane e = tab[blockIdx.z];
+  if (e.put.f32) vaxis_put_plane<float>(e, tile, hold, ipt, ncol, npts, cs);
+  else vaxis_put_plane<double>(e, tile, hold, ipt, ncol, npts, cs);
+}
+
+// The end of mckpp_hip_vaxis_init_profiles (initialize_ocean_profiles_mod.F90:83-85, :104-117), behind the launch that
+// wrote T and the whole S and raised *kelvin: a wave per column, four columns per workgroup.  Every lane reads S(1) and
+// S(nzp1) before the barrier and the column's S is rewritten after it; the barrier is reached by every thread.
+__global__ __launch_bounds__(256) void k_vaxis_init_finish(double *__restrict__ T, double *__restrict__ S, int ld, int nzp1,
+                                                           int64_t ncol, double *__restrict__ cs,
+                                                           const unsigned *__restrict__ kelvin, double tk0, int l_ssref)
+{
+  const int lane = threadIdx.x & 63;
+  const int64_t c = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+  const bool mine = c < ncol;
+  const int64_t ro = mine ? c * ld : 0;
+  double s1 = 0.0, sn = 0.0;
+  if (mine) { s1 = S[ro]; sn = S[ro + nzp1 - 1]; }
+  __syncthreads();
+  if (!mine) return;
+  const bool in_kelvin = *kelvin != 0u;
+  const double sref = (s1 + sn) / 2.;                            // :104-105
+  double t1 = 0.0, x1 = 0.0;
+  for (int lev = lane; lev < nzp1; lev += 64) {
+    double t = T[ro + lev];
+    if (in_kelvin) { t = t - tk0; T[ro + lev] = t; }             // :85
+    const double x = S[ro + lev] - sref;                         // :108
+    S[ro + lev] = x;
+    if (lev == 0) { t1 = t; x1 = x; }
+  }
+  if (lane != 0) return;
+  double *q = cs + c * MCKPP_CS;
+  q[CS_SREF] = sref;
+  q[CS_SSREF] = sref;                                            // :106
+  q[CS_TREF] = t1;                                               // :112
+  q[CS_SSURF] = l_ssref ? sref : x1 + sref;                      // :113-117
+}
+
+// Fields out on a caller's axis (mckpp_hip_vaxis_fetch_dev): k_fetch_planes with the value formed on the row side,
+// where tx is a caller level: the row's two bracket levels - S with the column's Sref added to each first - through the
+// out table.  kin rises with the caller level, so a wave's loads stay within the row's segments.  The land fill is
+// k_record_planes': the workgroups behind the column tiles.
+template <class T>
+__device__ __forceinline__ void vaxis_fetch_plane(const mckpp_vaxis_fetch_plane &e, double (*tile)[65],
+                                                  const int *__restrict__ ipt, int64_t ncol, int64_t npts,
+                                                  const double *__restrict__ cs, const int *__restrict__ land,
+                                                  int64_t nland, int coltiles)
+{
+  const mckpp_fetch_plane &f = e.f;
+  const int l0 = blockIdx.y * 64;
+  T *__restrict__ dst = static_cast<T *>(f.out);
+  if ((int)blockIdx.x >= coltiles) {
+    if (f.fill_land) fill_positions((int64_t)((int)blockIdx.x - coltiles), f.nlev, l0, land, nland, npts, dst, (T)f.land_value);
+    return;
+  }
+  tile_rows_to_points<false>(tile, ncol, f.nlev, l0, ipt, npts, dst, [&](int64_t c, int lev, bool in) {
+    if (!in) return 0.0;
+    const mckpp_vaxis_ent a = e.tab[lev];
+    const double *row = f.src + c * f.ld + f.off;
+    double va = row[a.kin];
+    double vb = a.branch == 2 ? row[a.kin + 1] : va;
+    if (f.add_sref) {
+      const double sref = cs[c * MCKPP_CS + CS_SREF];
+      va = va + sref;
+      vb = vb + sref;
+    }
+    return vaxis_value(a, va, vb);
+  });
+}
+
+__global__ __launch_bounds__(256) void k_vaxis_fetch_planes(const mckpp_vaxis_fetch_plane *__restrict__ tab,
+                                                            const int *__restrict__ ipt, int64_t ncol, int64_t npts,
+                                                            const double *__restrict__ cs, const int *__restrict__ land,
+                                                            int64_t nland, int coltiles)
+{
+  __shared__ double tile[64][65];
+  const mckpp_vaxis_fetch_plane e = tab[blockIdx.z];
+  if (e.f.f32) vaxis_fetch_plane<float>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
+  else vaxis_fetch_plane<double>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
+}
+
+// ---------------------------------------------------------------------------
 // Records reduced over levels and points (mckpp_hip_records_reduce_dev / _host).  include/mckpp_hip_reduce.h states the
 // arithmetic and its order; the four kernels below are that statement, each one launch for all planes of a call
 // (blockIdx.z, the table of mckpp_red_plane).  No atomics: every element of `terms` and of `out` has one writer per
@@ -635,6 +789,36 @@ hipError_t mckpp_launch_put_planes(const mckpp_put_plane *tab, int nplanes, int 
   if (nplanes <= 0 || maxlev <= 0 || ncol <= 0) return hipSuccess;
   dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
   hipLaunchKernelGGL(k_put_planes, grid, dim3(256), 0, stream, tab, ipt, ncol, npts, cs);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_vaxis_put_planes(const mckpp_vaxis_put_plane *tab, int nplanes, int nzp1, const int *ipt, int64_t ncol,
+                                         int64_t npts, double *cs, hipStream_t stream)
+{
+  if (nplanes <= 0 || nzp1 <= 0 || ncol <= 0) return hipSuccess;
+  dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((nzp1 + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_vaxis_put_planes, grid, dim3(256), 0, stream, tab, ipt, ncol, npts, cs);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_vaxis_fetch_planes(const mckpp_vaxis_fetch_plane *tab, int nplanes, int maxlev, const int *ipt,
+                                           int64_t ncol, int64_t npts, const double *cs, const int *land, int64_t nland,
+                                           hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0) return hipSuccess;
+  const int coltiles = (int)((ncol + 63) / 64), landtiles = (int)((nland + 63) / 64);
+  if (coltiles + landtiles == 0) return hipSuccess;
+  dim3 grid((unsigned)(coltiles + landtiles), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_vaxis_fetch_planes, grid, dim3(256), 0, stream, tab, ipt, ncol, npts, cs, land, nland, coltiles);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_vaxis_init_finish(double *T, double *S, int ld, int nzp1, int64_t ncol, double *cs,
+                                          const unsigned *kelvin, double tk0, int l_ssref, hipStream_t stream)
+{
+  if (ncol <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_vaxis_init_finish, dim3((unsigned)((ncol + 3) / 4)), dim3(256), 0, stream, T, S, ld, nzp1, ncol, cs,
+                     kelvin, tk0, l_ssref);
   return hipGetLastError();
 }
 

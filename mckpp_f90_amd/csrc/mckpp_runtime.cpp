@@ -1,5 +1,5 @@
 // mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companions mckpp_hip_device.h,
-// mckpp_hip_zoom.h, mckpp_hip_device_records.h and mckpp_hip_put.h.
+// mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h and mckpp_hip_vaxis.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
@@ -18,6 +18,7 @@
 #include "../../include/mckpp_hip_device_records.h"
 #include "../../include/mckpp_hip_put.h"
 #include "../../include/mckpp_hip_reduce.h"
+#include "../../include/mckpp_hip_vaxis.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -269,6 +270,19 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
     int m = MCKPP_RED_M;
   } red;
   plane_table<mckpp_red_plane, MCKPP_DEV_PLANES_MAX> red_tab;
+  // The caller's vertical axes (include/mckpp_hip_vaxis.h).  An axis is the context's, like the weights above: its
+  // levels on the host (empty: not defined) and the two tables on the device - `in`, nzp1 entries, the axis as the
+  // source of zm(1:nzp1), and `out`, an entry per caller level, zm(1:nzp1) as its source.  h_zm is zm(1:nzp1), kept
+  // for them.  The plane tables of the puts and the fetches, and the word the Kelvin rule of
+  // mckpp_hip_vaxis_init_profiles raises between its two launches.
+  struct vaxis {
+    std::vector<double> z;
+    dev_buf<mckpp_vaxis_ent> d_in, d_out;
+  } vax[MCKPP_VAXES];
+  std::vector<double> h_zm;
+  plane_table<mckpp_vaxis_put_plane, MCKPP_VAXIS_PLANES> vput_tab;
+  plane_table<mckpp_vaxis_fetch_plane, MCKPP_VAXIS_PLANES> vfetch_tab;
+  dev_buf<unsigned> d_kelvin;
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -507,6 +521,7 @@ int mckpp_hip_init(const mckpp_const_c *c, int device, mckpp_hip_handle *out)
   for (size_t i = 0; i < nt; ++i) wtab[i] = make_double2(c->wmt[i], c->wst[i]);
 
   HIPCHK(up(h->d_zm, zm.data(), ldc));
+  h->h_zm.assign(c->zm, c->zm + nzp1);
   HIPCHK(up(h->d_hm, hm.data(), ldc));
   HIPCHK(up(h->d_tri0, t0.data(), ldc));
   HIPCHK(up(h->d_tri1, t1.data(), ldc));
@@ -2681,6 +2696,46 @@ int mckpp_hip_dev_fence(mckpp_hip_handle h, void *stream)
 // ---------------------------------------------------------------------------
 extern "C++" {
 namespace {
+// What planes[k] of a put says apart from its array, checked and resolved into the kernel's entry (`in` left null) - the
+// one statement of it for put_check and for vaxis_put_check (include/mckpp_hip_vaxis.h), whose planes write levels
+// 0 .. nzp1 - 1.  *row: the profile the plane writes (the overlap check's key); *elem: the size of an element.
+int put_resolve(mckpp_hip_ctx *h, const char *who, int k, int field, int lev0, int nlev, int dtype, int op, int flags,
+                double skip_value, mckpp_put_plane &e, int *row_out, size_t *elem_out)
+{
+  int row, lv0, lv1, ref;
+  switch (field) {
+    case MCKPP_OUT_U: row = P_U; lv0 = P_US0; lv1 = P_US1; ref = CS_UREF; break;
+    case MCKPP_OUT_V: row = P_V; lv0 = P_VS0; lv1 = P_VS1; ref = CS_VREF; break;
+    case MCKPP_OUT_T: row = P_T; lv0 = P_TS0; lv1 = P_TS1; ref = CS_TREF; break;
+    case MCKPP_OUT_S_ANOM:
+    case MCKPP_OUT_S: row = P_S; lv0 = P_SS0; lv1 = P_SS1; ref = h->c.L_SSref ? -1 : CS_SSURF; break;   // L_SSref: Ssurf stays SSref
+    default:
+      if (field < 0 || field >= MCKPP_OUT_COUNT) return fail("%s: planes[%d]: unknown output field %d", who, k, field);
+      return fail("%s: planes[%d]: field %d is an output of the step, not state (MCKPP_OUT_U %d, _V %d, _T %d, _S_ANOM %d, _S %d)",
+                  who, k, field, MCKPP_OUT_U, MCKPP_OUT_V, MCKPP_OUT_T, MCKPP_OUT_S_ANOM, MCKPP_OUT_S);
+  }
+  out_desc d;
+  if (out_field(h, field, d)) return -1;
+  if (plane_levels_check(who, k, lev0, nlev, field, d.nlev)) return -1;
+  const size_t elem = plane_elem(who, k, dtype);
+  if (!elem) return -1;
+  if (op != MCKPP_PUT_SET && op != MCKPP_PUT_ADD)
+    return fail("%s: planes[%d]: op %d (MCKPP_PUT_SET 0, MCKPP_PUT_ADD 1)", who, k, op);
+  if (flags & ~(MCKPP_PUT_SKIP | MCKPP_PUT_TIME_LEVELS))
+    return fail("%s: planes[%d]: flags %#x (a mask of MCKPP_PUT_SKIP 1, MCKPP_PUT_TIME_LEVELS 2)", who, k, (unsigned)flags);
+  const bool skip = flags & MCKPP_PUT_SKIP, levels = flags & MCKPP_PUT_TIME_LEVELS;
+  if (skip && std::isnan(skip_value))
+    return fail("%s: planes[%d]: the skip value is NaN, which no element compares equal to", who, k);
+  const bool add = op == MCKPP_PUT_ADD;
+  e = mckpp_put_plane{nullptr, h->d_prof[row].get(), levels ? h->d_prof[lv0].get() : nullptr,
+                      levels ? h->d_prof[lv1].get() : nullptr, skip_value, d.ld, d.off + lev0, nlev,
+                      dtype == MCKPP_EXP_F32 ? 1 : 0, add ? 1 : 0, skip ? 1 : 0, (!add && d.add_sref) ? 1 : 0,
+                      lev0 == 0 ? ref : -1, ref == CS_SSURF ? 1 : 0};
+  *row_out = row;
+  *elem_out = elem;
+  return 0;
+}
+
 // The planes of a put, checked and resolved into the kernel's table.  dev_form: `in` is device memory (*dev, where asked
 // for: the device of the first plane's); otherwise host memory, and the table's `in` is set by put_host_queue.
 int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_put_plane_c *planes, bool dev_form,
@@ -2695,30 +2750,10 @@ int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_pu
   int prof[MCKPP_PUT_PLANES_MAX];
   for (int k = 0; k < nplanes; ++k) {
     const mckpp_put_plane_c &q = planes[k];
-    int row, lv0, lv1, ref;
-    switch (q.field) {
-      case MCKPP_OUT_U: row = P_U; lv0 = P_US0; lv1 = P_US1; ref = CS_UREF; break;
-      case MCKPP_OUT_V: row = P_V; lv0 = P_VS0; lv1 = P_VS1; ref = CS_VREF; break;
-      case MCKPP_OUT_T: row = P_T; lv0 = P_TS0; lv1 = P_TS1; ref = CS_TREF; break;
-      case MCKPP_OUT_S_ANOM:
-      case MCKPP_OUT_S: row = P_S; lv0 = P_SS0; lv1 = P_SS1; ref = h->c.L_SSref ? -1 : CS_SSURF; break;   // L_SSref: Ssurf stays SSref
-      default:
-        if (q.field < 0 || q.field >= MCKPP_OUT_COUNT) return fail("%s: planes[%d]: unknown output field %d", who, k, q.field);
-        return fail("%s: planes[%d]: field %d is an output of the step, not state (MCKPP_OUT_U %d, _V %d, _T %d, _S_ANOM %d, _S %d)",
-                    who, k, q.field, MCKPP_OUT_U, MCKPP_OUT_V, MCKPP_OUT_T, MCKPP_OUT_S_ANOM, MCKPP_OUT_S);
-    }
-    out_desc d;
-    if (out_field(h, q.field, d)) return -1;
-    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, d.nlev)) return -1;
-    const size_t elem = plane_elem(who, k, q.dtype);
-    if (!elem) return -1;
-    if (q.op != MCKPP_PUT_SET && q.op != MCKPP_PUT_ADD)
-      return fail("%s: planes[%d]: op %d (MCKPP_PUT_SET 0, MCKPP_PUT_ADD 1)", who, k, q.op);
-    if (q.flags & ~(MCKPP_PUT_SKIP | MCKPP_PUT_TIME_LEVELS))
-      return fail("%s: planes[%d]: flags %#x (a mask of MCKPP_PUT_SKIP 1, MCKPP_PUT_TIME_LEVELS 2)", who, k, (unsigned)q.flags);
-    const bool skip = q.flags & MCKPP_PUT_SKIP, levels = q.flags & MCKPP_PUT_TIME_LEVELS;
-    if (skip && std::isnan(q.skip_value))
-      return fail("%s: planes[%d]: the skip value is NaN, which no element compares equal to", who, k);
+    mckpp_put_plane e;
+    int row;
+    size_t elem;
+    if (put_resolve(h, who, k, q.field, q.lev0, q.nlev, q.dtype, q.op, q.flags, q.skip_value, e, &row, &elem)) return -1;
     for (int j = 0; j < k; ++j)
       if (prof[j] == row && q.lev0 < planes[j].lev0 + planes[j].nlev && planes[j].lev0 < q.lev0 + q.nlev)
         return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d) at overlapping levels %d..%d and %d..%d: the "
@@ -2732,11 +2767,8 @@ int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_pu
     } else if (dev_ptr_check(h, who, arg, q.in, (size_t)h->npts * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) {
       return -1;
     }
-    const bool add = q.op == MCKPP_PUT_ADD;
-    tab.push_back(mckpp_put_plane{q.in, h->d_prof[row].get(), levels ? h->d_prof[lv0].get() : nullptr,
-                                  levels ? h->d_prof[lv1].get() : nullptr, q.skip_value, d.ld, d.off + q.lev0, q.nlev,
-                                  q.dtype == MCKPP_EXP_F32 ? 1 : 0, add ? 1 : 0, skip ? 1 : 0, (!add && d.add_sref) ? 1 : 0,
-                                  q.lev0 == 0 ? ref : -1, ref == CS_SSURF ? 1 : 0});
+    e.in = q.in;
+    tab.push_back(e);
     *maxlev = std::max(*maxlev, (int)q.nlev);
   }
   return 0;
@@ -2798,6 +2830,348 @@ int mckpp_hip_put_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_put_plan
   int maxlev = 0;
   if (put_check(h, who, nplanes, planes, false, tab, &maxlev, nullptr)) return -1;
   return put_host_queue(h, tab, maxlev);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// The caller's vertical axes (include/mckpp_hip_vaxis.h): axes defined per context, state in and the reference's
+// initial profiles through the in table (k_vaxis_put_planes, k_vaxis_init_finish), fields out through the out table
+// (k_vaxis_fetch_planes).  Checks queue nothing; the parts that queue keep put_queue's and fetch_dev_queue's order.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// an axis table built on the host and copied to the device (the context's device is current)
+int vaxis_table(const char *who, int ns, const double *zs, int nt, const double *zt, dev_buf<mckpp_vaxis_ent> &d)
+{
+  std::vector<int32_t> branch((size_t)nt), kin((size_t)nt);
+  std::vector<double> t((size_t)nt), dz((size_t)nt);
+  if (mckpp_host_vaxis_map(ns, zs, nt, zt, branch.data(), kin.data(), t.data(), dz.data()))
+    return fail("%s: the model's zm is not finite and strictly decreasing", who);
+  std::vector<mckpp_vaxis_ent> tab((size_t)nt);
+  for (int j = 0; j < nt; ++j) tab[(size_t)j] = mckpp_vaxis_ent{branch[(size_t)j], kin[(size_t)j], t[(size_t)j], dz[(size_t)j]};
+  HIPCHK(d.alloc((size_t)nt));
+  HIPCHK(hipMemcpy(d, tab.data(), (size_t)nt * sizeof(mckpp_vaxis_ent), hipMemcpyHostToDevice));
+  return 0;
+}
+
+int vaxis_define(mckpp_hip_ctx *h, const char *who, int axis, int32_t n, const double *z)
+{
+  if (axis < 0 || axis >= MCKPP_VAXES) return fail("%s: axis %d (0..%d)", who, axis, MCKPP_VAXES - 1);
+  if (n < 0 || n == 1 || n > MCKPP_VAXIS_LEVELS_MAX)
+    return fail("%s: axis %d: n=%d levels (2..%d, or 0 to drop the axis)", who, axis, n, MCKPP_VAXIS_LEVELS_MAX);
+  if (n > 0) {
+    if (!z) return fail("%s: axis %d: z is null", who, axis);
+    for (int k = 0; k < n; ++k) {
+      if (!std::isfinite(z[k])) return fail("%s: axis %d: z[%d] is not finite", who, axis, k);
+      if (k > 0 && !(z[k] < z[k - 1]))
+        return fail("%s: axis %d: z[%d]=%.17g is not below z[%d]=%.17g: an axis holds heights, strictly decreasing like zm", who,
+                    axis, k, z[k], k - 1, z[k - 1]);
+    }
+  }
+  HIPCHK(hipSetDevice(h->device));
+  mckpp_hip_ctx::vaxis next;
+  if (n > 0) {
+    next.z.assign(z, z + n);
+    if (vaxis_table(who, n, z, h->nzp1, h->h_zm.data(), next.d_in)) return -1;
+    if (vaxis_table(who, h->nzp1, h->h_zm.data(), n, z, next.d_out)) return -1;
+  }
+  HIPCHK(hipStreamSynchronize(h->stream));   // (a launch in flight may read the tables this replaces)
+  h->vax[axis] = std::move(next);
+  return 0;
+}
+
+// the axis of planes[k] (or of member `what` of the profiles), defined; null, and the refusal, otherwise
+const mckpp_hip_ctx::vaxis *vaxis_of(mckpp_hip_ctx *h, const char *who, const char *what, int axis)
+{
+  if (axis >= 0 && axis < MCKPP_VAXES && !h->vax[axis].z.empty()) return &h->vax[axis];
+  fail("%s: %s: axis %d is not defined (mckpp_hip_vaxis_define; axes are 0..%d)", who, what, axis, MCKPP_VAXES - 1);
+  return nullptr;
+}
+
+struct vaxis_puts {
+  std::vector<mckpp_vaxis_put_plane> tab;
+  std::vector<size_t> bytes;   // of each plane's `in`
+};
+
+// The planes of a put on caller axes, checked and resolved into the kernel's table: put_resolve's checks, then the axis.
+int vaxis_put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, bool dev_form,
+                    vaxis_puts &r, int *dev)
+{
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (nplanes < 0 || nplanes > MCKPP_VAXIS_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_VAXIS_PLANES_MAX);
+  HIPCHK(hipSetDevice(h->device));
+  r.tab.clear();
+  r.bytes.clear();
+  int prof[MCKPP_VAXIS_PLANES_MAX];
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_vaxis_put_plane_c &q = planes[k];
+    mckpp_vaxis_put_plane e{};
+    int row;
+    size_t elem;
+    if (put_resolve(h, who, k, q.field, 0, h->nzp1, q.dtype, q.op, q.flags, q.skip_value, e.put, &row, &elem)) return -1;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d]", k);
+    const mckpp_hip_ctx::vaxis *ax = vaxis_of(h, who, arg, q.axis);
+    if (!ax) return -1;
+    for (int j = 0; j < k; ++j)
+      if (prof[j] == row)
+        return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d): a plane writes the whole profile, and the "
+                    "planes of a call have no order", who, k, j, q.field, planes[j].field);
+    prof[k] = row;
+    const size_t bytes = (size_t)h->npts * ax->z.size() * elem;
+    snprintf(arg, sizeof arg, "planes[%d].in", k);
+    if (!dev_form) {
+      if (!q.in) return fail("%s: %s is null", who, arg);
+    } else if (dev_ptr_check(h, who, arg, q.in, bytes, k == 0 ? dev : nullptr)) {
+      return -1;
+    }
+    e.put.in = q.in;
+    e.skip = e.put.skip;   // decided on the input side, where the values the branch reads are: put_element's own is off
+    e.put.skip = 0;
+    e.tab = ax->d_in;
+    r.tab.push_back(e);
+    r.bytes.push_back(bytes);
+  }
+  return 0;
+}
+
+// the table onto the device on the context's stream, a wait for `produced` (null: none), the launch, ev_read behind it
+int vaxis_put_queue(mckpp_hip_ctx *h, const std::vector<mckpp_vaxis_put_plane> &tab, hipEvent_t produced)
+{
+  if (tab.empty() || h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(h->vput_tab.put(tab, h->stream));
+  if (produced) HIPCHK(hipStreamWaitEvent(h->stream, produced, 0));
+  HIPCHK(mckpp_launch_vaxis_put_planes(h->vput_tab, (int)tab.size(), h->nzp1, h->d_ipt, h->ncol, h->npts, h->d_cs, h->stream));
+  HIPCHK(h->ev_read.record(h->stream));
+  return 0;
+}
+
+// the host forms: every plane as it is into the context's put staging (each at a multiple of 256 bytes) on the
+// context's stream, ahead of the launch that reads it there
+int vaxis_stage(mckpp_hip_ctx *h, vaxis_puts &r)
+{
+  HIPCHK(hipSetDevice(h->device));
+  std::vector<size_t> at(r.tab.size());
+  size_t total = 0;
+  for (size_t k = 0; k < r.tab.size(); ++k) {
+    at[k] = total;
+    total += (r.bytes[k] + 255) / 256 * 256;
+  }
+  HIPCHK(h->d_put_stage.reserve(total));   // (every call that read the staging ended with a wait)
+  for (size_t k = 0; k < r.tab.size(); ++k) {
+    HIPCHK(hipMemcpyAsync(h->d_put_stage + at[k], r.tab[k].put.in, r.bytes[k], hipMemcpyHostToDevice, h->stream));
+    r.tab[k].put.in = h->d_put_stage + at[k];
+  }
+  return 0;
+}
+
+int vaxis_put_host_queue(mckpp_hip_ctx *h, vaxis_puts &r)
+{
+  if (r.tab.empty() || h->ncol == 0) return 0;
+  if (vaxis_stage(h, r) || vaxis_put_queue(h, r.tab, nullptr)) return -1;
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// The profiles of mckpp_hip_vaxis_init_profiles as four planes of k_vaxis_put_planes: plain sets - S as it is
+// interpolated, Sref is formed from it afterwards -, U and V into U_init and V_init too, T raising the Kelvin word.
+int vaxis_profiles_check(mckpp_hip_ctx *h, const char *who, const mckpp_vaxis_profiles_c *p, bool dev_form, vaxis_puts &r, int *dev)
+{
+  if (!p) return fail("%s: null argument", who);
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  HIPCHK(hipSetDevice(h->device));
+  const size_t elem = p->dtype == MCKPP_EXP_F64 ? sizeof(double) : p->dtype == MCKPP_EXP_F32 ? sizeof(float) : 0;
+  if (!elem) return fail("%s: dtype %d (MCKPP_EXP_F64 1, MCKPP_EXP_F32 2)", who, p->dtype);
+  if (!std::isfinite(p->tk0)) return fail("%s: tk0 is not finite", who);
+  struct { const char *name; const void *in; int axis, row, row2; } m[4] = {
+    {"u", p->u, p->axis_vel, P_U, P_UINIT}, {"v", p->v, p->axis_vel, P_V, P_VINIT},
+    {"temp", p->temp, p->axis_temp, P_T, -1}, {"sal", p->sal, p->axis_sal, P_S, -1}};
+  r.tab.clear();
+  r.bytes.clear();
+  for (int k = 0; k < 4; ++k) {
+    const mckpp_hip_ctx::vaxis *ax = vaxis_of(h, who, m[k].name, m[k].axis);
+    if (!ax) return -1;
+    const size_t bytes = (size_t)h->npts * ax->z.size() * elem;
+    if (!dev_form) {
+      if (!m[k].in) return fail("%s: %s is null", who, m[k].name);
+    } else if (dev_ptr_check(h, who, m[k].name, m[k].in, bytes, k == 0 ? dev : nullptr)) {
+      return -1;
+    }
+    mckpp_vaxis_put_plane e{};
+    e.put = mckpp_put_plane{m[k].in, h->d_prof[m[k].row].get(), nullptr, nullptr, 0.0, h->ld, 0, h->nzp1,
+                            p->dtype == MCKPP_EXP_F32 ? 1 : 0, 0, 0, 0, -1, 0};
+    e.tab = ax->d_in;
+    e.row2 = m[k].row2 >= 0 ? h->d_prof[m[k].row2].get() : nullptr;
+    r.tab.push_back(e);
+    r.bytes.push_back(bytes);
+  }
+  return 0;
+}
+
+// first half: the Kelvin word cleared, the four planes written (host form: staged first); *kelvin: the word, read back
+int vaxis_profiles_write(mckpp_hip_ctx *h, vaxis_puts &r, bool dev_form, hipEvent_t produced, unsigned *kelvin)
+{
+  *kelvin = 0;
+  if (h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (!dev_form && vaxis_stage(h, r)) return -1;
+  if (!h->d_kelvin) HIPCHK(h->d_kelvin.alloc(1));
+  for (auto &e : r.tab)
+    if (e.put.row == h->d_prof[P_T].get()) e.kelvin = h->d_kelvin;   // the temperature plane raises the word
+  HIPCHK(hipMemsetAsync(h->d_kelvin, 0, sizeof(unsigned), h->stream));
+  if (vaxis_put_queue(h, r.tab, produced)) return -1;
+  HIPCHK(hipMemcpyAsync(kelvin, h->d_kelvin, sizeof(unsigned), hipMemcpyDeviceToHost, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// second half: the rule for `kelvin` - this context's word, or every shard's combined - and the references; waits
+int vaxis_profiles_finish(mckpp_hip_ctx *h, double tk0, unsigned kelvin, bool combined)
+{
+  if (h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (combined) HIPCHK(hipMemcpyAsync(h->d_kelvin, &kelvin, sizeof(unsigned), hipMemcpyHostToDevice, h->stream));
+  HIPCHK(mckpp_launch_vaxis_init_finish(h->d_prof[P_T], h->d_prof[P_S], h->ld, h->nzp1, h->ncol, h->d_cs, h->d_kelvin, tk0,
+                                        h->c.L_SSref ? 1 : 0, h->stream));
+  HIPCHK(hipStreamSynchronize(h->stream));
+  return 0;
+}
+
+// the interface-axis fields (src/mckpp_xios_io.F90: 0..nz), which no caller axis of heights like zm describes
+const char *vaxis_interface_name(int field)
+{
+  switch (field) {
+    case MCKPP_OUT_WU: return "wu";
+    case MCKPP_OUT_WV: return "wv";
+    case MCKPP_OUT_WT: return "wT";
+    case MCKPP_OUT_WS: return "wS";
+    case MCKPP_OUT_WB: return "wB";
+    case MCKPP_OUT_WTNT: return "wTnt";
+    case MCKPP_OUT_DIFM: return "difm";
+    case MCKPP_OUT_DIFT: return "dift";
+    case MCKPP_OUT_DIFS: return "difs";
+    default: return nullptr;
+  }
+}
+
+// The planes of a fetch on caller axes, checked and resolved into the kernel's table; *any_fill: a plane fills the land
+int vaxis_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes,
+                      std::vector<mckpp_vaxis_fetch_plane> &tab, int *maxlev, bool *any_fill, int *dev)
+{
+  if (nplanes < 0 || nplanes > MCKPP_VAXIS_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_VAXIS_PLANES_MAX);
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  HIPCHK(hipSetDevice(h->device));
+  tab.clear();
+  *maxlev = 0;
+  *any_fill = false;
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_vaxis_dev_plane_c &q = planes[k];
+    if (q.field < 0 || q.field >= MCKPP_OUT_COUNT) return fail("%s: planes[%d]: unknown output field %d", who, k, q.field);
+    if (const char *name = vaxis_interface_name(q.field))
+      return fail("%s: planes[%d]: field %d (%s) lives on the interface axis 0..nz, not on the levels zm(1:nzp1) a caller's axis "
+                  "is interpolated from", who, k, q.field, name);
+    out_desc d;
+    if (out_field(h, q.field, d)) return -1;
+    if (d.nlev == 1)
+      return fail("%s: planes[%d]: field %d%s is two-dimensional: it has no vertical axis to interpolate", who, k, q.field,
+                  q.field == MCKPP_OUT_HMIX ? " (hmix)" : "");
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d]", k);
+    const mckpp_hip_ctx::vaxis *ax = vaxis_of(h, who, arg, q.axis);
+    if (!ax) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    const int n = (int)ax->z.size();
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    if (!elem || dev_ptr_check(h, who, arg, q.out, (size_t)h->npts * (size_t)n * elem, k == 0 ? dev : nullptr)) return -1;
+    tab.push_back(mckpp_vaxis_fetch_plane{mckpp_fetch_plane{d.src, q.out, q.land_value, d.ld, d.off, n, d.add_sref,
+                                                            q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.fill_land ? 1 : 0},
+                                          ax->d_out});
+    *maxlev = std::max(*maxlev, n);
+    *any_fill = *any_fill || q.fill_land;
+  }
+  return 0;
+}
+
+int vaxis_fetch_queue(mckpp_hip_ctx *h, const std::vector<mckpp_vaxis_fetch_plane> &tab, int maxlev, bool any_fill,
+                      hipEvent_t before, void *consumer_stream)
+{
+  if (tab.empty()) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  if (any_fill && land_own(h)) return -1;
+  HIPCHK(h->vfetch_tab.put(tab, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
+  HIPCHK(mckpp_launch_vaxis_fetch_planes(h->vfetch_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
+                                         any_fill ? h->d_land.get() : nullptr, any_fill ? h->nland : 0, h->stream));
+  HIPCHK(h->ev_delivered.record(h->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_vaxis_define(mckpp_hip_handle h, int axis, int32_t n, const double *z)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return vaxis_define(h, who, axis, n, z); });
+}
+
+int mckpp_hip_vaxis_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  vaxis_puts r;
+  if (vaxis_put_check(h, who, nplanes, planes, true, r, nullptr)) return -1;
+  if (r.tab.empty() || h->ncol == 0) return 0;
+  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return vaxis_put_queue(h, r.tab, h->ev_caller);
+  });
+}
+
+int mckpp_hip_vaxis_put_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  vaxis_puts r;
+  if (vaxis_put_check(h, who, nplanes, planes, false, r, nullptr)) return -1;
+  return vaxis_put_host_queue(h, r);
+  });
+}
+
+int mckpp_hip_vaxis_init_profiles_dev(mckpp_hip_handle h, const mckpp_vaxis_profiles_c *p, void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  vaxis_puts r;
+  unsigned kelvin = 0;
+  if (vaxis_profiles_check(h, who, p, true, r, nullptr)) return -1;
+  if (h->ncol == 0) return 0;
+  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  if (vaxis_profiles_write(h, r, true, h->ev_caller, &kelvin)) return -1;
+  return vaxis_profiles_finish(h, p->tk0, kelvin, false);
+  });
+}
+
+int mckpp_hip_vaxis_init_profiles_host(mckpp_hip_handle h, const mckpp_vaxis_profiles_c *p)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  vaxis_puts r;
+  unsigned kelvin = 0;
+  if (vaxis_profiles_check(h, who, p, false, r, nullptr)) return -1;
+  if (vaxis_profiles_write(h, r, false, nullptr, &kelvin)) return -1;
+  return vaxis_profiles_finish(h, p->tk0, kelvin, false);
+  });
+}
+
+int mckpp_hip_vaxis_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  std::vector<mckpp_vaxis_fetch_plane> tab;
+  int maxlev = 0;
+  bool any_fill = false;
+  if (vaxis_fetch_check(h, who, nplanes, planes, tab, &maxlev, &any_fill, nullptr)) return -1;
+  if (tab.empty()) return 0;
+  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complement again)
+  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
+  return vaxis_fetch_queue(h, tab, maxlev, any_fill, h->ev_caller, consumer_stream);
   });
 }
 
@@ -4822,6 +5196,95 @@ int mckpp_hip_multi_put_host(mckpp_hip_multi_handle m, int32_t nplanes, const mc
     if (put_check(m->ctx[d], who, nplanes, planes, false, tabs[(size_t)d], &maxlev, nullptr)) return -1;
   for (int d = 0; d < ndev; ++d)
     if (put_host_queue(m->ctx[d], tabs[(size_t)d], maxlev)) return -1;
+  return 0;
+  });
+}
+
+// include/mckpp_hip_vaxis.h over all shards: an axis on every shard; the same planes for every shard, which touches its
+// own columns only; every shard checked before any of them queues
+int mckpp_hip_multi_vaxis_define(mckpp_hip_multi_handle m, int axis, int32_t n, const double *z)
+{
+  return multi_each(__func__, m, [&, who = __func__](auto *x) { return vaxis_define(x, who, axis, n, z); });
+}
+
+int mckpp_hip_multi_vaxis_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<vaxis_puts> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_put_check(m->ctx[d], who, nplanes, planes, true, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_put_queue(m->ctx[d], rs[(size_t)d].tab, m->ev_caller)) return -1;
+  return 0;
+  });
+}
+
+int mckpp_hip_multi_vaxis_put_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<vaxis_puts> rs((size_t)ndev);
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_put_check(m->ctx[d], who, nplanes, planes, false, rs[(size_t)d], nullptr)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_put_host_queue(m->ctx[d], rs[(size_t)d])) return -1;
+  return 0;
+  });
+}
+
+// the profiles: every shard writes its columns and reports its Kelvin word; the host combines them - the call waits,
+// like the upload it follows - and every shard finishes under the combined word
+static int multi_vaxis_profiles(mckpp_hip_multi *m, const char *who, const mckpp_vaxis_profiles_c *p, bool dev_form, void *producer_stream)
+{
+  const int ndev = (int)m->ctx.size();
+  std::vector<vaxis_puts> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_profiles_check(m->ctx[d], who, p, dev_form, rs[(size_t)d], dev_form ? &dev : nullptr)) return -1;
+  if (dev_form && multi_caller_event(m, dev, producer_stream)) return -1;
+  unsigned any = 0;
+  for (int d = 0; d < ndev; ++d) {
+    unsigned kelvin = 0;
+    if (vaxis_profiles_write(m->ctx[d], rs[(size_t)d], dev_form, dev_form ? (hipEvent_t)m->ev_caller : nullptr, &kelvin)) return -1;
+    any |= kelvin;
+  }
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_profiles_finish(m->ctx[d], p->tk0, any, true)) return -1;
+  return 0;
+}
+
+int mckpp_hip_multi_vaxis_init_profiles_dev(mckpp_hip_multi_handle m, const mckpp_vaxis_profiles_c *p, void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return multi_vaxis_profiles(m, who, p, true, producer_stream); });
+}
+
+int mckpp_hip_multi_vaxis_init_profiles_host(mckpp_hip_multi_handle m, const mckpp_vaxis_profiles_c *p)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return multi_vaxis_profiles(m, who, p, false, nullptr); });
+}
+
+int mckpp_hip_multi_vaxis_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<std::vector<mckpp_vaxis_fetch_plane>> tabs((size_t)ndev);
+  int maxlev = 0, dev = -1;
+  bool any_fill = false;
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_fetch_check(m->ctx[d], who, nplanes, planes, tabs[(size_t)d], &maxlev, &any_fill, &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (any_fill) {   // shard 0 fills the points that no shard holds, the others fill none: every point is written once
+    for (int d = 1; d < ndev; ++d)
+      for (auto &e : tabs[(size_t)d]) e.f.fill_land = 0;
+    if (multi_land(m, who)) return -1;
+  }
+  if (multi_caller_event(m, dev, consumer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (vaxis_fetch_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
   return 0;
   });
 }

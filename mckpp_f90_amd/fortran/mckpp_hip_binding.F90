@@ -1,5 +1,5 @@
 !> iso_c_binding view of include/mckpp_hip.h and of its companions
-!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h and mckpp_hip_put.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h and mckpp_hip_vaxis.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -80,6 +80,31 @@ module mckpp_hip_binding
   integer(c_int32_t), parameter :: MCKPP_PUT_SET = 0, MCKPP_PUT_ADD = 1
   integer(c_int32_t), parameter :: MCKPP_PUT_SKIP = 1, MCKPP_PUT_TIME_LEVELS = 2
   integer(c_int32_t), parameter :: MCKPP_PUT_PLANES_MAX = 64
+
+  !> the caller's vertical axes (include/mckpp_hip_vaxis.h): MCKPP_VAXES axes per context, each 2 .. MCKPP_VAXIS_LEVELS_MAX
+  !! heights, strictly decreasing like zm; the branch of an entry of mckpp_host_vaxis_map's table
+  integer(c_int32_t), parameter :: MCKPP_VAXES = 8, MCKPP_VAXIS_LEVELS_MAX = 1024, MCKPP_VAXIS_PLANES_MAX = 64
+  integer(c_int32_t), parameter :: MCKPP_VAXIS_ABOVE = 0, MCKPP_VAXIS_BELOW = 1, MCKPP_VAXIS_BRACKET = 2
+  !> one plane of mckpp_hip_vaxis_put_dev / _put_host: the array at `in`, (npts, n of axis `axis`) of MCKPP_EXP_F64 or
+  !! MCKPP_EXP_F32, interpolated onto every model level of state field `field`; op and flags are mckpp_put_plane_c's
+  type, bind(C) :: mckpp_vaxis_put_plane_c
+    integer(c_int32_t) :: field, axis, dtype, op, flags
+    real(c_double) :: skip_value
+    type(c_ptr) :: in
+  end type mckpp_vaxis_put_plane_c
+  !> the reference's initial profiles on their own axes (mckpp_hip_vaxis_init_profiles_dev / _host): u, v (npts, n of
+  !! axis_vel), temp (npts, n of axis_temp), sal (npts, n of axis_sal), all of `dtype`; tk0: what the Kelvin rule subtracts
+  type, bind(C) :: mckpp_vaxis_profiles_c
+    integer(c_int32_t) :: axis_vel, axis_temp, axis_sal, dtype
+    real(c_double) :: tk0
+    type(c_ptr) :: u, v, temp, sal
+  end type mckpp_vaxis_profiles_c
+  !> one plane of mckpp_hip_vaxis_fetch_dev: `field` as it stands, interpolated onto axis `axis`, into out (npts, n)
+  type, bind(C) :: mckpp_vaxis_dev_plane_c
+    integer(c_int32_t) :: field, axis, dtype, fill_land
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_vaxis_dev_plane_c
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -893,6 +918,99 @@ module mckpp_hip_binding
       type(c_ptr), value :: m
       integer(c_int32_t), value :: nplanes
       type(mckpp_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! the caller's vertical axes (include/mckpp_hip_vaxis.h): axes defined per context, state in and the reference's
+    ! initial profiles on the caller's levels, fields out on them.  As with the puts, the host's kpp_3d_fields copy of
+    ! what these write is stale afterwards, and the session layer does not see it
+    function mckpp_host_vaxis_map(ns, zs, nt, zt, branch, kin, t, dz) bind(C, name="mckpp_host_vaxis_map") result(rc)
+      import :: c_int, c_int32_t, c_double
+      integer(c_int32_t), value :: ns, nt
+      real(c_double), intent(in) :: zs(*), zt(*)
+      integer(c_int32_t), intent(out) :: branch(*), kin(*)
+      real(c_double), intent(out) :: t(*), dz(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vaxis_define(handle, axis, n, z) bind(C, name="mckpp_hip_vaxis_define") result(rc)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: axis
+      integer(c_int32_t), value :: n
+      real(c_double), intent(in) :: z(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vaxis_put_dev(handle, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_vaxis_put_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_put_plane_c
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vaxis_put_host(handle, nplanes, planes) bind(C, name="mckpp_hip_vaxis_put_host") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_put_plane_c
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vaxis_init_profiles_dev(handle, p, producer_stream) bind(C, name="mckpp_hip_vaxis_init_profiles_dev") result(rc)
+      import :: c_int, c_ptr, mckpp_vaxis_profiles_c
+      type(c_ptr), value :: handle, producer_stream
+      type(mckpp_vaxis_profiles_c), intent(in) :: p
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vaxis_init_profiles_host(handle, p) bind(C, name="mckpp_hip_vaxis_init_profiles_host") result(rc)
+      import :: c_int, c_ptr, mckpp_vaxis_profiles_c
+      type(c_ptr), value :: handle
+      type(mckpp_vaxis_profiles_c), intent(in) :: p
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vaxis_fetch_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_vaxis_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_dev_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_dev_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vaxis_define(m, axis, n, z) bind(C, name="mckpp_hip_multi_vaxis_define") result(rc)
+      import :: c_int, c_int32_t, c_double, c_ptr
+      type(c_ptr), value :: m
+      integer(c_int), value :: axis
+      integer(c_int32_t), value :: n
+      real(c_double), intent(in) :: z(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vaxis_put_dev(m, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_multi_vaxis_put_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_put_plane_c
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vaxis_put_host(m, nplanes, planes) bind(C, name="mckpp_hip_multi_vaxis_put_host") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_put_plane_c
+      type(c_ptr), value :: m
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vaxis_init_profiles_dev(m, p, producer_stream) bind(C, name="mckpp_hip_multi_vaxis_init_profiles_dev") result(rc)
+      import :: c_int, c_ptr, mckpp_vaxis_profiles_c
+      type(c_ptr), value :: m, producer_stream
+      type(mckpp_vaxis_profiles_c), intent(in) :: p
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vaxis_init_profiles_host(m, p) bind(C, name="mckpp_hip_multi_vaxis_init_profiles_host") result(rc)
+      import :: c_int, c_ptr, mckpp_vaxis_profiles_c
+      type(c_ptr), value :: m
+      type(mckpp_vaxis_profiles_c), intent(in) :: p
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vaxis_fetch_dev(m, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_multi_vaxis_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_dev_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_dev_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
