@@ -23,7 +23,8 @@ have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, 
 (include/mckpp_hip_device_records.h) are the fourth table, _SIGNATURES_RECORDS, and one more method of _DeviceArrays;
 the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _SIGNATURES_PUT, and two more methods there;
 records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixth, _SIGNATURES_REDUCE, and three more;
-the caller's vertical axes (include/mckpp_hip_vaxis.h) are the seventh, _SIGNATURES_VAXIS, and the mixin _VerticalAxes.
+the caller's vertical axes (include/mckpp_hip_vaxis.h) are the seventh, _SIGNATURES_VAXIS, and the mixin _VerticalAxes;
+the caller's horizontal grids (include/mckpp_hip_hgrid.h) are the eighth, _SIGNATURES_HGRID, and the mixin _HorizontalGrids.
 """
 import ctypes as C
 import sys
@@ -459,6 +460,32 @@ _SIGNATURES_VAXIS = {
 }
 
 
+class _HgridTableC(C.Structure):
+    """mckpp_hgrid_table_c"""
+    _fields_ = [("ptr", _i64p), ("idx", _ip), ("w", _dp)]
+
+
+class _HgridPlaneC(C.Structure):
+    """mckpp_hgrid_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "lev0", "nlev", "dtype", "grid", "norm", "fill_land")] + \
+               [("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_hgrid.h, the caller's horizontal grids, in the same form; tests/test_hgrid_cpu.py
+# holds this table to that header.
+_hgtp, _u8p = C.POINTER(_HgridTableC), C.POINTER(C.c_ubyte)
+_SIGNATURES_HGRID = {
+    "mckpp_host_hgrid_check": _sig(C.c_char_p, _i64, _i64, _hgtp, C.c_char_p, _i64),
+    "mckpp_host_hgrid_apply": _sig(_i64, _hgtp, _dp, _u8p, _i, _i, _d, _dp),
+    "mckpp_host_hgrid_slices": _sig(_i64, _i64p, _hgtp, _u8p, _i64p, _ip, _ip, _dp, res=_i64),
+    "mckpp_hip_hgrid_define": _sig(_H, _i, _i64, _hgtp, _hgtp, twin=True),
+    "mckpp_hip_hgrid_info": _sig(_H, _i, _i64p, twin=True),
+    "mckpp_hip_hgrid_fluxes_dev": _sig(_H, _i, _i, _voidpp, _i, _d, _d, C.c_void_p, twin=True),
+    "mckpp_hip_hgrid_flux_ring_put_dev": _sig(_H, _i, _i, _voidpp, C.c_void_p, twin=True),
+    "mckpp_hip_hgrid_fetch_dev": _sig(_H, _i32, C.POINTER(_HgridPlaneC), C.c_void_p, twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -504,6 +531,11 @@ def _signatures_vaxis():
     return _spelled(_SIGNATURES_VAXIS)
 
 
+def _signatures_hgrid():
+    """... and of every function of mckpp_hip_hgrid.h."""
+    return _spelled(_SIGNATURES_HGRID)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
@@ -511,7 +543,7 @@ def _bind(lib):
     # everything else works with it, and a call of that name fails there by name
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
                                   **_signatures_records(), **_signatures_put(), **_signatures_reduce(),
-                                  **_signatures_vaxis()}.items():
+                                  **_signatures_vaxis(), **_signatures_hgrid()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -1426,7 +1458,204 @@ class _VerticalAxes:
         self._call("vaxis_fetch_dev", len(planes), arr, _dev_stream(stream))
 
 
-class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays, _VerticalAxes):
+# the caller's horizontal grids (MCKPP_HGRIDS, MCKPP_HGRID_NORM_* of mckpp_hip_hgrid.h)
+HGRIDS = 4
+HGRID_NORM_NONE, HGRID_NORM_USED = 0, 1
+_HGRID_NORMS = {"none": HGRID_NORM_NONE, "used": HGRID_NORM_USED}
+
+
+class _HgridTable:
+    """A weight table as the library takes it: the three CSR arrays of the right element types, kept alive, and the
+    mckpp_hgrid_table_c that points at them.  `table` is a (ptr, idx, w) triple or anything with the CSR attributes
+    indptr, indices and data (scipy is not needed).  Only the shapes are checked here: the values are the library's to
+    check (mckpp_host_hgrid_check), so that its messages are the ones a caller sees."""
+
+    def __init__(self, who, table, nrows):
+        if hasattr(table, "indptr") and hasattr(table, "indices") and hasattr(table, "data"):
+            table = (table.indptr, table.indices, table.data)
+        if not isinstance(table, (tuple, list)) or len(table) != 3:
+            raise ValueError(f"{who}: a table is a (ptr, idx, w) triple or an object with indptr, indices and data")
+        self.ptr = np.ascontiguousarray(table[0], dtype=np.int64)
+        self.idx = np.ascontiguousarray(table[1], dtype=np.int32)
+        self.w = np.ascontiguousarray(table[2], dtype=np.float64)
+        if self.ptr.ndim != 1 or self.ptr.size != nrows + 1:
+            raise ValueError(f"{who}: ptr has shape {self.ptr.shape}; the table has {nrows} rows, so ptr has {nrows + 1} elements")
+        if self.idx.ndim != 1 or self.w.ndim != 1 or self.idx.size != self.w.size:
+            raise ValueError(f"{who}: idx has shape {self.idx.shape} and w {self.w.shape}; they hold an element per entry")
+        if self.idx.size < int(self.ptr.max(initial=0)):
+            raise ValueError(f"{who}: ptr names entry {int(self.ptr.max()) - 1}, idx and w hold {self.idx.size}")
+        self.c = _HgridTableC(self.ptr.ctypes.data_as(_i64p), self.idx.ctypes.data_as(_ip), self.w.ctypes.data_as(_dp))
+
+
+def host_hgrid_check(name, table, nrows, nsrc):
+    """None if `table` of nrows rows over source indices 0 .. nsrc - 1 passes the checks of hgrid_define, else the
+    refusal's text, which names the table, the row and the entry: mckpp_host_hgrid_check.  No GPU."""
+    t = _HgridTable("host_hgrid_check", table, nrows)
+    msg = C.create_string_buffer(256)
+    rc = _lib().mckpp_host_hgrid_check(str(name).encode(), int(nrows), int(nsrc), C.byref(t.c), msg, 256)
+    return None if rc == 0 else msg.value.decode()
+
+
+def host_hgrid_apply(table, x, nrows, used=None, norm=None, fill=True, land_value=1e20, out=None):
+    """One level through a weight table exactly as include/mckpp_hip_hgrid.h states the arithmetic:
+    mckpp_host_hgrid_apply, the yardstick of the device's results.  x: the source values; used: per source index whether
+    entries reading it are used (None: all); norm None: the in direction; "none" / "used": the out direction, where a
+    row without a used entry gets land_value (fill) or keeps what `out` held.  Returns the nrows values.  No GPU."""
+    t = _HgridTable("host_hgrid_apply", table, nrows)
+    x = np.ascontiguousarray(x, dtype=np.float64).ravel()
+    if t.idx.size and (int(t.idx.min()) < 0 or int(t.idx.max()) >= x.size):
+        raise ValueError(f"host_hgrid_apply: an index outside the {x.size} source values")
+    u = None
+    if used is not None:
+        u = np.ascontiguousarray(used, dtype=np.uint8).ravel()
+        if u.size != x.size:
+            raise ValueError(f"host_hgrid_apply: used has {u.size} elements, x has {x.size}")
+    res = np.zeros(nrows) if out is None else np.ascontiguousarray(out, dtype=np.float64).ravel().copy()
+    if res.size != nrows:
+        raise ValueError(f"host_hgrid_apply: out has {res.size} elements, the table has {nrows} rows")
+    rc = _lib().mckpp_host_hgrid_apply(int(nrows), C.byref(t.c), x.ctypes.data_as(_dp), None if u is None else u.ctypes.data_as(_u8p),
+                                       -1 if norm is None else _hgrid_norm("host_hgrid_apply", norm), int(bool(fill)),
+                                       float(land_value), res.ctypes.data_as(_dp))
+    if rc != 0:
+        raise ValueError("host_hgrid_apply: refused")
+    return res
+
+
+def host_hgrid_slices(table, nrows, rows=None, keep=None):
+    """(slice_off, len, idx, w): the device layout - a sliced ELL, 64 rows per slice - of the listed rows (None: all) of
+    `table` without the entries whose source index `keep` (None: none dropped) does not mark:
+    mckpp_host_hgrid_slices.  No GPU."""
+    t = _HgridTable("host_hgrid_slices", table, nrows)
+    r = None if rows is None else np.ascontiguousarray(rows, dtype=np.int64).ravel()
+    if r is not None and r.size and (int(r.min()) < 0 or int(r.max()) >= nrows):
+        raise ValueError(f"host_hgrid_slices: a listed row outside the table's {nrows}")
+    k = None if keep is None else np.ascontiguousarray(keep, dtype=np.uint8).ravel()
+    if k is not None and t.idx.size and int(t.idx.max()) >= k.size:
+        raise ValueError(f"host_hgrid_slices: keep has {k.size} elements, the table names index {int(t.idx.max())}")
+    nlist = nrows if r is None else r.size
+    off, ln = np.zeros((nlist + 63) // 64 + 1, dtype=np.int64), np.zeros(max(nlist, 1), dtype=np.int32)
+    args = (nlist, None if r is None else r.ctypes.data_as(_i64p), C.byref(t.c), None if k is None else k.ctypes.data_as(_u8p),
+            off.ctypes.data_as(_i64p), ln.ctypes.data_as(_ip))
+    padded = int(_lib().mckpp_host_hgrid_slices(*args, None, None))
+    if padded < 0:
+        raise ValueError("host_hgrid_slices: refused")
+    idx, w = np.zeros(max(padded, 1), dtype=np.int32), np.zeros(max(padded, 1))
+    _lib().mckpp_host_hgrid_slices(*args, idx.ctypes.data_as(_ip), w.ctypes.data_as(_dp))
+    return off, ln[:nlist], idx[:padded], w[:padded]
+
+
+def _hgrid_norm(who, norm):
+    if isinstance(norm, str) and norm in _HGRID_NORMS:
+        return _HGRID_NORMS[norm]
+    if isinstance(norm, (int, np.integer)) and not isinstance(norm, bool):
+        return int(norm)   # (an unknown number is the library's to refuse, by planes[k])
+    raise ValueError(f"{who}: norm {norm!r} (\"none\", \"used\", or HGRID_NORM_NONE, HGRID_NORM_USED)")
+
+
+class _HorizontalGrids:
+    """The caller's horizontal grids (include/mckpp_hip_hgrid.h): forcing in from arrays on a caller's grid and fields
+    out onto it, by remap weights the caller brings as CSR tables.  An array on grid g is (n_g,) or (nlev, n_g)."""
+
+    def _hgrids(self):
+        return self.__dict__.setdefault("_hgrid_n", {})
+
+    def _hgrid(self, who, grid):
+        """the number of points of a defined grid"""
+        if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or int(grid) not in self._hgrids():
+            raise ValueError(f"{who}: grid {grid!r} is not defined (hgrid_define; grids are 0 .. {HGRIDS - 1})")
+        return self._hgrids()[int(grid)]
+
+    def hgrid_define(self, grid, n, table_in=None, table_out=None):
+        """Caller grid `grid` (0 .. HGRIDS - 1) of n points.  table_in (caller -> model): npts rows over the caller's
+        points; table_out (model -> caller): n rows over the model's points; each a (ptr, idx, w) CSR triple or an object
+        with indptr, indices and data, or None - that direction is then refused when used.  n = 0 drops the grid.  After
+        the first upload or load_restart; the handle keeps the grid over later ones."""
+        if isinstance(grid, bool) or not isinstance(grid, (int, np.integer)) or not 0 <= int(grid) < HGRIDS:
+            raise ValueError(f"hgrid_define: grid {grid!r} (0 .. {HGRIDS - 1})")
+        n = int(n)
+        if n < 0:
+            raise ValueError(f"hgrid_define: n={n}")
+        if n and not self._npts:
+            raise ValueError("hgrid_define: upload the state first: the tables are checked against the grid's size")
+        tin = None if n == 0 or table_in is None else _HgridTable("hgrid_define: table_in", table_in, self._npts)
+        tout = None if n == 0 or table_out is None else _HgridTable("hgrid_define: table_out", table_out, n)
+        self._call("hgrid_define", int(grid), n, None if tin is None else C.byref(tin.c), None if tout is None else C.byref(tout.c))
+        if n:
+            self._hgrids()[int(grid)] = n
+        else:
+            self._hgrids().pop(int(grid), None)
+
+    def hgrid_info(self, grid):
+        """n, the entries (nnz_in, nnz_out; -1: no such table), the padded sizes of the device tables for the present
+        resident state (padded_in, padded_out) and the longest row of either table, as a dict."""
+        self._hgrid("hgrid_info", grid)
+        info = (C.c_int64 * 6)()
+        self._call("hgrid_info", int(grid), info)
+        return dict(zip(("n", "nnz_in", "nnz_out", "padded_in", "padded_out", "longest_row"), (int(v) for v in info)))
+
+    def _hgrid_fields(self, who, grid, fields):
+        """fields as the (void *)[8] the library takes: eight arrays of n, or one of (8, n)"""
+        n = self._hgrid(who, grid)
+        if not isinstance(fields, (list, tuple)):
+            base, _ = _dev_array(fields, f"{who}: fields", 8 * n)
+            ptrs = [base + 8 * n * m for m in range(8)]
+        else:
+            if len(fields) != 8:
+                raise ValueError(f"{who}: {len(fields)} fields; a record is taux, tauy, swf, lwf, lhf, shf, rain, snow")
+            ptrs = [_dev_array(a, f"{who}: fields[{m}]", n)[0] for m, a in enumerate(fields)]
+        self._hold_dev(fields)
+        return (C.c_void_p * 8)(*ptrs)
+
+    def hgrid_fluxes_dev(self, grid, ntime, fields, l_rest=0, flsn=334000.0, el=2.5e6, stream=None, fence=True):
+        """fluxes_dev() with the eight fields on caller grid `grid` (n points each): every resident column's values are
+        the sums of its row of the grid's in table."""
+        ptrs, s = self._hgrid_fields("hgrid_fluxes_dev", grid, fields), _dev_stream(stream)
+        self._call("hgrid_fluxes_dev", int(grid), int(ntime), ptrs, int(l_rest), float(flsn), float(el), s)
+        if fence:
+            self._call("dev_fence", s)
+
+    def hgrid_flux_ring_put_dev(self, grid, rec, fields, stream=None, fence=False):
+        """flux_ring_put_dev() likewise; host puts, device puts and remapped puts may alternate within one ring."""
+        ptrs, s = self._hgrid_fields("hgrid_flux_ring_put_dev", grid, fields), _dev_stream(stream)
+        self._call("hgrid_flux_ring_put_dev", int(grid), int(rec), ptrs, s)
+        if fence:
+            self._call("dev_fence", s)
+
+    def hgrid_fetch_dev(self, planes, stream=None, norm="none", land_value=1e20, fill_land=True):
+        """fetch_dev onto caller grids: a plane is (field, grid, out) or (field, grid, out, lev0, nlev), out of nlev * n
+        elements - a tensor of shape (nlev, n) - of float64 or float32.  norm "none": a caller point's value is the
+        weighted sum over the resident points of its row of the grid's out table; "used": divided by the sum of those
+        weights.  A caller point with no resident point in its row gets land_value (fill_land), or keeps what out held."""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"hgrid_fetch_dev: {len(planes)} planes, at most 64 in one call")
+        nrm = _hgrid_norm("hgrid_fetch_dev", norm)
+        arr = (_HgridPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            who = f"hgrid_fetch_dev: planes[{k}]"
+            if len(p) not in (3, 5):
+                raise ValueError(f"{who} is (field, grid, out) or (field, grid, out, lev0, nlev)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            n, out = self._hgrid(who, p[1]), p[2]
+            axis = 1 if f in _OUT_2D else self._nzp1
+            if len(p) == 5:
+                lev0, nlev = int(p[3]), int(p[4])
+            else:
+                shape = getattr(out, "shape", ())
+                lev0, nlev = 0, (int(np.prod(shape, dtype=np.int64)) // n if n and len(shape) else 0)
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > axis:
+                raise ValueError(f"{who}: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, whose axis has {axis}")
+            ptr, typestr = _dev_array(out, f"{who} out", nlev * n, tuple(_DEV_TYPESTR))
+            arr[k] = _HgridPlaneC(f, lev0, nlev, _DEV_TYPESTR[typestr], int(p[1]), nrm, int(bool(fill_land)), float(land_value), ptr)
+            self._hold_dev(out)
+        self._call("hgrid_fetch_dev", len(planes), arr, _dev_stream(stream))
+
+
+class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays, _VerticalAxes,
+              _HorizontalGrids):
     """What one device context and several GPUs behind one handle have in common: everything but how they are made.
     Method `name` is the C function self._pre + name applied to the handle self._h."""
     _pre = "mckpp_hip_"

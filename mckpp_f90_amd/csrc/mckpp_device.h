@@ -335,6 +335,37 @@ hipError_t mckpp_launch_vaxis_fetch_planes(const mckpp_vaxis_fetch_plane *tab, i
 // SSref, X2 = S - Sref, Tref and Ssurf, a wave per column
 hipError_t mckpp_launch_vaxis_init_finish(double *T, double *S, int ld, int nzp1, int64_t ncol, double *cs,
                                           const unsigned *kelvin, double tk0, int l_ssref, hipStream_t stream);
+// The caller's horizontal grids (include/mckpp_hip_hgrid.h states the arithmetic and the layout).  A weight table on the
+// device, the sliced ELL mckpp_host_hgrid_slices builds: slice s - rows 64 s .. 64 s + 63, one wave's - has the width
+// (off[s + 1] - off[s]) / 64, entry k of row r is element off[r / 64] + 64 k + r % 64 of idx and w, and len[r] entries
+// of row r are loaded.
+struct mckpp_hgrid_ell {
+  const int64_t *off;
+  const int *len;
+  const int *idx;
+  const double *w;
+  int64_t nrows;
+};
+// k_fluxes_dev / k_flux_gather with each resident column's eight values summed from the caller grid's arrays `f`
+// through the in table `t`, whose rows are the resident columns in column order
+hipError_t mckpp_launch_hgrid_fluxes(const mckpp_kparams &p, int ntime, const mckpp_hgrid_ell &t, const mckpp_dev_fields &f,
+                                     int l_rest, double flsn, double el, hipStream_t stream);
+hipError_t mckpp_launch_hgrid_flux_gather(const mckpp_hgrid_ell &t, const mckpp_dev_fields &f, int64_t ncol, double *slot,
+                                          hipStream_t stream);
+// One plane of mckpp_hip_hgrid_fetch_dev's second stage (k_hgrid_out): level lev of out(t.nrows, nlev), doubles or (f32)
+// floats, is the row sum through the out table `t` of stage(npts, nlev)'s level lev; norm: MCKPP_HGRID_NORM_*; fill: a
+// caller point without a used entry gets land_value.
+struct mckpp_hgrid_plane {
+  const double *stage;
+  void *out;
+  double land_value;
+  mckpp_hgrid_ell t;
+  int64_t npts;
+  int nlev, f32, norm, fill;
+};
+#define MCKPP_HGRID_PLANES 64   // most planes of one call (the device table's size)
+// all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane, maxn: the most points of a grid
+hipError_t mckpp_launch_hgrid_out(const mckpp_hgrid_plane *tab, int nplanes, int maxlev, int64_t maxn, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

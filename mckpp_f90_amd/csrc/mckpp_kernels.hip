@@ -239,6 +239,107 @@ __global__ __launch_bounds__(256) void k_flux_gather(mckpp_dev_fields f, const i
 }
 
 // ---------------------------------------------------------------------------
+// The caller's horizontal grids (include/mckpp_hip_hgrid.h): forcing in and fields out by remap weights.  The header
+// states the arithmetic; hgrid_row_sums is that statement, once, for the three kernels below.  A thread takes row r of
+// a sliced ELL table and a wave the slice r / 64 (the launches use workgroups of 256 with r = blockIdx.x * 256 +
+// threadIdx.x, so a wave's rows are one slice's).  The trip count is the slice's width, the same for the whole wave;
+// per trip the lanes read consecutive elements of idx and of w (256 B + 512 B a wave) and that one index and weight
+// feed NF independent gathers, products and sums.  Padding is never loaded: a lane whose row has ended is predicated
+// off.  The first entry assigns - a = w * x, d = w -, every further one adds; -ffp-contract=off keeps the product and
+// the sum two rounded operations.  x(m, i): source value i of field m.  Returns the row's length (0 past the table).
+// ---------------------------------------------------------------------------
+template <int NF, bool DEN, class X>
+__device__ __forceinline__ int hgrid_row_sums(const mckpp_hgrid_ell &t, int64_t r, X x, double (&a)[NF], double &d)
+{
+  const int lane = threadIdx.x & 63;
+  const int64_t first = r - lane;             // the slice's first row
+  int64_t base = 0;
+  int width = 0;
+  if (first < t.nrows) {                      // (a wave past the table has no slice: off[] ends with the last one's end)
+    const int64_t s = first >> 6;
+    base = t.off[s];
+    width = (int)((t.off[s + 1] - base) >> 6);
+  }
+  width = __builtin_amdgcn_readfirstlane(width);
+  const int len = r < t.nrows ? t.len[r] : 0;
+#pragma unroll
+  for (int m = 0; m < NF; ++m) a[m] = 0.0;
+  d = 0.0;
+  for (int k = 0; k < width; ++k) {
+    if (k >= len) continue;
+    const int64_t e = base + (int64_t)k * 64 + lane;
+    const int i = t.idx[e];
+    const double w = t.w[e];
+    if (k == 0) {
+#pragma unroll
+      for (int m = 0; m < NF; ++m) a[m] = w * x(m, i);
+      if (DEN) d = w;
+    } else {
+#pragma unroll
+      for (int m = 0; m < NF; ++m) a[m] = a[m] + w * x(m, i);
+      if (DEN) d = d + w;
+    }
+  }
+  return len;
+}
+
+// mckpp_hip_hgrid_fluxes_dev: k_fluxes_dev with the column's eight values summed from the caller grid's arrays; the
+// table's rows are the resident columns in column order
+__global__ __launch_bounds__(256) void k_hgrid_fluxes(mckpp_kparams p, int ntime, mckpp_hgrid_ell t, mckpp_dev_fields f,
+                                                      int l_rest, double flsn, double el)
+{
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double a[8], d;
+  hgrid_row_sums<8, false>(t, c, [&](int m, int i) { return f.f[m][i]; }, a, d);
+  if (c >= p.ncol) return;
+  if (!p.ci[(size_t)c * MCKPP_CI + CI_LOCEAN]) return;          // fluxes_mod.F90:55, as k_fluxes_dev
+  fluxes_column(p, (int)c, ntime, a[0], a[1], a[2], a[3], a[4], a[5], a[6], a[7], l_rest, flsn, el);
+}
+
+// mckpp_hip_hgrid_flux_ring_put_dev: k_flux_gather likewise, into a slot [8][ncol] of the flux ring
+__global__ __launch_bounds__(256) void k_hgrid_flux_gather(mckpp_hgrid_ell t, mckpp_dev_fields f, int64_t ncol,
+                                                           double *__restrict__ slot)
+{
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  double a[8], d;
+  hgrid_row_sums<8, false>(t, c, [&](int m, int i) { return f.f[m][i]; }, a, d);
+  if (c >= ncol) return;
+#pragma unroll
+  for (int m = 0; m < 8; ++m) slot[(int64_t)m * ncol + c] = a[m];
+}
+
+// The second stage of mckpp_hip_hgrid_fetch_dev: a thread per caller point, the level on blockIdx.y, the plane on
+// blockIdx.z.  The source is the staging plane k_fetch_planes wrote, points fastest, so the spatially local stencils
+// of a remap gather within shared sectors.  The out table holds the entries of resident points only, so there is no
+// mask: a point without a used entry has a row of length 0.
+template <class T>
+__device__ __forceinline__ void hgrid_out_plane(const mckpp_hgrid_plane &e)
+{
+  const int lev = blockIdx.y;
+  if (lev >= e.nlev) return;   // (the grid's levels are those of the deepest plane)
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  const double *__restrict__ x = e.stage + (int64_t)lev * e.npts;
+  double a[1], d;
+  const int len = hgrid_row_sums<1, true>(e.t, j, [&](int, int i) { return x[i]; }, a, d);
+  if (j >= e.t.nrows) return;
+  T *dst = static_cast<T *>(e.out) + (int64_t)lev * e.t.nrows + j;
+  const bool used = e.norm == 1;   // MCKPP_HGRID_NORM_USED
+  if (len == 0 || (used && d == 0.0)) {
+    if (e.fill) *dst = (T)e.land_value;
+    return;
+  }
+  const double v = used ? a[0] / d : a[0];
+  *dst = (T)v;
+}
+
+__global__ __launch_bounds__(256) void k_hgrid_out(const mckpp_hgrid_plane *__restrict__ tab)
+{
+  const mckpp_hgrid_plane e = tab[blockIdx.z];
+  if (e.f32) hgrid_out_plane<float>(e);
+  else hgrid_out_plane<double>(e);
+}
+
+// ---------------------------------------------------------------------------
 // mckpp_physics_overrides_bottomtemp, src/mckpp_physics_overrides.F90:12-24:
 // prescribed temperature of the bottom grid point; one thread per column.
 // ---------------------------------------------------------------------------
@@ -843,6 +944,31 @@ hipError_t mckpp_launch_flux_gather(const mckpp_dev_fields &f, const int *ipt, i
 {
   if (ncol <= 0) return hipSuccess;
   hipLaunchKernelGGL(k_flux_gather, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, stream, f, ipt, ncol, slot);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_hgrid_fluxes(const mckpp_kparams &p, int ntime, const mckpp_hgrid_ell &t, const mckpp_dev_fields &f,
+                                     int l_rest, double flsn, double el, hipStream_t stream)
+{
+  if (p.ncol <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_hgrid_fluxes, dim3((unsigned)((p.ncol + 255) / 256)), dim3(256), 0, stream, p, ntime, t, f, l_rest,
+                     flsn, el);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_hgrid_flux_gather(const mckpp_hgrid_ell &t, const mckpp_dev_fields &f, int64_t ncol, double *slot,
+                                          hipStream_t stream)
+{
+  if (ncol <= 0) return hipSuccess;
+  hipLaunchKernelGGL(k_hgrid_flux_gather, dim3((unsigned)((ncol + 255) / 256)), dim3(256), 0, stream, t, f, ncol, slot);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_hgrid_out(const mckpp_hgrid_plane *tab, int nplanes, int maxlev, int64_t maxn, hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0 || maxn <= 0) return hipSuccess;
+  dim3 grid((unsigned)((maxn + 255) / 256), (unsigned)maxlev, (unsigned)nplanes);
+  hipLaunchKernelGGL(k_hgrid_out, grid, dim3(256), 0, stream, tab);
   return hipGetLastError();
 }
 

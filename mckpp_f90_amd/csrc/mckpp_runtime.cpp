@@ -1,5 +1,6 @@
 // mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companions mckpp_hip_device.h,
-// mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h and mckpp_hip_vaxis.h.
+// mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h and
+// mckpp_hip_hgrid.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
@@ -19,6 +20,7 @@
 #include "../../include/mckpp_hip_put.h"
 #include "../../include/mckpp_hip_reduce.h"
 #include "../../include/mckpp_hip_vaxis.h"
+#include "../../include/mckpp_hip_hgrid.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -186,6 +188,22 @@ struct mckpp_ctx_resident {
   int64_t nland = 0;
   int land_kind = 0;
   dev_buf<double> d_stage;    // grow-only (ensure_stage)
+  // The device tables of the caller's horizontal grids (include/mckpp_hip_hgrid.h), per grid and direction the sliced
+  // ELL of mckpp_host_hgrid_slices.  They depend on the column map - `in` has the resident columns' rows in column
+  // order, `out` every caller point's row without the entries of non-resident points - so they are built on first use
+  // and go with the resident state, like d_land (a new column map marks them not built).  kind 0: not built; 1: for
+  // this context's column map; 2 (out, shard 0 of a multi handle): for the union of the shards' columns.  empty_point:
+  // the first resident column's point whose in row is empty (-1: none).  d_hstage: the staging plane(s) of
+  // mckpp_hip_hgrid_fetch_dev, (npts, nlev) doubles per plane, grow-only (hgrid_stage).
+  struct hgrid_dev {
+    dev_buf<int64_t> off;
+    dev_buf<int> len, idx;
+    dev_buf<double> w;
+    int64_t nrows = 0, padded = 0, empty_point = -1;
+    int kind = 0;
+  };
+  struct { hgrid_dev in, out; } hgd[MCKPP_HGRIDS];
+  dev_buf<double> d_hstage;
   dev_buf<char> d_put_stage;  // the planes of mckpp_hip_put_host, grow-only: the call ends with a wait, so nothing reads it between calls
   dev_buf<double> d_xfer[2];  // the staging buffers of the row transfers, grow-only (ensure_xfer)
   // pinned host images of the column records and of the forcing staging (grow-only: ensure_host_f)
@@ -283,6 +301,21 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   plane_table<mckpp_vaxis_put_plane, MCKPP_VAXIS_PLANES> vput_tab;
   plane_table<mckpp_vaxis_fetch_plane, MCKPP_VAXIS_PLANES> vfetch_tab;
   dev_buf<unsigned> d_kelvin;
+  // The caller's horizontal grids (include/mckpp_hip_hgrid.h).  A grid is the context's, like the axes above: n points
+  // (0: not defined), the npts it was defined for and the copies of its two CSR tables on the host (ptr empty: that
+  // direction is missing).  The device tables are the resident state's (mckpp_ctx_resident::hgd).  The plane table of
+  // the second stage of mckpp_hip_hgrid_fetch_dev.
+  struct hgrid_csr {
+    std::vector<int64_t> ptr;
+    std::vector<int32_t> idx;
+    std::vector<double> w;
+    mckpp_hgrid_table_c view() const { return mckpp_hgrid_table_c{ptr.data(), idx.data(), w.data()}; }
+  };
+  struct hgrid {
+    int64_t n = 0, npts = 0;
+    hgrid_csr in, out;
+  } hg[MCKPP_HGRIDS];
+  plane_table<mckpp_hgrid_plane, MCKPP_HGRID_PLANES> hgrid_tab;
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -732,6 +765,7 @@ static int new_state(mckpp_hip_ctx *h, int64_t npts, const std::vector<int> &ipt
       h->series_nrec = 0;
     }
     h->land_kind = 0;   // the list of non-resident points was of the previous column map
+    for (auto &g : h->hgd) g.in.kind = g.out.kind = 0;   // ... and so were the device tables of the caller's grids (hgrid_build waits, then rebuilds)
     if (from_restart) h->ext_inputs_resident = false;
     h->ipt = ipt;
   }
@@ -2511,8 +2545,9 @@ int caller_event(hip_event &ev, int device, void *stream)
   return 0;
 }
 
+// t (null: none): the fields live on a caller's grid and reach the columns through its in table (mckpp_hip_hgrid.h)
 int fluxes_dev_queue(mckpp_hip_ctx *h, int ntime, const double *const fields[8], int l_rest, double flsn, double el,
-                     hipEvent_t produced)
+                     hipEvent_t produced, const mckpp_hgrid_ell *t = nullptr)
 {
   if (h->ncol == 0) return 0;
   HIPCHK(hipSetDevice(h->device));
@@ -2521,12 +2556,14 @@ int fluxes_dev_queue(mckpp_hip_ctx *h, int ntime, const double *const fields[8],
   fill_params(h, p, ntime, MCKPP_MODE_STEP);
   mckpp_dev_fields f;
   for (int m = 0; m < 8; ++m) f.f[m] = fields[m];
-  HIPCHK(mckpp_launch_fluxes_dev(p, ntime, f, h->d_ipt, l_rest, flsn, el, h->stream));
+  if (t) HIPCHK(mckpp_launch_hgrid_fluxes(p, ntime, *t, f, l_rest, flsn, el, h->stream));
+  else HIPCHK(mckpp_launch_fluxes_dev(p, ntime, f, h->d_ipt, l_rest, flsn, el, h->stream));
   HIPCHK(h->ev_read.record(h->stream));
   return 0;
 }
 
-int ring_put_dev_queue(mckpp_hip_ctx *h, int rec, const double *const fields[8], hipEvent_t produced)
+int ring_put_dev_queue(mckpp_hip_ctx *h, int rec, const double *const fields[8], hipEvent_t produced,
+                       const mckpp_hgrid_ell *t = nullptr)
 {
   auto &g = h->ring;
   if (h->ncol > 0) {
@@ -2537,7 +2574,8 @@ int ring_put_dev_queue(mckpp_hip_ctx *h, int rec, const double *const fields[8],
     HIPCHK(hipStreamWaitEvent(h->flux_stream, produced, 0));
     // behind the launches of the last call that needed the record the slot held - on the device, never on the host
     HIPCHK(hipStreamWaitEvent(h->flux_stream, g.last_read[slot], 0));
-    HIPCHK(mckpp_launch_flux_gather(f, h->d_ipt, h->ncol, g.slots + slot * 8 * (size_t)h->ncol, h->flux_stream));
+    if (t) HIPCHK(mckpp_launch_hgrid_flux_gather(*t, f, h->ncol, g.slots + slot * 8 * (size_t)h->ncol, h->flux_stream));
+    else HIPCHK(mckpp_launch_flux_gather(f, h->d_ipt, h->ncol, g.slots + slot * 8 * (size_t)h->ncol, h->flux_stream));
     HIPCHK(hipEventRecord(g.arrived[slot], h->flux_stream));
     HIPCHK(h->ev_read_flux.record(h->flux_stream));
   }
@@ -3172,6 +3210,324 @@ int mckpp_hip_vaxis_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_v
   if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complement again)
   if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
   return vaxis_fetch_queue(h, tab, maxlev, any_fill, h->ev_caller, consumer_stream);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// The caller's horizontal grids (include/mckpp_hip_hgrid.h): grids and their weight tables per context, forcing in
+// through the in table (k_hgrid_fluxes, k_hgrid_flux_gather - queued by fluxes_dev_queue and ring_put_dev_queue, so
+// streams, events and ring bookkeeping are those calls'), fields out through the out table (k_fetch_planes into the
+// staging plane, then k_hgrid_out).  Checks queue nothing.  The device tables are built from the host's on first use
+// (mckpp_host_hgrid_slices) and belong to the resident state.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+using hgrid_dev = mckpp_ctx_resident::hgrid_dev;
+
+int hgrid_copy(const char *who, const char *name, int64_t nrows, int64_t nsrc, const mckpp_hgrid_table_c *t,
+               mckpp_hip_ctx::hgrid_csr &c)
+{
+  if (!t) return 0;
+  char msg[256];
+  if (mckpp_host_hgrid_check(name, nrows, nsrc, t, msg, (int64_t)sizeof msg)) return fail("%s: %s", who, msg);
+  const int64_t nnz = t->ptr[nrows];
+  c.ptr.assign(t->ptr, t->ptr + nrows + 1);
+  if (nnz > 0) {
+    c.idx.assign(t->idx, t->idx + nnz);
+    c.w.assign(t->w, t->w + nnz);
+  }
+  return 0;
+}
+
+int hgrid_define(mckpp_hip_ctx *h, const char *who, int grid, int64_t n, const mckpp_hgrid_table_c *in, const mckpp_hgrid_table_c *out)
+{
+  if (grid < 0 || grid >= MCKPP_HGRIDS) return fail("%s: grid %d (0..%d)", who, grid, MCKPP_HGRIDS - 1);
+  if (n < 0 || n > INT32_MAX) return fail("%s: grid %d: n=%lld points (0 drops the grid)", who, grid, (long long)n);
+  mckpp_hip_ctx::hgrid next;
+  if (n > 0) {
+    if (h->npts <= 0) return fail("%s: upload the state first: the tables are checked against the grid's size", who);
+    next.n = n;
+    next.npts = h->npts;
+    if (hgrid_copy(who, "in", h->npts, n, in, next.in)) return -1;
+    if (hgrid_copy(who, "out", n, h->npts, out, next.out)) return -1;
+  }
+  HIPCHK(hipSetDevice(h->device));
+  // a launch in flight on the context's stream or on the flux stream may read the device tables of the grid this replaces
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(hipStreamSynchronize(h->flux_stream));
+  h->hg[grid] = std::move(next);
+  h->hgd[grid].in = hgrid_dev{};
+  h->hgd[grid].out = hgrid_dev{};
+  return 0;
+}
+
+// grid `grid`, defined for the present npts; null, and the refusal naming `what`, otherwise
+const mckpp_hip_ctx::hgrid *hgrid_of(mckpp_hip_ctx *h, const char *who, const char *what, int grid)
+{
+  if (grid < 0 || grid >= MCKPP_HGRIDS || h->hg[grid].n == 0) {
+    fail("%s: %s: grid %d is not defined (mckpp_hip_hgrid_define; grids are 0..%d)", who, what, grid, MCKPP_HGRIDS - 1);
+    return nullptr;
+  }
+  if (h->hg[grid].npts != h->npts) {
+    fail("%s: %s: grid %d was defined for npts=%lld, the state has %lld: define it again", who, what, grid,
+         (long long)h->hg[grid].npts, (long long)h->npts);
+    return nullptr;
+  }
+  return &h->hg[grid];
+}
+
+mckpp_hgrid_ell hgrid_ell(const hgrid_dev &d) { return mckpp_hgrid_ell{d.off, d.len, d.idx, d.w, d.nrows}; }
+
+// a device table: list rows rows[0..nlist-1] (null: all) of t, without the entries keep (null: none) does not mark
+int hgrid_build(mckpp_hip_ctx *h, hgrid_dev &d, int64_t nlist, const int64_t *rows, const mckpp_hgrid_table_c &t,
+                const unsigned char *keep, int kind)
+{
+  const int64_t nslices = (nlist + 63) / 64;
+  std::vector<int64_t> off((size_t)nslices + 1);
+  std::vector<int32_t> len((size_t)std::max<int64_t>(nlist, 1));
+  const int64_t padded = mckpp_host_hgrid_slices(nlist, rows, &t, keep, off.data(), len.data(), nullptr, nullptr);
+  if (padded < 0) return fail("mckpp_host_hgrid_slices: a null argument");
+  std::vector<int32_t> idx((size_t)std::max<int64_t>(padded, 1));
+  std::vector<double> w((size_t)std::max<int64_t>(padded, 1));
+  (void)mckpp_host_hgrid_slices(nlist, rows, &t, keep, off.data(), len.data(), idx.data(), w.data());
+  HIPCHK(hipSetDevice(h->device));
+  hgrid_dev next;
+  HIPCHK(next.off.alloc(off.size()));
+  HIPCHK(next.len.alloc(len.size()));
+  HIPCHK(next.idx.alloc(idx.size()));
+  HIPCHK(next.w.alloc(w.size()));
+  HIPCHK(hipMemcpy(next.off, off.data(), off.size() * sizeof(int64_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(next.len, len.data(), len.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(next.idx, idx.data(), idx.size() * sizeof(int32_t), hipMemcpyHostToDevice));
+  HIPCHK(hipMemcpy(next.w, w.data(), w.size() * sizeof(double), hipMemcpyHostToDevice));
+  next.nrows = nlist;
+  next.padded = padded;
+  next.kind = kind;
+  for (int64_t j = 0; j < nlist && next.empty_point < 0; ++j)
+    if (len[(size_t)j] == 0) next.empty_point = rows ? rows[j] : j;
+  if (d.off) {   // a launch in flight on the context's stream or on the flux stream may read the table this replaces
+    HIPCHK(hipStreamSynchronize(h->stream));
+    HIPCHK(hipStreamSynchronize(h->flux_stream));
+  }
+  d = std::move(next);
+  return 0;
+}
+
+// the in table of the resident columns, built where it is not
+int hgrid_in_build(mckpp_hip_ctx *h, int grid)
+{
+  hgrid_dev &d = h->hgd[grid].in;
+  if (d.kind != 0) return 0;
+  std::vector<int64_t> rows(h->ipt.begin(), h->ipt.end());
+  return hgrid_build(h, d, (int64_t)rows.size(), rows.data(), h->hg[grid].in.view(), nullptr, 1);
+}
+
+// the out table for `covered` (null: this context's own columns; kind 1 / 2 as d_land's), built where it is not that
+int hgrid_out_build(mckpp_hip_ctx *h, int grid, const std::vector<unsigned char> *covered)
+{
+  hgrid_dev &d = h->hgd[grid].out;
+  const int kind = covered ? 2 : 1;
+  if (d.kind == kind) return 0;
+  std::vector<unsigned char> own;
+  if (!covered) {
+    own.assign((size_t)h->npts, 0);
+    for (int i : h->ipt) own[(size_t)i] = 1;
+    covered = &own;
+  }
+  return hgrid_build(h, d, h->hg[grid].n, nullptr, h->hg[grid].out.view(), covered->data(), kind);
+}
+
+// What a call of the in direction needs before it queues: the grid, its in table, the eight arrays of n doubles, and
+// no resident column with an empty row.  *t: the device table; *dev (where asked for): the device of the arrays.
+int hgrid_in_check(mckpp_hip_ctx *h, const char *who, int grid, const double *const fields[8], mckpp_hgrid_ell *t, int *dev)
+{
+  if (!fields) return fail("%s: null argument", who);
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, "grid", grid);
+  if (!g) return -1;
+  if (g->in.ptr.empty())
+    return fail("%s: grid %d has no in table (caller -> model): mckpp_hip_hgrid_define was given none", who, grid);
+  HIPCHK(hipSetDevice(h->device));
+  for (int m = 0; m < 8; ++m) {
+    char arg[48];
+    snprintf(arg, sizeof arg, "fields[%d] (%s)", m, flux_field_names[m]);
+    if (dev_ptr_check(h, who, arg, fields[m], (size_t)g->n * sizeof(double), m == 0 ? dev : nullptr)) return -1;
+  }
+  if (hgrid_in_build(h, grid)) return -1;
+  const hgrid_dev &d = h->hgd[grid].in;
+  if (d.empty_point >= 0)
+    return fail("%s: grid %d: the in row of point %lld, a resident column, is empty: nothing to form its forcing from", who,
+                grid, (long long)d.empty_point);
+  *t = hgrid_ell(d);
+  return 0;
+}
+
+// The planes of a delivery on caller grids: stage 1 as planes of k_fetch_planes into the staging (`out` set when it is
+// queued: at[k] doubles into the block), stage 2 as planes of k_hgrid_out (stage and table likewise).
+struct hgrid_fetch {
+  std::vector<mckpp_fetch_plane> first;
+  std::vector<mckpp_hgrid_plane> second;
+  std::vector<int> grid;
+  std::vector<size_t> at;
+  size_t elems = 0;
+  int maxlev = 0;
+  int64_t maxn = 0;
+};
+
+int hgrid_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_hgrid_plane_c *planes, hgrid_fetch &r, int *dev)
+{
+  if (nplanes < 0 || nplanes > MCKPP_HGRID_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_HGRID_PLANES_MAX);
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  HIPCHK(hipSetDevice(h->device));
+  r = hgrid_fetch{};
+  std::vector<std::pair<const char *, const char *>> span;
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_hgrid_plane_c &q = planes[k];
+    out_desc d;
+    if (out_field(h, q.field, d)) return -1;
+    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, d.nlev)) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem) return -1;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d]", k);
+    const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
+    if (!g) return -1;
+    if (g->out.ptr.empty())
+      return fail("%s: planes[%d]: grid %d has no out table (model -> caller): mckpp_hip_hgrid_define was given none", who, k,
+                  q.grid);
+    if (q.norm != MCKPP_HGRID_NORM_NONE && q.norm != MCKPP_HGRID_NORM_USED)
+      return fail("%s: planes[%d]: norm %d (MCKPP_HGRID_NORM_NONE 0, MCKPP_HGRID_NORM_USED 1)", who, k, q.norm);
+    const size_t bytes = (size_t)g->n * (size_t)q.nlev * elem;
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    if (dev_ptr_check(h, who, arg, q.out, bytes, k == 0 ? dev : nullptr)) return -1;
+    const char *b = static_cast<const char *>(q.out);
+    for (int j = 0; j < k; ++j)
+      if (b < span[(size_t)j].second && span[(size_t)j].first < b + bytes)
+        return fail("%s: planes[%d].out and planes[%d].out overlap: the planes of a call have no order", who, k, j);
+    span.emplace_back(b, b + bytes);
+    r.first.push_back(mckpp_fetch_plane{d.src, nullptr, 0.0, d.ld, d.off + q.lev0, q.nlev, d.add_sref, 0, 0});
+    r.second.push_back(mckpp_hgrid_plane{nullptr, q.out, q.land_value, mckpp_hgrid_ell{}, h->npts, q.nlev,
+                                         q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.norm, q.fill_land ? 1 : 0});
+    r.grid.push_back(q.grid);
+    r.at.push_back(r.elems);
+    r.elems += (size_t)h->npts * (size_t)q.nlev;
+    r.maxlev = std::max(r.maxlev, (int)q.nlev);
+    r.maxn = std::max(r.maxn, g->n);
+  }
+  return 0;
+}
+
+// the staging block with room for `elems` doubles; whoever regrows it waits first, as ensure_stage does
+int hgrid_stage(mckpp_hip_ctx *h, size_t elems)
+{
+  if (elems <= h->d_hstage.size()) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  // (both stages of an earlier call, which read and write the block, are on this context's stream)
+  if (h->d_hstage) HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(h->d_hstage.reserve(elems));
+  return 0;
+}
+
+// stage 1 on this context's stream, behind `before`: its columns' values into `stage`
+int hgrid_fetch_first(mckpp_hip_ctx *h, hgrid_fetch &r, double *stage, hipEvent_t before)
+{
+  HIPCHK(hipSetDevice(h->device));
+  for (size_t k = 0; k < r.first.size(); ++k) r.first[k].out = stage + r.at[k];
+  HIPCHK(h->fetch_tab.put(r.first, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
+  HIPCHK(mckpp_launch_fetch_planes(h->fetch_tab, (int)r.first.size(), r.maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs, nullptr, 0,
+                                   h->stream));
+  return 0;
+}
+
+// stage 2 on this context's stream, from `stage` through the out tables as they are built; the consumer waits for it
+int hgrid_fetch_second(mckpp_hip_ctx *h, hgrid_fetch &r, const double *stage, void *consumer_stream)
+{
+  HIPCHK(hipSetDevice(h->device));
+  for (size_t k = 0; k < r.second.size(); ++k) {
+    r.second[k].stage = stage + r.at[k];
+    r.second[k].t = hgrid_ell(h->hgd[r.grid[k]].out);
+  }
+  HIPCHK(h->hgrid_tab.put(r.second, h->stream));
+  HIPCHK(mckpp_launch_hgrid_out(h->hgrid_tab, (int)r.second.size(), r.maxlev, r.maxn, h->stream));
+  HIPCHK(h->ev_delivered.record(h->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+
+int hgrid_info(mckpp_hip_ctx *h, const char *who, int grid, int64_t info[6], bool keep_out_kind)
+{
+  if (!info) return fail("%s: null argument", who);
+  const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, "grid", grid);
+  if (!g) return -1;
+  info[0] = g->n;
+  info[5] = 0;
+  for (int dir = 0; dir < 2; ++dir) {
+    const mckpp_hip_ctx::hgrid_csr &c = dir ? g->out : g->in;
+    info[1 + dir] = c.ptr.empty() ? -1 : c.ptr.back();
+    info[3 + dir] = 0;
+    for (size_t r = 0; r + 1 < c.ptr.size(); ++r) info[5] = std::max(info[5], c.ptr[r + 1] - c.ptr[r]);
+  }
+  if (!g->in.ptr.empty()) {
+    if (hgrid_in_build(h, grid)) return -1;
+    info[3] = h->hgd[grid].in.padded;
+  }
+  if (!g->out.ptr.empty()) {
+    if (!(keep_out_kind && h->hgd[grid].out.kind == 2) && hgrid_out_build(h, grid, nullptr)) return -1;
+    info[4] = h->hgd[grid].out.padded;
+  }
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_hgrid_define(mckpp_hip_handle h, int grid, int64_t n, const mckpp_hgrid_table_c *in, const mckpp_hgrid_table_c *out)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return hgrid_define(h, who, grid, n, in, out); });
+}
+
+int mckpp_hip_hgrid_info(mckpp_hip_handle h, int grid, int64_t info[6])
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return hgrid_info(h, who, grid, info, false); });
+}
+
+int mckpp_hip_hgrid_fluxes_dev(mckpp_hip_handle h, int grid, int ntime, const double *const fields[8], int l_rest, double flsn,
+                               double el, void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  mckpp_hgrid_ell t;
+  if (hgrid_in_check(h, who, grid, fields, &t, nullptr)) return -1;
+  if (h->ncol == 0) return 0;
+  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return fluxes_dev_queue(h, ntime, fields, l_rest, flsn, el, h->ev_caller, &t);
+  });
+}
+
+int mckpp_hip_hgrid_flux_ring_put_dev(mckpp_hip_handle h, int grid, int rec, const double *const fields[8], void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  if (!fields) return fail("%s: null argument", who);
+  if (ring_put_check(h, who, rec)) return -1;
+  mckpp_hgrid_ell t;
+  if (hgrid_in_check(h, who, grid, fields, &t, nullptr)) return -1;
+  if (h->ncol > 0 && caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return ring_put_dev_queue(h, rec, fields, h->ev_caller, &t);
+  });
+}
+
+int mckpp_hip_hgrid_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hgrid_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  hgrid_fetch r;
+  if (hgrid_fetch_check(h, who, nplanes, planes, r, nullptr)) return -1;
+  if (r.first.empty()) return 0;
+  for (int g : r.grid)
+    if (hgrid_out_build(h, g, nullptr)) return -1;   // (a shard addressed on its own: its own columns again)
+  if (hgrid_stage(h, r.elems)) return -1;
+  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
+  if (hgrid_fetch_first(h, r, h->d_hstage, h->ev_caller)) return -1;
+  return hgrid_fetch_second(h, r, h->d_hstage, consumer_stream);
   });
 }
 
@@ -4345,6 +4701,8 @@ int mckpp_hip_multi_upload(mckpp_hip_multi_handle m, const mckpp_state_ptrs_c *s
   }
   m->gipt_valid = false;   // the root's copy of the column maps is of the previous upload
   for (auto *x : m->ctx) x->land_kind = 0;   // ... and so is shard 0's list of the points that no shard holds
+  for (auto *x : m->ctx)
+    for (auto &g : x->hgd) g.out.kind = 0;   // ... and the out tables of the caller's grids, built for the union of the shards' columns
   return 0;
   });
 }
@@ -5286,6 +5644,115 @@ int mckpp_hip_multi_vaxis_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, c
   for (int d = 0; d < ndev; ++d)
     if (vaxis_fetch_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
   return 0;
+  });
+}
+
+// include/mckpp_hip_hgrid.h over all shards: a grid on every shard; forcing in, every shard summing for its own columns
+// from the same caller arrays; fields out with every shard's first stage into shard 0's staging and shard 0's second
+// stage over the union of the shards' columns, so the sums are those of one context, entry for entry
+int mckpp_hip_multi_hgrid_define(mckpp_hip_multi_handle m, int grid, int64_t n, const mckpp_hgrid_table_c *in, const mckpp_hgrid_table_c *out)
+{
+  return multi_each(__func__, m, [&, who = __func__](auto *x) { return hgrid_define(x, who, grid, n, in, out); });
+}
+
+// shard 0's out table of `grid` for the points some shard holds, where it is not that already
+static int multi_hgrid_out(mckpp_hip_multi *m, const char *who, int grid)
+{
+  if (m->ctx[0]->hgd[grid].out.kind == 2) return 0;
+  std::vector<int64_t> ncol;
+  std::vector<const int32_t *> points;
+  for (auto *x : m->ctx) { ncol.push_back(x->ncol); points.push_back(x->ipt.data()); }
+  std::vector<unsigned char> covered;
+  if (export_covered(m->npts, (int)m->ctx.size(), ncol.data(), points.data(), covered))
+    return fail("%s: a column map names a point outside the grid", who);
+  return hgrid_out_build(m->ctx[0], grid, &covered);
+}
+
+int mckpp_hip_multi_hgrid_info(mckpp_hip_multi_handle m, int grid, int64_t info[6])
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  if (!info) return fail("%s: null argument", who);
+  int64_t padded_in = 0;
+  for (auto *x : m->ctx) {
+    if (!hgrid_of(x, who, "grid", grid)) return -1;
+    if (x == m->ctx[0] && !x->hg[grid].out.ptr.empty() && multi_hgrid_out(m, who, grid)) return -1;
+    if (hgrid_info(x, who, grid, info, true)) return -1;
+    padded_in += info[3];
+  }
+  if (hgrid_info(m->ctx[0], who, grid, info, true)) return -1;
+  info[3] = padded_in;
+  return 0;
+  });
+}
+
+int mckpp_hip_multi_hgrid_fluxes_dev(mckpp_hip_multi_handle m, int grid, int ntime, const double *const fields[8], int l_rest,
+                                     double flsn, double el, void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<mckpp_hgrid_ell> t((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (hgrid_in_check(m->ctx[d], who, grid, fields, &t[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (fluxes_dev_queue(m->ctx[d], ntime, fields, l_rest, flsn, el, m->ev_caller, &t[(size_t)d])) return -1;
+  return 0;
+  });
+}
+
+int mckpp_hip_multi_hgrid_flux_ring_put_dev(mckpp_hip_multi_handle m, int grid, int rec, const double *const fields[8], void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  if (!fields) return fail("%s: null argument", who);
+  const int ndev = (int)m->ctx.size();
+  std::vector<mckpp_hgrid_ell> t((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (ring_put_check(m->ctx[d], who, rec) || hgrid_in_check(m->ctx[d], who, grid, fields, &t[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (ring_put_dev_queue(m->ctx[d], rec, fields, m->ev_caller, &t[(size_t)d])) return -1;
+  return 0;
+  });
+}
+
+int mckpp_hip_multi_hgrid_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_hgrid_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<hgrid_fetch> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (hgrid_fetch_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  mckpp_hip_ctx *root = m->ctx[0];
+  for (int g : rs[0].grid)
+    if (multi_hgrid_out(m, who, g)) return -1;
+  if (hgrid_stage(root, rs[0].elems)) return -1;
+  double *stage = root->d_hstage;
+  for (int d = 1; d < ndev; ++d) {   // every shard's device reaches shard 0's staging (peer access, once per pair)
+    HIPCHK(hipSetDevice(m->ctx[d]->device));
+    if (dev_ptr_check(m->ctx[d], who, "the staging plane of shard 0", stage, rs[0].elems * sizeof(double))) return -1;
+  }
+  if (multi_caller_event(m, dev, consumer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d) {
+    mckpp_hip_ctx *x = m->ctx[d];
+    if (d > 0) {
+      HIPCHK(hipSetDevice(x->device));
+      // the staging is shard 0's: behind the second stage of the call before, which read it on shard 0's stream
+      if (root->ev_delivered) HIPCHK(hipStreamWaitEvent(x->stream, root->ev_delivered, 0));
+    }
+    if (hgrid_fetch_first(x, rs[(size_t)d], stage, m->ev_caller)) return -1;
+    if (d > 0) {   // ... and shard 0's second stage behind this shard's first
+      HIPCHK(x->ev_delivered.record(x->stream));
+      HIPCHK(hipSetDevice(root->device));
+      HIPCHK(hipStreamWaitEvent(root->stream, x->ev_delivered, 0));
+    }
+  }
+  return hgrid_fetch_second(root, rs[0], stage, consumer_stream);
   });
 }
 

@@ -1,5 +1,5 @@
 !> iso_c_binding view of include/mckpp_hip.h and of its companions
-!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h and mckpp_hip_vaxis.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h and mckpp_hip_hgrid.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -105,6 +105,21 @@ module mckpp_hip_binding
     real(c_double) :: land_value
     type(c_ptr) :: out
   end type mckpp_vaxis_dev_plane_c
+  !> the caller's horizontal grids (include/mckpp_hip_hgrid.h): MCKPP_HGRIDS grids per context; the normalisation of a
+  !! plane of mckpp_hip_hgrid_fetch_dev
+  integer(c_int32_t), parameter :: MCKPP_HGRIDS = 4, MCKPP_HGRID_PLANES_MAX = 64
+  integer(c_int32_t), parameter :: MCKPP_HGRID_NORM_NONE = 0, MCKPP_HGRID_NORM_USED = 1
+  !> a weight table in CSR form, host memory: ptr (nrows + 1 of c_int64_t), idx (c_int32_t, 0-based), w (c_double)
+  type, bind(C) :: mckpp_hgrid_table_c
+    type(c_ptr) :: ptr, idx, w
+  end type mckpp_hgrid_table_c
+  !> one plane of mckpp_hip_hgrid_fetch_dev: levels lev0 .. lev0 + nlev - 1 of `field` as they stand, remapped onto
+  !! caller grid `grid`, into out (n, nlev)
+  type, bind(C) :: mckpp_hgrid_plane_c
+    integer(c_int32_t) :: field, lev0, nlev, dtype, grid, norm, fill_land
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_hgrid_plane_c
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -1011,6 +1026,115 @@ module mckpp_hip_binding
       type(c_ptr), value :: m, consumer_stream
       integer(c_int32_t), value :: nplanes
       type(mckpp_vaxis_dev_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! the caller's horizontal grids (include/mckpp_hip_hgrid.h): grids and their weight tables per context, forcing in
+    ! and fields out on a caller's grid; the three host functions need no GPU
+    function mckpp_host_hgrid_check(name, nrows, nsrc, t, msg, msglen) bind(C, name="mckpp_host_hgrid_check") result(rc)
+      import :: c_int, c_int64_t, c_char, mckpp_hgrid_table_c
+      character(kind=c_char), intent(in) :: name(*)
+      integer(c_int64_t), value :: nrows, nsrc, msglen
+      type(mckpp_hgrid_table_c), intent(in) :: t
+      character(kind=c_char), intent(out) :: msg(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_host_hgrid_apply(nrows, t, x, used, norm, fill, land_value, out) bind(C, name="mckpp_host_hgrid_apply") result(rc)
+      import :: c_int, c_int64_t, c_double, c_ptr, mckpp_hgrid_table_c
+      integer(c_int64_t), value :: nrows
+      type(mckpp_hgrid_table_c), intent(in) :: t
+      real(c_double), intent(in) :: x(*)
+      type(c_ptr), value :: used   ! unsigned char per source index, or c_null_ptr: every entry is used
+      integer(c_int), value :: norm, fill
+      real(c_double), value :: land_value
+      real(c_double), intent(inout) :: out(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_host_hgrid_slices(nlist, rows, t, keep, slice_off, len, idx_out, w_out) &
+        bind(C, name="mckpp_host_hgrid_slices") result(padded)
+      import :: c_int32_t, c_int64_t, c_ptr, mckpp_hgrid_table_c
+      integer(c_int64_t), value :: nlist
+      type(c_ptr), value :: rows, keep, idx_out, w_out   ! c_null_ptr: all rows / nothing dropped / the sizing pass
+      type(mckpp_hgrid_table_c), intent(in) :: t
+      integer(c_int64_t), intent(out) :: slice_off(*)
+      integer(c_int32_t), intent(out) :: len(*)
+      integer(c_int64_t) :: padded
+    end function
+    function mckpp_hip_hgrid_define(handle, grid, n, tin, tout) bind(C, name="mckpp_hip_hgrid_define") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: grid
+      integer(c_int64_t), value :: n
+      type(c_ptr), value :: tin, tout   ! c_loc of a mckpp_hgrid_table_c, or c_null_ptr: that direction is missing
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_hgrid_info(handle, grid, info) bind(C, name="mckpp_hip_hgrid_info") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: handle
+      integer(c_int), value :: grid
+      integer(c_int64_t), intent(out) :: info(6)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_hgrid_fluxes_dev(handle, grid, ntime, fields, l_rest, flsn, el, producer_stream) &
+        bind(C, name="mckpp_hip_hgrid_fluxes_dev") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int), value :: grid, ntime, l_rest
+      type(c_ptr), intent(in) :: fields(8)
+      real(c_double), value :: flsn, el
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_hgrid_flux_ring_put_dev(handle, grid, rec, fields, producer_stream) &
+        bind(C, name="mckpp_hip_hgrid_flux_ring_put_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int), value :: grid, rec
+      type(c_ptr), intent(in) :: fields(8)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_hgrid_fetch_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_hgrid_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hgrid_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hgrid_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hgrid_define(m, grid, n, tin, tout) bind(C, name="mckpp_hip_multi_hgrid_define") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: m
+      integer(c_int), value :: grid
+      integer(c_int64_t), value :: n
+      type(c_ptr), value :: tin, tout   ! c_loc of a mckpp_hgrid_table_c, or c_null_ptr: that direction is missing
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hgrid_info(m, grid, info) bind(C, name="mckpp_hip_multi_hgrid_info") result(rc)
+      import :: c_int, c_int64_t, c_ptr
+      type(c_ptr), value :: m
+      integer(c_int), value :: grid
+      integer(c_int64_t), intent(out) :: info(6)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hgrid_fluxes_dev(m, grid, ntime, fields, l_rest, flsn, el, producer_stream) &
+        bind(C, name="mckpp_hip_multi_hgrid_fluxes_dev") result(rc)
+      import :: c_int, c_ptr, c_double
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int), value :: grid, ntime, l_rest
+      type(c_ptr), intent(in) :: fields(8)
+      real(c_double), value :: flsn, el
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hgrid_flux_ring_put_dev(m, grid, rec, fields, producer_stream) &
+        bind(C, name="mckpp_hip_multi_hgrid_flux_ring_put_dev") result(rc)
+      import :: c_int, c_ptr
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int), value :: grid, rec
+      type(c_ptr), intent(in) :: fields(8)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hgrid_fetch_dev(m, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_multi_hgrid_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hgrid_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hgrid_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
