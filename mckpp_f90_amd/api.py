@@ -24,7 +24,8 @@ have the zoomed output schedules of include/mckpp_hip_zoom.h: _SIGNATURES_ZOOM, 
 the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _SIGNATURES_PUT, and two more methods there;
 records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixth, _SIGNATURES_REDUCE, and three more;
 the caller's vertical axes (include/mckpp_hip_vaxis.h) are the seventh, _SIGNATURES_VAXIS, and the mixin _VerticalAxes;
-the caller's horizontal grids (include/mckpp_hip_hgrid.h) are the eighth, _SIGNATURES_HGRID, and the mixin _HorizontalGrids.
+the caller's horizontal grids (include/mckpp_hip_hgrid.h) are the eighth, _SIGNATURES_HGRID, and the mixin _HorizontalGrids;
+records out and state in on those grids (include/mckpp_hip_remap.h) are the ninth, _SIGNATURES_REMAP, and the mixin _Remap.
 """
 import ctypes as C
 import sys
@@ -486,6 +487,26 @@ _SIGNATURES_HGRID = {
 }
 
 
+class _RemapRecordPlaneC(C.Structure):
+    """mckpp_remap_record_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("sched", "field", "op", "lev0", "nlev", "dtype", "grid", "norm", "fill_land")] + \
+               [("rec", C.c_int64), ("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+class _RemapPutPlaneC(C.Structure):
+    """mckpp_remap_put_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "lev0", "nlev", "dtype", "op", "flags", "grid")] + \
+               [("skip_value", C.c_double), ("in", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_remap.h, records out and state in on the caller's horizontal grids, in the same
+# form; tests/test_remap_cpu.py holds this table to that header.
+_SIGNATURES_REMAP = {
+    "mckpp_hip_remap_records_dev": _sig(_H, _i32, C.POINTER(_RemapRecordPlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_remap_put_dev": _sig(_H, _i32, C.POINTER(_RemapPutPlaneC), C.c_void_p, twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -536,6 +557,11 @@ def _signatures_hgrid():
     return _spelled(_SIGNATURES_HGRID)
 
 
+def _signatures_remap():
+    """... and of every function of mckpp_hip_remap.h."""
+    return _spelled(_SIGNATURES_REMAP)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
@@ -543,7 +569,7 @@ def _bind(lib):
     # everything else works with it, and a call of that name fails there by name
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
                                   **_signatures_records(), **_signatures_put(), **_signatures_reduce(),
-                                  **_signatures_vaxis(), **_signatures_hgrid()}.items():
+                                  **_signatures_vaxis(), **_signatures_hgrid(), **_signatures_remap()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -1654,8 +1680,109 @@ class _HorizontalGrids:
         self._call("hgrid_fetch_dev", len(planes), arr, _dev_stream(stream))
 
 
+class _Remap:
+    """Records out and state in on the caller's horizontal grids (include/mckpp_hip_remap.h): records_dev and put_dev
+    through the weight tables of hgrid_define.  An array on grid g is (n_g,) or (nlev, n_g)."""
+
+    def remap_records_dev(self, planes, stream=None, norm="none", land_value=1e20, fill_land=True):
+        """records_dev onto caller grids: a plane is (sched, rec, field, op, grid, out) or (sched, rec, field, op, grid,
+        out, lev0, nlev) - op OP_MEAN / OP_MIN / OP_MAX / OP_LAST of `field` in record `rec` of schedule `sched`, levels
+        lev0 .. lev0 + nlev - 1 of the levels the schedule keeps (default: from 0, as many as out has room for), into
+        out, a tensor of shape (nlev, n) of float64 or float32 on grid `grid`.  A caller point's value is the weighted sum
+        over the points of its row of the grid's out table that are rows of the record - the resident columns, or a
+        zoom's listed resident columns -, with norm "used" divided by the sum of those weights; a caller point with no
+        such point gets land_value (fill_land), or keeps what out held.  The delivery is on the context's stream:
+        window_record_release and the next launch may follow at once."""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"remap_records_dev: {len(planes)} planes, at most 64 in one call")
+        nrm = _hgrid_norm("remap_records_dev", norm)
+        arr = (_RemapRecordPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            who = f"remap_records_dev: planes[{k}]"
+            if len(p) not in (6, 8):
+                raise ValueError(f"{who} is (sched, rec, field, op, grid, out) or (sched, rec, field, op, grid, out, lev0, nlev)")
+            sched, rec, op, out = int(p[0]), int(p[1]), int(p[3]), p[5]
+            try:
+                f = _win_check_fetch(self._scheds(), sched, p[2], op)
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            if rec < 0:
+                raise ValueError(f"{who}: record {rec}")
+            n = self._hgrid(who, p[4])
+            zoom = self._scheds()[sched].zoom
+            axis = 1 if f in _OUT_2D else (zoom[1] if zoom is not None else self._nzp1)
+            shape = tuple(getattr(out, "shape", ()))
+            if len(p) == 8:
+                lev0, nlev = int(p[6]), int(p[7])
+            else:
+                lev0, nlev = 0, (int(np.prod(shape, dtype=np.int64)) // n if n and len(shape) else 0)
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > axis:
+                raise ValueError(f"{who}: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, of which output "
+                                 f"schedule {sched} keeps {axis}")
+            if shape not in ((nlev, n), (nlev * n,)):
+                raise ValueError(f"{who}: out has shape {shape}; {nlev} levels on grid {int(p[4])} are ({nlev}, {n})")
+            ptr, typestr = _dev_array(out, f"{who} out", nlev * n, tuple(_DEV_TYPESTR))
+            arr[k] = _RemapRecordPlaneC(sched, f, op, lev0, nlev, _DEV_TYPESTR[typestr], int(p[4]), nrm, int(bool(fill_land)),
+                                        rec, float(land_value), ptr)
+            self._hold_dev(out)
+        self._call("remap_records_dev", len(planes), arr, _dev_stream(stream))
+
+    def remap_put_dev(self, planes, op="set", time_levels=False, skip=None, stream=None, fence=False):
+        """put_dev from caller grids: a plane is (field, grid, array) or (field, grid, array, lev0) - the array a tensor
+        of shape (nlev, n) of float64 or float32 on grid `grid`, for levels lev0 .. lev0 + nlev - 1 of field u, v, T,
+        S_anom or S.  Every resident column's value at a level is the sum of its row of the grid's in table over that
+        level of the array; op, time_levels and the surface references are put_dev's.  skip: a state element is left
+        untouched if any entry of its column's row reads this value at its level.  A resident column whose row is empty
+        is left untouched.  Nothing is cancelled.  The arrays must stay unchanged until a dev_fence on the stream that
+        next writes them (fence=True queues it on `stream`)."""
+        who = "remap_put_dev"
+        if op not in _PUT_OPS or isinstance(op, bool):
+            raise ValueError(f"{who}: op {op!r} (\"set\" or \"add\")")
+        flags, skip_value = (PUT_TIME_LEVELS if time_levels else 0), 0.0
+        if skip is not None:
+            flags, skip_value = flags | PUT_SKIP, float(skip)
+            if skip_value != skip_value:
+                raise ValueError(f"{who}: skip is NaN, which no element compares equal to")
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"{who}: {len(planes)} planes, at most 64 in one call")
+        arr, seen = (_RemapPutPlaneC * max(1, len(planes)))(), []
+        for k, p in enumerate(planes):
+            if len(p) not in (3, 4):
+                raise ValueError(f"{who}: planes[{k}] is (field, grid, array) or (field, grid, array, lev0)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: planes[{k}]: {e}") from None
+            if f not in _PUT_FIELDS:
+                raise ValueError(f"{who}: planes[{k}]: field {OUT_FIELDS[f]} is an output of the step, not state (u, v, T, "
+                                 "S_anom, S)")
+            n, a, lev0 = self._hgrid(f"{who}: planes[{k}]", p[1]), p[2], (int(p[3]) if len(p) > 3 else 0)
+            shape = tuple(getattr(a, "shape", ()))
+            nlev = int(np.prod(shape, dtype=np.int64)) // n if n and len(shape) else 0
+            if lev0 < 0 or nlev < 1 or lev0 + nlev > self._nzp1:
+                raise ValueError(f"{who}: planes[{k}]: levels {lev0} .. {lev0 + nlev - 1} of field {OUT_FIELDS[f]}, whose axis "
+                                 f"has {self._nzp1}")
+            if shape not in ((nlev, n), (nlev * n,)):
+                raise ValueError(f"{who}: planes[{k}]: the array has shape {shape}; levels on grid {int(p[1])} are (nlev, {n})")
+            for j, (g, a0, a1) in enumerate(seen):
+                if g == _PUT_FIELDS[f] and lev0 < a1 and a0 < lev0 + nlev:
+                    raise ValueError(f"{who}: planes[{k}] and planes[{j}] write {g} at overlapping levels {lev0} .. "
+                                     f"{lev0 + nlev - 1} and {a0} .. {a1 - 1}: the planes of a call have no order")
+            seen.append((_PUT_FIELDS[f], lev0, lev0 + nlev))
+            ptr, typestr = _dev_array(a, f"{who}: planes[{k}] array", nlev * n, tuple(_DEV_TYPESTR))
+            arr[k] = _RemapPutPlaneC(f, lev0, nlev, _DEV_TYPESTR[typestr], _PUT_OPS[op], flags, int(p[1]), skip_value, ptr)
+        s = _dev_stream(stream)
+        for p in planes:
+            self._hold_dev(p[2])
+        self._call("remap_put_dev", len(planes), arr, s)
+        if fence:
+            self._call("dev_fence", s)
+
+
 class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays, _VerticalAxes,
-              _HorizontalGrids):
+              _HorizontalGrids, _Remap):
     """What one device context and several GPUs behind one handle have in common: everything but how they are made.
     Method `name` is the C function self._pre + name applied to the handle self._h."""
     _pre = "mckpp_hip_"

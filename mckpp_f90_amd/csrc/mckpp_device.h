@@ -366,6 +366,20 @@ struct mckpp_hgrid_plane {
 #define MCKPP_HGRID_PLANES 64   // most planes of one call (the device table's size)
 // all `nplanes` planes of the device table `tab`; maxlev: the most levels of a plane, maxn: the most points of a grid
 hipError_t mckpp_launch_hgrid_out(const mckpp_hgrid_plane *tab, int nplanes, int maxlev, int64_t maxn, hipStream_t stream);
+// One plane of mckpp_hip_remap_put_dev (include/mckpp_hip_remap.h; k_remap_put_planes): put.in is in(n, put.nlev) on a
+// caller grid of n points; level lev of resident column c takes the sum of row c of the in table `t` - whose rows are
+// the resident columns in column order - over the plane's level lev, and put_element does with it what `put` says.
+// put's own skip is 0: `skip` is decided on the input side, where the values the entries read are.  A column with an
+// empty row is left alone.
+struct mckpp_remap_put_plane {
+  mckpp_put_plane put;
+  mckpp_hgrid_ell t;
+  int64_t n;
+  int skip;
+};
+#define MCKPP_REMAP_PLANES 64   // most planes of one call (the device table's size)
+hipError_t mckpp_launch_remap_put_planes(const mckpp_remap_put_plane *tab, int nplanes, int maxlev, int64_t ncol, double *cs,
+                                         hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

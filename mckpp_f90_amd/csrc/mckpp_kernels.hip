@@ -561,6 +561,75 @@ __global__ __launch_bounds__(256) void k_put_planes(const mckpp_put_plane *__res
   else tile_points_to_rows<true>(tile, ncol, e.nlev, l0, ipt, npts, static_cast<const double *>(e.in), put);
 }
 
+// State in from planes on a caller's horizontal grid (mckpp_hip_remap_put_dev, include/mckpp_hip_remap.h).  The relayout
+// tile of k_put_planes with the value formed on the point side, where tx is a resident column: the in table's rows are
+// the columns in column order, so the workgroup's 64 columns are one ELL slice, which its four waves share.  Wave ty
+// holds 16 of the tile's levels as the 16 running sums of hgrid_row_sums: an entry's index and weight are loaded once and
+// feed 16 gathers, one per level, each along the caller's points.  The sums cross the tile and a byte beside each says
+// that its element stays as it is - a value read was the skip value, or the row is empty; put_element is what happens
+// to the others on the row side.  A plane of one level takes a column per thread, 256 per workgroup, without the tile
+// (ONE_LEVEL above).  The barrier rule is kept by hand: the exits before the barrier depend on blockIdx and the plane.
+template <class T>
+__device__ __forceinline__ void remap_put_plane(const mckpp_remap_put_plane &e, double (*tile)[65], unsigned char (*hold)[68],
+                                                int64_t ncol, double *__restrict__ cs)
+{
+  const int l0 = blockIdx.y * 64, nlev = e.put.nlev;
+  if (l0 >= nlev) return;   // (the grid's level tiles are those of the deepest plane)
+  const T *__restrict__ src = static_cast<const T *>(e.put.in);
+  const double skip_value = e.put.skip_value;
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  if (nlev == 1) {   // the one-level path
+    if (blockIdx.x & 3) return;
+    const int64_t r = r0 + threadIdx.x;
+    double a[1], d;
+    bool hit = false;
+    const int len = hgrid_row_sums<1, false>(e.t, r, [&](int, int i) {
+      const double v = (double)src[i];
+      hit = hit || v == skip_value;
+      return v;
+    }, a, d);
+    if (r < ncol && len > 0 && !(e.skip && hit)) put_element(e.put, cs, r, 0, a[0]);
+    return;
+  }
+  {
+    const int lw = l0 + ty * 16;              // read: points fastest, 16 levels per wave
+    double a[16], d;
+    unsigned hit = 0u;
+    const int len = hgrid_row_sums<16, false>(e.t, r0 + tx, [&](int m, int i) {
+      if (lw + m >= nlev) return 0.0;         // (the wave's: a level past the plane is not read)
+      const double v = (double)src[(int64_t)(lw + m) * e.n + i];
+      if (v == skip_value) hit |= 1u << m;
+      return v;
+    }, a, d);
+    if (!e.skip) hit = 0u;
+    if (len == 0) hit = 0xffffu;              // an empty row, or a lane past the last column
+#pragma unroll
+    for (int m = 0; m < 16; ++m) {
+      tile[ty * 16 + m][tx] = a[m];
+      hold[ty * 16 + m][tx] = (hit >> m) & 1u;
+    }
+  }
+  __syncthreads();
+  const int lev = l0 + tx;
+  if (lev >= nlev) return;
+  for (int rr = ty; rr < 64; rr += 4) {       // write: levels fastest
+    const int64_t r = r0 + rr;
+    if (r >= ncol || hold[tx][rr]) continue;
+    put_element(e.put, cs, r, lev, tile[tx][rr]);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_remap_put_planes(const mckpp_remap_put_plane *__restrict__ tab, int64_t ncol,
+                                                          double *__restrict__ cs)
+{
+  __shared__ double tile[64][65];
+  __shared__ unsigned char hold[64][68];
+  const mckpp_remap_put_plane e = tab[blockIdx.z];
+  if (e.put.f32) remap_put_plane<float>(e, tile, hold, ncol, cs);
+  else remap_put_plane<double>(e, tile, hold, ncol, cs);
+}
+
 // ---------------------------------------------------------------------------
 // The caller's vertical axes (include/mckpp_hip_vaxis.h): planes on levels that are not the model's.  The interpolation
 // is stated there; vaxis_value is its per-element part - one subtraction, one product, one quotient, one sum, each a
@@ -890,6 +959,15 @@ hipError_t mckpp_launch_put_planes(const mckpp_put_plane *tab, int nplanes, int 
   if (nplanes <= 0 || maxlev <= 0 || ncol <= 0) return hipSuccess;
   dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
   hipLaunchKernelGGL(k_put_planes, grid, dim3(256), 0, stream, tab, ipt, ncol, npts, cs);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_remap_put_planes(const mckpp_remap_put_plane *tab, int nplanes, int maxlev, int64_t ncol, double *cs,
+                                         hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0 || ncol <= 0) return hipSuccess;
+  dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_remap_put_planes, grid, dim3(256), 0, stream, tab, ncol, cs);
   return hipGetLastError();
 }
 

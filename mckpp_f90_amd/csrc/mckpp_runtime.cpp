@@ -1,6 +1,6 @@
 // mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companions mckpp_hip_device.h,
 // mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h and
-// mckpp_hip_hgrid.h.
+// mckpp_hip_hgrid.h with mckpp_hip_remap.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
@@ -21,6 +21,7 @@
 #include "../../include/mckpp_hip_reduce.h"
 #include "../../include/mckpp_hip_vaxis.h"
 #include "../../include/mckpp_hip_hgrid.h"
+#include "../../include/mckpp_hip_remap.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -85,6 +86,14 @@ struct mckpp_ctx_resident {
   int window_count = 0;
   // output windows the step launches accumulate themselves (mckpp_hip_window_schedule): per schedule its fields, their
   // operation masks and rings of records; the steps run under it; the device table of all schedules' fields
+  // a device table of a caller's horizontal grid: see hgd below
+  struct hgrid_dev {
+    dev_buf<int64_t> off;
+    dev_buf<int> len, idx;
+    dev_buf<double> w;
+    int64_t nrows = 0, padded = 0, empty_point = -1;
+    int kind = 0;
+  };
   struct win_sched {
     std::vector<int> fields;        // empty: no schedule
     std::vector<unsigned> ops;
@@ -106,6 +115,12 @@ struct mckpp_ctx_resident {
     std::vector<int> rowpos;           // listed: row -> list position
     dev_buf<int> d_rowpos, d_colrow;   // listed: rowpos; resident column -> row, -1 outside the list (mckpp_win_t::row)
     dev_buf<int> d_rowpt;              // listed: row -> point number, where the reductions look a row's point weight up
+    std::vector<int> rowpt;            // ... and on the host, for what follows
+    // listed: per caller grid the out table of mckpp_hip_remap_records_dev (include/mckpp_hip_remap.h), the grid's out
+    // table with the entries kept whose point is a row of this schedule's records - kind as hgd[].out's: 0 not built,
+    // 1 this context's rows, 2 (shard 0 of a multi handle) the rows of any shard.  Built on first use; it goes with the
+    // schedule, being its member, and with the grid (hgrid_define)
+    hgrid_dev hout[MCKPP_HGRIDS];
     // listed: the list positions that are no row, for the planes of mckpp_hip_records_dev that fill them (an unlisted
     // schedule's are the context's d_land).  norow is this context's own, set with the schedule; d_norow holds nnorow
     // positions: norow itself (norow_kind 1), or - shard 0 of a multi handle - those no shard has a row for, the other
@@ -195,13 +210,6 @@ struct mckpp_ctx_resident {
   // this context's column map; 2 (out, shard 0 of a multi handle): for the union of the shards' columns.  empty_point:
   // the first resident column's point whose in row is empty (-1: none).  d_hstage: the staging plane(s) of
   // mckpp_hip_hgrid_fetch_dev, (npts, nlev) doubles per plane, grow-only (hgrid_stage).
-  struct hgrid_dev {
-    dev_buf<int64_t> off;
-    dev_buf<int> len, idx;
-    dev_buf<double> w;
-    int64_t nrows = 0, padded = 0, empty_point = -1;
-    int kind = 0;
-  };
   struct { hgrid_dev in, out; } hgd[MCKPP_HGRIDS];
   dev_buf<double> d_hstage;
   dev_buf<char> d_put_stage;  // the planes of mckpp_hip_put_host, grow-only: the call ends with a wait, so nothing reads it between calls
@@ -316,6 +324,7 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
     hgrid_csr in, out;
   } hg[MCKPP_HGRIDS];
   plane_table<mckpp_hgrid_plane, MCKPP_HGRID_PLANES> hgrid_tab;
+  plane_table<mckpp_remap_put_plane, MCKPP_REMAP_PLANES> rput_tab;   // mckpp_hip_remap_put_dev's (include/mckpp_hip_remap.h)
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -3258,6 +3267,7 @@ int hgrid_define(mckpp_hip_ctx *h, const char *who, int grid, int64_t n, const m
   h->hg[grid] = std::move(next);
   h->hgd[grid].in = hgrid_dev{};
   h->hgd[grid].out = hgrid_dev{};
+  for (auto &w : h->wsched) w.hout[grid] = hgrid_dev{};   // ... and the listed schedules' out tables on it (mckpp_hip_remap.h)
   return 0;
 }
 
@@ -3718,6 +3728,7 @@ static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, 
       bytes += rowpt.size() * sizeof(int);
       if (e == hipSuccess && w.nrow > 0) e = w.d_rowpt.alloc(rowpt.size());
       if (e == hipSuccess && w.nrow > 0) e = hipMemcpy(w.d_rowpt, rowpt.data(), rowpt.size() * sizeof(int), hipMemcpyHostToDevice);
+      w.rowpt = std::move(rowpt);
     }
     if (e == hipSuccess && !norow.empty()) {
       bytes += norow.size() * sizeof(int);
@@ -4016,6 +4027,226 @@ int mckpp_hip_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_r
   }
   if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
   return records_dev_queue(h, r, true, h->ev_caller, consumer_stream);
+  });
+}
+
+// ---------------------------------------------------------------------------
+// The caller's horizontal grids, second half (include/mckpp_hip_remap.h): a completed record's planes out through the
+// out table, U, V, T, S in through the in table.  Both are the existing calls' parts put together: a record plane is
+// resolved by what resolves a plane of mckpp_hip_records_dev and a grid by what mckpp_hip_hgrid_fetch_dev uses, stage 1
+// is k_record_planes into the hgrid staging (by point number, no fill), stage 2 k_hgrid_out; a put plane is resolved by
+// put_resolve and queued in put_queue's order, with k_remap_put_planes as the launch.  Checks queue nothing.
+// ---------------------------------------------------------------------------
+extern "C++" {
+namespace {
+// The planes of a record delivery on caller grids: stage 1 as planes of k_record_planes (`out` set when it is queued:
+// at[k] doubles into the staging block), stage 2 as planes of k_hgrid_out (stage and table likewise).
+struct remap_recs {
+  std::vector<mckpp_rec_plane> first;
+  std::vector<mckpp_hgrid_plane> second;
+  std::vector<int> sched, grid;
+  std::vector<size_t> at;
+  size_t elems = 0;
+  int maxlev = 0;
+  int64_t maxn = 0;
+};
+
+int remap_records_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_remap_record_plane_c *planes, remap_recs &r,
+                        int *dev)
+{
+  if (nplanes < 0 || nplanes > MCKPP_REMAP_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_REMAP_PLANES_MAX);
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  HIPCHK(hipSetDevice(h->device));
+  r = remap_recs{};
+  std::vector<std::pair<const char *, const char *>> span;
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_remap_record_plane_c &q = planes[k];
+    char at[96], arg[32];
+    snprintf(at, sizeof at, "%s: planes[%d]", who, k);
+    size_t i = 0;
+    if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
+    const auto &w = h->wsched[q.sched];
+    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem) return -1;
+    snprintf(arg, sizeof arg, "planes[%d]", k);
+    const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
+    if (!g) return -1;
+    if (g->out.ptr.empty())
+      return fail("%s: planes[%d]: grid %d has no out table (model -> caller): mckpp_hip_hgrid_define was given none", who, k,
+                  q.grid);
+    if (q.norm != MCKPP_HGRID_NORM_NONE && q.norm != MCKPP_HGRID_NORM_USED)
+      return fail("%s: planes[%d]: norm %d (MCKPP_HGRID_NORM_NONE 0, MCKPP_HGRID_NORM_USED 1)", who, k, q.norm);
+    const size_t bytes = (size_t)g->n * (size_t)q.nlev * elem;
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    if (dev_ptr_check(h, who, arg, q.out, bytes, k == 0 ? dev : nullptr)) return -1;
+    const char *b = static_cast<const char *>(q.out);
+    for (int j = 0; j < k; ++j)
+      if (b < span[(size_t)j].second && span[(size_t)j].first < b + bytes)
+        return fail("%s: planes[%d].out and planes[%d].out overlap: the planes of a call have no order", who, k, j);
+    span.emplace_back(b, b + bytes);
+    mckpp_rec_plane e{};   // into the staging by point number; what is no row is never written and never read
+    e.src = win_plane_rows(w, i, q.rec, q.op);
+    e.map = w.listed ? w.d_rowpt.get() : h->d_ipt.get();
+    e.period = (double)w.period;
+    e.nrow = w.nrow; e.npoints = h->npts;
+    e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
+    e.mean = q.op == 0;
+    r.first.push_back(e);
+    r.second.push_back(mckpp_hgrid_plane{nullptr, q.out, q.land_value, mckpp_hgrid_ell{}, h->npts, q.nlev,
+                                         q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.norm, q.fill_land ? 1 : 0});
+    r.sched.push_back(q.sched);
+    r.grid.push_back(q.grid);
+    r.at.push_back(r.elems);
+    r.elems += (size_t)h->npts * (size_t)q.nlev;
+    r.maxlev = std::max(r.maxlev, (int)q.nlev);
+    r.maxn = std::max(r.maxn, g->n);
+  }
+  return 0;
+}
+
+// the out table of a listed schedule on a grid for `covered` (null: this context's own rows; kind 1 / 2 as
+// hgrid_out_build's), built where it is not that
+int remap_out_build(mckpp_hip_ctx *h, int sched, int grid, const std::vector<unsigned char> *covered)
+{
+  auto &w = h->wsched[sched];
+  hgrid_dev &d = w.hout[grid];
+  const int kind = covered ? 2 : 1;
+  if (d.kind == kind) return 0;
+  std::vector<unsigned char> own;
+  if (!covered) {
+    own.assign((size_t)h->npts, 0);
+    for (int p : w.rowpt) own[(size_t)p] = 1;
+    covered = &own;
+  }
+  return hgrid_build(h, d, h->hg[grid].n, nullptr, h->hg[grid].out.view(), covered->data(), kind);
+}
+
+// the table stage 2 reads for plane k
+const hgrid_dev &remap_out_table(mckpp_hip_ctx *h, const remap_recs &r, size_t k)
+{
+  auto &w = h->wsched[r.sched[k]];
+  return w.listed ? w.hout[r.grid[k]] : h->hgd[r.grid[k]].out;
+}
+
+// stage 1 on this context's stream, behind `before`: its rows' values into `stage`
+int remap_records_first(mckpp_hip_ctx *h, remap_recs &r, double *stage, hipEvent_t before)
+{
+  HIPCHK(hipSetDevice(h->device));
+  int64_t xtiles = 0;
+  for (size_t k = 0; k < r.first.size(); ++k) {
+    r.first[k].out = stage + r.at[k];
+    xtiles = std::max<int64_t>(xtiles, (r.first[k].nrow + 63) / 64);
+  }
+  HIPCHK(h->rec_tab.put(r.first, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
+  HIPCHK(mckpp_launch_record_planes(h->rec_tab, (int)r.first.size(), r.maxlev, xtiles, h->stream));
+  return 0;
+}
+
+// stage 2 on this context's stream, from `stage` through the tables as they are built; the consumer waits for it
+int remap_records_second(mckpp_hip_ctx *h, remap_recs &r, const double *stage, void *consumer_stream)
+{
+  HIPCHK(hipSetDevice(h->device));
+  for (size_t k = 0; k < r.second.size(); ++k) {
+    r.second[k].stage = stage + r.at[k];
+    r.second[k].t = hgrid_ell(remap_out_table(h, r, k));
+  }
+  HIPCHK(h->hgrid_tab.put(r.second, h->stream));
+  HIPCHK(mckpp_launch_hgrid_out(h->hgrid_tab, (int)r.second.size(), r.maxlev, r.maxn, h->stream));
+  HIPCHK(h->ev_delivered.record(h->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+
+struct remap_puts {
+  std::vector<mckpp_remap_put_plane> tab;
+  int maxlev = 0;
+};
+
+// The planes of a put on caller grids, checked and resolved into the kernel's table (the device tables `t` set when it
+// is queued): put_resolve's checks and put_check's overlap rule, then the grid and its in table.
+int remap_put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_remap_put_plane_c *planes, remap_puts &r, int *dev)
+{
+  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (nplanes < 0 || nplanes > MCKPP_REMAP_PLANES_MAX || (nplanes > 0 && !planes))
+    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_REMAP_PLANES_MAX);
+  HIPCHK(hipSetDevice(h->device));
+  r = remap_puts{};
+  int prof[MCKPP_REMAP_PLANES_MAX];
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_remap_put_plane_c &q = planes[k];
+    mckpp_remap_put_plane e{};
+    int row;
+    size_t elem;
+    if (put_resolve(h, who, k, q.field, q.lev0, q.nlev, q.dtype, q.op, q.flags, q.skip_value, e.put, &row, &elem)) return -1;
+    for (int j = 0; j < k; ++j)
+      if (prof[j] == row && q.lev0 < planes[j].lev0 + planes[j].nlev && planes[j].lev0 < q.lev0 + q.nlev)
+        return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d) at overlapping levels %d..%d and %d..%d: the "
+                    "planes of a call have no order", who, k, j, q.field, planes[j].field, q.lev0, q.lev0 + q.nlev - 1,
+                    planes[j].lev0, planes[j].lev0 + planes[j].nlev - 1);
+    prof[k] = row;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d]", k);
+    const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
+    if (!g) return -1;
+    if (g->in.ptr.empty())
+      return fail("%s: planes[%d]: grid %d has no in table (caller -> model): mckpp_hip_hgrid_define was given none", who, k,
+                  q.grid);
+    snprintf(arg, sizeof arg, "planes[%d].in", k);
+    if (dev_ptr_check(h, who, arg, q.in, (size_t)g->n * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
+    e.put.in = q.in;
+    e.skip = e.put.skip;   // decided on the input side, where the values the entries read are: put_element's own is off
+    e.put.skip = 0;
+    e.n = g->n;
+    if (hgrid_in_build(h, q.grid)) return -1;   // (on first use, as hgrid_in_check does; an empty row is no refusal here)
+    e.t = hgrid_ell(h->hgd[q.grid].in);
+    r.tab.push_back(e);
+    r.maxlev = std::max(r.maxlev, (int)q.nlev);
+  }
+  return 0;
+}
+
+// put_queue's order with the remap's launch
+int remap_put_queue(mckpp_hip_ctx *h, const remap_puts &r, hipEvent_t produced)
+{
+  if (r.tab.empty() || h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(h->rput_tab.put(r.tab, h->stream));
+  if (produced) HIPCHK(hipStreamWaitEvent(h->stream, produced, 0));
+  HIPCHK(mckpp_launch_remap_put_planes(h->rput_tab, (int)r.tab.size(), r.maxlev, h->ncol, h->d_cs, h->stream));
+  HIPCHK(h->ev_read.record(h->stream));
+  return 0;
+}
+}  // namespace
+}  // extern "C++"
+
+int mckpp_hip_remap_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_remap_record_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  remap_recs r;
+  if (remap_records_check(h, who, nplanes, planes, r, nullptr)) return -1;
+  if (r.first.empty()) return 0;
+  for (size_t k = 0; k < r.first.size(); ++k) {   // (a shard addressed on its own: its own rows again)
+    if (h->wsched[r.sched[k]].listed ? remap_out_build(h, r.sched[k], r.grid[k], nullptr) : hgrid_out_build(h, r.grid[k], nullptr))
+      return -1;
+  }
+  if (hgrid_stage(h, r.elems)) return -1;
+  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
+  if (remap_records_first(h, r, h->d_hstage, h->ev_caller)) return -1;
+  return remap_records_second(h, r, h->d_hstage, consumer_stream);
+  });
+}
+
+int mckpp_hip_remap_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_remap_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int {
+  remap_puts r;
+  if (remap_put_check(h, who, nplanes, planes, r, nullptr)) return -1;
+  if (r.tab.empty() || h->ncol == 0) return 0;
+  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
+  return remap_put_queue(h, r, h->ev_caller);
   });
 }
 
@@ -5753,6 +5984,75 @@ int mckpp_hip_multi_hgrid_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, c
     }
   }
   return hgrid_fetch_second(root, rs[0], stage, consumer_stream);
+  });
+}
+
+// include/mckpp_hip_remap.h over all shards.  Records: mckpp_hip_multi_hgrid_fetch_dev's order - every shard's rows into
+// shard 0's staging, shard 0's second stage behind them, through tables whose used entries are the rows of any shard.
+// Puts: mckpp_hip_multi_put_dev's order, every shard through its own in table.
+static int multi_remap_out(mckpp_hip_multi *m, const char *who, int sched, int grid)
+{
+  mckpp_hip_ctx *root = m->ctx[0];
+  if (!root->wsched[sched].listed) return multi_hgrid_out(m, who, grid);
+  if (root->wsched[sched].hout[grid].kind == 2) return 0;
+  std::vector<unsigned char> covered((size_t)m->npts, 0);
+  for (auto *x : m->ctx)
+    for (int p : x->wsched[sched].rowpt) covered[(size_t)p] = 1;
+  return remap_out_build(root, sched, grid, &covered);
+}
+
+int mckpp_hip_multi_remap_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_remap_record_plane_c *planes,
+                                      void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<remap_recs> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (remap_records_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  mckpp_hip_ctx *root = m->ctx[0];
+  for (size_t k = 0; k < rs[0].first.size(); ++k)
+    if (multi_remap_out(m, who, rs[0].sched[k], rs[0].grid[k])) return -1;
+  if (hgrid_stage(root, rs[0].elems)) return -1;
+  double *stage = root->d_hstage;
+  for (int d = 1; d < ndev; ++d) {   // every shard's device reaches shard 0's staging (peer access, once per pair)
+    HIPCHK(hipSetDevice(m->ctx[d]->device));
+    if (dev_ptr_check(m->ctx[d], who, "the staging plane of shard 0", stage, rs[0].elems * sizeof(double))) return -1;
+  }
+  if (multi_caller_event(m, dev, consumer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d) {
+    mckpp_hip_ctx *x = m->ctx[d];
+    if (d > 0) {
+      HIPCHK(hipSetDevice(x->device));
+      // the staging is shard 0's: behind the second stage of the call before, which read it on shard 0's stream
+      if (root->ev_delivered) HIPCHK(hipStreamWaitEvent(x->stream, root->ev_delivered, 0));
+    }
+    if (remap_records_first(x, rs[(size_t)d], stage, m->ev_caller)) return -1;
+    if (d > 0) {   // ... and shard 0's second stage behind this shard's first
+      HIPCHK(x->ev_delivered.record(x->stream));
+      HIPCHK(hipSetDevice(root->device));
+      HIPCHK(hipStreamWaitEvent(root->stream, x->ev_delivered, 0));
+    }
+  }
+  return remap_records_second(root, rs[0], stage, consumer_stream);
+  });
+}
+
+int mckpp_hip_multi_remap_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_remap_put_plane_c *planes,
+                                  void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int {
+  const int ndev = (int)m->ctx.size();
+  std::vector<remap_puts> rs((size_t)ndev);
+  int dev = -1;
+  for (int d = 0; d < ndev; ++d)
+    if (remap_put_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (multi_caller_event(m, dev, producer_stream)) return -1;
+  for (int d = 0; d < ndev; ++d)
+    if (remap_put_queue(m->ctx[d], rs[(size_t)d], m->ev_caller)) return -1;
+  return 0;
   });
 }
 

@@ -1,5 +1,5 @@
 !> iso_c_binding view of include/mckpp_hip.h and of its companions
-!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h and mckpp_hip_hgrid.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h, mckpp_hip_hgrid.h and mckpp_hip_remap.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -120,6 +120,23 @@ module mckpp_hip_binding
     real(c_double) :: land_value
     type(c_ptr) :: out
   end type mckpp_hgrid_plane_c
+  !> records out and state in on the caller's horizontal grids (include/mckpp_hip_remap.h).  One plane of
+  !! mckpp_hip_remap_records_dev: mckpp_dev_record_plane_c's plane remapped onto caller grid `grid`, into out (n, nlev),
+  !! with norm and fill_land as in mckpp_hgrid_plane_c; the used entries are those whose point is a row of the record
+  integer(c_int32_t), parameter :: MCKPP_REMAP_PLANES_MAX = 64
+  type, bind(C) :: mckpp_remap_record_plane_c
+    integer(c_int32_t) :: sched, field, op, lev0, nlev, dtype, grid, norm, fill_land
+    integer(c_int64_t) :: rec
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_remap_record_plane_c
+  !> one plane of mckpp_hip_remap_put_dev: mckpp_put_plane_c's plane with the array at `in`, (n, nlev), on caller grid
+  !! `grid`; every resident column takes the sum of its row of the grid's in table, an empty row leaves it alone
+  type, bind(C) :: mckpp_remap_put_plane_c
+    integer(c_int32_t) :: field, lev0, nlev, dtype, op, flags, grid
+    real(c_double) :: skip_value
+    type(c_ptr) :: in
+  end type mckpp_remap_put_plane_c
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -1135,6 +1152,39 @@ module mckpp_hip_binding
       type(c_ptr), value :: m, consumer_stream
       integer(c_int32_t), value :: nplanes
       type(mckpp_hgrid_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! records out and state in on the caller's horizontal grids (include/mckpp_hip_remap.h): mckpp_hip_records_dev and
+    ! mckpp_hip_put_dev through the weight tables of mckpp_hip_hgrid_define, with those calls' ordering
+    function mckpp_hip_remap_records_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_remap_records_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_remap_record_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_remap_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_remap_put_dev(handle, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_remap_put_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_remap_put_plane_c
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_remap_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_remap_records_dev(m, nplanes, planes, consumer_stream) &
+        bind(C, name="mckpp_hip_multi_remap_records_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_remap_record_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_remap_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_remap_put_dev(m, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_multi_remap_put_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_remap_put_plane_c
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_remap_put_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
