@@ -122,10 +122,9 @@ struct mckpp_ctx_resident {
     // schedule, being its member, and with the grid (hgrid_define)
     hgrid_dev hout[MCKPP_HGRIDS];
     // listed: the list positions that are no row, for the planes of mckpp_hip_records_dev that fill them (an unlisted
-    // schedule's are the context's d_land).  norow is this context's own, set with the schedule; d_norow holds nnorow
-    // positions: norow itself (norow_kind 1), or - shard 0 of a multi handle - those no shard has a row for, the other
-    // shards filling none (2; win_norow_set)
-    std::vector<int> norow;
+    // schedule's are the context's d_land).  d_norow holds nnorow positions: this context's own, set with the schedule
+    // (norow_kind 1), or - shard 0 of a multi handle - those no shard has a row for, the other shards filling none (2);
+    // group_norow brings it up to date for the group a call addresses
     dev_buf<int> d_norow;
     int64_t nnorow = 0;
     int norow_kind = 1;
@@ -197,8 +196,8 @@ struct mckpp_ctx_resident {
     pinned_turns<double> stage;
   } ring;
   // the grid points that are no resident column, for the planes of mckpp_hip_fetch_dev that fill them.  land_kind 0: not
-  // built (first use builds it; a new column map drops it: land_drop); 1: the complement of this context's column map; 2: a
-  // shard of a multi handle, given its list - shard 0 the points no shard holds, the others none
+  // built (first use builds it; a new column map drops it); 1: the complement of this context's column map; 2: shard 0 of a
+  // multi handle - the points no shard holds, the other shards filling none (group_land)
   dev_buf<int> d_land;
   int64_t nland = 0;
   int land_kind = 0;
@@ -2487,12 +2486,44 @@ int mckpp_hip_window_fetch(mckpp_hip_handle h, int field, int op, double *out)
 
 // ---------------------------------------------------------------------------
 // The device-array interface (include/mckpp_hip_device.h): forcing from the caller's device arrays, output fields into
-// them, ordered by events on the caller's stream.  Every call is a check, which queues nothing, and a part that queues:
-// a multi handle checks all its shards before any of them queues.
+// them, ordered by events on the caller's stream.  Every call is a check, which queues nothing, and a part that queues.
+//
+// A call has one body, which takes the contexts it addresses as a ctx_group - a lone context is a group of one, a multi
+// handle the group of its shards, shard 0 the root - and keeps one order: every shard is checked before anything is
+// queued; the root's lists and tables of the points the group holds are brought up to date; one event goes on the
+// caller's stream; every shard's part is queued behind it; the root's last stage, where the call has one, runs.  Both
+// extern "C" entries of a call hand their group to that body.
 // ---------------------------------------------------------------------------
 extern "C++" {
 namespace {
 const char *const flux_field_names[8] = {"taux", "tauy", "swf", "lwf", "lhf", "shf", "rain", "snow"};
+
+// The contexts a call addresses.  kind: what the root's lists and tables of the group's points are marked with (land_kind,
+// norow_kind, hgrid_dev::kind) - 1 a lone context's own columns, 2 the union of a multi handle's shards; so a shard
+// addressed on its own after its multi handle finds the union's and builds its own again, and the other way round.
+// ev: the event recorded on the caller's stream.  A lone context's is its own, on its device (ev_dev null); a multi
+// handle's lives on *ev_dev, the device of the call's first array, and is made anew when that changes - the two differ
+// for arrays on a peer device.
+struct ctx_group {
+  mckpp_hip_ctx *const *ctx;
+  int n, kind;
+  hip_event *ev;
+  int *ev_dev;
+  mckpp_hip_ctx *root() const { return ctx[0]; }
+  mckpp_hip_ctx *const *begin() const { return ctx; }
+  mckpp_hip_ctx *const *end() const { return ctx + n; }
+};
+
+ctx_group lone(mckpp_hip_ctx *&h) { return ctx_group{&h, 1, 1, &h->ev_caller, nullptr}; }
+
+// what opens the checks of the plane tables: the count against the call's cap, and a state to deliver from or write to
+int planes_count_check(const char *who, int32_t nplanes, const void *planes, int cap)
+{
+  if (nplanes >= 0 && nplanes <= cap && (nplanes == 0 || planes)) return 0;
+  return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, cap);
+}
+
+int uploaded_check(const mckpp_hip_ctx *h, const char *who) { return h->npts > 0 ? 0 : fail("%s: upload the state first", who); }
 
 // Is `p` device memory with room for `bytes` that the context's device reaches?  (The context's device is current.)
 int dev_ptr_check(mckpp_hip_ctx *h, const char *who, const char *arg, const void *p, size_t bytes, int *dev_out = nullptr)
@@ -2545,12 +2576,14 @@ int dev_fields_check(mckpp_hip_ctx *h, const char *who, const double *const fiel
   return 0;
 }
 
-// An event on the caller's stream, recorded now: what the library's streams wait for.  `ev` lives on `device`, the
-// device of the caller's stream (taken to be that of its arrays).
-int caller_event(hip_event &ev, int device, void *stream)
+// The group's event on the caller's stream, recorded now: what the library's streams wait for.  dev: the device of the
+// call's first array, taken to be that of the caller's stream (ctx_group::ev).
+int caller_event(const ctx_group &g, int dev, void *stream)
 {
-  HIPCHK(hipSetDevice(device));
-  HIPCHK(ev.record(static_cast<hipStream_t>(stream)));
+  if (!g.ev_dev) dev = g.root()->device;
+  else if (*g.ev_dev != dev) { g.ev->reset(); *g.ev_dev = dev; }
+  HIPCHK(hipSetDevice(dev));
+  HIPCHK(g.ev->record(static_cast<hipStream_t>(stream)));
   return 0;
 }
 
@@ -2616,9 +2649,7 @@ size_t plane_elem(const char *who, int k, int dtype)
 int fetch_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_dev_plane_c *planes,
                     std::vector<mckpp_fetch_plane> &tab, int *maxlev, bool *any_fill, int *dev)
 {
-  if (nplanes < 0 || nplanes > MCKPP_DEV_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_DEV_PLANES_MAX);
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (planes_count_check(who, nplanes, planes, MCKPP_DEV_PLANES_MAX) || uploaded_check(h, who)) return -1;
   HIPCHK(hipSetDevice(h->device));
   tab.clear();
   *maxlev = 0;
@@ -2640,41 +2671,52 @@ int fetch_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mc
   return 0;
 }
 
-// the list of points a context's planes fill with their land value (mckpp_ctx_resident::d_land)
-int land_set(mckpp_hip_ctx *h, const std::vector<int> &land, int kind)
+// A list of the positions a context's planes fill with their land value - the grid's points (mckpp_ctx_resident::d_land)
+// or those of a schedule's point list (win_sched::d_norow) - as what `covered` does not mark, with its count and kind.
+int fill_list_set(mckpp_hip_ctx *h, dev_buf<int> &d, int64_t &n, int &kind_of, const std::vector<unsigned char> &covered, int kind)
 {
-  HIPCHK(hipStreamSynchronize(h->stream));   // (first use, or a new column map: a launch in flight may read the old list)
-  HIPCHK(h->d_land.reserve(std::max<size_t>(land.size(), 1)));
-  if (!land.empty()) HIPCHK(hipMemcpy(h->d_land, land.data(), land.size() * sizeof(int), hipMemcpyHostToDevice));
-  h->nland = (int64_t)land.size();
-  h->land_kind = kind;
+  std::vector<int> list;
+  for (size_t i = 0; i < covered.size(); ++i)
+    if (!covered[i]) list.push_back((int)i);
+  HIPCHK(hipSetDevice(h->device));
+  // first use, a new column map, or a change of who addresses the shard: a launch in flight may read the old list
+  HIPCHK(hipStreamSynchronize(h->stream));
+  HIPCHK(d.reserve(std::max<size_t>(list.size(), 1)));
+  if (!list.empty()) HIPCHK(hipMemcpy(d, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
+  n = (int64_t)list.size();
+  kind_of = kind;
   return 0;
 }
 
-// the points in 0 .. npts-1 that `covered` does not mark
-std::vector<int> points_not(const std::vector<unsigned char> &covered)
+// Which points does the group hold?  covered[i]: point i is a resident column of one of its contexts.
+int group_columns(const ctx_group &g, const char *who, std::vector<unsigned char> &covered)
 {
-  std::vector<int> out;
-  for (size_t i = 0; i < covered.size(); ++i)
-    if (!covered[i]) out.push_back((int)i);
-  return out;
+  covered.assign((size_t)g.root()->npts, 0);
+  for (auto *x : g)
+    for (int i : x->ipt) {
+      if (i < 0 || (size_t)i >= covered.size()) return fail("%s: a column map names a point outside the grid", who);
+      covered[(size_t)i] = 1;
+    }
+  return 0;
 }
 
-// ... of a context of its own, where none is built: everything its column map leaves out
-int land_own(mckpp_hip_ctx *h)
+// the root's land list as the points the group does not hold, where it is not that already: the root fills them, the
+// other shards of a multi handle fill none, so every point is written once
+int group_land(const ctx_group &g, const char *who)
 {
-  if (h->land_kind != 0) return 0;
-  std::vector<unsigned char> covered((size_t)h->npts, 0);
-  for (int i : h->ipt) covered[(size_t)i] = 1;
-  return land_set(h, points_not(covered), 1);
+  mckpp_hip_ctx *root = g.root();
+  if (root->land_kind == g.kind) return 0;
+  std::vector<unsigned char> covered;
+  if (group_columns(g, who, covered)) return -1;
+  return fill_list_set(root, root->d_land, root->nland, root->land_kind, covered, g.kind);
 }
 
+// any_fill: this context fills the land points (group_land has brought its list up to date)
 int fetch_dev_queue(mckpp_hip_ctx *h, const std::vector<mckpp_fetch_plane> &tab, int maxlev, bool any_fill, hipEvent_t before,
                     void *consumer_stream)
 {
   if (tab.empty()) return 0;
   HIPCHK(hipSetDevice(h->device));
-  if (any_fill && land_own(h)) return -1;
   HIPCHK(h->fetch_tab.put(tab, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
   HIPCHK(mckpp_launch_fetch_planes(h->fetch_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
@@ -2690,48 +2732,94 @@ int dev_fence_queue(mckpp_hip_ctx *h, void *stream)
   if (h->ev_read_flux) HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(stream), h->ev_read_flux, 0));
   return 0;
 }
+
+// (what a forcing call on a caller's grid checks in place of dev_fields_check: with the caller's horizontal grids, below)
+int hgrid_in_check(mckpp_hip_ctx *h, const char *who, int grid, const double *const fields[8], mckpp_hgrid_ell *t, int *dev);
+
+// mckpp_hip_fluxes_dev and, with a grid (include/mckpp_hip_hgrid.h), mckpp_hip_hgrid_fluxes_dev: every shard forms the
+// forcing of its own columns from the same caller arrays
+int fluxes_dev(const ctx_group &g, const char *who, int ntime, const double *const fields[8], int l_rest, double flsn, double el,
+               void *producer_stream, const int *grid = nullptr)
+{
+  std::vector<mckpp_hgrid_ell> t((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (!grid ? dev_fields_check(g.ctx[d], who, fields, &dev) : hgrid_in_check(g.ctx[d], who, *grid, fields, &t[(size_t)d], &dev))
+      return -1;
+  if (dev < 0) return 0;
+  if (caller_event(g, dev, producer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (fluxes_dev_queue(g.ctx[d], ntime, fields, l_rest, flsn, el, *g.ev, grid ? &t[(size_t)d] : nullptr)) return -1;
+  return 0;
+}
+
+// mckpp_hip_flux_ring_put_dev and mckpp_hip_hgrid_flux_ring_put_dev likewise
+int flux_ring_put_dev(const ctx_group &g, const char *who, int rec, const double *const fields[8], void *producer_stream,
+                      const int *grid = nullptr)
+{
+  if (!fields) return fail("%s: null argument", who);
+  std::vector<mckpp_hgrid_ell> t((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d) {
+    if (ring_put_check(g.ctx[d], who, rec)) return -1;
+    if (!grid ? dev_fields_check(g.ctx[d], who, fields, &dev) : hgrid_in_check(g.ctx[d], who, *grid, fields, &t[(size_t)d], &dev))
+      return -1;
+  }
+  if (dev < 0) return 0;
+  if (caller_event(g, dev, producer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (ring_put_dev_queue(g.ctx[d], rec, fields, *g.ev, grid ? &t[(size_t)d] : nullptr)) return -1;
+  return 0;
+}
+
+// mckpp_hip_fetch_dev: a shard writes its own columns of every plane, the root the land values
+int fetch_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
+{
+  std::vector<std::vector<mckpp_fetch_plane>> tabs((size_t)g.n);
+  int maxlev = 0, dev = -1;
+  bool any_fill = false;
+  for (int d = 0; d < g.n; ++d)
+    if (fetch_dev_check(g.ctx[d], who, nplanes, planes, tabs[(size_t)d], &maxlev, &any_fill, &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (any_fill) {
+    for (int d = 1; d < g.n; ++d)
+      for (auto &e : tabs[(size_t)d]) e.fill_land = 0;
+    if (group_land(g, who)) return -1;
+  }
+  if (caller_event(g, dev, consumer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (fetch_dev_queue(g.ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, *g.ev, consumer_stream)) return -1;
+  return 0;
+}
+
+int dev_fence(const ctx_group &g, void *stream)
+{
+  for (auto *x : g)
+    if (dev_fence_queue(x, stream)) return -1;
+  return 0;
+}
 }  // namespace
 }  // extern "C++"
 
 int mckpp_hip_fluxes_dev(mckpp_hip_handle h, int ntime, const double *const fields[8], int l_rest, double flsn, double el,
                          void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  if (dev_fields_check(h, who, fields, nullptr)) return -1;
-  if (h->ncol == 0) return 0;
-  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return fluxes_dev_queue(h, ntime, fields, l_rest, flsn, el, h->ev_caller);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return fluxes_dev(lone(h), who, ntime, fields, l_rest, flsn, el, producer_stream); });
 }
 
 int mckpp_hip_flux_ring_put_dev(mckpp_hip_handle h, int rec, const double *const fields[8], void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  if (!fields) return fail("%s: null argument", who);
-  if (ring_put_check(h, who, rec)) return -1;
-  if (dev_fields_check(h, who, fields, nullptr)) return -1;
-  if (h->ncol > 0 && caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return ring_put_dev_queue(h, rec, fields, h->ev_caller);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return flux_ring_put_dev(lone(h), who, rec, fields, producer_stream); });
 }
 
 int mckpp_hip_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  std::vector<mckpp_fetch_plane> tab;
-  int maxlev = 0;
-  bool any_fill = false;
-  if (fetch_dev_check(h, who, nplanes, planes, tab, &maxlev, &any_fill, nullptr)) return -1;
-  if (tab.empty()) return 0;
-  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complement again)
-  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
-  return fetch_dev_queue(h, tab, maxlev, any_fill, h->ev_caller, consumer_stream);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return fetch_dev(lone(h), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_dev_fence(mckpp_hip_handle h, void *stream)
 {
-  return entry(__func__, h, [&]() -> int { return dev_fence_queue(h, stream); });
+  return entry(__func__, h, [&]() -> int { return dev_fence(lone(h), stream); });
 }
 
 // ---------------------------------------------------------------------------
@@ -2783,14 +2871,27 @@ int put_resolve(mckpp_hip_ctx *h, const char *who, int k, int field, int lev0, i
   return 0;
 }
 
+// The planes of a call have no order: planes[k], which writes profile `row`, may share no level of it with a plane
+// before it (prof[j]: the profile planes[j] writes; prof[k] is set).  For the calls whose planes name their levels.
+template <class P>
+int put_overlap_check(const char *who, int k, const P *planes, int *prof, int row)
+{
+  const P &q = planes[k];
+  for (int j = 0; j < k; ++j)
+    if (prof[j] == row && q.lev0 < planes[j].lev0 + planes[j].nlev && planes[j].lev0 < q.lev0 + q.nlev)
+      return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d) at overlapping levels %d..%d and %d..%d: the "
+                  "planes of a call have no order", who, k, j, q.field, planes[j].field, q.lev0, q.lev0 + q.nlev - 1,
+                  planes[j].lev0, planes[j].lev0 + planes[j].nlev - 1);
+  prof[k] = row;
+  return 0;
+}
+
 // The planes of a put, checked and resolved into the kernel's table.  dev_form: `in` is device memory (*dev, where asked
 // for: the device of the first plane's); otherwise host memory, and the table's `in` is set by put_host_queue.
 int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_put_plane_c *planes, bool dev_form,
               std::vector<mckpp_put_plane> &tab, int *maxlev, int *dev)
 {
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
-  if (nplanes < 0 || nplanes > MCKPP_PUT_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_PUT_PLANES_MAX);
+  if (uploaded_check(h, who) || planes_count_check(who, nplanes, planes, MCKPP_PUT_PLANES_MAX)) return -1;
   HIPCHK(hipSetDevice(h->device));
   tab.clear();
   *maxlev = 0;
@@ -2801,12 +2902,7 @@ int put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_pu
     int row;
     size_t elem;
     if (put_resolve(h, who, k, q.field, q.lev0, q.nlev, q.dtype, q.op, q.flags, q.skip_value, e, &row, &elem)) return -1;
-    for (int j = 0; j < k; ++j)
-      if (prof[j] == row && q.lev0 < planes[j].lev0 + planes[j].nlev && planes[j].lev0 < q.lev0 + q.nlev)
-        return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d) at overlapping levels %d..%d and %d..%d: the "
-                    "planes of a call have no order", who, k, j, q.field, planes[j].field, q.lev0, q.lev0 + q.nlev - 1,
-                    planes[j].lev0, planes[j].lev0 + planes[j].nlev - 1);
-    prof[k] = row;
+    if (put_overlap_check(who, k, planes, prof, row)) return -1;
     char arg[32];
     snprintf(arg, sizeof arg, "planes[%d].in", k);
     if (!dev_form) {
@@ -2855,29 +2951,34 @@ int put_host_queue(mckpp_hip_ctx *h, std::vector<mckpp_put_plane> &tab, int maxl
   HIPCHK(hipStreamSynchronize(h->stream));
   return 0;
 }
+
+// mckpp_hip_put_dev / _put_host: the same planes for every shard, which writes its own columns only
+int put_planes(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_put_plane_c *planes, bool dev_form,
+               void *producer_stream)
+{
+  std::vector<std::vector<mckpp_put_plane>> tabs((size_t)g.n);
+  int maxlev = 0, dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (put_check(g.ctx[d], who, nplanes, planes, dev_form, tabs[(size_t)d], &maxlev, dev_form ? &dev : nullptr)) return -1;
+  if (dev_form) {
+    if (dev < 0) return 0;   // (no plane)
+    if (caller_event(g, dev, producer_stream)) return -1;
+  }
+  for (int d = 0; d < g.n; ++d)
+    if (dev_form ? put_queue(g.ctx[d], tabs[(size_t)d], maxlev, *g.ev) : put_host_queue(g.ctx[d], tabs[(size_t)d], maxlev)) return -1;
+  return 0;
+}
 }  // namespace
 }  // extern "C++"
 
 int mckpp_hip_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_put_plane_c *planes, void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  std::vector<mckpp_put_plane> tab;
-  int maxlev = 0;
-  if (put_check(h, who, nplanes, planes, true, tab, &maxlev, nullptr)) return -1;
-  if (tab.empty() || h->ncol == 0) return 0;
-  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return put_queue(h, tab, maxlev, h->ev_caller);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return put_planes(lone(h), who, nplanes, planes, true, producer_stream); });
 }
 
 int mckpp_hip_put_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_put_plane_c *planes)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  std::vector<mckpp_put_plane> tab;
-  int maxlev = 0;
-  if (put_check(h, who, nplanes, planes, false, tab, &maxlev, nullptr)) return -1;
-  return put_host_queue(h, tab, maxlev);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return put_planes(lone(h), who, nplanes, planes, false, nullptr); });
 }
 
 // ---------------------------------------------------------------------------
@@ -2944,9 +3045,7 @@ struct vaxis_puts {
 int vaxis_put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, bool dev_form,
                     vaxis_puts &r, int *dev)
 {
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
-  if (nplanes < 0 || nplanes > MCKPP_VAXIS_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_VAXIS_PLANES_MAX);
+  if (uploaded_check(h, who) || planes_count_check(who, nplanes, planes, MCKPP_VAXIS_PLANES_MAX)) return -1;
   HIPCHK(hipSetDevice(h->device));
   r.tab.clear();
   r.bytes.clear();
@@ -3107,9 +3206,7 @@ const char *vaxis_interface_name(int field)
 int vaxis_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes,
                       std::vector<mckpp_vaxis_fetch_plane> &tab, int *maxlev, bool *any_fill, int *dev)
 {
-  if (nplanes < 0 || nplanes > MCKPP_VAXIS_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_VAXIS_PLANES_MAX);
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (planes_count_check(who, nplanes, planes, MCKPP_VAXIS_PLANES_MAX) || uploaded_check(h, who)) return -1;
   HIPCHK(hipSetDevice(h->device));
   tab.clear();
   *maxlev = 0;
@@ -3147,13 +3244,69 @@ int vaxis_fetch_queue(mckpp_hip_ctx *h, const std::vector<mckpp_vaxis_fetch_plan
 {
   if (tab.empty()) return 0;
   HIPCHK(hipSetDevice(h->device));
-  if (any_fill && land_own(h)) return -1;
   HIPCHK(h->vfetch_tab.put(tab, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
   HIPCHK(mckpp_launch_vaxis_fetch_planes(h->vfetch_tab, (int)tab.size(), maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
                                          any_fill ? h->d_land.get() : nullptr, any_fill ? h->nland : 0, h->stream));
   HIPCHK(h->ev_delivered.record(h->stream));
   HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  return 0;
+}
+
+// mckpp_hip_vaxis_put_dev / _put_host: the same planes for every shard, which touches its own columns only
+int vaxis_put(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, bool dev_form,
+              void *producer_stream)
+{
+  std::vector<vaxis_puts> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (vaxis_put_check(g.ctx[d], who, nplanes, planes, dev_form, rs[(size_t)d], dev_form ? &dev : nullptr)) return -1;
+  if (dev_form) {
+    if (dev < 0) return 0;   // (no plane)
+    if (caller_event(g, dev, producer_stream)) return -1;
+  }
+  for (int d = 0; d < g.n; ++d)
+    if (dev_form ? vaxis_put_queue(g.ctx[d], rs[(size_t)d].tab, *g.ev) : vaxis_put_host_queue(g.ctx[d], rs[(size_t)d])) return -1;
+  return 0;
+}
+
+// mckpp_hip_vaxis_init_profiles_dev / _host: every shard writes its columns and reports its Kelvin word; the host
+// combines them - the call waits, like the upload it follows - and every shard finishes under the combined word
+int vaxis_init_profiles(const ctx_group &g, const char *who, const mckpp_vaxis_profiles_c *p, bool dev_form, void *producer_stream)
+{
+  std::vector<vaxis_puts> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (vaxis_profiles_check(g.ctx[d], who, p, dev_form, rs[(size_t)d], dev_form ? &dev : nullptr)) return -1;
+  if (dev_form && caller_event(g, dev, producer_stream)) return -1;
+  unsigned any = 0;
+  for (int d = 0; d < g.n; ++d) {
+    unsigned kelvin = 0;
+    if (vaxis_profiles_write(g.ctx[d], rs[(size_t)d], dev_form, dev_form ? (hipEvent_t)*g.ev : nullptr, &kelvin)) return -1;
+    any |= kelvin;
+  }
+  for (auto *x : g)   // (a lone context's word is on its device already: only a multi handle's is copied back)
+    if (vaxis_profiles_finish(x, p->tk0, any, g.kind == 2)) return -1;
+  return 0;
+}
+
+// mckpp_hip_vaxis_fetch_dev: fetch_dev's order
+int vaxis_fetch_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes, void *consumer_stream)
+{
+  std::vector<std::vector<mckpp_vaxis_fetch_plane>> tabs((size_t)g.n);
+  int maxlev = 0, dev = -1;
+  bool any_fill = false;
+  for (int d = 0; d < g.n; ++d)
+    if (vaxis_fetch_check(g.ctx[d], who, nplanes, planes, tabs[(size_t)d], &maxlev, &any_fill, &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (any_fill) {
+    for (int d = 1; d < g.n; ++d)
+      for (auto &e : tabs[(size_t)d]) e.f.fill_land = 0;
+    if (group_land(g, who)) return -1;
+  }
+  if (caller_event(g, dev, consumer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (vaxis_fetch_queue(g.ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, *g.ev, consumer_stream)) return -1;
   return 0;
 }
 }  // namespace
@@ -3166,60 +3319,27 @@ int mckpp_hip_vaxis_define(mckpp_hip_handle h, int axis, int32_t n, const double
 
 int mckpp_hip_vaxis_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  vaxis_puts r;
-  if (vaxis_put_check(h, who, nplanes, planes, true, r, nullptr)) return -1;
-  if (r.tab.empty() || h->ncol == 0) return 0;
-  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return vaxis_put_queue(h, r.tab, h->ev_caller);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return vaxis_put(lone(h), who, nplanes, planes, true, producer_stream); });
 }
 
 int mckpp_hip_vaxis_put_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  vaxis_puts r;
-  if (vaxis_put_check(h, who, nplanes, planes, false, r, nullptr)) return -1;
-  return vaxis_put_host_queue(h, r);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return vaxis_put(lone(h), who, nplanes, planes, false, nullptr); });
 }
 
 int mckpp_hip_vaxis_init_profiles_dev(mckpp_hip_handle h, const mckpp_vaxis_profiles_c *p, void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  vaxis_puts r;
-  unsigned kelvin = 0;
-  if (vaxis_profiles_check(h, who, p, true, r, nullptr)) return -1;
-  if (h->ncol == 0) return 0;
-  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  if (vaxis_profiles_write(h, r, true, h->ev_caller, &kelvin)) return -1;
-  return vaxis_profiles_finish(h, p->tk0, kelvin, false);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return vaxis_init_profiles(lone(h), who, p, true, producer_stream); });
 }
 
 int mckpp_hip_vaxis_init_profiles_host(mckpp_hip_handle h, const mckpp_vaxis_profiles_c *p)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  vaxis_puts r;
-  unsigned kelvin = 0;
-  if (vaxis_profiles_check(h, who, p, false, r, nullptr)) return -1;
-  if (vaxis_profiles_write(h, r, false, nullptr, &kelvin)) return -1;
-  return vaxis_profiles_finish(h, p->tk0, kelvin, false);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return vaxis_init_profiles(lone(h), who, p, false, nullptr); });
 }
 
 int mckpp_hip_vaxis_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  std::vector<mckpp_vaxis_fetch_plane> tab;
-  int maxlev = 0;
-  bool any_fill = false;
-  if (vaxis_fetch_check(h, who, nplanes, planes, tab, &maxlev, &any_fill, nullptr)) return -1;
-  if (tab.empty()) return 0;
-  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complement again)
-  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
-  return vaxis_fetch_queue(h, tab, maxlev, any_fill, h->ev_caller, consumer_stream);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return vaxis_fetch_dev(lone(h), who, nplanes, planes, consumer_stream); });
 }
 
 // ---------------------------------------------------------------------------
@@ -3332,19 +3452,15 @@ int hgrid_in_build(mckpp_hip_ctx *h, int grid)
   return hgrid_build(h, d, (int64_t)rows.size(), rows.data(), h->hg[grid].in.view(), nullptr, 1);
 }
 
-// the out table for `covered` (null: this context's own columns; kind 1 / 2 as d_land's), built where it is not that
-int hgrid_out_build(mckpp_hip_ctx *h, int grid, const std::vector<unsigned char> *covered)
+// the root's out table of `grid` for the points the group holds (kind as d_land's), built where it is not that
+int group_hgrid_out(const ctx_group &g, const char *who, int grid)
 {
-  hgrid_dev &d = h->hgd[grid].out;
-  const int kind = covered ? 2 : 1;
-  if (d.kind == kind) return 0;
-  std::vector<unsigned char> own;
-  if (!covered) {
-    own.assign((size_t)h->npts, 0);
-    for (int i : h->ipt) own[(size_t)i] = 1;
-    covered = &own;
-  }
-  return hgrid_build(h, d, h->hg[grid].n, nullptr, h->hg[grid].out.view(), covered->data(), kind);
+  mckpp_hip_ctx *root = g.root();
+  hgrid_dev &d = root->hgd[grid].out;
+  if (d.kind == g.kind) return 0;
+  std::vector<unsigned char> covered;
+  if (group_columns(g, who, covered)) return -1;
+  return hgrid_build(root, d, root->hg[grid].n, nullptr, root->hg[grid].out.view(), covered.data(), g.kind);
 }
 
 // What a call of the in direction needs before it queues: the grid, its in table, the eight arrays of n doubles, and
@@ -3372,58 +3488,70 @@ int hgrid_in_check(mckpp_hip_ctx *h, const char *who, int grid, const double *co
   return 0;
 }
 
-// The planes of a delivery on caller grids: stage 1 as planes of k_fetch_planes into the staging (`out` set when it is
-// queued: at[k] doubles into the block), stage 2 as planes of k_hgrid_out (stage and table likewise).
-struct hgrid_fetch {
-  std::vector<mckpp_fetch_plane> first;
+// The out planes of a delivery on caller grids - mckpp_hip_hgrid_fetch_dev's, and those of mckpp_hip_remap_records_dev
+// (include/mckpp_hip_remap.h).  Stage 1, the call's own, writes the model's values of plane k at[k] doubles into the
+// staging block; stage 2 is these planes of k_hgrid_out (stage and table set when they are queued).
+struct hgrid_outs {
   std::vector<mckpp_hgrid_plane> second;
   std::vector<int> grid;
   std::vector<size_t> at;
+  std::vector<std::pair<const char *, const char *>> span;   // [plane] the bytes of its `out`
   size_t elems = 0;
   int maxlev = 0;
   int64_t maxn = 0;
 };
 
+// What planes[k] says of its caller grid and its array, checked and resolved: the grid and its out table, the norm, the
+// array (*dev, where asked for: its device), which overlaps no array of a plane before it.  elem: the size of an element.
+template <class P>
+int hgrid_out_resolve(mckpp_hip_ctx *h, const char *who, int k, const P &q, size_t elem, int *dev, hgrid_outs &r)
+{
+  char arg[32];
+  snprintf(arg, sizeof arg, "planes[%d]", k);
+  const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
+  if (!g) return -1;
+  if (g->out.ptr.empty())
+    return fail("%s: planes[%d]: grid %d has no out table (model -> caller): mckpp_hip_hgrid_define was given none", who, k,
+                q.grid);
+  if (q.norm != MCKPP_HGRID_NORM_NONE && q.norm != MCKPP_HGRID_NORM_USED)
+    return fail("%s: planes[%d]: norm %d (MCKPP_HGRID_NORM_NONE 0, MCKPP_HGRID_NORM_USED 1)", who, k, q.norm);
+  const size_t bytes = (size_t)g->n * (size_t)q.nlev * elem;
+  snprintf(arg, sizeof arg, "planes[%d].out", k);
+  if (dev_ptr_check(h, who, arg, q.out, bytes, dev)) return -1;
+  const char *b = static_cast<const char *>(q.out);
+  for (int j = 0; j < k; ++j)
+    if (b < r.span[(size_t)j].second && r.span[(size_t)j].first < b + bytes)
+      return fail("%s: planes[%d].out and planes[%d].out overlap: the planes of a call have no order", who, k, j);
+  r.span.emplace_back(b, b + bytes);
+  r.second.push_back(mckpp_hgrid_plane{nullptr, q.out, q.land_value, mckpp_hgrid_ell{}, h->npts, q.nlev,
+                                       q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.norm, q.fill_land ? 1 : 0});
+  r.grid.push_back(q.grid);
+  r.at.push_back(r.elems);
+  r.elems += (size_t)h->npts * (size_t)q.nlev;
+  r.maxlev = std::max(r.maxlev, (int)q.nlev);
+  r.maxn = std::max(r.maxn, g->n);
+  return 0;
+}
+
+// The planes of mckpp_hip_hgrid_fetch_dev: stage 1 as planes of k_fetch_planes (`out` set when it is queued)
+struct hgrid_fetch {
+  std::vector<mckpp_fetch_plane> first;
+  hgrid_outs o;
+};
+
 int hgrid_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_hgrid_plane_c *planes, hgrid_fetch &r, int *dev)
 {
-  if (nplanes < 0 || nplanes > MCKPP_HGRID_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_HGRID_PLANES_MAX);
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (planes_count_check(who, nplanes, planes, MCKPP_HGRID_PLANES_MAX) || uploaded_check(h, who)) return -1;
   HIPCHK(hipSetDevice(h->device));
   r = hgrid_fetch{};
-  std::vector<std::pair<const char *, const char *>> span;
   for (int k = 0; k < nplanes; ++k) {
     const mckpp_hgrid_plane_c &q = planes[k];
     out_desc d;
     if (out_field(h, q.field, d)) return -1;
     if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, d.nlev)) return -1;
     const size_t elem = plane_elem(who, k, q.dtype);
-    if (!elem) return -1;
-    char arg[32];
-    snprintf(arg, sizeof arg, "planes[%d]", k);
-    const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
-    if (!g) return -1;
-    if (g->out.ptr.empty())
-      return fail("%s: planes[%d]: grid %d has no out table (model -> caller): mckpp_hip_hgrid_define was given none", who, k,
-                  q.grid);
-    if (q.norm != MCKPP_HGRID_NORM_NONE && q.norm != MCKPP_HGRID_NORM_USED)
-      return fail("%s: planes[%d]: norm %d (MCKPP_HGRID_NORM_NONE 0, MCKPP_HGRID_NORM_USED 1)", who, k, q.norm);
-    const size_t bytes = (size_t)g->n * (size_t)q.nlev * elem;
-    snprintf(arg, sizeof arg, "planes[%d].out", k);
-    if (dev_ptr_check(h, who, arg, q.out, bytes, k == 0 ? dev : nullptr)) return -1;
-    const char *b = static_cast<const char *>(q.out);
-    for (int j = 0; j < k; ++j)
-      if (b < span[(size_t)j].second && span[(size_t)j].first < b + bytes)
-        return fail("%s: planes[%d].out and planes[%d].out overlap: the planes of a call have no order", who, k, j);
-    span.emplace_back(b, b + bytes);
+    if (!elem || hgrid_out_resolve(h, who, k, q, elem, k == 0 ? dev : nullptr, r.o)) return -1;
     r.first.push_back(mckpp_fetch_plane{d.src, nullptr, 0.0, d.ld, d.off + q.lev0, q.nlev, d.add_sref, 0, 0});
-    r.second.push_back(mckpp_hgrid_plane{nullptr, q.out, q.land_value, mckpp_hgrid_ell{}, h->npts, q.nlev,
-                                         q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.norm, q.fill_land ? 1 : 0});
-    r.grid.push_back(q.grid);
-    r.at.push_back(r.elems);
-    r.elems += (size_t)h->npts * (size_t)q.nlev;
-    r.maxlev = std::max(r.maxlev, (int)q.nlev);
-    r.maxn = std::max(r.maxn, g->n);
   }
   return 0;
 }
@@ -3443,27 +3571,67 @@ int hgrid_stage(mckpp_hip_ctx *h, size_t elems)
 int hgrid_fetch_first(mckpp_hip_ctx *h, hgrid_fetch &r, double *stage, hipEvent_t before)
 {
   HIPCHK(hipSetDevice(h->device));
-  for (size_t k = 0; k < r.first.size(); ++k) r.first[k].out = stage + r.at[k];
+  for (size_t k = 0; k < r.first.size(); ++k) r.first[k].out = stage + r.o.at[k];
   HIPCHK(h->fetch_tab.put(r.first, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
-  HIPCHK(mckpp_launch_fetch_planes(h->fetch_tab, (int)r.first.size(), r.maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs, nullptr, 0,
+  HIPCHK(mckpp_launch_fetch_planes(h->fetch_tab, (int)r.first.size(), r.o.maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs, nullptr, 0,
                                    h->stream));
   return 0;
 }
 
-// stage 2 on this context's stream, from `stage` through the out tables as they are built; the consumer waits for it
-int hgrid_fetch_second(mckpp_hip_ctx *h, hgrid_fetch &r, const double *stage, void *consumer_stream)
+// The two-stage delivery of the root's out planes `o`, whose tables are set: first(d, stage, before) queues stage 1 of
+// shard d on its stream, behind `before`, into the root's staging block; the root's stage 2 runs behind every shard's
+// stage 1, from the staging through the tables, and the consumer waits for it.  dev: the device of the call's first array.
+template <class First>
+int two_stage_deliver(const ctx_group &g, const char *who, hgrid_outs &o, int dev, void *consumer_stream, First first)
 {
-  HIPCHK(hipSetDevice(h->device));
-  for (size_t k = 0; k < r.second.size(); ++k) {
-    r.second[k].stage = stage + r.at[k];
-    r.second[k].t = hgrid_ell(h->hgd[r.grid[k]].out);
+  mckpp_hip_ctx *root = g.root();
+  if (hgrid_stage(root, o.elems)) return -1;
+  double *stage = root->d_hstage;
+  for (int d = 1; d < g.n; ++d) {   // every shard's device reaches the root's staging (peer access, once per pair)
+    HIPCHK(hipSetDevice(g.ctx[d]->device));
+    if (dev_ptr_check(g.ctx[d], who, "the staging plane of shard 0", stage, o.elems * sizeof(double))) return -1;
   }
-  HIPCHK(h->hgrid_tab.put(r.second, h->stream));
-  HIPCHK(mckpp_launch_hgrid_out(h->hgrid_tab, (int)r.second.size(), r.maxlev, r.maxn, h->stream));
-  HIPCHK(h->ev_delivered.record(h->stream));
-  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  if (caller_event(g, dev, consumer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d) {
+    mckpp_hip_ctx *x = g.ctx[d];
+    if (d > 0) {
+      HIPCHK(hipSetDevice(x->device));
+      // the staging is the root's: behind the second stage of the call before, which read it on the root's stream
+      if (root->ev_delivered) HIPCHK(hipStreamWaitEvent(x->stream, root->ev_delivered, 0));
+    }
+    if (first(d, stage, (hipEvent_t)*g.ev)) return -1;
+    if (d > 0) {   // ... and the root's second stage behind this shard's first
+      HIPCHK(x->ev_delivered.record(x->stream));
+      HIPCHK(hipSetDevice(root->device));
+      HIPCHK(hipStreamWaitEvent(root->stream, x->ev_delivered, 0));
+    }
+  }
+  HIPCHK(hipSetDevice(root->device));
+  for (size_t k = 0; k < o.second.size(); ++k) o.second[k].stage = stage + o.at[k];
+  HIPCHK(root->hgrid_tab.put(o.second, root->stream));
+  HIPCHK(mckpp_launch_hgrid_out(root->hgrid_tab, (int)o.second.size(), o.maxlev, o.maxn, root->stream));
+  HIPCHK(root->ev_delivered.record(root->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), root->ev_delivered, 0));
   return 0;
+}
+
+// mckpp_hip_hgrid_fetch_dev: every shard's first stage into the root's staging, the root's second stage over the points
+// the group holds, so the sums of a multi handle are those of one context, entry for entry
+int hgrid_fetch_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_hgrid_plane_c *planes, void *consumer_stream)
+{
+  std::vector<hgrid_fetch> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (hgrid_fetch_check(g.ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  hgrid_outs &o = rs[0].o;
+  for (int grid : o.grid)
+    if (group_hgrid_out(g, who, grid)) return -1;
+  for (size_t k = 0; k < o.second.size(); ++k) o.second[k].t = hgrid_ell(g.root()->hgd[o.grid[k]].out);
+  return two_stage_deliver(g, who, o, dev, consumer_stream, [&](int d, double *stage, hipEvent_t before) {
+    return hgrid_fetch_first(g.ctx[d], rs[(size_t)d], stage, before);
+  });
 }
 
 int hgrid_info(mckpp_hip_ctx *h, const char *who, int grid, int64_t info[6], bool keep_out_kind)
@@ -3484,7 +3652,7 @@ int hgrid_info(mckpp_hip_ctx *h, const char *who, int grid, int64_t info[6], boo
     info[3] = h->hgd[grid].in.padded;
   }
   if (!g->out.ptr.empty()) {
-    if (!(keep_out_kind && h->hgd[grid].out.kind == 2) && hgrid_out_build(h, grid, nullptr)) return -1;
+    if (!(keep_out_kind && h->hgd[grid].out.kind == 2) && group_hgrid_out(lone(h), who, grid)) return -1;
     info[4] = h->hgd[grid].out.padded;
   }
   return 0;
@@ -3506,39 +3674,18 @@ int mckpp_hip_hgrid_fluxes_dev(mckpp_hip_handle h, int grid, int ntime, const do
                                double el, void *producer_stream)
 {
   return entry(__func__, h, [&, who = __func__]() -> int {
-  mckpp_hgrid_ell t;
-  if (hgrid_in_check(h, who, grid, fields, &t, nullptr)) return -1;
-  if (h->ncol == 0) return 0;
-  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return fluxes_dev_queue(h, ntime, fields, l_rest, flsn, el, h->ev_caller, &t);
+  return fluxes_dev(lone(h), who, ntime, fields, l_rest, flsn, el, producer_stream, &grid);
   });
 }
 
 int mckpp_hip_hgrid_flux_ring_put_dev(mckpp_hip_handle h, int grid, int rec, const double *const fields[8], void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  if (!fields) return fail("%s: null argument", who);
-  if (ring_put_check(h, who, rec)) return -1;
-  mckpp_hgrid_ell t;
-  if (hgrid_in_check(h, who, grid, fields, &t, nullptr)) return -1;
-  if (h->ncol > 0 && caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return ring_put_dev_queue(h, rec, fields, h->ev_caller, &t);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return flux_ring_put_dev(lone(h), who, rec, fields, producer_stream, &grid); });
 }
 
 int mckpp_hip_hgrid_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hgrid_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  hgrid_fetch r;
-  if (hgrid_fetch_check(h, who, nplanes, planes, r, nullptr)) return -1;
-  if (r.first.empty()) return 0;
-  for (int g : r.grid)
-    if (hgrid_out_build(h, g, nullptr)) return -1;   // (a shard addressed on its own: its own columns again)
-  if (hgrid_stage(h, r.elems)) return -1;
-  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
-  if (hgrid_fetch_first(h, r, h->d_hstage, h->ev_caller)) return -1;
-  return hgrid_fetch_second(h, r, h->d_hstage, consumer_stream);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return hgrid_fetch_dev(lone(h), who, nplanes, planes, consumer_stream); });
 }
 
 // ---------------------------------------------------------------------------
@@ -3737,7 +3884,6 @@ static int win_set(mckpp_hip_ctx *h, const char *who, int sched, int nt_origin, 
     }
     w.nnorow = (int64_t)norow.size();
     w.rowpos = std::move(rowpos);
-    w.norow = std::move(norow);
     for (int i = 0; i < nfields && e == hipSuccess; ++i) {
       out_desc d;
       out_field(h, fields[i], d);
@@ -3943,32 +4089,48 @@ struct rec_planes {
   int maxlev = 0;
 };
 
+// planes[k] of a call that names a plane of a completed record (schedule, record, field, operation, levels): may it be
+// fetched, are its levels among those the schedule keeps?  Resolved into what the kernels' entries of such a plane
+// share, mckpp_rec_plane's and mckpp_red_plane's; *fi: the field's index in the schedule.  The schedule, or null and the
+// refusal.
+template <class P, class E>
+const mckpp_hip_ctx::win_sched *record_plane(mckpp_hip_ctx *h, const char *who, int k, const P &q, E &e, size_t *fi = nullptr)
+{
+  char at[96];
+  snprintf(at, sizeof at, "%s: planes[%d]", who, k);
+  size_t i = 0;
+  if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return nullptr;
+  const auto &w = h->wsched[q.sched];
+  if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return nullptr;
+  e.src = win_plane_rows(w, i, q.rec, q.op);
+  e.period = (double)w.period;
+  e.nrow = w.nrow;
+  e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
+  e.mean = q.op == 0;
+  if (fi) *fi = i;
+  return &w;
+}
+
 int records_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_dev_record_plane_c *planes, rec_planes &r,
                       int *dev)
 {
-  if (nplanes < 0 || nplanes > MCKPP_DEV_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_DEV_PLANES_MAX);
+  if (planes_count_check(who, nplanes, planes, MCKPP_DEV_PLANES_MAX)) return -1;
   HIPCHK(hipSetDevice(h->device));
   r = rec_planes{};
   for (int k = 0; k < nplanes; ++k) {
     const mckpp_dev_record_plane_c &q = planes[k];
-    char at[96], arg[32];
-    snprintf(at, sizeof at, "%s: planes[%d]", who, k);
-    snprintf(arg, sizeof arg, "planes[%d].out", k);
-    size_t i = 0;
-    if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
-    const auto &w = h->wsched[q.sched];
-    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
-    const size_t elem = plane_elem(who, k, q.dtype);
-    if (!elem || dev_ptr_check(h, who, arg, q.out, (size_t)w.npoints * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
     mckpp_rec_plane e{};
-    e.src = win_plane_rows(w, i, q.rec, q.op);
+    const auto *w = record_plane(h, who, k, q, e);
+    if (!w) return -1;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem || dev_ptr_check(h, who, arg, q.out, (size_t)w->npoints * (size_t)q.nlev * elem, k == 0 ? dev : nullptr)) return -1;
     e.out = q.out;
-    e.map = win_map(h, w);
-    e.period = (double)w.period; e.land_value = q.land_value;
-    e.nrow = w.nrow; e.npoints = w.npoints;
-    e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
-    e.mean = q.op == 0; e.f32 = q.dtype == MCKPP_EXP_F32; e.fill = q.fill_land != 0;
+    e.map = win_map(h, *w);
+    e.land_value = q.land_value;
+    e.npoints = w->npoints;
+    e.f32 = q.dtype == MCKPP_EXP_F32; e.fill = q.fill_land != 0;
     r.tab.push_back(e);
     r.sched.push_back(q.sched);
     r.maxlev = std::max(r.maxlev, (int)q.nlev);
@@ -3976,18 +4138,22 @@ int records_dev_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const 
   return 0;
 }
 
-// the non-row list a listed schedule's planes fill (win_sched::d_norow): as land_set
-int win_norow_set(mckpp_hip_ctx *h, mckpp_hip_ctx::win_sched &w, const std::vector<int> &list, int kind)
+// the root's list of the positions of schedule `sched`'s point axis that the group has no row for - the grid's land
+// list, or the point list's own (win_sched::d_norow) -, where it is not that already
+int group_norow(const ctx_group &g, const char *who, int sched)
 {
-  HIPCHK(hipStreamSynchronize(h->stream));   // (a change of who addresses the shard: a delivery in flight may read the old list)
-  HIPCHK(w.d_norow.reserve(std::max<size_t>(list.size(), 1)));
-  if (!list.empty()) HIPCHK(hipMemcpy(w.d_norow, list.data(), list.size() * sizeof(int), hipMemcpyHostToDevice));
-  w.nnorow = (int64_t)list.size();
-  w.norow_kind = kind;
-  return 0;
+  mckpp_hip_ctx *root = g.root();
+  auto &w = root->wsched[sched];
+  if (!w.listed) return group_land(g, who);
+  if (w.norow_kind == g.kind) return 0;
+  std::vector<unsigned char> held((size_t)w.npoints, 0);
+  for (auto *x : g)
+    for (int p : x->wsched[sched].rowpos) held[(size_t)p] = 1;
+  return fill_list_set(root, w.d_norow, w.nnorow, w.norow_kind, held, g.kind);
 }
 
-// fill: this context writes the land values the planes ask for (a shard other than 0 of a multi handle writes none)
+// fill: this context writes the land values the planes ask for (the root does, from the lists group_norow has brought up
+// to date; another shard of a multi handle writes none)
 int records_dev_queue(mckpp_hip_ctx *h, rec_planes &r, bool fill, hipEvent_t before, void *consumer_stream)
 {
   if (r.tab.empty()) return 0;
@@ -3998,10 +4164,7 @@ int records_dev_queue(mckpp_hip_ctx *h, rec_planes &r, bool fill, hipEvent_t bef
     const auto &w = h->wsched[r.sched[k]];
     e.fill = e.fill && fill;
     if (e.fill && w.listed) { e.norow = w.d_norow; e.nnorow = w.nnorow; }
-    else if (e.fill) {
-      if (land_own(h)) return -1;
-      e.norow = h->d_land; e.nnorow = h->nland;
-    }
+    else if (e.fill) { e.norow = h->d_land; e.nnorow = h->nland; }
     xtiles = std::max<int64_t>(xtiles, (e.nrow + 63) / 64 + (e.nnorow + 63) / 64);
   }
   HIPCHK(h->rec_tab.put(r.tab, h->stream));
@@ -4011,23 +4174,30 @@ int records_dev_queue(mckpp_hip_ctx *h, rec_planes &r, bool fill, hipEvent_t bef
   HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
   return 0;
 }
+
+// mckpp_hip_records_dev: a shard writes its own rows of every plane, the root the land values - at the grid points, or
+// the positions of a schedule's point list, that the group has no row for
+int records_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_dev_record_plane_c *planes, void *consumer_stream)
+{
+  std::vector<rec_planes> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (records_dev_check(g.ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  const rec_planes &r0 = rs[0];
+  for (size_t k = 0; k < r0.tab.size(); ++k)
+    if (r0.tab[k].fill && group_norow(g, who, r0.sched[k])) return -1;
+  if (caller_event(g, dev, consumer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (records_dev_queue(g.ctx[d], rs[(size_t)d], d == 0, *g.ev, consumer_stream)) return -1;
+  return 0;
+}
 }  // namespace
 }  // extern "C++"
 
 int mckpp_hip_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_record_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  rec_planes r;
-  if (records_dev_check(h, who, nplanes, planes, r, nullptr)) return -1;
-  if (r.tab.empty()) return 0;
-  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complements again)
-  for (int s : r.sched) {
-    auto &w = h->wsched[s];
-    if (w.norow_kind == 2 && win_norow_set(h, w, w.norow, 1)) return -1;
-  }
-  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
-  return records_dev_queue(h, r, true, h->ev_caller, consumer_stream);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return records_dev(lone(h), who, nplanes, planes, consumer_stream); });
 }
 
 // ---------------------------------------------------------------------------
@@ -4039,95 +4209,55 @@ int mckpp_hip_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_r
 // ---------------------------------------------------------------------------
 extern "C++" {
 namespace {
-// The planes of a record delivery on caller grids: stage 1 as planes of k_record_planes (`out` set when it is queued:
-// at[k] doubles into the staging block), stage 2 as planes of k_hgrid_out (stage and table likewise).
+// The planes of mckpp_hip_remap_records_dev: stage 1 as planes of k_record_planes (`out` set when it is queued), [plane]
+// its schedule
 struct remap_recs {
   std::vector<mckpp_rec_plane> first;
-  std::vector<mckpp_hgrid_plane> second;
-  std::vector<int> sched, grid;
-  std::vector<size_t> at;
-  size_t elems = 0;
-  int maxlev = 0;
-  int64_t maxn = 0;
+  std::vector<int> sched;
+  hgrid_outs o;
 };
 
 int remap_records_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_remap_record_plane_c *planes, remap_recs &r,
                         int *dev)
 {
-  if (nplanes < 0 || nplanes > MCKPP_REMAP_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_REMAP_PLANES_MAX);
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
+  if (planes_count_check(who, nplanes, planes, MCKPP_REMAP_PLANES_MAX) || uploaded_check(h, who)) return -1;
   HIPCHK(hipSetDevice(h->device));
   r = remap_recs{};
-  std::vector<std::pair<const char *, const char *>> span;
   for (int k = 0; k < nplanes; ++k) {
     const mckpp_remap_record_plane_c &q = planes[k];
-    char at[96], arg[32];
-    snprintf(at, sizeof at, "%s: planes[%d]", who, k);
-    size_t i = 0;
-    if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
-    const auto &w = h->wsched[q.sched];
-    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
-    const size_t elem = plane_elem(who, k, q.dtype);
-    if (!elem) return -1;
-    snprintf(arg, sizeof arg, "planes[%d]", k);
-    const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
-    if (!g) return -1;
-    if (g->out.ptr.empty())
-      return fail("%s: planes[%d]: grid %d has no out table (model -> caller): mckpp_hip_hgrid_define was given none", who, k,
-                  q.grid);
-    if (q.norm != MCKPP_HGRID_NORM_NONE && q.norm != MCKPP_HGRID_NORM_USED)
-      return fail("%s: planes[%d]: norm %d (MCKPP_HGRID_NORM_NONE 0, MCKPP_HGRID_NORM_USED 1)", who, k, q.norm);
-    const size_t bytes = (size_t)g->n * (size_t)q.nlev * elem;
-    snprintf(arg, sizeof arg, "planes[%d].out", k);
-    if (dev_ptr_check(h, who, arg, q.out, bytes, k == 0 ? dev : nullptr)) return -1;
-    const char *b = static_cast<const char *>(q.out);
-    for (int j = 0; j < k; ++j)
-      if (b < span[(size_t)j].second && span[(size_t)j].first < b + bytes)
-        return fail("%s: planes[%d].out and planes[%d].out overlap: the planes of a call have no order", who, k, j);
-    span.emplace_back(b, b + bytes);
     mckpp_rec_plane e{};   // into the staging by point number; what is no row is never written and never read
-    e.src = win_plane_rows(w, i, q.rec, q.op);
-    e.map = w.listed ? w.d_rowpt.get() : h->d_ipt.get();
-    e.period = (double)w.period;
-    e.nrow = w.nrow; e.npoints = h->npts;
-    e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
-    e.mean = q.op == 0;
+    const auto *w = record_plane(h, who, k, q, e);
+    if (!w) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem || hgrid_out_resolve(h, who, k, q, elem, k == 0 ? dev : nullptr, r.o)) return -1;
+    e.map = w->listed ? w->d_rowpt.get() : h->d_ipt.get();
+    e.npoints = h->npts;
     r.first.push_back(e);
-    r.second.push_back(mckpp_hgrid_plane{nullptr, q.out, q.land_value, mckpp_hgrid_ell{}, h->npts, q.nlev,
-                                         q.dtype == MCKPP_EXP_F32 ? 1 : 0, q.norm, q.fill_land ? 1 : 0});
     r.sched.push_back(q.sched);
-    r.grid.push_back(q.grid);
-    r.at.push_back(r.elems);
-    r.elems += (size_t)h->npts * (size_t)q.nlev;
-    r.maxlev = std::max(r.maxlev, (int)q.nlev);
-    r.maxn = std::max(r.maxn, g->n);
   }
   return 0;
 }
 
-// the out table of a listed schedule on a grid for `covered` (null: this context's own rows; kind 1 / 2 as
-// hgrid_out_build's), built where it is not that
-int remap_out_build(mckpp_hip_ctx *h, int sched, int grid, const std::vector<unsigned char> *covered)
-{
-  auto &w = h->wsched[sched];
-  hgrid_dev &d = w.hout[grid];
-  const int kind = covered ? 2 : 1;
-  if (d.kind == kind) return 0;
-  std::vector<unsigned char> own;
-  if (!covered) {
-    own.assign((size_t)h->npts, 0);
-    for (int p : w.rowpt) own[(size_t)p] = 1;
-    covered = &own;
-  }
-  return hgrid_build(h, d, h->hg[grid].n, nullptr, h->hg[grid].out.view(), covered->data(), kind);
-}
-
-// the table stage 2 reads for plane k
-const hgrid_dev &remap_out_table(mckpp_hip_ctx *h, const remap_recs &r, size_t k)
+// the table stage 2 reads for plane k: a listed schedule's own on the grid, else the grid's
+hgrid_dev &remap_out_table(mckpp_hip_ctx *h, const remap_recs &r, size_t k)
 {
   auto &w = h->wsched[r.sched[k]];
-  return w.listed ? w.hout[r.grid[k]] : h->hgd[r.grid[k]].out;
+  return w.listed ? w.hout[r.o.grid[k]] : h->hgd[r.o.grid[k]].out;
+}
+
+// the root's out table for plane k of a delivery, for the rows the group holds of the plane's schedule (kind as
+// group_hgrid_out's), built where it is not that
+int group_remap_out(const ctx_group &g, const char *who, const remap_recs &r, size_t k)
+{
+  mckpp_hip_ctx *root = g.root();
+  const int sched = r.sched[k], grid = r.o.grid[k];
+  if (!root->wsched[sched].listed) return group_hgrid_out(g, who, grid);
+  hgrid_dev &d = remap_out_table(root, r, k);
+  if (d.kind == g.kind) return 0;
+  std::vector<unsigned char> covered((size_t)root->npts, 0);
+  for (auto *x : g)
+    for (int p : x->wsched[sched].rowpt) covered[(size_t)p] = 1;
+  return hgrid_build(root, d, root->hg[grid].n, nullptr, root->hg[grid].out.view(), covered.data(), g.kind);
 }
 
 // stage 1 on this context's stream, behind `before`: its rows' values into `stage`
@@ -4136,28 +4266,32 @@ int remap_records_first(mckpp_hip_ctx *h, remap_recs &r, double *stage, hipEvent
   HIPCHK(hipSetDevice(h->device));
   int64_t xtiles = 0;
   for (size_t k = 0; k < r.first.size(); ++k) {
-    r.first[k].out = stage + r.at[k];
+    r.first[k].out = stage + r.o.at[k];
     xtiles = std::max<int64_t>(xtiles, (r.first[k].nrow + 63) / 64);
   }
   HIPCHK(h->rec_tab.put(r.first, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
-  HIPCHK(mckpp_launch_record_planes(h->rec_tab, (int)r.first.size(), r.maxlev, xtiles, h->stream));
+  HIPCHK(mckpp_launch_record_planes(h->rec_tab, (int)r.first.size(), r.o.maxlev, xtiles, h->stream));
   return 0;
 }
 
-// stage 2 on this context's stream, from `stage` through the tables as they are built; the consumer waits for it
-int remap_records_second(mckpp_hip_ctx *h, remap_recs &r, const double *stage, void *consumer_stream)
+// mckpp_hip_remap_records_dev: hgrid_fetch_dev's order - every shard's rows into the root's staging, the root's second
+// stage behind them, through tables whose used entries are the rows of any shard
+int remap_records_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_remap_record_plane_c *planes,
+                      void *consumer_stream)
 {
-  HIPCHK(hipSetDevice(h->device));
-  for (size_t k = 0; k < r.second.size(); ++k) {
-    r.second[k].stage = stage + r.at[k];
-    r.second[k].t = hgrid_ell(remap_out_table(h, r, k));
-  }
-  HIPCHK(h->hgrid_tab.put(r.second, h->stream));
-  HIPCHK(mckpp_launch_hgrid_out(h->hgrid_tab, (int)r.second.size(), r.maxlev, r.maxn, h->stream));
-  HIPCHK(h->ev_delivered.record(h->stream));
-  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
-  return 0;
+  std::vector<remap_recs> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (remap_records_check(g.ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  remap_recs &r0 = rs[0];
+  for (size_t k = 0; k < r0.first.size(); ++k)
+    if (group_remap_out(g, who, r0, k)) return -1;
+  for (size_t k = 0; k < r0.first.size(); ++k) r0.o.second[k].t = hgrid_ell(remap_out_table(g.root(), r0, k));
+  return two_stage_deliver(g, who, r0.o, dev, consumer_stream, [&](int d, double *stage, hipEvent_t before) {
+    return remap_records_first(g.ctx[d], rs[(size_t)d], stage, before);
+  });
 }
 
 struct remap_puts {
@@ -4169,9 +4303,7 @@ struct remap_puts {
 // is queued): put_resolve's checks and put_check's overlap rule, then the grid and its in table.
 int remap_put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_remap_put_plane_c *planes, remap_puts &r, int *dev)
 {
-  if (h->npts <= 0) return fail("%s: upload the state first", who);
-  if (nplanes < 0 || nplanes > MCKPP_REMAP_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_REMAP_PLANES_MAX);
+  if (uploaded_check(h, who) || planes_count_check(who, nplanes, planes, MCKPP_REMAP_PLANES_MAX)) return -1;
   HIPCHK(hipSetDevice(h->device));
   r = remap_puts{};
   int prof[MCKPP_REMAP_PLANES_MAX];
@@ -4181,12 +4313,7 @@ int remap_put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mc
     int row;
     size_t elem;
     if (put_resolve(h, who, k, q.field, q.lev0, q.nlev, q.dtype, q.op, q.flags, q.skip_value, e.put, &row, &elem)) return -1;
-    for (int j = 0; j < k; ++j)
-      if (prof[j] == row && q.lev0 < planes[j].lev0 + planes[j].nlev && planes[j].lev0 < q.lev0 + q.nlev)
-        return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d) at overlapping levels %d..%d and %d..%d: the "
-                    "planes of a call have no order", who, k, j, q.field, planes[j].field, q.lev0, q.lev0 + q.nlev - 1,
-                    planes[j].lev0, planes[j].lev0 + planes[j].nlev - 1);
-    prof[k] = row;
+    if (put_overlap_check(who, k, planes, prof, row)) return -1;
     char arg[32];
     snprintf(arg, sizeof arg, "planes[%d]", k);
     const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
@@ -4219,35 +4346,31 @@ int remap_put_queue(mckpp_hip_ctx *h, const remap_puts &r, hipEvent_t produced)
   HIPCHK(h->ev_read.record(h->stream));
   return 0;
 }
+
+// mckpp_hip_remap_put_dev: put_planes' order, every shard through its own in table
+int remap_put_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_remap_put_plane_c *planes, void *producer_stream)
+{
+  std::vector<remap_puts> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (remap_put_check(g.ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (caller_event(g, dev, producer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (remap_put_queue(g.ctx[d], rs[(size_t)d], *g.ev)) return -1;
+  return 0;
+}
 }  // namespace
 }  // extern "C++"
 
 int mckpp_hip_remap_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_remap_record_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  remap_recs r;
-  if (remap_records_check(h, who, nplanes, planes, r, nullptr)) return -1;
-  if (r.first.empty()) return 0;
-  for (size_t k = 0; k < r.first.size(); ++k) {   // (a shard addressed on its own: its own rows again)
-    if (h->wsched[r.sched[k]].listed ? remap_out_build(h, r.sched[k], r.grid[k], nullptr) : hgrid_out_build(h, r.grid[k], nullptr))
-      return -1;
-  }
-  if (hgrid_stage(h, r.elems)) return -1;
-  if (caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
-  if (remap_records_first(h, r, h->d_hstage, h->ev_caller)) return -1;
-  return remap_records_second(h, r, h->d_hstage, consumer_stream);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return remap_records_dev(lone(h), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_remap_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_remap_put_plane_c *planes, void *producer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int {
-  remap_puts r;
-  if (remap_put_check(h, who, nplanes, planes, r, nullptr)) return -1;
-  if (r.tab.empty() || h->ncol == 0) return 0;
-  if (caller_event(h->ev_caller, h->device, producer_stream)) return -1;
-  return remap_put_queue(h, r, h->ev_caller);
-  });
+  return entry(__func__, h, [&, who = __func__]() -> int { return remap_put_dev(lone(h), who, nplanes, planes, producer_stream); });
 }
 
 // ---------------------------------------------------------------------------
@@ -4317,8 +4440,7 @@ const char *const red_op_names = "0 none, 1 sum, 2 average, 3 min, 4 max";
 int reduce_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
                  red_planes &r, int *dev)
 {
-  if (nplanes < 0 || nplanes > MCKPP_DEV_PLANES_MAX || (nplanes > 0 && !planes))
-    return fail("%s: nplanes=%d (0..%d) or a null table", who, nplanes, MCKPP_DEV_PLANES_MAX);
+  if (planes_count_check(who, nplanes, planes, MCKPP_DEV_PLANES_MAX)) return -1;
   HIPCHK(hipSetDevice(h->device));
   r = red_planes{};
   const auto &s = h->red;
@@ -4328,9 +4450,10 @@ int reduce_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp
     snprintf(at, sizeof at, "%s: planes[%d]", who, k);
     snprintf(arg, sizeof arg, "planes[%d].out", k);
     size_t i = 0;
-    if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return -1;
-    const auto &w = h->wsched[q.sched];
-    if (plane_levels_check(who, k, q.lev0, q.nlev, q.field, w.nlev[i], q.sched)) return -1;
+    mckpp_red_plane e{};
+    const auto *sched = record_plane(h, who, k, q, e, &i);
+    if (!sched) return -1;
+    const auto &w = *sched;
     if (q.axis_op < 0 || q.axis_op > 4) return fail("%s: axis_op %d (%s)", at, q.axis_op, red_op_names);
     if (q.domain_op < 0 || q.domain_op > 4) return fail("%s: domain_op %d (%s)", at, q.domain_op, red_op_names);
     if (q.axis_op == 0 && q.domain_op == 0)
@@ -4368,18 +4491,14 @@ int reduce_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp
     const size_t nout = q.domain_op == 0 ? (size_t)w.npoints : q.axis_op == 0 ? (size_t)q.nlev : 1;
     if (!dev_form && !q.out) return fail("%s: %s is null", who, arg);
     if (dev_form && dev_ptr_check(h, who, arg, q.out, nout * sizeof(double), k == 0 ? dev : nullptr)) return -1;
-    mckpp_red_plane e{};
-    e.src = win_plane_rows(w, i, q.rec, q.op);
     e.out = static_cast<double *>(q.out);
     e.map = win_map(h, w);
     e.point = w.listed ? w.d_rowpt.get() : h->d_ipt.get();
     e.wl = wl; e.wp = wp;
-    e.period = (double)w.period; e.land_value = q.land_value; e.wsum = wsum;
-    e.nrow = w.nrow;
+    e.land_value = q.land_value; e.wsum = wsum;
     e.n2 = 1;
     while (e.n2 < w.npoints) e.n2 *= 2;
-    e.ld = w.ld_out[i]; e.off = q.lev0; e.nlev = q.nlev;
-    e.mean = q.op == 0; e.axis_op = q.axis_op; e.domain_op = q.domain_op;
+    e.axis_op = q.axis_op; e.domain_op = q.domain_op;
     e.nslab = q.domain_op == 0 ? 0 : (q.axis_op == 0 ? q.nlev : 1) + (q.domain_op == MCKPP_RED_AVERAGE ? 1 : 0);
     r.tab.push_back(e);
     r.sched.push_back(q.sched);
@@ -4413,7 +4532,8 @@ int reduce_reserve(mckpp_hip_ctx *owner, const red_planes &r, bool dev_form)
   return 0;
 }
 
-// the table's blocks and lists: fill - this context writes what no row does; rows[k]: the rows all shards hold of plane k
+// the table's blocks and lists: fill - this context writes what no row does (the root, from the lists group_norow has
+// brought up to date); rows[k]: the rows all shards hold of plane k
 int reduce_bind(mckpp_hip_ctx *h, mckpp_hip_ctx *owner, red_planes &r, bool dev_form, bool fill, const std::vector<int64_t> &rows)
 {
   for (size_t k = 0; k < r.tab.size(); ++k) {
@@ -4425,10 +4545,7 @@ int reduce_bind(mckpp_hip_ctx *h, mckpp_hip_ctx *owner, red_planes &r, bool dev_
     e.norows = rows[k] == 0;
     if (fill && e.domain_op == 0) {
       if (w.listed) { e.norow = w.d_norow; e.nnorow = w.nnorow; }
-      else {
-        if (land_own(h)) return -1;
-        e.norow = h->d_land; e.nnorow = h->nland;
-      }
+      else { e.norow = h->d_land; e.nnorow = h->nland; }
     }
   }
   return 0;
@@ -4450,31 +4567,60 @@ int reduce_host_deliver(mckpp_hip_ctx *owner, const red_planes &r)
   return 0;
 }
 
-int reduce_single(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
-                  void *consumer_stream)
+// mckpp_hip_records_reduce_dev / _host.  Per-shard sums combined afterwards would not be the single context's bits, so the
+// shards deliver terms and the root reduces: the root fills its slabs (and the land values of the axis-only planes),
+// every shard then writes the terms - or, axis only, the results - of its own rows, and behind all of them the root runs
+// the tree and delivers.
+int records_reduce(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
+                   void *consumer_stream)
 {
-  red_planes r;
-  if (reduce_check(h, who, nplanes, planes, dev_form, r, nullptr)) return -1;
-  if (r.tab.empty()) return 0;
-  if (h->land_kind == 2) h->land_kind = 0;   // (a shard addressed on its own: its own complements again)
-  for (int s : r.sched) {
-    auto &w = h->wsched[s];
-    if (w.norow_kind == 2 && win_norow_set(h, w, w.norow, 1)) return -1;
+  mckpp_hip_ctx *root = g.root();
+  std::vector<red_planes> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (reduce_check(g.ctx[d], who, nplanes, planes, dev_form, rs[(size_t)d], &dev)) return -1;
+  red_planes &r0 = rs[0];
+  if (r0.tab.empty()) return 0;
+  std::vector<int64_t> rows(r0.tab.size(), 0);
+  for (size_t k = 0; k < r0.tab.size(); ++k) {
+    for (int d = 0; d < g.n; ++d) rows[k] += rs[(size_t)d].tab[k].nrow;
+    // axis only: the root writes the land value where the group has no row
+    if (r0.tab[k].domain_op == 0 && group_norow(g, who, r0.sched[k])) return -1;
   }
-  if (reduce_reserve(h, r, dev_form)) return -1;
-  std::vector<int64_t> rows;
-  for (const auto &e : r.tab) rows.push_back(e.nrow);
-  if (reduce_bind(h, h, r, dev_form, true, rows)) return -1;
-  if (dev_form && caller_event(h->ev_caller, h->device, consumer_stream)) return -1;
-  HIPCHK(hipSetDevice(h->device));
-  HIPCHK(h->red_tab.put(r.tab, h->stream));
-  if (dev_form) HIPCHK(hipStreamWaitEvent(h->stream, h->ev_caller, 0));   // what the consumer had queued on the arrays
-  if (reduce_launch(h, r, MCKPP_RED_PHASE_FILL) || reduce_launch(h, r, MCKPP_RED_PHASE_TERMS)) return -1;
-  if (r.halve && reduce_launch(h, r, MCKPP_RED_PHASE_HALVE)) return -1;
-  if (r.domain && reduce_launch(h, r, MCKPP_RED_PHASE_FINISH)) return -1;
-  if (!dev_form) return reduce_host_deliver(h, r);
-  HIPCHK(h->ev_delivered.record(h->stream));
-  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), h->ev_delivered, 0));
+  if (reduce_reserve(root, r0, dev_form)) return -1;
+  for (int d = 1; d < g.n; ++d) {   // the other shards write into the root's blocks
+    HIPCHK(hipSetDevice(g.ctx[d]->device));
+    if (r0.terms > 0 && dev_ptr_check(g.ctx[d], who, "shard 0's block of terms", root->red.d_terms, r0.terms * sizeof(double)))
+      return -1;
+    if (!dev_form && dev_ptr_check(g.ctx[d], who, "shard 0's block of results", root->red.d_out, r0.outs * sizeof(double)))
+      return -1;
+  }
+  for (int d = 0; d < g.n; ++d)
+    if (reduce_bind(g.ctx[d], root, rs[(size_t)d], dev_form, d == 0, rows)) return -1;
+  if (dev_form && caller_event(g, dev, consumer_stream)) return -1;
+  HIPCHK(hipSetDevice(root->device));
+  HIPCHK(root->red_tab.put(r0.tab, root->stream));
+  if (dev_form) HIPCHK(hipStreamWaitEvent(root->stream, *g.ev, 0));   // what the consumer had queued on the arrays
+  if (reduce_launch(root, r0, MCKPP_RED_PHASE_FILL)) return -1;
+  if (g.n > 1) {   // the other shards' terms behind the root's fill
+    HIPCHK(root->red.ev_fill.record(root->stream));
+    for (int d = 1; d < g.n; ++d) {
+      mckpp_hip_ctx *x = g.ctx[d];
+      HIPCHK(hipSetDevice(x->device));
+      HIPCHK(x->red_tab.put(rs[(size_t)d].tab, x->stream));
+      HIPCHK(hipStreamWaitEvent(x->stream, root->red.ev_fill, 0));
+      if (reduce_launch(x, rs[(size_t)d], MCKPP_RED_PHASE_TERMS)) return -1;
+      HIPCHK(x->red.ev_terms.record(x->stream));
+    }
+    HIPCHK(hipSetDevice(root->device));
+  }
+  if (reduce_launch(root, r0, MCKPP_RED_PHASE_TERMS)) return -1;
+  for (int d = 1; d < g.n; ++d) HIPCHK(hipStreamWaitEvent(root->stream, g.ctx[d]->red.ev_terms, 0));
+  if (r0.halve && reduce_launch(root, r0, MCKPP_RED_PHASE_HALVE)) return -1;
+  if (r0.domain && reduce_launch(root, r0, MCKPP_RED_PHASE_FINISH)) return -1;
+  if (!dev_form) return reduce_host_deliver(root, r0);
+  HIPCHK(root->ev_delivered.record(root->stream));
+  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), root->ev_delivered, 0));
   return 0;
 }
 }  // namespace
@@ -4487,12 +4633,12 @@ int mckpp_hip_reduce_weights(mckpp_hip_handle h, const double *point_w, const do
 
 int mckpp_hip_records_reduce_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_reduce_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int { return reduce_single(h, who, nplanes, planes, true, consumer_stream); });
+  return entry(__func__, h, [&, who = __func__]() -> int { return records_reduce(lone(h), who, nplanes, planes, true, consumer_stream); });
 }
 
 int mckpp_hip_records_reduce_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_reduce_plane_c *planes)
 {
-  return entry(__func__, h, [&, who = __func__]() -> int { return reduce_single(h, who, nplanes, planes, false, nullptr); });
+  return entry(__func__, h, [&, who = __func__]() -> int { return records_reduce(lone(h), who, nplanes, planes, false, nullptr); });
 }
 
 // the tree of include/mckpp_hip_reduce.h, c, as it is written there
@@ -5571,171 +5717,35 @@ int mckpp_hip_multi_step_log_clear(mckpp_hip_multi_handle m)
   return multi_each(__func__, m, [&](auto *x) { return mckpp_hip_step_log_clear(x); });
 }
 
-// the caller's arrays pinned on behalf of this handle go back to pageable memory (before the caller frees them)
-// ---- the device-array interface (mckpp_hip_device.h) over all shards: every shard is checked before any of them
-// queues, and one event on the caller's stream - created on the device of the caller's arrays - orders them all
-static int multi_caller_event(mckpp_hip_multi *m, int dev, void *stream)
-{
-  if (m->ev_caller_dev != dev) { m->ev_caller.reset(); m->ev_caller_dev = dev; }
-  return caller_event(m->ev_caller, dev, stream);
-}
+// ---- the device-array interface and what follows it (mckpp_hip_device.h, _device_records.h, _reduce.h, _put.h, _vaxis.h,
+// _hgrid.h, _remap.h) over all shards: each call is its one body, given the shards as its group.  The event on the
+// caller's stream is the handle's, on the device of the caller's arrays.
+extern "C++" {
+namespace {
+ctx_group shards(mckpp_hip_multi *m) { return ctx_group{m->ctx.data(), (int)m->ctx.size(), 2, &m->ev_caller, &m->ev_caller_dev}; }
+}  // namespace
+}  // extern "C++"
 
 int mckpp_hip_multi_fluxes_dev(mckpp_hip_multi_handle m, int ntime, const double *const fields[8], int l_rest, double flsn,
                                double el, void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  int dev = -1;
-  for (auto *x : m->ctx)
-    if (dev_fields_check(x, who, fields, &dev)) return -1;
-  if (dev < 0) return 0;
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (auto *x : m->ctx)
-    if (fluxes_dev_queue(x, ntime, fields, l_rest, flsn, el, m->ev_caller)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return fluxes_dev(shards(m), who, ntime, fields, l_rest, flsn, el, producer_stream); });
 }
 
 int mckpp_hip_multi_flux_ring_put_dev(mckpp_hip_multi_handle m, int rec, const double *const fields[8], void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  if (!fields) return fail("%s: null argument", who);
-  int dev = -1;
-  for (auto *x : m->ctx)
-    if (ring_put_check(x, who, rec) || dev_fields_check(x, who, fields, &dev)) return -1;
-  if (dev < 0) return 0;
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (auto *x : m->ctx)
-    if (ring_put_dev_queue(x, rec, fields, m->ev_caller)) return -1;
-  return 0;
-  });
-}
-
-// shard 0's land list as the points that no shard holds (land_kind 2), where it is not that already
-static int multi_land(mckpp_hip_multi *m, const char *who)
-{
-  if (m->ctx[0]->land_kind == 2) return 0;
-  std::vector<int64_t> ncol;
-  std::vector<const int32_t *> points;
-  for (auto *x : m->ctx) { ncol.push_back(x->ncol); points.push_back(x->ipt.data()); }
-  std::vector<unsigned char> covered;
-  if (export_covered(m->npts, (int)m->ctx.size(), ncol.data(), points.data(), covered))
-    return fail("%s: a column map names a point outside the grid", who);
-  HIPCHK(hipSetDevice(m->ctx[0]->device));
-  return land_set(m->ctx[0], points_not(covered), 2);
+  return entry(__func__, m, [&, who = __func__]() -> int { return flux_ring_put_dev(shards(m), who, rec, fields, producer_stream); });
 }
 
 int mckpp_hip_multi_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<std::vector<mckpp_fetch_plane>> tabs((size_t)ndev);
-  int maxlev = 0, dev = -1;
-  bool any_fill = false;
-  for (int d = 0; d < ndev; ++d)
-    if (fetch_dev_check(m->ctx[d], who, nplanes, planes, tabs[(size_t)d], &maxlev, &any_fill, &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  if (any_fill) {   // shard 0 fills the points that no shard holds, the others fill none: every point is written once
-    for (int d = 1; d < ndev; ++d)
-      for (auto &e : tabs[(size_t)d]) e.fill_land = 0;
-    if (multi_land(m, who)) return -1;
-  }
-  if (multi_caller_event(m, dev, consumer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (fetch_dev_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return fetch_dev(shards(m), who, nplanes, planes, consumer_stream); });
 }
 
-// shard 0's list of the positions of schedule `sched`'s point axis that no shard has a row for - the grid's land list, or
-// the point list's own -, where it is not that already
-static int multi_norow(mckpp_hip_multi *m, const char *who, int sched)
-{
-  auto &w = m->ctx[0]->wsched[sched];
-  if (!w.listed) return multi_land(m, who);
-  if (w.norow_kind == 2) return 0;
-  std::vector<unsigned char> held((size_t)w.npoints, 0);
-  for (auto *x : m->ctx)
-    for (int p : x->wsched[sched].rowpos) held[(size_t)p] = 1;
-  HIPCHK(hipSetDevice(m->ctx[0]->device));
-  return win_norow_set(m->ctx[0], w, points_not(held), 2);
-}
-
-// mckpp_hip_records_dev over all shards: a shard writes its own rows of every plane, shard 0 the land values - at the
-// grid points, or the positions of a schedule's point list, that no shard has a row for
 int mckpp_hip_multi_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_dev_record_plane_c *planes,
                                 void *consumer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<rec_planes> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (records_dev_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  const rec_planes &r0 = rs[0];
-  for (size_t k = 0; k < r0.tab.size(); ++k)
-    if (r0.tab[k].fill && multi_norow(m, who, r0.sched[k])) return -1;
-  if (multi_caller_event(m, dev, consumer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (records_dev_queue(m->ctx[d], rs[(size_t)d], d == 0, m->ev_caller, consumer_stream)) return -1;
-  return 0;
-  });
-}
-
-// The reductions of include/mckpp_hip_reduce.h over all shards.  Per-shard sums combined afterwards would not be the single
-// context's bits, so the shards deliver terms and shard 0 reduces: shard 0 fills its slabs (and the land values of the
-// axis-only planes), every shard then writes the terms - or, axis only, the results - of its own rows, and behind all of
-// them shard 0 runs the tree and delivers.
-static int multi_reduce(mckpp_hip_multi *m, const char *who, int32_t nplanes, const mckpp_reduce_plane_c *planes, bool dev_form,
-                        void *consumer_stream)
-{
-  const int ndev = (int)m->ctx.size();
-  mckpp_hip_ctx *root = m->ctx[0];
-  std::vector<red_planes> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (reduce_check(m->ctx[d], who, nplanes, planes, dev_form, rs[(size_t)d], &dev)) return -1;
-  red_planes &r0 = rs[0];
-  if (r0.tab.empty()) return 0;
-  std::vector<int64_t> rows(r0.tab.size(), 0);
-  for (size_t k = 0; k < r0.tab.size(); ++k) {
-    for (int d = 0; d < ndev; ++d) rows[k] += rs[(size_t)d].tab[k].nrow;
-    // axis only: shard 0 writes the land value where no shard has a row
-    if (r0.tab[k].domain_op == 0 && multi_norow(m, who, r0.sched[k])) return -1;
-  }
-  if (reduce_reserve(root, r0, dev_form)) return -1;
-  for (int d = 1; d < ndev; ++d) {   // the other shards write into shard 0's blocks
-    HIPCHK(hipSetDevice(m->ctx[d]->device));
-    if (r0.terms > 0 && dev_ptr_check(m->ctx[d], who, "shard 0's block of terms", root->red.d_terms, r0.terms * sizeof(double)))
-      return -1;
-    if (!dev_form && dev_ptr_check(m->ctx[d], who, "shard 0's block of results", root->red.d_out, r0.outs * sizeof(double)))
-      return -1;
-  }
-  for (int d = 0; d < ndev; ++d)
-    if (reduce_bind(m->ctx[d], root, rs[(size_t)d], dev_form, d == 0, rows)) return -1;
-  if (dev_form && multi_caller_event(m, dev, consumer_stream)) return -1;
-  HIPCHK(hipSetDevice(root->device));
-  HIPCHK(root->red_tab.put(r0.tab, root->stream));
-  if (dev_form) HIPCHK(hipStreamWaitEvent(root->stream, m->ev_caller, 0));
-  if (reduce_launch(root, r0, MCKPP_RED_PHASE_FILL)) return -1;
-  HIPCHK(root->red.ev_fill.record(root->stream));
-  for (int d = 1; d < ndev; ++d) {
-    mckpp_hip_ctx *x = m->ctx[d];
-    HIPCHK(hipSetDevice(x->device));
-    HIPCHK(x->red_tab.put(rs[(size_t)d].tab, x->stream));
-    HIPCHK(hipStreamWaitEvent(x->stream, root->red.ev_fill, 0));
-    if (reduce_launch(x, rs[(size_t)d], MCKPP_RED_PHASE_TERMS)) return -1;
-    HIPCHK(x->red.ev_terms.record(x->stream));
-  }
-  HIPCHK(hipSetDevice(root->device));
-  if (reduce_launch(root, r0, MCKPP_RED_PHASE_TERMS)) return -1;
-  for (int d = 1; d < ndev; ++d) HIPCHK(hipStreamWaitEvent(root->stream, m->ctx[d]->red.ev_terms, 0));
-  if (r0.halve && reduce_launch(root, r0, MCKPP_RED_PHASE_HALVE)) return -1;
-  if (r0.domain && reduce_launch(root, r0, MCKPP_RED_PHASE_FINISH)) return -1;
-  if (!dev_form) return reduce_host_deliver(root, r0);
-  HIPCHK(root->ev_delivered.record(root->stream));
-  HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), root->ev_delivered, 0));
-  return 0;
+  return entry(__func__, m, [&, who = __func__]() -> int { return records_dev(shards(m), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_multi_reduce_weights(mckpp_hip_multi_handle m, const double *point_w, const double *level_w, const double *iface_w)
@@ -5750,47 +5760,25 @@ int mckpp_hip_multi_reduce_weights(mckpp_hip_multi_handle m, const double *point
 int mckpp_hip_multi_records_reduce_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_reduce_plane_c *planes,
                                        void *consumer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int { return multi_reduce(m, who, nplanes, planes, true, consumer_stream); });
+  return entry(__func__, m, [&, who = __func__]() -> int { return records_reduce(shards(m), who, nplanes, planes, true, consumer_stream); });
 }
 
 int mckpp_hip_multi_records_reduce_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_reduce_plane_c *planes)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int { return multi_reduce(m, who, nplanes, planes, false, nullptr); });
+  return entry(__func__, m, [&, who = __func__]() -> int { return records_reduce(shards(m), who, nplanes, planes, false, nullptr); });
 }
 
-// mckpp_hip_put_dev / _put_host over all shards: the same planes for every shard, which writes its own columns only
 int mckpp_hip_multi_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_put_plane_c *planes, void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<std::vector<mckpp_put_plane>> tabs((size_t)ndev);
-  int maxlev = 0, dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (put_check(m->ctx[d], who, nplanes, planes, true, tabs[(size_t)d], &maxlev, &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (put_queue(m->ctx[d], tabs[(size_t)d], maxlev, m->ev_caller)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return put_planes(shards(m), who, nplanes, planes, true, producer_stream); });
 }
 
 int mckpp_hip_multi_put_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_put_plane_c *planes)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<std::vector<mckpp_put_plane>> tabs((size_t)ndev);
-  int maxlev = 0;
-  for (int d = 0; d < ndev; ++d)
-    if (put_check(m->ctx[d], who, nplanes, planes, false, tabs[(size_t)d], &maxlev, nullptr)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (put_host_queue(m->ctx[d], tabs[(size_t)d], maxlev)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return put_planes(shards(m), who, nplanes, planes, false, nullptr); });
 }
 
-// include/mckpp_hip_vaxis.h over all shards: an axis on every shard; the same planes for every shard, which touches its
-// own columns only; every shard checked before any of them queues
+// an axis on every shard
 int mckpp_hip_multi_vaxis_define(mckpp_hip_multi_handle m, int axis, int32_t n, const double *z)
 {
   return multi_each(__func__, m, [&, who = __func__](auto *x) { return vaxis_define(x, who, axis, n, z); });
@@ -5798,107 +5786,36 @@ int mckpp_hip_multi_vaxis_define(mckpp_hip_multi_handle m, int axis, int32_t n, 
 
 int mckpp_hip_multi_vaxis_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes, void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<vaxis_puts> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_put_check(m->ctx[d], who, nplanes, planes, true, rs[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_put_queue(m->ctx[d], rs[(size_t)d].tab, m->ev_caller)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return vaxis_put(shards(m), who, nplanes, planes, true, producer_stream); });
 }
 
 int mckpp_hip_multi_vaxis_put_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_put_plane_c *planes)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<vaxis_puts> rs((size_t)ndev);
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_put_check(m->ctx[d], who, nplanes, planes, false, rs[(size_t)d], nullptr)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_put_host_queue(m->ctx[d], rs[(size_t)d])) return -1;
-  return 0;
-  });
-}
-
-// the profiles: every shard writes its columns and reports its Kelvin word; the host combines them - the call waits,
-// like the upload it follows - and every shard finishes under the combined word
-static int multi_vaxis_profiles(mckpp_hip_multi *m, const char *who, const mckpp_vaxis_profiles_c *p, bool dev_form, void *producer_stream)
-{
-  const int ndev = (int)m->ctx.size();
-  std::vector<vaxis_puts> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_profiles_check(m->ctx[d], who, p, dev_form, rs[(size_t)d], dev_form ? &dev : nullptr)) return -1;
-  if (dev_form && multi_caller_event(m, dev, producer_stream)) return -1;
-  unsigned any = 0;
-  for (int d = 0; d < ndev; ++d) {
-    unsigned kelvin = 0;
-    if (vaxis_profiles_write(m->ctx[d], rs[(size_t)d], dev_form, dev_form ? (hipEvent_t)m->ev_caller : nullptr, &kelvin)) return -1;
-    any |= kelvin;
-  }
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_profiles_finish(m->ctx[d], p->tk0, any, true)) return -1;
-  return 0;
+  return entry(__func__, m, [&, who = __func__]() -> int { return vaxis_put(shards(m), who, nplanes, planes, false, nullptr); });
 }
 
 int mckpp_hip_multi_vaxis_init_profiles_dev(mckpp_hip_multi_handle m, const mckpp_vaxis_profiles_c *p, void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int { return multi_vaxis_profiles(m, who, p, true, producer_stream); });
+  return entry(__func__, m, [&, who = __func__]() -> int { return vaxis_init_profiles(shards(m), who, p, true, producer_stream); });
 }
 
 int mckpp_hip_multi_vaxis_init_profiles_host(mckpp_hip_multi_handle m, const mckpp_vaxis_profiles_c *p)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int { return multi_vaxis_profiles(m, who, p, false, nullptr); });
+  return entry(__func__, m, [&, who = __func__]() -> int { return vaxis_init_profiles(shards(m), who, p, false, nullptr); });
 }
 
 int mckpp_hip_multi_vaxis_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<std::vector<mckpp_vaxis_fetch_plane>> tabs((size_t)ndev);
-  int maxlev = 0, dev = -1;
-  bool any_fill = false;
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_fetch_check(m->ctx[d], who, nplanes, planes, tabs[(size_t)d], &maxlev, &any_fill, &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  if (any_fill) {   // shard 0 fills the points that no shard holds, the others fill none: every point is written once
-    for (int d = 1; d < ndev; ++d)
-      for (auto &e : tabs[(size_t)d]) e.f.fill_land = 0;
-    if (multi_land(m, who)) return -1;
-  }
-  if (multi_caller_event(m, dev, consumer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (vaxis_fetch_queue(m->ctx[d], tabs[(size_t)d], maxlev, any_fill && d == 0, m->ev_caller, consumer_stream)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return vaxis_fetch_dev(shards(m), who, nplanes, planes, consumer_stream); });
 }
 
-// include/mckpp_hip_hgrid.h over all shards: a grid on every shard; forcing in, every shard summing for its own columns
-// from the same caller arrays; fields out with every shard's first stage into shard 0's staging and shard 0's second
-// stage over the union of the shards' columns, so the sums are those of one context, entry for entry
+// a grid on every shard
 int mckpp_hip_multi_hgrid_define(mckpp_hip_multi_handle m, int grid, int64_t n, const mckpp_hgrid_table_c *in, const mckpp_hgrid_table_c *out)
 {
   return multi_each(__func__, m, [&, who = __func__](auto *x) { return hgrid_define(x, who, grid, n, in, out); });
 }
 
-// shard 0's out table of `grid` for the points some shard holds, where it is not that already
-static int multi_hgrid_out(mckpp_hip_multi *m, const char *who, int grid)
-{
-  if (m->ctx[0]->hgd[grid].out.kind == 2) return 0;
-  std::vector<int64_t> ncol;
-  std::vector<const int32_t *> points;
-  for (auto *x : m->ctx) { ncol.push_back(x->ncol); points.push_back(x->ipt.data()); }
-  std::vector<unsigned char> covered;
-  if (export_covered(m->npts, (int)m->ctx.size(), ncol.data(), points.data(), covered))
-    return fail("%s: a column map names a point outside the grid", who);
-  return hgrid_out_build(m->ctx[0], grid, &covered);
-}
-
+// shard 0's out table is that of the union of the shards' columns; the in tables' padded sizes add up
 int mckpp_hip_multi_hgrid_info(mckpp_hip_multi_handle m, int grid, int64_t info[6])
 {
   return entry(__func__, m, [&, who = __func__]() -> int {
@@ -5906,7 +5823,7 @@ int mckpp_hip_multi_hgrid_info(mckpp_hip_multi_handle m, int grid, int64_t info[
   int64_t padded_in = 0;
   for (auto *x : m->ctx) {
     if (!hgrid_of(x, who, "grid", grid)) return -1;
-    if (x == m->ctx[0] && !x->hg[grid].out.ptr.empty() && multi_hgrid_out(m, who, grid)) return -1;
+    if (x == m->ctx[0] && !x->hg[grid].out.ptr.empty() && group_hgrid_out(shards(m), who, grid)) return -1;
     if (hgrid_info(x, who, grid, info, true)) return -1;
     padded_in += info[3];
   }
@@ -5920,151 +5837,38 @@ int mckpp_hip_multi_hgrid_fluxes_dev(mckpp_hip_multi_handle m, int grid, int nti
                                      double flsn, double el, void *producer_stream)
 {
   return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<mckpp_hgrid_ell> t((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (hgrid_in_check(m->ctx[d], who, grid, fields, &t[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (fluxes_dev_queue(m->ctx[d], ntime, fields, l_rest, flsn, el, m->ev_caller, &t[(size_t)d])) return -1;
-  return 0;
+  return fluxes_dev(shards(m), who, ntime, fields, l_rest, flsn, el, producer_stream, &grid);
   });
 }
 
 int mckpp_hip_multi_hgrid_flux_ring_put_dev(mckpp_hip_multi_handle m, int grid, int rec, const double *const fields[8], void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  if (!fields) return fail("%s: null argument", who);
-  const int ndev = (int)m->ctx.size();
-  std::vector<mckpp_hgrid_ell> t((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (ring_put_check(m->ctx[d], who, rec) || hgrid_in_check(m->ctx[d], who, grid, fields, &t[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (ring_put_dev_queue(m->ctx[d], rec, fields, m->ev_caller, &t[(size_t)d])) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return flux_ring_put_dev(shards(m), who, rec, fields, producer_stream, &grid); });
 }
 
 int mckpp_hip_multi_hgrid_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_hgrid_plane_c *planes, void *consumer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<hgrid_fetch> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (hgrid_fetch_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  mckpp_hip_ctx *root = m->ctx[0];
-  for (int g : rs[0].grid)
-    if (multi_hgrid_out(m, who, g)) return -1;
-  if (hgrid_stage(root, rs[0].elems)) return -1;
-  double *stage = root->d_hstage;
-  for (int d = 1; d < ndev; ++d) {   // every shard's device reaches shard 0's staging (peer access, once per pair)
-    HIPCHK(hipSetDevice(m->ctx[d]->device));
-    if (dev_ptr_check(m->ctx[d], who, "the staging plane of shard 0", stage, rs[0].elems * sizeof(double))) return -1;
-  }
-  if (multi_caller_event(m, dev, consumer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d) {
-    mckpp_hip_ctx *x = m->ctx[d];
-    if (d > 0) {
-      HIPCHK(hipSetDevice(x->device));
-      // the staging is shard 0's: behind the second stage of the call before, which read it on shard 0's stream
-      if (root->ev_delivered) HIPCHK(hipStreamWaitEvent(x->stream, root->ev_delivered, 0));
-    }
-    if (hgrid_fetch_first(x, rs[(size_t)d], stage, m->ev_caller)) return -1;
-    if (d > 0) {   // ... and shard 0's second stage behind this shard's first
-      HIPCHK(x->ev_delivered.record(x->stream));
-      HIPCHK(hipSetDevice(root->device));
-      HIPCHK(hipStreamWaitEvent(root->stream, x->ev_delivered, 0));
-    }
-  }
-  return hgrid_fetch_second(root, rs[0], stage, consumer_stream);
-  });
-}
-
-// include/mckpp_hip_remap.h over all shards.  Records: mckpp_hip_multi_hgrid_fetch_dev's order - every shard's rows into
-// shard 0's staging, shard 0's second stage behind them, through tables whose used entries are the rows of any shard.
-// Puts: mckpp_hip_multi_put_dev's order, every shard through its own in table.
-static int multi_remap_out(mckpp_hip_multi *m, const char *who, int sched, int grid)
-{
-  mckpp_hip_ctx *root = m->ctx[0];
-  if (!root->wsched[sched].listed) return multi_hgrid_out(m, who, grid);
-  if (root->wsched[sched].hout[grid].kind == 2) return 0;
-  std::vector<unsigned char> covered((size_t)m->npts, 0);
-  for (auto *x : m->ctx)
-    for (int p : x->wsched[sched].rowpt) covered[(size_t)p] = 1;
-  return remap_out_build(root, sched, grid, &covered);
+  return entry(__func__, m, [&, who = __func__]() -> int { return hgrid_fetch_dev(shards(m), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_multi_remap_records_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_remap_record_plane_c *planes,
                                       void *consumer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<remap_recs> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (remap_records_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  mckpp_hip_ctx *root = m->ctx[0];
-  for (size_t k = 0; k < rs[0].first.size(); ++k)
-    if (multi_remap_out(m, who, rs[0].sched[k], rs[0].grid[k])) return -1;
-  if (hgrid_stage(root, rs[0].elems)) return -1;
-  double *stage = root->d_hstage;
-  for (int d = 1; d < ndev; ++d) {   // every shard's device reaches shard 0's staging (peer access, once per pair)
-    HIPCHK(hipSetDevice(m->ctx[d]->device));
-    if (dev_ptr_check(m->ctx[d], who, "the staging plane of shard 0", stage, rs[0].elems * sizeof(double))) return -1;
-  }
-  if (multi_caller_event(m, dev, consumer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d) {
-    mckpp_hip_ctx *x = m->ctx[d];
-    if (d > 0) {
-      HIPCHK(hipSetDevice(x->device));
-      // the staging is shard 0's: behind the second stage of the call before, which read it on shard 0's stream
-      if (root->ev_delivered) HIPCHK(hipStreamWaitEvent(x->stream, root->ev_delivered, 0));
-    }
-    if (remap_records_first(x, rs[(size_t)d], stage, m->ev_caller)) return -1;
-    if (d > 0) {   // ... and shard 0's second stage behind this shard's first
-      HIPCHK(x->ev_delivered.record(x->stream));
-      HIPCHK(hipSetDevice(root->device));
-      HIPCHK(hipStreamWaitEvent(root->stream, x->ev_delivered, 0));
-    }
-  }
-  return remap_records_second(root, rs[0], stage, consumer_stream);
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return remap_records_dev(shards(m), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_multi_remap_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_remap_put_plane_c *planes,
                                   void *producer_stream)
 {
-  return entry(__func__, m, [&, who = __func__]() -> int {
-  const int ndev = (int)m->ctx.size();
-  std::vector<remap_puts> rs((size_t)ndev);
-  int dev = -1;
-  for (int d = 0; d < ndev; ++d)
-    if (remap_put_check(m->ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  if (multi_caller_event(m, dev, producer_stream)) return -1;
-  for (int d = 0; d < ndev; ++d)
-    if (remap_put_queue(m->ctx[d], rs[(size_t)d], m->ev_caller)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&, who = __func__]() -> int { return remap_put_dev(shards(m), who, nplanes, planes, producer_stream); });
 }
 
 int mckpp_hip_multi_dev_fence(mckpp_hip_multi_handle m, void *stream)
 {
-  return entry(__func__, m, [&]() -> int {
-  for (auto *x : m->ctx)
-    if (dev_fence_queue(x, stream)) return -1;
-  return 0;
-  });
+  return entry(__func__, m, [&]() -> int { return dev_fence(shards(m), stream); });
 }
 
+// the caller's arrays pinned on behalf of this handle go back to pageable memory (before the caller frees them)
 int mckpp_hip_multi_release_host_arrays(mckpp_hip_multi_handle m)
 {
   return entry(__func__, m, [&]() -> int {

@@ -13,7 +13,7 @@ import pytest
 
 import anc_cases as ac
 import ref_loop_cases as lc
-from harness import assert_loop_step, assert_same, flux_args, loop_state, mk, resident  # noqa: F401
+from harness import assert_loop_step, assert_same, flux_args, initialised, loop_state, mk, resident  # noqa: F401
 from harness import loop_golden as golden  # noqa: F401
 
 pytestmark = pytest.mark.gpu
@@ -415,6 +415,98 @@ def test_two_shards_fetch_dev(mk, stepped):
             assert np.all(b[:, ~ocean] == (a.dtype.type(LAND) if fill else -7.0)), (p, dtype, fill, "land points")
             assert not np.any(b[:, ocean] == a.dtype.type(LAND)) and not np.any(b[:, ocean] == -7.0), (p, "ocean points")
     _fetch_and_compare(m, A, npts, 41, planes, what="2 shards against their own window_fetch")
+    m.close()
+
+
+def _alone(mk, m, d):
+    """Shard d of the multi handle m as a context of its own (mckpp_hip_multi_ctx): m's records of its schedules and
+    grids, the shard's handle.  The multi handle owns the context: drop the wrapper with _let_go, never close it."""
+    one = mk.MckppHip.__new__(mk.MckppHip)
+    one.__dict__.update(m.__dict__)
+    one._h = C.c_void_p(mk.api._lib().mckpp_hip_multi_ctx(m._h, d))
+    assert one._h
+    return one
+
+
+def _let_go(one):
+    one._h = C.c_void_p()
+
+
+def test_a_shard_addressed_alone_between_two_multi_calls(mk):
+    """A multi call that fills the points no shard holds leaves shard 0 with the lists and out tables of the union of the
+    shards' columns.  The same call on shard 0's own handle then delivers what a context of its own with shard 0's
+    run_physics mask delivers, bit for bit - shard 1's points are land to it -, and the multi call after it delivers what
+    the first did: fetch_dev, records_dev on a listed and on an unlisted schedule, hgrid_fetch_dev, and records_reduce_dev
+    with axis-only planes, all filling."""
+    import torch
+
+    import hgrid_ref as hr
+
+    A = mk.api
+    case = lc.CASES["sweep_nd3"]
+    npts, nd, ocean = case.ncol, case.ndtocn, lc.ocean(case)
+    n = hr.grids(npts)[1]
+    tout = hr.general_out(n, npts, ocean, 17)
+    pts = np.random.default_rng(5).permutation(npts)[:300]
+    NL = 9   # the levels the listed schedule keeps
+
+    def start(h):
+        h.hgrid_define(0, n, None, tout)
+        h.window_schedule_zoom(1, 1, nd, 2, ("T", "hmix"), A.WIN_MEAN | A.WIN_LAST, points=pts, levels=(2, NL))
+        h.window_schedule(2, 1, nd, 2, ("S",), A.WIN_LAST)
+        h.fluxes(1, *lc.flux_records(case)[0], **flux_args(case))
+        h.step(1, nd)
+
+    def outs(*shapes):
+        return [torch.full(s, -7.0, dtype=torch.float64, device="cuda") for s in shapes]
+
+    def fetch(h):
+        o = outs((1, npts), (41, npts), (1, npts))
+        h.fetch_dev([("T", o[0], 0, 1), ("u", o[1], 0, 41), ("hmix", o[2], 0, 1)], land_value=LAND, fill_land=True)
+        return o
+
+    def records(h):
+        o = outs((NL, len(pts)), (1, len(pts)), (41, npts))
+        h.records_dev([(1, 0, "T", A.OP_MEAN, o[0]), (1, 0, "hmix", A.OP_LAST, o[1]), (2, 0, "S", A.OP_LAST, o[2])],
+                      land_value=LAND, fill_land=True)
+        return o
+
+    def hgrid(h):
+        o = outs((3, n), (1, n))
+        h.hgrid_fetch_dev([("T", 0, o[0], 0, 3), ("hmix", 0, o[1])], norm="used", land_value=LAND, fill_land=True)
+        return o
+
+    def reduce(h):
+        o = outs((len(pts),), (npts,))
+        h.records_reduce_dev([(1, 0, "T", A.OP_MEAN, o[0], "sum", "none"), (2, 0, "S", A.OP_LAST, o[1], "max", "none")],
+                             land_value=LAND)
+        return o
+
+    def got(call, h):
+        return [_bits(o.cpu().numpy()) for o in call(h)]
+
+    m, kcm, k3m = resident(mk, case, shards=2)
+    start(m)
+    mask0, n0 = A.host_shard_mask(k3m.run_physics, 2, 0)
+    assert 0 < n0 < len(lc.active_columns(case)), "both shards hold columns"
+    kc, k3 = lc.hip_raw(case)
+    k3.run_physics[:] = mask0
+    fresh = initialised(mk, kc, k3)
+    start(fresh)
+    shard0 = _alone(mk, m, 0)
+    try:
+        for call in (fetch, records, hgrid, reduce):
+            first = got(call, m)
+            alone = got(call, shard0)
+            again = got(call, m)
+            want = got(call, fresh)
+            for k, (f, a, g, w) in enumerate(zip(first, alone, again, want)):
+                assert np.array_equal(a, w), (call.__name__, k, "shard 0 alone against a context with its mask")
+                assert np.array_equal(g, f), (call.__name__, k, "the multi call after against the one before")
+                assert not np.array_equal(a, f), (call.__name__, k, "shard 0 alone delivers what both shards do")
+    finally:
+        _let_go(shard0)
+    fresh.close()
     m.close()
 
 
