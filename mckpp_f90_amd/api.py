@@ -25,7 +25,8 @@ the state set or incremented in place (include/mckpp_hip_put.h) is the fifth, _S
 records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixth, _SIGNATURES_REDUCE, and three more;
 the caller's vertical axes (include/mckpp_hip_vaxis.h) are the seventh, _SIGNATURES_VAXIS, and the mixin _VerticalAxes;
 the caller's horizontal grids (include/mckpp_hip_hgrid.h) are the eighth, _SIGNATURES_HGRID, and the mixin _HorizontalGrids;
-records out and state in on those grids (include/mckpp_hip_remap.h) are the ninth, _SIGNATURES_REMAP, and the mixin _Remap.
+records out and state in on those grids (include/mckpp_hip_remap.h) are the ninth, _SIGNATURES_REMAP, and the mixin _Remap;
+a caller grid and a caller axis in one call (include/mckpp_hip_hv.h) are the tenth, _SIGNATURES_HV, and the mixin _GridAxis.
 """
 import ctypes as C
 import sys
@@ -507,6 +508,26 @@ _SIGNATURES_REMAP = {
 }
 
 
+class _HvPlaneC(C.Structure):
+    """mckpp_hv_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "axis", "dtype", "grid", "norm", "fill_land")] + \
+               [("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+class _HvPutPlaneC(C.Structure):
+    """mckpp_hv_put_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("field", "axis", "dtype", "op", "flags", "grid")] + \
+               [("skip_value", C.c_double), ("in", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_hv.h, a caller grid and a caller axis in one call, in the same form;
+# tests/test_hv_cpu.py holds this table to that header.
+_SIGNATURES_HV = {
+    "mckpp_hip_hv_fetch_dev": _sig(_H, _i32, C.POINTER(_HvPlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_hv_put_dev": _sig(_H, _i32, C.POINTER(_HvPutPlaneC), C.c_void_p, twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -562,6 +583,11 @@ def _signatures_remap():
     return _spelled(_SIGNATURES_REMAP)
 
 
+def _signatures_hv():
+    """... and of every function of mckpp_hip_hv.h."""
+    return _spelled(_SIGNATURES_HV)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
@@ -569,7 +595,8 @@ def _bind(lib):
     # everything else works with it, and a call of that name fails there by name
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
                                   **_signatures_records(), **_signatures_put(), **_signatures_reduce(),
-                                  **_signatures_vaxis(), **_signatures_hgrid(), **_signatures_remap()}.items():
+                                  **_signatures_vaxis(), **_signatures_hgrid(), **_signatures_remap(),
+                                  **_signatures_hv()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -1781,8 +1808,94 @@ class _Remap:
             self._call("dev_fence", s)
 
 
+class _GridAxis:
+    """A caller grid and a caller axis in one call (include/mckpp_hip_hv.h): fields out and state in on points and levels
+    that are both not the model's, through the tables of hgrid_define and vaxis_define.  An array on grid g and axis a
+    is (n_a, n_g): points fastest, the whole axis."""
+
+    def hv_fetch_dev(self, planes, stream=None, norm="none", land_value=1e20, fill_land=True):
+        """fetch_dev onto a caller grid and a caller axis: a plane is (field, grid, axis, out), out a tensor of shape
+        (n_axis, n_grid) of float64 or float32.  Vertical first: every resident column's profile is interpolated onto
+        the axis as vaxis_fetch_dev does; then every caller point's value at a caller level is hgrid_fetch_dev's of those
+        - norm, land_value and fill_land are its.  Two-dimensional fields and those on the interface axis are refused."""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"hv_fetch_dev: {len(planes)} planes, at most 64 in one call")
+        nrm = _hgrid_norm("hv_fetch_dev", norm)
+        arr = (_HvPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            who = f"hv_fetch_dev: planes[{k}]"
+            if len(p) != 4:
+                raise ValueError(f"{who} is (field, grid, axis, out)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: {e}") from None
+            if f in _OUT_2D:
+                raise ValueError(f"{who}: field {OUT_FIELDS[f]} is two-dimensional: it has no vertical axis to interpolate")
+            if f in _OUT_INTERFACE:
+                raise ValueError(f"{who}: field {OUT_FIELDS[f]} lives on the interface axis 0..nz, not on the levels a "
+                                 "caller's axis is interpolated from")
+            n, nax, out = self._hgrid(who, p[1]), self._vaxis(who, p[2]), p[3]
+            shape = tuple(getattr(out, "shape", ()))
+            if shape not in ((nax, n), (nax * n,)):
+                raise ValueError(f"{who}: out has shape {shape}; axis {int(p[2])} on grid {int(p[1])} is ({nax}, {n})")
+            ptr, typestr = _dev_array(out, f"{who} out", nax * n, tuple(_DEV_TYPESTR))
+            arr[k] = _HvPlaneC(f, int(p[2]), _DEV_TYPESTR[typestr], int(p[1]), nrm, int(bool(fill_land)), float(land_value), ptr)
+            self._hold_dev(out)
+        self._call("hv_fetch_dev", len(planes), arr, _dev_stream(stream))
+
+    def hv_put_dev(self, planes, op="set", time_levels=False, skip=None, stream=None, fence=False):
+        """put_dev from a caller grid and a caller axis: a plane is (field, grid, axis, array), the array a tensor of
+        shape (n_axis, n_grid) of float64 or float32, and writes every model level of u, v, T, S_anom or S.  Horizontal
+        first: a resident column's value at a caller level is the sum of its row of the grid's in table over that level
+        of the array; the model levels are then interpolated from those sums as vaxis_put_dev does.  op, time_levels,
+        stream and fence are put_dev's.  skip: a state element stays untouched if any entry of its column's row reads
+        this value at a caller level its model level is interpolated from.  A resident column whose row is empty is
+        left untouched.  Nothing is cancelled."""
+        who = "hv_put_dev"
+        if op not in _PUT_OPS or isinstance(op, bool):
+            raise ValueError(f"{who}: op {op!r} (\"set\" or \"add\")")
+        flags, skip_value = (PUT_TIME_LEVELS if time_levels else 0), 0.0
+        if skip is not None:
+            flags, skip_value = flags | PUT_SKIP, float(skip)
+            if skip_value != skip_value:
+                raise ValueError(f"{who}: skip is NaN, which no element compares equal to")
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"{who}: {len(planes)} planes, at most 64 in one call")
+        arr, seen = (_HvPutPlaneC * max(1, len(planes)))(), []
+        for k, p in enumerate(planes):
+            if len(p) != 4:
+                raise ValueError(f"{who}: planes[{k}] is (field, grid, axis, array)")
+            try:
+                f = _win_field(p[0])
+            except ValueError as e:
+                raise ValueError(f"{who}: planes[{k}]: {e}") from None
+            if f not in _PUT_FIELDS:
+                raise ValueError(f"{who}: planes[{k}]: field {OUT_FIELDS[f]} is an output of the step, not state (u, v, T, "
+                                 "S_anom, S)")
+            n, nax, a = self._hgrid(f"{who}: planes[{k}]", p[1]), self._vaxis(f"{who}: planes[{k}]", p[2]), p[3]
+            if _PUT_FIELDS[f] in seen:
+                raise ValueError(f"{who}: planes[{k}] and planes[{seen.index(_PUT_FIELDS[f])}] write {_PUT_FIELDS[f]}: a plane "
+                                 "writes the whole profile, and the planes of a call have no order")
+            seen.append(_PUT_FIELDS[f])
+            shape = tuple(getattr(a, "shape", ()))
+            if shape not in ((nax, n), (nax * n,)):
+                raise ValueError(f"{who}: planes[{k}]: the array has shape {shape}; axis {int(p[2])} on grid {int(p[1])} is "
+                                 f"({nax}, {n})")
+            ptr, typestr = _dev_array(a, f"{who}: planes[{k}] array", nax * n, tuple(_DEV_TYPESTR))
+            arr[k] = _HvPutPlaneC(f, int(p[2]), _DEV_TYPESTR[typestr], _PUT_OPS[op], flags, int(p[1]), skip_value, ptr)
+        s = _dev_stream(stream)
+        for p in planes:
+            self._hold_dev(p[3])
+        self._call("hv_put_dev", len(planes), arr, s)
+        if fence:
+            self._call("dev_fence", s)
+
+
 class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays, _VerticalAxes,
-              _HorizontalGrids, _Remap):
+              _HorizontalGrids, _Remap, _GridAxis):
     """What one device context and several GPUs behind one handle have in common: everything but how they are made.
     Method `name` is the C function self._pre + name applied to the handle self._h."""
     _pre = "mckpp_hip_"

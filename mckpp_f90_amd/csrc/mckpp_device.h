@@ -380,6 +380,21 @@ struct mckpp_remap_put_plane {
 #define MCKPP_REMAP_PLANES 64   // most planes of one call (the device table's size)
 hipError_t mckpp_launch_remap_put_planes(const mckpp_remap_put_plane *tab, int nplanes, int maxlev, int64_t ncol, double *cs,
                                          hipStream_t stream);
+// One plane of mckpp_hip_hv_put_dev (include/mckpp_hip_hv.h; k_hv_put_planes): put.in is in(n, n_axis) on a caller grid
+// of n points and a caller axis of n_axis levels, put.nlev the model's nzp1.  Level lev of resident column c takes
+// vinterp through tab[lev], the axis's in table, of the sums of row c of the in table `t` over the one or two caller
+// levels the entry names, and put_element does with it what `put` says.  put's own skip is 0: `skip` is decided on the
+// input side, where the values the entries read at those caller levels are.  A column with an empty row is left alone.
+struct mckpp_hv_put_plane {
+  mckpp_put_plane put;
+  mckpp_hgrid_ell t;
+  const mckpp_vaxis_ent *tab;
+  int64_t n;
+  int n_axis, skip;
+};
+#define MCKPP_HV_PLANES 64   // most planes of one call (the device table's size)
+hipError_t mckpp_launch_hv_put_planes(const mckpp_hv_put_plane *tab, int nplanes, int nzp1, int64_t ncol, double *cs,
+                                      hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

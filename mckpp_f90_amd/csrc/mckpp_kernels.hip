@@ -783,6 +783,75 @@ __global__ __launch_bounds__(256) void k_vaxis_fetch_planes(const mckpp_vaxis_fe
   else vaxis_fetch_plane<double>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
 }
 
+// State in from planes on a caller's grid and a caller's axis at once (mckpp_hip_hv_put_dev, include/mckpp_hip_hv.h):
+// horizontal first, at the caller's levels, then vertical.  remap_put_plane's shape - the workgroup's 64 columns are one
+// ELL slice, which its four waves share, and a tile of 64 model levels - with the 16 running sums of hgrid_row_sums
+// holding 8 model levels a pass: sums 2 j and 2 j + 1 are those of the caller levels kin and kin + 1 that the axis's in
+// table names for the pass's level j.  The entry is the wave's (the wave id goes through readfirstlane, so the eight
+// entries of a pass are scalar loads).  A clamp reads kin for both: every gather is issued unconditionally, the second
+// sum of a clamp is formed from the same values and vaxis_value does not look at it, and its skip bit says what the
+// first one says.  A level past the axis reads caller level 0 and is never written.  Two passes cover the wave's 16
+// levels, so an entry's index and weight are loaded twice a workgroup.  vaxis_value forms the element on the point side;
+// it and its hold byte - a value read at a level the branch reads was the skip value, or the row is empty - cross the
+// tiles, and put_element is what happens to the others on the row side.  The barrier rule is kept by hand: the one exit
+// before the barrier depends on blockIdx and the plane alone.
+template <class T>
+__device__ __forceinline__ void hv_put_plane(const mckpp_hv_put_plane &e, double (*tile)[65], unsigned char (*hold)[68],
+                                             int64_t ncol, double *__restrict__ cs)
+{
+  const int l0 = blockIdx.y * 64, nlev = e.put.nlev;
+  if (l0 >= nlev) return;   // (the grid's level tiles are those of the model's axis)
+  const T *__restrict__ src = static_cast<const T *>(e.put.in);
+  const double skip_value = e.put.skip_value;
+  const int64_t r0 = (int64_t)blockIdx.x * 64;
+  const int tx = threadIdx.x & 63, ty = threadIdx.x >> 6;
+  const int wave = __builtin_amdgcn_readfirstlane(ty);
+  for (int pass = 0; pass < 2; ++pass) {      // read: points fastest, 8 model levels per wave and pass
+    const int t0 = wave * 16 + pass * 8;      // the pass's first level of the tile
+    mckpp_vaxis_ent ent[8];
+    int64_t at[16];                           // where the caller levels of sums 2 j, 2 j + 1 begin in the plane
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      const int lev = l0 + t0 + j;
+      ent[j] = lev < nlev ? e.tab[lev] : mckpp_vaxis_ent{0, 0, 0.0, 1.0};
+      at[2 * j] = (int64_t)ent[j].kin * e.n;
+      at[2 * j + 1] = (int64_t)(ent[j].branch == 2 ? ent[j].kin + 1 : ent[j].kin) * e.n;
+    }
+    double a[16], d;
+    unsigned hit = 0u;
+    const int len = hgrid_row_sums<16, false>(e.t, r0 + tx, [&](int m, int i) {
+      const double v = (double)src[at[m] + i];
+      if (v == skip_value) hit |= 1u << m;
+      return v;
+    }, a, d);
+    if (!e.skip) hit = 0u;
+    if (len == 0) hit = 0xffffu;              // an empty row, or a lane past the last column
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      tile[t0 + j][tx] = vaxis_value(ent[j], a[2 * j], a[2 * j + 1]);
+      hold[t0 + j][tx] = (hit >> (2 * j)) & 3u ? 1 : 0;
+    }
+  }
+  __syncthreads();
+  const int lev = l0 + tx;
+  if (lev >= nlev) return;
+  for (int rr = ty; rr < 64; rr += 4) {       // write: levels fastest
+    const int64_t r = r0 + rr;
+    if (r >= ncol || hold[tx][rr]) continue;
+    put_element(e.put, cs, r, lev, tile[tx][rr]);
+  }
+}
+
+__global__ __launch_bounds__(256) void k_hv_put_planes(const mckpp_hv_put_plane *__restrict__ tab, int64_t ncol,
+                                                       double *__restrict__ cs)
+{
+  __shared__ double tile[64][65];
+  __shared__ unsigned char hold[64][68];
+  const mckpp_hv_put_plane e = tab[blockIdx.z];
+  if (e.put.f32) hv_put_plane<float>(e, tile, hold, ncol, cs);
+  else hv_put_plane<double>(e, tile, hold, ncol, cs);
+}
+
 // ---------------------------------------------------------------------------
 // Records reduced over levels and points (mckpp_hip_records_reduce_dev / _host).  include/mckpp_hip_reduce.h states the
 // arithmetic and its order; the four kernels below are that statement, each one launch for all planes of a call
@@ -968,6 +1037,15 @@ hipError_t mckpp_launch_remap_put_planes(const mckpp_remap_put_plane *tab, int n
   if (nplanes <= 0 || maxlev <= 0 || ncol <= 0) return hipSuccess;
   dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
   hipLaunchKernelGGL(k_remap_put_planes, grid, dim3(256), 0, stream, tab, ncol, cs);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_hv_put_planes(const mckpp_hv_put_plane *tab, int nplanes, int nzp1, int64_t ncol, double *cs,
+                                      hipStream_t stream)
+{
+  if (nplanes <= 0 || nzp1 <= 0 || ncol <= 0) return hipSuccess;
+  dim3 grid((unsigned)((ncol + 63) / 64), (unsigned)((nzp1 + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_hv_put_planes, grid, dim3(256), 0, stream, tab, ncol, cs);
   return hipGetLastError();
 }
 

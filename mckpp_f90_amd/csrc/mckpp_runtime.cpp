@@ -1,6 +1,6 @@
 // mckpp_runtime.cpp - host side of the C-ABI declared in include/mckpp_hip.h and its companions mckpp_hip_device.h,
 // mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h and
-// mckpp_hip_hgrid.h with mckpp_hip_remap.h.
+// mckpp_hip_hgrid.h with mckpp_hip_remap.h and mckpp_hip_hv.h.
 //
 // Owns the device-resident column state (level-fastest rows, one per
 // run_physics column), the device copies of kpp_const_fields, one HIP stream
@@ -22,6 +22,7 @@
 #include "../../include/mckpp_hip_vaxis.h"
 #include "../../include/mckpp_hip_hgrid.h"
 #include "../../include/mckpp_hip_remap.h"
+#include "../../include/mckpp_hip_hv.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -324,6 +325,7 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   } hg[MCKPP_HGRIDS];
   plane_table<mckpp_hgrid_plane, MCKPP_HGRID_PLANES> hgrid_tab;
   plane_table<mckpp_remap_put_plane, MCKPP_REMAP_PLANES> rput_tab;   // mckpp_hip_remap_put_dev's (include/mckpp_hip_remap.h)
+  plane_table<mckpp_hv_put_plane, MCKPP_HV_PLANES> hvput_tab;        // mckpp_hip_hv_put_dev's (include/mckpp_hip_hv.h)
   std::vector<int> peers;   // devices whose memory this context's device has been given peer access to
   int diag = 1;
   // optional-physics contexts: the relaxation / correction / advection inputs come with upload (or
@@ -3202,6 +3204,23 @@ const char *vaxis_interface_name(int field)
   }
 }
 
+// What planes[k] of a fetch on a caller axis says of its field and its axis, checked - the one statement of it for
+// vaxis_fetch_check and for hv_fetch_check (include/mckpp_hip_hv.h).  d: the field on the device; the axis, or null
+const mckpp_hip_ctx::vaxis *vaxis_fetch_resolve(mckpp_hip_ctx *h, const char *who, int k, int field, int axis, out_desc &d)
+{
+  if (field < 0 || field >= MCKPP_OUT_COUNT) return fail("%s: planes[%d]: unknown output field %d", who, k, field), nullptr;
+  if (const char *name = vaxis_interface_name(field))
+    return fail("%s: planes[%d]: field %d (%s) lives on the interface axis 0..nz, not on the levels zm(1:nzp1) a caller's axis "
+                "is interpolated from", who, k, field, name), nullptr;
+  if (out_field(h, field, d)) return nullptr;
+  if (d.nlev == 1)
+    return fail("%s: planes[%d]: field %d%s is two-dimensional: it has no vertical axis to interpolate", who, k, field,
+                field == MCKPP_OUT_HMIX ? " (hmix)" : ""), nullptr;
+  char arg[32];
+  snprintf(arg, sizeof arg, "planes[%d]", k);
+  return vaxis_of(h, who, arg, axis);
+}
+
 // The planes of a fetch on caller axes, checked and resolved into the kernel's table; *any_fill: a plane fills the land
 int vaxis_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_vaxis_dev_plane_c *planes,
                       std::vector<mckpp_vaxis_fetch_plane> &tab, int *maxlev, bool *any_fill, int *dev)
@@ -3213,19 +3232,10 @@ int vaxis_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const 
   *any_fill = false;
   for (int k = 0; k < nplanes; ++k) {
     const mckpp_vaxis_dev_plane_c &q = planes[k];
-    if (q.field < 0 || q.field >= MCKPP_OUT_COUNT) return fail("%s: planes[%d]: unknown output field %d", who, k, q.field);
-    if (const char *name = vaxis_interface_name(q.field))
-      return fail("%s: planes[%d]: field %d (%s) lives on the interface axis 0..nz, not on the levels zm(1:nzp1) a caller's axis "
-                  "is interpolated from", who, k, q.field, name);
     out_desc d;
-    if (out_field(h, q.field, d)) return -1;
-    if (d.nlev == 1)
-      return fail("%s: planes[%d]: field %d%s is two-dimensional: it has no vertical axis to interpolate", who, k, q.field,
-                  q.field == MCKPP_OUT_HMIX ? " (hmix)" : "");
-    char arg[32];
-    snprintf(arg, sizeof arg, "planes[%d]", k);
-    const mckpp_hip_ctx::vaxis *ax = vaxis_of(h, who, arg, q.axis);
+    const mckpp_hip_ctx::vaxis *ax = vaxis_fetch_resolve(h, who, k, q.field, q.axis, d);
     if (!ax) return -1;
+    char arg[32];
     const size_t elem = plane_elem(who, k, q.dtype);
     const int n = (int)ax->z.size();
     snprintf(arg, sizeof arg, "planes[%d].out", k);
@@ -4360,8 +4370,149 @@ int remap_put_dev(const ctx_group &g, const char *who, int32_t nplanes, const mc
     if (remap_put_queue(g.ctx[d], rs[(size_t)d], *g.ev)) return -1;
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// A caller grid and a caller axis in one call (include/mckpp_hip_hv.h), the parts above put together.  Fields out: a
+// plane's field and axis are resolved by vaxis_fetch_resolve and its grid, norm and array by hgrid_out_resolve, with the
+// axis's n as the plane's levels; stage 1 is k_vaxis_fetch_planes into the hgrid staging (doubles, no land fill), stage 2
+// k_hgrid_out through two_stage_deliver.  State in: put_resolve over the whole profile and vaxis_put_check's rules of
+// axis and planes, remap_put_check's of grid and array; put_queue's order with k_hv_put_planes as the launch.
+// ---------------------------------------------------------------------------
+struct hv_fetch {
+  std::vector<mckpp_vaxis_fetch_plane> first;   // (`f.out` set when it is queued)
+  hgrid_outs o;
+};
+
+int hv_fetch_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_hv_plane_c *planes, hv_fetch &r, int *dev)
+{
+  if (planes_count_check(who, nplanes, planes, MCKPP_HV_PLANES_MAX) || uploaded_check(h, who)) return -1;
+  HIPCHK(hipSetDevice(h->device));
+  r = hv_fetch{};
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_hv_plane_c &q = planes[k];
+    out_desc d;
+    const mckpp_hip_ctx::vaxis *ax = vaxis_fetch_resolve(h, who, k, q.field, q.axis, d);
+    if (!ax) return -1;
+    const int n = (int)ax->z.size();
+    // the plane as hgrid_out_resolve reads one: its levels are the caller axis'
+    const struct { int32_t grid, norm, nlev, dtype, fill_land; double land_value; void *out; } v{
+        q.grid, q.norm, n, q.dtype, q.fill_land, q.land_value, q.out};
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem || hgrid_out_resolve(h, who, k, v, elem, k == 0 ? dev : nullptr, r.o)) return -1;
+    r.first.push_back(mckpp_vaxis_fetch_plane{mckpp_fetch_plane{d.src, nullptr, 0.0, d.ld, d.off, n, d.add_sref, 0, 0}, ax->d_out});
+  }
+  return 0;
+}
+
+// stage 1 on this context's stream, behind `before`: its columns' profiles on the caller's levels into `stage`
+int hv_fetch_first(mckpp_hip_ctx *h, hv_fetch &r, double *stage, hipEvent_t before)
+{
+  HIPCHK(hipSetDevice(h->device));
+  for (size_t k = 0; k < r.first.size(); ++k) r.first[k].f.out = stage + r.o.at[k];
+  HIPCHK(h->vfetch_tab.put(r.first, h->stream));
+  HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
+  HIPCHK(mckpp_launch_vaxis_fetch_planes(h->vfetch_tab, (int)r.first.size(), r.o.maxlev, h->d_ipt, h->ncol, h->npts, h->d_cs,
+                                         nullptr, 0, h->stream));
+  return 0;
+}
+
+// mckpp_hip_hv_fetch_dev: hgrid_fetch_dev's order with another first stage
+int hv_fetch_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_hv_plane_c *planes, void *consumer_stream)
+{
+  std::vector<hv_fetch> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (hv_fetch_check(g.ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  hgrid_outs &o = rs[0].o;
+  for (int grid : o.grid)
+    if (group_hgrid_out(g, who, grid)) return -1;
+  for (size_t k = 0; k < o.second.size(); ++k) o.second[k].t = hgrid_ell(g.root()->hgd[o.grid[k]].out);
+  return two_stage_deliver(g, who, o, dev, consumer_stream, [&](int d, double *stage, hipEvent_t before) {
+    return hv_fetch_first(g.ctx[d], rs[(size_t)d], stage, before);
+  });
+}
+
+// The planes of a put on a caller grid and a caller axis, checked and resolved into the kernel's table
+int hv_put_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_hv_put_plane_c *planes,
+                 std::vector<mckpp_hv_put_plane> &tab, int *dev)
+{
+  if (uploaded_check(h, who) || planes_count_check(who, nplanes, planes, MCKPP_HV_PLANES_MAX)) return -1;
+  HIPCHK(hipSetDevice(h->device));
+  tab.clear();
+  int prof[MCKPP_HV_PLANES_MAX];
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_hv_put_plane_c &q = planes[k];
+    mckpp_hv_put_plane e{};
+    int row;
+    size_t elem;
+    if (put_resolve(h, who, k, q.field, 0, h->nzp1, q.dtype, q.op, q.flags, q.skip_value, e.put, &row, &elem)) return -1;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d]", k);
+    const mckpp_hip_ctx::vaxis *ax = vaxis_of(h, who, arg, q.axis);
+    if (!ax) return -1;
+    for (int j = 0; j < k; ++j)
+      if (prof[j] == row)
+        return fail("%s: planes[%d] and planes[%d] write the same field (%d, %d): a plane writes the whole profile, and the "
+                    "planes of a call have no order", who, k, j, q.field, planes[j].field);
+    prof[k] = row;
+    const mckpp_hip_ctx::hgrid *g = hgrid_of(h, who, arg, q.grid);
+    if (!g) return -1;
+    if (g->in.ptr.empty())
+      return fail("%s: planes[%d]: grid %d has no in table (caller -> model): mckpp_hip_hgrid_define was given none", who, k,
+                  q.grid);
+    snprintf(arg, sizeof arg, "planes[%d].in", k);
+    if (dev_ptr_check(h, who, arg, q.in, (size_t)g->n * ax->z.size() * elem, k == 0 ? dev : nullptr)) return -1;
+    e.put.in = q.in;
+    e.skip = e.put.skip;   // decided on the input side, where the values the entries read are: put_element's own is off
+    e.put.skip = 0;
+    e.n = g->n;
+    e.n_axis = (int)ax->z.size();
+    e.tab = ax->d_in;
+    if (hgrid_in_build(h, q.grid)) return -1;   // (on first use; an empty row is no refusal here)
+    e.t = hgrid_ell(h->hgd[q.grid].in);
+    tab.push_back(e);
+  }
+  return 0;
+}
+
+// put_queue's order with the launch of k_hv_put_planes
+int hv_put_queue(mckpp_hip_ctx *h, const std::vector<mckpp_hv_put_plane> &tab, hipEvent_t produced)
+{
+  if (tab.empty() || h->ncol == 0) return 0;
+  HIPCHK(hipSetDevice(h->device));
+  HIPCHK(h->hvput_tab.put(tab, h->stream));
+  if (produced) HIPCHK(hipStreamWaitEvent(h->stream, produced, 0));
+  HIPCHK(mckpp_launch_hv_put_planes(h->hvput_tab, (int)tab.size(), h->nzp1, h->ncol, h->d_cs, h->stream));
+  HIPCHK(h->ev_read.record(h->stream));
+  return 0;
+}
+
+// mckpp_hip_hv_put_dev: put_planes' order, every shard through its own in table
+int hv_put_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_hv_put_plane_c *planes, void *producer_stream)
+{
+  std::vector<std::vector<mckpp_hv_put_plane>> tabs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (hv_put_check(g.ctx[d], who, nplanes, planes, tabs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  if (caller_event(g, dev, producer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d)
+    if (hv_put_queue(g.ctx[d], tabs[(size_t)d], *g.ev)) return -1;
+  return 0;
+}
 }  // namespace
 }  // extern "C++"
+
+int mckpp_hip_hv_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hv_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return hv_fetch_dev(lone(h), who, nplanes, planes, consumer_stream); });
+}
+
+int mckpp_hip_hv_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hv_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return hv_put_dev(lone(h), who, nplanes, planes, producer_stream); });
+}
 
 int mckpp_hip_remap_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_remap_record_plane_c *planes, void *consumer_stream)
 {
@@ -5861,6 +6012,16 @@ int mckpp_hip_multi_remap_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, con
                                   void *producer_stream)
 {
   return entry(__func__, m, [&, who = __func__]() -> int { return remap_put_dev(shards(m), who, nplanes, planes, producer_stream); });
+}
+
+int mckpp_hip_multi_hv_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_hv_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return hv_fetch_dev(shards(m), who, nplanes, planes, consumer_stream); });
+}
+
+int mckpp_hip_multi_hv_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_hv_put_plane_c *planes, void *producer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return hv_put_dev(shards(m), who, nplanes, planes, producer_stream); });
 }
 
 int mckpp_hip_multi_dev_fence(mckpp_hip_multi_handle m, void *stream)

@@ -1,5 +1,5 @@
 !> iso_c_binding view of include/mckpp_hip.h and of its companions
-!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h, mckpp_hip_hgrid.h and mckpp_hip_remap.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
+!! mckpp_hip_device.h, mckpp_hip_zoom.h, mckpp_hip_device_records.h, mckpp_hip_put.h, mckpp_hip_reduce.h, mckpp_hip_vaxis.h, mckpp_hip_hgrid.h, mckpp_hip_remap.h and mckpp_hip_hv.h: the only place the Fortran host touches the HIP library.  Struct layouts mirror mckpp_const_c and
 !! mckpp_state_ptrs_c member for member.
 module mckpp_hip_binding
   use iso_c_binding
@@ -137,6 +137,23 @@ module mckpp_hip_binding
     real(c_double) :: skip_value
     type(c_ptr) :: in
   end type mckpp_remap_put_plane_c
+  !> a caller grid and a caller axis in one call (include/mckpp_hip_hv.h).  One plane of mckpp_hip_hv_fetch_dev: `field`
+  !! as it stands, interpolated onto axis `axis` at the model's points and then remapped onto caller grid `grid`, into
+  !! out (n_grid, n_axis), with norm and fill_land as in mckpp_hgrid_plane_c
+  integer(c_int32_t), parameter :: MCKPP_HV_PLANES_MAX = 64
+  type, bind(C) :: mckpp_hv_plane_c
+    integer(c_int32_t) :: field, axis, dtype, grid, norm, fill_land
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_hv_plane_c
+  !> one plane of mckpp_hip_hv_put_dev: the array at `in`, (n_grid, n_axis), on caller grid `grid` and caller axis
+  !! `axis`; every resident column takes the sums of its row of the grid's in table at the caller's levels and its
+  !! whole profile is interpolated from them; op, flags and skip_value as in mckpp_vaxis_put_plane_c
+  type, bind(C) :: mckpp_hv_put_plane_c
+    integer(c_int32_t) :: field, axis, dtype, op, flags, grid
+    real(c_double) :: skip_value
+    type(c_ptr) :: in
+  end type mckpp_hv_put_plane_c
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -1185,6 +1202,38 @@ module mckpp_hip_binding
       type(c_ptr), value :: m, producer_stream
       integer(c_int32_t), value :: nplanes
       type(mckpp_remap_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! a caller grid and a caller axis in one call (include/mckpp_hip_hv.h): vertical first on the way out, horizontal
+    ! first on the way in, with the ordering of mckpp_hip_hgrid_fetch_dev and of mckpp_hip_put_dev
+    function mckpp_hip_hv_fetch_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_hv_fetch_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hv_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hv_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_hv_put_dev(handle, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_hv_put_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hv_put_plane_c
+      type(c_ptr), value :: handle, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hv_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hv_fetch_dev(m, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_multi_hv_fetch_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hv_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hv_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_hv_put_dev(m, nplanes, planes, producer_stream) bind(C, name="mckpp_hip_multi_hv_put_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hv_put_plane_c
+      type(c_ptr), value :: m, producer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hv_put_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
