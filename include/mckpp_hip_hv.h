@@ -20,9 +20,9 @@
  * mckpp_hip_hgrid_define and axes from mckpp_hip_vaxis_define, both unchanged.  The device, the host helpers
  * (mckpp_host_hgrid_apply, mckpp_host_vaxis_map) and several shards give the same bits.
  *
- * Out of scope: interval means (records) on a caller axis; mckpp_hip_vaxis_init_profiles from a caller grid; a host
- * form - a host caller composes mckpp_host_hgrid_apply, mckpp_host_vaxis_map and mckpp_hip_put_host /
- * mckpp_hip_window_fetch.
+ * Out of scope: mckpp_hip_vaxis_init_profiles from a caller grid; a host form - a host caller composes
+ * mckpp_host_hgrid_apply, mckpp_host_vaxis_map and mckpp_hip_put_host / mckpp_hip_window_fetch.  Interval means
+ * (records) on a caller axis are mckpp_hip_vrecords.h's.
  *
  * Conventions are those of mckpp_hip_device.h: device pointers checked before anything is queued, streams passed as
  * void *, a refusal leaves state, schedules, records, grids and axes untouched and names the function and planes[k].

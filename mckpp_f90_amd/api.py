@@ -26,7 +26,9 @@ records reduced over levels and points (include/mckpp_hip_reduce.h) are the sixt
 the caller's vertical axes (include/mckpp_hip_vaxis.h) are the seventh, _SIGNATURES_VAXIS, and the mixin _VerticalAxes;
 the caller's horizontal grids (include/mckpp_hip_hgrid.h) are the eighth, _SIGNATURES_HGRID, and the mixin _HorizontalGrids;
 records out and state in on those grids (include/mckpp_hip_remap.h) are the ninth, _SIGNATURES_REMAP, and the mixin _Remap;
-a caller grid and a caller axis in one call (include/mckpp_hip_hv.h) are the tenth, _SIGNATURES_HV, and the mixin _GridAxis.
+a caller grid and a caller axis in one call (include/mckpp_hip_hv.h) are the tenth, _SIGNATURES_HV, and the mixin _GridAxis;
+completed records on a caller axis (include/mckpp_hip_vrecords.h) are the eleventh, _SIGNATURES_VRECORDS, and the mixin
+_AxisRecords.
 """
 import ctypes as C
 import sys
@@ -528,6 +530,28 @@ _SIGNATURES_HV = {
 }
 
 
+class _VaxisRecordPlaneC(C.Structure):
+    """mckpp_vaxis_record_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("sched", "field", "op", "axis", "dtype", "fill_land")] + \
+               [("rec", C.c_int64), ("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+class _HvRecordPlaneC(C.Structure):
+    """mckpp_hv_record_plane_c"""
+    _fields_ = [(n, C.c_int32) for n in ("sched", "field", "op", "axis", "dtype", "grid", "norm", "fill_land")] + \
+               [("rec", C.c_int64), ("land_value", C.c_double), ("out", C.c_void_p)]
+
+
+# Every function of include/mckpp_hip_vrecords.h, completed records on a caller axis, in the same form;
+# tests/test_vrecords_cpu.py holds this table to that header.
+_SIGNATURES_VRECORDS = {
+    "mckpp_host_vrecords_rule": _sig(_i32, _ip, _ip, _i32, _i32, _ip, _ip),
+    "mckpp_hip_vrecords_vaxis_dev": _sig(_H, _i32, C.POINTER(_VaxisRecordPlaneC), C.c_void_p, twin=True),
+    "mckpp_hip_vrecords_vaxis_host": _sig(_H, _i32, C.POINTER(_VaxisRecordPlaneC), twin=True),
+    "mckpp_hip_vrecords_hv_dev": _sig(_H, _i32, C.POINTER(_HvRecordPlaneC), C.c_void_p, twin=True),
+}
+
+
 def _spelled(table):
     """C name -> (restype, argtypes) of a signature table with the multi_ twins spelled out."""
     out = {}
@@ -588,6 +612,11 @@ def _signatures_hv():
     return _spelled(_SIGNATURES_HV)
 
 
+def _signatures_vrecords():
+    """... and of every function of mckpp_hip_vrecords.h."""
+    return _spelled(_SIGNATURES_VRECORDS)
+
+
 def _bind(lib):
     if getattr(lib, "_mckpp_bound", False):
         return lib
@@ -596,7 +625,7 @@ def _bind(lib):
     for name, (res, argtypes) in {**_signatures(), **_signatures_device(), **_signatures_zoom(),
                                   **_signatures_records(), **_signatures_put(), **_signatures_reduce(),
                                   **_signatures_vaxis(), **_signatures_hgrid(), **_signatures_remap(),
-                                  **_signatures_hv()}.items():
+                                  **_signatures_hv(), **_signatures_vrecords()}.items():
         fn = getattr(lib, name, None)
         if fn is not None:
             fn.restype, fn.argtypes = res, argtypes
@@ -1894,8 +1923,129 @@ class _GridAxis:
             self._call("dev_fence", s)
 
 
+def host_vrecords_rule(branch, kin, lev0, nlev):
+    """Does an axis whose out table is (branch, kin) - host_vaxis_map(zm, z)'s - read kept model levels only, the kept
+    levels being lev0 .. lev0 + nlev - 1?  None if so, else (caller level, model level): the first caller level that reads
+    a level outside them and the first such level it reads.  mckpp_host_vrecords_rule
+    (include/mckpp_hip_vrecords.h).  No GPU."""
+    branch = np.ascontiguousarray(branch, dtype=np.int32).ravel()
+    kin = np.ascontiguousarray(kin, dtype=np.int32).ravel()
+    j, lev = C.c_int32(-1), C.c_int32(-1)
+    rc = _lib().mckpp_host_vrecords_rule(branch.size if branch.size == kin.size else 0, branch.ctypes.data_as(_ip),
+                                         kin.ctypes.data_as(_ip), int(lev0), int(nlev), C.byref(j), C.byref(lev))
+    if rc < 0:
+        raise ValueError("host_vrecords_rule: branch and kin are one table of at least one caller level, and nlev >= 1")
+    return None if rc == 0 else (int(j.value), int(lev.value))
+
+
+class _AxisRecords:
+    """Completed records of output schedules on a caller axis (include/mckpp_hip_vrecords.h): records_dev and
+    remap_records_dev through the out table of vaxis_define.  Record value first - a mean divided by the period -, then
+    the vertical interpolation, then - on a caller grid - the row sum.  An array is (n_axis, npoints) or (n_axis, n_grid):
+    points fastest, the whole axis."""
+
+    def _axis_record(self, who, p, naxis):
+        """what a plane tuple (sched, rec, field, op, ...) says of its record, its field and its axis, checked:
+        (sched, rec, field, op, axis, n_axis, npoints of the schedule's records)"""
+        sched, rec, op = int(p[0]), int(p[1]), int(p[3])
+        try:
+            f = _win_field(p[2])
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        if f in _OUT_2D:
+            raise ValueError(f"{who}: field {OUT_FIELDS[f]} is two-dimensional: it has no vertical axis to interpolate")
+        if f in _OUT_INTERFACE:
+            raise ValueError(f"{who}: field {OUT_FIELDS[f]} lives on the interface axis 0..nz, not on the levels a "
+                             "caller's axis is interpolated from")
+        try:
+            _win_check_fetch(self._scheds(), sched, f, op)
+        except ValueError as e:
+            raise ValueError(f"{who}: {e}") from None
+        if rec < 0:
+            raise ValueError(f"{who}: record {rec}")
+        zoom = self._scheds()[sched].zoom
+        return sched, rec, f, op, int(naxis), self._vaxis(who, naxis), (zoom[0] if zoom is not None else self._npts)
+
+    def _vaxis_record_table(self, name, planes, land_value, fill_land, array):
+        """the planes of vaxis_records_dev / _host as the table the library takes; array(a, what, count) ->
+        (address, typestr) is the form's own check of a plane's array"""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"{name}: {len(planes)} planes, at most 64 in one call")
+        arr = (_VaxisRecordPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            who = f"{name}: planes[{k}]"
+            if len(p) != 6:
+                raise ValueError(f"{who} is (sched, rec, field, op, axis, out)")
+            sched, rec, f, op, axis, nax, n = self._axis_record(who, p, p[4])
+            out = p[5]
+            shape = tuple(getattr(out, "shape", ()))
+            if hasattr(out, "shape") and shape not in ((nax, n), (nax * n,)):
+                raise ValueError(f"{who}: out has shape {shape}; axis {axis} at the {n} points of schedule {sched}'s records "
+                                 f"is ({nax}, {n})")
+            ptr, typestr = array(out, f"{who} out", nax * n)
+            arr[k] = _VaxisRecordPlaneC(sched, f, op, axis, _DEV_TYPESTR[typestr], int(bool(fill_land)), rec,
+                                        float(land_value), ptr)
+        return len(planes), arr
+
+    def vaxis_records_dev(self, planes, stream=None, land_value=1e20, fill_land=True):
+        """records_dev onto caller axes: a plane is (sched, rec, field, op, axis, out) - op OP_MEAN / OP_MIN / OP_MAX /
+        OP_LAST of the three-dimensional `field` in record `rec` of schedule `sched`, interpolated from the model levels
+        the schedule keeps onto axis `axis`, into out, a tensor of shape (n_axis, npoints) of float64 or float32, npoints
+        the record's point axis.  The record's value comes first (the mean is sum / period), the interpolation second:
+        a record of minima gives the interpolation of the minima.  A schedule with a level zoom serves an axis whose
+        every caller level reads kept levels only; the library refuses any other by name.  land_value, fill_land and
+        the ordering are records_dev's: window_record_release and the next launch may follow at once."""
+        held = []
+
+        def array(a, what, count):
+            held.append(a)
+            return _dev_array(a, what, count, tuple(_DEV_TYPESTR))
+
+        n, arr = self._vaxis_record_table("vaxis_records_dev", planes, land_value, fill_land, array)
+        for a in held:
+            self._hold_dev(a)
+        self._call("vrecords_vaxis_dev", n, arr, _dev_stream(stream))
+
+    def vaxis_records_host(self, planes, land_value=1e20, fill_land=True):
+        """vaxis_records_dev into numpy arrays of float64 or float32; returns when they hold the planes (XIOS's
+        interpolate_axis for a host output path)."""
+        def array(a, what, count):
+            ptr, typestr = _host_plane(a, what, count)
+            self._hold(a)     # (the library pins the arrays it copies into, as window_record_fetch's)
+            return ptr, typestr
+
+        n, arr = self._vaxis_record_table("vaxis_records_host", planes, land_value, fill_land, array)
+        self._call("vrecords_vaxis_host", n, arr)
+
+    def hv_records_dev(self, planes, stream=None, norm="none", land_value=1e20, fill_land=True):
+        """remap_records_dev onto caller axes: a plane is (sched, rec, field, op, grid, axis, out), out a tensor of shape
+        (n_axis, n_grid) of float64 or float32.  Vertical first, at the record's rows, as vaxis_records_dev does; then every
+        caller point's value at a caller level is remap_records_dev's of those - the used entries are the rows of the
+        record, norm, land_value and fill_land are hgrid_fetch_dev's."""
+        planes = list(planes)
+        if len(planes) > 64:
+            raise ValueError(f"hv_records_dev: {len(planes)} planes, at most 64 in one call")
+        nrm = _hgrid_norm("hv_records_dev", norm)
+        arr = (_HvRecordPlaneC * max(1, len(planes)))()
+        for k, p in enumerate(planes):
+            who = f"hv_records_dev: planes[{k}]"
+            if len(p) != 7:
+                raise ValueError(f"{who} is (sched, rec, field, op, grid, axis, out)")
+            sched, rec, f, op, axis, nax, _ = self._axis_record(who, p, p[5])
+            n, out = self._hgrid(who, p[4]), p[6]
+            shape = tuple(getattr(out, "shape", ()))
+            if shape not in ((nax, n), (nax * n,)):
+                raise ValueError(f"{who}: out has shape {shape}; axis {axis} on grid {int(p[4])} is ({nax}, {n})")
+            ptr, typestr = _dev_array(out, f"{who} out", nax * n, tuple(_DEV_TYPESTR))
+            arr[k] = _HvRecordPlaneC(sched, f, op, axis, _DEV_TYPESTR[typestr], int(p[4]), nrm, int(bool(fill_land)), rec,
+                                     float(land_value), ptr)
+            self._hold_dev(out)
+        self._call("vrecords_hv_dev", len(planes), arr, _dev_stream(stream))
+
+
 class _Handle(_WindowSchedules, _RestartSchedule, _StepLog, _AncillarySeries, _FluxRing, _DeviceArrays, _VerticalAxes,
-              _HorizontalGrids, _Remap, _GridAxis):
+              _HorizontalGrids, _Remap, _GridAxis, _AxisRecords):
     """What one device context and several GPUs behind one handle have in common: everything but how they are made.
     Method `name` is the C function self._pre + name applied to the handle self._h."""
     _pre = "mckpp_hip_"

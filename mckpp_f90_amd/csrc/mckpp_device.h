@@ -395,6 +395,19 @@ struct mckpp_hv_put_plane {
 #define MCKPP_HV_PLANES 64   // most planes of one call (the device table's size)
 hipError_t mckpp_launch_hv_put_planes(const mckpp_hv_put_plane *tab, int nplanes, int nzp1, int64_t ncol, double *cs,
                                       hipStream_t stream);
+// One plane of mckpp_hip_vrecords_vaxis_dev / _host and of the first stage of mckpp_hip_vrecords_hv_dev
+// (include/mckpp_hip_vrecords.h; k_vaxis_record_planes): mckpp_rec_plane's rows and geometry with r.nlev the caller
+// axis' n: level j of out(npoints, n) takes vinterp through tab[j], the axis's out table, of the row's elements - of a
+// mean each divided by r.period first.  tab's kin counts model levels; the row's element 0 is model level lev0 of the
+// schedule, so the element read is r.off + kin - lev0 (the host has checked that every one is a kept level).
+struct mckpp_vrec_plane {
+  mckpp_rec_plane r;
+  const mckpp_vaxis_ent *tab;
+  int lev0;
+};
+#define MCKPP_VREC_PLANES 64   // most planes of one call (the device table's size)
+// as mckpp_launch_record_planes
+hipError_t mckpp_launch_vaxis_record_planes(const mckpp_vrec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream);
 // layout kernels: Fortran (npts-fastest) <-> device rows
 hipError_t mckpp_launch_gather_rows(const double *src3d, int64_t npts, int nlev, int lev_off,
                                     const int *ipt, int64_t ncol, double *dst, int ld, int dst_off,

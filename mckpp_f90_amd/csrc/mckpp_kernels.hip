@@ -45,9 +45,9 @@ __global__ void k_exp_batch(int64_t n, const double *x, double *y)
 }
 
 // ---------------------------------------------------------------------------
-// The move between device rows and caller planes, stated once for the eight kernels that make it (k_gather_rows,
+// The move between device rows and caller planes, stated once for the nine kernels that make it (k_gather_rows,
 // k_scatter_rows, k_record_pack, k_fetch_planes, k_record_planes, k_put_planes, k_vaxis_fetch_planes,
-// k_vaxis_put_planes; k_fetch_planes and k_vaxis_put_planes have the routines below written out in their bodies, for
+// k_vaxis_record_planes, k_vaxis_put_planes; k_fetch_planes and k_vaxis_put_planes have the routines below written out in their bodies, for
 // the reasons given there).
 //
 // Rows are [nrow][ld] doubles with a row's levels contiguous; a plane is plane(npoints, nlev) with points fastest, and
@@ -783,6 +783,46 @@ __global__ __launch_bounds__(256) void k_vaxis_fetch_planes(const mckpp_vaxis_fe
   else vaxis_fetch_plane<double>(e, tile, ipt, ncol, npts, cs, land, nland, coltiles);
 }
 
+// Completed records on a caller's axis (mckpp_hip_vrecords_vaxis_dev / _host, the first stage of mckpp_hip_vrecords_hv_dev;
+// include/mckpp_hip_vrecords.h): k_record_planes with the value formed on the row side, as vaxis_fetch_plane forms it.
+// There tx is a caller level: the row's one or two source elements - kin rebased by the schedule's first kept level, each
+// of a mean divided by the period first, k_record_planes' division - go through the axis's out table.  kin rises with the
+// caller level, so a wave's loads stay within the row's segments.  An axis has at least two levels: no one-level path.
+// The geometry is a plane's own, and the fill of the positions that are no row is k_record_planes': the workgroups
+// behind the row tiles.
+template <class T>
+__device__ __forceinline__ void vaxis_record_plane(const mckpp_vrec_plane &e, double (*tile)[65])
+{
+  const mckpp_rec_plane &r = e.r;
+  const int l0 = blockIdx.y * 64;
+  T *__restrict__ dst = static_cast<T *>(r.out);
+  const int64_t rowtiles = (r.nrow + 63) / 64;
+  if ((int64_t)blockIdx.x >= rowtiles) {
+    if (r.fill) fill_positions((int64_t)blockIdx.x - rowtiles, r.nlev, l0, r.norow, r.nnorow, r.npoints, dst, (T)r.land_value);
+    return;
+  }
+  tile_rows_to_points<false>(tile, r.nrow, r.nlev, l0, r.map, r.npoints, dst, [&](int64_t row, int lev, bool in) {
+    if (!in) return 0.0;
+    const mckpp_vaxis_ent a = e.tab[lev];
+    const double *src = r.src + row * r.ld + r.off + (a.kin - e.lev0);
+    double va = src[0];
+    double vb = a.branch == 2 ? src[1] : va;
+    if (r.mean) {
+      va = va / r.period;
+      vb = vb / r.period;
+    }
+    return vaxis_value(a, va, vb);
+  });
+}
+
+__global__ __launch_bounds__(256) void k_vaxis_record_planes(const mckpp_vrec_plane *__restrict__ tab)
+{
+  __shared__ double tile[64][65];
+  const mckpp_vrec_plane e = tab[blockIdx.z];
+  if (e.r.f32) vaxis_record_plane<float>(e, tile);
+  else vaxis_record_plane<double>(e, tile);
+}
+
 // State in from planes on a caller's grid and a caller's axis at once (mckpp_hip_hv_put_dev, include/mckpp_hip_hv.h):
 // horizontal first, at the caller's levels, then vertical.  remap_put_plane's shape - the workgroup's 64 columns are one
 // ELL slice, which its four waves share, and a tile of 64 model levels - with the 16 running sums of hgrid_row_sums
@@ -1084,6 +1124,14 @@ hipError_t mckpp_launch_record_planes(const mckpp_rec_plane *tab, int nplanes, i
   if (nplanes <= 0 || maxlev <= 0 || xtiles <= 0) return hipSuccess;
   dim3 grid((unsigned)xtiles, (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
   hipLaunchKernelGGL(k_record_planes, grid, dim3(256), 0, stream, tab);
+  return hipGetLastError();
+}
+
+hipError_t mckpp_launch_vaxis_record_planes(const mckpp_vrec_plane *tab, int nplanes, int maxlev, int64_t xtiles, hipStream_t stream)
+{
+  if (nplanes <= 0 || maxlev <= 0 || xtiles <= 0) return hipSuccess;
+  dim3 grid((unsigned)xtiles, (unsigned)((maxlev + 63) / 64), (unsigned)nplanes);
+  hipLaunchKernelGGL(k_vaxis_record_planes, grid, dim3(256), 0, stream, tab);
   return hipGetLastError();
 }
 

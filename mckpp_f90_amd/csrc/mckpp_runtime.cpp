@@ -23,6 +23,7 @@
 #include "../../include/mckpp_hip_hgrid.h"
 #include "../../include/mckpp_hip_remap.h"
 #include "../../include/mckpp_hip_hv.h"
+#include "../../include/mckpp_hip_vrecords.h"
 #include "mckpp_device.h"
 #include "mckpp_math.h"
 #include "mckpp_own.h"
@@ -304,10 +305,14 @@ struct mckpp_hip_ctx : mckpp_ctx_streams, mckpp_ctx_resident {
   struct vaxis {
     std::vector<double> z;
     dev_buf<mckpp_vaxis_ent> d_in, d_out;
+    // the out table's branch and kin on the host: which model levels a caller level reads, for the level rule of
+    // include/mckpp_hip_vrecords.h
+    std::vector<int32_t> out_branch, out_kin;
   } vax[MCKPP_VAXES];
   std::vector<double> h_zm;
   plane_table<mckpp_vaxis_put_plane, MCKPP_VAXIS_PLANES> vput_tab;
   plane_table<mckpp_vaxis_fetch_plane, MCKPP_VAXIS_PLANES> vfetch_tab;
+  plane_table<mckpp_vrec_plane, MCKPP_VREC_PLANES> vrec_tab;   // records on a caller axis (include/mckpp_hip_vrecords.h)
   dev_buf<unsigned> d_kelvin;
   // The caller's horizontal grids (include/mckpp_hip_hgrid.h).  A grid is the context's, like the axes above: n points
   // (0: not defined), the npts it was defined for and the copies of its two CSR tables on the host (ptr empty: that
@@ -2990,8 +2995,10 @@ int mckpp_hip_put_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_put_plan
 // ---------------------------------------------------------------------------
 extern "C++" {
 namespace {
-// an axis table built on the host and copied to the device (the context's device is current)
-int vaxis_table(const char *who, int ns, const double *zs, int nt, const double *zt, dev_buf<mckpp_vaxis_ent> &d)
+// an axis table built on the host and copied to the device (the context's device is current); keep_branch, keep_kin
+// (null: not kept): its branches and source levels, for the host
+int vaxis_table(const char *who, int ns, const double *zs, int nt, const double *zt, dev_buf<mckpp_vaxis_ent> &d,
+                std::vector<int32_t> *keep_branch = nullptr, std::vector<int32_t> *keep_kin = nullptr)
 {
   std::vector<int32_t> branch((size_t)nt), kin((size_t)nt);
   std::vector<double> t((size_t)nt), dz((size_t)nt);
@@ -3001,6 +3008,8 @@ int vaxis_table(const char *who, int ns, const double *zs, int nt, const double 
   for (int j = 0; j < nt; ++j) tab[(size_t)j] = mckpp_vaxis_ent{branch[(size_t)j], kin[(size_t)j], t[(size_t)j], dz[(size_t)j]};
   HIPCHK(d.alloc((size_t)nt));
   HIPCHK(hipMemcpy(d, tab.data(), (size_t)nt * sizeof(mckpp_vaxis_ent), hipMemcpyHostToDevice));
+  if (keep_branch) *keep_branch = std::move(branch);
+  if (keep_kin) *keep_kin = std::move(kin);
   return 0;
 }
 
@@ -3023,7 +3032,7 @@ int vaxis_define(mckpp_hip_ctx *h, const char *who, int axis, int32_t n, const d
   if (n > 0) {
     next.z.assign(z, z + n);
     if (vaxis_table(who, n, z, h->nzp1, h->h_zm.data(), next.d_in)) return -1;
-    if (vaxis_table(who, h->nzp1, h->h_zm.data(), n, z, next.d_out)) return -1;
+    if (vaxis_table(who, h->nzp1, h->h_zm.data(), n, z, next.d_out, &next.out_branch, &next.out_kin)) return -1;
   }
   HIPCHK(hipStreamSynchronize(h->stream));   // (a launch in flight may read the tables this replaces)
   h->vax[axis] = std::move(next);
@@ -4162,21 +4171,25 @@ int group_norow(const ctx_group &g, const char *who, int sched)
   return fill_list_set(root, w.d_norow, w.nnorow, w.norow_kind, held, g.kind);
 }
 
-// fill: this context writes the land values the planes ask for (the root does, from the lists group_norow has brought up
-// to date; another shard of a multi handle writes none)
+// The non-row list of plane `e` of schedule `sched`, stated once for the deliveries at a record's points (k_record_planes,
+// k_vaxis_record_planes).  fill: this context writes the land values the planes ask for (the root does, from the lists
+// group_norow has brought up to date; another shard of a multi handle writes none).  The plane's 64-entry tiles, rows and
+// - where it fills - non-row positions together.
+int64_t rec_plane_fill(mckpp_hip_ctx *h, mckpp_rec_plane &e, int sched, bool fill)
+{
+  const auto &w = h->wsched[sched];
+  e.fill = e.fill && fill;
+  if (e.fill && w.listed) { e.norow = w.d_norow; e.nnorow = w.nnorow; }
+  else if (e.fill) { e.norow = h->d_land; e.nnorow = h->nland; }
+  return (e.nrow + 63) / 64 + (e.nnorow + 63) / 64;
+}
+
 int records_dev_queue(mckpp_hip_ctx *h, rec_planes &r, bool fill, hipEvent_t before, void *consumer_stream)
 {
   if (r.tab.empty()) return 0;
   HIPCHK(hipSetDevice(h->device));
   int64_t xtiles = 0;
-  for (size_t k = 0; k < r.tab.size(); ++k) {
-    mckpp_rec_plane &e = r.tab[k];
-    const auto &w = h->wsched[r.sched[k]];
-    e.fill = e.fill && fill;
-    if (e.fill && w.listed) { e.norow = w.d_norow; e.nnorow = w.nnorow; }
-    else if (e.fill) { e.norow = h->d_land; e.nnorow = h->nland; }
-    xtiles = std::max<int64_t>(xtiles, (e.nrow + 63) / 64 + (e.nnorow + 63) / 64);
-  }
+  for (size_t k = 0; k < r.tab.size(); ++k) xtiles = std::max(xtiles, rec_plane_fill(h, r.tab[k], r.sched[k], fill));
   HIPCHK(h->rec_tab.put(r.tab, h->stream));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
   HIPCHK(mckpp_launch_record_planes(h->rec_tab, (int)r.tab.size(), r.maxlev, xtiles, h->stream));
@@ -4219,13 +4232,31 @@ int mckpp_hip_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_dev_r
 // ---------------------------------------------------------------------------
 extern "C++" {
 namespace {
-// The planes of mckpp_hip_remap_records_dev: stage 1 as planes of k_record_planes (`out` set when it is queued), [plane]
-// its schedule
-struct remap_recs {
-  std::vector<mckpp_rec_plane> first;
+// The planes of a delivery of records on caller grids: stage 1 as planes of its kernel (`out` set when it is queued),
+// [plane] its schedule.  mckpp_hip_remap_records_dev's stage 1 is k_record_planes, mckpp_hip_vrecords_hv_dev's
+// (include/mckpp_hip_vrecords.h) k_vaxis_record_planes; what differs between the two is stated by the overloads below.
+template <class Plane>
+struct grid_recs {
+  std::vector<Plane> first;
   std::vector<int> sched;
   hgrid_outs o;
 };
+using remap_recs = grid_recs<mckpp_rec_plane>;
+using hv_recs = grid_recs<mckpp_vrec_plane>;
+
+// a stage-1 plane's rows and geometry; its table onto the device and its launch, on the context's stream
+mckpp_rec_plane &rows_of(mckpp_rec_plane &e) { return e; }
+mckpp_rec_plane &rows_of(mckpp_vrec_plane &e) { return e.r; }
+hipError_t rows_put(mckpp_hip_ctx *h, const std::vector<mckpp_rec_plane> &t) { return h->rec_tab.put(t, h->stream); }
+hipError_t rows_put(mckpp_hip_ctx *h, const std::vector<mckpp_vrec_plane> &t) { return h->vrec_tab.put(t, h->stream); }
+hipError_t rows_launch(mckpp_hip_ctx *h, const std::vector<mckpp_rec_plane> &t, int maxlev, int64_t xtiles)
+{
+  return mckpp_launch_record_planes(h->rec_tab, (int)t.size(), maxlev, xtiles, h->stream);
+}
+hipError_t rows_launch(mckpp_hip_ctx *h, const std::vector<mckpp_vrec_plane> &t, int maxlev, int64_t xtiles)
+{
+  return mckpp_launch_vaxis_record_planes(h->vrec_tab, (int)t.size(), maxlev, xtiles, h->stream);
+}
 
 int remap_records_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_remap_record_plane_c *planes, remap_recs &r,
                         int *dev)
@@ -4248,21 +4279,21 @@ int remap_records_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, cons
   return 0;
 }
 
-// the table stage 2 reads for plane k: a listed schedule's own on the grid, else the grid's
-hgrid_dev &remap_out_table(mckpp_hip_ctx *h, const remap_recs &r, size_t k)
+// the table stage 2 reads for a plane of schedule `sched` on grid `grid`: a listed schedule's own on the grid, else the
+// grid's
+hgrid_dev &remap_out_table(mckpp_hip_ctx *h, int sched, int grid)
 {
-  auto &w = h->wsched[r.sched[k]];
-  return w.listed ? w.hout[r.o.grid[k]] : h->hgd[r.o.grid[k]].out;
+  auto &w = h->wsched[sched];
+  return w.listed ? w.hout[grid] : h->hgd[grid].out;
 }
 
-// the root's out table for plane k of a delivery, for the rows the group holds of the plane's schedule (kind as
+// the root's out table for a plane of a delivery, for the rows the group holds of the plane's schedule (kind as
 // group_hgrid_out's), built where it is not that
-int group_remap_out(const ctx_group &g, const char *who, const remap_recs &r, size_t k)
+int group_remap_out(const ctx_group &g, const char *who, int sched, int grid)
 {
   mckpp_hip_ctx *root = g.root();
-  const int sched = r.sched[k], grid = r.o.grid[k];
   if (!root->wsched[sched].listed) return group_hgrid_out(g, who, grid);
-  hgrid_dev &d = remap_out_table(root, r, k);
+  hgrid_dev &d = remap_out_table(root, sched, grid);
   if (d.kind == g.kind) return 0;
   std::vector<unsigned char> covered((size_t)root->npts, 0);
   for (auto *x : g)
@@ -4271,36 +4302,47 @@ int group_remap_out(const ctx_group &g, const char *who, const remap_recs &r, si
 }
 
 // stage 1 on this context's stream, behind `before`: its rows' values into `stage`
-int remap_records_first(mckpp_hip_ctx *h, remap_recs &r, double *stage, hipEvent_t before)
+template <class Plane>
+int grid_records_first(mckpp_hip_ctx *h, grid_recs<Plane> &r, double *stage, hipEvent_t before)
 {
   HIPCHK(hipSetDevice(h->device));
   int64_t xtiles = 0;
   for (size_t k = 0; k < r.first.size(); ++k) {
-    r.first[k].out = stage + r.o.at[k];
-    xtiles = std::max<int64_t>(xtiles, (r.first[k].nrow + 63) / 64);
+    rows_of(r.first[k]).out = stage + r.o.at[k];
+    xtiles = std::max<int64_t>(xtiles, (rows_of(r.first[k]).nrow + 63) / 64);
   }
-  HIPCHK(h->rec_tab.put(r.first, h->stream));
+  HIPCHK(rows_put(h, r.first));
   HIPCHK(hipStreamWaitEvent(h->stream, before, 0));   // what the consumer had queued on the arrays
-  HIPCHK(mckpp_launch_record_planes(h->rec_tab, (int)r.first.size(), r.o.maxlev, xtiles, h->stream));
+  HIPCHK(rows_launch(h, r.first, r.o.maxlev, xtiles));
   return 0;
 }
 
-// mckpp_hip_remap_records_dev: hgrid_fetch_dev's order - every shard's rows into the root's staging, the root's second
-// stage behind them, through tables whose used entries are the rows of any shard
+// Records onto caller grids, whatever the first stage: hgrid_fetch_dev's order - every shard's rows into the root's
+// staging, the root's second stage behind them, through tables whose used entries are the rows of any shard.
+// check(h, r, dev): the planes of the call checked and resolved for context h.
+template <class Plane, class Check>
+int grid_records_dev(const ctx_group &g, const char *who, void *consumer_stream, Check check)
+{
+  std::vector<grid_recs<Plane>> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (check(g.ctx[d], rs[(size_t)d], &dev)) return -1;
+  if (dev < 0) return 0;   // (no plane)
+  grid_recs<Plane> &r0 = rs[0];
+  for (size_t k = 0; k < r0.first.size(); ++k)
+    if (group_remap_out(g, who, r0.sched[k], r0.o.grid[k])) return -1;
+  for (size_t k = 0; k < r0.first.size(); ++k) r0.o.second[k].t = hgrid_ell(remap_out_table(g.root(), r0.sched[k], r0.o.grid[k]));
+  return two_stage_deliver(g, who, r0.o, dev, consumer_stream, [&](int d, double *stage, hipEvent_t before) {
+    return grid_records_first(g.ctx[d], rs[(size_t)d], stage, before);
+  });
+}
+
+// mckpp_hip_remap_records_dev
 int remap_records_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_remap_record_plane_c *planes,
                       void *consumer_stream)
 {
-  std::vector<remap_recs> rs((size_t)g.n);
-  int dev = -1;
-  for (int d = 0; d < g.n; ++d)
-    if (remap_records_check(g.ctx[d], who, nplanes, planes, rs[(size_t)d], &dev)) return -1;
-  if (dev < 0) return 0;   // (no plane)
-  remap_recs &r0 = rs[0];
-  for (size_t k = 0; k < r0.first.size(); ++k)
-    if (group_remap_out(g, who, r0, k)) return -1;
-  for (size_t k = 0; k < r0.first.size(); ++k) r0.o.second[k].t = hgrid_ell(remap_out_table(g.root(), r0, k));
-  return two_stage_deliver(g, who, r0.o, dev, consumer_stream, [&](int d, double *stage, hipEvent_t before) {
-    return remap_records_first(g.ctx[d], rs[(size_t)d], stage, before);
+  return grid_records_dev<mckpp_rec_plane>(g, who, consumer_stream, [&](mckpp_hip_ctx *h, remap_recs &r, int *dev) {
+    return remap_records_check(h, who, nplanes, planes, r, dev);
   });
 }
 
@@ -4501,6 +4543,197 @@ int hv_put_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp
     if (hv_put_queue(g.ctx[d], tabs[(size_t)d], *g.ev)) return -1;
   return 0;
 }
+
+// ---------------------------------------------------------------------------
+// Completed records on a caller axis (include/mckpp_hip_vrecords.h), the parts above put together once more.  A plane's
+// field and axis are resolved by vaxis_fetch_resolve, its record by win_record_check, and the axis is held against the
+// levels the schedule keeps by mckpp_host_vrecords_rule; the launch is k_vaxis_record_planes, queued in
+// records_dev_queue's order.  The host form sends the same launch into the root's put staging and copies from there.  On
+// a caller grid it is stage 1 of remap_records_dev's two stages, with the axis's n as the plane's levels.
+// ---------------------------------------------------------------------------
+// What planes[k] says of its field, its axis and its record, checked and resolved into the kernel's entry but for where
+// it goes (out, map, npoints, the fill).  The schedule, or null and the refusal.
+template <class P>
+const mckpp_hip_ctx::win_sched *vrec_resolve(mckpp_hip_ctx *h, const char *who, int k, const P &q, mckpp_vrec_plane &e)
+{
+  out_desc d;
+  const mckpp_hip_ctx::vaxis *ax = vaxis_fetch_resolve(h, who, k, q.field, q.axis, d);
+  if (!ax) return nullptr;
+  char at[96];
+  snprintf(at, sizeof at, "%s: planes[%d]", who, k);
+  size_t i = 0;
+  if (win_record_check(h, at, q.sched, q.rec, true, q.field, q.op, &i)) return nullptr;
+  const auto &w = h->wsched[q.sched];
+  const int n = (int)ax->z.size();
+  int32_t j = 0, lev = 0;
+  if (mckpp_host_vrecords_rule(n, ax->out_branch.data(), ax->out_kin.data(), w.lev_off[i], w.nlev[i], &j, &lev) != 0)
+    return fail("%s: planes[%d]: caller level %d of axis %d (z=%.17g) reads model level %d, and schedule %d keeps levels "
+                "%d..%d of field %d: every model level the axis reads must be a kept level", who, k, (int)j, q.axis, ax->z[(size_t)j],
+                (int)lev, q.sched, w.lev_off[i], w.lev_off[i] + w.nlev[i] - 1, q.field), nullptr;
+  e.r.src = win_plane_rows(w, i, q.rec, q.op);
+  e.r.period = (double)w.period;
+  e.r.nrow = w.nrow;
+  e.r.ld = w.ld_out[i]; e.r.off = 0; e.r.nlev = n;
+  e.r.mean = q.op == 0;
+  e.tab = ax->d_out;
+  e.lev0 = w.lev_off[i];
+  return &w;
+}
+
+// the planes of a delivery on caller axes resolved into the kernel's table, but for their non-row lists; [plane] its
+// schedule and - the host form - the bytes of its array
+struct vrec_planes {
+  std::vector<mckpp_vrec_plane> tab;
+  std::vector<int> sched;
+  std::vector<size_t> bytes;
+  int maxlev = 0;
+};
+
+int vrec_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_vaxis_record_plane_c *planes, bool dev_form,
+               vrec_planes &r, int *dev)
+{
+  if (planes_count_check(who, nplanes, planes, MCKPP_VRECORDS_PLANES_MAX) || uploaded_check(h, who)) return -1;
+  HIPCHK(hipSetDevice(h->device));
+  r = vrec_planes{};
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_vaxis_record_plane_c &q = planes[k];
+    mckpp_vrec_plane e{};
+    const auto *w = vrec_resolve(h, who, k, q, e);
+    if (!w) return -1;
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem) return -1;
+    const size_t bytes = (size_t)w->npoints * (size_t)e.r.nlev * elem;
+    char arg[32];
+    snprintf(arg, sizeof arg, "planes[%d].out", k);
+    if (!dev_form) {
+      if (!q.out) return fail("%s: %s is null", who, arg);
+    } else if (dev_ptr_check(h, who, arg, q.out, bytes, k == 0 ? dev : nullptr)) {
+      return -1;
+    }
+    e.r.out = q.out;
+    e.r.map = win_map(h, *w);
+    e.r.land_value = q.land_value;
+    e.r.npoints = w->npoints;
+    e.r.f32 = q.dtype == MCKPP_EXP_F32; e.r.fill = q.fill_land != 0;
+    r.tab.push_back(e);
+    r.sched.push_back(q.sched);
+    r.bytes.push_back(bytes);
+    r.maxlev = std::max(r.maxlev, e.r.nlev);
+  }
+  return 0;
+}
+
+// The table onto this context's device and the launch, on its stream.  fill: this context writes the land values the
+// planes ask for (records_dev_queue's rule: the root does, from the lists group_norow has brought up to date).
+int vrec_launch(mckpp_hip_ctx *h, vrec_planes &r, bool fill, hipEvent_t before)
+{
+  int64_t xtiles = 0;
+  for (size_t k = 0; k < r.tab.size(); ++k) xtiles = std::max(xtiles, rec_plane_fill(h, r.tab[k].r, r.sched[k], fill));
+  HIPCHK(rows_put(h, r.tab));
+  if (before) HIPCHK(hipStreamWaitEvent(h->stream, before, 0));
+  HIPCHK(rows_launch(h, r.tab, r.maxlev, xtiles));
+  HIPCHK(h->ev_delivered.record(h->stream));
+  return 0;
+}
+
+// The host form's delivery: every plane into the root's put staging (each at a multiple of 256 bytes) - a plane that
+// keeps what its array held at the positions without a row goes up first -, every shard's rows behind that, and one copy
+// per plane into the caller's array, pinned once, behind all of them on the root's stream; the call waits for it.
+int vrec_host_deliver(const ctx_group &g, const char *who, std::vector<vrec_planes> &rs, const mckpp_vaxis_record_plane_c *planes)
+{
+  mckpp_hip_ctx *root = g.root();
+  vrec_planes &r0 = rs[0];
+  std::vector<size_t> at(r0.tab.size());
+  size_t total = 0;
+  for (size_t k = 0; k < r0.tab.size(); ++k) {
+    at[k] = total;
+    total += (r0.bytes[k] + 255) / 256 * 256;
+  }
+  HIPCHK(hipSetDevice(root->device));
+  HIPCHK(root->d_put_stage.reserve(total));   // (every call that used the staging ended with a wait)
+  char *stage = root->d_put_stage;
+  for (int d = 1; d < g.n; ++d) {   // every shard's device reaches the root's staging (peer access, once per pair)
+    HIPCHK(hipSetDevice(g.ctx[d]->device));
+    if (dev_ptr_check(g.ctx[d], who, "the staging block of shard 0", stage, total)) return -1;
+  }
+  HIPCHK(hipSetDevice(root->device));
+  for (size_t k = 0; k < r0.tab.size(); ++k) {
+    pin_host(root, planes[k].out, r0.bytes[k]);
+    if (!r0.tab[k].r.fill) HIPCHK(hipMemcpyAsync(stage + at[k], planes[k].out, r0.bytes[k], hipMemcpyHostToDevice, root->stream));
+  }
+  for (int d = 0; d < g.n; ++d) {
+    mckpp_hip_ctx *x = g.ctx[d];
+    vrec_planes &r = rs[(size_t)d];
+    HIPCHK(hipSetDevice(x->device));
+    for (size_t k = 0; k < r.tab.size(); ++k) r.tab[k].r.out = stage + at[k];
+    // a further shard's rows behind the root's launch, which is behind the planes that went up
+    if (vrec_launch(x, r, d == 0, d > 0 ? (hipEvent_t)root->ev_delivered : nullptr)) return -1;
+    if (d > 0) {
+      HIPCHK(hipSetDevice(root->device));
+      HIPCHK(hipStreamWaitEvent(root->stream, x->ev_delivered, 0));
+    }
+  }
+  HIPCHK(hipSetDevice(root->device));
+  for (size_t k = 0; k < r0.tab.size(); ++k)
+    HIPCHK(hipMemcpyAsync(planes[k].out, stage + at[k], r0.bytes[k], hipMemcpyDeviceToHost, root->stream));
+  HIPCHK(hipStreamSynchronize(root->stream));
+  return 0;
+}
+
+// mckpp_hip_vrecords_vaxis_dev / _host: records_dev's rule - a shard writes its own rows of every plane, the root the
+// land values at the positions the group has no row for
+int vrecords_vaxis(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_vaxis_record_plane_c *planes, bool dev_form,
+                   void *consumer_stream)
+{
+  std::vector<vrec_planes> rs((size_t)g.n);
+  int dev = -1;
+  for (int d = 0; d < g.n; ++d)
+    if (vrec_check(g.ctx[d], who, nplanes, planes, dev_form, rs[(size_t)d], dev_form ? &dev : nullptr)) return -1;
+  const vrec_planes &r0 = rs[0];
+  if (r0.tab.empty()) return 0;   // (no plane)
+  for (size_t k = 0; k < r0.tab.size(); ++k)
+    if (r0.tab[k].r.fill && group_norow(g, who, r0.sched[k])) return -1;
+  if (!dev_form) return vrec_host_deliver(g, who, rs, planes);
+  if (caller_event(g, dev, consumer_stream)) return -1;
+  for (int d = 0; d < g.n; ++d) {
+    mckpp_hip_ctx *x = g.ctx[d];
+    HIPCHK(hipSetDevice(x->device));
+    if (vrec_launch(x, rs[(size_t)d], d == 0, *g.ev)) return -1;   // behind what the consumer had queued on the arrays
+    HIPCHK(hipStreamWaitEvent(static_cast<hipStream_t>(consumer_stream), x->ev_delivered, 0));
+  }
+  return 0;
+}
+
+int hv_records_check(mckpp_hip_ctx *h, const char *who, int32_t nplanes, const mckpp_hv_record_plane_c *planes, hv_recs &r, int *dev)
+{
+  if (planes_count_check(who, nplanes, planes, MCKPP_VRECORDS_PLANES_MAX) || uploaded_check(h, who)) return -1;
+  HIPCHK(hipSetDevice(h->device));
+  r = hv_recs{};
+  for (int k = 0; k < nplanes; ++k) {
+    const mckpp_hv_record_plane_c &q = planes[k];
+    mckpp_vrec_plane e{};   // into the staging by point number; what is no row is never written and never read
+    const auto *w = vrec_resolve(h, who, k, q, e);
+    if (!w) return -1;
+    // the plane as hgrid_out_resolve reads one: its levels are the caller axis'
+    const struct { int32_t grid, norm, nlev, dtype, fill_land; double land_value; void *out; } v{
+        q.grid, q.norm, e.r.nlev, q.dtype, q.fill_land, q.land_value, q.out};
+    const size_t elem = plane_elem(who, k, q.dtype);
+    if (!elem || hgrid_out_resolve(h, who, k, v, elem, k == 0 ? dev : nullptr, r.o)) return -1;
+    e.r.map = w->listed ? w->d_rowpt.get() : h->d_ipt.get();
+    e.r.npoints = h->npts;
+    r.first.push_back(e);
+    r.sched.push_back(q.sched);
+  }
+  return 0;
+}
+
+// mckpp_hip_vrecords_hv_dev: remap_records_dev's order with another first stage
+int vrecords_hv_dev(const ctx_group &g, const char *who, int32_t nplanes, const mckpp_hv_record_plane_c *planes, void *consumer_stream)
+{
+  return grid_records_dev<mckpp_vrec_plane>(g, who, consumer_stream, [&](mckpp_hip_ctx *h, hv_recs &r, int *dev) {
+    return hv_records_check(h, who, nplanes, planes, r, dev);
+  });
+}
 }  // namespace
 }  // extern "C++"
 
@@ -4512,6 +4745,21 @@ int mckpp_hip_hv_fetch_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hv_p
 int mckpp_hip_hv_put_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hv_put_plane_c *planes, void *producer_stream)
 {
   return entry(__func__, h, [&, who = __func__]() -> int { return hv_put_dev(lone(h), who, nplanes, planes, producer_stream); });
+}
+
+int mckpp_hip_vrecords_vaxis_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_record_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return vrecords_vaxis(lone(h), who, nplanes, planes, true, consumer_stream); });
+}
+
+int mckpp_hip_vrecords_vaxis_host(mckpp_hip_handle h, int32_t nplanes, const mckpp_vaxis_record_plane_c *planes)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return vrecords_vaxis(lone(h), who, nplanes, planes, false, nullptr); });
+}
+
+int mckpp_hip_vrecords_hv_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_hv_record_plane_c *planes, void *consumer_stream)
+{
+  return entry(__func__, h, [&, who = __func__]() -> int { return vrecords_hv_dev(lone(h), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_remap_records_dev(mckpp_hip_handle h, int32_t nplanes, const mckpp_remap_record_plane_c *planes, void *consumer_stream)
@@ -6022,6 +6270,23 @@ int mckpp_hip_multi_hv_fetch_dev(mckpp_hip_multi_handle m, int32_t nplanes, cons
 int mckpp_hip_multi_hv_put_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_hv_put_plane_c *planes, void *producer_stream)
 {
   return entry(__func__, m, [&, who = __func__]() -> int { return hv_put_dev(shards(m), who, nplanes, planes, producer_stream); });
+}
+
+int mckpp_hip_multi_vrecords_vaxis_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_record_plane_c *planes,
+                                       void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return vrecords_vaxis(shards(m), who, nplanes, planes, true, consumer_stream); });
+}
+
+int mckpp_hip_multi_vrecords_vaxis_host(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_vaxis_record_plane_c *planes)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return vrecords_vaxis(shards(m), who, nplanes, planes, false, nullptr); });
+}
+
+int mckpp_hip_multi_vrecords_hv_dev(mckpp_hip_multi_handle m, int32_t nplanes, const mckpp_hv_record_plane_c *planes,
+                                    void *consumer_stream)
+{
+  return entry(__func__, m, [&, who = __func__]() -> int { return vrecords_hv_dev(shards(m), who, nplanes, planes, consumer_stream); });
 }
 
 int mckpp_hip_multi_dev_fence(mckpp_hip_multi_handle m, void *stream)

@@ -8,6 +8,7 @@
 #include <cmath>
 
 #include "../../include/mckpp_hip_vaxis.h"
+#include "../../include/mckpp_hip_vrecords.h"
 
 namespace {
 bool strictly_decreasing(int32_t n, const double *z)
@@ -36,6 +37,26 @@ extern "C" int mckpp_host_vaxis_map(int32_t ns, const double *zs, int32_t nt, co
       kin[j] = k;
       t[j] = z - zs[k];
       dz[j] = zs[k] - zs[k + 1];
+    }
+  }
+  return 0;
+}
+
+// The level rule of include/mckpp_hip_vrecords.h: which model levels an out table reads, against the levels a schedule
+// keeps.  A clamp reads kin, a bracket kin and kin + 1; the first caller level that reads outside lev0 .. lev0 + nlev - 1
+// is reported with the first such level it reads.
+extern "C" int mckpp_host_vrecords_rule(int32_t nt, const int32_t *branch, const int32_t *kin, int32_t lev0, int32_t nlev,
+                                        int32_t *caller_level, int32_t *model_level)
+{
+  if (!branch || !kin || nt < 1 || nlev < 1) return -1;
+  for (int32_t j = 0; j < nt; ++j) {
+    const int32_t reads = branch[j] == MCKPP_VAXIS_BRACKET ? 2 : 1;
+    for (int32_t m = 0; m < reads; ++m) {
+      const int64_t lev = (int64_t)kin[j] + m;
+      if (lev >= lev0 && lev < (int64_t)lev0 + nlev) continue;
+      if (caller_level) *caller_level = j;
+      if (model_level) *model_level = (int32_t)lev;
+      return 1;
     }
   }
   return 0;

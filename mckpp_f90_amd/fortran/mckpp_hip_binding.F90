@@ -154,6 +154,24 @@ module mckpp_hip_binding
     real(c_double) :: skip_value
     type(c_ptr) :: in
   end type mckpp_hv_put_plane_c
+  !> completed records on a caller axis (include/mckpp_hip_vrecords.h).  One plane of mckpp_hip_vrecords_vaxis_dev /
+  !! _host: operation `op` of `field` in record `rec` of schedule `sched` - the record's value first, a mean divided by
+  !! the period - interpolated onto axis `axis` at the record's points, into out (npoints, n_axis)
+  integer(c_int32_t), parameter :: MCKPP_VRECORDS_PLANES_MAX = 64
+  type, bind(C) :: mckpp_vaxis_record_plane_c
+    integer(c_int32_t) :: sched, field, op, axis, dtype, fill_land
+    integer(c_int64_t) :: rec
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_vaxis_record_plane_c
+  !> one plane of mckpp_hip_vrecords_hv_dev: that plane remapped onto caller grid `grid`, into out (n_grid, n_axis), with
+  !! norm and fill_land as in mckpp_hgrid_plane_c; the used entries are those whose point is a row of the record
+  type, bind(C) :: mckpp_hv_record_plane_c
+    integer(c_int32_t) :: sched, field, op, axis, dtype, grid, norm, fill_land
+    integer(c_int64_t) :: rec
+    real(c_double) :: land_value
+    type(c_ptr) :: out
+  end type mckpp_hv_record_plane_c
 
   !> the zoom of an output schedule (include/mckpp_hip_zoom.h): npoints distinct 0-based point numbers at `points`
   !! (c_null_ptr: every point) and levels lev0 .. lev0+nlev-1 (0-based; 0, 0: the whole axis) of each 3-D field's axis
@@ -1234,6 +1252,55 @@ module mckpp_hip_binding
       type(c_ptr), value :: m, producer_stream
       integer(c_int32_t), value :: nplanes
       type(mckpp_hv_put_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    ! completed records on a caller axis (include/mckpp_hip_vrecords.h): the record's value, then the vertical
+    ! interpolation, then - on a caller grid - the row sum, with the ordering of mckpp_hip_records_dev
+    function mckpp_hip_vrecords_vaxis_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_vrecords_vaxis_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_record_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vrecords_vaxis_host(handle, nplanes, planes) bind(C, name="mckpp_hip_vrecords_vaxis_host") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_record_plane_c
+      type(c_ptr), value :: handle
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_vrecords_hv_dev(handle, nplanes, planes, consumer_stream) bind(C, name="mckpp_hip_vrecords_hv_dev") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hv_record_plane_c
+      type(c_ptr), value :: handle, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hv_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vrecords_vaxis_dev(m, nplanes, planes, consumer_stream) &
+        bind(C, name="mckpp_hip_multi_vrecords_vaxis_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_record_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vrecords_vaxis_host(m, nplanes, planes) bind(C, name="mckpp_hip_multi_vrecords_vaxis_host") &
+        result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_vaxis_record_plane_c
+      type(c_ptr), value :: m
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_vaxis_record_plane_c), intent(in) :: planes(*)
+      integer(c_int) :: rc
+    end function
+    function mckpp_hip_multi_vrecords_hv_dev(m, nplanes, planes, consumer_stream) &
+        bind(C, name="mckpp_hip_multi_vrecords_hv_dev") result(rc)
+      import :: c_int, c_int32_t, c_ptr, mckpp_hv_record_plane_c
+      type(c_ptr), value :: m, consumer_stream
+      integer(c_int32_t), value :: nplanes
+      type(mckpp_hv_record_plane_c), intent(in) :: planes(*)
       integer(c_int) :: rc
     end function
   end interface
